@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- suffixes sorted per second (SA + LCP) on the MI355X construction path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload human|elegans|ecoli] [--bases B]
+    python bench.py --gpus N --steps K --warmup W [--workload human|elegans|ecoli] [--bases B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, the device
+phases of the timed builds).  `--full` adds everything beside that headline, each outside the timed region: the check
+of the last step's arrays against the text, the batched device search, the CPU baseline, the end-to-end `sufr create`,
+the host-buffer ABI and the store-pattern floor of the partition kernel.  `--dump-outputs DIR` writes a fixed, seeded
+sample of the last timed step's SA and LCP (float64, exact for u32 values) as DIR/sa.npy and DIR/lcp.npy, so that two
+builds of the project can be compared output for output.
 
 One *step* = one full pass of the hot path over one genome-sized batch that is already resident in
 HBM: text normalisation + byte histogram, radix partition on packed k-char prefix keys, the remaining
@@ -391,6 +398,33 @@ def launch_ranks(args) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_SAMPLES = 3_000_000       # ranks per dumped array: 2 x 24 MB of float64 at most
+
+
+def dump_outputs(out_dir: str, parts, suffix: str = ""):
+    """--dump-outputs: the SA and LCP of the last timed step as float64 (exact for u32 values).  `parts` are the (sa, lcp)
+    pairs of the step in rank order (two shards under --force-dist), read as one array.  Arrays of up to DUMP_SAMPLES
+    entries are written whole; longer ones at DUMP_SAMPLES ranks drawn with a fixed seed (sorted, the same for the same
+    suffix count), so that two builds of the project can be compared output for output."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    sizes = [int(p[0].numel()) for p in parts]
+    s = sum(sizes)
+    if s <= DUMP_SAMPLES:
+        ranks = np.arange(s, dtype=np.int64)
+    else:
+        ranks = np.sort(np.random.default_rng(0).integers(0, s, size=DUMP_SAMPLES, dtype=np.int64))
+    got = {"sa": [], "lcp": []}
+    off = 0
+    for (sa, lcp), m in zip(parts, sizes):
+        sel = torch.from_numpy(ranks[(ranks >= off) & (ranks < off + m)] - off).to(sa.device)
+        for name, arr in (("sa", sa), ("lcp", lcp)):
+            got[name].append((arr[sel].to(torch.int64) & 0xFFFFFFFF).to(torch.float64).cpu().numpy())
+        off += m
+    for name, chunks in got.items():
+        np.save(d / f"{name}{suffix}.npy", np.concatenate(chunks))
+
+
 def file_sha256(path) -> str:
     import hashlib
     h = hashlib.sha256()
@@ -431,7 +465,14 @@ def main():
     ap.add_argument("--e2e-hash", action="store_true", help="add the sha256 of the .sufr file that e2e_create wrote to its record")
     ap.add_argument("--full-cpu-baseline", choices=("auto", "on", "off"), default=os.environ.get("SUFR_BENCH_FULL_CPU", "auto"),
                     help="time the CPU port on the WHOLE workload (auto: when the host has >= 200 GB and >= 32 cores)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: verify the last step's arrays, device search, CPU baseline, end-to-end "
+                         "`sufr create`, host-buffer ABI and store floor (the --no-* switches above drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's SA and LCP as DIR/sa.npy, DIR/lcp.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torch.distributed.run: start the N ranks as a CHILD job (decided before anything touches the GPU; the
@@ -623,6 +664,9 @@ def main():
     if num_shards > 1:
         totals["s_total"] = int(totals["bounds"][:, 2].sum().item())      # one read-back, outside the timed region
     s_total = totals["s_total"]
+    if args.dump_outputs:
+        # outside the timed region: what the last timed step handed back (every rank writes its own shard when N > 1)
+        dump_outputs(args.dump_outputs, totals["outs"] if vshards > 1 else [(sa, lcp)], f"_rank{rank}" if world > 1 else "")
     verified = None
     search = None
     forced = None
@@ -641,7 +685,7 @@ def main():
                           "time of BOTH shards on one GPU, not an N = 2 figure"}
         assert forced["equal_to_single_build"], "forced-dist: stitched shards differ from the single build"
         del cat_sa, cat_lcp, one_sa, one_lcp
-    if num_shards == 1 and not args.no_verify:
+    if num_shards == 1 and args.full and not args.no_verify:
         # outside the timed region: the arrays of the last timed step against the text (sufr_amd/verify.py)
         sys.path.insert(0, str(ROOT / "tests"))
         import gpu_verify as verify          # the GPU-side property checker: test infrastructure, like oracle/
@@ -666,7 +710,7 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     e2e_multi = None
-    if world > 1 and not args.no_e2e:
+    if world > 1 and args.full and not args.no_e2e:
         builder.close()              # every rank's bench context makes room for its create context
         e2e_multi = e2e_create_sharded(text, starts, flags, partitions, rank, world, local_rank, dev, args.backend,
                                        want_hash=args.e2e_hash)
@@ -725,14 +769,14 @@ def main():
             if args.share_device:
                 out["per_rank"]["share_device"] = ("all ranks ran on cuda:0 (smoke test of the N > 1 leg on a one-GPU box): "
                                                    "value is NOT an N-GPU figure")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sample_bases = min(bases, 400_000_000)
             full = None
             big_host = host_memory_gb() >= 200 and (os.cpu_count() or 1) >= 32
             if args.full_cpu_baseline == "on" or (args.full_cpu_baseline == "auto" and big_host and n > sample_bases + 1):
                 full = lambda: text.cpu().numpy()       # noqa: E731 -- the oracle needs ~24 bytes per base of host memory
             out["cpu_baseline"] = cpu_baseline(text[:sample_bases].cpu().numpy(), flags, partitions, full_text=full)
-        if world == 1 and not args.no_e2e:
+        if world == 1 and args.full and not args.no_e2e:
             builder.close()          # the CLI is its own process with its own context: free this one's HBM first
             text_cpu = text.cpu().numpy()
             if st.get("partition_variant"):

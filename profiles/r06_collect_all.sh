@@ -16,8 +16,8 @@ timeout 600 bash profiles/kt_class.sh human_dna > $O/kernel_table_human_dna.txt 
 timeout 600 bash profiles/kt_class.sh human_iupac > $O/kernel_table_human_iupac.txt 2>&1
 timeout 300 python3 profiles/host_abi_probe.py 3100000000 3 > $O/host_abi_final.txt 2>&1
 # the N > 1 leg on the one GPU: eight gloo ranks sharing the device (C5 at its real shape), and RCCL at world size 1 with two shards per step
-timeout 600 python3 bench.py --gpus 8 --backend gloo --share-device --e2e-hash > $O/bench_n8_share_human.json 2> $O/bench_n8_share_human.err
+timeout 600 python3 bench.py --full --gpus 8 --backend gloo --share-device --e2e-hash > $O/bench_n8_share_human.json 2> $O/bench_n8_share_human.err
 SUFR_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/bench_forced_dist_human.json 2> $O/bench_forced_dist_human.err
 # the driver's line (median of three placements, verified, cpu_baseline on the WHOLE workload when the host allows, host_abi, e2e_create)
-timeout 900 python3 bench.py --e2e-hash > $O/bench_default_human.json 2> $O/bench_default_human.err
+timeout 900 python3 bench.py --full --e2e-hash > $O/bench_default_human.json 2> $O/bench_default_human.err
 ls -la $O

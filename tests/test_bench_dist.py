@@ -58,7 +58,7 @@ def test_bench_eight_ranks_end_to_end():
     """BASELINE config C5 at its real shape, rehearsed on the one GPU: `python bench.py --gpus 8 --backend gloo
     --share-device` -- eight ranks, eight first-digit shards, the eight-writer `sufr create` into ONE file -- at C. elegans size.
     Eight per-rank records whose shards add up to the N = 1 count; the file is sha256-equal to the single-GPU file."""
-    common = ["--workload", "elegans", "--steps", "2", "--warmup", "1", "--placement-trials", "1", "--e2e-hash"]
+    common = ["--workload", "elegans", "--steps", "2", "--warmup", "1", "--placement-trials", "1", "--e2e-hash", "--full"]
     eight = _line(_run(["--gpus", "8", "--backend", "gloo", "--share-device"] + common, timeout=1500))
     one = _line(_run(["--gpus", "1", "--no-cpu-baseline", "--no-search"] + common))
     assert eight["n_gpus"] == 8 and eight["scaling"] == "strong"
@@ -77,7 +77,7 @@ def test_bench_two_ranks_end_to_end(workload):
     """`python bench.py --gpus 2 --backend gloo --share-device`: bench.py spawns its two ranks; the JSON line says n_gpus 2,
     the shards add up to the N = 1 suffix count, and the sharded e2e_create file is byte-identical (sha256) to the file the
     single-GPU `sufr create` of the N = 1 run wrote."""
-    common = ["--workload", workload, "--steps", "2", "--warmup", "1", "--placement-trials", "1", "--e2e-hash"]
+    common = ["--workload", workload, "--steps", "2", "--warmup", "1", "--placement-trials", "1", "--e2e-hash", "--full"]
     two = _line(_run(["--gpus", "2", "--backend", "gloo", "--share-device"] + common))
     one = _line(_run(["--gpus", "1", "--no-cpu-baseline", "--no-search"] + common))
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1

@@ -1095,7 +1095,7 @@ def test_bench_reads_a_real_fasta_through_the_package_reader(tmp_path):
     import sys
     from pathlib import Path
     r = subprocess.run([sys.executable, str(Path(__file__).resolve().parent.parent / "bench.py"), "--workload", "human", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-e2e", "--no-search", "--placement-trials", "1"],
+                        "--full", "--no-cpu-baseline", "--no-e2e", "--no-search", "--placement-trials", "1"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-400:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
