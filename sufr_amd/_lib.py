@@ -94,6 +94,10 @@ QUERY_EXPORTS = [
     "sufr_hip_index_load", "sufr_hip_index_wrap", "sufr_hip_index_free", "sufr_hip_index_width", "sufr_hip_search_batch",
     "sufr_hip_search_batch_device", "sufr_hip_locate_batch_device",
 ]
+# every symbol include/sufr_match.h declares
+MATCH_EXPORTS = [
+    "sufr_file_matching_stats", "sufr_file_smems", "sufr_hip_matching_stats_device", "sufr_hip_smems_device", "sufr_hip_smems",
+]
 
 
 class FileMeta(C.Structure):
@@ -203,6 +207,15 @@ def lib() -> C.CDLL:
     L.sufr_hip_search_batch_device.restype = C.c_int
     L.sufr_hip_locate_batch_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]
     L.sufr_hip_locate_batch_device.restype = C.c_int
+    # include/sufr_match.h
+    L.sufr_file_matching_stats.argtypes = [vp, vp, vp, u64, vp, C.c_int]; L.sufr_file_matching_stats.restype = C.c_int
+    L.sufr_file_smems.argtypes = [vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64), C.c_int]
+    L.sufr_file_smems.restype = C.c_int
+    L.sufr_hip_matching_stats_device.argtypes = [vp, vp, vp, vp, u64, vp]; L.sufr_hip_matching_stats_device.restype = C.c_int
+    L.sufr_hip_smems_device.argtypes = [vp, vp, vp, vp, u64, u32, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_smems_device.restype = C.c_int
+    L.sufr_hip_smems.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_smems.restype = C.c_int
     _lib = L
     return L
 

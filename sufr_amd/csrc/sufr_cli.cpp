@@ -19,6 +19,7 @@
 
 #include "../../include/sufr_hip.h"
 #include "../../include/sufr_query.h"
+#include "../../include/sufr_match.h"
 
 #include <algorithm>
 #include <fstream>
@@ -53,7 +54,11 @@ int usage(FILE* f)
             "  extract|ex   <SUFR> <QUERY>...       Extract sequences [-p PREFIX_LEN] [-s SUFFIX_LEN] [-m LEN] [-o OUT] [-l] [-v]\n"
             "  list|ls      <FILE> [RANK]...        List the suffix array [-r] [-s] [-p] [--len LEN] [-n NUM] [-o OUT] [-v]\n"
             "  summarize|su <SUFR>                  Summarize sufr file\n"
-            "  count / locate / extract take --device <ID>: the queries are searched as one batch on that GPU\n\n"
+            "  match|ma     <SUFR> [QUERY]...       Super-maximal exact matches of the queries: one line per SMEM,\n"
+            "                                       name  offset  length  count  positions\n"
+            "                                       [-k|--min-len N (20)] [-n|--max-hits N (0: all)] [-a|--abs]\n"
+            "                                       [-q|--reads FASTA/FASTQ] [-o OUT]\n"
+            "  count / locate / extract / match take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
             "  -l, --log <LOG>           Log level [possible values: info, debug]\n"
@@ -96,6 +101,8 @@ struct QueryArgs {
     bool has_len = false, has_number = false; uint64_t len = 0, number = 0;
     int device = -1;                            // --device N: the whole batch of queries is searched on that GPU
     int threads = 0;                            // -t/--threads (global option, sufr/src/lib.rs:29-46): host search workers
+    uint64_t min_len = 20, max_hits = 0;        // match: -k / -n
+    std::string reads;                          // match: -q FASTA / FASTQ of named queries
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -392,6 +399,78 @@ int cmd_summarize(const QueryArgs& a)
 }
 
 // arguments of the query sub-commands (clap definitions of lib.rs:129-271)
+// sufr match: the SMEMs of every query, one line each: name, offset, length, count, positions.
+// Positions: SA[rank_lo .. rank_lo + max_hits) (all with 0), printed as seq:pos ordered by sequence name then position
+// like locate's, or absolute in rank order with --abs.
+int cmd_match(const QueryArgs& a)
+{
+    sufr_file* f = open_or_die(a.file);
+    OutFile out;
+    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    if (a.min_len == 0 || a.min_len > 0xFFFFFFFFull) { fprintf(stderr, "Error: --min-len must be between 1 and 2^32 - 1\n"); return 1; }
+    std::vector<std::string> names = expand_queries(a.positional);
+    std::vector<std::string> seqs = names;
+    if (!a.reads.empty()) {
+        sufr_sequence_data sd{};
+        char err[512] = {0};
+        if (sufr_read_sequence_file(a.reads.c_str(), '%', &sd, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
+        for (uint64_t i = 0; i < sd.num_sequences; i++) {       // drop the delimiter after every sequence and the final sentinel
+            const uint64_t b = sd.start_positions[i];
+            const uint64_t e = i + 1 < sd.num_sequences ? sd.start_positions[i + 1] - 1 : (sd.seq_len ? sd.seq_len - 1 : 0);
+            names.push_back(sd.sequence_names[i]);
+            seqs.emplace_back((const char*)sd.seq + b, e > b ? e - b : 0);
+        }
+        sufr_sequence_data_free(&sd);
+    }
+    std::string bytes;
+    std::vector<uint64_t> off(seqs.size() + 1, 0);
+    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
+    sufr_hip_ctx* ctx = nullptr;
+    sufr_hip_index* ix = nullptr;
+    if (a.device >= 0) {
+        ctx = sufr_hip_create(a.device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
+        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
+    }
+    // records: room for one SMEM per 8 query bytes first, the exact count when that is short
+    uint64_t cap = bytes.size() / 8 + 16, total = 0;
+    std::vector<uint64_t> qi, lo, hi;
+    std::vector<uint32_t> qo, len;
+    for (;;) {
+        qi.resize(cap); lo.resize(cap); hi.resize(cap); qo.resize(cap); len.resize(cap);
+        const int rc = ix ? sufr_hip_smems(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, cap,
+                                           qi.data(), qo.data(), len.data(), lo.data(), hi.data(), &total)
+                          : sufr_file_smems(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, cap,
+                                            qi.data(), qo.data(), len.data(), lo.data(), hi.data(), &total, a.threads);
+        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
+        if (rc == SUFR_HIP_E_UNSUPPORTED) { fprintf(stderr, "Error: %s: match does not support files built with a seed mask\n", a.file.c_str()); return 1; }
+        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "match failed"); return 1; }
+        break;
+    }
+    if (ix) sufr_hip_index_free(ix);
+    if (ctx) sufr_hip_destroy(ctx);
+    for (uint64_t t = 0; t < total; t++) {
+        const uint64_t end = a.max_hits && hi[t] - lo[t] > a.max_hits ? lo[t] + a.max_hits : hi[t];
+        std::string pos;
+        if (a.abs) {
+            for (uint64_t r = lo[t]; r < end; r++) pos += (r > lo[t] ? "," : "") + std::to_string(sufr_file_suffix(f, r));
+        } else {
+            struct Pos { std::string name; uint64_t at; };
+            std::vector<Pos> ps;
+            for (uint64_t r = lo[t]; r < end; r++) {
+                const uint64_t sfx = sufr_file_suffix(f, r);
+                const uint64_t i = sufr_file_sequence_of(f, sfx);
+                ps.push_back({sufr_file_sequence_name(f, i), sfx - sufr_file_sequence_start(f, i)});
+            }
+            std::stable_sort(ps.begin(), ps.end(), [](const Pos& x, const Pos& y) { return x.name != y.name ? x.name < y.name : x.at < y.at; });
+            for (size_t k = 0; k < ps.size(); k++) pos += (k ? "," : "") + ps[k].name + ":" + std::to_string(ps[k].at);
+        }
+        fprintf(out.f, "%s\t%u\t%u\t%llu\t%s\n", names[qi[t]].c_str(), qo[t], len[t], (unsigned long long)(hi[t] - lo[t]), pos.c_str());
+    }
+    sufr_file_close(f);
+    return 0;
+}
+
 int run_query(const std::string& cmd, int argc, char** argv, int first, int threads)
 {
     QueryArgs a;
@@ -402,15 +481,19 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         return argv[++i];
     };
     const bool is_list = cmd == "list", is_extract = cmd == "extract", is_locate = cmd == "locate", is_sum = cmd == "summarize";
+    const bool is_match = cmd == "match";
     for (int i = first; i < argc; i++) {
         const std::string s = argv[i];
         if (s == "-h" || s == "--help") { usage(stdout); return 0; }
-        else if (!is_list && !is_sum && (s == "-m" || s == "--max-query-len")) { a.has_mql = true; a.mql = strtoull(need(i, "-m"), nullptr, 10); }
+        else if (!is_list && !is_sum && !is_match && (s == "-m" || s == "--max-query-len")) { a.has_mql = true; a.mql = strtoull(need(i, "-m"), nullptr, 10); }
         else if (!is_sum && (s == "-o" || s == "--output")) a.output = need(i, "-o");
         else if (!is_list && !is_sum && (s == "-l" || s == "--low-memory")) {}            // access mode only: the file is mapped
         else if (!is_sum && (s == "-v" || s == "--very-low-memory")) {}
         else if (!is_list && !is_sum && s == "--device") a.device = atoi(need(i, "--device"));
-        else if (is_locate && (s == "-a" || s == "--abs")) a.abs = true;
+        else if ((is_locate || is_match) && (s == "-a" || s == "--abs")) a.abs = true;
+        else if (is_match && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
+        else if (is_match && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
+        else if (is_match && (s == "-q" || s == "--reads")) a.reads = need(i, "-q");
         else if (is_extract && (s == "-p" || s == "--prefix-len")) { a.has_prefix = true; a.prefix_len = strtoull(need(i, "-p"), nullptr, 10); }
         else if (is_extract && (s == "-s" || s == "--suffix-len")) { a.has_suffix = true; a.suffix_len = strtoull(need(i, "-s"), nullptr, 10); }
         else if (is_list && (s == "-r" || s == "--show-rank")) a.show_rank = true;
@@ -429,12 +512,13 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     if (pos.empty()) { fprintf(stderr, "error: the following required arguments were not provided:\n  <%s>\n", is_list ? "FILE" : "SUFR"); return 2; }
     a.file = pos[0];
     a.positional.assign(pos.begin() + 1, pos.end());
-    if (!is_list && !is_sum && a.positional.empty()) {
+    if (!is_list && !is_sum && a.positional.empty() && !(is_match && !a.reads.empty())) {
         fprintf(stderr, "error: the following required arguments were not provided:\n  <QUERY>...\n");
         return 2;
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
+    if (is_match) return cmd_match(a);
     if (is_extract) return cmd_extract(a);
     if (is_list) return cmd_list(a);
     return cmd_summarize(a);
@@ -490,6 +574,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "create" || s == "cr")) have_cmd = true;
         else if (!have_cmd && (s == "count" || s == "co")) return run_query("count", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "locate" || s == "lo")) return run_query("locate", argc, argv, i + 1, threads);
+        else if (!have_cmd && (s == "match" || s == "ma")) return run_query("match", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "list" || s == "ls")) return run_query("list", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "summarize" || s == "su")) return run_query("summarize", argc, argv, i + 1, threads);

@@ -14,6 +14,7 @@
 
 #include "../../include/sufr_hip.h"
 #include "../../include/sufr_query.h"
+#include "../../include/sufr_match.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -86,5 +87,13 @@ int sufr_hip_search_batch_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const
                                  void*, void*) { return no_device(ctx); }
 int sufr_hip_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const void*, uint64_t, uint64_t, void*,
                                  void*, uint64_t, uint64_t*) { return no_device(ctx); }
+
+
+// ---- include/sufr_match.h: the device side (the host side is sufr_query.cpp) ----------------------------------------
+int sufr_hip_matching_stats_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const void*, uint64_t, void*) { return no_device(ctx); }
+int sufr_hip_smems_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const void*, uint64_t, uint32_t, void*, uint64_t, void*,
+                          void*, void*, void*, void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_smems(sufr_hip_ctx* ctx, const sufr_hip_index*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint64_t*,
+                   uint32_t*, uint32_t*, uint64_t*, uint64_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 
 #include "../../include/sufr_hip.h"
 #include "../../include/sufr_query.h"
+#include "../../include/sufr_match.h"
 
 struct sufr_file {
     std::string path;
@@ -281,6 +282,136 @@ int sufr_file_search_batch(const sufr_file* f, const uint8_t* queries, const uin
     std::vector<std::thread> th;
     for (unsigned t = 0; t < T; t++) th.emplace_back(worker);
     for (auto& t : th) t.join();
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- matching statistics and SMEMs (include/sufr_match.h) -------------------------------------
+namespace {
+
+// ms of one query offset: the lower bound of q[0..qlen) under compare(), then the longer of the prefixes it shares with
+// the suffixes at the insertion point and just below it (the sorted order puts the longest shared prefix next to it).
+// compare() caps at the build's max_query_len, so a capped file gives min(lcp, L).
+uint32_t host_ms(const sufr_file& f, const uint8_t* q, size_t qlen)
+{
+    const uint64_t n = f.meta.len_suffixes;
+    if (n == 0 || qlen == 0) return 0;
+    uint64_t lo = 0, hi = n, l = 0, r = 0;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const Comparison c = compare(f, q, qlen, false, 0, sufr_file_suffix(&f, mid), l < r ? l : r);
+        if (c.cmp > 0) { lo = mid + 1; l = c.lcp; }
+        else { hi = mid; r = c.lcp; }
+    }
+    uint64_t best = 0;
+    if (lo > 0) best = compare(f, q, qlen, false, 0, sufr_file_suffix(&f, lo - 1), 0).lcp;
+    if (lo < n) { const uint64_t v = compare(f, q, qlen, false, 0, sufr_file_suffix(&f, lo), 0).lcp; if (v > best) best = v; }
+    return (uint32_t)best;
+}
+
+// runs body(b, e) over [0, total) in chunks of `chunk`, `threads` workers (0: one per core)
+template <typename F>
+void parallel_chunks(uint64_t total, uint64_t chunk, int threads, F body)
+{
+    unsigned T = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
+    if (T == 0) T = 1;
+    if (T > total / chunk + 1) T = (unsigned)(total / chunk + 1);
+    std::atomic<uint64_t> next{0};
+    auto worker = [&]() {
+        for (;;) {
+            const uint64_t b = next.fetch_add(chunk);
+            if (b >= total) return;
+            body(b, b + chunk < total ? b + chunk : total);
+        }
+    };
+    if (T == 1) { worker(); return; }
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < T; t++) th.emplace_back(worker);
+    for (auto& t : th) t.join();
+}
+
+// the query that holds byte g of the batch: the last i < nq with offsets[i] <= g
+uint64_t query_of(const uint64_t* offsets, uint64_t nq, uint64_t g)
+{
+    uint64_t a = 0, b = nq;
+    while (b - a > 1) { const uint64_t m = a + (b - a) / 2; if (offsets[m] <= g) a = m; else b = m; }
+    return a;
+}
+
+int match_args(const sufr_file* f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq)
+{
+    if (!f || (nq && !offsets) || (nq && offsets[nq] > offsets[0] && !queries)) return SUFR_HIP_E_INVALID;
+    for (uint64_t i = 0; i < nq; i++) if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFFFull) return SUFR_HIP_E_INVALID;
+    if (f->meta.seed_mask_len) return SUFR_HIP_E_UNSUPPORTED;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_matching_stats(const sufr_file* f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t* ms,
+                             int threads)
+{
+    if (const int rc = match_args(f, queries, offsets, nq)) return rc;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    if (!ms) return SUFR_HIP_E_INVALID;
+    const uint64_t g0 = offsets[0];
+    parallel_chunks(offsets[nq] - g0, 4096, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t a = query_of(offsets, nq, g0 + b);
+        for (uint64_t g = g0 + b; g < g0 + e; g++) {
+            while (offsets[a + 1] <= g) a++;
+            ms[g] = host_ms(*f, queries + g, (size_t)(offsets[a + 1] - g));
+        }
+    });
+    return 0;
+}
+
+int sufr_file_smems(const sufr_file* f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t min_len,
+                    uint64_t cap, uint64_t* query, uint32_t* qoff, uint32_t* len, uint64_t* rank_lo, uint64_t* rank_hi,
+                    uint64_t* total_out, int threads)
+{
+    if (total_out) *total_out = 0;
+    if (const int rc = match_args(f, queries, offsets, nq)) return rc;
+    if (min_len == 0) return SUFR_HIP_E_INVALID;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    const uint64_t g0 = offsets[0], nbytes = offsets[nq] - g0;
+    std::vector<uint32_t> ms(nbytes);
+    parallel_chunks(nbytes, 4096, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t a = query_of(offsets, nq, g0 + b);
+        for (uint64_t g = g0 + b; g < g0 + e; g++) {
+            while (offsets[a + 1] <= g) a++;
+            ms[g - g0] = host_ms(*f, queries + g, (size_t)(offsets[a + 1] - g));
+        }
+    });
+    // the SMEM rule in (query, offset) order
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < nq; i++)
+        for (uint64_t g = offsets[i]; g < offsets[i + 1]; g++) {
+            const uint32_t v = ms[g - g0];
+            if (v >= min_len && (g == offsets[i] || ms[g - g0 - 1] <= v)) total++;
+        }
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!query || !qoff || !len || !rank_lo || !rank_hi) return SUFR_HIP_E_INVALID;
+    uint64_t t = 0;
+    for (uint64_t i = 0; i < nq; i++)
+        for (uint64_t g = offsets[i]; g < offsets[i + 1]; g++) {
+            const uint32_t v = ms[g - g0];
+            if (v >= min_len && (g == offsets[i] || ms[g - g0 - 1] <= v)) {
+                query[t] = i; qoff[t] = (uint32_t)(g - offsets[i]); len[t] = v; t++;
+            }
+        }
+    // the rank range of every SMEM: a plain search of its slice (it occurs: ms >= min_len >= 1)
+    parallel_chunks(total, 256, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t k = b; k < e; k++) {
+            uint64_t lo = 0, hi = 0;
+            const int hit = sufr_file_search(f, queries + offsets[query[k]] + qoff[k], len[k], 0, 0, &lo, &hi);
+            rank_lo[k] = hit ? lo : 0; rank_hi[k] = hit ? hi : 0;
+        }
+    });
     return 0;
 }
 

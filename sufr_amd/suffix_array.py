@@ -9,7 +9,7 @@ from .types import SufrBuilderArgs
 
 
 class SuffixArray:
-    """After `read`, count / extract / list / locate / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
+    """After `read`, count / extract / list / locate / smems / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
 
     def __init__(self, inner: SufrFile):
         self.inner = inner
@@ -32,6 +32,9 @@ class SuffixArray:
 
     def extract(self, queries, max_query_len: Optional[int] = None, low_memory: bool = False, prefix_len=None, suffix_len=None):
         return self.inner.extract(queries, max_query_len, low_memory, prefix_len, suffix_len)
+
+    def smems(self, queries, min_len: int = 20, max_hits: int = 0):
+        return self.inner.smems(queries, min_len, max_hits)
 
     def list(self, **opts):
         return self.inner.list(**opts)

@@ -3,7 +3,8 @@
 `SufrFile` follows SufrFile<T> / SuffixArray of the reference (libsufr/src/sufr_file.rs, suffix_array.rs:181-440):
 count / locate / extract / list / metadata / string_at with the reference's option and result names.  The work is done
 by the C ABI of include/sufr_query.h (a mapped file, two binary searches per query).  `DeviceIndex` answers batches of
-queries on the GPU from text + suffix array resident in HBM (sufr_hip_search_batch)."""
+queries on the GPU from text + suffix array resident in HBM (sufr_hip_search_batch).  Both also give the matching
+statistics and the super-maximal exact matches (SMEMs) of queries (include/sufr_match.h)."""
 from __future__ import annotations
 
 import builtins
@@ -54,6 +55,32 @@ class ExtractResult:                   # types.rs:400-409
     query_num: int
     query: str
     sequences: List[ExtractSequence] = field(default_factory=list)
+
+
+@dataclass
+class SmemHit:                         # one SMEM of a query (include/sufr_match.h)
+    query_num: int
+    query_offset: int                  # the SMEM is query[query_offset : query_offset + length]
+    length: int
+    rank_lo: int                       # the suffixes that start with it: ranks [rank_lo, rank_hi)
+    rank_hi: int
+    positions: np.ndarray              # SA[rank_lo : rank_lo + max_hits] (all with 0): absolute, rank order
+
+    @property
+    def count(self) -> int:
+        return self.rank_hi - self.rank_lo
+
+
+def _hit_end(lo: int, hi: int, max_hits: int) -> int:
+    return lo + max_hits if max_hits and hi - lo > max_hits else hi
+
+
+def _split(flat: np.ndarray, off: np.ndarray) -> list:
+    o = off.astype(np.int64)
+    return [flat[o[i] - o[0]:o[i + 1] - o[0]] for i in range(len(o) - 1)]
+
+
+_SMEM_DTYPES = (np.uint64, np.uint32, np.uint32, np.uint64, np.uint64)     # query, query_offset, length, rank_lo, rank_hi
 
 
 @dataclass
@@ -216,6 +243,51 @@ class SufrFile:
     def count(self, queries: Sequence, max_query_len: Optional[int] = None, low_memory: bool = False) -> List[CountResult]:
         lo, hi = self.search_batch(queries, max_query_len)
         return [CountResult(i, q if isinstance(q, str) else bytes(q).decode("latin-1"), int(hi[i] - lo[i])) for i, q in enumerate(queries)]
+
+    def matching_statistics(self, queries: Sequence, threads: int = 0) -> List[np.ndarray]:
+        """ms[j] per query (uint32 arrays): the longest prefix of query[j:] that starts an indexed suffix, capped at the
+        build's max_query_len (include/sufr_match.h)."""
+        qb, off = pack_queries(queries)
+        ms = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        rc = lib().sufr_file_matching_stats(self._h, qb.ctypes.data, off.ctypes.data, len(off) - 1, ms.ctypes.data, threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_file_matching_stats: " + ("files built with a seed mask are not supported" if rc == -6 else "failed"))
+        return _split(ms, off)
+
+    def smem_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, min_len: int = 20, cap: Optional[int] = None, threads: int = 0):
+        """(query, query_offset, length, rank_lo, rank_hi) of every SMEM of a packed batch, in (query, offset) order.  With a
+        `cap` too small the SufrHipError (code -5) carries the total in `.total`; without one the arrays are sized to fit."""
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nq = len(offsets) - 1
+        c = cap if cap is not None else int(offsets[-1] - offsets[0]) // 8 + 16
+        while True:
+            out = [np.zeros(max(c, 1), dtype=d) for d in _SMEM_DTYPES]
+            total = C.c_uint64(0)
+            rc = lib().sufr_file_smems(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, min_len, c,
+                                       *[a.ctypes.data for a in out], C.byref(total), threads)
+            if rc == -5 and cap is None:
+                c = total.value
+                continue
+            if rc != 0:
+                msg = {-5: f"{total.value} SMEMs, room for {c}", -6: "files built with a seed mask are not supported",
+                       -1: "invalid argument (min_len must be at least 1)"}.get(rc, "failed")
+                err = SufrHipError(rc, "sufr_file_smems: " + msg)
+                err.total = total.value
+                raise err
+            return tuple(a[:total.value] for a in out)
+
+    def smems(self, queries: Sequence, min_len: int = 20, max_hits: int = 0, threads: int = 0) -> List[List[SmemHit]]:
+        """The SMEMs of every query (at least `min_len` long) with their rank ranges and up to `max_hits` positions each
+        (0: all), on the host."""
+        qb, off = pack_queries(queries)
+        qi, qo, ln, lo, hi = self.smem_arrays(qb, off, min_len, threads=threads)
+        sa = self.suffix_array
+        out: List[List[SmemHit]] = [[] for _ in queries]
+        for t in range(len(qi)):
+            a, b = int(lo[t]), int(hi[t])
+            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), a, b, sa[a:_hit_end(a, b, max_hits)].copy()))
+        return out
 
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
@@ -416,3 +488,72 @@ class DeviceIndex:
         lo, hi = self.search(queries, max_query_len)
         return [CountResult(i, q if isinstance(q, str) else bytes(q).decode("latin-1"), int(hi[i] - lo[i]))
                 for i, q in enumerate(queries)]
+
+    # -- matching statistics and SMEMs (include/sufr_match.h) ---------------------------------------------------------
+    def matching_statistics_device(self, qbytes, offsets, wait: bool = True):
+        """ms of a packed batch of torch CUDA tensors (uint8 bytes, int64 offsets): an int32 tensor (u32 values) indexed like
+        the bytes.  wait=False: call ctx.synchronize() before reading it."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        if qbytes.numel() == 0:                               # (a batch of empty queries still needs a device address)
+            qbytes = torch.zeros(1, dtype=torch.uint8, device=qbytes.device)
+        ms = torch.zeros(max(int(offsets[-1]) if nq >= 0 and offsets.numel() else 0, 1), dtype=torch.int32, device=qbytes.device)
+        self.ctx.check(lib().sufr_hip_matching_stats_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(),
+                                                            max(nq, 0), ms.data_ptr()))
+        if wait:
+            self.ctx.synchronize()
+        return ms
+
+    def matching_statistics(self, queries: Sequence) -> List[np.ndarray]:
+        """ms[j] per query (uint32 arrays), computed on the device."""
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        ms = self.matching_statistics_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev))
+        return _split(ms.cpu().numpy().view(np.uint32), off)
+
+    def smems_device(self, qbytes, offsets, min_len: int = 20, cap: Optional[int] = None):
+        """SMEMs of a packed batch of torch CUDA tensors: (query int64, query_offset int32, length int32, rank_lo int64,
+        rank_hi int64) tensors in (query, offset) order, complete on return.  With a `cap` too small the SufrHipError
+        (code -5) carries the total in `.total`; without one the outputs are sized to fit."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        dev = qbytes.device
+        if qbytes.numel() == 0:                               # (a batch of empty queries still needs a device address)
+            qbytes = torch.zeros(1, dtype=torch.uint8, device=dev)
+        nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
+        ms = torch.empty(max(int(offsets[-1]) if nq > 0 else 0, 1), dtype=torch.int32, device=dev)
+        c = cap if cap is not None else nbytes // 8 + 16
+        while True:
+            out = [torch.empty(max(c, 1), dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.int32, torch.int64, torch.int64)]
+            total = C.c_uint64(0)
+            rc = lib().sufr_hip_smems_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0), min_len,
+                                             ms.data_ptr(), c, *[t.data_ptr() for t in out], C.byref(total))
+            if rc == -5 and cap is None:
+                c = total.value
+                continue
+            if rc != 0:
+                err = SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode())
+                err.total = total.value
+                raise err
+            self.ctx.synchronize()
+            self.last_ms = ms
+            return tuple(t[:total.value] for t in out)
+
+    def smems(self, queries: Sequence, min_len: int = 20, max_hits: int = 0) -> List[List[SmemHit]]:
+        """The SMEMs of every query with their rank ranges and up to `max_hits` positions (0: all), searched and gathered
+        on the device (sufr_hip_smems_device + sufr_hip_locate_batch_device)."""
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        qi, qo, ln, lo, hi = self.smems_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), min_len)
+        po, pos = self.locate_device(lo, hi, max_hits)
+        po = po.cpu().numpy()
+        pos = pos.cpu().numpy().view(np.uint64 if getattr(self, "index_width", 4) == 8 else np.uint32)
+        qi, qo, ln, lo, hi = (t.cpu().numpy() for t in (qi, qo, ln, lo, hi))
+        out: List[List[SmemHit]] = [[] for _ in queries]
+        for t in range(len(qi)):
+            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[po[t]:po[t + 1]].copy()))
+        return out
