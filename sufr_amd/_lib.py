@@ -98,6 +98,9 @@ QUERY_EXPORTS = [
 MATCH_EXPORTS = [
     "sufr_file_matching_stats", "sufr_file_smems", "sufr_hip_matching_stats_device", "sufr_hip_smems_device", "sufr_hip_smems",
 ]
+# every symbol include/sufr_mem.h declares
+MEM_EXPORTS = ["sufr_file_mems", "sufr_hip_mems_device", "sufr_hip_mems"]
+MEM_BOTH_STRANDS = 0x1
 
 
 class FileMeta(C.Structure):
@@ -216,6 +219,13 @@ def lib() -> C.CDLL:
     L.sufr_hip_smems_device.restype = C.c_int
     L.sufr_hip_smems.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.sufr_hip_smems.restype = C.c_int
+    # include/sufr_mem.h
+    L.sufr_file_mems.argtypes = [vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64), C.c_int]
+    L.sufr_file_mems.restype = C.c_int
+    L.sufr_hip_mems_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_mems_device.restype = C.c_int
+    L.sufr_hip_mems.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_mems.restype = C.c_int
     _lib = L
     return L
 

@@ -20,6 +20,7 @@
 #include "../../include/sufr_hip.h"
 #include "../../include/sufr_query.h"
 #include "../../include/sufr_match.h"
+#include "../../include/sufr_mem.h"
 
 #include <algorithm>
 #include <fstream>
@@ -58,7 +59,11 @@ int usage(FILE* f)
             "                                       name  offset  length  count  positions\n"
             "                                       [-k|--min-len N (20)] [-n|--max-hits N (0: all)] [-a|--abs]\n"
             "                                       [-q|--reads FASTA/FASTQ] [-o OUT]\n"
-            "  count / locate / extract / match take --device <ID>: the queries are searched as one batch on that GPU\n\n"
+            "  mems|me      <SUFR> [QUERY]...       Maximal exact matches of the queries: one line per MEM,\n"
+            "                                       name  strand(+/-)  offset  length  seq:pos\n"
+            "                                       [-k|--min-len N (20)] [--max-occ N (0: no limit)] [-b|--both-strands]\n"
+            "                                       [-a|--abs] [-q|--reads FASTA/FASTQ] [-o OUT]\n"
+            "  count / locate / extract / match / mems take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
             "  -l, --log <LOG>           Log level [possible values: info, debug]\n"
@@ -101,8 +106,10 @@ struct QueryArgs {
     bool has_len = false, has_number = false; uint64_t len = 0, number = 0;
     int device = -1;                            // --device N: the whole batch of queries is searched on that GPU
     int threads = 0;                            // -t/--threads (global option, sufr/src/lib.rs:29-46): host search workers
-    uint64_t min_len = 20, max_hits = 0;        // match: -k / -n
-    std::string reads;                          // match: -q FASTA / FASTQ of named queries
+    uint64_t min_len = 20, max_hits = 0;        // match / mems: -k, match: -n
+    std::string reads;                          // match / mems: -q FASTA / FASTQ of named queries
+    uint64_t max_occ = 0;                       // mems: --max-occ
+    bool both_strands = false;                  // mems: -b
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -398,6 +405,26 @@ int cmd_summarize(const QueryArgs& a)
     return 0;
 }
 
+// the queries of match / mems: the positional ones (named by themselves), then the records of -q FASTA / FASTQ
+bool named_queries(const QueryArgs& a, std::vector<std::string>& names, std::vector<std::string>& seqs)
+{
+    names = expand_queries(a.positional);
+    seqs = names;
+    if (!a.reads.empty()) {
+        sufr_sequence_data sd{};
+        char err[512] = {0};
+        if (sufr_read_sequence_file(a.reads.c_str(), '%', &sd, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return false; }
+        for (uint64_t i = 0; i < sd.num_sequences; i++) {       // drop the delimiter after every sequence and the final sentinel
+            const uint64_t b = sd.start_positions[i];
+            const uint64_t e = i + 1 < sd.num_sequences ? sd.start_positions[i + 1] - 1 : (sd.seq_len ? sd.seq_len - 1 : 0);
+            names.push_back(sd.sequence_names[i]);
+            seqs.emplace_back((const char*)sd.seq + b, e > b ? e - b : 0);
+        }
+        sufr_sequence_data_free(&sd);
+    }
+    return true;
+}
+
 // arguments of the query sub-commands (clap definitions of lib.rs:129-271)
 // sufr match: the SMEMs of every query, one line each: name, offset, length, count, positions.
 // Positions: SA[rank_lo .. rank_lo + max_hits) (all with 0), printed as seq:pos ordered by sequence name then position
@@ -408,20 +435,8 @@ int cmd_match(const QueryArgs& a)
     OutFile out;
     if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
     if (a.min_len == 0 || a.min_len > 0xFFFFFFFFull) { fprintf(stderr, "Error: --min-len must be between 1 and 2^32 - 1\n"); return 1; }
-    std::vector<std::string> names = expand_queries(a.positional);
-    std::vector<std::string> seqs = names;
-    if (!a.reads.empty()) {
-        sufr_sequence_data sd{};
-        char err[512] = {0};
-        if (sufr_read_sequence_file(a.reads.c_str(), '%', &sd, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
-        for (uint64_t i = 0; i < sd.num_sequences; i++) {       // drop the delimiter after every sequence and the final sentinel
-            const uint64_t b = sd.start_positions[i];
-            const uint64_t e = i + 1 < sd.num_sequences ? sd.start_positions[i + 1] - 1 : (sd.seq_len ? sd.seq_len - 1 : 0);
-            names.push_back(sd.sequence_names[i]);
-            seqs.emplace_back((const char*)sd.seq + b, e > b ? e - b : 0);
-        }
-        sufr_sequence_data_free(&sd);
-    }
+    std::vector<std::string> names, seqs;
+    if (!named_queries(a, names, seqs)) return 1;
     std::string bytes;
     std::vector<uint64_t> off(seqs.size() + 1, 0);
     for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
@@ -471,6 +486,59 @@ int cmd_match(const QueryArgs& a)
     return 0;
 }
 
+// sufr mems: every MEM of every query, one line each in record order: name, strand (+ / -), offset (in
+// the strand's coordinates), length, position as seq:pos (0-based) or absolute with --abs.
+int cmd_mems(const QueryArgs& a)
+{
+    sufr_file* f = open_or_die(a.file);
+    OutFile out;
+    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    if (a.min_len == 0 || a.min_len > 0xFFFFFFFFull) { fprintf(stderr, "Error: --min-len must be between 1 and 2^32 - 1\n"); return 1; }
+    std::vector<std::string> names, seqs;
+    if (!named_queries(a, names, seqs)) return 1;
+    std::string bytes;
+    std::vector<uint64_t> off(seqs.size() + 1, 0);
+    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
+    sufr_hip_ctx* ctx = nullptr;
+    sufr_hip_index* ix = nullptr;
+    if (a.device >= 0) {
+        ctx = sufr_hip_create(a.device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
+        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
+    }
+    const uint32_t flags = a.both_strands ? SUFR_MEM_BOTH_STRANDS : 0;
+    // records: room for one MEM per 4 query bytes first, the exact count when that is short
+    uint64_t cap = bytes.size() / 4 + 16, total = 0;
+    std::vector<uint64_t> qi, pos;
+    std::vector<uint32_t> qo, len;
+    std::vector<uint8_t> st;
+    for (;;) {
+        qi.resize(cap); pos.resize(cap); qo.resize(cap); len.resize(cap); st.resize(cap);
+        const int rc = ix ? sufr_hip_mems(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, a.max_occ,
+                                          flags, cap, qi.data(), qo.data(), st.data(), len.data(), pos.data(), &total)
+                          : sufr_file_mems(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, a.max_occ,
+                                           flags, cap, qi.data(), qo.data(), st.data(), len.data(), pos.data(), &total, a.threads);
+        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
+        if (rc == SUFR_HIP_E_UNSUPPORTED) { fprintf(stderr, "Error: %s: mems does not support files built with a seed mask\n", a.file.c_str()); return 1; }
+        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "mems failed"); return 1; }
+        break;
+    }
+    if (ix) sufr_hip_index_free(ix);
+    if (ctx) sufr_hip_destroy(ctx);
+    for (uint64_t t = 0; t < total; t++) {
+        const char* name = names[qi[t]].c_str();
+        const char sgn = st[t] ? '-' : '+';
+        if (a.abs) fprintf(out.f, "%s\t%c\t%u\t%u\t%llu\n", name, sgn, qo[t], len[t], (unsigned long long)pos[t]);
+        else {
+            const uint64_t i = sufr_file_sequence_of(f, pos[t]);
+            fprintf(out.f, "%s\t%c\t%u\t%u\t%s:%llu\n", name, sgn, qo[t], len[t], sufr_file_sequence_name(f, i),
+                    (unsigned long long)(pos[t] - sufr_file_sequence_start(f, i)));
+        }
+    }
+    sufr_file_close(f);
+    return 0;
+}
+
 int run_query(const std::string& cmd, int argc, char** argv, int first, int threads)
 {
     QueryArgs a;
@@ -481,7 +549,8 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         return argv[++i];
     };
     const bool is_list = cmd == "list", is_extract = cmd == "extract", is_locate = cmd == "locate", is_sum = cmd == "summarize";
-    const bool is_match = cmd == "match";
+    const bool is_mems = cmd == "mems";
+    const bool is_match = cmd == "match" || is_mems;
     for (int i = first; i < argc; i++) {
         const std::string s = argv[i];
         if (s == "-h" || s == "--help") { usage(stdout); return 0; }
@@ -492,7 +561,9 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         else if (!is_list && !is_sum && s == "--device") a.device = atoi(need(i, "--device"));
         else if ((is_locate || is_match) && (s == "-a" || s == "--abs")) a.abs = true;
         else if (is_match && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
-        else if (is_match && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
+        else if (is_mems && s == "--max-occ") a.max_occ = strtoull(need(i, "--max-occ"), nullptr, 10);
+        else if (is_mems && (s == "-b" || s == "--both-strands")) a.both_strands = true;
+        else if (is_match && !is_mems && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
         else if (is_match && (s == "-q" || s == "--reads")) a.reads = need(i, "-q");
         else if (is_extract && (s == "-p" || s == "--prefix-len")) { a.has_prefix = true; a.prefix_len = strtoull(need(i, "-p"), nullptr, 10); }
         else if (is_extract && (s == "-s" || s == "--suffix-len")) { a.has_suffix = true; a.suffix_len = strtoull(need(i, "-s"), nullptr, 10); }
@@ -518,6 +589,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
+    if (is_mems) return cmd_mems(a);
     if (is_match) return cmd_match(a);
     if (is_extract) return cmd_extract(a);
     if (is_list) return cmd_list(a);
@@ -575,6 +647,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "count" || s == "co")) return run_query("count", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "locate" || s == "lo")) return run_query("locate", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "match" || s == "ma")) return run_query("match", argc, argv, i + 1, threads);
+        else if (!have_cmd && (s == "mems" || s == "me")) return run_query("mems", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "list" || s == "ls")) return run_query("list", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "summarize" || s == "su")) return run_query("summarize", argc, argv, i + 1, threads);

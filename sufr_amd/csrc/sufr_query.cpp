@@ -12,6 +12,7 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "../../include/sufr_hip.h"
 #include "../../include/sufr_query.h"
 #include "../../include/sufr_match.h"
+#include "../../include/sufr_mem.h"
 
 struct sufr_file {
     std::string path;
@@ -32,6 +34,8 @@ struct sufr_file {
     std::vector<uint64_t> seq_starts;
     std::vector<std::string> seq_names;
     std::vector<uint64_t> mask_positions;     // offsets of the 1s: the "care" positions (types.rs:36-200)
+    mutable std::once_flag indexed_once;      // MEMs: bit p of `indexed` = position p starts an indexed suffix, built on
+    mutable std::vector<uint64_t> indexed;    // first use when the array leaves positions out (sufr_mem.h)
 };
 
 namespace {
@@ -412,6 +416,103 @@ int sufr_file_smems(const sufr_file* f, const uint8_t* queries, const uint64_t* 
             rank_lo[k] = hit ? lo : 0; rank_hi[k] = hit ? hi : 0;
         }
     });
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- maximal exact matches (include/sufr_mem.h) -----------------------------------------------
+namespace {
+
+struct MemRec { uint64_t query; uint32_t qoff; uint8_t strand; uint32_t len; uint64_t pos; };
+
+// the indexed positions as a bitmap, once per open file; empty when every position is indexed
+const std::vector<uint64_t>& indexed_bits(const sufr_file& f)
+{
+    std::call_once(f.indexed_once, [&f]() {
+        const uint64_t n = f.meta.text_len, s = f.meta.len_suffixes;
+        if (s == n) return;
+        f.indexed.assign((n + 63) / 64, 0);
+        for (uint64_t r = 0; r < s; r++) { const uint64_t p = sufr_file_suffix(&f, r); f.indexed[p >> 6] |= 1ull << (p & 63); }
+    });
+    return f.indexed;
+}
+
+uint8_t revcomp_byte(uint8_t c)
+{
+    switch (c) { case 'A': return 'T'; case 'T': return 'A'; case 'C': return 'G'; case 'G': return 'C'; default: return c; }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_mems(const sufr_file* f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t min_len,
+                   uint64_t max_occ, uint32_t flags, uint64_t cap, uint64_t* query, uint32_t* qoff, uint8_t* strand,
+                   uint32_t* len, uint64_t* position, uint64_t* total_out, int threads)
+{
+    if (total_out) *total_out = 0;
+    if (const int rc = match_args(f, queries, offsets, nq)) return rc;
+    if (min_len == 0) return SUFR_HIP_E_INVALID;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    // the batch in record order: query i, then (both strands) its reverse complement as query 2i + 1
+    const bool both = (flags & SUFR_MEM_BOTH_STRANDS) != 0;
+    const uint64_t g0 = offsets[0], nb = offsets[nq] - g0;
+    const uint8_t* qb = queries + g0;
+    std::vector<uint8_t> dbl;
+    std::vector<uint64_t> off(nq + 1);
+    for (uint64_t i = 0; i <= nq; i++) off[i] = offsets[i] - g0;
+    uint64_t nb2 = nb, nq2 = nq;
+    if (both) {
+        dbl.resize(2 * nb);
+        std::vector<uint64_t> o2(2 * nq + 1);
+        for (uint64_t i = 0; i < nq; i++) {
+            const uint64_t a = off[i], b = off[i + 1];
+            o2[2 * i] = 2 * a; o2[2 * i + 1] = a + b;
+            memcpy(dbl.data() + 2 * a, qb + a, (size_t)(b - a));
+            for (uint64_t t = 0; t < b - a; t++) dbl[a + b + t] = revcomp_byte(qb[b - 1 - t]);
+        }
+        o2[2 * nq] = 2 * nb;
+        off.swap(o2);
+        qb = dbl.data(); nb2 = 2 * nb; nq2 = 2 * nq;
+    }
+    const std::vector<uint64_t>& bits = indexed_bits(*f);
+    const uint64_t n = f->meta.text_len, L = f->meta.max_query_len;
+    const uint32_t kk = L > 0 && L < min_len ? (uint32_t)L : min_len;                    // k' of the contract
+    const uint8_t* text = f->text;
+    // workers over chunks of query bytes; chunk c keeps its records, the chunks are concatenated in order
+    const uint64_t chunk = 4096, nchunks = (nb2 + chunk - 1) / chunk;
+    std::vector<std::vector<MemRec>> recs(nchunks);
+    parallel_chunks(nb2, chunk, threads, [&](uint64_t b, uint64_t e) {
+        std::vector<MemRec>& out = recs[b / chunk];
+        uint64_t a = query_of(off.data(), nq2, b);
+        for (uint64_t g = b; g < e; g++) {
+            while (off[a + 1] <= g) a++;
+            const uint64_t j = g - off[a], m = off[a + 1] - off[a];
+            if (j + min_len > m) continue;
+            uint64_t lo = 0, hi = 0;
+            if (!sufr_file_search(f, qb + g, kk, 0, 0, &lo, &hi)) continue;
+            if (max_occ && hi - lo > max_occ) continue;
+            for (uint64_t r = lo; r < hi; r++) {
+                const uint64_t p = sufr_file_suffix(f, r);
+                if (j > 0 && p > 0 && qb[g - 1] == text[p - 1] && (bits.empty() || (bits[(p - 1) >> 6] >> ((p - 1) & 63) & 1))) continue;
+                const uint64_t lim = m - j < n - p ? m - j : n - p;
+                uint64_t l = kk;                                                         // the slice matched
+                while (l < lim && qb[g + l] == text[p + l]) l++;
+                if (l < min_len) continue;
+                out.push_back({both ? a >> 1 : a, (uint32_t)j, (uint8_t)(both ? a & 1 : 0), (uint32_t)l, p});
+            }
+        }
+    });
+    uint64_t total = 0;
+    for (const auto& v : recs) total += v.size();
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!query || !qoff || !strand || !len || !position) return SUFR_HIP_E_INVALID;
+    uint64_t t = 0;
+    for (const auto& v : recs)
+        for (const MemRec& x : v) { query[t] = x.query; qoff[t] = x.qoff; strand[t] = x.strand; len[t] = x.len; position[t] = x.pos; t++; }
     return 0;
 }
 

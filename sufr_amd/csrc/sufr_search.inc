@@ -255,6 +255,9 @@ struct sufr_hip_index {
     void* own_mask = nullptr;
     void* ptab = nullptr;          // prefix table and its byte -> code map
     void* pcode = nullptr;
+    mutable std::mutex mem_mu;     // MEMs (sufr_mem.inc): bitmap of the indexed positions, built by the first call that needs it
+    mutable void* mem_bits = nullptr;
+    mutable bool mem_bits_done = false;
 };
 
 namespace {
@@ -421,6 +424,7 @@ void sufr_hip_index_free(sufr_hip_index* ix)
     if (ix->own_mask) (void)hipFree(ix->own_mask);
     if (ix->ptab) (void)hipFree(ix->ptab);
     if (ix->pcode) (void)hipFree(ix->pcode);
+    if (ix->mem_bits) (void)hipFree(ix->mem_bits);
     delete ix;
 }
 

@@ -36,6 +36,9 @@ class SuffixArray:
     def smems(self, queries, min_len: int = 20, max_hits: int = 0):
         return self.inner.smems(queries, min_len, max_hits)
 
+    def mems(self, queries, min_len: int = 20, max_occ: int = 0, both_strands: bool = False, threads: int = 0):
+        return self.inner.mems(queries, min_len, max_occ, both_strands, threads)
+
     def list(self, **opts):
         return self.inner.list(**opts)
 

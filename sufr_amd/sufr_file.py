@@ -4,7 +4,8 @@
 count / locate / extract / list / metadata / string_at with the reference's option and result names.  The work is done
 by the C ABI of include/sufr_query.h (a mapped file, two binary searches per query).  `DeviceIndex` answers batches of
 queries on the GPU from text + suffix array resident in HBM (sufr_hip_search_batch).  Both also give the matching
-statistics and the super-maximal exact matches (SMEMs) of queries (include/sufr_match.h)."""
+statistics and the super-maximal exact matches (SMEMs) of queries (include/sufr_match.h), and their
+maximal exact matches (MEMs) on one or both strands (include/sufr_mem.h)."""
 from __future__ import annotations
 
 import builtins
@@ -81,6 +82,25 @@ def _split(flat: np.ndarray, off: np.ndarray) -> list:
 
 
 _SMEM_DTYPES = (np.uint64, np.uint32, np.uint32, np.uint64, np.uint64)     # query, query_offset, length, rank_lo, rank_hi
+
+
+@dataclass
+class MemHit:                          # one MEM of a query (include/sufr_mem.h)
+    query_offset: int                  # query[query_offset : query_offset + length] (strand 1: of the reverse complement) ...
+    position: int                      # ... equals text[position : position + length], an indexed suffix
+    length: int
+    strand: int                        # 0: the query as given, 1: its reverse complement
+
+
+_MEM_DTYPES = (np.uint64, np.uint32, np.uint8, np.uint32, np.uint64)        # query, query_offset, strand, length, position
+
+
+def _mem_hits(nq: int, recs) -> List[List[MemHit]]:
+    qi, qo, st, ln, pos = recs
+    out: List[List[MemHit]] = [[] for _ in range(nq)]
+    for t in range(len(qi)):
+        out[int(qi[t])].append(MemHit(int(qo[t]), int(pos[t]), int(ln[t]), int(st[t])))
+    return out
 
 
 @dataclass
@@ -288,6 +308,39 @@ class SufrFile:
             a, b = int(lo[t]), int(hi[t])
             out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), a, b, sa[a:_hit_end(a, b, max_hits)].copy()))
         return out
+
+    def mem_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
+                   cap: Optional[int] = None, threads: int = 0):
+        """(query, query_offset, strand, length, position) of every MEM of a packed batch, in (query, strand, offset, rank)
+        order.  With a `cap` too small the SufrHipError (code -5) carries the total in `.total`; without one the arrays are
+        sized to fit."""
+        from ._lib import MEM_BOTH_STRANDS
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nq = len(offsets) - 1
+        c = cap if cap is not None else int(offsets[-1] - offsets[0]) // 4 + 16
+        while True:
+            out = [np.zeros(max(c, 1), dtype=d) for d in _MEM_DTYPES]
+            total = C.c_uint64(0)
+            rc = lib().sufr_file_mems(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, min_len, max_occ,
+                                      MEM_BOTH_STRANDS if both_strands else 0, c, *[a.ctypes.data for a in out], C.byref(total), threads)
+            if rc == -5 and cap is None:
+                c = total.value
+                continue
+            if rc != 0:
+                msg = {-5: f"{total.value} MEMs, room for {c}", -6: "files built with a seed mask are not supported",
+                       -1: "invalid argument (min_len must be at least 1)"}.get(rc, "failed")
+                err = SufrHipError(rc, "sufr_file_mems: " + msg)
+                err.total = total.value
+                raise err
+            return tuple(a[:total.value] for a in out)
+
+    def mems(self, queries: Sequence, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
+             threads: int = 0) -> List[List[MemHit]]:
+        """The MEMs of every query, at least `min_len` long, in (strand, offset, rank) order; offsets whose first min_len
+        symbols start more than `max_occ` indexed suffixes give none (0: no limit).  On the host."""
+        qb, off = pack_queries(queries)
+        return _mem_hits(len(off) - 1, self.mem_arrays(qb, off, min_len, max_occ, both_strands, threads=threads))
 
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
@@ -557,3 +610,44 @@ class DeviceIndex:
         for t in range(len(qi)):
             out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[po[t]:po[t + 1]].copy()))
         return out
+
+    # -- MEMs (include/sufr_mem.h) -----------------------------------------------------------------------------------
+    def mems_device(self, qbytes, offsets, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
+                    cap: Optional[int] = None):
+        """MEMs of a packed batch of torch CUDA tensors (uint8 bytes, int64 offsets): (query int64, query_offset int32,
+        strand uint8, length int32, position int64) tensors in (query, strand, offset, rank) order, complete on return.
+        With a `cap` too small the SufrHipError (code -5) carries the total in `.total`; without one the outputs are sized
+        to fit."""
+        import torch
+        from ._lib import MEM_BOTH_STRANDS
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        dev = qbytes.device
+        if qbytes.numel() == 0:                               # (a batch of empty queries still needs a device address)
+            qbytes = torch.zeros(1, dtype=torch.uint8, device=dev)
+        nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
+        c = cap if cap is not None else nbytes // 4 + 16
+        while True:
+            out = [torch.empty(max(c, 1), dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.uint8, torch.int32, torch.int64)]
+            total = C.c_uint64(0)
+            rc = lib().sufr_hip_mems_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0), min_len,
+                                            max_occ, MEM_BOTH_STRANDS if both_strands else 0, c, *[t.data_ptr() for t in out],
+                                            C.byref(total))
+            if rc == -5 and cap is None:
+                c = total.value
+                continue
+            if rc != 0:
+                err = SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode())
+                err.total = total.value
+                raise err
+            self.ctx.synchronize()
+            return tuple(t[:total.value] for t in out)
+
+    def mems(self, queries: Sequence, min_len: int = 20, max_occ: int = 0, both_strands: bool = False) -> List[List[MemHit]]:
+        """The MEMs of every query (SufrFile.mems), found on the device."""
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        recs = self.mems_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), min_len, max_occ,
+                                both_strands)
+        return _mem_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
