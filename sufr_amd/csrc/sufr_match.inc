@@ -1,54 +1,28 @@
 // sufr_match.inc -- matching statistics and SMEMs of a query batch on a device-resident index (included by sufr_kernels.hip
 // after sufr_search.inc; include/sufr_match.h, DESIGN.md section 13).
 //
-// k_matching_stats   one lane per query byte: the lower bound of the query's remainder Q[j..m) under search_compare (the
-//                    loop of k_search_batch), then ms[j] = the longer common prefix with the suffixes at ranks lo - 1 and lo.
-//                    The lane -> query map is a binary search of the offsets (grid-stride loop: the grid does not depend on
-//                    the batch, so the launch needs nothing from the device).
+// k_matching_stats   one lane per query byte: the lower bound of the query's remainder Q[j..m) (search_seed + search_lower of
+//                    sufr_search.inc), then ms[j] = the longer common prefix with the suffixes at ranks lo - 1 and lo.
+//                    The lane -> query map is a binary search of the offsets (last_le; grid-stride loop: the grid does not
+//                    depend on the batch, so the launch needs nothing from the device).
 // k_smem_count       SMEM flags (ms[j] >= k and (j == 0 or ms[j-1] <= ms[j])) counted per workgroup, with the summed lengths
 // k_locate_scan      (sufr_search.inc) exclusive scan of both per-workgroup sums; one synchronisation reads the totals
 // k_smem_emit        the flags again, scanned inside the workgroup: records in (query, offset) order + packed slice offsets
 // k_smem_gather      the SMEM slices packed into one query batch, searched by the unchanged sufr_hip_search_batch_device
 // No MFMA, no LDS beyond the scan words, no scratch.
+// Its own: match_stat, the SMEM rule (match_flags8) and the three SMEM kernels.  The search, last_le, wg_scan, scan_chunk
+// (SCAN_WGS workgroups), query_check, read_totals and the staging of the host-pointer entry point are sufr_search.inc's.
 
 namespace sufr {
 
-static constexpr uint32_t SMEM_WGS = 1024;      // workgroups of k_smem_count / k_smem_emit (fixed: blocksums of k_locate_scan)
-
-// the query that holds byte g of the batch: the last a < nq with off[a] <= g (off[0] <= g < off[nq])
-__device__ __forceinline__ uint64_t match_query_of(const uint64_t* __restrict__ off, uint64_t nq, uint64_t g)
-{
-    uint64_t a = 0, b = nq;
-    while (b - a > 1) { const uint64_t m = a + (b - a) / 2; if (off[m] <= g) a = m; else b = m; }
-    return a;
-}
-
 // ms of Q[0..qlen) (qlen >= 1).  Prefix table: an entry narrows the search to the suffixes that share the first pk symbols;
-// a missing entry only says ms < pk, so the whole array is searched.  l / r seeded with pk are lower bounds inside the table
-// range, not LCPs with probed neighbours: ms is taken from explicit comparisons with ranks lo - 1 and lo.
+// a missing entry (s.none) only says ms < pk, so the whole array is searched, which is what the seed then holds.  The l / r
+// that search_lower seeds with pk are lower bounds inside the table range, not LCPs with probed neighbours: ms is taken
+// from explicit comparisons with ranks lo - 1 and lo.
 __device__ __forceinline__ uint32_t match_stat(const SearchIndex& ix, const uint8_t* __restrict__ q, uint32_t qlen, uint64_t mql)
 {
-    uint64_t lo = 0, hi = ix.s;
-    uint32_t l = 0, r = 0;
-    if (ix.ptab && qlen >= ix.pk && (mql == 0 || mql >= ix.pk)) {
-        uint64_t code = 0;
-        bool ok = true;
-        for (uint32_t k = 0; k < ix.pk; k++) {
-            const uint32_t c = ix.pcode[q[k]];
-            ok = ok && c != 0xFFu;
-            code = code * ix.pradix + (c & 0x7Fu);
-        }
-        if (ok) {
-            const uint2 e = ix.ptab[code];
-            if (e.x != 0xFFFFFFFFu) { lo = e.x; hi = ~e.y; l = r = ix.pk; }
-        }
-    }
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        const SearchCmp c = search_compare(ix, q, qlen, mql, ix.suffix(mid), l < r ? l : r);
-        if (c.cmp > 0) { lo = mid + 1; l = c.lcp; }
-        else { hi = mid; r = c.lcp; }
-    }
+    const SearchSeed s = search_seed(ix, q, qlen, mql);
+    const uint64_t lo = search_lower(ix, q, qlen, mql, s.lo, s.hi, s.shared).first;
     uint32_t best = 0;
     if (lo > 0) best = search_compare(ix, q, qlen, mql, ix.suffix(lo - 1), 0).lcp;
     if (lo < ix.s) { const uint32_t v = search_compare(ix, q, qlen, mql, ix.suffix(lo), 0).lcp; best = v > best ? v : best; }
@@ -61,37 +35,9 @@ __global__ __launch_bounds__(256) void k_matching_stats(SearchIndex ix, const ui
 {
     const uint64_t g_end = qoff[nq], stride = (uint64_t)gridDim.x * 256;
     for (uint64_t g = qoff[0] + (uint64_t)blockIdx.x * 256 + threadIdx.x; g < g_end; g += stride) {
-        const uint64_t a = match_query_of(qoff, nq, g);
+        const uint64_t a = last_le(qoff, 0, nq, g);
         ms[g] = match_stat(ix, queries + g, (uint32_t)(qoff[a + 1] - g), mql);
     }
-}
-
-// exclusive workgroup scan of two per-lane values (256 lanes); tx / ty: the workgroup totals
-__device__ __forceinline__ void match_wg_scan2(uint64_t& x, uint64_t& y, uint64_t& tx, uint64_t& ty, uint64_t* s_w)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint64_t ix = x, iy = y;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t vx = __shfl_up(ix, o), vy = __shfl_up(iy, o);
-        if (lane >= (uint32_t)o) { ix += vx; iy += vy; }
-    }
-    if (lane == 63) { s_w[w] = ix; s_w[4 + w] = iy; }
-    __syncthreads();
-    uint64_t bx = 0, by = 0;
-    tx = 0; ty = 0;
-    for (uint32_t k = 0; k < 4; k++) {
-        if (k < w) { bx += s_w[k]; by += s_w[4 + k]; }
-        tx += s_w[k]; ty += s_w[4 + k];
-    }
-    __syncthreads();                                   // (s_w is reused by the next tile)
-    x = bx + ix - x; y = by + iy - y;
-}
-
-// workgroup b owns bytes [g0 + b * chunk, g0 + (b + 1) * chunk), in tiles of LOC_BLK (8 consecutive bytes per lane)
-__device__ __forceinline__ uint64_t match_chunk(uint64_t g0, uint64_t g_end)
-{
-    const uint64_t c = (g_end - g0 + SMEM_WGS - 1) / SMEM_WGS;
-    return (c + LOC_BLK - 1) / LOC_BLK * LOC_BLK;
 }
 
 // flags (bit k: byte g + k starts an SMEM), count and summed lengths of the 8 bytes of a lane
@@ -100,7 +46,7 @@ __device__ __forceinline__ void match_flags8(const uint32_t* __restrict__ ms, co
 {
     fl = 0; cnt = 0; lsum = 0;
     if (g >= g_hi) return;
-    uint64_t a = match_query_of(qoff, nq, g);
+    uint64_t a = last_le(qoff, 0, nq, g);
     for (uint32_t k = 0; k < 8 && g + k < g_hi; k++) {
         while (qoff[a + 1] <= g + k) a++;
         const uint32_t v = ms[g + k];
@@ -112,15 +58,15 @@ __global__ __launch_bounds__(256) void k_smem_count(const uint32_t* __restrict__
                                                     uint32_t min_len, uint64_t* __restrict__ cnt_sum, uint64_t* __restrict__ len_sum)
 {
     __shared__ uint64_t s_w[8];
-    const uint64_t g0 = qoff[0], g_end = qoff[nq], chunk = match_chunk(g0, g_end);
+    const uint64_t g0 = qoff[0], g_end = qoff[nq], chunk = scan_chunk(g_end - g0);
     const uint64_t lo = g0 + (uint64_t)blockIdx.x * chunk, hi = lo + chunk < g_end ? lo + chunk : g_end;
     uint64_t c_acc = 0, l_acc = 0;
     for (uint64_t t = lo; t < hi; t += LOC_BLK) {
-        uint64_t c, l, tc, tl;
+        uint64_t v[2], tot[2];                         // count, summed lengths
         uint32_t fl;
-        match_flags8(ms, qoff, nq, t + (uint64_t)threadIdx.x * 8, hi, min_len, fl, c, l);
-        match_wg_scan2(c, l, tc, tl, s_w);
-        c_acc += tc; l_acc += tl;
+        match_flags8(ms, qoff, nq, t + (uint64_t)threadIdx.x * 8, hi, min_len, fl, v[0], v[1]);
+        wg_scan(v, tot, s_w);
+        c_acc += tot[0]; l_acc += tot[1];
     }
     if (threadIdx.x == 0) { cnt_sum[blockIdx.x] = c_acc; len_sum[blockIdx.x] = l_acc; }
 }
@@ -132,25 +78,25 @@ __global__ __launch_bounds__(256) void k_smem_emit(const uint32_t* __restrict__ 
                                                    uint64_t* __restrict__ slice_off)
 {
     __shared__ uint64_t s_w[8];
-    const uint64_t g0 = qoff[0], g_end = qoff[nq], chunk = match_chunk(g0, g_end);
+    const uint64_t g0 = qoff[0], g_end = qoff[nq], chunk = scan_chunk(g_end - g0);
     const uint64_t lo = g0 + (uint64_t)blockIdx.x * chunk, hi = lo + chunk < g_end ? lo + chunk : g_end;
     uint64_t c_run = cnt_base[blockIdx.x], l_run = len_base[blockIdx.x];
     for (uint64_t t = lo; t < hi; t += LOC_BLK) {
         const uint64_t g = t + (uint64_t)threadIdx.x * 8;
-        uint64_t c, l, tc, tl;
+        uint64_t v[2], tot[2];                         // count, summed lengths
         uint32_t fl;
-        match_flags8(ms, qoff, nq, g, hi, min_len, fl, c, l);
-        match_wg_scan2(c, l, tc, tl, s_w);
-        uint64_t at = c_run + c, bytes = l_run + l;
-        uint64_t a = fl ? match_query_of(qoff, nq, g) : 0;
+        match_flags8(ms, qoff, nq, g, hi, min_len, fl, v[0], v[1]);
+        wg_scan(v, tot, s_w);
+        uint64_t at = c_run + v[0], bytes = l_run + v[1];
+        uint64_t a = fl ? last_le(qoff, 0, nq, g) : 0;
         for (uint32_t k = 0; fl; k++, fl >>= 1) {
             if (!(fl & 1u)) continue;
             while (qoff[a + 1] <= g + k) a++;
-            const uint32_t v = ms[g + k];
-            out_query[at] = a; out_qoff[at] = (uint32_t)(g + k - qoff[a]); out_len[at] = v; slice_off[at] = bytes;
-            at++; bytes += v;
+            const uint32_t len = ms[g + k];
+            out_query[at] = a; out_qoff[at] = (uint32_t)(g + k - qoff[a]); out_len[at] = len; slice_off[at] = bytes;
+            at++; bytes += len;
         }
-        c_run += tc; l_run += tl;
+        c_run += tot[0]; l_run += tot[1];
     }
 }
 
@@ -172,18 +118,6 @@ __global__ __launch_bounds__(256) void k_smem_gather(const uint8_t* __restrict__
 
 }  // namespace sufr
 
-namespace {
-
-int match_check(sufr_hip_ctx* ctx, const sufr_hip_index* ix)
-{
-    if (ix->device != ctx->pl.device) { ctx->pl.set_error("the index lives on another device"); return SUFR_HIP_E_INVALID; }
-    if (ix->ix.maskpos) { ctx->pl.set_error("matching statistics of a seed-mask index are not supported"); return SUFR_HIP_E_UNSUPPORTED; }
-    if (hipSetDevice(ctx->pl.device) != hipSuccess) { ctx->pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
-    return 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 int sufr_hip_matching_stats_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets,
@@ -191,7 +125,7 @@ int sufr_hip_matching_stats_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, 
 {
     if (!ctx || !ix || (num_queries && (!d_queries || !d_offsets || !d_ms))) return SUFR_HIP_E_INVALID;
     ctx->pl.err.clear();
-    if (const int rc = match_check(ctx, ix)) return rc;
+    if (const int rc = query_check(ctx, ix, "matching statistics")) return rc;
     if (!num_queries) return 0;
     // latency-bound lanes: 8 workgroups of 4 waves per CU, looping over the batch
     const uint32_t grid = (ctx->pl.num_cus ? ctx->pl.num_cus : 256u) * 8u;
@@ -210,13 +144,13 @@ int sufr_hip_smems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const voi
     if (!ctx || !ix || (num_queries && (!d_queries || !d_offsets || !d_ms))) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
     pl.err.clear();
-    if (const int rc = match_check(ctx, ix)) return rc;
+    if (const int rc = query_check(ctx, ix, "matching statistics")) return rc;
     if (min_len == 0) { pl.set_error("smems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
     if (!num_queries) return 0;
     int rc;
     if ((rc = sufr_hip_matching_stats_device(ctx, ix, d_queries, d_offsets, num_queries, d_ms))) return rc;
     // blocksums of the counts and of the lengths, then their two totals
-    const uint64_t G = sufr::SMEM_WGS;
+    const uint64_t G = sufr::SCAN_WGS;
     if ((rc = pl.ensure(ctx->mtmp, (2 * G + 2) * 8))) return rc;
     uint64_t* cnt_sum = (uint64_t*)ctx->mtmp.p;
     uint64_t* len_sum = cnt_sum + G;
@@ -227,10 +161,7 @@ int sufr_hip_smems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const voi
     hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, G, tot);
     hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, len_sum, G, tot + 1);
     unsigned long long totals[2] = {0, 0};
-    if (hipMemcpyAsync(totals, tot, 16, hipMemcpyDeviceToHost, pl.stream) != hipSuccess || hipStreamSynchronize(pl.stream) != hipSuccess) {
-        pl.set_error("smems: counting the SMEMs failed");
-        return SUFR_HIP_E_HIP;
-    }
+    if ((rc = read_totals(pl, tot, 2, totals, "smems: counting the SMEMs failed"))) return rc;
     const uint64_t nsm = totals[0], nbytes = totals[1];
     if (total_out) *total_out = nsm;
     if (nsm > cap) {
@@ -262,32 +193,21 @@ int sufr_hip_smems(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* q
     if (total_out) *total_out = 0;
     if (!ctx || !ix || (num_queries && !offsets)) return SUFR_HIP_E_INVALID;
     ctx->pl.err.clear();
-    if (const int rc = match_check(ctx, ix)) return rc;
+    if (const int rc = query_check(ctx, ix, "matching statistics")) return rc;
     if (min_len == 0) { ctx->pl.set_error("smems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
     if (!num_queries) return 0;
     const uint64_t qbytes = offsets[num_queries], obytes = (num_queries + 1) * 8;
     // one allocation: queries | offsets | ms | records (cap of each)
     const uint64_t o_at = (qbytes + 7) / 8 * 8, ms_at = o_at + obytes, q_at = ms_at + (qbytes * 4 + 7) / 8 * 8;
     const uint64_t qo_at = q_at + cap * 8, len_at = qo_at + cap * 4, lo_at = len_at + cap * 4, hi_at = lo_at + cap * 8;
-    uint8_t* d = nullptr;
-    if (hipMalloc((void**)&d, hi_at + cap * 8 + 8) != hipSuccess) { ctx->pl.set_error("hipMalloc of the SMEM batch failed"); return SUFR_HIP_E_NOMEM; }
-    hipStream_t st = ctx->pl.stream;
-    int rc = 0;
-    if ((qbytes && hipMemcpyAsync(d, queries, qbytes, hipMemcpyHostToDevice, st) != hipSuccess) ||
-        hipMemcpyAsync(d + o_at, offsets, obytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = SUFR_HIP_E_HIP;
+    uint8_t* d;
+    int rc = stage_batch(ctx, "SMEM", queries, offsets, num_queries, o_at, hi_at + cap * 8 + 8, &d);
     uint64_t total = 0;
     if (!rc) rc = sufr_hip_smems_device(ctx, ix, d, d + o_at, num_queries, min_len, d + ms_at, cap, d + q_at, d + qo_at, d + len_at,
                                         d + lo_at, d + hi_at, &total);
     if (total_out) *total_out = total;
-    if (!rc && total && (hipMemcpyAsync(query, d + q_at, total * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(query_offset, d + qo_at, total * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(length, d + len_at, total * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(rank_lo, d + lo_at, total * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(rank_hi, d + hi_at, total * 8, hipMemcpyDeviceToHost, st) != hipSuccess)) rc = SUFR_HIP_E_HIP;
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = SUFR_HIP_E_HIP;
-    if (rc == SUFR_HIP_E_HIP && ctx->pl.err.empty()) ctx->pl.set_error("copying the SMEM batch failed");
-    (void)hipFree(d);
-    return rc;
+    return unstage_batch(ctx, "SMEM", d, rc, {{query, q_at, total * 8}, {query_offset, qo_at, total * 4}, {length, len_at, total * 4},
+                                              {rank_lo, lo_at, total * 8}, {rank_hi, hi_at, total * 8}});
 }
 
 }  // extern "C"

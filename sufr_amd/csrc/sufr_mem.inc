@@ -3,9 +3,9 @@
 //
 // k_mem_bitmap       once per index whose array leaves positions out: one lane per rank sets bit SA[r] (atomicOr on u32 words)
 // k_mem_revcomp      both strands: the doubled batch, query i as it is then its reverse complement, with the new offsets
-// k_mem_ranges       one lane per query offset (grid-stride): the rank range of the k'-prefix Q[j..j+k') found in place with the
-//                    prefix table and the bound loops of k_search_batch (copied: that kernel stays as it is); an empty range when
-//                    j + k > m or the range holds more than max_occ suffixes
+// k_mem_ranges       one lane per query offset (grid-stride): the rank range of the k'-prefix Q[j..j+k') found in place by
+//                    search_range (sufr_search.inc, what k_search_batch runs); an empty range when j + k > m or the range
+//                    holds more than max_occ suffixes
 // k_locate_counts / k_locate_scan / k_locate_apply (sufr_search.inc) exclusive scan of the range sizes: the candidate starts;
 //                    one synchronisation reads the candidate total
 // k_mem_count        1024 workgroups over the candidates, 8 per lane: candidate -> offset by binary search of the starts,
@@ -13,10 +13,10 @@
 // k_locate_scan      the MEM total (second synchronisation) and the workgroup bases
 // k_mem_emit         the flags again, scanned in the workgroup; every MEM is extended with 8-byte compares and written
 // No MFMA, no LDS beyond the scan words, no scratch.
+// From sufr_search.inc: search_range, common_prefix, last_le (offset -> query, candidate -> offset), wg_scan and scan_chunk
+// (SCAN_WGS workgroups), query_check, read_totals and the staging of the host-pointer entry point.
 
 namespace sufr {
-
-static constexpr uint32_t MEM_WGS = 1024;       // workgroups of k_mem_count / k_mem_emit (fixed: blocksums of k_locate_scan)
 
 struct MemBatch {
     const uint8_t* q;           // query bytes (the doubled batch with both strands)
@@ -53,54 +53,11 @@ __global__ __launch_bounds__(256) void k_mem_revcomp(const uint8_t* __restrict__
         else doff[2 * nq] = 2 * (g_end - g0);
     }
     for (uint64_t g = g0 + tid; g < g_end; g += stride) {
-        const uint64_t a = match_query_of(qoff, nq, g), b = qoff[a], e = qoff[a + 1];
+        const uint64_t a = last_le(qoff, 0, nq, g), b = qoff[a], e = qoff[a + 1];
         const uint8_t c = queries[g];
         dst[2 * (b - g0) + (g - b)] = c;
         dst[b + e - 2 * g0 + (e - 1 - g)] = mem_complement(c);
     }
-}
-
-// rank range [lo, hi) of the suffixes that start with q[0..qlen) (qlen <= the build's cap): the loops of k_search_batch
-__device__ __forceinline__ void mem_range(const SearchIndex& ix, const uint8_t* __restrict__ q, uint32_t qlen, uint64_t mql,
-                                          uint64_t& lo_out, uint64_t& hi_out)
-{
-    lo_out = hi_out = 0;
-    uint64_t lo = 0, hi = ix.s, above = ix.s;
-    uint32_t l = 0, r = 0, r_above = 0;
-    if (ix.ptab && qlen >= ix.pk && (mql == 0 || mql >= ix.pk)) {
-        uint64_t code = 0;
-        bool ok = true;
-        for (uint32_t k = 0; k < ix.pk; k++) {
-            const uint32_t c = ix.pcode[q[k]];
-            ok = ok && c != 0xFFu;
-            code = code * ix.pradix + (c & 0x7Fu);
-        }
-        if (ok) {
-            const uint2 e = ix.ptab[code];
-            if (e.x == 0xFFFFFFFFu) return;
-            lo = e.x; hi = above = ~e.y;
-            l = r = r_above = ix.pk;
-        }
-    }
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        const SearchCmp c = search_compare(ix, q, qlen, mql, ix.suffix(mid), l < r ? l : r);
-        if (c.cmp > 0) { lo = mid + 1; l = c.lcp; }
-        else {
-            hi = mid; r = c.lcp;
-            if (c.cmp < 0) { above = mid; r_above = c.lcp; }
-        }
-    }
-    const uint64_t first = lo;
-    uint64_t ulo = first, uhi = above;
-    uint32_t ul = l, ur = r_above;
-    while (ulo < uhi) {
-        const uint64_t mid = ulo + (uhi - ulo) / 2;
-        const SearchCmp c = search_compare(ix, q, qlen, mql, ix.suffix(mid), ul < ur ? ul : ur);
-        if (c.cmp >= 0) { ulo = mid + 1; ul = c.lcp; }
-        else { uhi = mid; ur = c.lcp; }
-    }
-    if (ulo > first) { lo_out = first; hi_out = ulo; }
 }
 
 __global__ __launch_bounds__(256) void k_mem_ranges(SearchIndex ix, const uint8_t* __restrict__ queries, const uint64_t* __restrict__ qoff,
@@ -109,43 +66,14 @@ __global__ __launch_bounds__(256) void k_mem_ranges(SearchIndex ix, const uint8_
 {
     const uint64_t g0 = qoff[0], g_end = qoff[nq], stride = (uint64_t)gridDim.x * 256;
     for (uint64_t g = g0 + (uint64_t)blockIdx.x * 256 + threadIdx.x; g < g_end; g += stride) {
-        const uint64_t a = match_query_of(qoff, nq, g);
+        const uint64_t a = last_le(qoff, 0, nq, g);
         uint64_t lo = 0, hi = 0;
         if (g + min_len <= qoff[a + 1]) {
-            mem_range(ix, queries + g, kk, mql, lo, hi);
+            search_range(ix, queries + g, kk, mql, lo, hi);      // (kk <= the build's cap)
             if (max_occ && hi - lo > max_occ) hi = lo;
         }
         lo_out[g - g0] = lo; hi_out[g - g0] = hi;
     }
-}
-
-// the offset that holds candidate c: the last g in [a, b) with cand[g] <= c (cand[a] <= c)
-__device__ __forceinline__ uint64_t mem_offset_of(const uint64_t* __restrict__ cand, uint64_t a, uint64_t b, uint64_t c)
-{
-    while (b - a > 1) { const uint64_t m = a + (b - a) / 2; if (cand[m] <= c) a = m; else b = m; }
-    return a;
-}
-
-// exclusive workgroup scan of one per-lane value (256 lanes); tot: the workgroup total
-__device__ __forceinline__ uint64_t mem_wg_scan(uint64_t x, uint64_t& tot, uint64_t* s_w)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint64_t inc = x;
-    for (int o = 1; o < 64; o <<= 1) { const uint64_t v = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += v; }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    uint64_t base = 0;
-    tot = 0;
-    for (uint32_t k = 0; k < 4; k++) { if (k < w) base += s_w[k]; tot += s_w[k]; }
-    __syncthreads();                                   // (s_w is reused by the next tile)
-    return base + inc - x;
-}
-
-// workgroup b owns candidates [b * chunk, (b + 1) * chunk), in tiles of LOC_BLK (8 consecutive candidates per lane)
-__device__ __forceinline__ uint64_t mem_chunk(uint64_t total)
-{
-    const uint64_t c = (total + MEM_WGS - 1) / MEM_WGS;
-    return (c + LOC_BLK - 1) / LOC_BLK * LOC_BLK;
 }
 
 // walks the (up to) 8 candidates [c, c_hi) of a lane: f(k, g, a, p) for every one that starts a MEM (g: offset index, a: query)
@@ -154,11 +82,11 @@ __device__ __forceinline__ void mem_walk8(const SearchIndex& ix, const MemBatch&
 {
     if (c >= c_hi) return;
     const uint64_t g0 = B.qoff[0];
-    uint64_t g = mem_offset_of(B.cand, 0, B.nb, c);
-    uint64_t a = match_query_of(B.qoff, B.nq, g0 + g);
+    uint64_t g = last_le(B.cand, 0, B.nb, c);
+    uint64_t a = last_le(B.qoff, 0, B.nq, g0 + g);
     for (uint32_t k = 0; k < 8 && c + k < c_hi; k++) {
         if (B.cand[g + 1] <= c + k) {
-            g = mem_offset_of(B.cand, g + 1, B.nb, c + k);
+            g = last_le(B.cand, g + 1, B.nb, c + k);
             while (B.qoff[a + 1] <= g0 + g) a++;
         }
         const uint64_t G = g0 + g;
@@ -177,14 +105,14 @@ __device__ __forceinline__ void mem_walk8(const SearchIndex& ix, const MemBatch&
 __global__ __launch_bounds__(256) void k_mem_count(SearchIndex ix, MemBatch B, uint64_t* __restrict__ cnt_sum)
 {
     __shared__ uint64_t s_w[4];
-    const uint64_t total = B.cand[B.nb], chunk = mem_chunk(total);
+    const uint64_t total = B.cand[B.nb], chunk = scan_chunk(total);
     const uint64_t lo = (uint64_t)blockIdx.x * chunk, hi = lo + chunk < total ? lo + chunk : total;
     uint64_t acc = 0;
     for (uint64_t t = lo; t < hi; t += LOC_BLK) {
-        uint64_t cnt = 0, tot;
-        mem_walk8(ix, B, t + (uint64_t)threadIdx.x * 8, hi, [&](uint32_t, uint64_t, uint64_t, uint64_t) { cnt++; });
-        mem_wg_scan(cnt, tot, s_w);
-        acc += tot;
+        uint64_t cnt[1] = {0}, tot[1];
+        mem_walk8(ix, B, t + (uint64_t)threadIdx.x * 8, hi, [&](uint32_t, uint64_t, uint64_t, uint64_t) { cnt[0]++; });
+        wg_scan(cnt, tot, s_w);
+        acc += tot[0];
     }
     if (threadIdx.x == 0) cnt_sum[blockIdx.x] = acc;
 }
@@ -195,32 +123,22 @@ __global__ __launch_bounds__(256) void k_mem_emit(SearchIndex ix, MemBatch B, co
                                                   uint64_t* __restrict__ out_pos)
 {
     __shared__ uint64_t s_w[4];
-    const uint64_t total = B.cand[B.nb], chunk = mem_chunk(total);
+    const uint64_t total = B.cand[B.nb], chunk = scan_chunk(total);
     const uint64_t lo = (uint64_t)blockIdx.x * chunk, hi = lo + chunk < total ? lo + chunk : total;
     uint64_t run = cnt_base[blockIdx.x];
     for (uint64_t t = lo; t < hi; t += LOC_BLK) {
         const uint64_t c = t + (uint64_t)threadIdx.x * 8;
         uint32_t fl = 0;
-        uint64_t cnt = 0, tot;
-        mem_walk8(ix, B, c, hi, [&](uint32_t k, uint64_t, uint64_t, uint64_t) { fl |= 1u << k; cnt++; });
-        uint64_t at = run + mem_wg_scan(cnt, tot, s_w);
+        uint64_t cnt[1] = {0}, tot[1];
+        mem_walk8(ix, B, c, hi, [&](uint32_t k, uint64_t, uint64_t, uint64_t) { fl |= 1u << k; cnt[0]++; });
+        wg_scan(cnt, tot, s_w);
+        uint64_t at = run + cnt[0];
         if (fl) {
             mem_walk8(ix, B, c, hi, [&](uint32_t, uint64_t g, uint64_t a, uint64_t p) {
-                // the exact length: 8 symbols per step from the k' already matched (the loop of search_compare, uncapped)
+                // the exact length: on from the k' already matched, to the end of the query or of the text
                 const uint64_t G = B.qoff[0] + g, qe = B.qoff[a + 1];
                 const uint64_t lim = qe - G < ix.n - p ? qe - G : ix.n - p;
-                const uint8_t* __restrict__ qs = B.q + G;
-                const uint8_t* __restrict__ ts = ix.text + p;
-                uint64_t l = B.kk;
-                bool diff = false;
-                while (l + 8 <= lim) {
-                    uint64_t x, y;
-                    __builtin_memcpy(&x, qs + l, 8);
-                    __builtin_memcpy(&y, ts + l, 8);
-                    if (x != y) { l += (uint64_t)(__builtin_ctzll(x ^ y) >> 3); diff = true; break; }
-                    l += 8;
-                }
-                if (!diff) while (l < lim && qs[l] == ts[l]) l++;
+                const uint64_t l = common_prefix<uint64_t>(B.q + G, ix.text + p, B.kk, lim);
                 out_query[at] = both ? a >> 1 : a;
                 out_qoff[at] = (uint32_t)(G - B.qoff[a]);
                 out_strand[at] = (uint8_t)(both ? a & 1 : 0);
@@ -229,7 +147,7 @@ __global__ __launch_bounds__(256) void k_mem_emit(SearchIndex ix, MemBatch B, co
                 at++;
             });
         }
-        run += tot;
+        run += tot[0];
     }
 }
 
@@ -261,15 +179,6 @@ int mem_bitmap(sufr_hip_ctx* ctx, const sufr_hip_index* ix)
     return 0;
 }
 
-int mem_check(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint32_t min_len)
-{
-    if (ix->device != ctx->pl.device) { ctx->pl.set_error("the index lives on another device"); return SUFR_HIP_E_INVALID; }
-    if (ix->ix.maskpos) { ctx->pl.set_error("MEMs of a seed-mask index are not supported"); return SUFR_HIP_E_UNSUPPORTED; }
-    if (min_len == 0) { ctx->pl.set_error("mems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
-    if (hipSetDevice(ctx->pl.device) != hipSuccess) { ctx->pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -283,7 +192,8 @@ int sufr_hip_mems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     if (!ctx || !ix || (num_queries && (!d_queries || !d_offsets))) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
     pl.err.clear();
-    if (const int rc = mem_check(ctx, ix, min_len)) return rc;
+    if (const int rc = query_check(ctx, ix, "MEMs")) return rc;
+    if (min_len == 0) { ctx->pl.set_error("mems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
     if (!num_queries) return 0;
     int rc;
     if ((rc = mem_bitmap(ctx, ix))) return rc;
@@ -311,7 +221,7 @@ int sufr_hip_mems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     const uint32_t kk = L > 0 && L < min_len ? (uint32_t)L : min_len;
     const uint64_t nblk = (nb + sufr::LOC_BLK - 1) / sufr::LOC_BLK;
     if ((rc = pl.ensure(ctx->xlo, nb * 8)) || (rc = pl.ensure(ctx->xhi, nb * 8)) || (rc = pl.ensure(ctx->xcand, (nb + 1) * 8)) ||
-        (rc = pl.ensure(ctx->xsum, (nblk + 1 + sufr::MEM_WGS + 1) * 8))) return rc;
+        (rc = pl.ensure(ctx->xsum, (nblk + 1 + sufr::SCAN_WGS + 1) * 8))) return rc;
     uint64_t* rlo = (uint64_t*)ctx->xlo.p;
     uint64_t* cand = (uint64_t*)ctx->xcand.p;
     uint64_t* bsum = (uint64_t*)ctx->xsum.p;
@@ -324,18 +234,14 @@ int sufr_hip_mems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((nb + 256) / 256)), dim3(256), 0, pl.stream, cand, nb, (const uint64_t*)bsum,
                        (const uint64_t*)(bsum + nblk));
     unsigned long long ncand = 0;
-    if (hipMemcpyAsync(&ncand, bsum + nblk, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess || hipStreamSynchronize(pl.stream) != hipSuccess) {
-        pl.set_error("mems: counting the candidates failed");
-        return SUFR_HIP_E_HIP;
-    }
+    if ((rc = read_totals(pl, bsum + nblk, 1, &ncand, "mems: counting the candidates failed"))) return rc;
     if (!ncand) return 0;
     // the left condition per candidate, counted per workgroup, then the MEM total
     const sufr::MemBatch B{q, qoff, nq, rlo, cand, nb, (const uint32_t*)ix->mem_bits, min_len, kk};
-    hipLaunchKernelGGL(sufr::k_mem_count, dim3(sufr::MEM_WGS), dim3(256), 0, pl.stream, ix->ix, B, cnt_sum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, (uint64_t)sufr::MEM_WGS, cnt_sum + sufr::MEM_WGS);
+    hipLaunchKernelGGL(sufr::k_mem_count, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, cnt_sum);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, (uint64_t)sufr::SCAN_WGS, cnt_sum + sufr::SCAN_WGS);
     unsigned long long nmem = 0;
-    if (hipMemcpyAsync(&nmem, cnt_sum + sufr::MEM_WGS, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-        hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("mems: counting the MEMs failed"); return SUFR_HIP_E_HIP; }
+    if ((rc = read_totals(pl, cnt_sum + sufr::SCAN_WGS, 1, &nmem, "mems: counting the MEMs failed"))) return rc;
     if (total_out) *total_out = nmem;
     if (nmem > cap) {
         pl.set_error("mems: " + std::to_string(nmem) + " MEMs, room for " + std::to_string(cap));
@@ -343,7 +249,7 @@ int sufr_hip_mems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     }
     if (!nmem) return 0;
     if (!d_query || !d_query_offset || !d_strand || !d_length || !d_position) return SUFR_HIP_E_INVALID;
-    hipLaunchKernelGGL(sufr::k_mem_emit, dim3(sufr::MEM_WGS), dim3(256), 0, pl.stream, ix->ix, B, (const uint64_t*)cnt_sum, (uint32_t)both,
+    hipLaunchKernelGGL(sufr::k_mem_emit, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, (const uint64_t*)cnt_sum, (uint32_t)both,
                        (uint64_t*)d_query, (uint32_t*)d_query_offset, (uint8_t*)d_strand, (uint32_t*)d_length, (uint64_t*)d_position);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { pl.set_error(std::string("mems: ") + hipGetErrorString(e)); return SUFR_HIP_E_HIP; }
@@ -357,31 +263,21 @@ int sufr_hip_mems(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* qu
     if (total_out) *total_out = 0;
     if (!ctx || !ix || (num_queries && !offsets)) return SUFR_HIP_E_INVALID;
     ctx->pl.err.clear();
-    if (const int rc = mem_check(ctx, ix, min_len)) return rc;
+    if (const int rc = query_check(ctx, ix, "MEMs")) return rc;
+    if (min_len == 0) { ctx->pl.set_error("mems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
     if (!num_queries) return 0;
     const uint64_t qbytes = offsets[num_queries], obytes = (num_queries + 1) * 8;
     // one allocation: queries | offsets | records (cap of each)
     const uint64_t o_at = (qbytes + 7) / 8 * 8, q_at = o_at + obytes, pos_at = q_at + cap * 8, qo_at = pos_at + cap * 8;
     const uint64_t len_at = qo_at + cap * 4, st_at = len_at + cap * 4;
-    uint8_t* d = nullptr;
-    if (hipMalloc((void**)&d, st_at + cap + 8) != hipSuccess) { ctx->pl.set_error("hipMalloc of the MEM batch failed"); return SUFR_HIP_E_NOMEM; }
-    hipStream_t st = ctx->pl.stream;
-    int rc = 0;
-    if ((qbytes && hipMemcpyAsync(d, queries, qbytes, hipMemcpyHostToDevice, st) != hipSuccess) ||
-        hipMemcpyAsync(d + o_at, offsets, obytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = SUFR_HIP_E_HIP;
+    uint8_t* d;
+    int rc = stage_batch(ctx, "MEM", queries, offsets, num_queries, o_at, st_at + cap + 8, &d);
     uint64_t total = 0;
     if (!rc) rc = sufr_hip_mems_device(ctx, ix, d, d + o_at, num_queries, min_len, max_occ, flags, cap, d + q_at, d + qo_at, d + st_at,
                                        d + len_at, d + pos_at, &total);
     if (total_out) *total_out = total;
-    if (!rc && total && (hipMemcpyAsync(query, d + q_at, total * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(query_offset, d + qo_at, total * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(strand, d + st_at, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(length, d + len_at, total * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipMemcpyAsync(position, d + pos_at, total * 8, hipMemcpyDeviceToHost, st) != hipSuccess)) rc = SUFR_HIP_E_HIP;
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = SUFR_HIP_E_HIP;
-    if (rc == SUFR_HIP_E_HIP && ctx->pl.err.empty()) ctx->pl.set_error("copying the MEM batch failed");
-    (void)hipFree(d);
-    return rc;
+    return unstage_batch(ctx, "MEM", d, rc, {{query, q_at, total * 8}, {query_offset, qo_at, total * 4}, {strand, st_at, total},
+                                             {length, len_at, total * 4}, {position, pos_at, total * 8}});
 }
 
 }  // extern "C"

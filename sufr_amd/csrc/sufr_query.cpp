@@ -115,6 +115,29 @@ Comparison compare(const sufr_file& f, const uint8_t* q, size_t qlen, bool has_r
     return {lcp, cmp};
 }
 
+// runs body(b, e) over [0, total) in chunks of `chunk`, `threads` workers (0: one per core), at most one per `least` items
+// (0: one per chunk)
+template <typename F>
+void parallel_chunks(uint64_t total, uint64_t chunk, int threads, F body, uint64_t least = 0)
+{
+    if (least == 0) least = chunk;
+    unsigned T = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
+    if (T == 0) T = 1;
+    if (T > total / least + 1) T = (unsigned)(total / least + 1);
+    std::atomic<uint64_t> next{0};
+    auto worker = [&]() {
+        for (;;) {
+            const uint64_t b = next.fetch_add(chunk);
+            if (b >= total) return;
+            body(b, b + chunk < total ? b + chunk : total);
+        }
+    };
+    if (T == 1) { worker(); return; }
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < T; t++) th.emplace_back(worker);
+    for (auto& t : th) t.join();
+}
+
 }  // namespace
 
 extern "C" {
@@ -266,26 +289,13 @@ int sufr_file_search_batch(const sufr_file* f, const uint8_t* queries, const uin
                            uint64_t mql, uint64_t* rank_lo, uint64_t* rank_hi, int threads)
 {
     if (!f || (nq && (!offsets || !rank_lo || !rank_hi))) return SUFR_HIP_E_INVALID;
-    unsigned T = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
-    if (T == 0) T = 1;
-    if (T > nq / 64 + 1) T = (unsigned)(nq / 64 + 1);          // a worker is not worth fewer than 64 queries
-    std::atomic<uint64_t> next{0};
-    auto worker = [&]() {
-        for (;;) {
-            const uint64_t b = next.fetch_add(256);
-            if (b >= nq) return;
-            const uint64_t e = b + 256 < nq ? b + 256 : nq;
-            for (uint64_t i = b; i < e; i++) {
-                uint64_t lo = 0, hi = 0;
-                const int hit = sufr_file_search(f, queries + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), has_mql, mql, &lo, &hi);
-                rank_lo[i] = hit ? lo : 0; rank_hi[i] = hit ? hi : 0;
-            }
+    parallel_chunks(nq, 256, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t i = b; i < e; i++) {
+            uint64_t lo = 0, hi = 0;
+            const int hit = sufr_file_search(f, queries + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), has_mql, mql, &lo, &hi);
+            rank_lo[i] = hit ? lo : 0; rank_hi[i] = hit ? hi : 0;
         }
-    };
-    if (T == 1) { worker(); return 0; }
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < T; t++) th.emplace_back(worker);
-    for (auto& t : th) t.join();
+    }, 64);                                                    // a worker is not worth fewer than 64 queries
     return 0;
 }
 
@@ -314,27 +324,6 @@ uint32_t host_ms(const sufr_file& f, const uint8_t* q, size_t qlen)
     return (uint32_t)best;
 }
 
-// runs body(b, e) over [0, total) in chunks of `chunk`, `threads` workers (0: one per core)
-template <typename F>
-void parallel_chunks(uint64_t total, uint64_t chunk, int threads, F body)
-{
-    unsigned T = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
-    if (T == 0) T = 1;
-    if (T > total / chunk + 1) T = (unsigned)(total / chunk + 1);
-    std::atomic<uint64_t> next{0};
-    auto worker = [&]() {
-        for (;;) {
-            const uint64_t b = next.fetch_add(chunk);
-            if (b >= total) return;
-            body(b, b + chunk < total ? b + chunk : total);
-        }
-    };
-    if (T == 1) { worker(); return; }
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < T; t++) th.emplace_back(worker);
-    for (auto& t : th) t.join();
-}
-
 // the query that holds byte g of the batch: the last i < nq with offsets[i] <= g
 uint64_t query_of(const uint64_t* offsets, uint64_t nq, uint64_t g)
 {
@@ -351,6 +340,20 @@ int match_args(const sufr_file* f, const uint8_t* queries, const uint64_t* offse
     return 0;
 }
 
+// ms of every byte of the batch: ms[g - base] for g in [offsets[0], offsets[nq])
+void host_ms_batch(const sufr_file& f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, int threads, uint32_t* ms,
+                   uint64_t base)
+{
+    const uint64_t g0 = offsets[0];
+    parallel_chunks(offsets[nq] - g0, 4096, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t a = query_of(offsets, nq, g0 + b);
+        for (uint64_t g = g0 + b; g < g0 + e; g++) {
+            while (offsets[a + 1] <= g) a++;
+            ms[g - base] = host_ms(f, queries + g, (size_t)(offsets[a + 1] - g));
+        }
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -361,14 +364,7 @@ int sufr_file_matching_stats(const sufr_file* f, const uint8_t* queries, const u
     if (const int rc = match_args(f, queries, offsets, nq)) return rc;
     if (!nq || offsets[nq] == offsets[0]) return 0;
     if (!ms) return SUFR_HIP_E_INVALID;
-    const uint64_t g0 = offsets[0];
-    parallel_chunks(offsets[nq] - g0, 4096, threads, [&](uint64_t b, uint64_t e) {
-        uint64_t a = query_of(offsets, nq, g0 + b);
-        for (uint64_t g = g0 + b; g < g0 + e; g++) {
-            while (offsets[a + 1] <= g) a++;
-            ms[g] = host_ms(*f, queries + g, (size_t)(offsets[a + 1] - g));
-        }
-    });
+    host_ms_batch(*f, queries, offsets, nq, threads, ms, 0);
     return 0;
 }
 
@@ -380,34 +376,25 @@ int sufr_file_smems(const sufr_file* f, const uint8_t* queries, const uint64_t* 
     if (const int rc = match_args(f, queries, offsets, nq)) return rc;
     if (min_len == 0) return SUFR_HIP_E_INVALID;
     if (!nq || offsets[nq] == offsets[0]) return 0;
-    const uint64_t g0 = offsets[0], nbytes = offsets[nq] - g0;
-    std::vector<uint32_t> ms(nbytes);
-    parallel_chunks(nbytes, 4096, threads, [&](uint64_t b, uint64_t e) {
-        uint64_t a = query_of(offsets, nq, g0 + b);
-        for (uint64_t g = g0 + b; g < g0 + e; g++) {
-            while (offsets[a + 1] <= g) a++;
-            ms[g - g0] = host_ms(*f, queries + g, (size_t)(offsets[a + 1] - g));
-        }
-    });
-    // the SMEM rule in (query, offset) order
+    const uint64_t g0 = offsets[0];
+    std::vector<uint32_t> ms(offsets[nq] - g0);
+    host_ms_batch(*f, queries, offsets, nq, threads, ms.data(), g0);
+    // the SMEM rule in (query, offset) order: emit(i, g, length) for every SMEM; they are counted, then written
+    auto each_smem = [&](auto emit) {
+        for (uint64_t i = 0; i < nq; i++)
+            for (uint64_t g = offsets[i]; g < offsets[i + 1]; g++) {
+                const uint32_t v = ms[g - g0];
+                if (v >= min_len && (g == offsets[i] || ms[g - g0 - 1] <= v)) emit(i, g, v);
+            }
+    };
     uint64_t total = 0;
-    for (uint64_t i = 0; i < nq; i++)
-        for (uint64_t g = offsets[i]; g < offsets[i + 1]; g++) {
-            const uint32_t v = ms[g - g0];
-            if (v >= min_len && (g == offsets[i] || ms[g - g0 - 1] <= v)) total++;
-        }
+    each_smem([&](uint64_t, uint64_t, uint32_t) { total++; });
     if (total_out) *total_out = total;
     if (total > cap) return SUFR_HIP_E_CAPACITY;
     if (!total) return 0;
     if (!query || !qoff || !len || !rank_lo || !rank_hi) return SUFR_HIP_E_INVALID;
     uint64_t t = 0;
-    for (uint64_t i = 0; i < nq; i++)
-        for (uint64_t g = offsets[i]; g < offsets[i + 1]; g++) {
-            const uint32_t v = ms[g - g0];
-            if (v >= min_len && (g == offsets[i] || ms[g - g0 - 1] <= v)) {
-                query[t] = i; qoff[t] = (uint32_t)(g - offsets[i]); len[t] = v; t++;
-            }
-        }
+    each_smem([&](uint64_t i, uint64_t g, uint32_t v) { query[t] = i; qoff[t] = (uint32_t)(g - offsets[i]); len[t] = v; t++; });
     // the rank range of every SMEM: a plain search of its slice (it occurs: ms >= min_len >= 1)
     parallel_chunks(total, 256, threads, [&](uint64_t b, uint64_t e) {
         for (uint64_t k = b; k < e; k++) {

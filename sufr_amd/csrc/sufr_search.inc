@@ -13,6 +13,10 @@
 // ~20 steps of every query fall on the same 2^20 array cells and stay in L2 / MALL; the last log2(s) - 20 steps of both
 // searches are random 64-byte HBM sectors.  The kernel is latency bound per lane and sector-rate bound per device,
 // nowhere near the byte rate of HBM.
+//
+// This file owns what every query kernel shares; sufr_match.inc and sufr_mem.inc, included after it, add only their own
+// rules.  Device: search_compare / common_prefix, the range search (search_seed, search_lower, search_range), last_le,
+// wg_scan, scan_chunk.  Host: query_check, read_totals, stage_batch / unstage_batch.
 
 namespace sufr {
 
@@ -43,6 +47,23 @@ __device__ __forceinline__ uint64_t search_full_offset(const SearchIndex& ix, ui
     return (next > off && next - off > 1) ? next : off + 1;
 }
 
+// symbols a and b share from `from` on, `lim` at most: 8 per step (a byte loop pays one L2 round trip per symbol)
+template <typename T>
+__device__ __forceinline__ T common_prefix(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, T from, T lim)
+{
+    T k = from;
+    bool diff = false;
+    while (k + 8 <= lim) {
+        uint64_t x, y;
+        __builtin_memcpy(&x, a + k, 8);
+        __builtin_memcpy(&y, b + k, 8);
+        if (x != y) { k += (T)(__builtin_ctzll(x ^ y) >> 3); diff = true; break; }
+        k += 8;
+    }
+    if (!diff) while (k < lim && a[k] == b[k]) k++;
+    return k;
+}
+
 // SufrSearch::compare (sufr_search.rs:241-343); mql = the effective max_query_len (0: none), resolved on the host
 __device__ __forceinline__ SearchCmp search_compare(const SearchIndex& ix, const uint8_t* __restrict__ q, uint32_t qlen, uint64_t mql,
                                                     uint64_t sp, uint32_t skip)
@@ -54,20 +75,9 @@ __device__ __forceinline__ SearchCmp search_compare(const SearchIndex& ix, const
             const uint64_t ts = sp + skip;
             uint64_t te = mql > 0 ? ts + mql : ts + qlen;
             if (te > ix.n) te = ix.n;
-            const uint8_t* __restrict__ t = ix.text + ts;
             const uint32_t room = te > ts ? (uint32_t)(te - ts) : 0;
             const uint32_t lim = qlen - skip < room ? qlen - skip : room;      // skip <= qlen: it is an lcp with the query
-            uint32_t k = 0;
-            bool diff = false;
-            while (k + 8 <= lim) {                      // 8 symbols per step: a byte loop pays one L2 round trip per symbol
-                uint64_t a, b;
-                __builtin_memcpy(&a, q + skip + k, 8);
-                __builtin_memcpy(&b, t + k, 8);
-                if (a != b) { k += (uint32_t)(__builtin_ctzll(a ^ b) >> 3); diff = true; break; }
-                k += 8;
-            }
-            if (!diff) while (k < lim && q[skip + k] == t[k]) k++;
-            lcp = skip + k;
+            lcp = skip + common_prefix<uint32_t>(q + skip, ix.text + ts, 0, lim);
         }
     } else {
         const uint32_t weight = ix.weight;
@@ -95,6 +105,74 @@ __device__ __forceinline__ SearchCmp search_compare(const SearchIndex& ix, const
         }
     }
     return {lcp, cmp};
+}
+
+// ---- the range search every query kernel shares (k_search_batch, k_matching_stats, k_mem_ranges) ------------------
+// Returned by value: reference parameters for l / above / r_above cost these kernels 12 bytes of scratch per lane.
+struct SearchSeed { uint64_t lo, hi; uint32_t shared; bool none; };               // [lo, hi) holds every suffix that can match
+struct SearchLower { uint64_t first, above; uint32_t l, r_above; };
+
+// Prefix table: the suffixes that start with the query's first pk symbols are one rank range, looked up instead of
+// searched (`shared` = pk), or there are none (`none`).  Without a table, for a shorter query or cap, and for symbols
+// outside the table alphabet: the whole array with nothing shared.
+__device__ __forceinline__ SearchSeed search_seed(const SearchIndex& ix, const uint8_t* __restrict__ q, uint32_t qlen, uint64_t mql)
+{
+    SearchSeed s{0, ix.s, 0, false};
+    if (ix.ptab && qlen >= ix.pk && (mql == 0 || mql >= ix.pk)) {
+        uint64_t code = 0;
+        bool ok = true;
+        for (uint32_t k = 0; k < ix.pk; k++) {
+            const uint32_t c = ix.pcode[q[k]];
+            ok = ok && c != 0xFFu;
+            code = code * ix.pradix + (c & 0x7Fu);
+        }
+        if (ok) {
+            const uint2 e = ix.ptab[code];
+            if (e.x == 0xFFFFFFFFu) s.none = true;
+            else { s.lo = e.x; s.hi = ~e.y; s.shared = ix.pk; }
+        }
+    }
+    return s;
+}
+
+// Lower bound in [lo, hi), whose suffixes all share `shared` symbols with the query: `first` = the first rank whose
+// suffix is not below the query, `above` = the lowest rank seen above it (hi if none), l = symbols shared with the
+// suffix just below `first` (or with the whole range), r_above = those shared with `above`.
+__device__ __forceinline__ SearchLower search_lower(const SearchIndex& ix, const uint8_t* __restrict__ q, uint32_t qlen, uint64_t mql,
+                                                    uint64_t lo, uint64_t hi, uint32_t shared)
+{
+    uint64_t above = hi;
+    uint32_t l = shared, r = shared, r_above = shared;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const SearchCmp c = search_compare(ix, q, qlen, mql, ix.suffix(mid), l < r ? l : r);
+        if (c.cmp > 0) { lo = mid + 1; l = c.lcp; }
+        else {
+            hi = mid; r = c.lcp;
+            if (c.cmp < 0) { above = mid; r_above = c.lcp; }
+        }
+    }
+    return {lo, above, l, r_above};
+}
+
+// The half-open rank range of the suffixes that match q[0..qlen); lo == hi == 0 when there are none.
+__device__ __forceinline__ void search_range(const SearchIndex& ix, const uint8_t* __restrict__ q, uint32_t qlen, uint64_t mql,
+                                             uint64_t& lo_out, uint64_t& hi_out)
+{
+    lo_out = hi_out = 0;
+    const SearchSeed s = search_seed(ix, q, qlen, mql);
+    if (s.none) return;
+    const SearchLower b = search_lower(ix, q, qlen, mql, s.lo, s.hi, s.shared);
+    // upper bound inside [first, above): the first rank whose suffix is above the query
+    uint64_t ulo = b.first, uhi = b.above;
+    uint32_t ul = b.l, ur = b.r_above;
+    while (ulo < uhi) {
+        const uint64_t mid = ulo + (uhi - ulo) / 2;
+        const SearchCmp c = search_compare(ix, q, qlen, mql, ix.suffix(mid), ul < ur ? ul : ur);
+        if (c.cmp >= 0) { ulo = mid + 1; ul = c.lcp; }
+        else { uhi = mid; ur = c.lcp; }
+    }
+    if (ulo > b.first) { lo_out = b.first; hi_out = ulo; }
 }
 
 // byte histogram of the text (the table alphabet is chosen from it)
@@ -133,55 +211,59 @@ __global__ __launch_bounds__(256) void k_search_batch(SearchIndex ix, const uint
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
-    const uint8_t* q = queries + qoff[i];
-    const uint32_t qlen = (uint32_t)(qoff[i + 1] - qoff[i]);
-    // lower bound: the first rank whose suffix is not below the query; remembers the lowest rank seen above it
-    uint64_t lo = 0, hi = ix.s, above = ix.s;
-    uint32_t l = 0, r = 0, r_above = 0;
-    if (ix.ptab && qlen >= ix.pk && (mql == 0 || mql >= ix.pk)) {
-        // the suffixes that start with the query's first pk symbols are one rank range, looked up instead of searched;
-        // symbols outside the table alphabet take the whole array
-        uint64_t code = 0;
-        bool ok = true;
-        for (uint32_t k = 0; k < ix.pk; k++) {
-            const uint32_t c = ix.pcode[q[k]];
-            ok = ok && c != 0xFFu;
-            code = code * ix.pradix + (c & 0x7Fu);
-        }
-        if (ok) {
-            const uint2 e = ix.ptab[code];
-            if (e.x == 0xFFFFFFFFu) { lo_out[i] = 0; hi_out[i] = 0; return; }
-            lo = e.x; hi = above = ~e.y;
-            l = r = r_above = ix.pk;
-        }
-    }
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        const SearchCmp c = search_compare(ix, q, qlen, mql, ix.suffix(mid), l < r ? l : r);
-        if (c.cmp > 0) { lo = mid + 1; l = c.lcp; }
-        else {
-            hi = mid; r = c.lcp;
-            if (c.cmp < 0) { above = mid; r_above = c.lcp; }
-        }
-    }
-    const uint64_t first = lo;
-    // upper bound inside [first, above): the first rank whose suffix is above the query
-    uint64_t ulo = first, uhi = above;
-    uint32_t ul = l, ur = r_above;          // l: symbols shared with the suffix just below `first` (or with the whole table range)
-    while (ulo < uhi) {
-        const uint64_t mid = ulo + (uhi - ulo) / 2;
-        const SearchCmp c = search_compare(ix, q, qlen, mql, ix.suffix(mid), ul < ur ? ul : ur);
-        if (c.cmp >= 0) { ulo = mid + 1; ul = c.lcp; }
-        else { uhi = mid; ur = c.lcp; }
-    }
-    const bool found = ulo > first;
-    lo_out[i] = found ? first : 0;
-    hi_out[i] = found ? ulo : 0;
+    uint64_t lo, hi;
+    search_range(ix, queries + qoff[i], (uint32_t)(qoff[i + 1] - qoff[i]), mql, lo, hi);
+    lo_out[i] = lo;
+    hi_out[i] = hi;
 }
 
 // ---- locate: the positions behind the rank ranges ----------------------------------------------------------------
 // counts (capped) -> exclusive scan in three small kernels -> one lane per output position
 static constexpr int LOC_BLK = 2048;       // counts per workgroup of the scan (256 lanes x 8)
+// k_locate_scan scans 1024 sums in one launch: the kernels that walk a whole batch with a scan of their own (SMEMs, MEMs)
+// run this many workgroups, workgroup b over items [b * chunk, (b + 1) * chunk) in tiles of LOC_BLK (8 per lane)
+static constexpr uint32_t SCAN_WGS = 1024;
+__device__ __forceinline__ uint64_t scan_chunk(uint64_t total)
+{
+    const uint64_t c = (total + SCAN_WGS - 1) / SCAN_WGS;
+    return (c + LOC_BLK - 1) / LOC_BLK * LOC_BLK;
+}
+
+// the last i in [a, b) with arr[i] <= v (arr ascending, arr[a] <= v): the slice of an exclusive scan that holds item v
+__device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ arr, uint64_t a, uint64_t b, uint64_t v)
+{
+    while (b - a > 1) { const uint64_t m = a + (b - a) / 2; if (arr[m] <= v) a = m; else b = m; }
+    return a;
+}
+
+// exclusive scan of N per-lane values over the 256 lanes of a workgroup (v: in place), tot: the workgroup totals;
+// s_w: 4 * N words of LDS, free again on return
+template <int N>
+__device__ __forceinline__ void wg_scan(uint64_t (&v)[N], uint64_t (&tot)[N], uint64_t* s_w)
+{
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t inc[N];
+#pragma unroll
+    for (int n = 0; n < N; n++) inc[n] = v[n];
+    for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+        for (int n = 0; n < N; n++) { const uint64_t u = __shfl_up(inc[n], o); if (lane >= (uint32_t)o) inc[n] += u; }
+    }
+    if (lane == 63) {
+#pragma unroll
+        for (int n = 0; n < N; n++) s_w[4 * n + w] = inc[n];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < N; n++) { inc[n] -= v[n]; v[n] = 0; tot[n] = 0; }
+    for (uint32_t k = 0; k < 4; k++) {
+#pragma unroll
+        for (int n = 0; n < N; n++) { if (k < w) v[n] += s_w[4 * n + k]; tot[n] += s_w[4 * n + k]; }
+    }
+    __syncthreads();                                   // (s_w is reused by the next tile)
+#pragma unroll
+    for (int n = 0; n < N; n++) v[n] += inc[n];
+}
 
 __global__ __launch_bounds__(256) void k_locate_counts(const uint64_t* __restrict__ lo, const uint64_t* __restrict__ hi, uint64_t nq,
                                                        uint64_t max_hits, uint64_t* __restrict__ off, uint64_t* __restrict__ blocksum)
@@ -194,14 +276,10 @@ __global__ __launch_bounds__(256) void k_locate_counts(const uint64_t* __restric
         if (max_hits && v > max_hits) v = max_hits;
         c[k] = sum; sum += v;                                      // exclusive inside the lane
     }
-    uint64_t incl = sum;
-    for (int o = 1; o < 64; o <<= 1) { const uint64_t v = __shfl_up(incl, o); if ((threadIdx.x & 63) >= (unsigned)o) incl += v; }
-    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint64_t base = incl - sum;
-    for (unsigned w = 0; w < (threadIdx.x >> 6); w++) base += s_w[w];
-    for (int k = 0; k < 8; k++) if (i0 + k < nq) off[i0 + k] = base + c[k];
-    if (threadIdx.x == 255) blocksum[blockIdx.x] = base + sum;
+    uint64_t base[1] = {sum}, tot[1];
+    wg_scan(base, tot, s_w);
+    for (int k = 0; k < 8; k++) if (i0 + k < nq) off[i0 + k] = base[0] + c[k];
+    if (threadIdx.x == 0) blocksum[blockIdx.x] = tot[0];
 }
 
 __global__ __launch_bounds__(1024) void k_locate_scan(uint64_t* __restrict__ blocksum, uint64_t nblk, uint64_t* __restrict__ total)
@@ -237,8 +315,7 @@ __global__ __launch_bounds__(256) void k_locate_gather(SearchIndex ix, const uin
 {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= total) return;
-    uint64_t a = 0, b = nq;                                        // the query whose slice holds output j: last off <= j
-    while (b - a > 1) { const uint64_t m = a + (b - a) / 2; if (off[m] <= j) a = m; else b = m; }
+    const uint64_t a = last_le(off, 0, nq, j);                     // the query whose slice holds output j
     const uint64_t p = ix.suffix(lo[a] + (j - off[a]));
     if (positions64) positions64[j] = p; else positions[j] = (uint32_t)p;
 }
@@ -332,6 +409,53 @@ uint64_t effective_mql(const sufr_hip_index* ix, int has_mql, uint64_t mql)
     if (ix->ix.maskpos) return has_mql ? mql : 0;
     if (ix->built_mql > 0 && has_mql) return ix->built_mql < mql ? ix->built_mql : mql;
     return has_mql ? mql : ix->built_mql;
+}
+
+// what every query entry point checks before it touches the device; `masked`: what a seed-mask index does not support
+// (nullptr: it does)
+int query_check(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const char* masked = nullptr)
+{
+    if (ix->device != ctx->pl.device) { ctx->pl.set_error("the index lives on another device"); return SUFR_HIP_E_INVALID; }
+    if (masked && ix->ix.maskpos) { ctx->pl.set_error(std::string(masked) + " of a seed-mask index are not supported"); return SUFR_HIP_E_UNSUPPORTED; }
+    if (hipSetDevice(ctx->pl.device) != hipSuccess) { ctx->pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
+    return 0;
+}
+
+// n totals of the device to the host, complete on return (one synchronisation); `what` is the error text
+int read_totals(sufr::Pipeline& pl, const void* d_src, int n, unsigned long long* dst, const char* what)
+{
+    if (hipMemcpyAsync(dst, d_src, (size_t)n * 8, hipMemcpyDeviceToHost, pl.stream) == hipSuccess &&
+        hipStreamSynchronize(pl.stream) == hipSuccess) return 0;
+    pl.set_error(what);
+    return SUFR_HIP_E_HIP;
+}
+
+// The host-pointer entry points stage their batch in one allocation, queries | offsets (at o_at) | what the caller lays
+// out behind them, and call their *_device twin on it.  `what` names the batch in the error texts.
+int stage_batch(sufr_hip_ctx* ctx, const char* what, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint64_t o_at,
+                uint64_t bytes, uint8_t** d)
+{
+    if (hipMalloc((void**)d, bytes) != hipSuccess) {
+        *d = nullptr;
+        ctx->pl.set_error(std::string("hipMalloc of the ") + what + " batch failed");
+        return SUFR_HIP_E_NOMEM;
+    }
+    if ((offsets[nq] && hipMemcpyAsync(*d, queries, offsets[nq], hipMemcpyHostToDevice, ctx->pl.stream) != hipSuccess) ||
+        hipMemcpyAsync(*d + o_at, offsets, (nq + 1) * 8, hipMemcpyHostToDevice, ctx->pl.stream) != hipSuccess) return SUFR_HIP_E_HIP;
+    return 0;
+}
+
+struct StageBack { void* dst; uint64_t at, bytes; };             // to the host: `bytes` from offset `at` of the allocation
+
+// rc: what staging and the device call gave; when that is 0 the results are copied back, complete on return
+int unstage_batch(sufr_hip_ctx* ctx, const char* what, uint8_t* d, int rc, std::initializer_list<StageBack> back)
+{
+    for (const StageBack& b : back)
+        if (!rc && b.bytes && hipMemcpyAsync(b.dst, d + b.at, b.bytes, hipMemcpyDeviceToHost, ctx->pl.stream) != hipSuccess) rc = SUFR_HIP_E_HIP;
+    if (!rc && hipStreamSynchronize(ctx->pl.stream) != hipSuccess) rc = SUFR_HIP_E_HIP;
+    if (rc == SUFR_HIP_E_HIP && ctx->pl.err.empty()) ctx->pl.set_error(std::string("copying the ") + what + " batch failed");
+    (void)hipFree(d);
+    return rc;
 }
 
 }  // namespace
@@ -435,8 +559,7 @@ int sufr_hip_search_batch_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, co
     if (!ctx || !ix || (num_queries && (!d_queries || !d_offsets || !d_rank_lo || !d_rank_hi))) return SUFR_HIP_E_INVALID;
     ctx->pl.err.clear();
     if (!num_queries) return 0;
-    if (ix->device != ctx->pl.device) { ctx->pl.set_error("the index lives on another device"); return SUFR_HIP_E_INVALID; }
-    if (hipSetDevice(ctx->pl.device) != hipSuccess) { ctx->pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
+    if (const int rc = query_check(ctx, ix)) return rc;
     const uint64_t blocks = (num_queries + 255) / 256;
     if (blocks > 0x7fffffffull) { ctx->pl.set_error("too many queries in one batch"); return SUFR_HIP_E_INVALID; }
     sufr::k_search_batch<<<(unsigned)blocks, 256, 0, ctx->pl.stream>>>(ix->ix, (const uint8_t*)d_queries, (const uint64_t*)d_offsets,
@@ -455,9 +578,8 @@ int sufr_hip_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, co
     sufr::Pipeline& pl = ctx->pl;
     pl.err.clear();
     if (total_out) *total_out = 0;
-    if (ix->device != pl.device) { pl.set_error("the index lives on another device"); return SUFR_HIP_E_INVALID; }
-    if (hipSetDevice(pl.device) != hipSuccess) { pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
     int rc;
+    if ((rc = query_check(ctx, ix))) return rc;
     const uint64_t nblk = (num_queries + sufr::LOC_BLK - 1) / sufr::LOC_BLK;
     if ((rc = pl.ensure(pl.scalars, sufr::Pipeline::SC_N * 8)) || (rc = pl.ensure(pl.partials, (size_t)(nblk + 1) * 8))) return rc;
     unsigned long long total = 0;
@@ -469,8 +591,7 @@ int sufr_hip_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, co
                            (uint64_t*)pl.sc(sufr::Pipeline::SC_TOTAL));
         hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((num_queries + 256) / 256)), dim3(256), 0, pl.stream, off, num_queries,
                            (const uint64_t*)pl.partials.p, (const uint64_t*)pl.sc(sufr::Pipeline::SC_TOTAL));
-        if (hipMemcpyAsync(&total, pl.sc(sufr::Pipeline::SC_TOTAL), 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-            hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("locate: counting the matches failed"); return SUFR_HIP_E_HIP; }
+        if ((rc = read_totals(pl, pl.sc(sufr::Pipeline::SC_TOTAL), 1, &total, "locate: counting the matches failed"))) return rc;
     } else if (hipMemsetAsync(d_offsets, 0, 8, pl.stream) != hipSuccess) { pl.set_error("memset failed"); return SUFR_HIP_E_HIP; }
     if (total_out) *total_out = total;
     if (total > cap) {
@@ -497,21 +618,13 @@ int sufr_hip_search_batch(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uin
     ctx->pl.err.clear();
     if (!num_queries) return 0;
     if (hipSetDevice(ctx->pl.device) != hipSuccess) { ctx->pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
-    const uint64_t qbytes = offsets[num_queries], obytes = (num_queries + 1) * 8, rbytes = num_queries * 8;
-    uint8_t* d = nullptr;
-    const uint64_t o_at = (qbytes + 7) / 8 * 8, lo_at = o_at + obytes, hi_at = lo_at + rbytes;
-    if (hipMalloc((void**)&d, hi_at + rbytes) != hipSuccess) { ctx->pl.set_error("hipMalloc of the query batch failed"); return SUFR_HIP_E_NOMEM; }
-    int rc = 0;
-    hipStream_t st = ctx->pl.stream;
-    if ((qbytes && hipMemcpyAsync(d, queries, qbytes, hipMemcpyHostToDevice, st) != hipSuccess) ||
-        hipMemcpyAsync(d + o_at, offsets, obytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = SUFR_HIP_E_HIP;
+    // one allocation: queries | offsets | rank_lo | rank_hi
+    const uint64_t obytes = (num_queries + 1) * 8, rbytes = num_queries * 8;
+    const uint64_t o_at = (offsets[num_queries] + 7) / 8 * 8, lo_at = o_at + obytes, hi_at = lo_at + rbytes;
+    uint8_t* d;
+    int rc = stage_batch(ctx, "query", queries, offsets, num_queries, o_at, hi_at + rbytes, &d);
     if (!rc) rc = sufr_hip_search_batch_device(ctx, ix, d, d + o_at, num_queries, has_max_query_len, max_query_len, d + lo_at, d + hi_at);
-    if (!rc && (hipMemcpyAsync(rank_lo, d + lo_at, rbytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(rank_hi, d + hi_at, rbytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)) rc = SUFR_HIP_E_HIP;
-    if (rc == SUFR_HIP_E_HIP && ctx->pl.err.empty()) ctx->pl.set_error("copying the query batch failed");
-    (void)hipFree(d);
-    return rc;
+    return unstage_batch(ctx, "query", d, rc, {{rank_lo, lo_at, rbytes}, {rank_hi, hi_at, rbytes}});
 }
 
 }  // extern "C"

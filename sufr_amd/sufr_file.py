@@ -121,6 +121,34 @@ class SufrMetadata:                    # types.rs:587-626
     seed_mask: Optional[str]           # ... or Mask(seed mask)
 
 
+def _sized_to_fit(cap: Optional[int], guess: int, alloc, call, error):
+    """The record arrays of an SMEM / MEM call, cut to the total it reports.  alloc(c) makes the outputs for c records and
+    call(c, outputs, total) returns the library's code.  With a `cap` the call is made once; without one it starts at
+    `guess` and, told -5 (capacity), once more with the total.  error(rc, total, c) makes the SufrHipError of a failure,
+    which carries the total in `.total`."""
+    c = cap if cap is not None else guess
+    while True:
+        out = alloc(max(c, 1))
+        total = C.c_uint64(0)
+        rc = call(c, out, total)
+        if rc == -5 and cap is None:
+            c = total.value
+            continue
+        if rc != 0:
+            err = error(rc, total.value, c)
+            err.total = total.value
+            raise err
+        return tuple(a[:total.value] for a in out)
+
+
+def _file_error(fn: str, noun: str):
+    def error(rc, total, c):
+        msg = {-5: f"{total} {noun}, room for {c}", -6: "files built with a seed mask are not supported",
+               -1: "invalid argument (min_len must be at least 1)"}.get(rc, "failed")
+        return SufrHipError(rc, f"{fn}: " + msg)
+    return error
+
+
 def _as_bytes(q) -> bytes:
     return q.encode() if isinstance(q, str) else bytes(q)
 
@@ -280,22 +308,11 @@ class SufrFile:
         qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nq = len(offsets) - 1
-        c = cap if cap is not None else int(offsets[-1] - offsets[0]) // 8 + 16
-        while True:
-            out = [np.zeros(max(c, 1), dtype=d) for d in _SMEM_DTYPES]
-            total = C.c_uint64(0)
-            rc = lib().sufr_file_smems(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, min_len, c,
-                                       *[a.ctypes.data for a in out], C.byref(total), threads)
-            if rc == -5 and cap is None:
-                c = total.value
-                continue
-            if rc != 0:
-                msg = {-5: f"{total.value} SMEMs, room for {c}", -6: "files built with a seed mask are not supported",
-                       -1: "invalid argument (min_len must be at least 1)"}.get(rc, "failed")
-                err = SufrHipError(rc, "sufr_file_smems: " + msg)
-                err.total = total.value
-                raise err
-            return tuple(a[:total.value] for a in out)
+        return _sized_to_fit(
+            cap, int(offsets[-1] - offsets[0]) // 8 + 16, lambda c: [np.zeros(c, dtype=d) for d in _SMEM_DTYPES],
+            lambda c, out, total: lib().sufr_file_smems(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, min_len, c,
+                                                        *[a.ctypes.data for a in out], C.byref(total), threads),
+            _file_error("sufr_file_smems", "SMEMs"))
 
     def smems(self, queries: Sequence, min_len: int = 20, max_hits: int = 0, threads: int = 0) -> List[List[SmemHit]]:
         """The SMEMs of every query (at least `min_len` long) with their rank ranges and up to `max_hits` positions each
@@ -318,22 +335,12 @@ class SufrFile:
         qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nq = len(offsets) - 1
-        c = cap if cap is not None else int(offsets[-1] - offsets[0]) // 4 + 16
-        while True:
-            out = [np.zeros(max(c, 1), dtype=d) for d in _MEM_DTYPES]
-            total = C.c_uint64(0)
-            rc = lib().sufr_file_mems(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, min_len, max_occ,
-                                      MEM_BOTH_STRANDS if both_strands else 0, c, *[a.ctypes.data for a in out], C.byref(total), threads)
-            if rc == -5 and cap is None:
-                c = total.value
-                continue
-            if rc != 0:
-                msg = {-5: f"{total.value} MEMs, room for {c}", -6: "files built with a seed mask are not supported",
-                       -1: "invalid argument (min_len must be at least 1)"}.get(rc, "failed")
-                err = SufrHipError(rc, "sufr_file_mems: " + msg)
-                err.total = total.value
-                raise err
-            return tuple(a[:total.value] for a in out)
+        flags = MEM_BOTH_STRANDS if both_strands else 0
+        return _sized_to_fit(
+            cap, int(offsets[-1] - offsets[0]) // 4 + 16, lambda c: [np.zeros(c, dtype=d) for d in _MEM_DTYPES],
+            lambda c, out, total: lib().sufr_file_mems(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, min_len, max_occ, flags, c,
+                                                       *[a.ctypes.data for a in out], C.byref(total), threads),
+            _file_error("sufr_file_mems", "MEMs"))
 
     def mems(self, queries: Sequence, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
              threads: int = 0) -> List[List[MemHit]]:
@@ -543,14 +550,27 @@ class DeviceIndex:
                 for i, q in enumerate(queries)]
 
     # -- matching statistics and SMEMs (include/sufr_match.h) ---------------------------------------------------------
+    @staticmethod
+    def _device_bytes(qbytes):
+        """The query bytes as the library takes them: a batch of empty queries still needs a device address."""
+        import torch
+        return qbytes if qbytes.numel() else torch.zeros(1, dtype=torch.uint8, device=qbytes.device)
+
+    def _device_records(self, cap, guess, device, dtypes, call):
+        """_sized_to_fit for torch outputs on `device`; the error text is the context's, the records are complete on return."""
+        import torch
+        out = _sized_to_fit(cap, guess, lambda c: [torch.empty(c, dtype=d, device=device) for d in dtypes], call,
+                            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
+        self.ctx.synchronize()
+        return out
+
     def matching_statistics_device(self, qbytes, offsets, wait: bool = True):
         """ms of a packed batch of torch CUDA tensors (uint8 bytes, int64 offsets): an int32 tensor (u32 values) indexed like
         the bytes.  wait=False: call ctx.synchronize() before reading it."""
         import torch
         torch.cuda.current_stream(qbytes.device).synchronize()
         nq = offsets.numel() - 1
-        if qbytes.numel() == 0:                               # (a batch of empty queries still needs a device address)
-            qbytes = torch.zeros(1, dtype=torch.uint8, device=qbytes.device)
+        qbytes = self._device_bytes(qbytes)
         ms = torch.zeros(max(int(offsets[-1]) if nq >= 0 and offsets.numel() else 0, 1), dtype=torch.int32, device=qbytes.device)
         self.ctx.check(lib().sufr_hip_matching_stats_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(),
                                                             max(nq, 0), ms.data_ptr()))
@@ -574,26 +594,15 @@ class DeviceIndex:
         torch.cuda.current_stream(qbytes.device).synchronize()
         nq = offsets.numel() - 1
         dev = qbytes.device
-        if qbytes.numel() == 0:                               # (a batch of empty queries still needs a device address)
-            qbytes = torch.zeros(1, dtype=torch.uint8, device=dev)
+        qbytes = self._device_bytes(qbytes)
         nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
         ms = torch.empty(max(int(offsets[-1]) if nq > 0 else 0, 1), dtype=torch.int32, device=dev)
-        c = cap if cap is not None else nbytes // 8 + 16
-        while True:
-            out = [torch.empty(max(c, 1), dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.int32, torch.int64, torch.int64)]
-            total = C.c_uint64(0)
-            rc = lib().sufr_hip_smems_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0), min_len,
-                                             ms.data_ptr(), c, *[t.data_ptr() for t in out], C.byref(total))
-            if rc == -5 and cap is None:
-                c = total.value
-                continue
-            if rc != 0:
-                err = SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode())
-                err.total = total.value
-                raise err
-            self.ctx.synchronize()
-            self.last_ms = ms
-            return tuple(t[:total.value] for t in out)
+        out = self._device_records(
+            cap, nbytes // 8 + 16, dev, (torch.int64, torch.int32, torch.int32, torch.int64, torch.int64),
+            lambda c, out, total: lib().sufr_hip_smems_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
+                                                              min_len, ms.data_ptr(), c, *[t.data_ptr() for t in out], C.byref(total)))
+        self.last_ms = ms
+        return out
 
     def smems(self, queries: Sequence, min_len: int = 20, max_hits: int = 0) -> List[List[SmemHit]]:
         """The SMEMs of every query with their rank ranges and up to `max_hits` positions (0: all), searched and gathered
@@ -623,25 +632,13 @@ class DeviceIndex:
         torch.cuda.current_stream(qbytes.device).synchronize()
         nq = offsets.numel() - 1
         dev = qbytes.device
-        if qbytes.numel() == 0:                               # (a batch of empty queries still needs a device address)
-            qbytes = torch.zeros(1, dtype=torch.uint8, device=dev)
+        qbytes = self._device_bytes(qbytes)
         nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
-        c = cap if cap is not None else nbytes // 4 + 16
-        while True:
-            out = [torch.empty(max(c, 1), dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.uint8, torch.int32, torch.int64)]
-            total = C.c_uint64(0)
-            rc = lib().sufr_hip_mems_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0), min_len,
-                                            max_occ, MEM_BOTH_STRANDS if both_strands else 0, c, *[t.data_ptr() for t in out],
-                                            C.byref(total))
-            if rc == -5 and cap is None:
-                c = total.value
-                continue
-            if rc != 0:
-                err = SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode())
-                err.total = total.value
-                raise err
-            self.ctx.synchronize()
-            return tuple(t[:total.value] for t in out)
+        flags = MEM_BOTH_STRANDS if both_strands else 0
+        return self._device_records(
+            cap, nbytes // 4 + 16, dev, (torch.int64, torch.int32, torch.uint8, torch.int32, torch.int64),
+            lambda c, out, total: lib().sufr_hip_mems_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
+                                                             min_len, max_occ, flags, c, *[t.data_ptr() for t in out], C.byref(total)))
 
     def mems(self, queries: Sequence, min_len: int = 20, max_occ: int = 0, both_strands: bool = False) -> List[List[MemHit]]:
         """The MEMs of every query (SufrFile.mems), found on the device."""
