@@ -101,6 +101,9 @@ MATCH_EXPORTS = [
 # every symbol include/sufr_mem.h declares
 MEM_EXPORTS = ["sufr_file_mems", "sufr_hip_mems_device", "sufr_hip_mems"]
 MEM_BOTH_STRANDS = 0x1
+# every symbol include/sufr_approx.h declares
+APPROX_EXPORTS = ["sufr_file_approx", "sufr_hip_approx_device", "sufr_hip_approx"]
+APPROX_BOTH_STRANDS = 0x1
 
 
 class FileMeta(C.Structure):
@@ -226,6 +229,13 @@ def lib() -> C.CDLL:
     L.sufr_hip_mems_device.restype = C.c_int
     L.sufr_hip_mems.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.sufr_hip_mems.restype = C.c_int
+    # include/sufr_approx.h
+    L.sufr_file_approx.argtypes = [vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64), C.c_int]
+    L.sufr_file_approx.restype = C.c_int
+    L.sufr_hip_approx_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_approx_device.restype = C.c_int
+    L.sufr_hip_approx.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_approx.restype = C.c_int
     _lib = L
     return L
 

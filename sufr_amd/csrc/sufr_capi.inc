@@ -7,7 +7,7 @@ struct sufr_hip_ctx {
     uint64_t array_budget = 0;        // sufr_hip_set_array_budget: device bytes the SA + LCP of a windowed create may take at once (0: no limit set)
     sufr::DevBuf wtext, wsa, wlcp, wblk;
     sufr::DevBuf mtmp, mpoff, mbytes;  // SMEM scan sums, slice offsets and packed slices (sufr_match.inc)
-    sufr::DevBuf xq, xoff, xlo, xhi, xcand, xsum;  // MEMs (sufr_mem.inc): doubled batch, rank ranges, candidate starts, scan sums
+    sufr::DevBuf xq, xoff, xlo, xhi, xcand, xsum;  // MEMs, k-mismatch (sufr_mem.inc, sufr_approx.inc): doubled batch, rank ranges, candidate starts, scan sums
     bool wide(uint64_t n) const { return n >= sufr::SUFR_MAX_TEXT_LEN || (wide_window && n > wide_window); }
 };
 

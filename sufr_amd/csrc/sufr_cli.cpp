@@ -21,6 +21,7 @@
 #include "../../include/sufr_query.h"
 #include "../../include/sufr_match.h"
 #include "../../include/sufr_mem.h"
+#include "../../include/sufr_approx.h"
 
 #include <algorithm>
 #include <fstream>
@@ -63,7 +64,11 @@ int usage(FILE* f)
             "                                       name  strand(+/-)  offset  length  seq:pos\n"
             "                                       [-k|--min-len N (20)] [--max-occ N (0: no limit)] [-b|--both-strands]\n"
             "                                       [-a|--abs] [-q|--reads FASTA/FASTQ] [-o OUT]\n"
-            "  count / locate / extract / match / mems take --device <ID>: the queries are searched as one batch on that GPU\n\n"
+            "  approx|ap    <SUFR> [QUERY]...       Occurrences of the queries with at most N mismatches: one line per window,\n"
+            "                                       name  strand(+/-)  seq:pos  mismatches\n"
+            "                                       [-d|--mismatches N (2)] [--max-occ N (0: no limit)] [-b|--both-strands]\n"
+            "                                       [-a|--abs] [-q|--reads FASTA/FASTQ] [-o OUT]\n"
+            "  count / locate / extract / match / mems / approx take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
             "  -l, --log <LOG>           Log level [possible values: info, debug]\n"
@@ -108,8 +113,9 @@ struct QueryArgs {
     int threads = 0;                            // -t/--threads (global option, sufr/src/lib.rs:29-46): host search workers
     uint64_t min_len = 20, max_hits = 0;        // match / mems: -k, match: -n
     std::string reads;                          // match / mems: -q FASTA / FASTQ of named queries
-    uint64_t max_occ = 0;                       // mems: --max-occ
-    bool both_strands = false;                  // mems: -b
+    uint64_t max_occ = 0;                       // mems / approx: --max-occ
+    bool both_strands = false;                  // mems / approx: -b
+    uint64_t mismatches = 2;                    // approx: -d
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -539,6 +545,58 @@ int cmd_mems(const QueryArgs& a)
     return 0;
 }
 
+// sufr approx: every window of the text within -d mismatches of a query, one line each in record order:
+// name, strand (+ / -), the window start as seq:pos (0-based) or absolute with --abs, mismatches.
+int cmd_approx(const QueryArgs& a)
+{
+    if (a.mismatches > SUFR_APPROX_MAX_MISMATCHES) { fprintf(stderr, "Error: --mismatches must be at most %u\n", SUFR_APPROX_MAX_MISMATCHES); return 1; }
+    sufr_file* f = open_or_die(a.file);
+    OutFile out;
+    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    std::vector<std::string> names, seqs;
+    if (!named_queries(a, names, seqs)) return 1;
+    std::string bytes;
+    std::vector<uint64_t> off(seqs.size() + 1, 0);
+    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
+    sufr_hip_ctx* ctx = nullptr;
+    sufr_hip_index* ix = nullptr;
+    if (a.device >= 0) {
+        ctx = sufr_hip_create(a.device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
+        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
+    }
+    const uint32_t flags = a.both_strands ? SUFR_APPROX_BOTH_STRANDS : 0;
+    // records: room for four windows per query first, the exact count when that is short
+    uint64_t cap = 4 * seqs.size() + 16, total = 0;
+    std::vector<uint64_t> qi, pos;
+    std::vector<uint8_t> st, mm;
+    for (;;) {
+        qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
+        const int rc = ix ? sufr_hip_approx(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.mismatches, a.max_occ,
+                                            flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total)
+                          : sufr_file_approx(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.mismatches, a.max_occ,
+                                             flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total, a.threads);
+        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
+        if (rc == SUFR_HIP_E_UNSUPPORTED) { fprintf(stderr, "Error: %s: approx does not support files built with a seed mask\n", a.file.c_str()); return 1; }
+        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "approx failed"); return 1; }
+        break;
+    }
+    if (ix) sufr_hip_index_free(ix);
+    if (ctx) sufr_hip_destroy(ctx);
+    for (uint64_t t = 0; t < total; t++) {
+        const char* name = names[qi[t]].c_str();
+        const char sgn = st[t] ? '-' : '+';
+        if (a.abs) fprintf(out.f, "%s\t%c\t%llu\t%u\n", name, sgn, (unsigned long long)pos[t], (unsigned)mm[t]);
+        else {
+            const uint64_t i = sufr_file_sequence_of(f, pos[t]);
+            fprintf(out.f, "%s\t%c\t%s:%llu\t%u\n", name, sgn, sufr_file_sequence_name(f, i),
+                    (unsigned long long)(pos[t] - sufr_file_sequence_start(f, i)), (unsigned)mm[t]);
+        }
+    }
+    sufr_file_close(f);
+    return 0;
+}
+
 int run_query(const std::string& cmd, int argc, char** argv, int first, int threads)
 {
     QueryArgs a;
@@ -549,8 +607,9 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         return argv[++i];
     };
     const bool is_list = cmd == "list", is_extract = cmd == "extract", is_locate = cmd == "locate", is_sum = cmd == "summarize";
+    const bool is_approx = cmd == "approx";
     const bool is_mems = cmd == "mems";
-    const bool is_match = cmd == "match" || is_mems;
+    const bool is_match = cmd == "match" || is_mems || is_approx;
     for (int i = first; i < argc; i++) {
         const std::string s = argv[i];
         if (s == "-h" || s == "--help") { usage(stdout); return 0; }
@@ -560,10 +619,11 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         else if (!is_sum && (s == "-v" || s == "--very-low-memory")) {}
         else if (!is_list && !is_sum && s == "--device") a.device = atoi(need(i, "--device"));
         else if ((is_locate || is_match) && (s == "-a" || s == "--abs")) a.abs = true;
-        else if (is_match && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
-        else if (is_mems && s == "--max-occ") a.max_occ = strtoull(need(i, "--max-occ"), nullptr, 10);
-        else if (is_mems && (s == "-b" || s == "--both-strands")) a.both_strands = true;
-        else if (is_match && !is_mems && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
+        else if (is_match && !is_approx && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
+        else if ((is_mems || is_approx) && s == "--max-occ") a.max_occ = strtoull(need(i, "--max-occ"), nullptr, 10);
+        else if ((is_mems || is_approx) && (s == "-b" || s == "--both-strands")) a.both_strands = true;
+        else if (is_approx && (s == "-d" || s == "--mismatches")) a.mismatches = strtoull(need(i, "-d"), nullptr, 10);
+        else if (is_match && !is_mems && !is_approx && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
         else if (is_match && (s == "-q" || s == "--reads")) a.reads = need(i, "-q");
         else if (is_extract && (s == "-p" || s == "--prefix-len")) { a.has_prefix = true; a.prefix_len = strtoull(need(i, "-p"), nullptr, 10); }
         else if (is_extract && (s == "-s" || s == "--suffix-len")) { a.has_suffix = true; a.suffix_len = strtoull(need(i, "-s"), nullptr, 10); }
@@ -589,6 +649,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
+    if (is_approx) return cmd_approx(a);
     if (is_mems) return cmd_mems(a);
     if (is_match) return cmd_match(a);
     if (is_extract) return cmd_extract(a);
@@ -648,6 +709,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "locate" || s == "lo")) return run_query("locate", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "match" || s == "ma")) return run_query("match", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "mems" || s == "me")) return run_query("mems", argc, argv, i + 1, threads);
+        else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "list" || s == "ls")) return run_query("list", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "summarize" || s == "su")) return run_query("summarize", argc, argv, i + 1, threads);

@@ -16,6 +16,7 @@
 #include "../../include/sufr_query.h"
 #include "../../include/sufr_match.h"
 #include "../../include/sufr_mem.h"
+#include "../../include/sufr_approx.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -102,5 +103,11 @@ int sufr_hip_mems_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, 
                          uint64_t, void*, void*, void*, void*, void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 int sufr_hip_mems(sufr_hip_ctx* ctx, const sufr_hip_index*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint32_t, uint64_t,
                   uint64_t*, uint32_t*, uint8_t*, uint32_t*, uint64_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+
+// ---- include/sufr_approx.h: the device side (the host side is sufr_query.cpp) ---------------------------------------
+int sufr_hip_approx_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const void*, uint64_t, uint32_t, uint64_t, uint32_t,
+                           uint64_t, void*, void*, void*, void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_approx(sufr_hip_ctx* ctx, const sufr_hip_index*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint32_t, uint64_t,
+                    uint64_t*, uint8_t*, uint64_t*, uint8_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 
 }  // extern "C"

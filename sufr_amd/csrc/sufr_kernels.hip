@@ -2994,3 +2994,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_match.inc"
 #include "../../include/sufr_mem.h"
 #include "sufr_mem.inc"
+#include "../../include/sufr_approx.h"
+#include "sufr_approx.inc"

@@ -21,6 +21,7 @@
 #include "../../include/sufr_query.h"
 #include "../../include/sufr_match.h"
 #include "../../include/sufr_mem.h"
+#include "../../include/sufr_approx.h"
 
 struct sufr_file {
     std::string path;
@@ -500,6 +501,112 @@ int sufr_file_mems(const sufr_file* f, const uint8_t* queries, const uint64_t* o
     uint64_t t = 0;
     for (const auto& v : recs)
         for (const MemRec& x : v) { query[t] = x.query; qoff[t] = x.qoff; strand[t] = x.strand; len[t] = x.len; position[t] = x.pos; t++; }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- k-mismatch search (include/sufr_approx.h) --------------------------------------------------
+namespace {
+
+struct ApproxRec { uint64_t query; uint8_t strand; uint64_t pos; uint8_t mism; };
+
+// the batch in record order, offsets from 0: query i, then (both strands) its reverse complement as query 2i + 1, in `dbl`;
+// one strand: the caller's bytes in place.  Returns the first byte of query 0.
+const uint8_t* strand_batch(const uint8_t* queries, const uint64_t* offsets, uint64_t nq, bool both, std::vector<uint8_t>& dbl,
+                            std::vector<uint64_t>& off)
+{
+    const uint64_t g0 = offsets[0], nb = offsets[nq] - g0;
+    const uint8_t* qb = queries + g0;
+    if (!both) {
+        off.resize(nq + 1);
+        for (uint64_t i = 0; i <= nq; i++) off[i] = offsets[i] - g0;
+        return qb;
+    }
+    dbl.resize(2 * nb);
+    off.resize(2 * nq + 1);
+    for (uint64_t i = 0; i < nq; i++) {
+        const uint64_t a = offsets[i] - g0, b = offsets[i + 1] - g0;
+        off[2 * i] = 2 * a; off[2 * i + 1] = a + b;
+        memcpy(dbl.data() + 2 * a, qb + a, (size_t)(b - a));
+        for (uint64_t t = 0; t < b - a; t++) dbl[a + b + t] = revcomp_byte(qb[b - 1 - t]);
+    }
+    off[2 * nq] = 2 * nb;
+    return dbl.data();
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_approx(const sufr_file* f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t max_mismatches,
+                     uint64_t max_occ, uint32_t flags, uint64_t cap, uint64_t* query, uint8_t* strand, uint64_t* position,
+                     uint8_t* mismatches, uint64_t* total_out, int threads)
+{
+    if (total_out) *total_out = 0;
+    if (const int rc = match_args(f, queries, offsets, nq)) return rc;
+    if (max_mismatches > SUFR_APPROX_MAX_MISMATCHES) return SUFR_HIP_E_INVALID;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    const bool both = (flags & SUFR_APPROX_BOTH_STRANDS) != 0;
+    std::vector<uint8_t> dbl;
+    std::vector<uint64_t> off;
+    const uint8_t* qb = strand_batch(queries, offsets, nq, both, dbl, off);
+    const uint64_t nq2 = off.size() - 1;
+    const std::vector<uint64_t>& bits = indexed_bits(*f);
+    const uint64_t n = f->meta.text_len, L = f->meta.max_query_len;
+    const uint32_t d = max_mismatches, np = d + 1;
+    const uint8_t* text = f->text;
+    // workers over chunks of queries; chunk c keeps its records, the chunks are concatenated in order
+    const uint64_t chunk = 16, nchunks = (nq2 + chunk - 1) / chunk;
+    std::vector<std::vector<ApproxRec>> recs(nchunks);
+    parallel_chunks(nq2, chunk, threads, [&](uint64_t b, uint64_t e) {
+        std::vector<ApproxRec>& out = recs[b / chunk];
+        uint64_t o[SUFR_APPROX_MAX_MISMATCHES + 2], lo[SUFR_APPROX_MAX_MISMATCHES + 1], hi[SUFR_APPROX_MAX_MISMATCHES + 1];
+        bool live[SUFR_APPROX_MAX_MISMATCHES + 1];
+        for (uint64_t a = b; a < e; a++) {
+            const uint8_t* Q = qb + off[a];
+            const uint64_t m = off[a + 1] - off[a];
+            if (m < np || m > n) continue;
+            for (uint32_t i = 0; i <= np; i++) o[i] = (uint64_t)i * m / np;
+            for (uint32_t i = 0; i < np; i++) {                              // the rank range of every seed
+                const uint64_t len = o[i + 1] - o[i], kk = L > 0 && L < len ? L : len;
+                lo[i] = hi[i] = 0;
+                (void)sufr_file_search(f, Q + o[i], (size_t)kk, 0, 0, &lo[i], &hi[i]);
+                live[i] = !max_occ || hi[i] - lo[i] <= max_occ;
+            }
+            for (uint32_t i = 0; i < np; i++) {
+                if (!live[i]) continue;
+                const uint64_t len = o[i + 1] - o[i], kk = L > 0 && L < len ? L : len;
+                for (uint64_t r = lo[i]; r < hi[i]; r++) {
+                    const uint64_t sp = sufr_file_suffix(f, r);
+                    if (sp < o[i]) continue;                                 // the window would start before the text
+                    const uint64_t p = sp - o[i];
+                    if (p + m > n) continue;
+                    if (kk < len && memcmp(Q + o[i] + kk, text + sp + kk, (size_t)(len - kk)) != 0) continue;
+                    bool lower = false;                                      // a lower piece anchors p: it reports the window
+                    for (uint32_t j = 0; j < i && !lower; j++) {
+                        const uint64_t pj = p + o[j];
+                        lower = live[j] && (bits.empty() || (bits[pj >> 6] >> (pj & 63) & 1)) &&
+                                memcmp(Q + o[j], text + pj, (size_t)(o[j + 1] - o[j])) == 0;
+                    }
+                    if (lower) continue;
+                    uint32_t h = 0;
+                    for (uint64_t t = 0; t < m && h <= d; t++) h += Q[t] != text[p + t];
+                    if (h > d) continue;
+                    out.push_back({both ? a >> 1 : a, (uint8_t)(both ? a & 1 : 0), p, (uint8_t)h});
+                }
+            }
+        }
+    }, 4);
+    uint64_t total = 0;
+    for (const auto& v : recs) total += v.size();
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!query || !strand || !position || !mismatches) return SUFR_HIP_E_INVALID;
+    uint64_t t = 0;
+    for (const auto& v : recs)
+        for (const ApproxRec& x : v) { query[t] = x.query; strand[t] = x.strand; position[t] = x.pos; mismatches[t] = x.mism; t++; }
     return 0;
 }
 

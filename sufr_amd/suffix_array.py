@@ -9,7 +9,7 @@ from .types import SufrBuilderArgs
 
 
 class SuffixArray:
-    """After `read`, count / extract / list / locate / smems / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
+    """After `read`, count / extract / list / locate / smems / mems / approx / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
 
     def __init__(self, inner: SufrFile):
         self.inner = inner
@@ -38,6 +38,9 @@ class SuffixArray:
 
     def mems(self, queries, min_len: int = 20, max_occ: int = 0, both_strands: bool = False, threads: int = 0):
         return self.inner.mems(queries, min_len, max_occ, both_strands, threads)
+
+    def approx(self, queries, max_mismatches: int = 2, max_occ: int = 0, both_strands: bool = False, threads: int = 0):
+        return self.inner.approx(queries, max_mismatches, max_occ, both_strands, threads)
 
     def list(self, **opts):
         return self.inner.list(**opts)

@@ -5,7 +5,8 @@ count / locate / extract / list / metadata / string_at with the reference's opti
 by the C ABI of include/sufr_query.h (a mapped file, two binary searches per query).  `DeviceIndex` answers batches of
 queries on the GPU from text + suffix array resident in HBM (sufr_hip_search_batch).  Both also give the matching
 statistics and the super-maximal exact matches (SMEMs) of queries (include/sufr_match.h), and their
-maximal exact matches (MEMs) on one or both strands (include/sufr_mem.h)."""
+maximal exact matches (MEMs) on one or both strands (include/sufr_mem.h), and where they occur with
+at most d mismatches (include/sufr_approx.h)."""
 from __future__ import annotations
 
 import builtins
@@ -100,6 +101,25 @@ def _mem_hits(nq: int, recs) -> List[List[MemHit]]:
     out: List[List[MemHit]] = [[] for _ in range(nq)]
     for t in range(len(qi)):
         out[int(qi[t])].append(MemHit(int(qo[t]), int(pos[t]), int(ln[t]), int(st[t])))
+    return out
+
+
+@dataclass
+class ApproxHit:                       # one k-mismatch occurrence of a query (include/sufr_approx.h)
+    query: int
+    strand: int                        # 0: the query as given, 1: its reverse complement ...
+    position: int                      # ... differs from text[position : position + len(query)] in `mismatches` bytes
+    mismatches: int
+
+
+_APPROX_DTYPES = (np.uint64, np.uint8, np.uint64, np.uint8)                 # query, strand, position, mismatches
+
+
+def _approx_hits(nq: int, recs) -> List[List[ApproxHit]]:
+    qi, st, pos, mm = recs
+    out: List[List[ApproxHit]] = [[] for _ in range(nq)]
+    for t in range(len(qi)):
+        out[int(qi[t])].append(ApproxHit(int(qi[t]), int(st[t]), int(pos[t]), int(mm[t])))
     return out
 
 
@@ -348,6 +368,32 @@ class SufrFile:
         symbols start more than `max_occ` indexed suffixes give none (0: no limit).  On the host."""
         qb, off = pack_queries(queries)
         return _mem_hits(len(off) - 1, self.mem_arrays(qb, off, min_len, max_occ, both_strands, threads=threads))
+
+    def approx_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, max_mismatches: int = 2, max_occ: int = 0,
+                      both_strands: bool = False, cap: Optional[int] = None, threads: int = 0):
+        """(query, strand, position, mismatches) of every window of the text within `max_mismatches` substitutions of a query
+        of a packed batch, in (query, strand, piece, rank) order.  With a `cap` too small the SufrHipError (code -5) carries
+        the total in `.total`; without one the arrays are sized to fit."""
+        from ._lib import APPROX_BOTH_STRANDS
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nq = len(offsets) - 1
+        flags = APPROX_BOTH_STRANDS if both_strands else 0
+        return _sized_to_fit(
+            cap, 4 * nq + 16, lambda c: [np.zeros(c, dtype=d) for d in _APPROX_DTYPES],
+            lambda c, out, total: lib().sufr_file_approx(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, max_mismatches, max_occ,
+                                                         flags, c, *[a.ctypes.data for a in out], C.byref(total), threads),
+            lambda rc, total, c: SufrHipError(rc, "sufr_file_approx: " + {
+                -5: f"{total} records, room for {c}", -6: "files built with a seed mask are not supported",
+                -1: "invalid argument (max_mismatches must be at most 15)"}.get(rc, "failed")))
+
+    def approx(self, queries: Sequence, max_mismatches: int = 2, max_occ: int = 0, both_strands: bool = False,
+               threads: int = 0) -> List[List[ApproxHit]]:
+        """Where every query occurs with at most `max_mismatches` substitutions (seed and verify: the query is cut into
+        max_mismatches + 1 pieces, pieces that start more than `max_occ` indexed suffixes seed nothing, 0: no limit), in
+        (strand, piece, rank) order.  On the host."""
+        qb, off = pack_queries(queries)
+        return _approx_hits(len(off) - 1, self.approx_arrays(qb, off, max_mismatches, max_occ, both_strands, threads=threads))
 
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
@@ -648,3 +694,31 @@ class DeviceIndex:
         recs = self.mems_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), min_len, max_occ,
                                 both_strands)
         return _mem_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
+
+    # -- k-mismatch search (include/sufr_approx.h) -------------------------------------------------------------------
+    def approx_device(self, qbytes, offsets, max_mismatches: int = 2, max_occ: int = 0, both_strands: bool = False,
+                      cap: Optional[int] = None):
+        """k-mismatch occurrences of a packed batch of torch CUDA tensors (uint8 bytes, int64 offsets): (query int64, strand
+        uint8, position int64, mismatches uint8) tensors in (query, strand, piece, rank) order, complete on return.  With a
+        `cap` too small the SufrHipError (code -5) carries the total in `.total`; without one the outputs are sized to fit."""
+        import torch
+        from ._lib import APPROX_BOTH_STRANDS
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        dev = qbytes.device
+        qbytes = self._device_bytes(qbytes)
+        flags = APPROX_BOTH_STRANDS if both_strands else 0
+        return self._device_records(
+            cap, 4 * max(nq, 0) + 16, dev, (torch.int64, torch.uint8, torch.int64, torch.uint8),
+            lambda c, out, total: lib().sufr_hip_approx_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
+                                                               max_mismatches, max_occ, flags, c, *[t.data_ptr() for t in out],
+                                                               C.byref(total)))
+
+    def approx(self, queries: Sequence, max_mismatches: int = 2, max_occ: int = 0, both_strands: bool = False) -> List[List[ApproxHit]]:
+        """The k-mismatch occurrences of every query (SufrFile.approx), found on the device."""
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        recs = self.approx_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_mismatches,
+                                  max_occ, both_strands)
+        return _approx_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
