@@ -104,6 +104,10 @@ MEM_BOTH_STRANDS = 0x1
 # every symbol include/sufr_approx.h declares
 APPROX_EXPORTS = ["sufr_file_approx", "sufr_hip_approx_device", "sufr_hip_approx"]
 APPROX_BOTH_STRANDS = 0x1
+# every symbol include/sufr_edit.h declares
+EDIT_EXPORTS = ["sufr_file_edit", "sufr_hip_edit_device", "sufr_hip_edit"]
+EDIT_BOTH_STRANDS = 0x1
+EDIT_LOCAL_MINIMA = 0x2
 
 
 class FileMeta(C.Structure):
@@ -236,6 +240,13 @@ def lib() -> C.CDLL:
     L.sufr_hip_approx_device.restype = C.c_int
     L.sufr_hip_approx.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64)]
     L.sufr_hip_approx.restype = C.c_int
+    # include/sufr_edit.h
+    L.sufr_file_edit.argtypes = [vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64), C.c_int]
+    L.sufr_file_edit.restype = C.c_int
+    L.sufr_hip_edit_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_edit_device.restype = C.c_int
+    L.sufr_hip_edit.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_edit.restype = C.c_int
     _lib = L
     return L
 

@@ -7,7 +7,8 @@ struct sufr_hip_ctx {
     uint64_t array_budget = 0;        // sufr_hip_set_array_budget: device bytes the SA + LCP of a windowed create may take at once (0: no limit set)
     sufr::DevBuf wtext, wsa, wlcp, wblk;
     sufr::DevBuf mtmp, mpoff, mbytes;  // SMEM scan sums, slice offsets and packed slices (sufr_match.inc)
-    sufr::DevBuf xq, xoff, xlo, xhi, xcand, xsum;  // MEMs, k-mismatch (sufr_mem.inc, sufr_approx.inc): doubled batch, rank ranges, candidate starts, scan sums
+    sufr::DevBuf xq, xoff, xlo, xhi, xcand, xsum;  // MEMs, k-mismatch, k-difference (sufr_mem.inc, sufr_approx.inc, sufr_edit.inc): doubled batch, rank ranges, candidate starts, scan sums
+    sufr::DevBuf ecnt, ekeys, ekeys2, ehist;  // k-difference (sufr_edit.inc): ends per candidate, the two key buffers of the sort, its digit counts
     bool wide(uint64_t n) const { return n >= sufr::SUFR_MAX_TEXT_LEN || (wide_window && n > wide_window); }
 };
 
@@ -212,7 +213,8 @@ void sufr_hip_destroy(sufr_hip_ctx* ctx)
     sufr_io_release_ctx_(ctx);
     (void)hipSetDevice(ctx->pl.device);
     for (sufr::DevBuf* b : {&ctx->wtext, &ctx->wsa, &ctx->wlcp, &ctx->wblk, &ctx->mtmp, &ctx->mpoff, &ctx->mbytes,
-                            &ctx->xq, &ctx->xoff, &ctx->xlo, &ctx->xhi, &ctx->xcand, &ctx->xsum}) ctx->pl.release(*b);
+                            &ctx->xq, &ctx->xoff, &ctx->xlo, &ctx->xhi, &ctx->xcand, &ctx->xsum,
+                            &ctx->ecnt, &ctx->ekeys, &ctx->ekeys2, &ctx->ehist}) ctx->pl.release(*b);
     ctx->pl.destroy();
     delete ctx;
 }

@@ -22,6 +22,7 @@
 #include "../../include/sufr_match.h"
 #include "../../include/sufr_mem.h"
 #include "../../include/sufr_approx.h"
+#include "../../include/sufr_edit.h"
 
 #include <algorithm>
 #include <fstream>
@@ -68,7 +69,11 @@ int usage(FILE* f)
             "                                       name  strand(+/-)  seq:pos  mismatches\n"
             "                                       [-d|--mismatches N (2)] [--max-occ N (0: no limit)] [-b|--both-strands]\n"
             "                                       [-a|--abs] [-q|--reads FASTA/FASTQ] [-o OUT]\n"
-            "  count / locate / extract / match / mems / approx take --device <ID>: the queries are searched as one batch on that GPU\n\n"
+            "  edit|ed      <SUFR> [QUERY]...       Where the queries end with at most N edits (substitutions, insertions,\n"
+            "                                       deletions): one line per end, name  strand(+/-)  seq:end  edits\n"
+            "                                       [-d|--edits N (2)] [--max-occ N (0: no limit)] [-b|--both-strands]\n"
+            "                                       [-l|--local-minima] [-a|--abs] [-q|--reads FASTA/FASTQ] [-o OUT]\n"
+            "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
             "  -l, --log <LOG>           Log level [possible values: info, debug]\n"
@@ -116,6 +121,8 @@ struct QueryArgs {
     uint64_t max_occ = 0;                       // mems / approx: --max-occ
     bool both_strands = false;                  // mems / approx: -b
     uint64_t mismatches = 2;                    // approx: -d
+    uint64_t edits = 2;                         // edit: -d
+    bool local_minima = false;                  // edit: -l
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -597,6 +604,61 @@ int cmd_approx(const QueryArgs& a)
     return 0;
 }
 
+// sufr edit: every text position where a query ends with at most -d edits, one line each in record
+// order (query, strand, end): name, strand (+ / -), the end as seq:offset (0-based) or absolute with --abs, edits.
+int cmd_edit(const QueryArgs& a)
+{
+    if (a.edits > SUFR_EDIT_MAX_EDITS) { fprintf(stderr, "Error: --edits must be at most %u\n", SUFR_EDIT_MAX_EDITS); return 1; }
+    sufr_file* f = open_or_die(a.file);
+    OutFile out;
+    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    std::vector<std::string> names, seqs;
+    if (!named_queries(a, names, seqs)) return 1;
+    std::string bytes;
+    std::vector<uint64_t> off(seqs.size() + 1, 0);
+    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
+    sufr_hip_ctx* ctx = nullptr;
+    sufr_hip_index* ix = nullptr;
+    if (a.device >= 0) {
+        ctx = sufr_hip_create(a.device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
+        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
+    }
+    const uint32_t flags = (a.both_strands ? SUFR_EDIT_BOTH_STRANDS : 0) | (a.local_minima ? SUFR_EDIT_LOCAL_MINIMA : 0);
+    // records: room for a hill of ends per query first, the exact count when that is short
+    uint64_t cap = (2 * a.edits + 1) * seqs.size() + 16, total = 0;
+    std::vector<uint64_t> qi, end;
+    std::vector<uint8_t> st, ed;
+    for (;;) {
+        qi.resize(cap); end.resize(cap); st.resize(cap); ed.resize(cap);
+        const int rc = ix ? sufr_hip_edit(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.edits, a.max_occ, flags,
+                                          cap, qi.data(), st.data(), end.data(), ed.data(), &total)
+                          : sufr_file_edit(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.edits, a.max_occ, flags,
+                                           cap, qi.data(), st.data(), end.data(), ed.data(), &total, a.threads);
+        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
+        if (rc == SUFR_HIP_E_UNSUPPORTED && !(ctx && strstr(sufr_hip_last_error(ctx), "sort key"))) {
+            fprintf(stderr, "Error: %s: edit does not support files built with a seed mask\n", a.file.c_str());
+            return 1;
+        }
+        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "edit failed"); return 1; }
+        break;
+    }
+    if (ix) sufr_hip_index_free(ix);
+    if (ctx) sufr_hip_destroy(ctx);
+    for (uint64_t t = 0; t < total; t++) {
+        const char* name = names[qi[t]].c_str();
+        const char sgn = st[t] ? '-' : '+';
+        if (a.abs) fprintf(out.f, "%s\t%c\t%llu\t%u\n", name, sgn, (unsigned long long)end[t], (unsigned)ed[t]);
+        else {
+            const uint64_t i = sufr_file_sequence_of(f, end[t]);
+            fprintf(out.f, "%s\t%c\t%s:%llu\t%u\n", name, sgn, sufr_file_sequence_name(f, i),
+                    (unsigned long long)(end[t] - sufr_file_sequence_start(f, i)), (unsigned)ed[t]);
+        }
+    }
+    sufr_file_close(f);
+    return 0;
+}
+
 int run_query(const std::string& cmd, int argc, char** argv, int first, int threads)
 {
     QueryArgs a;
@@ -607,7 +669,8 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         return argv[++i];
     };
     const bool is_list = cmd == "list", is_extract = cmd == "extract", is_locate = cmd == "locate", is_sum = cmd == "summarize";
-    const bool is_approx = cmd == "approx";
+    const bool is_edit = cmd == "edit";
+    const bool is_approx = cmd == "approx" || is_edit;
     const bool is_mems = cmd == "mems";
     const bool is_match = cmd == "match" || is_mems || is_approx;
     for (int i = first; i < argc; i++) {
@@ -615,14 +678,16 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         if (s == "-h" || s == "--help") { usage(stdout); return 0; }
         else if (!is_list && !is_sum && !is_match && (s == "-m" || s == "--max-query-len")) { a.has_mql = true; a.mql = strtoull(need(i, "-m"), nullptr, 10); }
         else if (!is_sum && (s == "-o" || s == "--output")) a.output = need(i, "-o");
-        else if (!is_list && !is_sum && (s == "-l" || s == "--low-memory")) {}            // access mode only: the file is mapped
+        else if (!is_list && !is_sum && ((s == "-l" && !is_edit) || s == "--low-memory")) {}   // access mode only: the file is mapped (edit: -l is --local-minima)
         else if (!is_sum && (s == "-v" || s == "--very-low-memory")) {}
         else if (!is_list && !is_sum && s == "--device") a.device = atoi(need(i, "--device"));
         else if ((is_locate || is_match) && (s == "-a" || s == "--abs")) a.abs = true;
         else if (is_match && !is_approx && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
         else if ((is_mems || is_approx) && s == "--max-occ") a.max_occ = strtoull(need(i, "--max-occ"), nullptr, 10);
         else if ((is_mems || is_approx) && (s == "-b" || s == "--both-strands")) a.both_strands = true;
-        else if (is_approx && (s == "-d" || s == "--mismatches")) a.mismatches = strtoull(need(i, "-d"), nullptr, 10);
+        else if (is_edit && (s == "-d" || s == "--edits")) a.edits = strtoull(need(i, "-d"), nullptr, 10);
+        else if (is_edit && (s == "-l" || s == "--local-minima")) a.local_minima = true;
+        else if (is_approx && !is_edit && (s == "-d" || s == "--mismatches")) a.mismatches = strtoull(need(i, "-d"), nullptr, 10);
         else if (is_match && !is_mems && !is_approx && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
         else if (is_match && (s == "-q" || s == "--reads")) a.reads = need(i, "-q");
         else if (is_extract && (s == "-p" || s == "--prefix-len")) { a.has_prefix = true; a.prefix_len = strtoull(need(i, "-p"), nullptr, 10); }
@@ -649,6 +714,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
+    if (is_edit) return cmd_edit(a);
     if (is_approx) return cmd_approx(a);
     if (is_mems) return cmd_mems(a);
     if (is_match) return cmd_match(a);
@@ -710,6 +776,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "match" || s == "ma")) return run_query("match", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "mems" || s == "me")) return run_query("mems", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
+        else if (!have_cmd && (s == "edit" || s == "ed")) return run_query("edit", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "list" || s == "ls")) return run_query("list", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "summarize" || s == "su")) return run_query("summarize", argc, argv, i + 1, threads);

@@ -11,10 +11,12 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/sufr_hip.h"
@@ -22,6 +24,7 @@
 #include "../../include/sufr_match.h"
 #include "../../include/sufr_mem.h"
 #include "../../include/sufr_approx.h"
+#include "../../include/sufr_edit.h"
 
 struct sufr_file {
     std::string path;
@@ -607,6 +610,117 @@ int sufr_file_approx(const sufr_file* f, const uint8_t* queries, const uint64_t*
     uint64_t t = 0;
     for (const auto& v : recs)
         for (const ApproxRec& x : v) { query[t] = x.query; strand[t] = x.strand; position[t] = x.pos; mismatches[t] = x.mism; t++; }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- k-difference search (include/sufr_edit.h) --------------------------------------------------
+namespace {
+
+struct EditRec { uint64_t query; uint8_t strand; uint64_t end; uint8_t edits; };
+
+// The band of diagonal p: row r holds the cells of the columns p + r - 2d + k, k = 0 .. 4d; +inf outside the band and outside
+// [0, n]; row 0 is free.  Plain cells, one row kept (the device walks the same band bit-parallel).  last: row m.
+void edit_band_scalar(const uint8_t* Q, uint64_t m, const uint8_t* T, uint64_t n, int64_t p, uint32_t d, std::vector<uint32_t>& prev,
+                      std::vector<uint32_t>& cur)
+{
+    const int64_t W = 4 * (int64_t)d + 1, sn = (int64_t)n;
+    const uint32_t INF = 1u << 20;
+    prev.assign((size_t)W + 2, INF);
+    cur.assign((size_t)W + 2, INF);
+    for (int64_t k = 0; k < W; k++) { const int64_t c = p - 2 * (int64_t)d + k; if (c >= 0 && c <= sn) prev[(size_t)k + 1] = 0; }
+    for (uint64_t r = 1; r <= m; r++) {
+        uint32_t low = INF;
+        for (int64_t k = 0; k < W; k++) {
+            const int64_t c = p + (int64_t)r - 2 * (int64_t)d + k;
+            uint32_t v = INF;
+            if (c >= 0 && c <= sn) {
+                if (c >= 1) v = std::min(v, prev[(size_t)k + 1] + (Q[r - 1] != T[c - 1]));       // (r - 1, c - 1)
+                v = std::min(v, prev[(size_t)k + 2] + 1);                                        // (r - 1, c)
+                v = std::min(v, cur[(size_t)k] + 1);                                             // (r, c - 1)
+            }
+            cur[(size_t)k + 1] = std::min(v, INF);
+            low = std::min(low, v);
+        }
+        prev.swap(cur);
+        cur[0] = INF;
+        if (low > d) { prev.assign((size_t)W + 2, INF); return; }                                // nothing below comes back under d
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_edit(const sufr_file* f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t max_edits, uint64_t max_occ,
+                   uint32_t flags, uint64_t cap, uint64_t* query, uint8_t* strand, uint64_t* end, uint8_t* edits, uint64_t* total_out,
+                   int threads)
+{
+    if (total_out) *total_out = 0;
+    if (const int rc = match_args(f, queries, offsets, nq)) return rc;
+    if (max_edits > SUFR_EDIT_MAX_EDITS) return SUFR_HIP_E_INVALID;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    const bool both = (flags & SUFR_EDIT_BOTH_STRANDS) != 0, minima = (flags & SUFR_EDIT_LOCAL_MINIMA) != 0;
+    std::vector<uint8_t> dbl;
+    std::vector<uint64_t> off;
+    const uint8_t* qb = strand_batch(queries, offsets, nq, both, dbl, off);
+    const uint64_t nq2 = off.size() - 1;
+    const uint64_t n = f->meta.text_len, L = f->meta.max_query_len;
+    const uint32_t d = max_edits, np = d + 1;
+    const uint8_t* text = f->text;
+    // workers over chunks of queries; chunk c keeps its records, the chunks are concatenated in order
+    const uint64_t chunk = 16, nchunks = (nq2 + chunk - 1) / chunk;
+    std::vector<std::vector<EditRec>> recs(nchunks);
+    parallel_chunks(nq2, chunk, threads, [&](uint64_t b, uint64_t e) {
+        std::vector<EditRec>& out = recs[b / chunk];
+        std::vector<int64_t> diags;
+        std::vector<std::pair<uint64_t, uint32_t>> ends;                     // (exclusive end, D)
+        std::vector<uint32_t> row, tmp;
+        for (uint64_t a = b; a < e; a++) {
+            const uint8_t* Q = qb + off[a];
+            const uint64_t m = off[a + 1] - off[a];
+            if (m < np) continue;
+            diags.clear();
+            for (uint32_t i = 0; i < np; i++) {                              // the diagonals of every live seed
+                const uint64_t o = (uint64_t)i * m / np, len = (uint64_t)(i + 1) * m / np - o, kk = L > 0 && L < len ? L : len;
+                uint64_t lo = 0, hi = 0;
+                (void)sufr_file_search(f, Q + o, (size_t)kk, 0, 0, &lo, &hi);
+                if (max_occ && hi - lo > max_occ) continue;
+                for (uint64_t r = lo; r < hi; r++) diags.push_back((int64_t)sufr_file_suffix(f, r) - (int64_t)o);
+            }
+            std::sort(diags.begin(), diags.end());
+            diags.erase(std::unique(diags.begin(), diags.end()), diags.end());
+            ends.clear();
+            for (const int64_t p : diags) {
+                edit_band_scalar(Q, m, text, n, p, d, row, tmp);
+                for (uint32_t j = 0; j <= 2 * d; j++) {                      // cell d + j of the last row: the end p + m - d + j
+                    const int64_t x = p + (int64_t)m - (int64_t)d + j;
+                    if (x >= 1 && x <= (int64_t)n && row[(size_t)d + j + 1] <= d) ends.push_back({(uint64_t)x, row[(size_t)d + j + 1]});
+                }
+            }
+            std::sort(ends.begin(), ends.end());
+            ends.erase(std::unique(ends.begin(), ends.end()), ends.end());
+            for (size_t t = 0; t < ends.size(); t++) {
+                if (minima) {
+                    const uint32_t v = ends[t].second;
+                    const uint32_t vl = t > 0 && ends[t - 1].first + 1 == ends[t].first ? ends[t - 1].second : d + 1;
+                    const uint32_t vr = t + 1 < ends.size() && ends[t + 1].first == ends[t].first + 1 ? ends[t + 1].second : d + 1;
+                    if (!(vl > v && vr >= v)) continue;
+                }
+                out.push_back({both ? a >> 1 : a, (uint8_t)(both ? a & 1 : 0), ends[t].first - 1, (uint8_t)ends[t].second});
+            }
+        }
+    }, 4);
+    uint64_t total = 0;
+    for (const auto& v : recs) total += v.size();
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!query || !strand || !end || !edits) return SUFR_HIP_E_INVALID;
+    uint64_t t = 0;
+    for (const auto& v : recs)
+        for (const EditRec& x : v) { query[t] = x.query; strand[t] = x.strand; end[t] = x.end; edits[t] = x.edits; t++; }
     return 0;
 }
 

@@ -9,7 +9,7 @@ from .types import SufrBuilderArgs
 
 
 class SuffixArray:
-    """After `read`, count / extract / list / locate / smems / mems / approx / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
+    """After `read`, count / extract / list / locate / smems / mems / approx / edit / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
 
     def __init__(self, inner: SufrFile):
         self.inner = inner
@@ -41,6 +41,10 @@ class SuffixArray:
 
     def approx(self, queries, max_mismatches: int = 2, max_occ: int = 0, both_strands: bool = False, threads: int = 0):
         return self.inner.approx(queries, max_mismatches, max_occ, both_strands, threads)
+
+    def edit(self, queries, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False, local_minima: bool = False,
+             threads: int = 0):
+        return self.inner.edit(queries, max_edits, max_occ, both_strands, local_minima, threads)
 
     def list(self, **opts):
         return self.inner.list(**opts)

@@ -6,7 +6,8 @@ by the C ABI of include/sufr_query.h (a mapped file, two binary searches per que
 queries on the GPU from text + suffix array resident in HBM (sufr_hip_search_batch).  Both also give the matching
 statistics and the super-maximal exact matches (SMEMs) of queries (include/sufr_match.h), and their
 maximal exact matches (MEMs) on one or both strands (include/sufr_mem.h), and where they occur with
-at most d mismatches (include/sufr_approx.h)."""
+at most d mismatches (include/sufr_approx.h) or end with at most d edits (include/sufr_edit.h,
+DESIGN.md section 16)."""
 from __future__ import annotations
 
 import builtins
@@ -120,6 +121,27 @@ def _approx_hits(nq: int, recs) -> List[List[ApproxHit]]:
     out: List[List[ApproxHit]] = [[] for _ in range(nq)]
     for t in range(len(qi)):
         out[int(qi[t])].append(ApproxHit(int(qi[t]), int(st[t]), int(pos[t]), int(mm[t])))
+    return out
+
+
+@dataclass
+class EditHit:                         # one k-difference occurrence of a query (include/sufr_edit.h)
+    query: int
+    strand: int                        # 0: the query as given, 1: its reverse complement ...
+    end: int                           # ... is within `edits` substitutions, insertions and deletions of a piece of the text
+    edits: int                         #     whose last byte is text[end]
+
+
+def _edit_flags(both_strands: bool, local_minima: bool) -> int:
+    from ._lib import EDIT_BOTH_STRANDS, EDIT_LOCAL_MINIMA
+    return (EDIT_BOTH_STRANDS if both_strands else 0) | (EDIT_LOCAL_MINIMA if local_minima else 0)
+
+
+def _edit_hits(nq: int, recs) -> List[List[EditHit]]:
+    qi, st, end, ed = recs
+    out: List[List[EditHit]] = [[] for _ in range(nq)]
+    for t in range(len(qi)):
+        out[int(qi[t])].append(EditHit(int(qi[t]), int(st[t]), int(end[t]), int(ed[t])))
     return out
 
 
@@ -394,6 +416,30 @@ class SufrFile:
         (strand, piece, rank) order.  On the host."""
         qb, off = pack_queries(queries)
         return _approx_hits(len(off) - 1, self.approx_arrays(qb, off, max_mismatches, max_occ, both_strands, threads=threads))
+
+    def edit_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False,
+                    local_minima: bool = False, cap: Optional[int] = None, threads: int = 0):
+        """(query, strand, end, edits) of every text position where a query of a packed batch ends with at most `max_edits`
+        substitutions, insertions and deletions, sorted by (query, strand, end), each once.  With a `cap` too small the
+        SufrHipError (code -5) carries the total in `.total`; without one the arrays are sized to fit."""
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nq = len(offsets) - 1
+        flags = _edit_flags(both_strands, local_minima)
+        return _sized_to_fit(
+            cap, 4 * nq + 16, lambda c: [np.zeros(c, dtype=d) for d in _APPROX_DTYPES],
+            lambda c, out, total: lib().sufr_file_edit(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, max_edits, max_occ,
+                                                       flags, c, *[a.ctypes.data for a in out], C.byref(total), threads),
+            lambda rc, total, c: SufrHipError(rc, "sufr_file_edit: " + {
+                -5: f"{total} records, room for {c}", -6: "files built with a seed mask are not supported",
+                -1: "invalid argument (max_edits must be at most 15)"}.get(rc, "failed")))
+
+    def edit(self, queries: Sequence, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False, local_minima: bool = False,
+             threads: int = 0) -> List[List[EditHit]]:
+        """Where every query ends in the text with at most `max_edits` edits (pigeonhole seeds as in `approx`, a banded
+        Sellers table per candidate), by end; `local_minima` keeps one end per hill.  On the host."""
+        qb, off = pack_queries(queries)
+        return _edit_hits(len(off) - 1, self.edit_arrays(qb, off, max_edits, max_occ, both_strands, local_minima, threads=threads))
 
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
@@ -722,3 +768,31 @@ class DeviceIndex:
         recs = self.approx_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_mismatches,
                                   max_occ, both_strands)
         return _approx_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
+
+    # -- k-difference search (include/sufr_edit.h) -------------------------------------------------------------------
+    def edit_device(self, qbytes, offsets, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False,
+                    local_minima: bool = False, cap: Optional[int] = None):
+        """k-difference ends of a packed batch of torch CUDA tensors (uint8 bytes, int64 offsets): (query int64, strand uint8,
+        end int64, edits uint8) tensors sorted by (query, strand, end), complete on return.  With a `cap` too small the
+        SufrHipError (code -5) carries the total in `.total`; without one the outputs are sized to fit."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        dev = qbytes.device
+        qbytes = self._device_bytes(qbytes)
+        flags = _edit_flags(both_strands, local_minima)
+        return self._device_records(
+            cap, 4 * max(nq, 0) + 16, dev, (torch.int64, torch.uint8, torch.int64, torch.uint8),
+            lambda c, out, total: lib().sufr_hip_edit_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
+                                                             max_edits, max_occ, flags, c, *[t.data_ptr() for t in out],
+                                                             C.byref(total)))
+
+    def edit(self, queries: Sequence, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False,
+             local_minima: bool = False) -> List[List[EditHit]]:
+        """The k-difference ends of every query (SufrFile.edit), found on the device."""
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        recs = self.edit_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_edits, max_occ,
+                                both_strands, local_minima)
+        return _edit_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
