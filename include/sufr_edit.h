@@ -29,7 +29,8 @@
  * unindexed positions.  A -m L build gives the records of the uncapped build of the same text when max_occ == 0.
  *
  * Out of scope: alignment starts, CIGAR strings, traceback.  The call is the "find the ends" phase; a caller traces back the
- * few ends it keeps (a backward banded table from `end` over at most m + d text bytes).
+ * few ends it keeps (a backward banded table from `end` over at most m + d text bytes).  See sufr_align.h, which does that
+ * for a list of records, on the host and on the GPU.
  *
  * Limits.  max_edits above SUFR_EDIT_MAX_EDITS is SUFR_HIP_E_INVALID; 0 is legal (exact occurrences, by their last byte).
  * Files and indexes built with a seed mask are refused (SUFR_HIP_E_UNSUPPORTED).  The device path sorts 64-bit keys that

@@ -108,6 +108,8 @@ APPROX_BOTH_STRANDS = 0x1
 EDIT_EXPORTS = ["sufr_file_edit", "sufr_hip_edit_device", "sufr_hip_edit"]
 EDIT_BOTH_STRANDS = 0x1
 EDIT_LOCAL_MINIMA = 0x2
+# every symbol include/sufr_align.h declares
+ALIGN_EXPORTS = ["sufr_file_edit_trace", "sufr_hip_edit_trace_device", "sufr_hip_edit_trace", "sufr_hip_set_trace_scratch"]
 
 
 class FileMeta(C.Structure):
@@ -247,6 +249,14 @@ def lib() -> C.CDLL:
     L.sufr_hip_edit_device.restype = C.c_int
     L.sufr_hip_edit.argtypes = [vp, vp, vp, vp, u64, u32, u64, u32, u64, vp, vp, vp, vp, C.POINTER(u64)]
     L.sufr_hip_edit.restype = C.c_int
+    # include/sufr_align.h
+    L.sufr_file_edit_trace.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp, vp, C.POINTER(u64), C.c_int, cp, C.c_size_t]
+    L.sufr_file_edit_trace.restype = C.c_int
+    L.sufr_hip_edit_trace_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_edit_trace_device.restype = C.c_int
+    L.sufr_hip_edit_trace.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_edit_trace.restype = C.c_int
+    L.sufr_hip_set_trace_scratch.argtypes = [vp, u64]; L.sufr_hip_set_trace_scratch.restype = C.c_int
     _lib = L
     return L
 
@@ -287,6 +297,10 @@ class Context:
     def set_array_budget(self, nbytes: int = 0):
         """Out-of-core windowed create: device bytes the SA + LCP arrays may take at once (sufr_hip_set_array_budget; 0: no limit)."""
         self.check(lib().sufr_hip_set_array_budget(self._h, nbytes))
+
+    def set_trace_scratch(self, nbytes: int = 0):
+        """Alignment traceback: device bytes the rows of a chunk of records may take (sufr_hip_set_trace_scratch; 0: the default)."""
+        self.check(lib().sufr_hip_set_trace_scratch(self._h, nbytes))
 
     @property
     def window_repairs(self) -> int:

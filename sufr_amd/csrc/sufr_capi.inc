@@ -9,6 +9,8 @@ struct sufr_hip_ctx {
     sufr::DevBuf mtmp, mpoff, mbytes;  // SMEM scan sums, slice offsets and packed slices (sufr_match.inc)
     sufr::DevBuf xq, xoff, xlo, xhi, xcand, xsum;  // MEMs, k-mismatch, k-difference (sufr_mem.inc, sufr_approx.inc, sufr_edit.inc): doubled batch, rank ranges, candidate starts, scan sums
     sufr::DevBuf ecnt, ekeys, ekeys2, ehist;  // k-difference (sufr_edit.inc): ends per candidate, the two key buffers of the sort, its digit counts
+    sufr::DevBuf tsc, trows, tmisc;    // alignment traceback (sufr_trace.inc): the scalars of a call, the rows of a chunk, its scan sums and run counts
+    uint64_t trace_scratch = 0;        // sufr_hip_set_trace_scratch: bytes of row storage (0: the default)
     bool wide(uint64_t n) const { return n >= sufr::SUFR_MAX_TEXT_LEN || (wide_window && n > wide_window); }
 };
 
@@ -214,7 +216,7 @@ void sufr_hip_destroy(sufr_hip_ctx* ctx)
     (void)hipSetDevice(ctx->pl.device);
     for (sufr::DevBuf* b : {&ctx->wtext, &ctx->wsa, &ctx->wlcp, &ctx->wblk, &ctx->mtmp, &ctx->mpoff, &ctx->mbytes,
                             &ctx->xq, &ctx->xoff, &ctx->xlo, &ctx->xhi, &ctx->xcand, &ctx->xsum,
-                            &ctx->ecnt, &ctx->ekeys, &ctx->ekeys2, &ctx->ehist}) ctx->pl.release(*b);
+                            &ctx->ecnt, &ctx->ekeys, &ctx->ekeys2, &ctx->ehist, &ctx->tsc, &ctx->trows, &ctx->tmisc}) ctx->pl.release(*b);
     ctx->pl.destroy();
     delete ctx;
 }

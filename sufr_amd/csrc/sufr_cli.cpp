@@ -23,6 +23,7 @@
 #include "../../include/sufr_mem.h"
 #include "../../include/sufr_approx.h"
 #include "../../include/sufr_edit.h"
+#include "../../include/sufr_align.h"
 
 #include <algorithm>
 #include <fstream>
@@ -73,6 +74,7 @@ int usage(FILE* f)
             "                                       deletions): one line per end, name  strand(+/-)  seq:end  edits\n"
             "                                       [-d|--edits N (2)] [--max-occ N (0: no limit)] [-b|--both-strands]\n"
             "                                       [-l|--local-minima] [-a|--abs] [-q|--reads FASTA/FASTQ] [-o OUT]\n"
+            "                                       [-c|--cigar: two more columns, the start (as the end) and the CIGAR (= X I D)]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -123,6 +125,7 @@ struct QueryArgs {
     uint64_t mismatches = 2;                    // approx: -d
     uint64_t edits = 2;                         // edit: -d
     bool local_minima = false;                  // edit: -l
+    bool cigar = false;                         // edit: -c
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -606,6 +609,8 @@ int cmd_approx(const QueryArgs& a)
 
 // sufr edit: every text position where a query ends with at most -d edits, one line each in record
 // order (query, strand, end): name, strand (+ / -), the end as seq:offset (0-based) or absolute with --abs, edits.
+// -c: the records are traced back (on the device with --device); two more columns, the start in the
+// form of the end and the CIGAR.
 int cmd_edit(const QueryArgs& a)
 {
     if (a.edits > SUFR_EDIT_MAX_EDITS) { fprintf(stderr, "Error: --edits must be at most %u\n", SUFR_EDIT_MAX_EDITS); return 1; }
@@ -643,17 +648,46 @@ int cmd_edit(const QueryArgs& a)
         if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "edit failed"); return 1; }
         break;
     }
+    // -c: the sizing call, then the runs
+    std::vector<uint64_t> start(total + 1), coff(total + 1, 0);
+    std::vector<uint32_t> cigar;
+    if (a.cigar && total) {
+        char err[512] = "";
+        uint64_t runs = 0;
+        for (int pass = 0; pass < 2; pass++) {
+            const int rc = ix ? sufr_hip_edit_trace(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), total, qi.data(), st.data(),
+                                                    end.data(), ed.data(), cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs)
+                              : sufr_file_edit_trace(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), total, qi.data(), st.data(), end.data(),
+                                                     ed.data(), cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs,
+                                                     a.threads, err, sizeof err);
+            if (rc == SUFR_HIP_E_CAPACITY && pass == 0) { cigar.resize(runs); continue; }
+            if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : err); return 1; }
+            break;
+        }
+    }
     if (ix) sufr_hip_index_free(ix);
     if (ctx) sufr_hip_destroy(ctx);
-    for (uint64_t t = 0; t < total; t++) {
-        const char* name = names[qi[t]].c_str();
-        const char sgn = st[t] ? '-' : '+';
-        if (a.abs) fprintf(out.f, "%s\t%c\t%llu\t%u\n", name, sgn, (unsigned long long)end[t], (unsigned)ed[t]);
+    auto place = [&](uint64_t p) {
+        if (a.abs) fprintf(out.f, "%llu", (unsigned long long)p);
         else {
-            const uint64_t i = sufr_file_sequence_of(f, end[t]);
-            fprintf(out.f, "%s\t%c\t%s:%llu\t%u\n", name, sgn, sufr_file_sequence_name(f, i),
-                    (unsigned long long)(end[t] - sufr_file_sequence_start(f, i)), (unsigned)ed[t]);
+            const uint64_t i = sufr_file_sequence_of(f, p);
+            fprintf(out.f, "%s:%llu", sufr_file_sequence_name(f, i), (unsigned long long)(p - sufr_file_sequence_start(f, i)));
         }
+    };
+    for (uint64_t t = 0; t < total; t++) {
+        fprintf(out.f, "%s\t%c\t", names[qi[t]].c_str(), st[t] ? '-' : '+');
+        place(end[t]);
+        fprintf(out.f, "\t%u", (unsigned)ed[t]);
+        if (a.cigar) {
+            fputc('\t', out.f);
+            place(start[t]);
+            fputc('\t', out.f);
+            for (uint64_t r = coff[t]; r < coff[t + 1]; r++) {
+                const uint32_t op = cigar[r] & 15u;
+                fprintf(out.f, "%u%c", cigar[r] >> 4, op == 1 ? 'I' : op == 2 ? 'D' : op == 7 ? '=' : 'X');
+            }
+        }
+        fputc('\n', out.f);
     }
     sufr_file_close(f);
     return 0;
@@ -687,6 +721,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         else if ((is_mems || is_approx) && (s == "-b" || s == "--both-strands")) a.both_strands = true;
         else if (is_edit && (s == "-d" || s == "--edits")) a.edits = strtoull(need(i, "-d"), nullptr, 10);
         else if (is_edit && (s == "-l" || s == "--local-minima")) a.local_minima = true;
+        else if (is_edit && (s == "-c" || s == "--cigar")) a.cigar = true;
         else if (is_approx && !is_edit && (s == "-d" || s == "--mismatches")) a.mismatches = strtoull(need(i, "-d"), nullptr, 10);
         else if (is_match && !is_mems && !is_approx && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
         else if (is_match && (s == "-q" || s == "--reads")) a.reads = need(i, "-q");

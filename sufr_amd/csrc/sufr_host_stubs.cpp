@@ -18,6 +18,7 @@
 #include "../../include/sufr_mem.h"
 #include "../../include/sufr_approx.h"
 #include "../../include/sufr_edit.h"
+#include "../../include/sufr_align.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -116,5 +117,12 @@ int sufr_hip_edit_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, 
                          uint64_t, void*, void*, void*, void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 int sufr_hip_edit(sufr_hip_ctx* ctx, const sufr_hip_index*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint32_t, uint64_t,
                   uint64_t*, uint8_t*, uint64_t*, uint8_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+
+// ---- include/sufr_align.h: the device side (the host side is sufr_query.cpp) ----------------------------------------
+int sufr_hip_edit_trace_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const void*, uint64_t, uint64_t, const void*, const void*,
+                               const void*, const void*, uint64_t, void*, void*, void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_edit_trace(sufr_hip_ctx* ctx, const sufr_hip_index*, const uint8_t*, const uint64_t*, uint64_t, uint64_t, const uint64_t*, const uint8_t*,
+                        const uint64_t*, const uint8_t*, uint64_t, uint64_t*, uint64_t*, uint32_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_set_trace_scratch(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
 
 }  // extern "C"

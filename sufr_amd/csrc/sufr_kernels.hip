@@ -2998,3 +2998,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_approx.inc"
 #include "../../include/sufr_edit.h"
 #include "sufr_edit.inc"
+#include "../../include/sufr_align.h"
+#include "sufr_trace.inc"

@@ -25,6 +25,7 @@
 #include "../../include/sufr_mem.h"
 #include "../../include/sufr_approx.h"
 #include "../../include/sufr_edit.h"
+#include "../../include/sufr_align.h"
 
 struct sufr_file {
     std::string path;
@@ -721,6 +722,125 @@ int sufr_file_edit(const sufr_file* f, const uint8_t* queries, const uint64_t* o
     uint64_t t = 0;
     for (const auto& v : recs)
         for (const EditRec& x : v) { query[t] = x.query; strand[t] = x.strand; end[t] = x.end; edits[t] = x.edits; t++; }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- alignment traceback of k-difference records (include/sufr_align.h) ---------------------------
+namespace {
+
+// One record: the table of Q against T on the diagonals g - v .. g + v (g = e - m), every row kept: tab[r * W + k] is the cell
+// of row r and column r + g - v + k, +inf outside the band and outside the columns 0 .. n; row 0 is free, column 0 holds r.
+// Plain cells (the device keeps two bit vectors per row instead).  Then the walk of sufr_align.h, runs pushed last run first.
+// false: the end cell does not hold v, so v is not D(e).
+bool trace_scalar(const uint8_t* Q, uint64_t m, const uint8_t* T, uint64_t n, uint64_t e, uint32_t v, std::vector<uint32_t>& tab,
+                  uint64_t& start, std::vector<uint32_t>& runs)
+{
+    const int64_t W = 2 * (int64_t)v + 1, sn = (int64_t)n, g = (int64_t)e - (int64_t)m;
+    const uint32_t INF = 0x7FFFFFFFu;
+    tab.assign((size_t)((m + 1) * (uint64_t)W), INF);
+    auto col = [&](uint64_t r, int64_t k) { return (int64_t)r + g - (int64_t)v + k; };
+    auto at = [&](uint64_t r, int64_t k) -> uint32_t { return k < 0 || k >= W ? INF : tab[(size_t)(r * (uint64_t)W + (uint64_t)k)]; };
+    for (int64_t k = 0; k < W; k++) { const int64_t c = col(0, k); if (c >= 0 && c <= sn) tab[(size_t)k] = 0; }
+    for (uint64_t r = 1; r <= m; r++)
+        for (int64_t k = 0; k < W; k++) {
+            const int64_t c = col(r, k);
+            if (c < 0 || c > sn) continue;
+            uint32_t x = INF;
+            if (c >= 1 && at(r - 1, k) != INF) x = std::min(x, at(r - 1, k) + (Q[r - 1] != T[c - 1]));      // (r - 1, c - 1)
+            if (at(r - 1, k + 1) != INF) x = std::min(x, at(r - 1, k + 1) + 1);                             // (r - 1, c)
+            if (at(r, k - 1) != INF) x = std::min(x, at(r, k - 1) + 1);                                     // (r, c - 1)
+            tab[(size_t)(r * (uint64_t)W + (uint64_t)k)] = x;
+        }
+    if (at(m, v) != v) return false;
+    runs.clear();
+    uint64_t i = m;
+    int64_t k = v;
+    uint32_t op = 0, len = 0;
+    auto step = [&](uint32_t o) { if (o != op) { if (len) runs.push_back(len << 4 | op); op = o; len = 0; } len++; };
+    while (i > 0) {
+        const int64_t j = col(i, k);
+        const uint32_t cur = at(i, k);
+        if (j > 0 && at(i - 1, k) != INF && at(i - 1, k) + (Q[i - 1] != T[j - 1]) == cur) { step(Q[i - 1] == T[j - 1] ? 7u : 8u); i--; }
+        else if (at(i - 1, k + 1) != INF && at(i - 1, k + 1) + 1 == cur) { step(1u); i--; k++; }
+        else { step(2u); k--; }
+    }
+    if (len) runs.push_back(len << 4 | op);
+    start = (uint64_t)col(0, k);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_edit_trace(const sufr_file* f, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint64_t num_records,
+                         const uint64_t* query, const uint8_t* strand, const uint64_t* end, const uint8_t* edits, uint64_t cigar_cap,
+                         uint64_t* start, uint64_t* cigar_off, uint32_t* cigar, uint64_t* total_out, int threads, char* err, size_t errlen)
+{
+    if (total_out) *total_out = 0;
+    if (err && errlen) err[0] = 0;
+    if (!f || !cigar_off || (cigar_cap && !cigar) || (nq && !offsets) || (nq && offsets[nq] > offsets[0] && !queries) ||
+        (num_records && (!query || !strand || !end || !edits || !start))) {
+        put_err(err, errlen, "trace: null argument");
+        return SUFR_HIP_E_INVALID;
+    }
+    cigar_off[0] = 0;
+    if (!num_records) return 0;
+    const uint64_t n = f->meta.text_len;
+    const uint8_t* text = f->text;
+    // workers over chunks of records; a chunk keeps its runs, forward, record after record; cigar_off[t + 1]: the runs of t
+    const uint64_t chunk = 64, nchunks = (num_records + chunk - 1) / chunk;
+    std::vector<std::vector<uint32_t>> runs_of(nchunks);
+    std::atomic<uint64_t> bad{~0ull};
+    parallel_chunks(num_records, chunk, threads, [&](uint64_t b, uint64_t e) {
+        std::vector<uint32_t>& out = runs_of[b / chunk];
+        std::vector<uint32_t> tab, runs;
+        std::vector<uint8_t> rc;
+        for (uint64_t t = b; t < e; t++) {
+            cigar_off[t + 1] = 0;
+            start[t] = 0;
+            bool ok = query[t] < nq && strand[t] <= 1 && end[t] < n && edits[t] <= SUFR_EDIT_MAX_EDITS &&
+                      offsets[query[t] + 1] >= offsets[query[t]] && offsets[query[t] + 1] - offsets[query[t]] >= (uint64_t)edits[t] + 1;
+            if (ok) {
+                const uint8_t* Q = queries + offsets[query[t]];
+                const uint64_t m = offsets[query[t] + 1] - offsets[query[t]];
+                if (strand[t]) {
+                    rc.resize((size_t)m);
+                    for (uint64_t x = 0; x < m; x++) rc[(size_t)x] = revcomp_byte(Q[m - 1 - x]);
+                    Q = rc.data();
+                }
+                ok = trace_scalar(Q, m, text, n, end[t] + 1, edits[t], tab, start[t], runs);
+                if (ok) {
+                    out.insert(out.end(), runs.rbegin(), runs.rend());
+                    cigar_off[t + 1] = runs.size();
+                }
+            }
+            if (!ok) { uint64_t cur = bad.load(); while (t < cur && !bad.compare_exchange_weak(cur, t)) {} }
+        }
+    }, 64);
+    if (bad.load() != ~0ull) {
+        const uint64_t t = bad.load();
+        const bool range = !(query[t] < nq && strand[t] <= 1 && end[t] < n && edits[t] <= SUFR_EDIT_MAX_EDITS &&
+                             offsets[query[t] + 1] >= offsets[query[t]] && offsets[query[t] + 1] - offsets[query[t]] >= (uint64_t)edits[t] + 1);
+        put_err(err, errlen, "trace: record " + std::to_string(t) + (range ? " is no record of this batch and text (query, strand, end, edits "
+                             "or the length of its query out of range)" : ": edits is not D(end + 1)"));
+        return SUFR_HIP_E_INVALID;
+    }
+    for (uint64_t t = 0; t < num_records; t++) cigar_off[t + 1] += cigar_off[t];
+    const uint64_t total = cigar_off[num_records];
+    if (total_out) *total_out = total;
+    for (uint64_t c = 0; c < nchunks; c++) {
+        const uint64_t at = cigar_off[c * chunk];
+        if (at >= cigar_cap) break;
+        const uint64_t cnt = std::min<uint64_t>(runs_of[c].size(), cigar_cap - at);
+        if (cnt) memcpy(cigar + at, runs_of[c].data(), (size_t)cnt * 4);
+    }
+    if (total > cigar_cap) {
+        put_err(err, errlen, "trace: " + std::to_string(total) + " CIGAR runs, room for " + std::to_string(cigar_cap));
+        return SUFR_HIP_E_CAPACITY;
+    }
     return 0;
 }
 

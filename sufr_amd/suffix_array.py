@@ -9,7 +9,7 @@ from .types import SufrBuilderArgs
 
 
 class SuffixArray:
-    """After `read`, count / extract / list / locate / smems / mems / approx / edit / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
+    """After `read`, count / extract / list / locate / smems / mems / approx / edit / align / metadata / string_at are SufrFile's (suffix_array.rs:181-440)."""
 
     def __init__(self, inner: SufrFile):
         self.inner = inner
@@ -45,6 +45,10 @@ class SuffixArray:
     def edit(self, queries, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False, local_minima: bool = False,
              threads: int = 0):
         return self.inner.edit(queries, max_edits, max_occ, both_strands, local_minima, threads)
+
+    def align(self, queries, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False, local_minima: bool = False,
+              threads: int = 0):
+        return self.inner.align(queries, max_edits, max_occ, both_strands, local_minima, threads)
 
     def list(self, **opts):
         return self.inner.list(**opts)

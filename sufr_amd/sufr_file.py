@@ -7,7 +7,7 @@ queries on the GPU from text + suffix array resident in HBM (sufr_hip_search_bat
 statistics and the super-maximal exact matches (SMEMs) of queries (include/sufr_match.h), and their
 maximal exact matches (MEMs) on one or both strands (include/sufr_mem.h), and where they occur with
 at most d mismatches (include/sufr_approx.h) or end with at most d edits (include/sufr_edit.h,
-DESIGN.md section 16)."""
+DESIGN.md section 16), with the start and the CIGAR of every such end (include/sufr_align.h)."""
 from __future__ import annotations
 
 import builtins
@@ -142,6 +142,34 @@ def _edit_hits(nq: int, recs) -> List[List[EditHit]]:
     out: List[List[EditHit]] = [[] for _ in range(nq)]
     for t in range(len(qi)):
         out[int(qi[t])].append(EditHit(int(qi[t]), int(st[t]), int(end[t]), int(ed[t])))
+    return out
+
+
+@dataclass
+class AlignHit:                        # a k-difference occurrence with its alignment (include/sufr_align.h)
+    query: int
+    strand: int
+    end: int                           # the alignment covers text[start : end + 1] ...
+    edits: int
+    start: int
+    cigar: str                         # ... with these ops ('=' 'X' 'I' 'D'), e.g. 37=1X12=2D98=
+
+
+_CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}
+
+
+def cigar_string(runs) -> str:
+    """BAM-encoded runs (len << 4 | op) as text."""
+    return "".join(f"{int(r) >> 4}{_CIGAR_OPS[int(r) & 15]}" for r in runs)
+
+
+def _align_hits(nq: int, recs, trace) -> List[List[AlignHit]]:
+    qi, st, end, ed = recs
+    start, off, cigar = trace
+    out: List[List[AlignHit]] = [[] for _ in range(nq)]
+    for t in range(len(qi)):
+        out[int(qi[t])].append(AlignHit(int(qi[t]), int(st[t]), int(end[t]), int(ed[t]), int(start[t]),
+                                        cigar_string(cigar[int(off[t]):int(off[t + 1])])))
     return out
 
 
@@ -440,6 +468,35 @@ class SufrFile:
         Sellers table per candidate), by end; `local_minima` keeps one end per hill.  On the host."""
         qb, off = pack_queries(queries)
         return _edit_hits(len(off) - 1, self.edit_arrays(qb, off, max_edits, max_occ, both_strands, local_minima, threads=threads))
+
+    def edit_trace_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, query, strand, end, edits, cap: Optional[int] = None,
+                          threads: int = 0):
+        """(start, cigar_off, cigar) of the records (query, strand, end, edits) of `edit_arrays` on the same packed batch:
+        record t starts at start[t] and owns the BAM-encoded runs cigar[cigar_off[t]:cigar_off[t + 1]] (include/sufr_align.h).
+        With a `cap` (of runs) too small the SufrHipError (code -5) carries the total in `.total`; without one the runs are
+        sized to fit.  A record that is none of this batch and text is code -1, with its index in the message."""
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        recs = [np.ascontiguousarray(a, dtype=d) for a, d in zip((query, strand, end, edits), _APPROX_DTYPES)]
+        nq, nr = len(offsets) - 1, len(recs[0])
+        start = np.zeros(max(nr, 1), dtype=np.uint64)
+        off = np.zeros(nr + 1, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        (cigar,) = _sized_to_fit(
+            cap, 4 * nr + 16, lambda c: [np.zeros(c, dtype=np.uint32)],
+            lambda c, out, total: lib().sufr_file_edit_trace(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, nr,
+                                                             *[a.ctypes.data for a in recs], c, start.ctypes.data, off.ctypes.data,
+                                                             out[0].ctypes.data, C.byref(total), threads, err, len(err)),
+            lambda rc, total, c: SufrHipError(rc, "sufr_file_edit_trace: " + (err.value.decode() or "failed")))
+        return start[:nr], off, cigar
+
+    def align(self, queries: Sequence, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False, local_minima: bool = False,
+              threads: int = 0) -> List[List[AlignHit]]:
+        """The hits of `edit` with the start and the CIGAR string of every one (`edit_arrays`, then `edit_trace_arrays`).  On
+        the host."""
+        qb, off = pack_queries(queries)
+        recs = self.edit_arrays(qb, off, max_edits, max_occ, both_strands, local_minima, threads=threads)
+        return _align_hits(len(off) - 1, recs, self.edit_trace_arrays(qb, off, *recs, threads=threads))
 
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
@@ -796,3 +853,53 @@ class DeviceIndex:
         recs = self.edit_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_edits, max_occ,
                                 both_strands, local_minima)
         return _edit_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
+
+    # -- alignment traceback (include/sufr_align.h) -------------------------------------------------------------------
+    def edit_trace_device(self, qbytes, offsets, query, strand, end, edits, cap: Optional[int] = None):
+        """Start and CIGAR of k-difference records on torch CUDA tensors (the batch and the four tensors of `edit_device`):
+        (start int64, cigar_off int64[records + 1], cigar int32 holding BAM-encoded u32 runs), complete on return.  With a
+        `cap` (of runs) too small the SufrHipError (code -5) carries the total in `.total`; without one the runs are sized to
+        fit."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq, nr = offsets.numel() - 1, query.numel()
+        dev = qbytes.device
+        qbytes = self._device_bytes(qbytes)
+        start = torch.zeros(max(nr, 1), dtype=torch.int64, device=dev)
+        off = torch.zeros(nr + 1, dtype=torch.int64, device=dev)
+        (cigar,) = self._device_records(
+            cap, 4 * nr + 16, dev, (torch.int32,),
+            lambda c, out, total: lib().sufr_hip_edit_trace_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
+                                                                   nr, query.data_ptr(), strand.data_ptr(), end.data_ptr(), edits.data_ptr(),
+                                                                   c, start.data_ptr(), off.data_ptr(), out[0].data_ptr(), C.byref(total)))
+        return start[:nr], off, cigar
+
+    def edit_trace(self, qbytes: np.ndarray, offsets: np.ndarray, query, strand, end, edits, cap: Optional[int] = None):
+        """`SufrFile.edit_trace_arrays` on host arrays through sufr_hip_edit_trace (staged, traced on the device, copied back)."""
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        recs = [np.ascontiguousarray(a, dtype=d) for a, d in zip((query, strand, end, edits), _APPROX_DTYPES)]
+        nq, nr = len(offsets) - 1, len(recs[0])
+        start = np.zeros(max(nr, 1), dtype=np.uint64)
+        off = np.zeros(nr + 1, dtype=np.uint64)
+        (cigar,) = _sized_to_fit(
+            cap, 4 * nr + 16, lambda c: [np.zeros(c, dtype=np.uint32)],
+            lambda c, out, total: lib().sufr_hip_edit_trace(self.ctx.handle, self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, nr,
+                                                            *[a.ctypes.data for a in recs], c, start.ctypes.data, off.ctypes.data,
+                                                            out[0].ctypes.data, C.byref(total)),
+            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
+        return start[:nr], off, cigar
+
+    def align(self, queries: Sequence, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False,
+              local_minima: bool = False) -> List[List[AlignHit]]:
+        """The hits of `edit` with the start and the CIGAR string of every one (SufrFile.align), searched and traced on the
+        device."""
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        dq, do = torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev)
+        recs = self.edit_device(dq, do, max_edits, max_occ, both_strands, local_minima)
+        recs = tuple(t.contiguous() for t in recs)
+        st, co, cg = self.edit_trace_device(dq, do, *recs)
+        return _align_hits(len(off) - 1, [t.cpu().numpy() for t in recs],
+                           (st.cpu().numpy(), co.cpu().numpy(), cg.cpu().numpy().view(np.uint32)))
