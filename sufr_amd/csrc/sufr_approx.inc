@@ -1,21 +1,23 @@
 // sufr_approx.inc -- k-mismatch search of a query batch on a device-resident index: seed and verify with the pigeonhole
 // filter (included by sufr_kernels.hip after sufr_mem.inc; include/sufr_approx.h, DESIGN.md section 15).
 //
-// k_mem_revcomp      (sufr_mem.inc) both strands: the doubled batch
+// take_batch         (sufr_search.inc) the bitmap of the index, the two ends of the batch (a synchronisation of its own), the
+//                    doubled batch with both strands
 // k_approx_seeds     one lane per seed g = a * (d + 1) + i (grid-stride): the rank range of the first k' bytes of piece i of
 //                    query a, found in place by search_range; empty when the query is shorter than d + 1, marked dead
 //                    (APPROX_DEAD in the low bound) when it holds more than max_occ suffixes
-// k_locate_counts / k_locate_scan / k_locate_apply (sufr_search.inc) exclusive scan of the range sizes: the candidate starts;
-//                    one synchronisation reads the candidate total
+// candidate_starts   (sufr_search.inc) the exclusive scan of the range sizes: the candidate starts; one synchronisation
+//                    reads the candidate total.  pigeonhole_candidates (below) is these two steps, shared with sufr_edit.inc
 // k_approx_count     SCAN_WGS workgroups over the candidates, 8 per lane: candidate -> seed by binary search of the starts,
 //                    p = SA[lo + ...] - o_i, the window bounds, the rest of a capped piece, the anchors of the lower pieces
 //                    (piece bytes, one bitmap bit, liveness), the Hamming distance 8 bytes a step with an exit at d + 1;
 //                    counts per workgroup
-// k_locate_scan      the record total (second synchronisation) and the workgroup bases
+// scan_total         (sufr_search.inc) k_locate_scan: the record total (second synchronisation) and the workgroup bases
 // k_approx_emit      the verdicts again (one byte per candidate, kept in a register), scanned in the workgroup; the records
 // No MFMA, no LDS beyond the scan words, no scratch.
-// From sufr_search.inc: search_range, common_prefix, last_le, wg_scan and scan_chunk (SCAN_WGS workgroups), query_check,
-// read_totals and the staging of the host-pointer entry point.  From sufr_mem.inc: k_mem_revcomp and mem_bitmap().
+// From sufr_search.inc: search_range, common_prefix, last_le, wg_scan and scan_chunk (SCAN_WGS workgroups); the host side of
+// the driver (query_check, take_batch, candidate_starts, scan_total, records_fit, any_null, launch_status) and
+// staged_records for the host-pointer entry points.
 
 namespace sufr {
 
@@ -158,6 +160,55 @@ __global__ __launch_bounds__(256) void k_approx_emit(SearchIndex ix, ApproxBatch
 
 }  // namespace sufr
 
+namespace {
+
+int approx_args(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint32_t max_mismatches)
+{
+    if (const int rc = query_check(ctx, ix, "k-mismatch searches")) return rc;
+    if (max_mismatches > SUFR_APPROX_MAX_MISMATCHES) {
+        ctx->pl.set_error("approx: max_mismatches must be at most " + std::to_string(SUFR_APPROX_MAX_MISMATCHES));
+        return SUFR_HIP_E_INVALID;
+    }
+    return 0;
+}
+
+// The pigeonhole candidates of a batch (k-mismatch and k-difference): d + 1 seeds per query, the rank range of every seed
+// (k_approx_seeds), the exclusive scan of the live range sizes.  B: what the count and emit kernels read.
+int pigeonhole_candidates(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const QueryBatch& b, uint32_t d, uint64_t max_occ, const char* tag,
+                          sufr::ApproxBatch& B, Candidates& c)
+{
+    const uint32_t np = d + 1;
+    const uint64_t ns = b.nq * np;
+    if (const int rc = candidate_starts(ctx, ns, tag, [&](uint64_t* rlo, uint64_t* rhi) {
+        hipLaunchKernelGGL(sufr::k_approx_seeds, dim3(b.grid), dim3(256), 0, ctx->pl.stream, ix->ix, b.q, b.qoff, b.nq, (uint64_t)ix->built_mql, np,
+                           max_occ, rlo, rhi);
+    }, c)) return rc;                                                // (c is not set when the scratch could not be had)
+    B = sufr::ApproxBatch{b.q, b.qoff, b.nq, c.rlo, c.cand, ns, (const uint32_t*)ix->mem_bits, ix->built_mql, np, d};
+    return 0;
+}
+
+// The host-pointer entry point of a pigeonhole search: `limits` checks the arguments, `device` is the *_device twin; the
+// record columns are query, strand, where (position / end) and distance (mismatches / edits).
+using PigeonholeDevice = int (*)(sufr_hip_ctx*, const sufr_hip_index*, const void*, const void*, uint64_t, uint32_t, uint64_t, uint32_t, uint64_t,
+                                 void*, void*, void*, void*, uint64_t*);
+
+int pigeonhole_host(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* queries, const uint64_t* offsets, uint64_t num_queries, uint32_t d,
+                    uint64_t max_occ, uint32_t flags, uint64_t cap, uint64_t* query, uint8_t* strand, uint64_t* where, uint8_t* distance,
+                    uint64_t* total_out, const char* what, int (*limits)(sufr_hip_ctx*, const sufr_hip_index*, uint32_t), PigeonholeDevice device)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !ix || (num_queries && !offsets)) return SUFR_HIP_E_INVALID;
+    ctx->pl.err.clear();
+    if (const int rc = limits(ctx, ix, d)) return rc;
+    if (!num_queries) return 0;
+    return staged_records(ctx, what, queries, offsets, num_queries, cap, {{query, 8}, {strand, 1}, {where, 8}, {distance, 1}}, 0, total_out,
+                          [&](const void* d_q, const void* d_off, void* const* col, uint64_t* total) {
+        return device(ctx, ix, d_q, d_off, num_queries, d, max_occ, flags, cap, col[0], col[1], col[2], col[3], total);
+    });
+}
+
+}  // namespace
+
 extern "C" {
 
 int sufr_hip_approx_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets,
@@ -168,96 +219,30 @@ int sufr_hip_approx_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const vo
     if (!ctx || !ix || (num_queries && (!d_queries || !d_offsets))) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
     pl.err.clear();
-    if (const int rc = query_check(ctx, ix, "k-mismatch searches")) return rc;
-    if (max_mismatches > SUFR_APPROX_MAX_MISMATCHES) {
-        pl.set_error("approx: max_mismatches must be at most " + std::to_string(SUFR_APPROX_MAX_MISMATCHES));
-        return SUFR_HIP_E_INVALID;
-    }
-    if (!num_queries) return 0;
     int rc;
-    if ((rc = mem_bitmap(ctx, ix))) return rc;
-    // the byte count of the batch sizes the doubled batch
-    unsigned long long ends[2] = {0, 0};
-    const uint64_t* uoff = (const uint64_t*)d_offsets;
-    if (hipMemcpyAsync(&ends[0], uoff, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-        hipMemcpyAsync(&ends[1], uoff + num_queries, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-        hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("approx: reading the batch offsets failed"); return SUFR_HIP_E_HIP; }
-    if (ends[1] <= ends[0]) return 0;
-    const bool both = (flags & SUFR_APPROX_BOTH_STRANDS) != 0;
-    const uint64_t nb = (ends[1] - ends[0]) * (both ? 2 : 1), nq = num_queries * (both ? 2 : 1);
-    const uint32_t grid = (pl.num_cus ? pl.num_cus : 256u) * 8u;
-    const uint8_t* q = (const uint8_t*)d_queries;
-    const uint64_t* qoff = uoff;
-    if (both) {
-        if ((rc = pl.ensure(ctx->xq, nb + 8)) || (rc = pl.ensure(ctx->xoff, (nq + 1) * 8))) return rc;
-        hipLaunchKernelGGL(sufr::k_mem_revcomp, dim3(grid), dim3(256), 0, pl.stream, q, uoff, num_queries, (uint8_t*)ctx->xq.p,
-                           (uint64_t*)ctx->xoff.p);
-        q = (const uint8_t*)ctx->xq.p;
-        qoff = (const uint64_t*)ctx->xoff.p;
-    }
-    // rank range of every seed, then the exclusive scan of the live range sizes
-    const uint32_t np = max_mismatches + 1;
-    const uint64_t ns = nq * np, nblk = (ns + sufr::LOC_BLK - 1) / sufr::LOC_BLK;
-    if ((rc = pl.ensure(ctx->xlo, ns * 8)) || (rc = pl.ensure(ctx->xhi, ns * 8)) || (rc = pl.ensure(ctx->xcand, (ns + 1) * 8)) ||
-        (rc = pl.ensure(ctx->xsum, (nblk + 1 + sufr::SCAN_WGS + 1) * 8))) return rc;
-    uint64_t* rlo = (uint64_t*)ctx->xlo.p;
-    uint64_t* cand = (uint64_t*)ctx->xcand.p;
-    uint64_t* bsum = (uint64_t*)ctx->xsum.p;
-    uint64_t* cnt_sum = bsum + nblk + 1;
-    hipLaunchKernelGGL(sufr::k_approx_seeds, dim3(grid), dim3(256), 0, pl.stream, ix->ix, q, qoff, nq, (uint64_t)ix->built_mql, np, max_occ,
-                       rlo, (uint64_t*)ctx->xhi.p);
-    hipLaunchKernelGGL(sufr::k_locate_counts, dim3((uint32_t)nblk), dim3(256), 0, pl.stream, (const uint64_t*)rlo,
-                       (const uint64_t*)ctx->xhi.p, ns, (uint64_t)0, cand, bsum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, bsum, nblk, bsum + nblk);
-    hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((ns + 256) / 256)), dim3(256), 0, pl.stream, cand, ns, (const uint64_t*)bsum,
-                       (const uint64_t*)(bsum + nblk));
-    unsigned long long ncand = 0;
-    if ((rc = read_totals(pl, bsum + nblk, 1, &ncand, "approx: counting the candidates failed"))) return rc;
-    if (!ncand) return 0;
+    if ((rc = approx_args(ctx, ix, max_mismatches))) return rc;
+    QueryBatch b;
+    if ((rc = take_batch(ctx, ix, d_queries, d_offsets, num_queries, (flags & SUFR_APPROX_BOTH_STRANDS) != 0, "approx", b)) || !b.nb) return rc;
+    sufr::ApproxBatch B;
+    Candidates c;
+    if ((rc = pigeonhole_candidates(ctx, ix, b, max_mismatches, max_occ, "approx", B, c)) || !c.ncand) return rc;
     // the verdict of every candidate, counted per workgroup, then the record total
-    const sufr::ApproxBatch B{q, qoff, nq, rlo, cand, ns, (const uint32_t*)ix->mem_bits, ix->built_mql, np, max_mismatches};
-    hipLaunchKernelGGL(sufr::k_approx_count, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, cnt_sum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, (uint64_t)sufr::SCAN_WGS, cnt_sum + sufr::SCAN_WGS);
+    hipLaunchKernelGGL(sufr::k_approx_count, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, c.cnt_sum);
     unsigned long long nrec = 0;
-    if ((rc = read_totals(pl, cnt_sum + sufr::SCAN_WGS, 1, &nrec, "approx: counting the records failed"))) return rc;
-    if (total_out) *total_out = nrec;
-    if (nrec > cap) {
-        pl.set_error("approx: " + std::to_string(nrec) + " records, room for " + std::to_string(cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    if (!nrec) return 0;
-    if (!d_query || !d_strand || !d_position || !d_mismatches) return SUFR_HIP_E_INVALID;
-    hipLaunchKernelGGL(sufr::k_approx_emit, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, (const uint64_t*)cnt_sum, (uint32_t)both,
+    if ((rc = scan_total(pl, c.cnt_sum, sufr::SCAN_WGS, &nrec, "approx", "counting the records failed"))) return rc;
+    if ((rc = records_fit(pl, "approx", "records", nrec, cap, total_out)) || !nrec) return rc;
+    if (any_null({d_query, d_strand, d_position, d_mismatches})) return SUFR_HIP_E_INVALID;
+    hipLaunchKernelGGL(sufr::k_approx_emit, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, (const uint64_t*)c.cnt_sum, (uint32_t)b.both,
                        (uint64_t*)d_query, (uint8_t*)d_strand, (uint64_t*)d_position, (uint8_t*)d_mismatches);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pl.set_error(std::string("approx: ") + hipGetErrorString(e)); return SUFR_HIP_E_HIP; }
-    return 0;
+    return launch_status(pl, "approx");
 }
 
 int sufr_hip_approx(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* queries, const uint64_t* offsets, uint64_t num_queries,
                     uint32_t max_mismatches, uint64_t max_occ, uint32_t flags, uint64_t cap, uint64_t* query, uint8_t* strand,
                     uint64_t* position, uint8_t* mismatches, uint64_t* total_out)
 {
-    if (total_out) *total_out = 0;
-    if (!ctx || !ix || (num_queries && !offsets)) return SUFR_HIP_E_INVALID;
-    ctx->pl.err.clear();
-    if (const int rc = query_check(ctx, ix, "k-mismatch searches")) return rc;
-    if (max_mismatches > SUFR_APPROX_MAX_MISMATCHES) {
-        ctx->pl.set_error("approx: max_mismatches must be at most " + std::to_string(SUFR_APPROX_MAX_MISMATCHES));
-        return SUFR_HIP_E_INVALID;
-    }
-    if (!num_queries) return 0;
-    const uint64_t qbytes = offsets[num_queries], obytes = (num_queries + 1) * 8;
-    // one allocation: queries | offsets | records (cap of each)
-    const uint64_t o_at = (qbytes + 7) / 8 * 8, q_at = o_at + obytes, pos_at = q_at + cap * 8, st_at = pos_at + cap * 8, mm_at = st_at + cap;
-    uint8_t* d;
-    int rc = stage_batch(ctx, "k-mismatch", queries, offsets, num_queries, o_at, mm_at + cap + 8, &d);
-    uint64_t total = 0;
-    if (!rc) rc = sufr_hip_approx_device(ctx, ix, d, d + o_at, num_queries, max_mismatches, max_occ, flags, cap, d + q_at, d + st_at,
-                                         d + pos_at, d + mm_at, &total);
-    if (total_out) *total_out = total;
-    return unstage_batch(ctx, "k-mismatch", d, rc, {{query, q_at, total * 8}, {strand, st_at, total}, {position, pos_at, total * 8},
-                                                    {mismatches, mm_at, total}});
+    return pigeonhole_host(ctx, ix, queries, offsets, num_queries, max_mismatches, max_occ, flags, cap, query, strand, position, mismatches,
+                           total_out, "k-mismatch", approx_args, sufr_hip_approx_device);
 }
 
 }  // extern "C"

@@ -441,64 +441,119 @@ bool named_queries(const QueryArgs& a, std::vector<std::string>& names, std::vec
     return true;
 }
 
+// What match, mems, approx and edit hold while they run: the .sufr file, the output, the named queries packed into one
+// batch and, with --device, the context and the index on it.  Everything is released on every way out.
+struct QuerySession {
+    sufr_file* f = nullptr;
+    OutFile out;
+    std::vector<std::string> names;
+    std::string bytes;                          // the queries, one after the other ...
+    std::vector<uint64_t> off;                  // ... query i is bytes [off[i], off[i + 1])
+    sufr_hip_ctx* ctx = nullptr;
+    sufr_hip_index* ix = nullptr;
+
+    bool open(const QueryArgs& a)
+    {
+        f = open_or_die(a.file);
+        if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return false; }
+        return true;
+    }
+    bool load(const QueryArgs& a)
+    {
+        std::vector<std::string> seqs;
+        if (!named_queries(a, names, seqs)) return false;
+        off.assign(seqs.size() + 1, 0);
+        for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
+        if (a.device < 0) return true;
+        ctx = sufr_hip_create(a.device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return false; }
+        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return false; }
+        return true;
+    }
+    const uint8_t* q() const { return (const uint8_t*)bytes.data(); }
+    uint64_t nq() const { return off.size() - 1; }
+    // the device is not held while the records are printed: the output may be large
+    void release_device()
+    {
+        if (ix) sufr_hip_index_free(ix);
+        if (ctx) sufr_hip_destroy(ctx);
+        ix = nullptr; ctx = nullptr;
+    }
+    ~QuerySession() { release_device(); if (f) sufr_file_close(f); }
+    QuerySession() = default;
+    QuerySession(const QuerySession&) = delete;
+    QuerySession& operator=(const QuerySession&) = delete;
+
+    // call(cap, &total) until the records fit: `cap` first, the exact count when that is short.  false: an error, printed
+    // (`cmd` names the sub-command; ok_unsupported: an E_UNSUPPORTED whose text has it is no seed-mask refusal)
+    template <typename Call>
+    bool until_fits(const QueryArgs& a, const char* cmd, uint64_t cap, uint64_t& total, Call call, const char* ok_unsupported = nullptr)
+    {
+        for (;;) {
+            const int rc = call(cap, &total);
+            if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
+            if (rc == SUFR_HIP_E_UNSUPPORTED && !(ok_unsupported && ctx && strstr(sufr_hip_last_error(ctx), ok_unsupported))) {
+                fprintf(stderr, "Error: %s: %s does not support files built with a seed mask\n", a.file.c_str(), cmd);
+                return false;
+            }
+            if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : (std::string(cmd) + " failed").c_str()); return false; }
+            return true;
+        }
+    }
+};
+
+// position `at` of sequence i as seq:pos (0-based inside the sequence)
+std::string seq_pos(const sufr_file* f, uint64_t i, uint64_t at) { return std::string(sufr_file_sequence_name(f, i)) + ":" + std::to_string(at); }
+
+// a text position as seq:pos, or absolute with --abs
+std::string place(const sufr_file* f, bool abs, uint64_t p)
+{
+    if (abs) return std::to_string(p);
+    const uint64_t i = sufr_file_sequence_of(f, p);
+    return seq_pos(f, i, p - sufr_file_sequence_start(f, i));
+}
+
 // arguments of the query sub-commands (clap definitions of lib.rs:129-271)
 // sufr match: the SMEMs of every query, one line each: name, offset, length, count, positions.
 // Positions: SA[rank_lo .. rank_lo + max_hits) (all with 0), printed as seq:pos ordered by sequence name then position
 // like locate's, or absolute in rank order with --abs.
 int cmd_match(const QueryArgs& a)
 {
-    sufr_file* f = open_or_die(a.file);
-    OutFile out;
-    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    QuerySession s;
+    if (!s.open(a)) return 1;
     if (a.min_len == 0 || a.min_len > 0xFFFFFFFFull) { fprintf(stderr, "Error: --min-len must be between 1 and 2^32 - 1\n"); return 1; }
-    std::vector<std::string> names, seqs;
-    if (!named_queries(a, names, seqs)) return 1;
-    std::string bytes;
-    std::vector<uint64_t> off(seqs.size() + 1, 0);
-    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
-    sufr_hip_ctx* ctx = nullptr;
-    sufr_hip_index* ix = nullptr;
-    if (a.device >= 0) {
-        ctx = sufr_hip_create(a.device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
-        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
-    }
+    if (!s.load(a)) return 1;
     // records: room for one SMEM per 8 query bytes first, the exact count when that is short
-    uint64_t cap = bytes.size() / 8 + 16, total = 0;
+    uint64_t total = 0;
     std::vector<uint64_t> qi, lo, hi;
     std::vector<uint32_t> qo, len;
-    for (;;) {
-        qi.resize(cap); lo.resize(cap); hi.resize(cap); qo.resize(cap); len.resize(cap);
-        const int rc = ix ? sufr_hip_smems(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, cap,
-                                           qi.data(), qo.data(), len.data(), lo.data(), hi.data(), &total)
-                          : sufr_file_smems(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, cap,
-                                            qi.data(), qo.data(), len.data(), lo.data(), hi.data(), &total, a.threads);
-        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-        if (rc == SUFR_HIP_E_UNSUPPORTED) { fprintf(stderr, "Error: %s: match does not support files built with a seed mask\n", a.file.c_str()); return 1; }
-        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "match failed"); return 1; }
-        break;
-    }
-    if (ix) sufr_hip_index_free(ix);
-    if (ctx) sufr_hip_destroy(ctx);
+    if (!s.until_fits(a, "match", s.bytes.size() / 8 + 16, total, [&](uint64_t cap, uint64_t* tot) {
+            qi.resize(cap); lo.resize(cap); hi.resize(cap); qo.resize(cap); len.resize(cap);
+            return s.ix ? sufr_hip_smems(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(),
+                                         lo.data(), hi.data(), tot)
+                        : sufr_file_smems(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(), lo.data(),
+                                          hi.data(), tot, a.threads);
+        })) return 1;
+    s.release_device();
     for (uint64_t t = 0; t < total; t++) {
         const uint64_t end = a.max_hits && hi[t] - lo[t] > a.max_hits ? lo[t] + a.max_hits : hi[t];
         std::string pos;
-        if (a.abs) {
-            for (uint64_t r = lo[t]; r < end; r++) pos += (r > lo[t] ? "," : "") + std::to_string(sufr_file_suffix(f, r));
-        } else {
-            struct Pos { std::string name; uint64_t at; };
+        if (a.abs) for (uint64_t r = lo[t]; r < end; r++) pos += (r > lo[t] ? "," : "") + place(s.f, true, sufr_file_suffix(s.f, r));
+        else {
+            struct Pos { uint64_t seq, at; };
             std::vector<Pos> ps;
             for (uint64_t r = lo[t]; r < end; r++) {
-                const uint64_t sfx = sufr_file_suffix(f, r);
-                const uint64_t i = sufr_file_sequence_of(f, sfx);
-                ps.push_back({sufr_file_sequence_name(f, i), sfx - sufr_file_sequence_start(f, i)});
+                const uint64_t sfx = sufr_file_suffix(s.f, r), i = sufr_file_sequence_of(s.f, sfx);
+                ps.push_back({i, sfx - sufr_file_sequence_start(s.f, i)});
             }
-            std::stable_sort(ps.begin(), ps.end(), [](const Pos& x, const Pos& y) { return x.name != y.name ? x.name < y.name : x.at < y.at; });
-            for (size_t k = 0; k < ps.size(); k++) pos += (k ? "," : "") + ps[k].name + ":" + std::to_string(ps[k].at);
+            std::stable_sort(ps.begin(), ps.end(), [&](const Pos& x, const Pos& y) {
+                const int c = x.seq == y.seq ? 0 : strcmp(sufr_file_sequence_name(s.f, x.seq), sufr_file_sequence_name(s.f, y.seq));
+                return c ? c < 0 : x.at < y.at;
+            });
+            for (size_t k = 0; k < ps.size(); k++) pos += (k ? "," : "") + seq_pos(s.f, ps[k].seq, ps[k].at);
         }
-        fprintf(out.f, "%s\t%u\t%u\t%llu\t%s\n", names[qi[t]].c_str(), qo[t], len[t], (unsigned long long)(hi[t] - lo[t]), pos.c_str());
+        fprintf(s.out.f, "%s\t%u\t%u\t%llu\t%s\n", s.names[qi[t]].c_str(), qo[t], len[t], (unsigned long long)(hi[t] - lo[t]), pos.c_str());
     }
-    sufr_file_close(f);
     return 0;
 }
 
@@ -506,52 +561,26 @@ int cmd_match(const QueryArgs& a)
 // the strand's coordinates), length, position as seq:pos (0-based) or absolute with --abs.
 int cmd_mems(const QueryArgs& a)
 {
-    sufr_file* f = open_or_die(a.file);
-    OutFile out;
-    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    QuerySession s;
+    if (!s.open(a)) return 1;
     if (a.min_len == 0 || a.min_len > 0xFFFFFFFFull) { fprintf(stderr, "Error: --min-len must be between 1 and 2^32 - 1\n"); return 1; }
-    std::vector<std::string> names, seqs;
-    if (!named_queries(a, names, seqs)) return 1;
-    std::string bytes;
-    std::vector<uint64_t> off(seqs.size() + 1, 0);
-    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
-    sufr_hip_ctx* ctx = nullptr;
-    sufr_hip_index* ix = nullptr;
-    if (a.device >= 0) {
-        ctx = sufr_hip_create(a.device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
-        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
-    }
+    if (!s.load(a)) return 1;
     const uint32_t flags = a.both_strands ? SUFR_MEM_BOTH_STRANDS : 0;
     // records: room for one MEM per 4 query bytes first, the exact count when that is short
-    uint64_t cap = bytes.size() / 4 + 16, total = 0;
+    uint64_t total = 0;
     std::vector<uint64_t> qi, pos;
     std::vector<uint32_t> qo, len;
     std::vector<uint8_t> st;
-    for (;;) {
-        qi.resize(cap); pos.resize(cap); qo.resize(cap); len.resize(cap); st.resize(cap);
-        const int rc = ix ? sufr_hip_mems(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, a.max_occ,
-                                          flags, cap, qi.data(), qo.data(), st.data(), len.data(), pos.data(), &total)
-                          : sufr_file_mems(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.min_len, a.max_occ,
-                                           flags, cap, qi.data(), qo.data(), st.data(), len.data(), pos.data(), &total, a.threads);
-        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-        if (rc == SUFR_HIP_E_UNSUPPORTED) { fprintf(stderr, "Error: %s: mems does not support files built with a seed mask\n", a.file.c_str()); return 1; }
-        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "mems failed"); return 1; }
-        break;
-    }
-    if (ix) sufr_hip_index_free(ix);
-    if (ctx) sufr_hip_destroy(ctx);
-    for (uint64_t t = 0; t < total; t++) {
-        const char* name = names[qi[t]].c_str();
-        const char sgn = st[t] ? '-' : '+';
-        if (a.abs) fprintf(out.f, "%s\t%c\t%u\t%u\t%llu\n", name, sgn, qo[t], len[t], (unsigned long long)pos[t]);
-        else {
-            const uint64_t i = sufr_file_sequence_of(f, pos[t]);
-            fprintf(out.f, "%s\t%c\t%u\t%u\t%s:%llu\n", name, sgn, qo[t], len[t], sufr_file_sequence_name(f, i),
-                    (unsigned long long)(pos[t] - sufr_file_sequence_start(f, i)));
-        }
-    }
-    sufr_file_close(f);
+    if (!s.until_fits(a, "mems", s.bytes.size() / 4 + 16, total, [&](uint64_t cap, uint64_t* tot) {
+            qi.resize(cap); pos.resize(cap); qo.resize(cap); len.resize(cap); st.resize(cap);
+            return s.ix ? sufr_hip_mems(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, a.max_occ, flags, cap, qi.data(), qo.data(),
+                                        st.data(), len.data(), pos.data(), tot)
+                        : sufr_file_mems(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, a.max_occ, flags, cap, qi.data(), qo.data(),
+                                         st.data(), len.data(), pos.data(), tot, a.threads);
+        })) return 1;
+    s.release_device();
+    for (uint64_t t = 0; t < total; t++)
+        fprintf(s.out.f, "%s\t%c\t%u\t%u\t%s\n", s.names[qi[t]].c_str(), st[t] ? '-' : '+', qo[t], len[t], place(s.f, a.abs, pos[t]).c_str());
     return 0;
 }
 
@@ -560,50 +589,23 @@ int cmd_mems(const QueryArgs& a)
 int cmd_approx(const QueryArgs& a)
 {
     if (a.mismatches > SUFR_APPROX_MAX_MISMATCHES) { fprintf(stderr, "Error: --mismatches must be at most %u\n", SUFR_APPROX_MAX_MISMATCHES); return 1; }
-    sufr_file* f = open_or_die(a.file);
-    OutFile out;
-    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
-    std::vector<std::string> names, seqs;
-    if (!named_queries(a, names, seqs)) return 1;
-    std::string bytes;
-    std::vector<uint64_t> off(seqs.size() + 1, 0);
-    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
-    sufr_hip_ctx* ctx = nullptr;
-    sufr_hip_index* ix = nullptr;
-    if (a.device >= 0) {
-        ctx = sufr_hip_create(a.device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
-        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
-    }
+    QuerySession s;
+    if (!s.open(a) || !s.load(a)) return 1;
     const uint32_t flags = a.both_strands ? SUFR_APPROX_BOTH_STRANDS : 0;
     // records: room for four windows per query first, the exact count when that is short
-    uint64_t cap = 4 * seqs.size() + 16, total = 0;
+    uint64_t total = 0;
     std::vector<uint64_t> qi, pos;
     std::vector<uint8_t> st, mm;
-    for (;;) {
-        qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
-        const int rc = ix ? sufr_hip_approx(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.mismatches, a.max_occ,
-                                            flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total)
-                          : sufr_file_approx(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.mismatches, a.max_occ,
-                                             flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total, a.threads);
-        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-        if (rc == SUFR_HIP_E_UNSUPPORTED) { fprintf(stderr, "Error: %s: approx does not support files built with a seed mask\n", a.file.c_str()); return 1; }
-        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "approx failed"); return 1; }
-        break;
-    }
-    if (ix) sufr_hip_index_free(ix);
-    if (ctx) sufr_hip_destroy(ctx);
-    for (uint64_t t = 0; t < total; t++) {
-        const char* name = names[qi[t]].c_str();
-        const char sgn = st[t] ? '-' : '+';
-        if (a.abs) fprintf(out.f, "%s\t%c\t%llu\t%u\n", name, sgn, (unsigned long long)pos[t], (unsigned)mm[t]);
-        else {
-            const uint64_t i = sufr_file_sequence_of(f, pos[t]);
-            fprintf(out.f, "%s\t%c\t%s:%llu\t%u\n", name, sgn, sufr_file_sequence_name(f, i),
-                    (unsigned long long)(pos[t] - sufr_file_sequence_start(f, i)), (unsigned)mm[t]);
-        }
-    }
-    sufr_file_close(f);
+    if (!s.until_fits(a, "approx", 4 * s.nq() + 16, total, [&](uint64_t cap, uint64_t* tot) {
+            qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
+            return s.ix ? sufr_hip_approx(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.mismatches, a.max_occ, flags, cap, qi.data(),
+                                          st.data(), pos.data(), mm.data(), tot)
+                        : sufr_file_approx(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.mismatches, a.max_occ, flags, cap, qi.data(), st.data(),
+                                           pos.data(), mm.data(), tot, a.threads);
+        })) return 1;
+    s.release_device();
+    for (uint64_t t = 0; t < total; t++)
+        fprintf(s.out.f, "%s\t%c\t%s\t%u\n", s.names[qi[t]].c_str(), st[t] ? '-' : '+', place(s.f, a.abs, pos[t]).c_str(), (unsigned)mm[t]);
     return 0;
 }
 
@@ -614,40 +616,20 @@ int cmd_approx(const QueryArgs& a)
 int cmd_edit(const QueryArgs& a)
 {
     if (a.edits > SUFR_EDIT_MAX_EDITS) { fprintf(stderr, "Error: --edits must be at most %u\n", SUFR_EDIT_MAX_EDITS); return 1; }
-    sufr_file* f = open_or_die(a.file);
-    OutFile out;
-    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
-    std::vector<std::string> names, seqs;
-    if (!named_queries(a, names, seqs)) return 1;
-    std::string bytes;
-    std::vector<uint64_t> off(seqs.size() + 1, 0);
-    for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
-    sufr_hip_ctx* ctx = nullptr;
-    sufr_hip_index* ix = nullptr;
-    if (a.device >= 0) {
-        ctx = sufr_hip_create(a.device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
-        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return 1; }
-    }
+    QuerySession s;
+    if (!s.open(a) || !s.load(a)) return 1;
     const uint32_t flags = (a.both_strands ? SUFR_EDIT_BOTH_STRANDS : 0) | (a.local_minima ? SUFR_EDIT_LOCAL_MINIMA : 0);
     // records: room for a hill of ends per query first, the exact count when that is short
-    uint64_t cap = (2 * a.edits + 1) * seqs.size() + 16, total = 0;
+    uint64_t total = 0;
     std::vector<uint64_t> qi, end;
     std::vector<uint8_t> st, ed;
-    for (;;) {
-        qi.resize(cap); end.resize(cap); st.resize(cap); ed.resize(cap);
-        const int rc = ix ? sufr_hip_edit(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.edits, a.max_occ, flags,
-                                          cap, qi.data(), st.data(), end.data(), ed.data(), &total)
-                          : sufr_file_edit(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), (uint32_t)a.edits, a.max_occ, flags,
-                                           cap, qi.data(), st.data(), end.data(), ed.data(), &total, a.threads);
-        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-        if (rc == SUFR_HIP_E_UNSUPPORTED && !(ctx && strstr(sufr_hip_last_error(ctx), "sort key"))) {
-            fprintf(stderr, "Error: %s: edit does not support files built with a seed mask\n", a.file.c_str());
-            return 1;
-        }
-        if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : "edit failed"); return 1; }
-        break;
-    }
+    if (!s.until_fits(a, "edit", (2 * a.edits + 1) * s.nq() + 16, total, [&](uint64_t cap, uint64_t* tot) {
+            qi.resize(cap); end.resize(cap); st.resize(cap); ed.resize(cap);
+            return s.ix ? sufr_hip_edit(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.edits, a.max_occ, flags, cap, qi.data(), st.data(),
+                                        end.data(), ed.data(), tot)
+                        : sufr_file_edit(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.edits, a.max_occ, flags, cap, qi.data(), st.data(), end.data(),
+                                         ed.data(), tot, a.threads);
+        }, "sort key")) return 1;
     // -c: the sizing call, then the runs
     std::vector<uint64_t> start(total + 1), coff(total + 1, 0);
     std::vector<uint32_t> cigar;
@@ -655,41 +637,28 @@ int cmd_edit(const QueryArgs& a)
         char err[512] = "";
         uint64_t runs = 0;
         for (int pass = 0; pass < 2; pass++) {
-            const int rc = ix ? sufr_hip_edit_trace(ctx, ix, (const uint8_t*)bytes.data(), off.data(), seqs.size(), total, qi.data(), st.data(),
-                                                    end.data(), ed.data(), cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs)
-                              : sufr_file_edit_trace(f, (const uint8_t*)bytes.data(), off.data(), seqs.size(), total, qi.data(), st.data(), end.data(),
-                                                     ed.data(), cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs,
-                                                     a.threads, err, sizeof err);
+            const int rc = s.ix ? sufr_hip_edit_trace(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), total, qi.data(), st.data(), end.data(), ed.data(),
+                                                      cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs)
+                                : sufr_file_edit_trace(s.f, s.q(), s.off.data(), s.nq(), total, qi.data(), st.data(), end.data(), ed.data(),
+                                                       cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs,
+                                                       a.threads, err, sizeof err);
             if (rc == SUFR_HIP_E_CAPACITY && pass == 0) { cigar.resize(runs); continue; }
-            if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : err); return 1; }
+            if (rc != 0) { fprintf(stderr, "Error: %s\n", s.ctx ? sufr_hip_last_error(s.ctx) : err); return 1; }
             break;
         }
     }
-    if (ix) sufr_hip_index_free(ix);
-    if (ctx) sufr_hip_destroy(ctx);
-    auto place = [&](uint64_t p) {
-        if (a.abs) fprintf(out.f, "%llu", (unsigned long long)p);
-        else {
-            const uint64_t i = sufr_file_sequence_of(f, p);
-            fprintf(out.f, "%s:%llu", sufr_file_sequence_name(f, i), (unsigned long long)(p - sufr_file_sequence_start(f, i)));
-        }
-    };
+    s.release_device();
     for (uint64_t t = 0; t < total; t++) {
-        fprintf(out.f, "%s\t%c\t", names[qi[t]].c_str(), st[t] ? '-' : '+');
-        place(end[t]);
-        fprintf(out.f, "\t%u", (unsigned)ed[t]);
+        fprintf(s.out.f, "%s\t%c\t%s\t%u", s.names[qi[t]].c_str(), st[t] ? '-' : '+', place(s.f, a.abs, end[t]).c_str(), (unsigned)ed[t]);
         if (a.cigar) {
-            fputc('\t', out.f);
-            place(start[t]);
-            fputc('\t', out.f);
+            fprintf(s.out.f, "\t%s\t", place(s.f, a.abs, start[t]).c_str());
             for (uint64_t r = coff[t]; r < coff[t + 1]; r++) {
                 const uint32_t op = cigar[r] & 15u;
-                fprintf(out.f, "%u%c", cigar[r] >> 4, op == 1 ? 'I' : op == 2 ? 'D' : op == 7 ? '=' : 'X');
+                fprintf(s.out.f, "%u%c", cigar[r] >> 4, op == 1 ? 'I' : op == 2 ? 'D' : op == 7 ? '=' : 'X');
             }
         }
-        fputc('\n', out.f);
+        fputc('\n', s.out.f);
     }
-    sufr_file_close(f);
     return 0;
 }
 

@@ -2,14 +2,14 @@
 // bit-parallel banded Sellers table per candidate, a radix sort and a unique step over the reported ends (included by
 // sufr_kernels.hip after sufr_approx.inc; include/sufr_edit.h, DESIGN.md section 16).
 //
-// k_mem_revcomp      (sufr_mem.inc) both strands: the doubled batch
-// k_approx_seeds     (sufr_approx.inc) the rank range of every seed, dead seeds marked
-// k_locate_counts / k_locate_scan / k_locate_apply (sufr_search.inc) the candidate starts; first synchronisation: the total
+// batch_extent / double_batch (sufr_search.inc) the ends of the batch (a synchronisation of its own); the sort-key check sits between
+//                    the two; the doubled batch with both strands
+// pigeonhole_candidates (sufr_approx.inc) k_approx_seeds, then the candidate starts; first synchronisation: their total
 // k_edit_count       SCAN_WGS workgroups over the candidates, 8 per lane (approx_walk8): candidate -> seed, diagonal
 //                    p = SA[..] - o_i; the pre-filter (a lower live piece whose seed matches at an indexed position on the
 //                    same diagonal has the same band: it reports); the band; the ends of [p + m - d, p + m + d] that pass,
 //                    counted per candidate (one byte each) and per workgroup
-// k_locate_scan      the emission total (second synchronisation) and the workgroup bases
+// scan_total         (sufr_search.inc) k_locate_scan: the emission total (second synchronisation) and the workgroup bases
 // k_edit_emit        the band again for the candidates that counted an end; the packed keys
 // sort_keys          (below) LSD radix sort over the key bits that vary
 // k_key_count / k_key_compact <KEY_UNIQUE>   the first key of every run of equal (query, strand, end): third synchronisation
@@ -359,61 +359,27 @@ int sufr_hip_edit_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     pl.err.clear();
     int rc;
     if ((rc = edit_args(ctx, ix, max_edits))) return rc;
-    if (!num_queries) return 0;
-    if ((rc = mem_bitmap(ctx, ix))) return rc;
-    // the byte count of the batch sizes the doubled batch
-    unsigned long long ends[2] = {0, 0};
-    const uint64_t* uoff = (const uint64_t*)d_offsets;
-    if (hipMemcpyAsync(&ends[0], uoff, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-        hipMemcpyAsync(&ends[1], uoff + num_queries, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-        hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("edit: reading the batch offsets failed"); return SUFR_HIP_E_HIP; }
-    if (ends[1] <= ends[0]) return 0;
+    QueryBatch b;
+    if ((rc = batch_extent(ctx, ix, d_queries, d_offsets, num_queries, "edit", b)) || !b.nb) return rc;
+    // the sort key: query (and strand) above the exclusive end above the distance; checked before the batch is doubled
     const bool both = (flags & SUFR_EDIT_BOTH_STRANDS) != 0;
-    const uint64_t nb = (ends[1] - ends[0]) * (both ? 2 : 1), nq = num_queries * (both ? 2 : 1);
-    // the sort key: query (and strand) above the exclusive end above the distance
+    const uint64_t nq = num_queries * (both ? 2 : 1);
     const uint32_t eb = bit_width_u64(ix->ix.n), ab = bit_width_u64(nq - 1);
     if (eb + ab + sufr::EDIT_VAL_BITS > 64) {
         pl.set_error("edit: " + std::to_string(nq) + " queries on a text of " + std::to_string(ix->ix.n) + " bytes need a sort key of " +
                      std::to_string(eb + ab + sufr::EDIT_VAL_BITS) + " bits; 64 are sorted");
         return SUFR_HIP_E_UNSUPPORTED;
     }
-    const uint32_t grid = (pl.num_cus ? pl.num_cus : 256u) * 8u;
-    const uint8_t* q = (const uint8_t*)d_queries;
-    const uint64_t* qoff = uoff;
-    if (both) {
-        if ((rc = pl.ensure(ctx->xq, nb + 8)) || (rc = pl.ensure(ctx->xoff, (nq + 1) * 8))) return rc;
-        hipLaunchKernelGGL(sufr::k_mem_revcomp, dim3(grid), dim3(256), 0, pl.stream, q, uoff, num_queries, (uint8_t*)ctx->xq.p,
-                           (uint64_t*)ctx->xoff.p);
-        q = (const uint8_t*)ctx->xq.p;
-        qoff = (const uint64_t*)ctx->xoff.p;
-    }
-    // rank range of every seed, then the exclusive scan of the live range sizes
-    const uint32_t np = max_edits + 1;
-    const uint64_t ns = nq * np, nblk = (ns + sufr::LOC_BLK - 1) / sufr::LOC_BLK;
-    if ((rc = pl.ensure(ctx->xlo, ns * 8)) || (rc = pl.ensure(ctx->xhi, ns * 8)) || (rc = pl.ensure(ctx->xcand, (ns + 1) * 8)) ||
-        (rc = pl.ensure(ctx->xsum, (nblk + 1 + sufr::SCAN_WGS + 1) * 8))) return rc;
-    uint64_t* rlo = (uint64_t*)ctx->xlo.p;
-    uint64_t* cand = (uint64_t*)ctx->xcand.p;
-    uint64_t* bsum = (uint64_t*)ctx->xsum.p;
-    uint64_t* cnt_sum = bsum + nblk + 1;
-    hipLaunchKernelGGL(sufr::k_approx_seeds, dim3(grid), dim3(256), 0, pl.stream, ix->ix, q, qoff, nq, (uint64_t)ix->built_mql, np, max_occ,
-                       rlo, (uint64_t*)ctx->xhi.p);
-    hipLaunchKernelGGL(sufr::k_locate_counts, dim3((uint32_t)nblk), dim3(256), 0, pl.stream, (const uint64_t*)rlo,
-                       (const uint64_t*)ctx->xhi.p, ns, (uint64_t)0, cand, bsum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, bsum, nblk, bsum + nblk);
-    hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((ns + 256) / 256)), dim3(256), 0, pl.stream, cand, ns, (const uint64_t*)bsum,
-                       (const uint64_t*)(bsum + nblk));
-    unsigned long long ncand = 0;
-    if ((rc = read_totals(pl, bsum + nblk, 1, &ncand, "edit: counting the candidates failed"))) return rc;
-    if (!ncand) return 0;
+    if (both && (rc = double_batch(ctx, b))) return rc;
+    sufr::ApproxBatch B;
+    Candidates c;
+    if ((rc = pigeonhole_candidates(ctx, ix, b, max_edits, max_occ, "edit", B, c)) || !c.ncand) return rc;
     // the ends every candidate reports, counted per candidate and per workgroup, then the emission total
-    if ((rc = pl.ensure(ctx->ecnt, ncand))) return rc;
-    const sufr::ApproxBatch B{q, qoff, nq, rlo, cand, ns, (const uint32_t*)ix->mem_bits, ix->built_mql, np, max_edits};
+    if ((rc = pl.ensure(ctx->ecnt, c.ncand))) return rc;
+    uint64_t* cnt_sum = c.cnt_sum;
     hipLaunchKernelGGL(sufr::k_edit_count, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, (uint8_t*)ctx->ecnt.p, cnt_sum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, (uint64_t)sufr::SCAN_WGS, cnt_sum + sufr::SCAN_WGS);
     unsigned long long nemit = 0;
-    if ((rc = read_totals(pl, cnt_sum + sufr::SCAN_WGS, 1, &nemit, "edit: counting the reported ends failed"))) return rc;
-    if (!nemit) return 0;
+    if ((rc = scan_total(pl, cnt_sum, sufr::SCAN_WGS, &nemit, "edit", "counting the reported ends failed")) || !nemit) return rc;
     // the keys, sorted over the bits that vary, and the first of every run
     if ((rc = pl.ensure(ctx->ekeys, nemit * 8)) || (rc = pl.ensure(ctx->ekeys2, nemit * 8)) ||
         (rc = pl.ensure(ctx->ehist, ((uint64_t)256 * sufr::SCAN_WGS + 1) * 8))) return rc;
@@ -425,9 +391,8 @@ int sufr_hip_edit_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     uint64_t* other = sorted == ka ? kb : ka;
     hipLaunchKernelGGL(sufr::k_key_count<sufr::KEY_UNIQUE>, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, (const uint64_t*)sorted,
                        (uint64_t)nemit, max_edits, cnt_sum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, (uint64_t)sufr::SCAN_WGS, cnt_sum + sufr::SCAN_WGS);
     unsigned long long nrec = 0;
-    if ((rc = read_totals(pl, cnt_sum + sufr::SCAN_WGS, 1, &nrec, "edit: counting the records failed"))) return rc;
+    if ((rc = scan_total(pl, cnt_sum, sufr::SCAN_WGS, &nrec, "edit", "counting the records failed"))) return rc;
     const uint64_t* recs = sorted;                                   // (all of them distinct: nothing to move)
     if (nrec < nemit) {
         hipLaunchKernelGGL(sufr::k_key_compact<sufr::KEY_UNIQUE>, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, (const uint64_t*)sorted,
@@ -438,8 +403,7 @@ int sufr_hip_edit_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     if (flags & SUFR_EDIT_LOCAL_MINIMA) {
         const uint64_t nuniq = nrec;
         hipLaunchKernelGGL(sufr::k_key_count<sufr::KEY_MINIMA>, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, recs, nuniq, max_edits, cnt_sum);
-        hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, (uint64_t)sufr::SCAN_WGS, cnt_sum + sufr::SCAN_WGS);
-        if ((rc = read_totals(pl, cnt_sum + sufr::SCAN_WGS, 1, &nrec, "edit: counting the local minima failed"))) return rc;
+        if ((rc = scan_total(pl, cnt_sum, sufr::SCAN_WGS, &nrec, "edit", "counting the local minima failed"))) return rc;
         if (nrec <= cap && nrec) {
             hipLaunchKernelGGL(sufr::k_key_compact<sufr::KEY_MINIMA>, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, recs, nuniq, max_edits,
                                (const uint64_t*)cnt_sum, other);
@@ -447,41 +411,20 @@ int sufr_hip_edit_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
         }
     }
     if (pl.debug) fprintf(stderr, "[sufr_hip debug] edit: d=%u max_occ=%llu flags=%u: %llu seeds, %llu candidates, %llu reported ends, %llu records\n",
-                          max_edits, (unsigned long long)max_occ, flags, (unsigned long long)ns, ncand, nemit, nrec);
-    if (total_out) *total_out = nrec;
-    if (nrec > cap) {
-        pl.set_error("edit: " + std::to_string(nrec) + " records, room for " + std::to_string(cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    if (!nrec) return 0;
-    if (!d_query || !d_strand || !d_end || !d_edits) return SUFR_HIP_E_INVALID;
-    hipLaunchKernelGGL(sufr::k_edit_records, dim3(grid), dim3(256), 0, pl.stream, recs, (uint64_t)nrec, eb, (uint32_t)both, (uint64_t*)d_query,
+                          max_edits, (unsigned long long)max_occ, flags, (unsigned long long)B.ns, c.ncand, nemit, nrec);
+    if ((rc = records_fit(pl, "edit", "records", nrec, cap, total_out)) || !nrec) return rc;
+    if (any_null({d_query, d_strand, d_end, d_edits})) return SUFR_HIP_E_INVALID;
+    hipLaunchKernelGGL(sufr::k_edit_records, dim3(b.grid), dim3(256), 0, pl.stream, recs, (uint64_t)nrec, eb, (uint32_t)both, (uint64_t*)d_query,
                        (uint8_t*)d_strand, (uint64_t*)d_end, (uint8_t*)d_edits);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pl.set_error(std::string("edit: ") + hipGetErrorString(e)); return SUFR_HIP_E_HIP; }
-    return 0;
+    return launch_status(pl, "edit");
 }
 
 int sufr_hip_edit(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* queries, const uint64_t* offsets, uint64_t num_queries,
                   uint32_t max_edits, uint64_t max_occ, uint32_t flags, uint64_t cap, uint64_t* query, uint8_t* strand, uint64_t* end,
                   uint8_t* edits, uint64_t* total_out)
 {
-    if (total_out) *total_out = 0;
-    if (!ctx || !ix || (num_queries && !offsets)) return SUFR_HIP_E_INVALID;
-    ctx->pl.err.clear();
-    if (const int rc = edit_args(ctx, ix, max_edits)) return rc;
-    if (!num_queries) return 0;
-    const uint64_t qbytes = offsets[num_queries], obytes = (num_queries + 1) * 8;
-    // one allocation: queries | offsets | records (cap of each)
-    const uint64_t o_at = (qbytes + 7) / 8 * 8, q_at = o_at + obytes, end_at = q_at + cap * 8, st_at = end_at + cap * 8, ed_at = st_at + cap;
-    uint8_t* d;
-    int rc = stage_batch(ctx, "k-difference", queries, offsets, num_queries, o_at, ed_at + cap + 8, &d);
-    uint64_t total = 0;
-    if (!rc) rc = sufr_hip_edit_device(ctx, ix, d, d + o_at, num_queries, max_edits, max_occ, flags, cap, d + q_at, d + st_at, d + end_at,
-                                       d + ed_at, &total);
-    if (total_out) *total_out = total;
-    return unstage_batch(ctx, "k-difference", d, rc, {{query, q_at, total * 8}, {strand, st_at, total}, {end, end_at, total * 8},
-                                                      {edits, ed_at, total}});
+    return pigeonhole_host(ctx, ix, queries, offsets, num_queries, max_edits, max_occ, flags, cap, query, strand, end, edits, total_out,
+                           "k-difference", edit_args, sufr_hip_edit_device);
 }
 
 }  // extern "C"

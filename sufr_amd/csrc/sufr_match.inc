@@ -11,7 +11,7 @@
 // k_smem_gather      the SMEM slices packed into one query batch, searched by the unchanged sufr_hip_search_batch_device
 // No MFMA, no LDS beyond the scan words, no scratch.
 // Its own: match_stat, the SMEM rule (match_flags8) and the three SMEM kernels.  The search, last_le, wg_scan, scan_chunk
-// (SCAN_WGS workgroups), query_check, read_totals and the staging of the host-pointer entry point are sufr_search.inc's.
+// (SCAN_WGS workgroups), query_check, read_totals, the record epilogue and staged_records are sufr_search.inc's.
 
 namespace sufr {
 
@@ -128,7 +128,7 @@ int sufr_hip_matching_stats_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, 
     if (const int rc = query_check(ctx, ix, "matching statistics")) return rc;
     if (!num_queries) return 0;
     // latency-bound lanes: 8 workgroups of 4 waves per CU, looping over the batch
-    const uint32_t grid = (ctx->pl.num_cus ? ctx->pl.num_cus : 256u) * 8u;
+    const uint32_t grid = batch_grid(ctx->pl);
     hipLaunchKernelGGL(sufr::k_matching_stats, dim3(grid), dim3(256), 0, ctx->pl.stream, ix->ix, (const uint8_t*)d_queries,
                        (const uint64_t*)d_offsets, num_queries, effective_mql(ix, 0, 0), (uint32_t*)d_ms);
     const hipError_t e = hipGetLastError();
@@ -161,15 +161,10 @@ int sufr_hip_smems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const voi
     hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, G, tot);
     hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, len_sum, G, tot + 1);
     unsigned long long totals[2] = {0, 0};
-    if ((rc = read_totals(pl, tot, 2, totals, "smems: counting the SMEMs failed"))) return rc;
+    if ((rc = read_totals(pl, tot, 2, totals, "smems", "counting the SMEMs failed"))) return rc;
     const uint64_t nsm = totals[0], nbytes = totals[1];
-    if (total_out) *total_out = nsm;
-    if (nsm > cap) {
-        pl.set_error("smems: " + std::to_string(nsm) + " SMEMs, room for " + std::to_string(cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    if (!nsm) return 0;
-    if (!d_query || !d_query_offset || !d_length || !d_rank_lo || !d_rank_hi) return SUFR_HIP_E_INVALID;
+    if ((rc = records_fit(pl, "smems", "SMEMs", nsm, cap, total_out)) || !nsm) return rc;
+    if (any_null({d_query, d_query_offset, d_length, d_rank_lo, d_rank_hi})) return SUFR_HIP_E_INVALID;
     if ((rc = pl.ensure(ctx->mpoff, (nsm + 1) * 8)) || (rc = pl.ensure(ctx->mbytes, nbytes))) return rc;
     uint64_t* slice_off = (uint64_t*)ctx->mpoff.p;
     hipLaunchKernelGGL(sufr::k_smem_emit, dim3((uint32_t)G), dim3(256), 0, pl.stream, ms, off, num_queries, min_len,
@@ -180,8 +175,7 @@ int sufr_hip_smems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const voi
     hipLaunchKernelGGL(sufr::k_smem_gather, dim3((uint32_t)gw), dim3(256), 0, pl.stream, (const uint8_t*)d_queries, off,
                        (const uint64_t*)d_query, (const uint32_t*)d_query_offset, (const uint32_t*)d_length, slice_off, nsm, nbytes,
                        (uint8_t*)ctx->mbytes.p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pl.set_error(std::string("smems: ") + hipGetErrorString(e)); return SUFR_HIP_E_HIP; }
+    if ((rc = launch_status(pl, "smems"))) return rc;
     // the rank range of every SMEM: the unchanged batched search of the packed slices (the build's cap applies as in count)
     return sufr_hip_search_batch_device(ctx, ix, ctx->mbytes.p, slice_off, nsm, 0, 0, d_rank_lo, d_rank_hi);
 }
@@ -196,18 +190,11 @@ int sufr_hip_smems(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* q
     if (const int rc = query_check(ctx, ix, "matching statistics")) return rc;
     if (min_len == 0) { ctx->pl.set_error("smems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
     if (!num_queries) return 0;
-    const uint64_t qbytes = offsets[num_queries], obytes = (num_queries + 1) * 8;
-    // one allocation: queries | offsets | ms | records (cap of each)
-    const uint64_t o_at = (qbytes + 7) / 8 * 8, ms_at = o_at + obytes, q_at = ms_at + (qbytes * 4 + 7) / 8 * 8;
-    const uint64_t qo_at = q_at + cap * 8, len_at = qo_at + cap * 4, lo_at = len_at + cap * 4, hi_at = lo_at + cap * 8;
-    uint8_t* d;
-    int rc = stage_batch(ctx, "SMEM", queries, offsets, num_queries, o_at, hi_at + cap * 8 + 8, &d);
-    uint64_t total = 0;
-    if (!rc) rc = sufr_hip_smems_device(ctx, ix, d, d + o_at, num_queries, min_len, d + ms_at, cap, d + q_at, d + qo_at, d + len_at,
-                                        d + lo_at, d + hi_at, &total);
-    if (total_out) *total_out = total;
-    return unstage_batch(ctx, "SMEM", d, rc, {{query, q_at, total * 8}, {query_offset, qo_at, total * 4}, {length, len_at, total * 4},
-                                              {rank_lo, lo_at, total * 8}, {rank_hi, hi_at, total * 8}});
+    // the matching statistics (4 bytes per query byte) stay on the device: they ride behind the record columns
+    return staged_records(ctx, "SMEM", queries, offsets, num_queries, cap, {{query, 8}, {query_offset, 4}, {length, 4}, {rank_lo, 8}, {rank_hi, 8}},
+                          offsets[num_queries] * 4, total_out, [&](const void* d_q, const void* d_off, void* const* col, uint64_t* total) {
+        return sufr_hip_smems_device(ctx, ix, d_q, d_off, num_queries, min_len, col[5], cap, col[0], col[1], col[2], col[3], col[4], total);
+    });
 }
 
 }  // extern "C"

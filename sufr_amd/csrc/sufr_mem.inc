@@ -1,20 +1,21 @@
 // sufr_mem.inc -- maximal exact matches (MEMs) of a query batch on a device-resident index (included by sufr_kernels.hip
 // after sufr_match.inc; include/sufr_mem.h, DESIGN.md section 14).
 //
-// k_mem_bitmap       once per index whose array leaves positions out: one lane per rank sets bit SA[r] (atomicOr on u32 words)
-// k_mem_revcomp      both strands: the doubled batch, query i as it is then its reverse complement, with the new offsets
+// take_batch         (sufr_search.inc) the bitmap of the index (k_mem_bitmap, once), the two ends of the batch (a
+//                    synchronisation of its own) and, with both strands, the doubled batch (k_mem_revcomp)
 // k_mem_ranges       one lane per query offset (grid-stride): the rank range of the k'-prefix Q[j..j+k') found in place by
-//                    search_range (sufr_search.inc, what k_search_batch runs); an empty range when j + k > m or the range
-//                    holds more than max_occ suffixes
-// k_locate_counts / k_locate_scan / k_locate_apply (sufr_search.inc) exclusive scan of the range sizes: the candidate starts;
-//                    one synchronisation reads the candidate total
+//                    search_range (what k_search_batch runs); an empty range when j + k > m or the range holds more than
+//                    max_occ suffixes
+// candidate_starts   (sufr_search.inc) k_locate_counts / k_locate_scan / k_locate_apply: the exclusive scan of the range sizes
+//                    is the candidate starts; one synchronisation reads the candidate total
 // k_mem_count        1024 workgroups over the candidates, 8 per lane: candidate -> offset by binary search of the starts,
 //                    p = SA[lo + ...], the left condition (one query byte, one text byte, one bitmap bit); counts per workgroup
-// k_locate_scan      the MEM total (second synchronisation) and the workgroup bases
+// scan_total         (sufr_search.inc) k_locate_scan: the MEM total (second synchronisation) and the workgroup bases
 // k_mem_emit         the flags again, scanned in the workgroup; every MEM is extended with 8-byte compares and written
 // No MFMA, no LDS beyond the scan words, no scratch.
 // From sufr_search.inc: search_range, common_prefix, last_le (offset -> query, candidate -> offset), wg_scan and scan_chunk
-// (SCAN_WGS workgroups), query_check, read_totals and the staging of the host-pointer entry point.
+// (SCAN_WGS workgroups); the host side of the driver (query_check, take_batch, candidate_starts, scan_total, records_fit,
+// any_null, launch_status) and staged_records for the host-pointer entry point.
 
 namespace sufr {
 
@@ -28,37 +29,6 @@ struct MemBatch {
     const uint32_t* bits;       // indexed positions, or nullptr: every position is indexed
     uint32_t min_len, kk;       // k and k' = min(k, L)
 };
-
-__global__ __launch_bounds__(256) void k_mem_bitmap(SearchIndex ix, uint32_t* __restrict__ bits)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < ix.s; r += stride) {
-        const uint64_t p = ix.suffix(r);
-        atomicOr(&bits[p >> 5], 1u << (p & 31));
-    }
-}
-
-__device__ __forceinline__ uint8_t mem_complement(uint8_t c)
-{
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
-}
-
-__global__ __launch_bounds__(256) void k_mem_revcomp(const uint8_t* __restrict__ queries, const uint64_t* __restrict__ qoff, uint64_t nq,
-                                                     uint8_t* __restrict__ dst, uint64_t* __restrict__ doff)
-{
-    const uint64_t g0 = qoff[0], g_end = qoff[nq], stride = (uint64_t)gridDim.x * 256;
-    const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    for (uint64_t i = tid; i <= nq; i += stride) {
-        if (i < nq) { doff[2 * i] = 2 * (qoff[i] - g0); doff[2 * i + 1] = qoff[i] + qoff[i + 1] - 2 * g0; }
-        else doff[2 * nq] = 2 * (g_end - g0);
-    }
-    for (uint64_t g = g0 + tid; g < g_end; g += stride) {
-        const uint64_t a = last_le(qoff, 0, nq, g), b = qoff[a], e = qoff[a + 1];
-        const uint8_t c = queries[g];
-        dst[2 * (b - g0) + (g - b)] = c;
-        dst[b + e - 2 * g0 + (e - 1 - g)] = mem_complement(c);
-    }
-}
 
 __global__ __launch_bounds__(256) void k_mem_ranges(SearchIndex ix, const uint8_t* __restrict__ queries, const uint64_t* __restrict__ qoff,
                                                     uint64_t nq, uint64_t mql, uint32_t min_len, uint32_t kk, uint64_t max_occ,
@@ -153,34 +123,6 @@ __global__ __launch_bounds__(256) void k_mem_emit(SearchIndex ix, MemBatch B, co
 
 }  // namespace sufr
 
-namespace {
-
-// the bitmap of the indexed positions, once per index (none when every position is indexed)
-int mem_bitmap(sufr_hip_ctx* ctx, const sufr_hip_index* ix)
-{
-    if (ix->ix.s >= ix->ix.n) return 0;
-    std::lock_guard<std::mutex> lock(ix->mem_mu);
-    if (ix->mem_bits_done) return 0;
-    sufr::Pipeline& pl = ctx->pl;
-    const uint64_t words = (ix->ix.n + 31) / 32;
-    void* bits = nullptr;
-    if (hipMalloc(&bits, words * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        pl.set_error("mems: hipMalloc of the indexed-position bitmap (" + std::to_string(words * 4) + " bytes) failed");
-        return SUFR_HIP_E_NOMEM;
-    }
-    const uint32_t grid = (pl.num_cus ? pl.num_cus : 256u) * 8u;
-    bool ok = hipMemsetAsync(bits, 0, words * 4, pl.stream) == hipSuccess;
-    if (ok) hipLaunchKernelGGL(sufr::k_mem_bitmap, dim3(grid), dim3(256), 0, pl.stream, ix->ix, (uint32_t*)bits);
-    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(pl.stream) == hipSuccess;   // other streams may use it next
-    if (!ok) { (void)hipFree(bits); pl.set_error("mems: building the indexed-position bitmap failed"); return SUFR_HIP_E_HIP; }
-    ix->mem_bits = bits;
-    ix->mem_bits_done = true;
-    return 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 int sufr_hip_mems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets,
@@ -192,68 +134,30 @@ int sufr_hip_mems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void
     if (!ctx || !ix || (num_queries && (!d_queries || !d_offsets))) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
     pl.err.clear();
-    if (const int rc = query_check(ctx, ix, "MEMs")) return rc;
-    if (min_len == 0) { ctx->pl.set_error("mems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
-    if (!num_queries) return 0;
     int rc;
-    if ((rc = mem_bitmap(ctx, ix))) return rc;
-    // the byte count of the batch sizes the scratch
-    unsigned long long ends[2] = {0, 0};
-    const uint64_t* uoff = (const uint64_t*)d_offsets;
-    if (hipMemcpyAsync(&ends[0], uoff, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-        hipMemcpyAsync(&ends[1], uoff + num_queries, 8, hipMemcpyDeviceToHost, pl.stream) != hipSuccess ||
-        hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("mems: reading the batch offsets failed"); return SUFR_HIP_E_HIP; }
-    if (ends[1] <= ends[0]) return 0;
-    const bool both = (flags & SUFR_MEM_BOTH_STRANDS) != 0;
-    const uint64_t nb = (ends[1] - ends[0]) * (both ? 2 : 1), nq = num_queries * (both ? 2 : 1);
-    const uint32_t grid = (pl.num_cus ? pl.num_cus : 256u) * 8u;
-    const uint8_t* q = (const uint8_t*)d_queries;
-    const uint64_t* qoff = uoff;
-    if (both) {
-        if ((rc = pl.ensure(ctx->xq, nb + 8)) || (rc = pl.ensure(ctx->xoff, (nq + 1) * 8))) return rc;
-        hipLaunchKernelGGL(sufr::k_mem_revcomp, dim3(grid), dim3(256), 0, pl.stream, q, uoff, num_queries, (uint8_t*)ctx->xq.p,
-                           (uint64_t*)ctx->xoff.p);
-        q = (const uint8_t*)ctx->xq.p;
-        qoff = (const uint64_t*)ctx->xoff.p;
-    }
-    // rank range of every offset's k'-prefix, then the exclusive scan of the range sizes
+    if ((rc = query_check(ctx, ix, "MEMs"))) return rc;
+    if (min_len == 0) { pl.set_error("mems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
+    QueryBatch b;
+    if ((rc = take_batch(ctx, ix, d_queries, d_offsets, num_queries, (flags & SUFR_MEM_BOTH_STRANDS) != 0, "mems", b)) || !b.nb) return rc;
+    // rank range of every offset's k'-prefix: the candidates
     const uint64_t L = ix->built_mql;
     const uint32_t kk = L > 0 && L < min_len ? (uint32_t)L : min_len;
-    const uint64_t nblk = (nb + sufr::LOC_BLK - 1) / sufr::LOC_BLK;
-    if ((rc = pl.ensure(ctx->xlo, nb * 8)) || (rc = pl.ensure(ctx->xhi, nb * 8)) || (rc = pl.ensure(ctx->xcand, (nb + 1) * 8)) ||
-        (rc = pl.ensure(ctx->xsum, (nblk + 1 + sufr::SCAN_WGS + 1) * 8))) return rc;
-    uint64_t* rlo = (uint64_t*)ctx->xlo.p;
-    uint64_t* cand = (uint64_t*)ctx->xcand.p;
-    uint64_t* bsum = (uint64_t*)ctx->xsum.p;
-    uint64_t* cnt_sum = bsum + nblk + 1;
-    hipLaunchKernelGGL(sufr::k_mem_ranges, dim3(grid), dim3(256), 0, pl.stream, ix->ix, q, qoff, nq, effective_mql(ix, 0, 0), min_len, kk,
-                       max_occ, rlo, (uint64_t*)ctx->xhi.p);
-    hipLaunchKernelGGL(sufr::k_locate_counts, dim3((uint32_t)nblk), dim3(256), 0, pl.stream, (const uint64_t*)rlo,
-                       (const uint64_t*)ctx->xhi.p, nb, (uint64_t)0, cand, bsum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, bsum, nblk, bsum + nblk);
-    hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((nb + 256) / 256)), dim3(256), 0, pl.stream, cand, nb, (const uint64_t*)bsum,
-                       (const uint64_t*)(bsum + nblk));
-    unsigned long long ncand = 0;
-    if ((rc = read_totals(pl, bsum + nblk, 1, &ncand, "mems: counting the candidates failed"))) return rc;
-    if (!ncand) return 0;
+    Candidates c;
+    rc = candidate_starts(ctx, b.nb, "mems", [&](uint64_t* rlo, uint64_t* rhi) {
+        hipLaunchKernelGGL(sufr::k_mem_ranges, dim3(b.grid), dim3(256), 0, pl.stream, ix->ix, b.q, b.qoff, b.nq, effective_mql(ix, 0, 0), min_len,
+                           kk, max_occ, rlo, rhi);
+    }, c);
+    if (rc || !c.ncand) return rc;
     // the left condition per candidate, counted per workgroup, then the MEM total
-    const sufr::MemBatch B{q, qoff, nq, rlo, cand, nb, (const uint32_t*)ix->mem_bits, min_len, kk};
-    hipLaunchKernelGGL(sufr::k_mem_count, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, cnt_sum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, (uint64_t)sufr::SCAN_WGS, cnt_sum + sufr::SCAN_WGS);
+    const sufr::MemBatch B{b.q, b.qoff, b.nq, c.rlo, c.cand, b.nb, (const uint32_t*)ix->mem_bits, min_len, kk};
+    hipLaunchKernelGGL(sufr::k_mem_count, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, c.cnt_sum);
     unsigned long long nmem = 0;
-    if ((rc = read_totals(pl, cnt_sum + sufr::SCAN_WGS, 1, &nmem, "mems: counting the MEMs failed"))) return rc;
-    if (total_out) *total_out = nmem;
-    if (nmem > cap) {
-        pl.set_error("mems: " + std::to_string(nmem) + " MEMs, room for " + std::to_string(cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    if (!nmem) return 0;
-    if (!d_query || !d_query_offset || !d_strand || !d_length || !d_position) return SUFR_HIP_E_INVALID;
-    hipLaunchKernelGGL(sufr::k_mem_emit, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, (const uint64_t*)cnt_sum, (uint32_t)both,
+    if ((rc = scan_total(pl, c.cnt_sum, sufr::SCAN_WGS, &nmem, "mems", "counting the MEMs failed"))) return rc;
+    if ((rc = records_fit(pl, "mems", "MEMs", nmem, cap, total_out)) || !nmem) return rc;
+    if (any_null({d_query, d_query_offset, d_strand, d_length, d_position})) return SUFR_HIP_E_INVALID;
+    hipLaunchKernelGGL(sufr::k_mem_emit, dim3(sufr::SCAN_WGS), dim3(256), 0, pl.stream, ix->ix, B, (const uint64_t*)c.cnt_sum, (uint32_t)b.both,
                        (uint64_t*)d_query, (uint32_t*)d_query_offset, (uint8_t*)d_strand, (uint32_t*)d_length, (uint64_t*)d_position);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pl.set_error(std::string("mems: ") + hipGetErrorString(e)); return SUFR_HIP_E_HIP; }
-    return 0;
+    return launch_status(pl, "mems");
 }
 
 int sufr_hip_mems(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* queries, const uint64_t* offsets, uint64_t num_queries,
@@ -266,18 +170,10 @@ int sufr_hip_mems(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* qu
     if (const int rc = query_check(ctx, ix, "MEMs")) return rc;
     if (min_len == 0) { ctx->pl.set_error("mems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
     if (!num_queries) return 0;
-    const uint64_t qbytes = offsets[num_queries], obytes = (num_queries + 1) * 8;
-    // one allocation: queries | offsets | records (cap of each)
-    const uint64_t o_at = (qbytes + 7) / 8 * 8, q_at = o_at + obytes, pos_at = q_at + cap * 8, qo_at = pos_at + cap * 8;
-    const uint64_t len_at = qo_at + cap * 4, st_at = len_at + cap * 4;
-    uint8_t* d;
-    int rc = stage_batch(ctx, "MEM", queries, offsets, num_queries, o_at, st_at + cap + 8, &d);
-    uint64_t total = 0;
-    if (!rc) rc = sufr_hip_mems_device(ctx, ix, d, d + o_at, num_queries, min_len, max_occ, flags, cap, d + q_at, d + qo_at, d + st_at,
-                                       d + len_at, d + pos_at, &total);
-    if (total_out) *total_out = total;
-    return unstage_batch(ctx, "MEM", d, rc, {{query, q_at, total * 8}, {query_offset, qo_at, total * 4}, {strand, st_at, total},
-                                             {length, len_at, total * 4}, {position, pos_at, total * 8}});
+    return staged_records(ctx, "MEM", queries, offsets, num_queries, cap, {{query, 8}, {query_offset, 4}, {strand, 1}, {length, 4}, {position, 8}},
+                          0, total_out, [&](const void* d_q, const void* d_off, void* const* col, uint64_t* total) {
+        return sufr_hip_mems_device(ctx, ix, d_q, d_off, num_queries, min_len, max_occ, flags, cap, col[0], col[1], col[2], col[3], col[4], total);
+    });
 }
 
 }  // extern "C"

@@ -435,6 +435,60 @@ uint8_t revcomp_byte(uint8_t c)
     switch (c) { case 'A': return 'T'; case 'T': return 'A'; case 'C': return 'G'; case 'G': return 'C'; default: return c; }
 }
 
+// the batch in record order, offsets from 0: query i, then (both strands) its reverse complement as query 2i + 1, in `dbl`;
+// one strand: the caller's bytes in place.  Returns the first byte of query 0.
+const uint8_t* strand_batch(const uint8_t* queries, const uint64_t* offsets, uint64_t nq, bool both, std::vector<uint8_t>& dbl,
+                            std::vector<uint64_t>& off)
+{
+    const uint64_t g0 = offsets[0], nb = offsets[nq] - g0;
+    const uint8_t* qb = queries + g0;
+    if (!both) {
+        off.resize(nq + 1);
+        for (uint64_t i = 0; i <= nq; i++) off[i] = offsets[i] - g0;
+        return qb;
+    }
+    dbl.resize(2 * nb);
+    off.resize(2 * nq + 1);
+    for (uint64_t i = 0; i < nq; i++) {
+        const uint64_t a = offsets[i] - g0, b = offsets[i + 1] - g0;
+        off[2 * i] = 2 * a; off[2 * i + 1] = a + b;
+        memcpy(dbl.data() + 2 * a, qb + a, (size_t)(b - a));
+        for (uint64_t t = 0; t < b - a; t++) dbl[a + b + t] = revcomp_byte(qb[b - 1 - t]);
+    }
+    off[2 * nq] = 2 * nb;
+    return dbl.data();
+}
+
+// query a of a strand batch as the records name it
+struct QueryStrand { uint64_t query; uint8_t strand; };
+QueryStrand query_strand(bool both, uint64_t a) { return {both ? a >> 1 : a, (uint8_t)(both ? a & 1 : 0)}; }
+
+// piece i of the np pigeonhole pieces of a query of m bytes: its offset, its length, and how many of its bytes are searched
+// (k' = min(len, L) on a build capped at L)
+struct Piece { uint64_t o, len, kk; };
+Piece piece_of(uint32_t i, uint64_t m, uint32_t np, uint64_t L)
+{
+    const uint64_t o = (uint64_t)i * m / np, len = (uint64_t)(i + 1) * m / np - o;
+    return {o, len, L > 0 && L < len ? L : len};
+}
+
+// The records of the chunks, concatenated in order, against the room of the caller: the total, E_CAPACITY when it does not
+// fit, nothing to write for 0, E_INVALID for a null column; else put(t, record) writes record t to the columns.
+template <typename Rec, typename Put>
+int collect_records(const std::vector<std::vector<Rec>>& recs, uint64_t cap, uint64_t* total_out, bool null_column, Put put)
+{
+    uint64_t total = 0;
+    for (const auto& v : recs) total += v.size();
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (null_column) return SUFR_HIP_E_INVALID;
+    uint64_t t = 0;
+    for (const auto& v : recs)
+        for (const Rec& x : v) put(t++, x);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -447,27 +501,11 @@ int sufr_file_mems(const sufr_file* f, const uint8_t* queries, const uint64_t* o
     if (const int rc = match_args(f, queries, offsets, nq)) return rc;
     if (min_len == 0) return SUFR_HIP_E_INVALID;
     if (!nq || offsets[nq] == offsets[0]) return 0;
-    // the batch in record order: query i, then (both strands) its reverse complement as query 2i + 1
     const bool both = (flags & SUFR_MEM_BOTH_STRANDS) != 0;
-    const uint64_t g0 = offsets[0], nb = offsets[nq] - g0;
-    const uint8_t* qb = queries + g0;
     std::vector<uint8_t> dbl;
-    std::vector<uint64_t> off(nq + 1);
-    for (uint64_t i = 0; i <= nq; i++) off[i] = offsets[i] - g0;
-    uint64_t nb2 = nb, nq2 = nq;
-    if (both) {
-        dbl.resize(2 * nb);
-        std::vector<uint64_t> o2(2 * nq + 1);
-        for (uint64_t i = 0; i < nq; i++) {
-            const uint64_t a = off[i], b = off[i + 1];
-            o2[2 * i] = 2 * a; o2[2 * i + 1] = a + b;
-            memcpy(dbl.data() + 2 * a, qb + a, (size_t)(b - a));
-            for (uint64_t t = 0; t < b - a; t++) dbl[a + b + t] = revcomp_byte(qb[b - 1 - t]);
-        }
-        o2[2 * nq] = 2 * nb;
-        off.swap(o2);
-        qb = dbl.data(); nb2 = 2 * nb; nq2 = 2 * nq;
-    }
+    std::vector<uint64_t> off;
+    const uint8_t* qb = strand_batch(queries, offsets, nq, both, dbl, off);
+    const uint64_t nq2 = off.size() - 1, nb2 = off[nq2];
     const std::vector<uint64_t>& bits = indexed_bits(*f);
     const uint64_t n = f->meta.text_len, L = f->meta.max_query_len;
     const uint32_t kk = L > 0 && L < min_len ? (uint32_t)L : min_len;                    // k' of the contract
@@ -492,20 +530,14 @@ int sufr_file_mems(const sufr_file* f, const uint8_t* queries, const uint64_t* o
                 uint64_t l = kk;                                                         // the slice matched
                 while (l < lim && qb[g + l] == text[p + l]) l++;
                 if (l < min_len) continue;
-                out.push_back({both ? a >> 1 : a, (uint32_t)j, (uint8_t)(both ? a & 1 : 0), (uint32_t)l, p});
+                const QueryStrand qs = query_strand(both, a);
+                out.push_back({qs.query, (uint32_t)j, qs.strand, (uint32_t)l, p});
             }
         }
     });
-    uint64_t total = 0;
-    for (const auto& v : recs) total += v.size();
-    if (total_out) *total_out = total;
-    if (total > cap) return SUFR_HIP_E_CAPACITY;
-    if (!total) return 0;
-    if (!query || !qoff || !strand || !len || !position) return SUFR_HIP_E_INVALID;
-    uint64_t t = 0;
-    for (const auto& v : recs)
-        for (const MemRec& x : v) { query[t] = x.query; qoff[t] = x.qoff; strand[t] = x.strand; len[t] = x.len; position[t] = x.pos; t++; }
-    return 0;
+    return collect_records(recs, cap, total_out, !query || !qoff || !strand || !len || !position, [&](uint64_t t, const MemRec& x) {
+        query[t] = x.query; qoff[t] = x.qoff; strand[t] = x.strand; len[t] = x.len; position[t] = x.pos;
+    });
 }
 
 }  // extern "C"
@@ -514,30 +546,6 @@ int sufr_file_mems(const sufr_file* f, const uint8_t* queries, const uint64_t* o
 namespace {
 
 struct ApproxRec { uint64_t query; uint8_t strand; uint64_t pos; uint8_t mism; };
-
-// the batch in record order, offsets from 0: query i, then (both strands) its reverse complement as query 2i + 1, in `dbl`;
-// one strand: the caller's bytes in place.  Returns the first byte of query 0.
-const uint8_t* strand_batch(const uint8_t* queries, const uint64_t* offsets, uint64_t nq, bool both, std::vector<uint8_t>& dbl,
-                            std::vector<uint64_t>& off)
-{
-    const uint64_t g0 = offsets[0], nb = offsets[nq] - g0;
-    const uint8_t* qb = queries + g0;
-    if (!both) {
-        off.resize(nq + 1);
-        for (uint64_t i = 0; i <= nq; i++) off[i] = offsets[i] - g0;
-        return qb;
-    }
-    dbl.resize(2 * nb);
-    off.resize(2 * nq + 1);
-    for (uint64_t i = 0; i < nq; i++) {
-        const uint64_t a = offsets[i] - g0, b = offsets[i + 1] - g0;
-        off[2 * i] = 2 * a; off[2 * i + 1] = a + b;
-        memcpy(dbl.data() + 2 * a, qb + a, (size_t)(b - a));
-        for (uint64_t t = 0; t < b - a; t++) dbl[a + b + t] = revcomp_byte(qb[b - 1 - t]);
-    }
-    off[2 * nq] = 2 * nb;
-    return dbl.data();
-}
 
 }  // namespace
 
@@ -565,53 +573,47 @@ int sufr_file_approx(const sufr_file* f, const uint8_t* queries, const uint64_t*
     std::vector<std::vector<ApproxRec>> recs(nchunks);
     parallel_chunks(nq2, chunk, threads, [&](uint64_t b, uint64_t e) {
         std::vector<ApproxRec>& out = recs[b / chunk];
-        uint64_t o[SUFR_APPROX_MAX_MISMATCHES + 2], lo[SUFR_APPROX_MAX_MISMATCHES + 1], hi[SUFR_APPROX_MAX_MISMATCHES + 1];
+        Piece pc[SUFR_APPROX_MAX_MISMATCHES + 1];
+        uint64_t lo[SUFR_APPROX_MAX_MISMATCHES + 1], hi[SUFR_APPROX_MAX_MISMATCHES + 1];
         bool live[SUFR_APPROX_MAX_MISMATCHES + 1];
         for (uint64_t a = b; a < e; a++) {
             const uint8_t* Q = qb + off[a];
             const uint64_t m = off[a + 1] - off[a];
             if (m < np || m > n) continue;
-            for (uint32_t i = 0; i <= np; i++) o[i] = (uint64_t)i * m / np;
             for (uint32_t i = 0; i < np; i++) {                              // the rank range of every seed
-                const uint64_t len = o[i + 1] - o[i], kk = L > 0 && L < len ? L : len;
+                pc[i] = piece_of(i, m, np, L);
                 lo[i] = hi[i] = 0;
-                (void)sufr_file_search(f, Q + o[i], (size_t)kk, 0, 0, &lo[i], &hi[i]);
+                (void)sufr_file_search(f, Q + pc[i].o, (size_t)pc[i].kk, 0, 0, &lo[i], &hi[i]);
                 live[i] = !max_occ || hi[i] - lo[i] <= max_occ;
             }
             for (uint32_t i = 0; i < np; i++) {
                 if (!live[i]) continue;
-                const uint64_t len = o[i + 1] - o[i], kk = L > 0 && L < len ? L : len;
+                const uint64_t o = pc[i].o, len = pc[i].len, kk = pc[i].kk;
                 for (uint64_t r = lo[i]; r < hi[i]; r++) {
                     const uint64_t sp = sufr_file_suffix(f, r);
-                    if (sp < o[i]) continue;                                 // the window would start before the text
-                    const uint64_t p = sp - o[i];
+                    if (sp < o) continue;                                    // the window would start before the text
+                    const uint64_t p = sp - o;
                     if (p + m > n) continue;
-                    if (kk < len && memcmp(Q + o[i] + kk, text + sp + kk, (size_t)(len - kk)) != 0) continue;
+                    if (kk < len && memcmp(Q + o + kk, text + sp + kk, (size_t)(len - kk)) != 0) continue;
                     bool lower = false;                                      // a lower piece anchors p: it reports the window
                     for (uint32_t j = 0; j < i && !lower; j++) {
-                        const uint64_t pj = p + o[j];
+                        const uint64_t pj = p + pc[j].o;
                         lower = live[j] && (bits.empty() || (bits[pj >> 6] >> (pj & 63) & 1)) &&
-                                memcmp(Q + o[j], text + pj, (size_t)(o[j + 1] - o[j])) == 0;
+                                memcmp(Q + pc[j].o, text + pj, (size_t)pc[j].len) == 0;
                     }
                     if (lower) continue;
                     uint32_t h = 0;
                     for (uint64_t t = 0; t < m && h <= d; t++) h += Q[t] != text[p + t];
                     if (h > d) continue;
-                    out.push_back({both ? a >> 1 : a, (uint8_t)(both ? a & 1 : 0), p, (uint8_t)h});
+                    const QueryStrand qs = query_strand(both, a);
+                    out.push_back({qs.query, qs.strand, p, (uint8_t)h});
                 }
             }
         }
     }, 4);
-    uint64_t total = 0;
-    for (const auto& v : recs) total += v.size();
-    if (total_out) *total_out = total;
-    if (total > cap) return SUFR_HIP_E_CAPACITY;
-    if (!total) return 0;
-    if (!query || !strand || !position || !mismatches) return SUFR_HIP_E_INVALID;
-    uint64_t t = 0;
-    for (const auto& v : recs)
-        for (const ApproxRec& x : v) { query[t] = x.query; strand[t] = x.strand; position[t] = x.pos; mismatches[t] = x.mism; t++; }
-    return 0;
+    return collect_records(recs, cap, total_out, !query || !strand || !position || !mismatches, [&](uint64_t t, const ApproxRec& x) {
+        query[t] = x.query; strand[t] = x.strand; position[t] = x.pos; mismatches[t] = x.mism;
+    });
 }
 
 }  // extern "C"
@@ -684,11 +686,11 @@ int sufr_file_edit(const sufr_file* f, const uint8_t* queries, const uint64_t* o
             if (m < np) continue;
             diags.clear();
             for (uint32_t i = 0; i < np; i++) {                              // the diagonals of every live seed
-                const uint64_t o = (uint64_t)i * m / np, len = (uint64_t)(i + 1) * m / np - o, kk = L > 0 && L < len ? L : len;
+                const Piece pc = piece_of(i, m, np, L);
                 uint64_t lo = 0, hi = 0;
-                (void)sufr_file_search(f, Q + o, (size_t)kk, 0, 0, &lo, &hi);
+                (void)sufr_file_search(f, Q + pc.o, (size_t)pc.kk, 0, 0, &lo, &hi);
                 if (max_occ && hi - lo > max_occ) continue;
-                for (uint64_t r = lo; r < hi; r++) diags.push_back((int64_t)sufr_file_suffix(f, r) - (int64_t)o);
+                for (uint64_t r = lo; r < hi; r++) diags.push_back((int64_t)sufr_file_suffix(f, r) - (int64_t)pc.o);
             }
             std::sort(diags.begin(), diags.end());
             diags.erase(std::unique(diags.begin(), diags.end()), diags.end());
@@ -709,20 +711,14 @@ int sufr_file_edit(const sufr_file* f, const uint8_t* queries, const uint64_t* o
                     const uint32_t vr = t + 1 < ends.size() && ends[t + 1].first == ends[t].first + 1 ? ends[t + 1].second : d + 1;
                     if (!(vl > v && vr >= v)) continue;
                 }
-                out.push_back({both ? a >> 1 : a, (uint8_t)(both ? a & 1 : 0), ends[t].first - 1, (uint8_t)ends[t].second});
+                const QueryStrand qs = query_strand(both, a);
+                out.push_back({qs.query, qs.strand, ends[t].first - 1, (uint8_t)ends[t].second});
             }
         }
     }, 4);
-    uint64_t total = 0;
-    for (const auto& v : recs) total += v.size();
-    if (total_out) *total_out = total;
-    if (total > cap) return SUFR_HIP_E_CAPACITY;
-    if (!total) return 0;
-    if (!query || !strand || !end || !edits) return SUFR_HIP_E_INVALID;
-    uint64_t t = 0;
-    for (const auto& v : recs)
-        for (const EditRec& x : v) { query[t] = x.query; strand[t] = x.strand; end[t] = x.end; edits[t] = x.edits; t++; }
-    return 0;
+    return collect_records(recs, cap, total_out, !query || !strand || !end || !edits, [&](uint64_t t, const EditRec& x) {
+        query[t] = x.query; strand[t] = x.strand; end[t] = x.end; edits[t] = x.edits;
+    });
 }
 
 }  // extern "C"
@@ -794,6 +790,11 @@ int sufr_file_edit_trace(const sufr_file* f, const uint8_t* queries, const uint6
     const uint64_t chunk = 64, nchunks = (num_records + chunk - 1) / chunk;
     std::vector<std::vector<uint32_t>> runs_of(nchunks);
     std::atomic<uint64_t> bad{~0ull};
+    // the checks that need no table: record t names a query of the batch, a strand, an end of the text and a distance its query allows
+    auto in_range = [&](uint64_t t) {
+        return query[t] < nq && strand[t] <= 1 && end[t] < n && edits[t] <= SUFR_EDIT_MAX_EDITS &&
+               offsets[query[t] + 1] >= offsets[query[t]] && offsets[query[t] + 1] - offsets[query[t]] >= (uint64_t)edits[t] + 1;
+    };
     parallel_chunks(num_records, chunk, threads, [&](uint64_t b, uint64_t e) {
         std::vector<uint32_t>& out = runs_of[b / chunk];
         std::vector<uint32_t> tab, runs;
@@ -801,8 +802,7 @@ int sufr_file_edit_trace(const sufr_file* f, const uint8_t* queries, const uint6
         for (uint64_t t = b; t < e; t++) {
             cigar_off[t + 1] = 0;
             start[t] = 0;
-            bool ok = query[t] < nq && strand[t] <= 1 && end[t] < n && edits[t] <= SUFR_EDIT_MAX_EDITS &&
-                      offsets[query[t] + 1] >= offsets[query[t]] && offsets[query[t] + 1] - offsets[query[t]] >= (uint64_t)edits[t] + 1;
+            bool ok = in_range(t);
             if (ok) {
                 const uint8_t* Q = queries + offsets[query[t]];
                 const uint64_t m = offsets[query[t] + 1] - offsets[query[t]];
@@ -822,9 +822,7 @@ int sufr_file_edit_trace(const sufr_file* f, const uint8_t* queries, const uint6
     }, 64);
     if (bad.load() != ~0ull) {
         const uint64_t t = bad.load();
-        const bool range = !(query[t] < nq && strand[t] <= 1 && end[t] < n && edits[t] <= SUFR_EDIT_MAX_EDITS &&
-                             offsets[query[t] + 1] >= offsets[query[t]] && offsets[query[t] + 1] - offsets[query[t]] >= (uint64_t)edits[t] + 1);
-        put_err(err, errlen, "trace: record " + std::to_string(t) + (range ? " is no record of this batch and text (query, strand, end, edits "
+        put_err(err, errlen, "trace: record " + std::to_string(t) + (!in_range(t) ? " is no record of this batch and text (query, strand, end, edits "
                              "or the length of its query out of range)" : ": edits is not D(end + 1)"));
         return SUFR_HIP_E_INVALID;
     }

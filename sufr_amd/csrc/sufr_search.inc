@@ -14,9 +14,13 @@
 // searches are random 64-byte HBM sectors.  The kernel is latency bound per lane and sector-rate bound per device,
 // nowhere near the byte rate of HBM.
 //
-// This file owns what every query kernel shares; sufr_match.inc and sufr_mem.inc, included after it, add only their own
-// rules.  Device: search_compare / common_prefix, the range search (search_seed, search_lower, search_range), last_le,
-// wg_scan, scan_chunk.  Host: query_check, read_totals, stage_batch / unstage_batch.
+// This file owns what every query kernel shares; sufr_match.inc, sufr_mem.inc, sufr_approx.inc, sufr_edit.inc and
+// sufr_trace.inc, included after it, add only their own rules (DESIGN.md section 10, "The shared front end").
+// Device: search_compare / common_prefix, the range search (search_seed, search_lower, search_range), last_le, wg_scan,
+// scan_chunk, the locate scan (k_locate_counts / k_locate_scan / k_locate_apply), k_mem_bitmap and k_mem_revcomp.
+// Host: query_check, read_totals, scan_total; the batch of a call (take_batch = batch_extent + double_batch, mem_bitmap);
+// candidate_starts; the record epilogue (records_fit, any_null, launch_status); the staging of the host-pointer entry
+// points (stage_batch / unstage_batch, staged_records).
 
 namespace sufr {
 
@@ -320,6 +324,40 @@ __global__ __launch_bounds__(256) void k_locate_gather(SearchIndex ix, const uin
     if (positions64) positions64[j] = p; else positions[j] = (uint32_t)p;
 }
 
+// ---- what the seeded searches (MEMs, k-mismatch, k-difference, traceback) share on the device ----------------------
+// once per index whose array leaves positions out: one lane per rank sets bit SA[r] (atomicOr on u32 words)
+__global__ __launch_bounds__(256) void k_mem_bitmap(SearchIndex ix, uint32_t* __restrict__ bits)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < ix.s; r += stride) {
+        const uint64_t p = ix.suffix(r);
+        atomicOr(&bits[p >> 5], 1u << (p & 31));
+    }
+}
+
+__device__ __forceinline__ uint8_t mem_complement(uint8_t c)
+{
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
+}
+
+// both strands: the doubled batch, query i as it is then its reverse complement, with the new offsets (from 0)
+__global__ __launch_bounds__(256) void k_mem_revcomp(const uint8_t* __restrict__ queries, const uint64_t* __restrict__ qoff, uint64_t nq,
+                                                     uint8_t* __restrict__ dst, uint64_t* __restrict__ doff)
+{
+    const uint64_t g0 = qoff[0], g_end = qoff[nq], stride = (uint64_t)gridDim.x * 256;
+    const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    for (uint64_t i = tid; i <= nq; i += stride) {
+        if (i < nq) { doff[2 * i] = 2 * (qoff[i] - g0); doff[2 * i + 1] = qoff[i] + qoff[i + 1] - 2 * g0; }
+        else doff[2 * nq] = 2 * (g_end - g0);
+    }
+    for (uint64_t g = g0 + tid; g < g_end; g += stride) {
+        const uint64_t a = last_le(qoff, 0, nq, g), b = qoff[a], e = qoff[a + 1];
+        const uint8_t c = queries[g];
+        dst[2 * (b - g0) + (g - b)] = c;
+        dst[b + e - 2 * g0 + (e - 1 - g)] = mem_complement(c);
+    }
+}
+
 }  // namespace sufr
 
 struct sufr_hip_index {
@@ -421,12 +459,138 @@ int query_check(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const char* masked 
     return 0;
 }
 
-// n totals of the device to the host, complete on return (one synchronisation); `what` is the error text
-int read_totals(sufr::Pipeline& pl, const void* d_src, int n, unsigned long long* dst, const char* what)
+// the workgroups of the kernels that loop over a batch (latency-bound lanes: 8 workgroups of 4 waves per CU)
+uint32_t batch_grid(const sufr::Pipeline& pl) { return (pl.num_cus ? pl.num_cus : 256u) * 8u; }
+
+// n totals of the device to the host, complete on return (one synchronisation); the error text is "<tag>: <what>"
+int read_totals(sufr::Pipeline& pl, const void* d_src, int n, unsigned long long* dst, const char* tag, const char* what)
 {
     if (hipMemcpyAsync(dst, d_src, (size_t)n * 8, hipMemcpyDeviceToHost, pl.stream) == hipSuccess &&
         hipStreamSynchronize(pl.stream) == hipSuccess) return 0;
-    pl.set_error(what);
+    pl.set_error(std::string(tag) + ": " + what);
+    return SUFR_HIP_E_HIP;
+}
+
+// k_locate_scan over n workgroup sums (in place: the exclusive bases) and their total, read to the host: one
+// synchronisation.  The error text is "<tag>: <what>".
+int scan_total(sufr::Pipeline& pl, uint64_t* sums, uint64_t n, unsigned long long* total, const char* tag, const char* what)
+{
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, sums, n, sums + n);
+    return read_totals(pl, sums + n, 1, total, tag, what);
+}
+
+// the bitmap of the indexed positions, once per index (none when every position is indexed)
+int mem_bitmap(sufr_hip_ctx* ctx, const sufr_hip_index* ix)
+{
+    if (ix->ix.s >= ix->ix.n) return 0;
+    std::lock_guard<std::mutex> lock(ix->mem_mu);
+    if (ix->mem_bits_done) return 0;
+    sufr::Pipeline& pl = ctx->pl;
+    const uint64_t words = (ix->ix.n + 31) / 32;
+    void* bits = nullptr;
+    if (hipMalloc(&bits, words * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        pl.set_error("mems: hipMalloc of the indexed-position bitmap (" + std::to_string(words * 4) + " bytes) failed");
+        return SUFR_HIP_E_NOMEM;
+    }
+    const uint32_t grid = batch_grid(pl);
+    bool ok = hipMemsetAsync(bits, 0, words * 4, pl.stream) == hipSuccess;
+    if (ok) hipLaunchKernelGGL(sufr::k_mem_bitmap, dim3(grid), dim3(256), 0, pl.stream, ix->ix, (uint32_t*)bits);
+    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(pl.stream) == hipSuccess;   // other streams may use it next
+    if (!ok) { (void)hipFree(bits); pl.set_error("mems: building the indexed-position bitmap failed"); return SUFR_HIP_E_HIP; }
+    ix->mem_bits = bits;
+    ix->mem_bits_done = true;
+    return 0;
+}
+
+// ---- the batch of a call (MEMs, k-mismatch, k-difference, traceback) -------------------------------------------------
+// q / qoff: the bytes and the nq + 1 offsets the kernels read (the doubled batch with both strands), nb: its byte count
+// (0: an empty batch, nothing to do), grid: the workgroups of the kernels that loop over it
+struct QueryBatch { const uint8_t* q; const uint64_t* qoff; uint64_t nq, nb; uint32_t grid; bool both; };
+
+// the batch as the caller gave it: the bitmap of the index, then the two ends of the offsets (one synchronisation)
+int batch_extent(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets, uint64_t num_queries,
+                 const char* tag, QueryBatch& b)
+{
+    sufr::Pipeline& pl = ctx->pl;
+    b = QueryBatch{(const uint8_t*)d_queries, (const uint64_t*)d_offsets, num_queries, 0, batch_grid(pl), false};
+    if (!num_queries) return 0;
+    if (const int rc = mem_bitmap(ctx, ix)) return rc;
+    unsigned long long ends[2] = {0, 0};                             // offsets[0] and offsets[num_queries]
+    bool ok = true;
+    for (int k = 0; k < 2; k++)
+        ok = ok && hipMemcpyAsync(&ends[k], b.qoff + k * num_queries, 8, hipMemcpyDeviceToHost, pl.stream) == hipSuccess;
+    if (!ok || hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error(std::string(tag) + ": reading the batch offsets failed"); return SUFR_HIP_E_HIP; }
+    if (ends[1] > ends[0]) b.nb = ends[1] - ends[0];
+    return 0;
+}
+
+// both strands: k_mem_revcomp of the batch as given (nb bytes) into the context's xq / xoff, which b then names
+int double_batch(sufr_hip_ctx* ctx, QueryBatch& b)
+{
+    sufr::Pipeline& pl = ctx->pl;
+    int rc;
+    if ((rc = pl.ensure(ctx->xq, 2 * b.nb + 8)) || (rc = pl.ensure(ctx->xoff, (2 * b.nq + 1) * 8))) return rc;
+    hipLaunchKernelGGL(sufr::k_mem_revcomp, dim3(b.grid), dim3(256), 0, pl.stream, b.q, b.qoff, b.nq, (uint8_t*)ctx->xq.p, (uint64_t*)ctx->xoff.p);
+    b = QueryBatch{(const uint8_t*)ctx->xq.p, (const uint64_t*)ctx->xoff.p, 2 * b.nq, 2 * b.nb, b.grid, true};
+    return 0;
+}
+
+int take_batch(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets, uint64_t num_queries, bool both,
+               const char* tag, QueryBatch& b)
+{
+    if (const int rc = batch_extent(ctx, ix, d_queries, d_offsets, num_queries, tag, b)) return rc;
+    return both && b.nb ? double_batch(ctx, b) : 0;
+}
+
+// ---- candidate starts ---------------------------------------------------------------------------------------------------
+// n items (the offsets of MEMs, the seeds of the pigeonhole searches) each with a rank range: ranges(rlo, rhi) launches the
+// kernel that fills them, then k_locate_counts / k_locate_scan / k_locate_apply make cand[0 .. n] the exclusive scan of the
+// range sizes and one synchronisation reads their total.  cnt_sum: SCAN_WGS + 1 words for the count kernel that follows.
+struct Candidates { uint64_t* rlo; uint64_t* cand; uint64_t* cnt_sum; unsigned long long ncand; };
+
+template <typename Ranges>
+int candidate_starts(sufr_hip_ctx* ctx, uint64_t n, const char* tag, Ranges ranges, Candidates& c)
+{
+    sufr::Pipeline& pl = ctx->pl;
+    const uint64_t nblk = (n + sufr::LOC_BLK - 1) / sufr::LOC_BLK;
+    int rc;
+    if ((rc = pl.ensure(ctx->xlo, n * 8)) || (rc = pl.ensure(ctx->xhi, n * 8)) || (rc = pl.ensure(ctx->xcand, (n + 1) * 8)) ||
+        (rc = pl.ensure(ctx->xsum, (nblk + 1 + sufr::SCAN_WGS + 1) * 8))) return rc;
+    uint64_t* rhi = (uint64_t*)ctx->xhi.p;
+    uint64_t* bsum = (uint64_t*)ctx->xsum.p;
+    c = Candidates{(uint64_t*)ctx->xlo.p, (uint64_t*)ctx->xcand.p, bsum + nblk + 1, 0};
+    ranges(c.rlo, rhi);
+    hipLaunchKernelGGL(sufr::k_locate_counts, dim3((uint32_t)nblk), dim3(256), 0, pl.stream, (const uint64_t*)c.rlo, (const uint64_t*)rhi, n,
+                       (uint64_t)0, c.cand, bsum);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, bsum, nblk, bsum + nblk);
+    hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((n + 256) / 256)), dim3(256), 0, pl.stream, c.cand, n, (const uint64_t*)bsum,
+                       (const uint64_t*)(bsum + nblk));
+    return read_totals(pl, bsum + nblk, 1, &c.ncand, tag, "counting the candidates failed");
+}
+
+// ---- the record epilogue ------------------------------------------------------------------------------------------------
+// the total of a call against the room of its caller: "<tag>: N <noun>, room for M"
+int records_fit(sufr::Pipeline& pl, const char* tag, const char* noun, uint64_t total, uint64_t cap, uint64_t* total_out)
+{
+    if (total_out) *total_out = total;
+    if (total <= cap) return 0;
+    pl.set_error(std::string(tag) + ": " + std::to_string(total) + " " + noun + ", room for " + std::to_string(cap));
+    return SUFR_HIP_E_CAPACITY;
+}
+
+bool any_null(std::initializer_list<const void*> ptrs)
+{
+    for (const void* p : ptrs) if (!p) return true;
+    return false;
+}
+
+// what the launches of a call left behind
+int launch_status(sufr::Pipeline& pl, const char* tag)
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    pl.set_error(std::string(tag) + ": " + hipGetErrorString(e));
     return SUFR_HIP_E_HIP;
 }
 
@@ -448,14 +612,50 @@ int stage_batch(sufr_hip_ctx* ctx, const char* what, const uint8_t* queries, con
 struct StageBack { void* dst; uint64_t at, bytes; };             // to the host: `bytes` from offset `at` of the allocation
 
 // rc: what staging and the device call gave; when that is 0 the results are copied back, complete on return
-int unstage_batch(sufr_hip_ctx* ctx, const char* what, uint8_t* d, int rc, std::initializer_list<StageBack> back)
+int unstage_batch(sufr_hip_ctx* ctx, const char* what, uint8_t* d, int rc, const StageBack* back, size_t n)
 {
-    for (const StageBack& b : back)
-        if (!rc && b.bytes && hipMemcpyAsync(b.dst, d + b.at, b.bytes, hipMemcpyDeviceToHost, ctx->pl.stream) != hipSuccess) rc = SUFR_HIP_E_HIP;
+    for (size_t k = 0; k < n; k++)
+        if (!rc && back[k].bytes && hipMemcpyAsync(back[k].dst, d + back[k].at, back[k].bytes, hipMemcpyDeviceToHost, ctx->pl.stream) != hipSuccess)
+            rc = SUFR_HIP_E_HIP;
     if (!rc && hipStreamSynchronize(ctx->pl.stream) != hipSuccess) rc = SUFR_HIP_E_HIP;
     if (rc == SUFR_HIP_E_HIP && ctx->pl.err.empty()) ctx->pl.set_error(std::string("copying the ") + what + " batch failed");
     (void)hipFree(d);
     return rc;
+}
+
+int unstage_batch(sufr_hip_ctx* ctx, const char* what, uint8_t* d, int rc, std::initializer_list<StageBack> back)
+{
+    return unstage_batch(ctx, what, d, rc, back.begin(), back.size());
+}
+
+// A host-pointer entry point whose results are record columns: one allocation, queries | offsets | every column at `cap`
+// elements of its width | `extra` bytes, each part on an 8-byte boundary.  call(d_queries, d_offsets, col, &total) runs the
+// *_device twin on it (col[k]: column k, col[number of columns]: the extra bytes); `total` elements of every column go back.
+struct Column { void* host; uint32_t width; };
+static constexpr size_t STAGE_MAX_COLUMNS = 6;
+
+template <typename Call>
+int staged_records(sufr_hip_ctx* ctx, const char* what, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint64_t cap,
+                   std::initializer_list<Column> cols, uint64_t extra, uint64_t* total_out, Call call)
+{
+    const uint64_t o_at = (offsets[nq] + 7) / 8 * 8;
+    uint64_t at[STAGE_MAX_COLUMNS + 1], end = o_at + (nq + 1) * 8;
+    size_t k = 0;
+    for (const Column& c : cols) { at[k++] = end; end += (cap * c.width + 7) / 8 * 8; }
+    at[k] = end;
+    uint8_t* d;
+    int rc = stage_batch(ctx, what, queries, offsets, nq, o_at, end + extra + 8, &d);
+    uint64_t total = 0;
+    if (!rc) {
+        void* col[STAGE_MAX_COLUMNS + 1];
+        for (size_t j = 0; j <= k; j++) col[j] = d + at[j];
+        rc = call(d, d + o_at, col, &total);
+    }
+    if (total_out) *total_out = total;
+    StageBack back[STAGE_MAX_COLUMNS];
+    k = 0;
+    for (const Column& c : cols) { back[k] = StageBack{c.host, at[k], total * c.width}; k++; }
+    return unstage_batch(ctx, what, d, rc, back, k);
 }
 
 }  // namespace
@@ -591,7 +791,7 @@ int sufr_hip_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, co
                            (uint64_t*)pl.sc(sufr::Pipeline::SC_TOTAL));
         hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((num_queries + 256) / 256)), dim3(256), 0, pl.stream, off, num_queries,
                            (const uint64_t*)pl.partials.p, (const uint64_t*)pl.sc(sufr::Pipeline::SC_TOTAL));
-        if ((rc = read_totals(pl, pl.sc(sufr::Pipeline::SC_TOTAL), 1, &total, "locate: counting the matches failed"))) return rc;
+        if ((rc = read_totals(pl, pl.sc(sufr::Pipeline::SC_TOTAL), 1, &total, "locate", "counting the matches failed"))) return rc;
     } else if (hipMemsetAsync(d_offsets, 0, 8, pl.stream) != hipSuccess) { pl.set_error("memset failed"); return SUFR_HIP_E_HIP; }
     if (total_out) *total_out = total;
     if (total > cap) {

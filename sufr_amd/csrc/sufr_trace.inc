@@ -5,7 +5,7 @@
 // k_trace_check      one lane per record: the five checks that need no table (query, strand, end, edits, query length); the
 //                    first offending record (atomicMin), the longest query of the records (atomicMax), whether a record is on
 //                    strand 1, the byte range of the batch.  First synchronisation: it sizes the chunks.
-// k_mem_revcomp      (sufr_mem.inc) only when a record is on strand 1: the doubled batch
+// k_mem_revcomp      (double_batch, sufr_search.inc) only when a record is on strand 1: the doubled batch
 // per chunk of records (as many as the row storage holds at 8 bytes per row of the longest query):
 //   k_trace_rows     one record per lane: the rows of the 2 * edits + 1 band (trace_forward, sufr_trace.h), two words per row to
 //                    rows[(r - 1) * chunk_records + lane_record]; the banded value of the end cell against `edits` (the sixth
@@ -175,7 +175,7 @@ int sufr_hip_edit_trace_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, cons
     hipLaunchKernelGGL(sufr::k_trace_check, dim3((uint32_t)((num_records + 255) / 256)), dim3(256), 0, pl.stream, R, uoff, num_queries,
                        ix->ix.n, sc);
     unsigned long long h[sufr::TR_N];
-    if ((rc = read_totals(pl, sc, sufr::TR_N, h, "trace: checking the records failed"))) return rc;
+    if ((rc = read_totals(pl, sc, sufr::TR_N, h, "trace", "checking the records failed"))) return rc;
     if (h[sufr::TR_BAD] != ~0ull) {
         pl.set_error("trace: record " + std::to_string(h[sufr::TR_BAD]) + " is no record of this batch and text (query, strand, end, edits "
                      "or the length of its query out of range)");
@@ -195,39 +195,28 @@ int sufr_hip_edit_trace_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, cons
     if ((rc = pl.ensure(ctx->trows, cr * 8 * max_m)) || (rc = pl.ensure(ctx->tmisc, cr * 4 + (max_wgs + 1) * 8))) return rc;
     uint64_t* wgsum = (uint64_t*)ctx->tmisc.p;
     uint32_t* nruns = (uint32_t*)(wgsum + max_wgs + 1);
-    // strand 1: the doubled batch
-    const bool both = h[sufr::TR_STRAND1] != 0;
-    const uint8_t* q = (const uint8_t*)d_queries + h[sufr::TR_G0];
-    const uint64_t* qoff = uoff;
-    uint64_t g0 = h[sufr::TR_G0];
-    if (both) {
-        const uint64_t nb = 2 * (h[sufr::TR_GEND] - h[sufr::TR_G0]);
-        const uint32_t grid = (pl.num_cus ? pl.num_cus : 256u) * 8u;
-        if ((rc = pl.ensure(ctx->xq, nb + 8)) || (rc = pl.ensure(ctx->xoff, (2 * num_queries + 1) * 8))) return rc;
-        hipLaunchKernelGGL(sufr::k_mem_revcomp, dim3(grid), dim3(256), 0, pl.stream, (const uint8_t*)d_queries, uoff, num_queries,
-                           (uint8_t*)ctx->xq.p, (uint64_t*)ctx->xoff.p);
-        q = (const uint8_t*)ctx->xq.p;
-        qoff = (const uint64_t*)ctx->xoff.p;
-        g0 = 0;
-    }
+    // strand 1: the doubled batch (offsets from 0); else the batch as it is, read from its first byte
+    QueryBatch b{(const uint8_t*)d_queries, uoff, num_queries, h[sufr::TR_GEND] - h[sufr::TR_G0], batch_grid(pl), false};
+    uint64_t g0 = 0;
+    if (h[sufr::TR_STRAND1]) { if ((rc = double_batch(ctx, b))) return rc; }
+    else { g0 = h[sufr::TR_G0]; b.q += g0; }
     uint32_t slot = 0;
     for (uint64_t c0 = 0; c0 < num_records; c0 += cr, slot ^= 1u) {
         const uint64_t n_here = num_records - c0 < cr ? num_records - c0 : cr;
         const uint32_t wgs = (uint32_t)((n_here + 255) / 256);
-        hipLaunchKernelGGL(sufr::k_trace_rows, dim3(wgs), dim3(256), 0, pl.stream, ix->ix.text, ix->ix.n, R, q, qoff, g0, (uint32_t)both, c0, n_here,
+        hipLaunchKernelGGL(sufr::k_trace_rows, dim3(wgs), dim3(256), 0, pl.stream, ix->ix.text, ix->ix.n, R, b.q, b.qoff, g0, (uint32_t)b.both, c0, n_here,
                            (uint2*)ctx->trows.p, (uint64_t*)d_start, nruns, (uint64_t*)d_cigar_off, wgsum, sc);
         hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, wgsum, (uint64_t)wgs, (uint64_t*)(sc + sufr::TR_CHUNK));
-        hipLaunchKernelGGL(sufr::k_trace_write, dim3(wgs), dim3(256), 0, pl.stream, ix->ix.text, R, q, qoff, g0, (uint32_t)both, c0, n_here,
+        hipLaunchKernelGGL(sufr::k_trace_write, dim3(wgs), dim3(256), 0, pl.stream, ix->ix.text, R, b.q, b.qoff, g0, (uint32_t)b.both, c0, n_here,
                            (const uint2*)ctx->trows.p, (const uint32_t*)nruns, (const uint64_t*)wgsum, slot, (uint64_t*)d_cigar_off,
                            (uint32_t*)d_cigar, cigar_cap, sc);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { pl.set_error(std::string("trace: ") + hipGetErrorString(e)); return SUFR_HIP_E_HIP; }
+    if ((rc = launch_status(pl, "trace"))) return rc;
     if (hipMemcpyAsync((uint64_t*)d_cigar_off + num_records, sc + sufr::TR_BASE0 + slot, 8, hipMemcpyDeviceToDevice, pl.stream) != hipSuccess) {
         pl.set_error("trace: hipMemcpyAsync failed");
         return SUFR_HIP_E_HIP;
     }
-    if ((rc = read_totals(pl, sc, sufr::TR_N, h, "trace: reading the CIGAR total failed"))) return rc;
+    if ((rc = read_totals(pl, sc, sufr::TR_N, h, "trace", "reading the CIGAR total failed"))) return rc;
     if (h[sufr::TR_BAD] != ~0ull) {
         pl.set_error("trace: record " + std::to_string(h[sufr::TR_BAD]) + ": edits is not D(end + 1)");
         return SUFR_HIP_E_INVALID;
@@ -235,12 +224,7 @@ int sufr_hip_edit_trace_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, cons
     const uint64_t total = h[sufr::TR_BASE0 + slot];
     if (pl.debug) fprintf(stderr, "[sufr_hip debug] trace: %llu records, longest query %llu, %llu per chunk, %llu runs\n",
                           (unsigned long long)num_records, (unsigned long long)max_m, (unsigned long long)cr, (unsigned long long)total);
-    if (total_out) *total_out = total;
-    if (total > cigar_cap) {
-        pl.set_error("trace: " + std::to_string(total) + " CIGAR runs, room for " + std::to_string(cigar_cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    return 0;
+    return records_fit(pl, "trace", "CIGAR runs", total, cigar_cap, total_out);
 }
 
 int sufr_hip_edit_trace(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* queries, const uint64_t* offsets, uint64_t num_queries,

@@ -71,3 +71,35 @@ def test_damaged_inputs_end_in_an_error_string_never_in_a_crash():
     _clean(r.stdout + r.stderr)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     assert "no crash, no sanitizer report" in r.stdout
+
+
+def test_failing_query_commands_exit_1_with_their_message(tmp_path):
+    """`sufr approx`, `sufr edit` and `sufr mems` under the sanitized CLI: an output that cannot be created (the .sufr file is
+    open by then: the way out has to close it) and a distance above the limit end in exit code 1 with their one-line
+    message, no sanitizer report and no leak report.  The CLI is a program of its own that links the sanitizer runtime, so
+    it runs with nothing preloaded and with LeakSanitizer on (the library tests above keep it off).  Where LeakSanitizer
+    cannot run at all (a container without ptrace: it says "LeakSanitizer has encountered a fatal error") the run is
+    repeated without it, and the exit code and the message are what is left to assert."""
+    env = _asan_env()
+    del env["LD_PRELOAD"]
+    cli = CSRC / "_build" / "sufr_host_asan"
+    sufr = ROOT / "tests" / "golden" / "expected" / "long_dna_sequence.sufr"
+    out = tmp_path / "no_such_dir" / "out.txt"
+
+    def fails(*args):
+        for leaks in (1, 0):
+            env["ASAN_OPTIONS"] = f"detect_leaks={leaks}:abort_on_error=1"
+            r = subprocess.run([str(cli), *map(str, args)], env=env, capture_output=True, text=True, timeout=120)
+            if "LeakSanitizer has encountered a fatal error" not in r.stderr:
+                break
+        _clean(r.stdout + r.stderr)
+        assert "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
+        assert r.returncode == 1 and r.stdout == "", r.stdout + r.stderr
+        return r.stderr
+
+    for cmd in ("approx", "edit", "mems"):
+        assert fails(cmd, "-o", out, sufr, "ACGTACGTACGTACGTACGTACGT") == f"Error: {out}: cannot create\n"
+        assert not out.parent.exists()
+    assert fails("approx", "--mismatches", 16, "-o", out, sufr, "ACGTACGTACGT") == "Error: --mismatches must be at most 15\n"
+    assert fails("edit", "--edits", 16, "-o", out, sufr, "ACGTACGTACGT") == "Error: --edits must be at most 15\n"
+    assert fails("mems", "--min-len", 0, sufr, "ACGTACGTACGT") == "Error: --min-len must be between 1 and 2^32 - 1\n"
