@@ -134,6 +134,18 @@ uint64_t sufr_hip_window_repairs(const sufr_hip_ctx *ctx);
  * with one shard per context and goes to 2, 4, 8 ... times as many while a build runs out of device memory.  The price is one windowed
  * sort of the text per shard.  Seed-mask builds and max_query_len < 8 are not sharded (they keep the whole-array path). */
 int  sufr_hip_set_array_budget(sufr_hip_ctx *ctx, uint64_t bytes);
+/* The buckets whose suffixes agree on all key characters ("left-over" buckets) and the runs of equal keys are two chains of
+ * re-keying levels.  From min_records left-over records on, the first chain runs on a helper pipeline of the context (a stream
+ * and a host thread of its own) beside the second; prefix doubling, which reads the ranks of all suffixes, waits for it.
+ * 0: the default (2^22 records); UINT64_MAX: the chains never overlap (no helper thread, less device memory); a small value sends
+ * small texts down the overlapped path (the tests).  The arrays do not depend on it.  Additive: the ABI version stays 3, as for
+ * every function added without a change to a struct. */
+int  sufr_hip_set_overlap_min(sufr_hip_ctx *ctx, uint64_t min_records);
+/* 1 if the context's last build ran the left-over chain on the helper pipeline, else 0 (a windowed build: 1 if a window did) */
+int  sufr_hip_overlapped(const sufr_hip_ctx *ctx);
+/* how many times the context's last build handed a level to prefix doubling: both chains, added up after the helper was joined
+ * (a windowed build: all windows) */
+uint64_t sufr_hip_doublings(const sufr_hip_ctx *ctx);
 
 /* ---- text normalisation: sufr_builder.rs:144-160 (host helper; the GPU build can also do it) --- */
 int sufr_hip_normalize(const uint8_t *in, uint8_t *out, uint64_t n, int ignore_softmask);

@@ -80,7 +80,7 @@ FLAG_SA_U64 = 0x200               # sufr_hip_index_wrap only: 64-bit suffix arra
 # every symbol include/sufr_hip.h declares
 EXPORTS = [
     "sufr_hip_abi_version", "sufr_hip_device_count", "sufr_hip_create", "sufr_hip_destroy",
-    "sufr_hip_last_error", "sufr_hip_set_stream", "sufr_hip_synchronize", "sufr_hip_set_window", "sufr_hip_set_window_retry", "sufr_hip_set_array_budget", "sufr_hip_window_repairs", "sufr_hip_normalize", "sufr_hip_sort_device_u32",
+    "sufr_hip_last_error", "sufr_hip_set_stream", "sufr_hip_synchronize", "sufr_hip_set_window", "sufr_hip_set_window_retry", "sufr_hip_set_array_budget", "sufr_hip_window_repairs", "sufr_hip_set_overlap_min", "sufr_hip_overlapped", "sufr_hip_doublings", "sufr_hip_normalize", "sufr_hip_sort_device_u32",
     "sufr_hip_sort_device_u64", "sufr_hip_stitch_device_u32", "sufr_hip_stitch_device_u64", "sufr_hip_build_u32", "sufr_hip_build_u64", "sufr_hip_lcp_pair",
     "sufr_read_sequence_file", "sufr_sequence_data_free", "sufr_write_file", "sufr_hip_create_file", "sufr_hip_create_from_sequence",
     "sufr_hip_shard_build", "sufr_write_frame", "sufr_hip_shard_write", "sufr_hip_create_from_sequence_multi",
@@ -163,6 +163,9 @@ def lib() -> C.CDLL:
     L.sufr_hip_set_window_retry.argtypes = [vp, u64]; L.sufr_hip_set_window_retry.restype = C.c_int
     L.sufr_hip_set_array_budget.argtypes = [vp, u64]; L.sufr_hip_set_array_budget.restype = C.c_int
     L.sufr_hip_window_repairs.argtypes = [vp]; L.sufr_hip_window_repairs.restype = u64
+    L.sufr_hip_set_overlap_min.argtypes = [vp, u64]; L.sufr_hip_set_overlap_min.restype = C.c_int
+    L.sufr_hip_overlapped.argtypes = [vp]; L.sufr_hip_overlapped.restype = C.c_int
+    L.sufr_hip_doublings.argtypes = [vp]; L.sufr_hip_doublings.restype = u64
     L.sufr_hip_normalize.argtypes = [vp, vp, u64, C.c_int]; L.sufr_hip_normalize.restype = C.c_int
     dev_sig = [vp, vp, u64, u32, u64, cp, u64, u64, u32, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(Stats)]
     L.sufr_hip_sort_device_u32.argtypes = dev_sig; L.sufr_hip_sort_device_u32.restype = C.c_int
@@ -306,6 +309,21 @@ class Context:
     def window_repairs(self) -> int:
         """Suffixes of the last windowed build that were ordered by whole-text comparison."""
         return int(lib().sufr_hip_window_repairs(self._h))
+
+    def set_overlap_min(self, min_records: int = 0):
+        """Left-over records (buckets that agree on the whole key) from which their re-keying chain runs on the helper pipeline,
+        beside the tie runs (sufr_hip_set_overlap_min; 0: the default of 2^22, 2^64 - 1: never)."""
+        self.check(lib().sufr_hip_set_overlap_min(self._h, min_records))
+
+    @property
+    def overlapped(self) -> int:
+        """1 if the last build ran the left-over chain on the helper pipeline (a windowed build: in one of its windows)."""
+        return int(lib().sufr_hip_overlapped(self._h))
+
+    @property
+    def doublings(self) -> int:
+        """How many times the last build handed a level to prefix doubling (both chains; a windowed build: all windows)."""
+        return int(lib().sufr_hip_doublings(self._h))
 
     def synchronize(self):
         self.check(lib().sufr_hip_synchronize(self._h))

@@ -271,6 +271,16 @@ int sufr_hip_set_window_retry(sufr_hip_ctx* ctx, uint64_t widest_margin)
 
 uint64_t sufr_hip_window_repairs(const sufr_hip_ctx* ctx) { return ctx ? ctx->pl.wide_orphans : 0; }
 
+int sufr_hip_set_overlap_min(sufr_hip_ctx* ctx, uint64_t min_records)
+{
+    if (!ctx) return SUFR_HIP_E_INVALID;
+    ctx->pl.opt_overlap_min = min_records;
+    return 0;
+}
+
+int sufr_hip_overlapped(const sufr_hip_ctx* ctx) { return ctx ? (int)ctx->pl.last_overlapped : 0; }
+uint64_t sufr_hip_doublings(const sufr_hip_ctx* ctx) { return ctx ? ctx->pl.last_doublings : 0; }
+
 int sufr_hip_synchronize(sufr_hip_ctx* ctx)
 {
     if (!ctx) return SUFR_HIP_E_INVALID;

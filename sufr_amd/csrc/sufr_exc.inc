@@ -603,6 +603,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
         const uint32_t stride = (E + EXC_LDS_LIST - 1) / EXC_LDS_LIST, ns = (E + stride - 1) / stride;
         const size_t lds = ((size_t)EXC_COARSE_WORDS + ns) * 4;
         const uint32_t grid = nblk < 8192u ? nblk : 8192u;
+        if (nblk)                                                          // (an empty shard: nothing to mark, the suffixes of its range are added below)
         hipLaunchKernelGGL(k_exc_mark, dim3(grid), dim3(256), lds, st, bsa, blcp, s, d_exc, E, cshift,
                            shard.sharded ? (uint32_t)(shard.D - 1) : 0u, shard.cap, bits, blkcnt, nblk, list, list_cap,
                            (unsigned int*)pl.sc(Pipeline::SC_TMP0));
@@ -610,6 +611,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
     }
     // the listed bytes back into the text: every comparison from here on is on the caller's text
     hipLaunchKernelGGL(k_exc_restore, dim3((E + 255) / 256), dim3(256), 0, st, d_text, (const uint32_t*)pl.exc_pos.p, (const uint8_t*)pl.exc_byte.p, E);
+    pl.exc_pending = 0;
     if ((rc = pl.scan_u32(blkcnt, nblk + 1, blkoff))) return rc;          // (one entry past the last block: the total)
     unsigned long long tot = 0;
     if (pl.d2h(&tot, pl.sc(Pipeline::SC_SCANTOTAL), 8) != hipSuccess || pl.sync_reads() != hipSuccess) { pl.set_error("marking the affected suffixes failed"); return SUFR_HIP_E_HIP; }
@@ -639,6 +641,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
                           (unsigned long long)A_out, s, (unsigned long long)A);
     if (*s_out > out_cap) { pl.set_error("output capacity " + std::to_string(out_cap) + " < num_suffixes " + std::to_string(*s_out)); return SUFR_HIP_E_CAPACITY; }
     if (A == 0 && A_out == 0) {
+        if (s == 0) return 0;
         if (hipMemcpyAsync(out_sa, bsa, (size_t)s * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
             hipMemcpyAsync(out_lcp, blcp, (size_t)s * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { pl.set_error("copy failed"); return SUFR_HIP_E_HIP; }
         return 0;
@@ -660,6 +663,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
                        (const uint32_t*)blkoff, (const uint32_t*)list, (uint32_t)A, ins_rank, ins_u);
     }
     hipLaunchKernelGGL(k_exc_block_counts, dim3((nblk + 1 + 255) / 256), dim3(256), 0, st, (const uint32_t*)blkoff, nblk, (const uint32_t*)ins_u, (uint32_t)A, cblk);
+    if (nblk)
     hipLaunchKernelGGL(k_exc_merge, dim3(nblk < 8192u ? nblk : 8192u), dim3(256), 0, st, X, bsa, blcp, s, (const unsigned long long*)bits,
                        (const uint32_t*)blkoff, (const uint32_t*)cblk, (const uint32_t*)list, (const uint32_t*)ins_u, nblk, out_sa, out_lcp);
     if (A)

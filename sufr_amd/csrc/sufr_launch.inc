@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
@@ -82,8 +83,17 @@ public:
     // levels: latency-bound kernels and host round trips, level after level.  Round 6 runs the first chain on a helper pipeline
     // of its own (own stream, level arrays, scalars, read-back buffer; a host thread drives it) while this one does the tie runs:
     // the two write disjoint ranks of SA / LCP.  --dna on the 3.1 Gb stand-in: 0.297 -> 0.26 s (profiles/r06_input_classes.txt).
+    // That holds for the text-keyed levels only: prefix doubling keys a suffix by the RANK of another one, which may lie in a
+    // left-over bucket, so the tie chain joins the helper (and places the run buckets) before it enters run_doubling.
     std::unique_ptr<Pipeline> helper;
     bool overlap_chains = true;    // probes: off = one chain after the other (rounds 1-5)
+    static constexpr uint64_t OVERLAP_MIN_DEFAULT = (uint64_t)1 << 22;
+    uint64_t opt_overlap_min = 0;  // left-over records from which their chain runs on the helper (sufr_hip_set_overlap_min; 0: the default, ~0: never)
+    uint32_t last_overlapped = 0;  // the last build ran the left-over chain on the helper (windowed builds: one of the windows did)
+    uint64_t dbl_entries = 0;      // entries into run_doubling by this pipeline in the current build
+    uint64_t last_doublings = 0;   // ... of the last build, both chains (windowed builds: all windows)
+    std::function<int()> before_doubling;      // run_levels calls it right before run_doubling (the join of the helper chain)
+    uint32_t exc_pending = 0;      // listed bytes that are still 'N' in `text` (put back by exc_reinsert, or on the way out of the build)
     bool mql_fast_ok = true;       // probes: off = a capped build is the exact build + apply_max_query_len (rounds 1-5)
     bool exc_disable = false;      // this build takes the general code table whatever the text holds (the retry of a build that listed too much)
     bool no_exceptions = false;    // probes: every byte outside the table sends the build to the general code table (round 5)
@@ -1143,6 +1153,7 @@ public:
                 st.deep_records -= m2;                    // (counted again by the rounds)
                 st.num_levels--;
                 st.num_large_groups -= L;
+                if (before_doubling && (rc = before_doubling())) return rc;     // (every rank outside this chain is final from here on)
                 return run_doubling((const uint32_t*)A.idxA.p, (const uint32_t*)A.segA.p, (const uint32_t*)A.opos.p,
                                     (const uint32_t*)starts.p, (const uint32_t*)depth_nxt->p, L, m2, d_text, n, kp, d_sa,
                                     d_lcp, z.s_total, lv[which ^ 1], st);
@@ -1228,6 +1239,7 @@ public:
     {
         const DblShard dsh = dbl_shard;
         int rc;
+        dbl_entries++;
         const size_t rwords = (size_t)s / 32 + 2;
         const size_t pwords = (size_t)(n / 64) + 2;
         if ((rc = ensure(rankbuf, (size_t)n * 4 + 64))) return rc;
@@ -1717,9 +1729,34 @@ public:
     }
 
     // ---- the build ------------------------------------------------------------------------------
+    // Every way out of a build that listed bytes outside the DNA table -- an empty build, outputs that are too small, an
+    // allocation that fails -- hands out the caller's text: what exc_reinsert has not put back yet is put back here (the helper
+    // chain, which reads the text, has been joined by then).
     int sort_device_u32(const void* d_in, uint64_t n, uint32_t flags, uint32_t shard_index,
                         uint32_t num_shards, uint32_t* d_sa, uint32_t* d_lcp, uint64_t cap,
                         uint64_t* num_suffixes_out, sufr_hip_stats* st_out)
+    {
+        last_overlapped = 0; last_doublings = 0; dbl_entries = 0;
+        if (helper) helper->dbl_entries = 0;
+        const int rc = sort_build(d_in, n, flags, shard_index, num_shards, d_sa, d_lcp, cap, num_suffixes_out, st_out);
+        before_doubling = nullptr;
+        last_doublings = dbl_entries + (helper ? helper->dbl_entries : 0);       // (both chains: the helper has been joined)
+        if (exc_pending) {
+            const uint32_t E = exc_pending;
+            exc_pending = 0;
+            hipLaunchKernelGGL(k_exc_restore, dim3((E + 255) / 256), dim3(256), 0, stream, (uint8_t*)text.p,
+                               (const uint32_t*)exc_pos.p, (const uint8_t*)exc_byte.p, E);
+            if ((hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) && !rc) {
+                set_error("putting the listed bytes back into the text failed");
+                return SUFR_HIP_E_HIP;
+            }
+        }
+        return rc;
+    }
+
+    int sort_build(const void* d_in, uint64_t n, uint32_t flags, uint32_t shard_index,
+                   uint32_t num_shards, uint32_t* d_sa, uint32_t* d_lcp, uint64_t cap,
+                   uint64_t* num_suffixes_out, sufr_hip_stats* st_out)
     {
         sufr_hip_stats st;
         memset(&st, 0, sizeof st);
@@ -1872,6 +1909,7 @@ public:
             if (foreign == 0 || (foreign <= EXC_MAX_LIST && foreign * 64 <= n && !no_exceptions)) {
                 dna_table = true;
                 nexc = (uint32_t)foreign;
+                exc_pending = nexc; st.num_exceptions = nexc;
                 memset(hist, 0, sizeof hist);
                 for (int c = 1; c < 8; c++) hist[dna_bytes[c]] = cnt9[c];
             } else {
@@ -2206,13 +2244,64 @@ public:
         const uint64_t s = s_ull;
         st.num_suffixes = s;
         if (num_suffixes_out) *num_suffixes_out = s;
-        if (s == 0) { if (st_out) *st_out = st; return 0; }
+        uint32_t* const caller_sa = d_sa; uint32_t* const caller_lcp = d_lcp;
+        // ---- the listed bytes back into the text, the suffixes that looked at them re-placed (sufr_exc.inc): bsa / blcp = the m
+        // ranks of the build on 'N', the caller's arrays take the result.  `rebuilt`: the general code table has built the text instead.
+        uint32_t mql_count = 0;                                // suffixes of the finished arrays
+        auto reinsert_listed = [&](const uint32_t* bsa, const uint32_t* blcp, uint32_t m, bool& rebuilt) -> int {
+            rebuilt = false;
+            HIP_TRY(hipEventRecord(ev[9], stream));
+            std::vector<uint32_t> ep(nexc);
+            HIP_TRY(hipMemcpyAsync(ep.data(), exc_pos.p, (size_t)nexc * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(sync_reads());
+            std::sort(ep.begin(), ep.end());
+            int rc2;
+            if ((rc2 = ensure(exc_sorted, (size_t)nexc * 4))) return rc2;
+            HIP_TRY(hipMemcpyAsync(exc_sorted.p, ep.data(), (size_t)nexc * 4, hipMemcpyHostToDevice, stream));
+            uint64_t affected = 0, s_final = m;
+            ExcShard esh;
+            esh.sharded = num_shards > 1 ? 1 : 0; esh.raw_lo = raw_lo; esh.raw_hi = raw_hi; esh.D = mbits / kp.b; esh.allow_amb = allow_amb ? 1 : 0;
+            esh.cap = mql_fast ? (uint32_t)opt_max_query_len : 0u;
+            rc2 = exc_reinsert(*this, d_text, n, bsa, blcp, m, (const uint32_t*)exc_sorted.p, nexc, caller_sa, caller_lcp, cap, &affected, esh, &s_final);
+            HIP_TRY(sync_reads());                              // (ep: a host vector)
+            if (rc2 == SUFR_HIP_E_UNSUPPORTED && err.empty()) {
+                // more suffixes looked at the listed bytes than the whole-text sort takes: the general code table, from the caller's text
+                exc_disable = true;
+                rc2 = sort_device_u32(d_in_caller, n, flags, shard_index, num_shards, caller_sa, caller_lcp, cap, num_suffixes_out, st_out);
+                exc_disable = false;
+                rebuilt = true;
+                return rc2;
+            }
+            if (rc2 == SUFR_HIP_E_CAPACITY && num_suffixes_out) *num_suffixes_out = s_final;      // (what the call needs)
+            if (rc2) return rc2;
+            st.num_exceptions = nexc; st.num_reinserted = affected;
+            if (s_final != m) {                                // (a shard: suffixes moved between the shards)
+                st.num_suffixes = s_final;
+                if (num_suffixes_out) *num_suffixes_out = s_final;
+            }
+            mql_count = (uint32_t)s_final;
+            HIP_TRY(hipEventRecord(ev[10], stream));
+            return 0;
+        };
+        if (s == 0) {
+            // (a shard whose range is empty in the text as it was BUILT still takes the suffixes whose true first bytes fall into it)
+            // -- unless that range holds no digit at all (bin_lo == bin_hi: nothing lies in it, and its raw bounds say nothing)
+            if (nexc && num_shards > 1 && bin_lo < bin_hi) {
+                bool rebuilt = false;
+                rc = reinsert_listed(nullptr, nullptr, 0u, rebuilt);
+                if (rc || rebuilt) return rc;
+                if (!mql_fast && opt_max_query_len > 0 && (rc = apply_max_query_len(opt_max_query_len, n, caller_sa, caller_lcp, mql_count))) return rc;
+                HIP_TRY(sync_reads());
+                HIP_TRY(hipGetLastError());
+            }
+            if (st_out) *st_out = st;
+            return 0;
+        }
         if (s > cap || !d_sa || !d_lcp) {
             set_error("output capacity " + std::to_string(cap) + " < num_suffixes " + std::to_string(s));
             return SUFR_HIP_E_CAPACITY;
         }
         const uint32_t m0 = (uint32_t)s;
-        uint32_t* const caller_sa = d_sa; uint32_t* const caller_lcp = d_lcp;
         if (nexc) {                                            // the arrays of the build on 'N' for the listed bytes: the caller's are written by exc_reinsert
             // (re-writing the caller's arrays in place, only the blocks of ranks that change, was built and measured in round 6: a
             // suffix that leaves its rank comes back millions of ranks away -- "ACGR" sorts behind ALL of "ACGN...", and half of a
@@ -2436,8 +2525,19 @@ public:
         st.num_levels = 1;
 
         // (the chain of the left-over buckets when it runs on the helper pipeline: joined after the tie runs, and on every way out)
+        // (prefix doubling reads the ranks of ALL suffixes: the tie chain joins it before its first round, before_doubling)
         struct LeftChain { std::thread th; int rc = 0; sufr_hip_stats st; ~LeftChain() { if (th.joinable()) th.join(); } } left_chain;
         memset(&left_chain.st, 0, sizeof left_chain.st);
+        // the join: once per build, whoever comes first -- its result, its counts, then the run buckets it left to be expanded
+        auto join_left_chain = [&]() -> int {
+            if (!left_chain.th.joinable()) return 0;           // (not started, or joined already)
+            left_chain.th.join();
+            if (left_chain.rc) { err = helper->err; return left_chain.rc; }
+            st.num_levels += left_chain.st.num_levels;
+            st.num_large_groups += left_chain.st.num_large_groups;
+            st.deep_records += left_chain.st.deep_records;
+            return run_groups_expand(d_text, n, kp, d_sa, d_lcp);
+        };
         // ---- buckets whose members agree on all K key characters: groups for the re-keying levels ----------
         {
             // (run buckets of the whole key among them are found here; those taken out after the first level join the list now,
@@ -2471,7 +2571,10 @@ public:
                 lg.seg_depth = left_depth; lg.seg_depth_of = depth_of;
                 lg.pos_keys = mql_fast;
                 if (mql_fast) lg.seg_depth = (uint32_t)kp.K;          // (they agree on their L characters: every LCP inside is cut back to L)
-                if (overlap_chains && left_records >= ((uint64_t)1 << 22)) {
+                const bool side_by_side = overlap_chains && left_records >= (opt_overlap_min ? opt_overlap_min : OVERLAP_MIN_DEFAULT);
+                if (debug) fprintf(stderr, "[sufr_hip debug] left-over buckets: groups=%u records=%llu%s\n", left_groups,
+                                   (unsigned long long)left_records, side_by_side ? " (on the helper pipeline)" : "");
+                if (side_by_side) {
                     // this chain on the helper pipeline, side by side with the tie runs below
                     if (!helper) {
                         helper.reset(new Pipeline);
@@ -2488,6 +2591,8 @@ public:
                     lg.heads_cur = &H.headsA; lg.heads_nxt = &H.headsB; lg.depth_cur = &H.depthA; lg.depth_nxt = &H.depthB;
                     H.pin_items.clear(); H.pin_used = 0; H.pub_items.clear(); H.copies_queued = false; H.zlist.n = 0;
                     left_chain.st = sufr_hip_stats(); left_chain.rc = 0;
+                    H.dbl_entries = 0;
+                    last_overlapped = 1;
                     left_chain.th = std::thread([&H, &left_chain, lg, d_text, n, kp, d_sa, d_lcp, this]() {
                         (void)hipSetDevice(device);
                         left_chain.rc = H.run_levels(lg, d_text, n, kp, d_sa, d_lcp, left_chain.st);
@@ -2568,53 +2673,23 @@ public:
                 dbl_shard = DblShard{kp.packed, kp.b, mbits, raw_lo, raw_hi, num_shards > 1 ? 1 : 0};
                 lt.allow_doubling = !mql_fast && (num_shards <= 1 || (packed_path && kp.packed != nullptr)); lt.s_total = m0;
                 lt.pos_keys = mql_fast;
-                if ((rc = run_levels(lt, d_text, n, kp, d_sa, d_lcp, st))) return rc;
+                before_doubling = join_left_chain;
+                rc = run_levels(lt, d_text, n, kp, d_sa, d_lcp, st);
+                before_doubling = nullptr;
+                if (rc) return rc;
             }
         }
-        if (left_chain.th.joinable()) {
-            left_chain.th.join();
-            if (left_chain.rc) { err = helper->err; return left_chain.rc; }
-            st.num_levels += left_chain.st.num_levels;
-            st.num_large_groups += left_chain.st.num_large_groups;
-            st.deep_records += left_chain.st.deep_records;
-            if ((rc = run_groups_expand(d_text, n, kp, d_sa, d_lcp))) return rc;
-        }
-        uint32_t mql_count = m0;                               // suffixes of the finished arrays
+        if ((rc = join_left_chain())) return rc;
+        mql_count = m0;
         if (mql_fast) {                                        // (before the listed bytes are dealt with: their pass compares under the cap)
             hipLaunchKernelGGL(k_mql_cap, dim3((m0 / 4 + 256) / 256), dim3(256), 0, stream, d_lcp, m0, (uint32_t)opt_max_query_len);
             HIP_TRY(hipGetLastError());
         }
         if (nexc) {
-            HIP_TRY(hipEventRecord(ev[9], stream));
-            std::vector<uint32_t> ep(nexc);
-            HIP_TRY(hipMemcpyAsync(ep.data(), exc_pos.p, (size_t)nexc * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(sync_reads());
-            std::sort(ep.begin(), ep.end());
-            if ((rc = ensure(exc_sorted, (size_t)nexc * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(exc_sorted.p, ep.data(), (size_t)nexc * 4, hipMemcpyHostToDevice, stream));
-            uint64_t affected = 0, s_final = m0;
-            ExcShard esh;
-            esh.sharded = num_shards > 1 ? 1 : 0; esh.raw_lo = raw_lo; esh.raw_hi = raw_hi; esh.D = mbits / kp.b; esh.allow_amb = allow_amb ? 1 : 0;
-            esh.cap = mql_fast ? (uint32_t)opt_max_query_len : 0u;
-            rc = exc_reinsert(*this, d_text, n, d_sa, d_lcp, m0, (const uint32_t*)exc_sorted.p, nexc, caller_sa, caller_lcp, cap, &affected, esh, &s_final);
-            HIP_TRY(sync_reads());                              // (ep: a host vector)
-            if (rc == SUFR_HIP_E_UNSUPPORTED && err.empty()) {
-                // more suffixes looked at the listed bytes than the whole-text sort takes: the general code table, from the caller's text
-                exc_disable = true;
-                rc = sort_device_u32(d_in_caller, n, flags, shard_index, num_shards, caller_sa, caller_lcp, cap, num_suffixes_out, st_out);
-                exc_disable = false;
-                return rc;
-            }
-            if (rc == SUFR_HIP_E_CAPACITY && num_suffixes_out) *num_suffixes_out = s_final;      // (what the call needs)
-            if (rc) return rc;
+            bool rebuilt = false;
+            rc = reinsert_listed(d_sa, d_lcp, m0, rebuilt);
+            if (rc || rebuilt) return rc;
             d_sa = caller_sa; d_lcp = caller_lcp;
-            st.num_exceptions = nexc; st.num_reinserted = affected;
-            if (s_final != m0) {                               // (a shard: suffixes moved between the shards)
-                st.num_suffixes = s_final;
-                if (num_suffixes_out) *num_suffixes_out = s_final;
-            }
-            mql_count = (uint32_t)s_final;
-            HIP_TRY(hipEventRecord(ev[10], stream));
         }
         if (!mql_fast && opt_max_query_len > 0 && (rc = apply_max_query_len(opt_max_query_len, n, d_sa, d_lcp, mql_count))) return rc;
         HIP_TRY(hipEventRecord(ev[8], stream));

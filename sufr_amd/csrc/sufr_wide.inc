@@ -639,6 +639,8 @@ int sort_device_wide(Pipeline& pl, const void* d_in, uint64_t n, uint32_t flags,
     if (hipSetDevice(pl.device) != hipSuccess) { pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
     struct NotResident { Pipeline& p; ~NotResident() { p.resident_text_len = 0; } } not_resident{pl};   // (pl.text ends up holding a window)
     pl.wide_text_len = 0;                                    // (set again when the build succeeds: what the shard stitch checks)
+    // (sufr_hip_overlapped / sufr_hip_doublings speak of the whole build: every window's build adds to them)
+    struct Chains { Pipeline& p; uint32_t overlapped = 0; uint64_t doublings = 0; ~Chains() { p.last_overlapped = overlapped; p.last_doublings = doublings; } } chains{pl};
     WidePlan plan = wide_plan(n, window, margin);
     // the order of the build: a window must hold every symbol a comparison of its own suffixes looks at
     WideOrder wo = {0, 0u, nullptr, 0u};
@@ -741,7 +743,9 @@ int sort_device_wide(Pipeline& pl, const void* d_in, uint64_t n, uint32_t flags,
             if ((rc = pl.ensure(pl.sa32, len * 4 + 4)) || (rc = pl.ensure(pl.lcp32, len * 4 + 4))) return rc;
             uint64_t s = 0;
             sufr_hip_stats wst;
-            if ((rc = pl.sort_device_u32(t + base, len, wflags, 0, 1, (uint32_t*)pl.sa32.p, (uint32_t*)pl.lcp32.p, len, &s, &wst))) return rc;
+            rc = pl.sort_device_u32(t + base, len, wflags, 0, 1, (uint32_t*)pl.sa32.p, (uint32_t*)pl.lcp32.p, len, &s, &wst);
+            chains.overlapped |= pl.last_overlapped; chains.doublings += pl.last_doublings;
+            if (rc) return rc;
             if (i == 0 && attempt == 0) acc = wst;
             else { acc.ms_total += wst.ms_total; acc.ms_normalize += wst.ms_normalize; acc.ms_hist_text += wst.ms_hist_text;
                    acc.ms_partition += wst.ms_partition; acc.ms_passes += wst.ms_passes; acc.ms_finish += wst.ms_finish;

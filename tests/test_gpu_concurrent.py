@@ -1,7 +1,10 @@
 """Several builds at the same time on one GPU: one context (DeviceBuilder) per host thread, each with its own stream, scalars and
-mapped read-back buffer (Pipeline::sync_reads spins on a word in mapped pinned memory; a repeat-rich build adds a helper pipeline
-on a thread of its own).  Every build equals the oracle; the library's contract is one thread per context, any number of contexts
-(INTEGRATION.md)."""
+mapped read-back buffer (Pipeline::sync_reads spins on a word in mapped pinned memory).  Every build equals the oracle; the
+library's contract is one thread per context, any number of contexts.
+
+A build adds a helper pipeline on a thread of its own from 2^22 left-over records on: the texts of the first test, 2 M symbols
+at the most, stay far below that and never start one.  The second test lowers the threshold (Context.set_overlap_min) and runs
+two such builds at once: four streams and two helper threads on one device."""
 import threading
 
 import numpy as np
@@ -56,6 +59,35 @@ def test_four_contexts_on_four_threads_equal_the_oracle(oracle):
             errors.append(f"text {k}: {e!r}")
 
     threads = [threading.Thread(target=work, args=(k,)) for k in range(len(cases))]
+    for t in threads: t.start()
+    for t in threads: t.join(timeout=600)
+    assert not any(t.is_alive() for t in threads), "a build did not return"
+    assert not errors, errors
+
+
+def test_two_contexts_with_helper_pipelines_equal_the_oracle():
+    """two threads, two contexts, both with the left-over chain on the helper pipeline, three builds each: the text of
+    test_gpu_overlap.py (left-over buckets and prefix doubling in one build) and the same text with 30 listed bytes"""
+    import test_gpu_overlap as ov
+    cases = [(ov.text_a()[0], ov.want("a")), (ov.text_d(), ov.want("d"))]
+    errors = []
+
+    def work(k):
+        try:
+            raw, (osa, olcp) = cases[k]
+            x = torch.from_numpy(raw.copy()).cuda()
+            db = sufr_amd.DeviceBuilder(0)
+            for rep in range(3):
+                got = ov.build(db, x, overlap_min=1)
+                if got[2] != [(1, got[2][0][1])] or got[2][0][1] < 1:
+                    errors.append(f"text {k}, build {rep}: (helper, doublings) = {got[2]}"); break
+                if not (np.array_equal(got[0], osa) and np.array_equal(got[1], olcp)):
+                    errors.append(f"text {k}, build {rep}: arrays differ from the oracle's"); break
+            db.close()
+        except Exception as e:                        # noqa: BLE001 (reported below, in the main thread)
+            errors.append(f"text {k}: {e!r}")
+
+    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
     for t in threads: t.start()
     for t in threads: t.join(timeout=600)
     assert not any(t.is_alive() for t in threads), "a build did not return"

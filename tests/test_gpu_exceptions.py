@@ -2,6 +2,7 @@
 (sufr_amd/csrc/sufr_exc.inc): the build runs on 'N' in their place and the suffixes whose comparisons reached such a byte are
 re-placed by whole-text comparison.  Every case: whole SA and LCP equal the CPU oracle's (which compares raw bytes,
 sufr_builder.rs:346-394), the normalised text handed back carries the original bytes, and the stats say the path was taken."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -254,3 +255,131 @@ def test_long_n_runs_under_allow_ambiguity_are_exact(oracle, shards, cap, plante
     keep = np.ones(osa.size, dtype=bool); keep[starts[1:]] = False
     bad = np.nonzero((glcp != olcp) & keep)[0]
     assert bad.size == 0, f"LCP differs at rank {bad[0]}: got {glcp[bad[0]]} want {olcp[bad[0]]} ({bad.size} ranks)"
+
+
+# ---- the ways out of a build before the listed bytes are re-placed: the text handed out is the caller's all the same --------------
+def _context_text(ctx, n):
+    """the normalised text the context keeps on the device after a build through sufr_hip_sort_device_u64 (what the shard stitch
+    and the device search read), copied to the host with the HIP runtime the process has loaded"""
+    L = sufr_amd.lib()
+    dev = C.c_int(-1); t = C.c_void_p(); sa = C.c_void_p(); lcp = C.c_void_p()
+    L.sufr_hip_resident_arrays_.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.sufr_hip_resident_arrays_.restype = C.c_int
+    ctx.check(L.sufr_hip_resident_arrays_(ctx.handle, C.byref(dev), C.byref(t), C.byref(sa), C.byref(lcp)))
+    ctx.synchronize()
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    hip = C.CDLL(path)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]; hip.hipMemcpy.restype = C.c_int
+    out = np.zeros(n, dtype=np.uint8)
+    assert hip.hipMemcpy(out.ctypes.data, t, n, 2) == 0          # hipMemcpyDeviceToHost
+    return out
+
+
+def _listed(norm):
+    return int((~np.isin(norm, np.frombuffer(b"$%ACGNT", dtype=np.uint8))).sum())
+
+
+@pytest.mark.parametrize("soft", [False, True])
+def test_an_empty_build_keeps_its_bytes(oracle, soft):
+    """500 'N' with an 'R' and a 'y': --dna without --allow-ambiguity, no sentinel -- no position starts a suffix, the build
+    returns right after the text pass, which has written 'N' over the listed bytes.  The text handed out is the reference's
+    normalised text all the same (upper-cased: 'R' and 'Y', two listed bytes; under --ignore-softmask the reference turns the
+    lowercase 'y' into 'N' itself, sufr_builder.rs:144-160, and one listed byte is left), and the stats count the listed bytes."""
+    raw = np.full(500, ord("N"), np.uint8)
+    raw[100] = ord("R"); raw[300] = ord("y")
+    norm = oracle.normalize(raw, soft)
+    assert _listed(norm) == (1 if soft else 2) and norm[100] == ord("R") and norm[300] == (ord("N") if soft else ord("Y"))
+    ctx = sufr_amd.Context(0)
+    b = sufr_amd.SufrBuilder(sufr_amd.SufrBuilderArgs(text=raw, is_dna=True, ignore_softmask=soft), index_width=4, ctx=ctx, write=False)
+    assert b.num_suffixes == 0
+    assert np.array_equal(b.text, norm), f"host buffers: text differs at {np.nonzero(b.text != norm)[0]}"
+    assert b.stats.num_exceptions == _listed(norm)
+    ctx.close()
+    db = sufr_amd.DeviceBuilder(0)
+    sa, lcp = db.sort(torch.from_numpy(raw).cuda(), raw_text=True, is_dna=True, ignore_softmask=soft, index_width=8)
+    assert sa.numel() == 0 and lcp.numel() == 0 and db.stats.num_suffixes == 0
+    got = _context_text(db.ctx, raw.size)
+    assert np.array_equal(got, norm), f"device entry point: text differs at {np.nonzero(got != norm)[0]}"
+    assert db.stats.num_exceptions == _listed(norm)
+    db.close()
+
+
+def test_a_build_that_does_not_fit_then_fits(oracle):
+    """outputs of 10 entries: the capacity error and the number of suffixes the call needs -- and the context's text is the
+    caller's, not the build's; the same context then builds the text into full-size outputs"""
+    rng = np.random.default_rng(41)
+    raw = _acgt(rng, 300_000)
+    raw[40_000:40_400] = raw[200_000:200_400]
+    raw[rng.choice(raw.size - 1, 20, replace=False)] = IUPAC[rng.integers(0, 10, 20)]
+    raw[-1] = ord("$")
+    norm = oracle.normalize(raw, False)
+    assert _listed(norm) == 20
+    osa, olcp, _ = oracle.build(norm, is_dna=True, threads=8)
+    x = torch.from_numpy(raw).cuda()
+    db = sufr_amd.DeviceBuilder(0)
+    small_sa = torch.zeros(10, dtype=torch.int64, device="cuda"); small_lcp = torch.zeros(10, dtype=torch.int64, device="cuda")
+    ns = C.c_uint64(0)
+    rc = sufr_amd.lib().sufr_hip_sort_device_u64(db.ctx.handle, x.data_ptr(), x.numel(), 1 | 8, 0, None, 16, 42, 0, 1, small_sa.data_ptr(),
+                                                small_lcp.data_ptr(), 10, C.byref(ns), C.byref(db.stats))
+    assert rc == -5 and ns.value == osa.size, (rc, ns.value, osa.size)          # SUFR_HIP_E_CAPACITY
+    got = _context_text(db.ctx, raw.size)
+    assert np.array_equal(got, norm), f"after the capacity error: text differs at {np.nonzero(got != norm)[0][:8]}"
+    out_sa = torch.zeros(raw.size, dtype=torch.int64, device="cuda"); out_lcp = torch.zeros(raw.size, dtype=torch.int64, device="cuda")
+    sa, lcp = db.sort(x, raw_text=True, is_dna=True, index_width=8, out_sa=out_sa, out_lcp=out_lcp)
+    assert db.stats.num_exceptions == 20
+    assert np.array_equal(sa.cpu().numpy().astype(np.uint32), osa) and np.array_equal(lcp.cpu().numpy().astype(np.uint32), olcp)
+    assert np.array_equal(_context_text(db.ctx, raw.size), norm)
+    db.close()
+
+
+def _empty_shard_text(case):
+    if case == "a_runs":                         # 3 000 'A': the bucket AAAAA holds all but a few suffixes, the digits after it few
+        raw = np.full(3001, ord("A"), np.uint8); at = [400, 1000, 1001, 1900, 2995]
+    elif case == "t_runs":
+        # 3 000 'T': TTTTT is the LAST digit of the built text, the ranks behind the first own the range above every digit of
+        # the built text -- where the true first digits of the suffixes with a 'Y' (above 'T') among their first five bytes lie
+        raw = np.full(3001, ord("T"), np.uint8); at = [0, 700, 1500, 1502, 2996]
+    else:                                        # fewer suffixes than shards: ranks that own digits no suffix starts with
+        raw = np.full(401, ord("N"), np.uint8); at = [150]; raw[149] = ord("A"); raw[300] = ord("C")
+    raw[at] = ord("Y")
+    raw[-1] = ord("$")
+    return raw
+
+
+@pytest.mark.parametrize("case", ["a_runs", "t_runs", "few_suffixes"])
+def test_empty_shards_lose_and_repeat_no_suffix(oracle, case):
+    """more shards than the built text has first digits to deal out: ranks whose own range is empty (top_hi <= top_lo) or holds
+    no suffix.  Every rank still puts the listed bytes back and takes the suffixes whose TRUE first bytes lie in its range --
+    those and no others: the shards concatenate to the oracle's arrays."""
+    raw = _empty_shard_text(case)
+    amb = case != "few_suffixes"
+    shards = 7
+    if amb:
+        osa, olcp, _ = oracle.build(raw, is_dna=True, allow_ambiguity=True, threads=8)
+    else:                                        # (three suffixes: the reference cannot draw its pivots; the naive witness)
+        from oracle_helper import naive_sa_lcp
+        osa, olcp = naive_sa_lcp(raw, True, False)
+        osa = np.asarray(osa, dtype=np.uint32); olcp = np.asarray(olcp, dtype=np.uint32)
+        assert osa.size == 3
+    x = torch.from_numpy(raw).cuda()
+    db = sufr_amd.DeviceBuilder(0)
+    parts_sa, parts_lcp, ranges = [], [], []
+    for k in range(shards):
+        out_sa = torch.zeros(raw.size, dtype=torch.int32, device="cuda"); out_lcp = torch.zeros(raw.size, dtype=torch.int32, device="cuda")
+        sa, lcp = db.sort(x, raw_text=True, is_dna=True, allow_ambiguity=amb, shard_index=k, num_shards=shards, out_sa=out_sa, out_lcp=out_lcp)
+        assert db.stats.bits_per_char == 3 and db.stats.num_exceptions == _listed(raw), (k, db.stats.num_exceptions)
+        assert db.stats.num_suffixes == sa.numel()
+        ranges.append((db.stats.top_lo, db.stats.top_hi))
+        parts_sa.append(sa.cpu().numpy().view(np.uint32).copy()); parts_lcp.append(lcp.cpu().numpy().view(np.uint32).copy())
+    db.close()
+    sizes = [p.size for p in parts_sa]
+    print(f"{case}: first-digit ranges {ranges}, shard sizes {sizes}")
+    assert any(hi <= lo for lo, hi in ranges), f"no rank's own range is empty: {ranges}"
+    gsa = np.concatenate(parts_sa); glcp = np.concatenate(parts_lcp)
+    assert np.unique(gsa).size == gsa.size, f"a suffix appears twice (shard sizes {sizes})"
+    assert gsa.size == osa.size, f"{osa.size - gsa.size} suffixes lost (shard sizes {sizes})"
+    bad = np.nonzero(gsa != osa)[0]
+    assert bad.size == 0, f"SA differs at rank {bad[0]}: got {gsa[bad[0]]} want {osa[bad[0]]} ({bad.size} ranks; shard sizes {sizes})"
+    keep = np.ones(osa.size, dtype=bool); keep[np.cumsum(sizes[:-1])[np.cumsum(sizes[:-1]) < osa.size]] = False      # (a shard's first LCP is the stitch's)
+    assert np.array_equal(glcp[keep], olcp[keep])
