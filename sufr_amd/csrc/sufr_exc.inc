@@ -614,7 +614,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
     pl.exc_pending = 0;
     if ((rc = pl.scan_u32(blkcnt, nblk + 1, blkoff))) return rc;          // (one entry past the last block: the total)
     unsigned long long tot = 0;
-    if (pl.d2h(&tot, pl.sc(Pipeline::SC_SCANTOTAL), 8) != hipSuccess || pl.sync_reads() != hipSuccess) { pl.set_error("marking the affected suffixes failed"); return SUFR_HIP_E_HIP; }
+    if (pl.read_at_sync(&tot, pl.sc(Pipeline::SC_SCANTOTAL), 8) != hipSuccess || pl.sync_reads() != hipSuccess) { pl.set_error("marking the affected suffixes failed"); return SUFR_HIP_E_HIP; }
     const uint64_t A_out = tot;                                            // ranks taken out of the arrays
     if (A_out > EXC_MAX_AFFECTED) return SUFR_HIP_E_UNSUPPORTED;
     ExcText X;
@@ -630,7 +630,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
         hipLaunchKernelGGL(k_exc_shard_add, dim3((E * (uint32_t)shard.D + 255) / 256), dim3(256), 0, st, X, shard, list2, list_cap,
                            (unsigned int*)pl.sc(Pipeline::SC_TMP1));
         unsigned long long cnt = 0;
-        if (pl.d2h(&cnt, pl.sc(Pipeline::SC_TMP1), 8) != hipSuccess || pl.sync_reads() != hipSuccess) { pl.set_error("re-sharding the affected suffixes failed"); return SUFR_HIP_E_HIP; }
+        if (pl.read_at_sync(&cnt, pl.sc(Pipeline::SC_TMP1), 8) != hipSuccess || pl.sync_reads() != hipSuccess) { pl.set_error("re-sharding the affected suffixes failed"); return SUFR_HIP_E_HIP; }
         A = (uint32_t)cnt;
         if (A > EXC_MAX_AFFECTED) return SUFR_HIP_E_UNSUPPORTED;
         list = list2;

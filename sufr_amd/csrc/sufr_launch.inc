@@ -164,9 +164,9 @@ public:
 
     // Small results come back through a pinned staging buffer: a device-to-host copy into pageable memory (a stack variable, a
     // vector) costs ~9 us more per round trip -- 23 against 14 us for kernel + copy + synchronise, profiles/micro/readback.hip --
-    // and a build makes 8 (4.6 Mb) to ~30 (3.1 Gb) of them.  d2h() queues the copy into the staging buffer, sync_reads() waits for
+    // and a build makes 8 (4.6 Mb) to ~30 (3.1 Gb) of them.  d2h_at() queues the copy into the staging buffer, sync_reads() waits for
     // the stream and hands the bytes out; what does not fit the buffer is copied directly.  Every synchronisation of this file
-    // goes through sync_reads(); a build that fails between the two leaves its queue to be dropped by the next one.
+    // goes through sync_reads(); a build that fails between the two leaves its queue to be dropped by the next one (reset_reads).
     static constexpr size_t PIN_CAP = (size_t)512 << 10;
     uint8_t* pin = nullptr;
     size_t pin_used = 0;
@@ -180,10 +180,12 @@ public:
         if (e == hipSuccess) { pin_items.push_back({dst, pin_used, bytes}); pin_used += (bytes + 63) & ~(size_t)63; copies_queued = true; }
         return e;
     }
-    // d2h(): the value is read when sync_reads() runs (every caller queues it right before; nothing that writes the source may be
-    // launched in between).  Up to eight small items go out through ONE launch of k_publish into mapped pinned memory, and the
-    // host spins on the sequence number behind them: 7 us per round trip against 16 (profiles/micro/readback.hip).  Larger
-    // ones, a ninth item, or a context without the mapped buffer take the copies.
+    // read_at_sync(): nothing is queued here -- the source is READ WHEN sync_reads() RUNS, so no kernel that writes it may be
+    // launched between the two.  Nothing checks that: every read_at_sync() stands right in front of its sync_reads(), in the same
+    // function (the stages of a build were cut so that no pair straddles two of them).  Up to eight small items go out through
+    // ONE launch of k_publish into mapped pinned memory, and the host spins on the sequence number behind them: 7 us per round
+    // trip against 16 (profiles/micro/readback.hip).  Larger ones, a ninth item, or a context without the mapped buffer take
+    // the copies of d2h_at(), queued by sync_reads() itself.
     static constexpr size_t PUB_CAP = 8192;              // bytes of results per round trip through k_publish
     uint8_t* pub = nullptr;                              // mapped pinned memory: PUB_CAP bytes + the sequence word
     uint8_t* pub_dev = nullptr;
@@ -193,13 +195,15 @@ public:
     bool pub_drop = false;                               // (probes build, SUFR_PROBE_PUBLISH_DROP: pretend it never arrives)
     struct PubItem { void* dst; const void* src; size_t bytes; };
     std::vector<PubItem> pub_items;
-    hipError_t d2h(void* dst, const void* src, size_t bytes)
+    hipError_t read_at_sync(void* dst, const void* src, size_t bytes)
     {
         pub_items.push_back({dst, src, bytes});
         return hipSuccess;
     }
     // ranges to clear, collected and cleared by one launch (k_zero_ranges)
     ZeroList zlist = {};
+    // what a build that failed left queued is dropped (the destinations of its reads are gone)
+    void reset_reads() { pin_items.clear(); pin_used = 0; pub_items.clear(); copies_queued = false; zlist.n = 0; }
     hipError_t zero_flush()
     {
         if (!zlist.n) return hipSuccess;
@@ -557,7 +561,7 @@ public:
         hipLaunchKernelGGL(k_check_sorted, dim3((m + 255) / 256), dim3(256), 0, stream, keys, segs, m, shift,
                            (uint32_t*)sc(SC_BAD));
         unsigned long long got = 0;
-        HIP_TRY(d2h(&got, sc(SC_BAD), 8));
+        HIP_TRY(read_at_sync(&got, sc(SC_BAD), 8));
         HIP_TRY(sync_reads());
         uint32_t bad = (uint32_t)got;
         fprintf(stderr, "[sufr_hip debug] %s: m=%u shift=%d first_unsorted=%s%u\n", what, m, shift,
@@ -616,7 +620,7 @@ public:
         if ((rc = scan_u32(wcnt, nchunk, woff, sc(SC_TMP0)))) return rc;
         if ((rc = scan_u32(lcnt, nchunk, loff, sc(SC_TMP1)))) return rc;
         unsigned long long tot[2] = {0, 0};
-        HIP_TRY(d2h(tot, sc(SC_TMP0), 16));
+        HIP_TRY(read_at_sync(tot, sc(SC_TMP0), 16));
         HIP_TRY(sync_reads());
         const uint32_t W = (uint32_t)tot[0], L1 = (uint32_t)tot[1];
         if ((rc = ensure(wlhead, ((size_t)W + 2) * 4))) return rc;
@@ -660,7 +664,7 @@ public:
         hipLaunchKernelGGL(k_rg_detect, dim3((nseg + 255) / 256), dim3(256), 0, stream, recs_src, seg_start,
                            (const uint32_t*)seg_size, nseg, kp.b, (int)K, min_size, d_text, (RunGroup*)(misc + 16), misc);
         uint32_t hostbuf[16 + 6 * RG_MAX_GROUPS];
-        HIP_TRY(d2h(hostbuf, misc, sizeof hostbuf));
+        HIP_TRY(read_at_sync(hostbuf, misc, sizeof hostbuf));
         HIP_TRY(sync_reads());
         const uint32_t ng = hostbuf[0] < RG_MAX_GROUPS ? hostbuf[0] : RG_MAX_GROUPS;
         if (!ng) return 0;
@@ -677,7 +681,7 @@ public:
                                (uint32_t*)nullptr, (unsigned long long*)nullptr);
             if ((rc = scan_u32((const uint32_t*)rg_blk.p, nblk, (uint32_t*)rg_blkoff.p))) return rc;
             unsigned long long tot = 0;
-            HIP_TRY(d2h(&tot, sc(SC_SCANTOTAL), 8));
+            HIP_TRY(read_at_sync(&tot, sc(SC_SCANTOTAL), 8));
             HIP_TRY(sync_reads());
             const uint32_t M = (uint32_t)tot;
             if (!M || M > g.size) continue;
@@ -690,7 +694,7 @@ public:
                                (const uint32_t*)rg_blkoff.p, (uint32_t*)nullptr, (uint32_t*)rg_rs.p + run_off,
                                (uint32_t*)rg_rl.p + run_off, lhist, (unsigned long long*)(lhist + (size_t)RG_REPL * RG_HBINS));
             std::vector<uint32_t> hr((size_t)RG_REPL * RG_HBINS + 2 * RG_REPL);
-            HIP_TRY(d2h(hr.data(), lhist, hr.size() * 4));
+            HIP_TRY(read_at_sync(hr.data(), lhist, hr.size() * 4));
             HIP_TRY(sync_reads());
             std::vector<uint32_t> h(RG_HBINS, 0u);
             unsigned long long records = 0;
@@ -755,7 +759,7 @@ public:
             hipLaunchKernelGGL(k_rg_long_list, dim3((M + 255) / 256), dim3(256), 0, stream, (const uint32_t*)rg_L.p, M, rcap,
                                misc + 16, misc + 8);
             std::vector<uint32_t> hb(16 + RG_NLONG);
-            HIP_TRY(d2h(hb.data(), misc, hb.size() * 4));
+            HIP_TRY(read_at_sync(hb.data(), misc, hb.size() * 4));
             HIP_TRY(sync_reads());
             if (hb[3] || hb[8] > RG_NLONG) { set_error("internal error: a run bucket did not come back in run order"); return SUFR_HIP_E_HIP; }
             const uint32_t M1 = hb[0], M0 = M - M1, R0max = hb[1], R1max = hb[2], nlong = hb[8];
@@ -790,7 +794,7 @@ public:
                 if ((rc = scan_u32((const uint32_t*)rg_tab[cls].p, (uint32_t)cells, (uint32_t*)rg_off[cls].p, sc(cls ? SC_TMP1 : SC_TMP0)))) return rc;
             }
             unsigned long long tt[2] = {0, 0};
-            HIP_TRY(d2h(tt, sc(SC_TMP0), 16));
+            HIP_TRY(read_at_sync(tt, sc(SC_TMP0), 16));
             HIP_TRY(sync_reads());
             if (R[0].nt) T[0] = tt[0];
             if (R[1].nt) T[1] = tt[1];
@@ -882,8 +886,8 @@ public:
         const size_t ne = rg_active.size() - before;
         if (!ne) return 0;
         std::vector<uint32_t> hs(nseg), hz(nseg);
-        HIP_TRY(d2h(hs.data(), segst[segcur].p, (size_t)nseg * 4));
-        HIP_TRY(d2h(hz.data(), segsz[segcur].p, (size_t)nseg * 4));
+        HIP_TRY(read_at_sync(hs.data(), segst[segcur].p, (size_t)nseg * 4));
+        HIP_TRY(read_at_sync(hz.data(), segsz[segcur].p, (size_t)nseg * 4));
         HIP_TRY(sync_reads());
         std::vector<uint32_t> taken;
         for (size_t i = before; i < rg_active.size(); i++) taken.push_back(rg_active[i].g.start);
@@ -1106,7 +1110,7 @@ public:
                                    (uint8_t*)period.p, (uint32_t*)sc(SC_MAXSIZE));
             if ((rc = scan_u32((const uint32_t*)sizes.p, L, (uint32_t*)starts.p))) return rc;
             unsigned long long two[2] = {0, 0};
-            HIP_TRY(d2h(two, sc(SC_MAXSIZE), 16));
+            HIP_TRY(read_at_sync(two, sc(SC_MAXSIZE), 16));
             HIP_TRY(sync_reads());
             const uint32_t maxsize = (uint32_t)two[0];
             const uint32_t nperiodic = (uint32_t)(two[0] >> 32);      // (k_group_extent only)
@@ -1177,7 +1181,7 @@ public:
             GroupPlan gp;
             if ((rc = group_sort_prepare((const uint32_t*)starts.p, (const uint32_t*)sizes.p, L, m2, maxsize, gp))) return rc;
             unsigned long long maxtok = 0;
-            HIP_TRY(d2h(&maxtok, sc(SC_MAXTOK), 8));
+            HIP_TRY(read_at_sync(&maxtok, sc(SC_MAXTOK), 8));
             HIP_TRY(sync_reads());
             // passes on the key digits (lowest sorted digit first), then on the segment ordinal; every token
             // of the level lies inside the sorted bits (tokens above 34 bits: runs of 2^16 bytes and more)
@@ -1289,7 +1293,7 @@ public:
                                (const uint16_t*)lut.p, kp, (const uint32_t*)i1, (const uint32_t*)g1, (const uint32_t*)dp, m,
                                (const uint32_t*)R, k1, (uint32_t*)sc(SC_MAXTOK), dsh);
             unsigned long long any = 0;
-            HIP_TRY(d2h(&any, sc(SC_MAXTOK), 8));
+            HIP_TRY(read_at_sync(&any, sc(SC_MAXTOK), 8));
             HIP_TRY(sync_reads());
             if (debug) fprintf(stderr, "[sufr_hip debug] doubling round %u: groups=%u records=%u%s\n", round, ng, m,
                                any ? " (run keys among them)" : "");
@@ -1321,7 +1325,7 @@ public:
                                d_lcp, R, Dpos, defer, keep, newhead);
             unsigned long long mk = 0, mg = 0;
             if ((rc = scan_u32(keep, m, keepoff))) return rc;
-            HIP_TRY(d2h(&mk, sc(SC_SCANTOTAL), 8));
+            HIP_TRY(read_at_sync(&mk, sc(SC_SCANTOTAL), 8));
             HIP_TRY(sync_reads());
             if (mk) {
                 // new group ordinals: exclusive scan of the heads (into `keep`'s place: keep is read before by the
@@ -1329,7 +1333,7 @@ public:
                 if ((rc = ensure(wloff, ((size_t)m + 2) * 4))) return rc;
                 ngoff = (uint32_t*)wloff.p;
                 if ((rc = scan_u32(newhead, m, ngoff))) return rc;
-                HIP_TRY(d2h(&mg, sc(SC_SCANTOTAL), 8));
+                HIP_TRY(read_at_sync(&mg, sc(SC_SCANTOTAL), 8));
                 HIP_TRY(sync_reads());
                 hipLaunchKernelGGL(k_dbl_compact, dim3((m + 255) / 256), dim3(256), 0, stream, (const uint32_t*)i1,
                                    (const uint32_t*)g1, (const uint32_t*)flag, (const uint32_t*)ordx, (const uint32_t*)first,
@@ -1365,7 +1369,7 @@ public:
         hipLaunchKernelGGL(k_mql_flags, dim3((s + 255) / 256), dim3(256), 0, stream, d_lcp, s, L, (uint32_t*)optA.p);
         if ((rc = scan_u32((const uint32_t*)optA.p, s, (uint32_t*)optB.p))) return rc;
         unsigned long long tot = 0;
-        HIP_TRY(d2h(&tot, sc(SC_SCANTOTAL), 8));
+        HIP_TRY(read_at_sync(&tot, sc(SC_SCANTOTAL), 8));
         HIP_TRY(sync_reads());
         const uint32_t M = (uint32_t)tot;
         if (debug) fprintf(stderr, "[sufr_hip debug] max_query_len=%u: %u of %u ranks in tie runs\n", L, M, s);
@@ -1381,7 +1385,7 @@ public:
                            (const uint32_t*)d_lcp, (const uint32_t*)optA.p, (const uint32_t*)optB.p, s, L,
                            (uint32_t*)idxA.p, (uint32_t*)optC.p, (uint32_t*)optD.p);
         if ((rc = scan_u32((const uint32_t*)optD.p, M, (uint32_t*)optE.p))) return rc;
-        HIP_TRY(d2h(&tot, sc(SC_SCANTOTAL), 8));
+        HIP_TRY(read_at_sync(&tot, sc(SC_SCANTOTAL), 8));
         HIP_TRY(sync_reads());
         const int pos_bits = ceil_log2_u64(n) < 1 ? 1 : ceil_log2_u64(n);
         const int run_bits = ceil_log2_u64(tot + 1) < 1 ? 1 : ceil_log2_u64(tot + 1);
@@ -1404,7 +1408,7 @@ public:
             if ((rc = group_sort_prepare((const uint32_t*)starts.p, (const uint32_t*)sizes.p, R, M, M /* not known yet */, gp)))
                 return rc;
             unsigned long long maxrun = 0;
-            HIP_TRY(d2h(&maxrun, sc(SC_MAXSIZE), 8));
+            HIP_TRY(read_at_sync(&maxrun, sc(SC_MAXSIZE), 8));
             HIP_TRY(sync_reads());
             if ((rc = group_sort_run(gp, kcur, icur, (const uint32_t*)optE.p, kalt, ialt, (const uint32_t*)starts.p,
                                      (const uint32_t*)sizes.p, R, M, (uint32_t)maxrun, pos_bits, lv[0], done)))
@@ -1467,7 +1471,7 @@ public:
             hipLaunchKernelGGL(k_mask_top_hist, dim3(tiles), dim3(256), 0, stream, d_text, n, (const uint16_t*)lut.p, ms,
                                (uint32_t*)optD.p);
             std::vector<uint32_t> tot(1024);
-            HIP_TRY(d2h(tot.data(), optD.p, 1024 * 4));
+            HIP_TRY(read_at_sync(tot.data(), optD.p, 1024 * 4));
             HIP_TRY(sync_reads());
             tot.resize((size_t)1 << (ms.mch * kp.b));
             uint64_t all = 0, cnt_shard = 0;
@@ -1481,10 +1485,7 @@ public:
         st.num_suffixes = s;
         if (num_suffixes_out) *num_suffixes_out = s;
         if (s == 0) { st.num_levels = 1; if (st_out) *st_out = st; return 0; }
-        if (s > cap || !d_sa || !d_lcp) {
-            set_error("output capacity " + std::to_string(cap) + " < num_suffixes " + std::to_string(s));
-            return SUFR_HIP_E_CAPACITY;
-        }
+        if ((rc = check_capacity(s, cap, d_sa, d_lcp))) return rc;
         const uint32_t m = (uint32_t)s;
         if ((rc = ensure(keyA, (size_t)m * 8))) return rc;
         if ((rc = ensure(keyB, (size_t)m * 8))) return rc;
@@ -1700,7 +1701,7 @@ public:
                                (const unsigned long long*)sc(SC_WTOTAL), 0u);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(d2h(two, sc(SC_NBIG), 24));                  // (the leaf kernels leave these three alone)
+        HIP_TRY(read_at_sync(two, sc(SC_NBIG), 24));                  // (the leaf kernels leave these three alone)
         HIP_TRY(sync_reads());
         nbig = (uint32_t)two[0];
         mbig = two[1];
@@ -1754,14 +1755,128 @@ public:
         return rc;
     }
 
+    // ---- the state of ONE plain-order build: lives on sort_build's stack and goes to its stages by reference.  A member is set
+    // by the stage named above it and read by the stages after it.  Four are touched again, each in one place: kp (cut to the
+    // digit by first_digit_map), d_sa / d_lcp (the caller's again once reinsert_listed has written them, in sort_build),
+    // mql_count (m0 in sort_build, the final count in reinsert_listed).
+    struct Build {
+        // check_call: the call
+        const void* d_in_caller = nullptr;                 // the caller's text as it was handed in
+        uint64_t n = 0, cap = 0;
+        uint32_t flags = 0, shard_index = 0, num_shards = 1;
+        bool is_dna = false, allow_amb = false, raw = false, softmask = false, masked = false;
+        uint32_t* caller_sa = nullptr; uint32_t* caller_lcp = nullptr;
+        uint64_t* num_suffixes_out = nullptr;
+        sufr_hip_stats* st_out = nullptr;
+        sufr_hip_stats st;                                 // filled stage by stage; handed out by done()
+        // open_text
+        uint8_t* d_text = nullptr;                         // the normalised text (Pipeline::text)
+        const void* d_in = nullptr;                        // what the text stage STARTS from: the caller's text, or its 16-byte aligned copy
+        // plan_text_chunks: workgroup w of the streaming kernels takes chunk w (tchunk positions), group w % G1
+        uint32_t ngrid = 0, G1 = 0;                        // (ngrid: the grid of k_normalize_bytehist)
+        uint64_t nwg_t = 0, tchunk = 0;
+        bool small_tiles = false;                          // 16384-position tiles of k_msd_part_text (256 threads), not 65536
+        // text_stage
+        bool dna_table = false;                            // the fixed 3-bit table {$ % A C G N T}; the packed stream is written
+        uint32_t nexc = 0;                                 // listed bytes outside the table (the build then runs on 'N' in their place)
+        unsigned long long hist[256];
+        std::vector<uint64_t> pwords;                      // which raw first digits occur: a bit each (DNA text pass), or
+        std::vector<uint32_t> pflags;                      // a flag each (first_digit_map: the presence pass, or fewer characters)
+        // code_table
+        KeyParams kp;
+        uint64_t eligible_total = 0;
+        // first_digit_map
+        bool packed_path = false, mql_fast = false;
+        int mql_charbits = 0, mbits = 0;                   // bits of the L characters of a capped key; of the first digit (D = mbits / kp.b)
+        DigitMap dm;
+        std::vector<uint32_t> present_vals;                // raw value of every dense first digit
+        uint32_t NB = 0;
+        const uint16_t* d_remap = nullptr;
+        // char_model
+        CharModel cc;
+        // count_and_shard: this shard's first digits, raw [raw_lo, raw_hi) = dense [bin_lo, bin_hi) (all of them, then the shard's), its suffixes
+        uint32_t raw_lo = 0, raw_hi = 0, bin_lo = 0, bin_hi = 0;
+        uint64_t s = 0;
+        // working_arrays: d_sa / d_lcp = the caller's, or the exception build's (exc_reinsert then writes the caller's)
+        uint32_t m0 = 0;
+        uint32_t* d_sa = nullptr; uint32_t* d_lcp = nullptr;
+        Rec* xr[2] = {nullptr, nullptr};                   // records ping-pong between the levels; the sorted ones end up in [1]
+        // msd_levels
+        uint32_t nwin = 0, wcnt_stride = 0, fixcap = 0;    // 128-position windows of the tie bitmaps, a row of their counts, the fix list
+        FinishOut fo;
+        // reinsert_listed (else: m0)
+        uint32_t mql_count = 0;                            // suffixes of the finished arrays
+    };
+    struct LeftOver { uint32_t groups = 0; uint64_t records = 0; uint32_t depth = 0; uint64_t maxbig = 0; };   // buckets whose members agree on every key character
+    // the chain of the left-over buckets when it runs on the helper pipeline: joined after the tie runs, before prefix doubling
+    // (before_doubling), and on every way out of sort_build
+    struct LeftChain { std::thread th; int rc = 0; sufr_hip_stats st = {}; ~LeftChain() { if (th.joinable()) th.join(); } };
+
+    int done(Build& B) { if (B.st_out) *B.st_out = B.st; return 0; }
+    int check_capacity(uint64_t s, uint64_t cap, const uint32_t* d_sa, const uint32_t* d_lcp)
+    {
+        if (s > cap || !d_sa || !d_lcp) {
+            set_error("output capacity " + std::to_string(cap) + " < num_suffixes " + std::to_string(s));
+            return SUFR_HIP_E_CAPACITY;
+        }
+        return 0;
+    }
+
     int sort_build(const void* d_in, uint64_t n, uint32_t flags, uint32_t shard_index,
                    uint32_t num_shards, uint32_t* d_sa, uint32_t* d_lcp, uint64_t cap,
                    uint64_t* num_suffixes_out, sufr_hip_stats* st_out)
     {
-        sufr_hip_stats st;
-        memset(&st, 0, sizeof st);
-        st.text_len = n;
-        pin_items.clear(); pin_used = 0; pub_items.clear(); copies_queued = false;   // (reads a failed build queued: their destinations are gone)
+        Build B;
+        LeftChain chain;                                       // (after B: joined before B goes)
+        int rc;
+        if ((rc = check_call(B, d_in, n, flags, shard_index, num_shards, d_sa, d_lcp, cap, num_suffixes_out, st_out))) return rc;
+        if (n == 0) return done(B);
+        if ((rc = open_text(B))) return rc;
+        if ((rc = plan_text_chunks(B))) return rc;
+        if ((rc = text_stage(B))) return rc;
+        if ((rc = code_table(B))) return rc;
+        if (B.eligible_total == 0) return done(B);
+        if (B.masked) {
+            if (num_suffixes_out) *num_suffixes_out = B.eligible_total;
+            return sort_masked(B.d_text, n, B.kp, B.eligible_total, shard_index, num_shards, d_sa, d_lcp, cap, num_suffixes_out, B.st, st_out);
+        }
+        if ((rc = first_digit_map(B))) return rc;
+        if ((rc = char_model(B))) return rc;
+        if ((rc = count_and_shard(B))) return rc;
+        if (B.s == 0) return empty_shard(B);
+        if ((rc = check_capacity(B.s, cap, d_sa, d_lcp))) return rc;
+        if ((rc = working_arrays(B))) return rc;
+        if ((rc = launch_partition(B))) return rc;
+        LeftOver left;
+        if ((rc = msd_levels(B, left))) return rc;
+        if ((rc = start_left_chain(B, left, chain))) return rc;
+        if ((rc = tie_level(B, chain))) return rc;
+        if ((rc = join_left_chain(B, chain))) return rc;
+        B.mql_count = B.m0;
+        if (B.mql_fast) {                                      // (before the listed bytes are dealt with: their pass compares under the cap)
+            hipLaunchKernelGGL(k_mql_cap, dim3((B.m0 / 4 + 256) / 256), dim3(256), 0, stream, B.d_lcp, B.m0, (uint32_t)opt_max_query_len);
+            HIP_TRY(hipGetLastError());
+        }
+        if (B.nexc) {
+            bool rebuilt = false;
+            rc = reinsert_listed(B, B.d_sa, B.d_lcp, B.m0, rebuilt);
+            if (rc || rebuilt) return rc;
+            B.d_sa = B.caller_sa; B.d_lcp = B.caller_lcp;
+        }
+        if (!B.mql_fast && opt_max_query_len > 0 && (rc = apply_max_query_len(opt_max_query_len, n, B.d_sa, B.d_lcp, B.mql_count))) return rc;
+        HIP_TRY(hipEventRecord(ev[8], stream));
+        HIP_TRY(sync_reads());
+        HIP_TRY(hipGetLastError());
+        return finish_stats(B);
+    }
+
+    int check_call(Build& B, const void* d_in, uint64_t n, uint32_t flags, uint32_t shard_index, uint32_t num_shards,
+                   uint32_t* d_sa, uint32_t* d_lcp, uint64_t cap, uint64_t* num_suffixes_out, sufr_hip_stats* st_out)
+    {
+        memset(&B.st, 0, sizeof B.st);
+        B.st.text_len = n;
+        B.st_out = st_out;
+        reset_reads();                                     // (reads a failed build queued: their destinations are gone)
         if (num_suffixes_out) *num_suffixes_out = 0;
         if (num_shards == 0 || shard_index >= num_shards) { set_error("bad shard index"); return SUFR_HIP_E_INVALID; }
         // 32-bit record indices with tile-sized strides: keep a margin below 2^32 so that no loop counter wraps
@@ -1770,43 +1885,54 @@ public:
             return SUFR_HIP_E_UNSUPPORTED;
         }
         read_env();
-        const bool masked = !opt_mask_offsets.empty();
+        B.masked = !opt_mask_offsets.empty();
         // Shards of the other two orders (find_lcp's other arms, 272-314: "a bounded key, then descending position"): a seed-mask
         // build is split on its own first key digit (sort_masked); a --max-query-len build on the first digit of the plain
         // order, which ties no two suffixes across a shard as long as the cap is at least a digit long (<= 7 symbols)
-        if (num_shards > 1 && !masked && opt_max_query_len > 0 && opt_max_query_len < SHARD_MIN_MQL) {
+        if (num_shards > 1 && !B.masked && opt_max_query_len > 0 && opt_max_query_len < SHARD_MIN_MQL) {
             set_error("a max_query_len below " + std::to_string(SHARD_MIN_MQL) + " ties suffixes across first-digit shards: build it on one GPU");
             return SUFR_HIP_E_UNSUPPORTED;
         }
         stitch_weight = 0;
-        stitch_cap = (!masked && opt_max_query_len > 0) ? opt_max_query_len : 0;
-        if (n == 0) { if (st_out) *st_out = st; return 0; }
-        if (!d_in) { set_error("null text"); return SUFR_HIP_E_INVALID; }
+        stitch_cap = (!B.masked && opt_max_query_len > 0) ? opt_max_query_len : 0;
+        B.d_in_caller = d_in; B.n = n; B.flags = flags; B.shard_index = shard_index; B.num_shards = num_shards;
+        B.caller_sa = d_sa; B.caller_lcp = d_lcp; B.cap = cap; B.num_suffixes_out = num_suffixes_out;
+        B.is_dna = flags & SUFR_HIP_FLAG_DNA; B.allow_amb = flags & SUFR_HIP_FLAG_ALLOW_AMBIGUITY;
+        B.raw = flags & SUFR_HIP_FLAG_RAW_TEXT; B.softmask = flags & SUFR_HIP_FLAG_IGNORE_SOFTMASK;
+        return 0;
+    }
+
+    // the workspace of every build, and the text where vector loads can read it
+    int open_text(Build& B)
+    {
+        const uint64_t n = B.n;
+        if (!B.d_in_caller) { set_error("null text"); return SUFR_HIP_E_INVALID; }
         HIP_TRY(hipSetDevice(device));
         int rc;
-        const bool is_dna = flags & SUFR_HIP_FLAG_DNA;
-        const bool allow_amb = flags & SUFR_HIP_FLAG_ALLOW_AMBIGUITY;
-        const bool raw = flags & SUFR_HIP_FLAG_RAW_TEXT;
-        const bool softmask = flags & SUFR_HIP_FLAG_IGNORE_SOFTMASK;
-
         resident_text_len = 0;
         if ((rc = ensure(text, n + TEXT_PAD))) return rc;
         resident_text_len = n;                             // (`text` takes the normalised text of THIS call from here on)
         if ((rc = ensure(bytehist, 256 * 8))) return rc;
         if ((rc = ensure(lut, 512))) return rc;
         if ((rc = ensure(scalars, SC_N * 8))) return rc;
-        uint8_t* d_text = (uint8_t*)text.p;
+        uint8_t* d_text = B.d_text = (uint8_t*)text.p;
 
         HIP_TRY(hipEventRecord(ev[0], stream));
-        const void* const d_in_orig = d_in;
-        if ((uintptr_t)d_in & 15u) {   // vector loads need a 16-byte aligned source: stage it first
-            HIP_TRY(hipMemcpyAsync(d_text, d_in, n, hipMemcpyDeviceToDevice, stream));
-            d_in = d_text;
+        B.d_in = B.d_in_caller;
+        if ((uintptr_t)B.d_in & 15u) {   // vector loads need a 16-byte aligned source: stage it first
+            HIP_TRY(hipMemcpyAsync(d_text, B.d_in, n, hipMemcpyDeviceToDevice, stream));
+            B.d_in = d_text;
         }
-        zlist.n = 0;
         HIP_TRY(zero_later(d_text + n, TEXT_PAD));
         HIP_TRY(zero_later(bytehist.p, 256 * 8));
-        uint32_t ngrid;
+        return 0;
+    }
+
+    // ---- text chunking for the streaming kernels: workgroup w takes chunk w, group w % G.  The one place that knows the tile units.
+    int plan_text_chunks(Build& B)
+    {
+        const uint64_t n = B.n;
+        int rc;
         {
             uint64_t nvec = n / 16;
             uint32_t grid = (uint32_t)((nvec + 255) / 256);
@@ -1817,9 +1943,8 @@ public:
             if ((rc = ensure(runends, (size_t)rtiles0 * 64 * 8))) return rc;
             if ((rc = ensure(tileany, (size_t)rtiles0 * 8))) return rc;
             if (grid > rtiles0) grid = rtiles0;
-            ngrid = grid;
+            B.ngrid = grid;
         }
-        // ---- text chunking for the streaming kernels: workgroup w takes chunk w, group w % G -------------
         const uint64_t ttiles = (n + TILE - 1) / TILE;
         uint64_t nwg_t = ttiles < text_wgs ? ttiles : text_wgs;
         uint64_t tiles_per = (ttiles + nwg_t - 1) / nwg_t;
@@ -1842,27 +1967,39 @@ public:
             }
             tiles_per = best_per * tile_unit;
         }
-        const uint64_t tchunk = tiles_per * TILE;
-        nwg_t = (n + tchunk - 1) / tchunk;
-        st.partition_workgroups = (uint32_t)nwg_t;
-        const uint32_t G1 = msd_groups;
-        if ((rc = ensure(startbuf, (size_t)ttiles * 64 * 8 + 64))) return rc;     // suffix-start bitmap, whole tiles
-        // DNA builds first try the fixed 3-bit code table {$ % A C G N T}: ONE pass over the text (k_text_pass_dna)
-        // then writes the normalised text, the bit-packed code stream and the run-end tables, counts those
-        // symbols, the first digit of every suffix start and the 5-mers that occur; any other byte falls back to
-        // the general path (the text is normalised by then, and normalising is idempotent)
-        static const uint8_t dna_bytes[8] = {0, '$', '%', 'A', 'C', 'G', 'N', 'T'};
-        bool dna_table = false;
-        uint32_t nexc = 0;                                     // listed bytes outside the table (the build then runs on 'N' in their place)
-        const void* const d_in_caller = d_in_orig;
-        unsigned long long hist[256];
-        std::vector<uint32_t> pflags;                          // which raw digit values occur in the text: one flag each, or
-        std::vector<uint64_t> pwords;                          // (DNA text pass) one bit each
-        if (is_dna && !masked && !no_dna_table && !exc_disable) {
-            const uint64_t ptiles = (n + TILE - 1) / TILE;
-            const size_t pbytes = (size_t)ptiles * (TILE * 3 / 8);
-            const size_t ptail = (size_t)16 * TILE * 3 / 8 + 64;      // the partition kernel's tiles (65536 positions) read past the last 4 KB tile
-            if ((rc = ensure(packedbuf, pbytes + ptail))) return rc;
+        B.small_tiles = small_tiles;
+        B.tchunk = tiles_per * TILE;
+        B.nwg_t = (n + B.tchunk - 1) / B.tchunk;
+        B.st.partition_workgroups = (uint32_t)B.nwg_t;
+        B.G1 = msd_groups;
+        return ensure(startbuf, (size_t)ttiles * 64 * 8 + 64);     // suffix-start bitmap, whole tiles
+    }
+
+    // the bit-packed stream of b-bit codes: whole 4 KB tiles, then a tail (cleared by the caller) for the partition kernel's
+    // tiles of 65536 positions, which read past the last of them
+    int ensure_packed(uint64_t n, int b, size_t& pbytes, size_t& ptail)
+    {
+        pbytes = (size_t)((n + TILE - 1) / TILE) * (TILE * b / 8);
+        ptail = (size_t)16 * TILE * b / 8 + 64;
+        return ensure(packedbuf, pbytes + ptail);
+    }
+
+    // ---- the normalised text, its byte counts and run-end tables.  DNA builds first try the fixed 3-bit code table
+    // {$ % A C G N T}: ONE pass over the text (k_text_pass_dna) then writes the normalised text, the bit-packed code stream
+    // and the run-end tables, counts those symbols, the first digit of every suffix start and the 5-mers that occur; any
+    // other byte falls back to the general path (the text is normalised by then, and normalising is idempotent)
+    static const uint8_t* dna_table_bytes() { static const uint8_t t[8] = {0, '$', '%', 'A', 'C', 'G', 'N', 'T'}; return t; }
+    int text_stage(Build& B)
+    {
+        const uint8_t* const dna_bytes = dna_table_bytes();
+        const uint64_t n = B.n, nwg_t = B.nwg_t, tchunk = B.tchunk;
+        const uint32_t G1 = B.G1, num_shards = B.num_shards;
+        const bool raw = B.raw, softmask = B.softmask;
+        uint8_t* const d_text = B.d_text; const void* d_in = B.d_in; unsigned long long* const hist = B.hist;
+        int rc;
+        if (B.is_dna && !B.masked && !no_dna_table && !exc_disable) {
+            size_t pbytes, ptail;
+            if ((rc = ensure_packed(n, 3, pbytes, ptail))) return rc;
             if ((rc = ensure(rawtab, (size_t)G1 * TP_RAW_BINS * 4))) return rc;
             if ((rc = ensure(presbuf, (size_t)TP_RAW_BINS / 8))) return rc;
             if ((rc = ensure(rawtot, (size_t)TP_RAW_BINS * 4))) return rc;
@@ -1872,7 +2009,7 @@ public:
             HIP_TRY(zero_later(rawtab.p, (size_t)G1 * TP_RAW_BINS * 4));
             HIP_TRY(zero_later(presbuf.p, (size_t)TP_RAW_BINS / 8));
             HIP_TRY(zero_flush());                          // (with the text pad and the byte counts: one launch)
-            const uint32_t fixed_elig = allow_amb ? 0xFEu : ((1u << 1) | (1u << 3) | (1u << 4) | (1u << 5) | (1u << 7));
+            const uint32_t fixed_elig = B.allow_amb ? 0xFEu : ((1u << 1) | (1u << 3) | (1u << 4) | (1u << 5) | (1u << 7));
             HIP_TRY(hipFuncSetAttribute((const void*)k_text_pass_dna, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TP_LDS));
             // one resident workgroup per CU (its 128 KB of LDS counters allow no second), each over every tp_grid-th chunk; a
             // multiple of the groups, so that a workgroup's chunks all count into one group's row
@@ -1893,24 +2030,24 @@ public:
             unsigned long long cnt9[10];                       // [1..7] the table's symbols, [9] bytes outside it
             unsigned long long occurs[TP_RAW_BINS / 64];
             rawtot_host.clear();
-            HIP_TRY(d2h(cnt9, bytehist.p, sizeof cnt9));
-            HIP_TRY(d2h(occurs, flagsbuf.p, sizeof occurs));
+            HIP_TRY(read_at_sync(cnt9, bytehist.p, sizeof cnt9));
+            HIP_TRY(read_at_sync(occurs, flagsbuf.p, sizeof occurs));
             if (num_shards > 1) {                          // (a single shard needs no counts: it holds every eligible suffix)
                 rawtot_host.resize(TP_RAW_BINS);
-                HIP_TRY(d2h(rawtot_host.data(), rawtot.p, (size_t)TP_RAW_BINS * 4));
+                HIP_TRY(read_at_sync(rawtot_host.data(), rawtot.p, (size_t)TP_RAW_BINS * 4));
             }
             HIP_TRY(sync_reads());
-            pwords.assign(occurs, occurs + TP_RAW_BINS / 64);    // (the digit map is built from the words: 5 us of host time, not 67)
+            B.pwords.assign(occurs, occurs + TP_RAW_BINS / 64);    // (the digit map is built from the words: 5 us of host time, not 67)
             // Bytes outside the table (sufr_exc.inc): the text pass has written 'N' for them and listed them.  A handful -- the IUPAC
             // codes of a real assembly, a '#' between sequences -- stay on this path: the build runs on that text and
             // exc_reinsert re-places the suffixes that looked at them (a sharded build: also into the shard their true first
             // digit says).  A text with more of them than the list holds does not.
             const unsigned long long foreign = cnt9[9];
             if (foreign == 0 || (foreign <= EXC_MAX_LIST && foreign * 64 <= n && !no_exceptions)) {
-                dna_table = true;
-                nexc = (uint32_t)foreign;
-                exc_pending = nexc; st.num_exceptions = nexc;
-                memset(hist, 0, sizeof hist);
+                B.dna_table = true;
+                B.nexc = (uint32_t)foreign;
+                exc_pending = B.nexc; B.st.num_exceptions = B.nexc;
+                memset(hist, 0, sizeof B.hist);
                 for (int c = 1; c < 8; c++) hist[dna_bytes[c]] = cnt9[c];
             } else {
                 HIP_TRY(hipMemsetAsync(bytehist.p, 0, 256 * 8, stream));
@@ -1919,17 +2056,17 @@ public:
                                        (const uint32_t*)exc_pos.p, (const uint8_t*)exc_byte.p, (uint32_t)foreign);
                     d_in = d_text;                             // already normalised
                 } else {                                       // the list is cut short: from the caller's text again
-                    d_in = d_in_caller;
+                    d_in = B.d_in_caller;
                     if ((uintptr_t)d_in & 15u) { HIP_TRY(hipMemcpyAsync(d_text, d_in, n, hipMemcpyDeviceToDevice, stream)); d_in = d_text; }
                 }
             }
         }
         HIP_TRY(zero_flush());                              // (builds that did not take the DNA text pass)
-        if (!dna_table) {
-            hipLaunchKernelGGL(k_normalize_bytehist, dim3(ngrid), dim3(256), 0, stream, (const uint8_t*)d_in,
+        if (!B.dna_table) {
+            hipLaunchKernelGGL(k_normalize_bytehist, dim3(B.ngrid), dim3(256), 0, stream, (const uint8_t*)d_in,
                                d_text, n, raw ? 1 : 0, softmask ? 1 : 0, (unsigned long long*)bytehist.p,
                                (uint32_t*)tilefirst.p, (uint64_t*)runends.p, (uint64_t*)tileany.p);
-            HIP_TRY(d2h(hist, bytehist.p, sizeof hist));
+            HIP_TRY(read_at_sync(hist, bytehist.p, sizeof B.hist));
             HIP_TRY(sync_reads());
         }
         rtab.ends = (const uint64_t*)runends.p;            // run-end tables of the normalised text
@@ -1954,32 +2091,30 @@ public:
             rtab.next_tile = (const uint32_t*)nexttile.p;
         }
         HIP_TRY(hipEventRecord(ev[1], stream));
+        return 0;
+    }
 
-        // ---- alphabet -> dense codes (integer order of codes == raw byte order) ----------------------
+    // ---- alphabet -> dense codes (integer order of codes == raw byte order) ----------------------
+    int code_table(Build& B)
+    {
+        const unsigned long long* const hist = B.hist;
+        const uint8_t* const dna_bytes = dna_table_bytes();
+        KeyParams& kp = B.kp;
         uint32_t sigma = 0;
-        uint64_t eligible_total = 0;
-        double ent = 0.0;
         for (int c = 0; c < 256; c++) {
             h_lut[c] = 0;
             if (!hist[c]) continue;
             sigma++;
             // eligibility predicate, sufr_builder.rs:446-449
-            bool el = c == '$' || !is_dna || c == 'A' || c == 'C' || c == 'G' || c == 'T' || allow_amb;
+            bool el = c == '$' || !B.is_dna || c == 'A' || c == 'C' || c == 'G' || c == 'T' || B.allow_amb;
             uint32_t code = sigma;                         // dense rank among the bytes present
-            if (dna_table) for (uint32_t k = 1; k < 8; k++) if (dna_bytes[k] == c) code = k;   // fixed table
+            if (B.dna_table) for (uint32_t k = 1; k < 8; k++) if (dna_bytes[k] == c) code = k;   // fixed table
             h_lut[c] = (uint16_t)(code | (el ? 0x8000u : 0u));
-            if (el) eligible_total += hist[c];
+            if (el) B.eligible_total += hist[c];
         }
-        for (int c = 0; c < 256; c++)
-            if (hist[c] && (h_lut[c] & 0x8000u)) {
-                double p = (double)hist[c] / (double)(eligible_total ? eligible_total : 1);
-                ent -= p * log2(p);
-            }
-        if (ent < 0.25) ent = 0.25;
-        KeyParams kp;
         kp.b = 1; while ((1u << kp.b) <= sigma) kp.b++;          // codes 0..sigma need b bits
-        if (dna_table) kp.b = 3;                                 // the packed stream is already written
-        leaf_dna3 = dna_table;
+        if (B.dna_table) kp.b = 3;                               // the packed stream is already written
+        leaf_dna3 = B.dna_table;
         kp.K = 64 / kp.b;
         if (key_chars_knob > 0 && key_chars_knob < kp.K && key_chars_knob * kp.b >= 32 && packed_ok_for_knob(kp.b))
             kp.K = key_chars_knob;                               // probes: what a shorter key costs (DESIGN.md section 4)
@@ -1994,20 +2129,22 @@ public:
                 if (h_lut[c] & 0x8000u) kp.elig_codes |= 1u << (h_lut[c] & 0x7fu);
         kp.detect_period = detect_period ? 1 : 0;
         kp.packed = nullptr;
-        st.alphabet_size = sigma; st.bits_per_char = kp.b; st.chars_per_key = kp.K;
+        B.st.alphabet_size = sigma; B.st.bits_per_char = kp.b; B.st.chars_per_key = kp.K;
         HIP_TRY(hipMemcpyAsync(lut.p, h_lut, sizeof h_lut, hipMemcpyHostToDevice, stream));   // (h_lut is a member)
+        return 0;
+    }
 
-        if (eligible_total == 0) { if (st_out) *st_out = st; return 0; }
-        if (masked) {
-            if (num_suffixes_out) *num_suffixes_out = eligible_total;
-            return sort_masked(d_text, n, kp, eligible_total, shard_index, num_shards, d_sa, d_lcp, cap, num_suffixes_out, st, st_out);
-        }
-
-        // ---- MSD digits: D characters each, as many as 15 bits hold when the bit-packed stream exists -----
-        // (DNA: 5 characters, ~1400-1800 of the 32768 nominal values occur), else the 12-bit digits of the
-        // text-staging kernels.  The presence pass gives the set of D-mers of the text; the dense digit map
-        // numbers them in order.
-        const bool packed_path = kp.b >= 2 && kp.b <= 4;
+    // ---- MSD digits: D characters each, as many as 15 bits hold when the bit-packed stream exists -----
+    // (DNA: 5 characters, ~1400-1800 of the 32768 nominal values occur), else the 12-bit digits of the
+    // text-staging kernels.  The presence pass gives the set of D-mers of the text; the dense digit map
+    // numbers them in order.
+    int first_digit_map(Build& B)
+    {
+        const uint64_t n = B.n;
+        const bool dna_table = B.dna_table;
+        KeyParams& kp = B.kp; std::vector<uint32_t>& pflags = B.pflags; std::vector<uint64_t>& pwords = B.pwords;
+        int rc;
+        const bool packed_path = B.packed_path = kp.b >= 2 && kp.b <= 4;
         // --max-query-len L with 32 <= L b <= K b (DNA: 11 <= L <= 21; the reference authors' `-m 12`, `-m 16`): the capped
         // build never looks beyond L characters.  Keys keep L characters; the bits below them carry the top of ~position
         // (k_msd_part_text<.., POS>), so equal L-prefixes come out of the MSD levels and the leaf sort in descending position;
@@ -2015,39 +2152,33 @@ public:
         // apply_max_query_len over the finished arrays.  Rounds 1-5 built the exact arrays first: `elegans -m 12` 9.6 ms
         // against 4.4 ms without the cap.  Other caps (and 5-bit alphabets) keep that form.  Listed bytes outside the DNA table
         // go with it: the suffixes whose first L symbols hold one are re-placed under the capped order (sufr_exc.inc).
-        const bool mql_fast = mql_fast_ok && opt_max_query_len > 0 && kp.b == 3 && packed_path &&
-                              opt_max_query_len <= (uint64_t)kp.K && opt_max_query_len * (uint64_t)kp.b >= 32;
-        const int mql_charbits = mql_fast ? (int)opt_max_query_len * kp.b : 0;
-        if (mql_fast) { kp.K = (int)opt_max_query_len; kp.detect_period = 0; st.chars_per_key = (uint32_t)kp.K; }
+        const bool mql_fast = B.mql_fast = mql_fast_ok && opt_max_query_len > 0 && kp.b == 3 && packed_path &&
+                                           opt_max_query_len <= (uint64_t)kp.K && opt_max_query_len * (uint64_t)kp.b >= 32;
+        B.mql_charbits = mql_fast ? (int)opt_max_query_len * kp.b : 0;
+        if (mql_fast) { kp.K = (int)opt_max_query_len; kp.detect_period = 0; B.st.chars_per_key = (uint32_t)kp.K; }
         int D = packed_path ? 15 / kp.b : kp.dchars;
         int mbits = D * kp.b;
         KeyParams kq = kp;                                 // the presence pass flags digits of mbits bits
         kq.dchars = D; kq.dbits = mbits; kq.raw_bins = 1u << mbits; kq.nbins = kq.raw_bins; kq.top_shift = 64 - mbits;
         if (!dna_table) pflags.assign(kq.raw_bins, 1u);
-        const bool want_presence = kq.raw_bins > 256;
+        const bool want_presence = kq.raw_bins > 256;      // (packed alphabets have 12- to 15-bit digits: always)
         if (packed_path && !dna_table) {
-            const uint64_t ptiles = (n + TILE - 1) / TILE;
-            const size_t pbytes = (size_t)ptiles * (TILE * kp.b / 8);
-            const size_t ptail = (size_t)16 * TILE * kp.b / 8 + 64;   // 65536-position tiles read past the last 4 KB tile
-            if ((rc = ensure(packedbuf, pbytes + ptail))) return rc;
+            size_t pbytes, ptail;
+            if ((rc = ensure_packed(n, kp.b, pbytes, ptail))) return rc;
             HIP_TRY(hipMemsetAsync((uint8_t*)packedbuf.p + pbytes, 0, ptail, stream));
         }
         if (want_presence) {
-            if (!dna_table) {                              // (the DNA text pass has left the flags in pflags)
+            if (!dna_table) {                              // (the DNA text pass has left the flags in pwords)
                 if ((rc = ensure(flagsbuf, (size_t)kq.raw_bins * 4))) return rc;
                 HIP_TRY(hipMemsetAsync(flagsbuf.p, 0, (size_t)kq.raw_bins * 4, stream));
-                if ((rc = launch_presence((uint32_t)nwg_t, (size_t)kq.raw_bins + TILE + HALO + 512, d_text, n, kq,
-                                          tchunk, (uint32_t*)flagsbuf.p,
+                if ((rc = launch_presence((uint32_t)B.nwg_t, (size_t)kq.raw_bins + TILE + HALO + 512, B.d_text, n, kq,
+                                          B.tchunk, (uint32_t*)flagsbuf.p,
                                           packed_path ? (uint8_t*)packedbuf.p : (uint8_t*)nullptr)))
                     return rc;
-                HIP_TRY(d2h(pflags.data(), flagsbuf.p, (size_t)kq.raw_bins * 4));
+                HIP_TRY(read_at_sync(pflags.data(), flagsbuf.p, (size_t)kq.raw_bins * 4));
                 HIP_TRY(sync_reads());
             }
             if (dna_table) pwords[0] |= 1ull; else pflags[0] = 1;     // digits entirely past the end of the text
-        } else if (packed_path && !dna_table) {
-            // (cannot happen: packed alphabets have 12- to 15-bit digits) -- keep the stream consistent anyway
-            set_error("internal error: packed path without presence pass");
-            return SUFR_HIP_E_HIP;
         }
         if (packed_path) kp.packed = (const uint8_t*)packedbuf.p;
         // fewer characters per digit while more than MSD_MAX_BINS values occur
@@ -2070,15 +2201,14 @@ public:
             for (uint32_t v = 0; v < pflags.size(); v++) if (pflags[v]) f2[v >> kp.b] = 1u;
             pflags.swap(f2);
         }
-        DigitMap dm;
-        std::vector<uint32_t> present_vals;
-        if ((rc = from_words ? upload_digit_map_words(pwords, mbits, dmapbuf, dmaphost, dm, present_vals)
-                             : upload_digit_map(pflags, mbits, dmapbuf, dmaphost, dm, &present_vals))) return rc;
+        DigitMap& dm = B.dm;
+        if ((rc = from_words ? upload_digit_map_words(pwords, mbits, dmapbuf, dmaphost, dm, B.present_vals)
+                             : upload_digit_map(pflags, mbits, dmapbuf, dmaphost, dm, &B.present_vals))) return rc;
         if (dm.nbins > MSD_MAX_BINS) { set_error("alphabet too large for the radix digit counters"); return SUFR_HIP_E_UNSUPPORTED; }
-        const uint32_t NB = dm.nbins;
-        st.digit_bits = (uint32_t)mbits;
+        const uint32_t NB = B.NB = dm.nbins;
+        B.mbits = mbits;
+        B.st.digit_bits = (uint32_t)mbits;
         // the text-staging kernels (alphabets of more than 15 symbols) take the same digits through a flat table
-        const uint16_t* d_remap = nullptr;
         if (!packed_path) {
             kp.dchars = D; kp.dbits = mbits; kp.raw_bins = 1u << mbits; kp.top_shift = 64 - mbits; kp.nbins = (NB + 3u) & ~3u;
             if (want_presence) {
@@ -2087,69 +2217,81 @@ public:
                 for (uint32_t v = 0; v < kp.raw_bins; v++) { remaphost[v] = (uint16_t)dense; if (pflags[v]) dense++; }
                 if ((rc = ensure(remapbuf, (size_t)kp.raw_bins * 2))) return rc;
                 HIP_TRY(hipMemcpyAsync(remapbuf.p, remaphost.data(), (size_t)kp.raw_bins * 2, hipMemcpyHostToDevice, stream));
-                d_remap = (const uint16_t*)remapbuf.p;
+                B.d_remap = (const uint16_t*)remapbuf.p;
             } else {
                 kp.nbins = kp.raw_bins;
             }
         }
+        return 0;
+    }
 
-        // ---- sorted depth: enough characters that groups are small (the finisher ranks inside groups) ----
-        int C;                                             // characters sorted before the finisher
-        {
-            const uint64_t s_guess = eligible_total / num_shards;
-            double need = log2((double)(s_guess > 1 ? s_guess : 2)) - 3.0;
-            C = (int)ceil(need / ent);
-            const int q = 12 / kp.b > 0 ? 12 / kp.b : 1;   // in steps of the former 12-bit digit (4 bases)
-            C = (C + q - 1) / q * q;
-            if (C < q) C = q;
-            if (C > kp.K) C = kp.K;
+    // character model of the leaf sort's counting digit: share of the suffix starts below every code
+    // (codes that occur but start no suffix -- 'N', '%' -- get a sliver)
+    int char_model(Build& B)
+    {
+        const unsigned long long* const hist = B.hist; const KeyParams& kp = B.kp; CharModel& cc = B.cc;
+        int rc;
+        double wsum = 0.0;
+        double wt[257];
+        const uint32_t ncodes = 1u << kp.b;
+        for (uint32_t v = 0; v <= 256; v++) wt[v] = 0.0;
+        for (int c = 0; c < 256; c++)
+            if (hist[c]) { const double x = (h_lut[c] & 0x8000u) ? (double)hist[c] : 0.0; wt[h_lut[c] & 0xffu] += x; wsum += x; }
+        const double floor_w = wsum / 4096.0;
+        double tot = 0.0;
+        for (int c = 0; c < 256; c++)
+            if (hist[c] && wt[h_lut[c] & 0xffu] < floor_w) wt[h_lut[c] & 0xffu] = floor_w;
+        for (uint32_t v = 0; v < ncodes; v++) tot += wt[v];
+        cumhost.assign(ncodes + 1, 0u);
+        double before = 0.0, ent2 = 0.0;
+        for (uint32_t v = 0; v < ncodes; v++) {
+            double f = before / (tot > 0 ? tot : 1.0) * 4294967296.0;
+            cumhost[v] = f >= 4294967295.0 ? 0xffffffffu : (uint32_t)f;
+            if (wt[v] > 0) { const double p = wt[v] / tot; ent2 -= p * log2(p); }
+            before += wt[v];
         }
-        (void)C;
-        // character model of the leaf sort's counting digit: share of the suffix starts below every code
-        // (codes that occur but start no suffix -- 'N', '%' -- get a sliver)
-        CharModel cc;
-        {
-            double wsum = 0.0;
-            double wt[257];
-            const uint32_t ncodes = 1u << kp.b;
-            for (uint32_t v = 0; v <= 256; v++) wt[v] = 0.0;
-            for (int c = 0; c < 256; c++)
-                if (hist[c]) { const double x = (h_lut[c] & 0x8000u) ? (double)hist[c] : 0.0; wt[h_lut[c] & 0xffu] += x; wsum += x; }
-            const double floor_w = wsum / 4096.0;
-            double tot = 0.0;
-            for (int c = 0; c < 256; c++)
-                if (hist[c] && wt[h_lut[c] & 0xffu] < floor_w) wt[h_lut[c] & 0xffu] = floor_w;
-            for (uint32_t v = 0; v < ncodes; v++) tot += wt[v];
-            cumhost.assign(ncodes + 1, 0u);
-            double before = 0.0, ent2 = 0.0;
-            for (uint32_t v = 0; v < ncodes; v++) {
-                double f = before / (tot > 0 ? tot : 1.0) * 4294967296.0;
-                cumhost[v] = f >= 4294967295.0 ? 0xffffffffu : (uint32_t)f;
-                if (wt[v] > 0) { const double p = wt[v] / tot; ent2 -= p * log2(p); }
-                before += wt[v];
-            }
-            cumhost[ncodes] = 0xffffffffu;
-            if ((rc = ensure(cumbuf, (size_t)(ncodes + 1) * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(cumbuf.p, cumhost.data(), (size_t)(ncodes + 1) * 4, hipMemcpyHostToDevice, stream));
-            cc.cum = (const uint32_t*)cumbuf.p;
-            cc.b = kp.b;
-            cc.lastbit = mql_fast ? 0 : 64 - kp.K * kp.b;       // (a capped build sorts the position bits below the characters too)
-            if (ent2 < 0.25) ent2 = 0.25;
-            cc.mchars = (int)ceil(13.0 / ent2) + 1;        // ~12 bits of bucket number
-            if (cc.mchars > 16) cc.mchars = 16;
-        }
-        // ---- level 1: histogram + THE radix-partition kernel over the text ---------------------------
-        uint32_t raw_lo = 0, raw_hi = 1u << mbits;         // raw first-digit range of this shard
-        uint32_t bin_lo = 0, bin_hi = NB;
+        cumhost[ncodes] = 0xffffffffu;
+        if ((rc = ensure(cumbuf, (size_t)(ncodes + 1) * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(cumbuf.p, cumhost.data(), (size_t)(ncodes + 1) * 4, hipMemcpyHostToDevice, stream));
+        cc.cum = (const uint32_t*)cumbuf.p;
+        cc.b = kp.b;
+        cc.lastbit = B.mql_fast ? 0 : 64 - kp.K * kp.b;     // (a capped build sorts the position bits below the characters too)
+        if (ent2 < 0.25) ent2 = 0.25;
+        cc.mchars = (int)ceil(13.0 / ent2) + 1;        // ~12 bits of bucket number
+        if (cc.mchars > 16) cc.mchars = 16;
+        return 0;
+    }
+
+    // the raw first digits of the dense range [bin_lo, bin_hi): from the value of its first digit up to that of the first one
+    // behind it (none behind it: no upper bound; the first shard: no lower bound)
+    static void shard_raw_range(Build& B)
+    {
+        B.raw_lo = B.bin_lo < B.NB ? B.present_vals[B.bin_lo] : (1u << B.mbits);
+        B.raw_hi = B.bin_hi < B.NB ? B.present_vals[B.bin_hi] : (1u << B.mbits);
+        if (B.bin_lo == 0) B.raw_lo = 0;
+    }
+
+    // ---- level 1: the first-digit histogram, this shard's range of digits and its suffixes, the write cursors ----------
+    int count_and_shard(Build& B)
+    {
+        const uint64_t n = B.n, nwg_t = B.nwg_t, tchunk = B.tchunk;
+        const uint32_t G1 = B.G1, NB = B.NB, num_shards = B.num_shards, shard_index = B.shard_index;
+        const int mbits = B.mbits;
+        const KeyParams& kp = B.kp; const DigitMap& dm = B.dm; const std::vector<uint32_t>& present_vals = B.present_vals;
+        const uint16_t* const d_remap = B.d_remap;
+        uint32_t& bin_lo = B.bin_lo; uint32_t& bin_hi = B.bin_hi;
+        int rc;
+        B.raw_lo = 0; B.raw_hi = 1u << mbits;              // raw first-digit range of this shard
+        bin_lo = 0; bin_hi = NB;
         if ((rc = ensure(leafbase, ((size_t)NB + 1) * 4))) return rc;
         HIP_TRY(hipEventRecord(ev[2], stream));
         uint64_t s_host = 0;                               // suffixes of this shard, when the host can tell
         bool s_known = false;
-        if (packed_path) {
+        if (B.packed_path) {
             if ((rc = ensure(grouptab, (size_t)G1 * NB * 4))) return rc;
             if ((rc = ensure(gcur, (size_t)G1 * NB * 4))) return rc;
             std::vector<uint32_t> tot;                     // suffix starts per dense first digit (all groups)
-            if (dna_table) {
+            if (B.dna_table) {
                 // the text pass has counted raw 5-character digits; a digit of fewer characters (more than
                 // MSD_MAX_BINS 5-mers occur) sums the raw values it is a prefix of
                 const int fold = 15 - mbits;
@@ -2166,7 +2308,7 @@ public:
                         tot[d] = (uint32_t)t;
                     }
                 } else {
-                    s_host = eligible_total; s_known = true;  // every eligible position starts a suffix of the one shard
+                    s_host = B.eligible_total; s_known = true;  // every eligible position starts a suffix of the one shard
                 }
             } else {
                 HIP_TRY(hipMemsetAsync(grouptab.p, 0, (size_t)G1 * NB * 4, stream));
@@ -2177,7 +2319,7 @@ public:
 #undef SUFR_HIST_TEXT
                 if (num_shards > 1) {
                     std::vector<uint32_t> gt((size_t)G1 * NB);
-                    HIP_TRY(d2h(gt.data(), grouptab.p, gt.size() * 4));
+                    HIP_TRY(read_at_sync(gt.data(), grouptab.p, gt.size() * 4));
                     HIP_TRY(sync_reads());
                     tot.assign(NB, 0u);
                     for (uint32_t g = 0; g < G1; g++) for (uint32_t d = 0; d < NB; d++) tot[d] += gt[(size_t)g * NB + d];
@@ -2191,9 +2333,7 @@ public:
                 for (uint32_t d = 0; d < NB; d++) all += tot[d];
                 uint64_t dummy = 0;
                 choose_shard(tot, all, shard_index, num_shards, bin_lo, bin_hi, dummy);
-                raw_lo = bin_lo < NB ? present_vals[bin_lo] : (1u << mbits);
-                raw_hi = bin_hi < NB ? present_vals[bin_hi] : (1u << mbits);
-                if (bin_lo == 0) raw_lo = 0;
+                shard_raw_range(B);
             }
             if (!tot.empty()) {
                 for (uint32_t d = bin_lo; d < bin_hi; d++) s_host += tot[d];
@@ -2211,113 +2351,127 @@ public:
                 // splitters only need proportions: every 16th tile is histogrammed (identical on every rank);
                 // exact shard sizes come from the filtered histogram below
                 const uint32_t stride = n > (64u << 20) ? 16u : 1u;
-                if ((rc = launch_hist_text((uint32_t)nwg_t, lds_hist_text, d_text, n, kp, d_remap, kp.top_shift, tchunk,
+                if ((rc = launch_hist_text((uint32_t)nwg_t, lds_hist_text, B.d_text, n, kp, d_remap, kp.top_shift, tchunk,
                                            0u, kp.raw_bins, stride))) return rc;
                 hipLaunchKernelGGL(k_scan_table_cols, dim3((kp.nbins + 255) / 256), dim3(256), 0, stream,
                                    (uint32_t*)table.p, (uint32_t)nwg_t, kp.nbins, (uint32_t*)bintot.p);
                 std::vector<uint32_t> tot(kp.nbins);
-                HIP_TRY(d2h(tot.data(), bintot.p, (size_t)kp.nbins * 4));
+                HIP_TRY(read_at_sync(tot.data(), bintot.p, (size_t)kp.nbins * 4));
                 HIP_TRY(sync_reads());
                 tot.resize(NB);
                 uint64_t sampled = 0, dummy = 0;
                 for (uint32_t v : tot) sampled += v;
                 choose_shard(tot, sampled, shard_index, num_shards, bin_lo, bin_hi, dummy);
-                raw_lo = bin_lo < NB ? present_vals[bin_lo] : (1u << mbits);
-                raw_hi = bin_hi < NB ? present_vals[bin_hi] : (1u << mbits);
-                if (bin_lo == 0) raw_lo = 0;
+                shard_raw_range(B);
             }
-            if ((rc = launch_hist_text((uint32_t)nwg_t, lds_hist_text, d_text, n, kp, d_remap, kp.top_shift, tchunk,
-                                       raw_lo, raw_hi))) return rc;
+            if ((rc = launch_hist_text((uint32_t)nwg_t, lds_hist_text, B.d_text, n, kp, d_remap, kp.top_shift, tchunk,
+                                       B.raw_lo, B.raw_hi))) return rc;
             hipLaunchKernelGGL(k_scan_table_cols, dim3((kp.nbins + 255) / 256), dim3(256), 0, stream,
                                (uint32_t*)table.p, (uint32_t)nwg_t, kp.nbins, (uint32_t*)bintot.p);
             hipLaunchKernelGGL(k_scan_bins, dim3(1), dim3(256), 0, stream, (const uint32_t*)bintot.p, kp.nbins,
                                (uint32_t*)binbase.p, sc(SC_TOTAL));
             HIP_TRY(hipMemcpyAsync(leafbase.p, binbase.p, (size_t)NB * 4, hipMemcpyDeviceToDevice, stream));
         }
-        st.top_lo = bin_lo; st.top_hi = bin_hi;
+        B.st.top_lo = bin_lo; B.st.top_hi = bin_hi;
         HIP_TRY(hipEventRecord(ev[3], stream));
         unsigned long long s_ull = s_host;
         if (!s_known) {
-            HIP_TRY(d2h(&s_ull, sc(SC_TOTAL), 8));
+            HIP_TRY(read_at_sync(&s_ull, sc(SC_TOTAL), 8));
             HIP_TRY(sync_reads());
         }
-        const uint64_t s = s_ull;
-        st.num_suffixes = s;
-        if (num_suffixes_out) *num_suffixes_out = s;
-        uint32_t* const caller_sa = d_sa; uint32_t* const caller_lcp = d_lcp;
-        // ---- the listed bytes back into the text, the suffixes that looked at them re-placed (sufr_exc.inc): bsa / blcp = the m
-        // ranks of the build on 'N', the caller's arrays take the result.  `rebuilt`: the general code table has built the text instead.
-        uint32_t mql_count = 0;                                // suffixes of the finished arrays
-        auto reinsert_listed = [&](const uint32_t* bsa, const uint32_t* blcp, uint32_t m, bool& rebuilt) -> int {
-            rebuilt = false;
-            HIP_TRY(hipEventRecord(ev[9], stream));
-            std::vector<uint32_t> ep(nexc);
-            HIP_TRY(hipMemcpyAsync(ep.data(), exc_pos.p, (size_t)nexc * 4, hipMemcpyDeviceToHost, stream));
+        B.s = s_ull;
+        B.st.num_suffixes = B.s;
+        if (B.num_suffixes_out) *B.num_suffixes_out = B.s;
+        return 0;
+    }
+
+    // ---- the listed bytes back into the text, the suffixes that looked at them re-placed (sufr_exc.inc): bsa / blcp = the m
+    // ranks of the build on 'N', the caller's arrays take the result.  `rebuilt`: the general code table has built the text instead.
+    int reinsert_listed(Build& B, const uint32_t* bsa, const uint32_t* blcp, uint32_t m, bool& rebuilt)
+    {
+        const uint32_t nexc = B.nexc;
+        rebuilt = false;
+        HIP_TRY(hipEventRecord(ev[9], stream));
+        std::vector<uint32_t> ep(nexc);
+        HIP_TRY(hipMemcpyAsync(ep.data(), exc_pos.p, (size_t)nexc * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(sync_reads());
+        std::sort(ep.begin(), ep.end());
+        int rc2;
+        if ((rc2 = ensure(exc_sorted, (size_t)nexc * 4))) return rc2;
+        HIP_TRY(hipMemcpyAsync(exc_sorted.p, ep.data(), (size_t)nexc * 4, hipMemcpyHostToDevice, stream));
+        uint64_t affected = 0, s_final = m;
+        ExcShard esh;
+        esh.sharded = B.num_shards > 1 ? 1 : 0; esh.raw_lo = B.raw_lo; esh.raw_hi = B.raw_hi; esh.D = B.mbits / B.kp.b; esh.allow_amb = B.allow_amb ? 1 : 0;
+        esh.cap = B.mql_fast ? (uint32_t)opt_max_query_len : 0u;
+        rc2 = exc_reinsert(*this, B.d_text, B.n, bsa, blcp, m, (const uint32_t*)exc_sorted.p, nexc, B.caller_sa, B.caller_lcp, B.cap, &affected, esh, &s_final);
+        HIP_TRY(sync_reads());                              // (ep: a host vector)
+        if (rc2 == SUFR_HIP_E_UNSUPPORTED && err.empty()) {
+            // more suffixes looked at the listed bytes than the whole-text sort takes: the general code table, from the caller's text
+            exc_disable = true;
+            rc2 = sort_device_u32(B.d_in_caller, B.n, B.flags, B.shard_index, B.num_shards, B.caller_sa, B.caller_lcp, B.cap, B.num_suffixes_out, B.st_out);
+            exc_disable = false;
+            rebuilt = true;
+            return rc2;
+        }
+        if (rc2 == SUFR_HIP_E_CAPACITY && B.num_suffixes_out) *B.num_suffixes_out = s_final;      // (what the call needs)
+        if (rc2) return rc2;
+        B.st.num_exceptions = nexc; B.st.num_reinserted = affected;
+        if (s_final != m) {                                // (a shard: suffixes moved between the shards)
+            B.st.num_suffixes = s_final;
+            if (B.num_suffixes_out) *B.num_suffixes_out = s_final;
+        }
+        B.mql_count = (uint32_t)s_final;
+        HIP_TRY(hipEventRecord(ev[10], stream));
+        return 0;
+    }
+
+    // a shard without suffixes in the text as it was BUILT still takes the suffixes whose true first bytes fall into its range
+    // -- unless that range holds no digit at all (bin_lo == bin_hi: nothing lies in it, and its raw bounds say nothing)
+    int empty_shard(Build& B)
+    {
+        if (B.nexc && B.num_shards > 1 && B.bin_lo < B.bin_hi) {
+            bool rebuilt = false;
+            int rc = reinsert_listed(B, nullptr, nullptr, 0u, rebuilt);
+            if (rc || rebuilt) return rc;
+            if (!B.mql_fast && opt_max_query_len > 0 && (rc = apply_max_query_len(opt_max_query_len, B.n, B.caller_sa, B.caller_lcp, B.mql_count))) return rc;
             HIP_TRY(sync_reads());
-            std::sort(ep.begin(), ep.end());
-            int rc2;
-            if ((rc2 = ensure(exc_sorted, (size_t)nexc * 4))) return rc2;
-            HIP_TRY(hipMemcpyAsync(exc_sorted.p, ep.data(), (size_t)nexc * 4, hipMemcpyHostToDevice, stream));
-            uint64_t affected = 0, s_final = m;
-            ExcShard esh;
-            esh.sharded = num_shards > 1 ? 1 : 0; esh.raw_lo = raw_lo; esh.raw_hi = raw_hi; esh.D = mbits / kp.b; esh.allow_amb = allow_amb ? 1 : 0;
-            esh.cap = mql_fast ? (uint32_t)opt_max_query_len : 0u;
-            rc2 = exc_reinsert(*this, d_text, n, bsa, blcp, m, (const uint32_t*)exc_sorted.p, nexc, caller_sa, caller_lcp, cap, &affected, esh, &s_final);
-            HIP_TRY(sync_reads());                              // (ep: a host vector)
-            if (rc2 == SUFR_HIP_E_UNSUPPORTED && err.empty()) {
-                // more suffixes looked at the listed bytes than the whole-text sort takes: the general code table, from the caller's text
-                exc_disable = true;
-                rc2 = sort_device_u32(d_in_caller, n, flags, shard_index, num_shards, caller_sa, caller_lcp, cap, num_suffixes_out, st_out);
-                exc_disable = false;
-                rebuilt = true;
-                return rc2;
-            }
-            if (rc2 == SUFR_HIP_E_CAPACITY && num_suffixes_out) *num_suffixes_out = s_final;      // (what the call needs)
-            if (rc2) return rc2;
-            st.num_exceptions = nexc; st.num_reinserted = affected;
-            if (s_final != m) {                                // (a shard: suffixes moved between the shards)
-                st.num_suffixes = s_final;
-                if (num_suffixes_out) *num_suffixes_out = s_final;
-            }
-            mql_count = (uint32_t)s_final;
-            HIP_TRY(hipEventRecord(ev[10], stream));
-            return 0;
-        };
-        if (s == 0) {
-            // (a shard whose range is empty in the text as it was BUILT still takes the suffixes whose true first bytes fall into it)
-            // -- unless that range holds no digit at all (bin_lo == bin_hi: nothing lies in it, and its raw bounds say nothing)
-            if (nexc && num_shards > 1 && bin_lo < bin_hi) {
-                bool rebuilt = false;
-                rc = reinsert_listed(nullptr, nullptr, 0u, rebuilt);
-                if (rc || rebuilt) return rc;
-                if (!mql_fast && opt_max_query_len > 0 && (rc = apply_max_query_len(opt_max_query_len, n, caller_sa, caller_lcp, mql_count))) return rc;
-                HIP_TRY(sync_reads());
-                HIP_TRY(hipGetLastError());
-            }
-            if (st_out) *st_out = st;
-            return 0;
+            HIP_TRY(hipGetLastError());
         }
-        if (s > cap || !d_sa || !d_lcp) {
-            set_error("output capacity " + std::to_string(cap) + " < num_suffixes " + std::to_string(s));
-            return SUFR_HIP_E_CAPACITY;
-        }
-        const uint32_t m0 = (uint32_t)s;
-        if (nexc) {                                            // the arrays of the build on 'N' for the listed bytes: the caller's are written by exc_reinsert
+        return done(B);
+    }
+
+    int working_arrays(Build& B)
+    {
+        const uint64_t s = B.s;
+        int rc;
+        B.m0 = (uint32_t)s;
+        B.d_sa = B.caller_sa; B.d_lcp = B.caller_lcp;
+        if (B.nexc) {                                          // the arrays of the build on 'N' for the listed bytes: the caller's are written by exc_reinsert
             // (re-writing the caller's arrays in place, only the blocks of ranks that change, was built and measured in round 6: a
             // suffix that leaves its rank comes back millions of ranks away -- "ACGR" sorts behind ALL of "ACGN...", and half of a
             // soft-mask-ignored genome is N --, so 70-91 % of the blocks shift by one or more: save + write of those is more
             // traffic than this one streaming pass, 66.8 against 62.0 ms with 23 '#' delimiters)
             if ((rc = ensure(exc_sa, s * 4 + 64)) || (rc = ensure(exc_lcp, s * 4 + 64))) return rc;
-            d_sa = (uint32_t*)exc_sa.p; d_lcp = (uint32_t*)exc_lcp.p;
+            B.d_sa = (uint32_t*)exc_sa.p; B.d_lcp = (uint32_t*)exc_lcp.p;
         }
         if ((rc = ensure(recA, s * sizeof(Rec) + 64))) return rc;
         if ((rc = ensure(recB, s * sizeof(Rec) + 64))) return rc;
         const size_t nheads = s / 64 + 2;
         if ((rc = ensure(headsA, nheads * 4))) return rc;
-        Rec* xr[2] = {(Rec*)recA.p, (Rec*)recB.p};         // records ping-pong between the levels; the sorted ones end up in [1]
+        B.xr[0] = (Rec*)recA.p; B.xr[1] = (Rec*)recB.p;
+        return 0;
+    }
 
+    // ---- THE radix-partition kernel over the text: nothing but the choice of its instantiation -------------
+    int launch_partition(Build& B)
+    {
+        const uint64_t n = B.n, nwg_t = B.nwg_t, tchunk = B.tchunk;
+        const uint32_t G1 = B.G1, NB = B.NB, raw_lo = B.raw_lo, raw_hi = B.raw_hi, num_shards = B.num_shards;
+        const bool small_tiles = B.small_tiles, mql_fast = B.mql_fast;
+        const KeyParams& kp = B.kp; const DigitMap& dm = B.dm; Rec* const* const xr = B.xr;
+        int rc;
         HIP_TRY(hipEventRecord(ev[4], stream));
-        if (packed_path) {
+        if (B.packed_path) {
 #define SUFR_PART_TEXT_G(BB, NT_, RN_, SH)                                                                               \
             {                                                                                                            \
                 using Geom = PartGeom<BB, NT_, RN_>;                                                                     \
@@ -2368,7 +2522,7 @@ public:
             }
             const bool sh = num_shards > 1;
             bool half_tiles = false;
-            if (!dna_table) {                              // (the DNA text pass has written the suffix-start bitmap)
+            if (!B.dna_table) {                            // (the DNA text pass has written the suffix-start bitmap)
                 const uint32_t nw64 = (uint32_t)((n + 63) / 64);
 #define SUFR_STARTBITS(BB) hipLaunchKernelGGL(k_startbits_packed<BB>, dim3((nw64 + 255) / 256), dim3(256), 0, stream, \
                                               kp.packed, n, kp.elig_codes, (uint64_t*)startbuf.p)
@@ -2380,321 +2534,326 @@ public:
 #undef SUFR_PART_TEXT_V
 #undef SUFR_PART_TEXT
 #undef SUFR_PART_TEXT_G
-            st.partition_variant = half_tiles ? 4u : 3u;
+            B.st.partition_variant = half_tiles ? 4u : 3u;
         } else {
-            if ((rc = launch_scatter_text((uint32_t)nwg_t, d_text, n, kp, d_remap, kp.top_shift, tchunk, raw_lo, raw_hi,
+            if ((rc = launch_scatter_text((uint32_t)nwg_t, B.d_text, n, kp, B.d_remap, kp.top_shift, tchunk, raw_lo, raw_hi,
                                           num_shards > 1, xr[0]))) return rc;
-            st.partition_variant = 0u;
+            B.st.partition_variant = 0u;
         }
         HIP_TRY(hipEventRecord(ev[5], stream));
         HIP_TRY(hipGetLastError());
+        return 0;
+    }
 
-        // ---- leaf sort + finish of the small buckets; further MSD levels for the others -------------------
-        const uint32_t nwin = (m0 + 127) / 128;            // 128-position windows of the tie bitmaps
-        const uint32_t fixcap = (uint32_t)(s / 32 + 65536);
+    // ---- leaf sort + finish of the small buckets; further MSD levels for the others; what no level can split: `left` ----
+    int msd_levels(Build& B, LeftOver& left)
+    {
+        const uint64_t n = B.n, s = B.s;
+        const uint32_t m0 = B.m0, NB = B.NB;
+        const int mbits = B.mbits;
+        const bool mql_fast = B.mql_fast;
+        const KeyParams& kp = B.kp; const DigitMap& dm = B.dm; Rec* const* const xr = B.xr; FinishOut& fo = B.fo;
+        int rc;
+        const uint32_t nwin = B.nwin = (m0 + 127) / 128;     // 128-position windows of the tie bitmaps
+        const uint32_t fixcap = B.fixcap = (uint32_t)(s / 32 + 65536);
         if ((rc = ensure(wmaskbuf, (size_t)nwin * 32))) return rc;
-        const uint32_t wcnt_stride = (nwin + 3u) & ~3u;      // (the second row starts 16-byte aligned: scan_u32 takes one launch)
-        if ((rc = ensure(wcntbuf, (size_t)wcnt_stride * 8))) return rc;
+        B.wcnt_stride = (nwin + 3u) & ~3u;                   // (the second row starts 16-byte aligned: scan_u32 takes one launch)
+        if ((rc = ensure(wcntbuf, (size_t)B.wcnt_stride * 8))) return rc;
         if ((rc = ensure(fixbuf, (size_t)fixcap * 4))) return rc;
         HIP_TRY(zero_later(wmaskbuf.p, (size_t)nwin * 32));
         HIP_TRY(zero_later(sc(SC_NFIX), 8));
         HIP_TRY(zero_flush());
-        FinishOut fo;
-        fo.SA = d_sa; fo.LCP = d_lcp; fo.wmask = (unsigned long long*)wmaskbuf.p; fo.fixlist = (uint32_t*)fixbuf.p;
+        fo.SA = B.d_sa; fo.LCP = B.d_lcp; fo.wmask = (unsigned long long*)wmaskbuf.p; fo.fixlist = (uint32_t*)fixbuf.p;
         fo.nfix = (uint32_t*)sc(SC_NFIX); fo.fixcap = fixcap; fo.b = kp.b; fo.K = kp.K;
-        uint32_t left_groups = 0;                          // buckets whose members agree on every key character
         rg_active.clear(); rg_run_off = 0;                 // (run buckets of this build: sufr_runs.inc)
-        uint64_t left_records = 0;
-        uint32_t left_depth = 0;
-        uint64_t left_maxbig = 0;                          // the largest of them
-        {
-            if ((rc = ensure(segst[0], 256))) return rc;
-            if ((rc = ensure(segsz[0], 256))) return rc;
-            segcur = 0;
-            h_seg0[0] = 0u; h_seg0[1] = m0;                 // (a member: the copies are asynchronous)
-            HIP_TRY(hipMemcpyAsync(segst[0].p, &h_seg0[0], 4, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(segsz[0].p, &h_seg0[1], 4, hipMemcpyHostToDevice, stream));
-            uint32_t nseg = 1;
-            uint64_t m = s;
-            int src = 0;
-            int bits_done = mbits;
-            DigitMap dl = dm;                              // digit map of the level that produced the current leaves
-            const int maxbits = mql_fast ? 64 : kp.K * kp.b;     // (a capped build: the position bits below the characters are digits too)
-            const int charbits = mql_fast ? mql_charbits : maxbits;
-            uint32_t levels = 1;
-            for (;;) {
-                uint32_t nbig = 0; uint64_t mbig = 0, maxbig = 0;
-                if ((rc = leaf_stage(xr[src], xr[1], nseg, m, dl, cc, fo, 64 - bits_done, nbig, mbig, maxbig)))
-                    return rc;
-                if (debug) fprintf(stderr, "[sufr_hip debug] msd level %u: segments=%u records=%llu bits=%d -> big leaves=%u records=%llu\n",
-                                   levels, nseg, (unsigned long long)m, bits_done, nbig, (unsigned long long)mbig);
-                if (!nbig) break;
-                segcur ^= 1; nseg = nbig; m = mbig;
-                if (levels == 1 && packed_path && !mql_fast) {
-                    if ((rc = run_groups_extract(d_text, n, kp, xr[src], xr[1], (uint32_t)(mbits / kp.b), s, fo, nseg, m, maxbig))) return rc;
-                    if (!nseg) break;
-                }
-                // digit of the next level: the dense D-character digit while the table of sub-buckets stays small,
-                // else as many plain bits as that allows; nothing once the key is used up
-                int w = 0;
-                const bool in_chars = bits_done < charbits;   // (a digit never holds characters and position bits)
-                const int digit_end = in_chars ? charbits : maxbits;
-                bool char_digit = false;                      // the dense D-character digit of the text
-                if (bits_done < digit_end) {
-                    w = mbits;
-                    if (bits_done + w > digit_end) w = digit_end - bits_done;
-                    uint64_t budget = (1ull << 26) / nseg;      // sub-bucket cells per level (2^28: one level less on the --dna build, -1 ms of 105: the tables themselves cost)
-                    int wb = 0; while (wb < 12 && (2ull << wb) <= budget) wb++;     // an identity map holds <= MSD_MAX_BINS values
-                    char_digit = in_chars && bits_done % mbits == 0 && w == mbits && (uint64_t)NB <= budget;
-                    if (!char_digit) { if (w > wb) w = wb; if (w < 1) w = 1; }
-                }
-                // Segments are dealt to the groups whole (their workgroups share an XCD and complete each other's lines in
-                // its L2): one segment that outweighs a group's share -- the N^k bucket of an --allow-ambiguity build is
-                // half of all records -- would leave seven eighths of the chip idle.  Then every workgroup strides over
-                // the whole tile list.
-                const uint32_t G = (nseg >= 64 && maxbig * msd_groups <= m + m / 2) ? msd_groups : 1u;
-                uint32_t SG = 0, tub = 0;
-                if ((rc = plan_tiles(nseg, m, G, (uint32_t)(ms_nt * ms_e), SG, tub))) return rc;
-                if (w == 0) {
-                    // these buckets' members share all K key characters: the re-keying levels take them as groups
-                    // (their records must lie in the array the levels read: xr[1])
-                    if (src != 1)
-                        hipLaunchKernelGGL(k_copy_tiles, dim3(1024), dim3(256), 0, stream, (const Rec*)xr[src],
-                                           (const uint4*)tdesc.p, (const unsigned long long*)sc(SC_UTOTAL), xr[1]);
-                    hipLaunchKernelGGL(k_append_starts, dim3((nseg + 255) / 256), dim3(256), 0, stream,
-                                       (const uint32_t*)segst[segcur].p, nseg, fo.fixlist, fo.nfix, fo.fixcap);
-                    hipLaunchKernelGGL(k_advance_fix, dim3(1), dim3(64), 0, stream, (uint32_t*)sc(SC_NFIX),
-                                       (const unsigned long long*)nullptr, nseg);
-                    HIP_TRY(hipGetLastError());
-                    left_groups = nseg; left_records = m; left_depth = (uint32_t)(bits_done / kp.b); left_maxbig = maxbig;
-                    break;
-                }
-                DigitMap dn = dm;
-                if (!char_digit) { if ((rc = identity_digit_map(w, dn))) return rc; }
-                bits_done += w;
-                const int shift = 64 - bits_done;
-                const uint32_t NBn = dn.nbins;
-                const uint64_t cells = (uint64_t)nseg * NBn;
-                if ((rc = ensure(leafcnt, cells * 4))) return rc;
-                if ((rc = ensure(leafoff, cells * 4))) return rc;
-                if ((rc = ensure(leafbase, cells * 4))) return rc;
-                if ((rc = ensure(leafcur, cells * 4))) return rc;
-                HIP_TRY(hipMemsetAsync(leafcnt.p, 0, cells * 4, stream));
-                {
-                    const size_t lds = msd_map_bytes_host(dn.rows) + (size_t)NBn * 4;
-                    hipLaunchKernelGGL(k_msd_hist, dim3(2048), dim3(THREADS), lds, stream, (const Rec*)xr[src],
-                                       (const uint4*)tdesc.p, (const unsigned long long*)sc(SC_UTOTAL), shift, dn,
-                                       (uint32_t*)leafcnt.p);
-                }
-                if ((rc = scan_u32((const uint32_t*)leafcnt.p, (uint32_t)cells, (uint32_t*)leafoff.p))) return rc;
-                hipLaunchKernelGGL(k_msd_leafbase, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, stream,
-                                   (const uint32_t*)leafoff.p, (const uint32_t*)segst[segcur].p, nseg, NBn,
-                                   (uint32_t*)leafbase.p, (uint32_t*)leafcur.p);
-                {
-#define SUFR_MSD_SCATTER(NT_, E_)                                                                                        \
-                    {                                                                                                    \
-                        const size_t lds = (size_t)(NT_ * E_) * 14 + msd_map_bytes_host(dn.rows) +                      \
-                                           (size_t)((NBn + 3u) & ~3u) * 4 + 128;                                        \
-                        HIP_TRY(hipFuncSetAttribute((const void*)k_msd_scatter<NT_, E_>,                                \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
-                        hipLaunchKernelGGL((k_msd_scatter<NT_, E_>), dim3(ms_e == 8 ? 1024 : 2048), dim3(NT_), lds, stream, \
-                                           (const Rec*)xr[src], (const uint4*)tdesc.p, (const uint32_t*)upre.p, G, SG,  \
-                                           (const unsigned long long*)sc(SC_UTOTAL), shift, dn, (uint32_t*)leafcur.p,   \
-                                           xr[src ^ 1]);                                                                \
-                    }
-                    // (1024 threads / 8192-record tiles: no faster, and one workgroup per CU)
-                    // (1024 threads x 10: 10 240-record tiles, one workgroup per CU: +2 ms, profiles/r06_level2_tiles.txt)
-                    if (ms_e == 4) SUFR_MSD_SCATTER(512, 4) else if (ms_e == 6) SUFR_MSD_SCATTER(512, 6) else SUFR_MSD_SCATTER(512, 8)
-#undef SUFR_MSD_SCATTER
-                }
-                HIP_TRY(hipGetLastError());
-                src ^= 1;
-                dl = dn;
-                levels++;
+        if ((rc = ensure(segst[0], 256))) return rc;
+        if ((rc = ensure(segsz[0], 256))) return rc;
+        segcur = 0;
+        h_seg0[0] = 0u; h_seg0[1] = m0;                 // (a member: the copies are asynchronous)
+        HIP_TRY(hipMemcpyAsync(segst[0].p, &h_seg0[0], 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(segsz[0].p, &h_seg0[1], 4, hipMemcpyHostToDevice, stream));
+        uint32_t nseg = 1;
+        uint64_t m = s;
+        int src = 0;
+        int bits_done = mbits;
+        DigitMap dl = dm;                              // digit map of the level that produced the current leaves
+        const int maxbits = mql_fast ? 64 : kp.K * kp.b;     // (a capped build: the position bits below the characters are digits too)
+        const int charbits = mql_fast ? B.mql_charbits : maxbits;
+        uint32_t levels = 1;
+        for (;;) {
+            uint32_t nbig = 0; uint64_t mbig = 0, maxbig = 0;
+            if ((rc = leaf_stage(xr[src], xr[1], nseg, m, dl, B.cc, fo, 64 - bits_done, nbig, mbig, maxbig)))
+                return rc;
+            if (debug) fprintf(stderr, "[sufr_hip debug] msd level %u: segments=%u records=%llu bits=%d -> big leaves=%u records=%llu\n",
+                               levels, nseg, (unsigned long long)m, bits_done, nbig, (unsigned long long)mbig);
+            if (!nbig) break;
+            segcur ^= 1; nseg = nbig; m = mbig;
+            if (levels == 1 && B.packed_path && !mql_fast) {
+                if ((rc = run_groups_extract(B.d_text, n, kp, xr[src], xr[1], (uint32_t)(mbits / kp.b), s, fo, nseg, m, maxbig))) return rc;
+                if (!nseg) break;
             }
-            st.num_passes = levels;
+            // digit of the next level: the dense D-character digit while the table of sub-buckets stays small,
+            // else as many plain bits as that allows; nothing once the key is used up
+            int w = 0;
+            const bool in_chars = bits_done < charbits;   // (a digit never holds characters and position bits)
+            const int digit_end = in_chars ? charbits : maxbits;
+            bool char_digit = false;                      // the dense D-character digit of the text
+            if (bits_done < digit_end) {
+                w = mbits;
+                if (bits_done + w > digit_end) w = digit_end - bits_done;
+                uint64_t budget = (1ull << 26) / nseg;      // sub-bucket cells per level (2^28: one level less on the --dna build, -1 ms of 105: the tables themselves cost)
+                int wb = 0; while (wb < 12 && (2ull << wb) <= budget) wb++;     // an identity map holds <= MSD_MAX_BINS values
+                char_digit = in_chars && bits_done % mbits == 0 && w == mbits && (uint64_t)NB <= budget;
+                if (!char_digit) { if (w > wb) w = wb; if (w < 1) w = 1; }
+            }
+            // Segments are dealt to the groups whole (their workgroups share an XCD and complete each other's lines in
+            // its L2): one segment that outweighs a group's share -- the N^k bucket of an --allow-ambiguity build is
+            // half of all records -- would leave seven eighths of the chip idle.  Then every workgroup strides over
+            // the whole tile list.
+            const uint32_t G = (nseg >= 64 && maxbig * msd_groups <= m + m / 2) ? msd_groups : 1u;
+            uint32_t SG = 0, tub = 0;
+            if ((rc = plan_tiles(nseg, m, G, (uint32_t)(ms_nt * ms_e), SG, tub))) return rc;
+            if (w == 0) {
+                // these buckets' members share all K key characters: the re-keying levels take them as groups
+                // (their records must lie in the array the levels read: xr[1])
+                if (src != 1)
+                    hipLaunchKernelGGL(k_copy_tiles, dim3(1024), dim3(256), 0, stream, (const Rec*)xr[src],
+                                       (const uint4*)tdesc.p, (const unsigned long long*)sc(SC_UTOTAL), xr[1]);
+                hipLaunchKernelGGL(k_append_starts, dim3((nseg + 255) / 256), dim3(256), 0, stream,
+                                   (const uint32_t*)segst[segcur].p, nseg, fo.fixlist, fo.nfix, fo.fixcap);
+                hipLaunchKernelGGL(k_advance_fix, dim3(1), dim3(64), 0, stream, (uint32_t*)sc(SC_NFIX),
+                                   (const unsigned long long*)nullptr, nseg);
+                HIP_TRY(hipGetLastError());
+                left.groups = nseg; left.records = m; left.depth = (uint32_t)(bits_done / kp.b); left.maxbig = maxbig;
+                break;
+            }
+            DigitMap dn = dm;
+            if (!char_digit) { if ((rc = identity_digit_map(w, dn))) return rc; }
+            bits_done += w;
+            const int shift = 64 - bits_done;
+            const uint32_t NBn = dn.nbins;
+            const uint64_t cells = (uint64_t)nseg * NBn;
+            if ((rc = ensure(leafcnt, cells * 4))) return rc;
+            if ((rc = ensure(leafoff, cells * 4))) return rc;
+            if ((rc = ensure(leafbase, cells * 4))) return rc;
+            if ((rc = ensure(leafcur, cells * 4))) return rc;
+            HIP_TRY(hipMemsetAsync(leafcnt.p, 0, cells * 4, stream));
+            {
+                const size_t lds = msd_map_bytes_host(dn.rows) + (size_t)NBn * 4;
+                hipLaunchKernelGGL(k_msd_hist, dim3(2048), dim3(THREADS), lds, stream, (const Rec*)xr[src],
+                                   (const uint4*)tdesc.p, (const unsigned long long*)sc(SC_UTOTAL), shift, dn,
+                                   (uint32_t*)leafcnt.p);
+            }
+            if ((rc = scan_u32((const uint32_t*)leafcnt.p, (uint32_t)cells, (uint32_t*)leafoff.p))) return rc;
+            hipLaunchKernelGGL(k_msd_leafbase, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, stream,
+                               (const uint32_t*)leafoff.p, (const uint32_t*)segst[segcur].p, nseg, NBn,
+                               (uint32_t*)leafbase.p, (uint32_t*)leafcur.p);
+            {
+#define SUFR_MSD_SCATTER(NT_, E_)                                                                                        \
+                {                                                                                                    \
+                    const size_t lds = (size_t)(NT_ * E_) * 14 + msd_map_bytes_host(dn.rows) +                      \
+                                       (size_t)((NBn + 3u) & ~3u) * 4 + 128;                                        \
+                    HIP_TRY(hipFuncSetAttribute((const void*)k_msd_scatter<NT_, E_>,                                \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
+                    hipLaunchKernelGGL((k_msd_scatter<NT_, E_>), dim3(ms_e == 8 ? 1024 : 2048), dim3(NT_), lds, stream, \
+                                       (const Rec*)xr[src], (const uint4*)tdesc.p, (const uint32_t*)upre.p, G, SG,  \
+                                       (const unsigned long long*)sc(SC_UTOTAL), shift, dn, (uint32_t*)leafcur.p,   \
+                                       xr[src ^ 1]);                                                                \
+                }
+                // (1024 threads / 8192-record tiles: no faster, and one workgroup per CU)
+                // (1024 threads x 10: 10 240-record tiles, one workgroup per CU: +2 ms, profiles/r06_level2_tiles.txt)
+                if (ms_e == 4) SUFR_MSD_SCATTER(512, 4) else if (ms_e == 6) SUFR_MSD_SCATTER(512, 6) else SUFR_MSD_SCATTER(512, 8)
+#undef SUFR_MSD_SCATTER
+            }
+            HIP_TRY(hipGetLastError());
+            src ^= 1;
+            dl = dn;
+            levels++;
         }
+        B.st.num_passes = levels;
         HIP_TRY(hipEventRecord(ev[6], stream));
         // LCP of every window's (and left-over group's) first record with the record before it
         hipLaunchKernelGGL(k_fix_window_lcp, dim3(1024), dim3(256), 0, stream, (const uint32_t*)fixbuf.p,
-                           (const uint32_t*)sc(SC_NFIX), fixcap, (const Rec*)xr[1], d_lcp, kp.b, kp.K);
+                           (const uint32_t*)sc(SC_NFIX), fixcap, (const Rec*)xr[1], B.d_lcp, kp.b, kp.K);
         hipLaunchKernelGGL(k_tie_counts, dim3((nwin + 255) / 256), dim3(256), 0, stream,
-                           (const unsigned long long*)wmaskbuf.p, nwin, (uint32_t*)wcntbuf.p, wcnt_stride);
+                           (const unsigned long long*)wmaskbuf.p, nwin, (uint32_t*)wcntbuf.p, B.wcnt_stride);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ev[7], stream));
-        st.num_levels = 1;
+        B.st.num_levels = 1;
+        return 0;
+    }
 
-        // (the chain of the left-over buckets when it runs on the helper pipeline: joined after the tie runs, and on every way out)
-        // (prefix doubling reads the ranks of ALL suffixes: the tie chain joins it before its first round, before_doubling)
-        struct LeftChain { std::thread th; int rc = 0; sufr_hip_stats st; ~LeftChain() { if (th.joinable()) th.join(); } } left_chain;
-        memset(&left_chain.st, 0, sizeof left_chain.st);
-        // the join: once per build, whoever comes first -- its result, its counts, then the run buckets it left to be expanded
-        auto join_left_chain = [&]() -> int {
-            if (!left_chain.th.joinable()) return 0;           // (not started, or joined already)
-            left_chain.th.join();
-            if (left_chain.rc) { err = helper->err; return left_chain.rc; }
-            st.num_levels += left_chain.st.num_levels;
-            st.num_large_groups += left_chain.st.num_large_groups;
-            st.deep_records += left_chain.st.deep_records;
-            return run_groups_expand(d_text, n, kp, d_sa, d_lcp);
-        };
-        // ---- buckets whose members agree on all K key characters: groups for the re-keying levels ----------
-        {
-            // (run buckets of the whole key among them are found here; those taken out after the first level join the list now,
-            // with their own depth)
-            if (left_groups && left_maxbig >= RG_MIN_SIZE && !mql_fast && (rc = run_groups_find(d_text, n, kp, xr[1], xr[1], (const uint32_t*)segst[segcur].p, (uint32_t*)segsz[segcur].p,
-                                                     left_groups, (uint32_t)kp.K, RG_MIN_SIZE, false))) return rc;
-            uint32_t early = 0;
-            for (const RunGroupState& S : rg_active) if (S.K != (uint32_t)kp.K) early++;
-            const uint32_t* depth_of = nullptr;
-            if (early) {
-                const uint32_t Lall = left_groups + early;
-                std::vector<uint32_t> hs(early), hz(early), hd(Lall, left_depth);
-                uint32_t e = 0;
-                for (const RunGroupState& S : rg_active)
-                    if (S.K != (uint32_t)kp.K) { hs[e] = S.g.start; hz[e] = S.M; hd[left_groups + e] = S.K; e++; }
-                if ((rc = ensure_keep(segst[segcur], (size_t)Lall * 4)) || (rc = ensure_keep(segsz[segcur], (size_t)Lall * 4))) return rc;
-                if ((rc = ensure(rg_depth, (size_t)Lall * 4))) return rc;
-                HIP_TRY(hipMemcpyAsync((uint32_t*)segst[segcur].p + left_groups, hs.data(), (size_t)early * 4, hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyAsync((uint32_t*)segsz[segcur].p + left_groups, hz.data(), (size_t)early * 4, hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(rg_depth.p, hd.data(), (size_t)Lall * 4, hipMemcpyHostToDevice, stream));
-                HIP_TRY(sync_reads());           // (host vectors)
-                depth_of = (const uint32_t*)rg_depth.p;
-                left_groups = Lall;
-            }
-            if (left_groups) {
-                LevelState lg;
-                lg.k = nullptr; lg.i = (const uint32_t*)xr[1] + 2; lg.istride = 3; lg.s = nullptr; lg.o = nullptr; lg.m = m0; lg.deep = false; lg.sbits = 0;
-                lg.L = left_groups; lg.heads_cur = &headsA; lg.heads_nxt = &headsB; lg.depth_cur = &depthA;
-                lg.depth_nxt = &depthB; lg.which = 0;
-                lg.seg_start = (const uint32_t*)segst[segcur].p; lg.seg_size = (const uint32_t*)segsz[segcur].p;
-                lg.seg_depth = left_depth; lg.seg_depth_of = depth_of;
-                lg.pos_keys = mql_fast;
-                if (mql_fast) lg.seg_depth = (uint32_t)kp.K;          // (they agree on their L characters: every LCP inside is cut back to L)
-                const bool side_by_side = overlap_chains && left_records >= (opt_overlap_min ? opt_overlap_min : OVERLAP_MIN_DEFAULT);
-                if (debug) fprintf(stderr, "[sufr_hip debug] left-over buckets: groups=%u records=%llu%s\n", left_groups,
-                                   (unsigned long long)left_records, side_by_side ? " (on the helper pipeline)" : "");
-                if (side_by_side) {
-                    // this chain on the helper pipeline, side by side with the tie runs below
-                    if (!helper) {
-                        helper.reset(new Pipeline);
-                        if ((rc = helper->init(device))) { err = helper->err; helper->destroy(); helper.reset(); return rc; }
-                    }
-                    Pipeline& H = *helper;
-                    H.read_env();
-                    H.debug = debug;
-                    H.rtab = rtab;
-                    if ((rc = H.ensure(H.lut, 512)) || (rc = H.ensure(H.scalars, SC_N * 8))) { err = H.err; return rc; }
-                    HIP_TRY(hipMemcpyAsync(H.lut.p, lut.p, sizeof h_lut, hipMemcpyDeviceToDevice, stream));
-                    HIP_TRY(hipEventRecord(ev[11], stream));           // the records, the segment list and the code table are in place
-                    HIP_TRY(hipStreamWaitEvent(H.stream, ev[11], 0));
-                    lg.heads_cur = &H.headsA; lg.heads_nxt = &H.headsB; lg.depth_cur = &H.depthA; lg.depth_nxt = &H.depthB;
-                    H.pin_items.clear(); H.pin_used = 0; H.pub_items.clear(); H.copies_queued = false; H.zlist.n = 0;
-                    left_chain.st = sufr_hip_stats(); left_chain.rc = 0;
-                    H.dbl_entries = 0;
-                    last_overlapped = 1;
-                    left_chain.th = std::thread([&H, &left_chain, lg, d_text, n, kp, d_sa, d_lcp, this]() {
-                        (void)hipSetDevice(device);
-                        left_chain.rc = H.run_levels(lg, d_text, n, kp, d_sa, d_lcp, left_chain.st);
-                        if (hipStreamSynchronize(H.stream) != hipSuccess && !left_chain.rc) { H.set_error("the helper stream failed"); left_chain.rc = SUFR_HIP_E_HIP; }
-                    });
-                } else {
-                    if ((rc = run_levels(lg, d_text, n, kp, d_sa, d_lcp, st))) return rc;
-                    if ((rc = run_groups_expand(d_text, n, kp, d_sa, d_lcp))) return rc;
-                }
-            }
-        }
+    // the join: once per build, whoever comes first -- its result, its counts, then the run buckets it left to be expanded
+    int join_left_chain(Build& B, LeftChain& chain)
+    {
+        if (!chain.th.joinable()) return 0;                // (not started, or joined already)
+        chain.th.join();
+        if (chain.rc) { err = helper->err; return chain.rc; }
+        B.st.num_levels += chain.st.num_levels;
+        B.st.num_large_groups += chain.st.num_large_groups;
+        B.st.deep_records += chain.st.deep_records;
+        return run_groups_expand(B.d_text, B.n, B.kp, B.d_sa, B.d_lcp);
+    }
 
-        // ---- the tie level: tie runs (equal whole keys) packed densely, whole segments as groups ----------
-        {
-            uint32_t* cnt = (uint32_t*)wcntbuf.p;
-            const uint32_t* icur = d_sa;                   // tie members lie in SA in key order
-            // wcnt = [records per window | runs per window]: two exclusive scans give the dense offsets
-            if ((rc = ensure(recoff, (size_t)nwin * 4))) return rc;
-            if ((rc = ensure(runoff, (size_t)nwin * 4))) return rc;
-            if ((rc = scan_u32((const uint32_t*)cnt, nwin, (uint32_t*)recoff.p, sc(SC_TMP0)))) return rc;
-            unsigned long long tot2[2] = {0, 0};          // records in tie runs, tie runs, (and the fix-list length)
-            if ((rc = scan_u32((const uint32_t*)(cnt + wcnt_stride), nwin, (uint32_t*)runoff.p, sc(SC_TMP1)))) return rc;
-            unsigned long long nf = 0;
-            HIP_TRY(d2h(tot2, sc(SC_TMP0), 16));
-            HIP_TRY(d2h(&nf, sc(SC_NFIX), 8));
-            HIP_TRY(sync_reads());        // one round trip for the three
-            if ((uint32_t)nf > fixcap) { set_error("internal error: window list overflow"); return SUFR_HIP_E_HIP; }
-            const unsigned long long tot_rec = tot2[0], tot_run = tot2[1];
-            const uint32_t m2 = (uint32_t)tot_rec, L2 = (uint32_t)tot_run;
-            if (debug) fprintf(stderr, "[sufr_hip debug] tie level: runs=%u records=%u\n", L2, m2);
-            if (m2 > 0) {
-                st.num_levels++;
-                st.num_large_groups += L2;
-                st.deep_records += m2;
-                LevelArrays& A = lv[0];
-                if ((rc = ensure(A.keyA, (size_t)m2 * 8))) return rc;
-                if ((rc = ensure(A.idxA, (size_t)m2 * 4))) return rc;
-                if ((rc = ensure(A.segA, (size_t)m2 * 4))) return rc;
-                if ((rc = ensure(A.opos, (size_t)m2 * 4))) return rc;
-                if ((rc = ensure(depthA, (size_t)L2 * 4))) return rc;
-                if ((rc = ensure(period, (size_t)L2))) return rc;
-                if ((rc = ensure(headsA, ((size_t)m2 / 64 + 2) * 4))) return rc;
-                // (a wave per window pays from ~8 tied records per window on: measured 2.5 / 1.0 ms at 3, ~6 / 16.7 ms at 22)
-                if ((uint64_t)m2 >= (uint64_t)nwin * 8)
-                    hipLaunchKernelGGL(k_build_ties<true>, dim3((nwin + 3) / 4), dim3(256), 0, stream,
-                                       (const unsigned long long*)wmaskbuf.p, (const uint32_t*)recoff.p,
-                                       (const uint32_t*)runoff.p, (const uint32_t*)icur, m0, (uint32_t)kp.K,
-                                       (uint32_t*)A.idxA.p, (uint32_t*)A.segA.p, (uint32_t*)A.opos.p,
-                                       (uint32_t*)depthA.p, (uint8_t*)period.p);
-                else
-                    hipLaunchKernelGGL(k_build_ties<false>, dim3((nwin + 255) / 256), dim3(256), 0, stream,
-                                       (const unsigned long long*)wmaskbuf.p, (const uint32_t*)recoff.p,
-                                       (const uint32_t*)runoff.p, (const uint32_t*)icur, m0, (uint32_t)kp.K,
-                                       (uint32_t*)A.idxA.p, (uint32_t*)A.segA.p, (uint32_t*)A.opos.p,
-                                       (uint32_t*)depthA.p, (uint8_t*)period.p);
-                if (mql_fast)
-                    hipLaunchKernelGGL(k_pos_keys, dim3((m2 + 255) / 256), dim3(256), 0, stream, (const uint32_t*)A.idxA.p, m2, (uint64_t*)A.keyA.p);
-                else
-                hipLaunchKernelGGL(k_gather_keys, dim3((m2 + 255) / 256), dim3(256), 0, stream,
-                                   (const uint8_t*)d_text, n, rtab, (const uint16_t*)lut.p,
-                                   (const uint32_t*)A.idxA.p, (const uint32_t*)A.segA.p, (const uint32_t*)depthA.p,
-                                   (const uint8_t*)period.p, m2, kp, (uint64_t*)A.keyA.p, (uint32_t*)nullptr);
-                uint32_t Lt = 0;
-                if ((rc = finish_level((const uint64_t*)A.keyA.p, (const uint32_t*)A.idxA.p, (const uint32_t*)A.segA.p,
-                                       (const uint32_t*)A.opos.p, (const uint32_t*)depthA.p, m2, 0, d_text, n, kp, d_sa, d_lcp,
-                                       &headsA, Lt))) return rc;
-                LevelState lt;
-                lt.k = (const uint64_t*)A.keyA.p; lt.i = (const uint32_t*)A.idxA.p; lt.s = (const uint32_t*)A.segA.p;
-                lt.o = (const uint32_t*)A.opos.p; lt.m = m2; lt.deep = true; lt.sbits = 0; lt.L = Lt;
-                lt.heads_cur = &headsA; lt.heads_nxt = &headsB; lt.depth_cur = &depthA; lt.depth_nxt = &depthB;
-                lt.which = 1;
-                // Prefix doubling keys a suffix p of depth d by the RANK of p + d.  A shard holds the ranks of its own first-digit range
-                // only (round 4's soak found sharded builds reading whatever the rank array held elsewhere: 38 000 wrong ranks in a
-                // 4 Mb text of templated repeats over two shards, then a memory fault): there the rank array is cleared first, and a
-                // position without a rank is keyed like one that starts no suffix -- by its run key --, below or above all ranked
-                // ones as its first digit lies below or above the shard's range (DblShard).  Without a packed stream to read that
-                // digit from, sharded builds stay with the levels.
-                dbl_shard = DblShard{kp.packed, kp.b, mbits, raw_lo, raw_hi, num_shards > 1 ? 1 : 0};
-                lt.allow_doubling = !mql_fast && (num_shards <= 1 || (packed_path && kp.packed != nullptr)); lt.s_total = m0;
-                lt.pos_keys = mql_fast;
-                before_doubling = join_left_chain;
-                rc = run_levels(lt, d_text, n, kp, d_sa, d_lcp, st);
-                before_doubling = nullptr;
-                if (rc) return rc;
+    // ---- buckets whose members agree on all K key characters: groups for the re-keying levels, here or (from opt_overlap_min
+    // records on) on the helper pipeline, side by side with the tie level ----------
+    int start_left_chain(Build& B, const LeftOver& left, LeftChain& chain)
+    {
+        const uint64_t n = B.n;
+        const bool mql_fast = B.mql_fast;
+        const KeyParams kp = B.kp;                             // (the helper thread takes a copy)
+        uint8_t* const d_text = B.d_text; uint32_t* const d_sa = B.d_sa; uint32_t* const d_lcp = B.d_lcp; Rec* const* const xr = B.xr;
+        uint32_t left_groups = left.groups;
+        int rc;
+        // (run buckets of the whole key among them are found here; those taken out after the first level join the list now,
+        // with their own depth)
+        if (left_groups && left.maxbig >= RG_MIN_SIZE && !mql_fast && (rc = run_groups_find(d_text, n, kp, xr[1], xr[1], (const uint32_t*)segst[segcur].p, (uint32_t*)segsz[segcur].p,
+                                                 left_groups, (uint32_t)kp.K, RG_MIN_SIZE, false))) return rc;
+        uint32_t early = 0;
+        for (const RunGroupState& S : rg_active) if (S.K != (uint32_t)kp.K) early++;
+        const uint32_t* depth_of = nullptr;
+        if (early) {
+            const uint32_t Lall = left_groups + early;
+            std::vector<uint32_t> hs(early), hz(early), hd(Lall, left.depth);
+            uint32_t e = 0;
+            for (const RunGroupState& S : rg_active)
+                if (S.K != (uint32_t)kp.K) { hs[e] = S.g.start; hz[e] = S.M; hd[left_groups + e] = S.K; e++; }
+            if ((rc = ensure_keep(segst[segcur], (size_t)Lall * 4)) || (rc = ensure_keep(segsz[segcur], (size_t)Lall * 4))) return rc;
+            if ((rc = ensure(rg_depth, (size_t)Lall * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync((uint32_t*)segst[segcur].p + left_groups, hs.data(), (size_t)early * 4, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync((uint32_t*)segsz[segcur].p + left_groups, hz.data(), (size_t)early * 4, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(rg_depth.p, hd.data(), (size_t)Lall * 4, hipMemcpyHostToDevice, stream));
+            HIP_TRY(sync_reads());           // (host vectors)
+            depth_of = (const uint32_t*)rg_depth.p;
+            left_groups = Lall;
+        }
+        if (!left_groups) return 0;
+        LevelState lg;
+        lg.k = nullptr; lg.i = (const uint32_t*)xr[1] + 2; lg.istride = 3; lg.s = nullptr; lg.o = nullptr; lg.m = B.m0; lg.deep = false; lg.sbits = 0;
+        lg.L = left_groups; lg.heads_cur = &headsA; lg.heads_nxt = &headsB; lg.depth_cur = &depthA;
+        lg.depth_nxt = &depthB; lg.which = 0;
+        lg.seg_start = (const uint32_t*)segst[segcur].p; lg.seg_size = (const uint32_t*)segsz[segcur].p;
+        lg.seg_depth = left.depth; lg.seg_depth_of = depth_of;
+        lg.pos_keys = mql_fast;
+        if (mql_fast) lg.seg_depth = (uint32_t)kp.K;          // (they agree on their L characters: every LCP inside is cut back to L)
+        const bool side_by_side = overlap_chains && left.records >= (opt_overlap_min ? opt_overlap_min : OVERLAP_MIN_DEFAULT);
+        if (debug) fprintf(stderr, "[sufr_hip debug] left-over buckets: groups=%u records=%llu%s\n", left_groups,
+                           (unsigned long long)left.records, side_by_side ? " (on the helper pipeline)" : "");
+        if (side_by_side) {
+            // this chain on the helper pipeline, side by side with the tie runs
+            if (!helper) {
+                helper.reset(new Pipeline);
+                if ((rc = helper->init(device))) { err = helper->err; helper->destroy(); helper.reset(); return rc; }
             }
+            Pipeline& H = *helper;
+            H.read_env();
+            H.debug = debug;
+            H.rtab = rtab;
+            if ((rc = H.ensure(H.lut, 512)) || (rc = H.ensure(H.scalars, SC_N * 8))) { err = H.err; return rc; }
+            HIP_TRY(hipMemcpyAsync(H.lut.p, lut.p, sizeof h_lut, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipEventRecord(ev[11], stream));           // the records, the segment list and the code table are in place
+            HIP_TRY(hipStreamWaitEvent(H.stream, ev[11], 0));
+            lg.heads_cur = &H.headsA; lg.heads_nxt = &H.headsB; lg.depth_cur = &H.depthA; lg.depth_nxt = &H.depthB;
+            H.reset_reads();
+            chain.st = sufr_hip_stats(); chain.rc = 0;
+            H.dbl_entries = 0;
+            last_overlapped = 1;
+            chain.th = std::thread([&H, &chain, lg, d_text, n, kp, d_sa, d_lcp, this]() {
+                (void)hipSetDevice(device);
+                chain.rc = H.run_levels(lg, d_text, n, kp, d_sa, d_lcp, chain.st);
+                if (hipStreamSynchronize(H.stream) != hipSuccess && !chain.rc) { H.set_error("the helper stream failed"); chain.rc = SUFR_HIP_E_HIP; }
+            });
+        } else {
+            if ((rc = run_levels(lg, d_text, n, kp, d_sa, d_lcp, B.st))) return rc;
+            if ((rc = run_groups_expand(d_text, n, kp, d_sa, d_lcp))) return rc;
         }
-        if ((rc = join_left_chain())) return rc;
-        mql_count = m0;
-        if (mql_fast) {                                        // (before the listed bytes are dealt with: their pass compares under the cap)
-            hipLaunchKernelGGL(k_mql_cap, dim3((m0 / 4 + 256) / 256), dim3(256), 0, stream, d_lcp, m0, (uint32_t)opt_max_query_len);
-            HIP_TRY(hipGetLastError());
-        }
-        if (nexc) {
-            bool rebuilt = false;
-            rc = reinsert_listed(d_sa, d_lcp, m0, rebuilt);
-            if (rc || rebuilt) return rc;
-            d_sa = caller_sa; d_lcp = caller_lcp;
-        }
-        if (!mql_fast && opt_max_query_len > 0 && (rc = apply_max_query_len(opt_max_query_len, n, d_sa, d_lcp, mql_count))) return rc;
-        HIP_TRY(hipEventRecord(ev[8], stream));
-        HIP_TRY(sync_reads());
-        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+
+    // tie runs packed densely: a wave per window (WAVE), or a thread per window
+    template <bool WAVE>
+    void launch_build_ties(uint32_t nwin, const uint32_t* icur, uint32_t m0, uint32_t K, LevelArrays& A)
+    {
+        hipLaunchKernelGGL(k_build_ties<WAVE>, dim3(WAVE ? (nwin + 3) / 4 : (nwin + 255) / 256), dim3(256), 0, stream,
+                           (const unsigned long long*)wmaskbuf.p, (const uint32_t*)recoff.p, (const uint32_t*)runoff.p, icur, m0, K,
+                           (uint32_t*)A.idxA.p, (uint32_t*)A.segA.p, (uint32_t*)A.opos.p, (uint32_t*)depthA.p, (uint8_t*)period.p);
+    }
+
+    // ---- the tie level: tie runs (equal whole keys) packed densely, whole segments as groups ----------
+    int tie_level(Build& B, LeftChain& chain)
+    {
+        const uint64_t n = B.n;
+        const uint32_t m0 = B.m0, nwin = B.nwin, wcnt_stride = B.wcnt_stride, num_shards = B.num_shards;
+        const bool mql_fast = B.mql_fast;
+        const KeyParams& kp = B.kp; sufr_hip_stats& st = B.st;
+        uint8_t* const d_text = B.d_text; uint32_t* const d_sa = B.d_sa; uint32_t* const d_lcp = B.d_lcp;
+        int rc;
+        uint32_t* cnt = (uint32_t*)wcntbuf.p;
+        const uint32_t* icur = d_sa;                   // tie members lie in SA in key order
+        // wcnt = [records per window | runs per window]: two exclusive scans give the dense offsets
+        if ((rc = ensure(recoff, (size_t)nwin * 4))) return rc;
+        if ((rc = ensure(runoff, (size_t)nwin * 4))) return rc;
+        if ((rc = scan_u32((const uint32_t*)cnt, nwin, (uint32_t*)recoff.p, sc(SC_TMP0)))) return rc;
+        unsigned long long tot2[2] = {0, 0};          // records in tie runs, tie runs, (and the fix-list length)
+        if ((rc = scan_u32((const uint32_t*)(cnt + wcnt_stride), nwin, (uint32_t*)runoff.p, sc(SC_TMP1)))) return rc;
+        unsigned long long nf = 0;
+        HIP_TRY(read_at_sync(tot2, sc(SC_TMP0), 16));
+        HIP_TRY(read_at_sync(&nf, sc(SC_NFIX), 8));
+        HIP_TRY(sync_reads());        // one round trip for the three
+        if ((uint32_t)nf > B.fixcap) { set_error("internal error: window list overflow"); return SUFR_HIP_E_HIP; }
+        const unsigned long long tot_rec = tot2[0], tot_run = tot2[1];
+        const uint32_t m2 = (uint32_t)tot_rec, L2 = (uint32_t)tot_run;
+        if (debug) fprintf(stderr, "[sufr_hip debug] tie level: runs=%u records=%u\n", L2, m2);
+        if (m2 == 0) return 0;
+        st.num_levels++;
+        st.num_large_groups += L2;
+        st.deep_records += m2;
+        LevelArrays& A = lv[0];
+        if ((rc = ensure(A.keyA, (size_t)m2 * 8))) return rc;
+        if ((rc = ensure(A.idxA, (size_t)m2 * 4))) return rc;
+        if ((rc = ensure(A.segA, (size_t)m2 * 4))) return rc;
+        if ((rc = ensure(A.opos, (size_t)m2 * 4))) return rc;
+        if ((rc = ensure(depthA, (size_t)L2 * 4))) return rc;
+        if ((rc = ensure(period, (size_t)L2))) return rc;
+        if ((rc = ensure(headsA, ((size_t)m2 / 64 + 2) * 4))) return rc;
+        // (a wave per window pays from ~8 tied records per window on: measured 2.5 / 1.0 ms at 3, ~6 / 16.7 ms at 22)
+        if ((uint64_t)m2 >= (uint64_t)nwin * 8) launch_build_ties<true>(nwin, icur, m0, (uint32_t)kp.K, A);
+        else launch_build_ties<false>(nwin, icur, m0, (uint32_t)kp.K, A);
+        if (mql_fast)
+            hipLaunchKernelGGL(k_pos_keys, dim3((m2 + 255) / 256), dim3(256), 0, stream, (const uint32_t*)A.idxA.p, m2, (uint64_t*)A.keyA.p);
+        else
+        hipLaunchKernelGGL(k_gather_keys, dim3((m2 + 255) / 256), dim3(256), 0, stream,
+                           (const uint8_t*)d_text, n, rtab, (const uint16_t*)lut.p,
+                           (const uint32_t*)A.idxA.p, (const uint32_t*)A.segA.p, (const uint32_t*)depthA.p,
+                           (const uint8_t*)period.p, m2, kp, (uint64_t*)A.keyA.p, (uint32_t*)nullptr);
+        uint32_t Lt = 0;
+        if ((rc = finish_level((const uint64_t*)A.keyA.p, (const uint32_t*)A.idxA.p, (const uint32_t*)A.segA.p,
+                               (const uint32_t*)A.opos.p, (const uint32_t*)depthA.p, m2, 0, d_text, n, kp, d_sa, d_lcp,
+                               &headsA, Lt))) return rc;
+        LevelState lt;
+        lt.k = (const uint64_t*)A.keyA.p; lt.i = (const uint32_t*)A.idxA.p; lt.s = (const uint32_t*)A.segA.p;
+        lt.o = (const uint32_t*)A.opos.p; lt.m = m2; lt.deep = true; lt.sbits = 0; lt.L = Lt;
+        lt.heads_cur = &headsA; lt.heads_nxt = &headsB; lt.depth_cur = &depthA; lt.depth_nxt = &depthB;
+        lt.which = 1;
+        // Prefix doubling keys a suffix p of depth d by the RANK of p + d.  A shard holds the ranks of its own first-digit range
+        // only (round 4's soak found sharded builds reading whatever the rank array held elsewhere: 38 000 wrong ranks in a
+        // 4 Mb text of templated repeats over two shards, then a memory fault): there the rank array is cleared first, and a
+        // position without a rank is keyed like one that starts no suffix -- by its run key --, below or above all ranked
+        // ones as its first digit lies below or above the shard's range (DblShard).  Without a packed stream to read that
+        // digit from, sharded builds stay with the levels.
+        dbl_shard = DblShard{kp.packed, kp.b, B.mbits, B.raw_lo, B.raw_hi, num_shards > 1 ? 1 : 0};
+        lt.allow_doubling = !mql_fast && (num_shards <= 1 || (B.packed_path && kp.packed != nullptr)); lt.s_total = m0;
+        lt.pos_keys = mql_fast;
+        before_doubling = [this, &B, &chain]() { return join_left_chain(B, chain); };
+        rc = run_levels(lt, d_text, n, kp, d_sa, d_lcp, st);
+        before_doubling = nullptr;
+        return rc;
+    }
+
+    // the times of the phases, from the events the stages have recorded (ev[8]: the end of the build, behind a synchronisation)
+    int finish_stats(Build& B)
+    {
+        sufr_hip_stats& st = B.st;
 #ifdef SUFR_HIP_PROBES
         if (debug) {
             unsigned long long ws[4] = {0, 0, 0, 0}, zero[4] = {0, 0, 0, 0};
@@ -2723,9 +2882,8 @@ public:
         (void)hipEventElapsedTime(&st.ms_passes, ev[5], ev[6]);
         (void)hipEventElapsedTime(&st.ms_finish, ev[6], ev[7]);
         (void)hipEventElapsedTime(&st.ms_deep, ev[7], ev[8]);
-        if (nexc) (void)hipEventElapsedTime(&st.ms_exceptions, ev[9], ev[10]);
-        if (st_out) *st_out = st;
-        return 0;
+        if (B.nexc) (void)hipEventElapsedTime(&st.ms_exceptions, ev[9], ev[10]);
+        return done(B);
     }
 
     // Contiguous top-digit range for shard `r` of `R`: cumulative suffix counts balanced to s/R.
