@@ -146,6 +146,23 @@ int  sufr_hip_overlapped(const sufr_hip_ctx *ctx);
 /* how many times the context's last build handed a level to prefix doubling: both chains, added up after the helper was joined
  * (a windowed build: all windows) */
 uint64_t sufr_hip_doublings(const sufr_hip_ctx *ctx);
+/* A --dna build of a text with a few bytes outside {$ % A C G N T} runs on 'N' in their place and re-places the suffixes whose
+ * comparisons reached such a byte (sufr_exc.inc).  With more than max_affected of them the text is built again with the general
+ * code table -- same arrays, more time.  0: the default, 2^22, which is also the most: the whole-text sort of the affected
+ * suffixes and its buffers are sized for it, a larger value is refused with SUFR_HIP_E_INVALID and a message.  A small value
+ * sends small texts down the retry (the tests).  A rank of a sharded build that retries builds the WHOLE text as one shard into
+ * arrays of its own (4 + 4 bytes per suffix of the text beside the shard's) and hands out the ranks whose first bytes lie in its
+ * first-digit range, so that its neighbours, which chose theirs on the 3-bit digits, still fit.  Additive: ABI version 3. */
+int  sufr_hip_set_exc_max_affected(sufr_hip_ctx *ctx, uint64_t max_affected);
+/* why the context's last build call took that retry: 0 it did not; 1 the ranges of positions in front of the listed bytes hold
+ * more than 16 max_affected positions (single shard); 2 more than max_affected ranks were taken out of the arrays; 3 a shard was
+ * left with more than max_affected suffixes to place after those of other shards that belong to it were added (a windowed
+ * build: the largest value over its windows) */
+int  sufr_hip_exc_retry(const sufr_hip_ctx *ctx);
+/* ranks the context's last build took out of the arrays of the text with 'N' for the listed bytes, also when it then went to the
+ * retry for reason 2 or 3 (0: no listed byte, or reason 1, which gives up before it counts them; a windowed build: of the last
+ * window that took any out) */
+uint64_t sufr_hip_exc_taken(const sufr_hip_ctx *ctx);
 
 /* ---- text normalisation: sufr_builder.rs:144-160 (host helper; the GPU build can also do it) --- */
 int sufr_hip_normalize(const uint8_t *in, uint8_t *out, uint64_t n, int ignore_softmask);

@@ -80,7 +80,7 @@ FLAG_SA_U64 = 0x200               # sufr_hip_index_wrap only: 64-bit suffix arra
 # every symbol include/sufr_hip.h declares
 EXPORTS = [
     "sufr_hip_abi_version", "sufr_hip_device_count", "sufr_hip_create", "sufr_hip_destroy",
-    "sufr_hip_last_error", "sufr_hip_set_stream", "sufr_hip_synchronize", "sufr_hip_set_window", "sufr_hip_set_window_retry", "sufr_hip_set_array_budget", "sufr_hip_window_repairs", "sufr_hip_set_overlap_min", "sufr_hip_overlapped", "sufr_hip_doublings", "sufr_hip_normalize", "sufr_hip_sort_device_u32",
+    "sufr_hip_last_error", "sufr_hip_set_stream", "sufr_hip_synchronize", "sufr_hip_set_window", "sufr_hip_set_window_retry", "sufr_hip_set_array_budget", "sufr_hip_window_repairs", "sufr_hip_set_overlap_min", "sufr_hip_overlapped", "sufr_hip_doublings", "sufr_hip_set_exc_max_affected", "sufr_hip_exc_retry", "sufr_hip_exc_taken", "sufr_hip_normalize", "sufr_hip_sort_device_u32",
     "sufr_hip_sort_device_u64", "sufr_hip_stitch_device_u32", "sufr_hip_stitch_device_u64", "sufr_hip_build_u32", "sufr_hip_build_u64", "sufr_hip_lcp_pair",
     "sufr_read_sequence_file", "sufr_sequence_data_free", "sufr_write_file", "sufr_hip_create_file", "sufr_hip_create_from_sequence",
     "sufr_hip_shard_build", "sufr_write_frame", "sufr_hip_shard_write", "sufr_hip_create_from_sequence_multi",
@@ -166,6 +166,9 @@ def lib() -> C.CDLL:
     L.sufr_hip_set_overlap_min.argtypes = [vp, u64]; L.sufr_hip_set_overlap_min.restype = C.c_int
     L.sufr_hip_overlapped.argtypes = [vp]; L.sufr_hip_overlapped.restype = C.c_int
     L.sufr_hip_doublings.argtypes = [vp]; L.sufr_hip_doublings.restype = u64
+    L.sufr_hip_set_exc_max_affected.argtypes = [vp, u64]; L.sufr_hip_set_exc_max_affected.restype = C.c_int
+    L.sufr_hip_exc_retry.argtypes = [vp]; L.sufr_hip_exc_retry.restype = C.c_int
+    L.sufr_hip_exc_taken.argtypes = [vp]; L.sufr_hip_exc_taken.restype = u64
     L.sufr_hip_normalize.argtypes = [vp, vp, u64, C.c_int]; L.sufr_hip_normalize.restype = C.c_int
     dev_sig = [vp, vp, u64, u32, u64, cp, u64, u64, u32, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(Stats)]
     L.sufr_hip_sort_device_u32.argtypes = dev_sig; L.sufr_hip_sort_device_u32.restype = C.c_int
@@ -324,6 +327,22 @@ class Context:
     def doublings(self) -> int:
         """How many times the last build handed a level to prefix doubling (both chains; a windowed build: all windows)."""
         return int(lib().sufr_hip_doublings(self._h))
+
+    def set_exc_max_affected(self, max_affected: int = 0):
+        """Suffixes that may have looked at a byte outside the DNA table before a --dna build goes to the general code table
+        instead of re-placing them (sufr_hip_set_exc_max_affected; 0: the default of 2^22, which is also the most)."""
+        self.check(lib().sufr_hip_set_exc_max_affected(self._h, max_affected))
+
+    @property
+    def exc_retry(self) -> int:
+        """Why the last build built its text again with the general code table: 0 it did not, 1 / 2 / 3 the limit it met
+        (sufr_hip_exc_retry; a windowed build: the largest over its windows)."""
+        return int(lib().sufr_hip_exc_retry(self._h))
+
+    @property
+    def exc_taken(self) -> int:
+        """Ranks the last build took out of the arrays of the text with 'N' for the listed bytes (sufr_hip_exc_taken)."""
+        return int(lib().sufr_hip_exc_taken(self._h))
 
     def synchronize(self):
         self.check(lib().sufr_hip_synchronize(self._h))

@@ -281,6 +281,20 @@ int sufr_hip_set_overlap_min(sufr_hip_ctx* ctx, uint64_t min_records)
 int sufr_hip_overlapped(const sufr_hip_ctx* ctx) { return ctx ? (int)ctx->pl.last_overlapped : 0; }
 uint64_t sufr_hip_doublings(const sufr_hip_ctx* ctx) { return ctx ? ctx->pl.last_doublings : 0; }
 
+int sufr_hip_set_exc_max_affected(sufr_hip_ctx* ctx, uint64_t max_affected)
+{
+    if (!ctx) return SUFR_HIP_E_INVALID;
+    if (max_affected > sufr::Pipeline::EXC_MAX_AFFECTED_DEFAULT) {
+        ctx->pl.set_error("max_affected " + std::to_string(max_affected) + " > 2^22: the whole-text sort of the affected suffixes and its buffers are sized for 2^22");
+        return SUFR_HIP_E_INVALID;
+    }
+    ctx->pl.opt_exc_max_affected = max_affected;
+    return 0;
+}
+
+int sufr_hip_exc_retry(const sufr_hip_ctx* ctx) { return ctx ? (int)ctx->pl.last_exc_retry : 0; }
+uint64_t sufr_hip_exc_taken(const sufr_hip_ctx* ctx) { return ctx ? ctx->pl.last_exc_taken : 0; }
+
 int sufr_hip_synchronize(sufr_hip_ctx* ctx)
 {
     if (!ctx) return SUFR_HIP_E_INVALID;

@@ -31,13 +31,19 @@
 // Which byte T' carries at a listed position does not matter for correctness (no surviving comparison looks at it).  Cost on the
 // 3.1 Gb stand-in with 50 IUPAC bytes: one read of SA' / LCP' to mark, one read + one write to merge (~8 ms); nothing when the
 // text has no such byte.  More than EXC_MAX_LIST listed positions or more than 2^22 affected suffixes take the general code
-// table as before.
+// table as before.  The second limit can be lowered (sufr_hip_set_exc_max_affected; never raised: the list and the whole-text
+// sort are sized for 2^22): exc_reinsert compares against it in three places -- (1) the position ranges of k_exc_pmin, 16 x the
+// limit, before the listed bytes are put back; (2) the ranks taken out; (3) in a shard, the suffixes left to place -- and
+// records which one gave up (Pipeline::last_exc_retry, last_exc_taken).  Pipeline::reinsert_listed then puts back what is still
+// 'N' and builds the text again from the caller's pointer.
 //
 // Shards (first-digit ranges, identical on every rank): a suffix with a listed byte among its first D characters may belong to
 // another shard than the one its 'N' form was built in.  Every rank takes ALL suffixes with a listed byte among their first D
 // characters out of its arrays (k_exc_mark: a reach of at least D - 1), keeps of the taken ones those whose TRUE first D bytes
 // lie in its range, and adds the ones of the other shards' that do (k_exc_shard_add: at most D per listed byte, found from the
-// list alone): every suffix ends up in exactly one shard, no communication.
+// list alone): every suffix ends up in exactly one shard, no communication.  That holds for a rank that takes the retry, too:
+// it builds the whole text with the general table and hands out the ranks whose true first D bytes lie in its range
+// (Pipeline::retry_whole_text) -- a range chosen again on the general table's digits would not fit between its neighbours'.
 
 namespace sufr {
 
@@ -549,10 +555,10 @@ k_exc_shard_add(ExcText X, ExcShard S, uint32_t* __restrict__ out, uint32_t out_
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side.  bsa / blcp: the arrays of the build on T' (s ranks), out_sa / out_lcp: the caller's.  Returns
-// SUFR_HIP_E_UNSUPPORTED (no error text) when more suffixes are affected than the whole-text sort takes: the caller builds
-// the text again with the general code table.
+// SUFR_HIP_E_UNSUPPORTED (no error text) when more suffixes are affected than the whole-text sort takes or the context allows
+// (pl.exc_max_affected()): the caller builds the text again with the general code table.
 // ---------------------------------------------------------------------------------------------------------------
-static constexpr uint64_t EXC_MAX_AFFECTED = (uint64_t)1 << 22;
+static constexpr uint64_t EXC_MAX_AFFECTED = Pipeline::EXC_MAX_AFFECTED_DEFAULT;     // what the list and the whole-text sort are sized for
 
 int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa, const uint32_t* blcp, uint32_t s,
                  const uint32_t* d_exc, uint32_t E, uint32_t* out_sa, uint32_t* out_lcp, uint64_t out_cap, uint64_t* affected_out,
@@ -563,6 +569,10 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
     hipStream_t st = pl.stream;
     int rc;
     *affected_out = 0;
+    // the limit of all three comparisons below (sufr_hip_set_exc_max_affected: EXC_MAX_AFFECTED or less; the buffers keep their sizes);
+    // the one that gives up says so in last_exc_retry
+    const uint64_t max_affected = pl.exc_max_affected();
+    auto give_up = [&pl](uint32_t way) { if (way > pl.last_exc_retry) pl.last_exc_retry = way; return SUFR_HIP_E_UNSUPPORTED; };
     const uint32_t nblk = (s + EXC_BLK - 1) / EXC_BLK;
     const size_t nwords = (size_t)nblk * (EXC_BLK / 64);
     if ((rc = pl.ensure(pl.exc_bits, nwords * 8 + 64)) || (rc = pl.ensure(pl.exc_blk, ((size_t)nblk + 4) * 4)) ||
@@ -588,7 +598,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
         std::vector<unsigned long long> ro((size_t)E + 1, 0ull);
         for (uint32_t e = 0; e < E; e++) ro[e + 1] = ro[e] + (hp[e] <= he[e] ? (unsigned long long)he[e] - hp[e] + 1ull : 0ull);
         const unsigned long long T = ro[E];
-        if (T > ((unsigned long long)EXC_MAX_AFFECTED << 4)) return SUFR_HIP_E_UNSUPPORTED;       // (ranges of positions: most start a suffix)
+        if (T > ((unsigned long long)max_affected << 4)) return give_up(1);       // (ranges of positions: most start a suffix; the text still holds 'N')
         if (T) {
             if (hipMemcpyAsync(pl.exc_roff.p, ro.data(), ((size_t)E + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess) { pl.set_error("copy failed"); return SUFR_HIP_E_HIP; }
             hipLaunchKernelGGL(k_exc_expand, dim3((uint32_t)((T + 255) / 256)), dim3(256), 0, st, XB, d_exc, E, (const uint32_t*)pl.exc_pmin.p,
@@ -616,7 +626,8 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
     unsigned long long tot = 0;
     if (pl.read_at_sync(&tot, pl.sc(Pipeline::SC_SCANTOTAL), 8) != hipSuccess || pl.sync_reads() != hipSuccess) { pl.set_error("marking the affected suffixes failed"); return SUFR_HIP_E_HIP; }
     const uint64_t A_out = tot;                                            // ranks taken out of the arrays
-    if (A_out > EXC_MAX_AFFECTED) return SUFR_HIP_E_UNSUPPORTED;
+    pl.last_exc_taken = A_out;
+    if (A_out > max_affected) return give_up(2);
     ExcText X;
     X.t = d_text; X.n = n; X.rt = pl.rtab; X.exc = d_exc; X.E = E; X.cap = shard.cap;
     uint64_t A = A_out;                                                    // suffixes placed by whole-text comparison
@@ -632,7 +643,7 @@ int exc_reinsert(Pipeline& pl, uint8_t* d_text, uint64_t n, const uint32_t* bsa,
         unsigned long long cnt = 0;
         if (pl.read_at_sync(&cnt, pl.sc(Pipeline::SC_TMP1), 8) != hipSuccess || pl.sync_reads() != hipSuccess) { pl.set_error("re-sharding the affected suffixes failed"); return SUFR_HIP_E_HIP; }
         A = (uint32_t)cnt;
-        if (A > EXC_MAX_AFFECTED) return SUFR_HIP_E_UNSUPPORTED;
+        if (A > max_affected) return give_up(3);
         list = list2;
     }
     *affected_out = A;

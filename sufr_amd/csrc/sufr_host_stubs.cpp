@@ -57,6 +57,9 @@ uint64_t sufr_hip_window_repairs(const sufr_hip_ctx*) { return 0; }
 int sufr_hip_set_overlap_min(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
 int sufr_hip_overlapped(const sufr_hip_ctx*) { return 0; }
 uint64_t sufr_hip_doublings(const sufr_hip_ctx*) { return 0; }
+int sufr_hip_set_exc_max_affected(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
+int sufr_hip_exc_retry(const sufr_hip_ctx*) { return 0; }
+uint64_t sufr_hip_exc_taken(const sufr_hip_ctx*) { return 0; }
 int sufr_hip_sort_device_u32(sufr_hip_ctx* ctx, const void*, uint64_t, uint32_t, uint64_t, const char*, uint64_t, uint64_t,
                              uint32_t, uint32_t, void*, void*, uint64_t, uint64_t*, sufr_hip_stats*) { return no_device(ctx); }
 int sufr_hip_sort_device_u64(sufr_hip_ctx* ctx, const void*, uint64_t, uint32_t, uint64_t, const char*, uint64_t, uint64_t,

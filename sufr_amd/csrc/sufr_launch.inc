@@ -96,6 +96,12 @@ public:
     uint32_t exc_pending = 0;      // listed bytes that are still 'N' in `text` (put back by exc_reinsert, or on the way out of the build)
     bool mql_fast_ok = true;       // probes: off = a capped build is the exact build + apply_max_query_len (rounds 1-5)
     bool exc_disable = false;      // this build takes the general code table whatever the text holds (the retry of a build that listed too much)
+    static constexpr uint64_t EXC_MAX_AFFECTED_DEFAULT = (uint64_t)1 << 22;     // affected suffixes the whole-text sort and its buffers take
+    uint64_t opt_exc_max_affected = 0;         // ... from which a build goes to the general code table (sufr_hip_set_exc_max_affected; 0: the default)
+    uint64_t exc_max_affected() const { return opt_exc_max_affected ? opt_exc_max_affected : EXC_MAX_AFFECTED_DEFAULT; }
+    uint32_t last_exc_retry = 0;   // why the last build took that retry: 0 it did not, 1 / 2 / 3 the comparison of exc_reinsert that gave up (windowed builds: the largest)
+    uint64_t last_exc_taken = 0;   // ranks the last exc_reinsert took out of the arrays (also when it then gave up)
+    DevBuf exc_all_sa, exc_all_lcp;            // the whole arrays of a sharded build's retry (retry_whole_text)
     bool no_exceptions = false;    // probes: every byte outside the table sends the build to the general code table (round 5)
     std::vector<uint32_t> rawtot_host, valshost;
     uint16_t h_lut[256];                       // code table of the build (host copy: uploaded asynchronously)
@@ -366,7 +372,7 @@ public:
                          &idxB, &recA, &recB, &headsA, &headsB, &sizes, &starts, &partials, &sa32, &lcp32,
                          &tilefirst, &runends, &tileany, &nexttile, &nextblk, &depthA, &depthB, &period, &remapbuf, &flagsbuf, &packedbuf, &wmaskbuf, &wcntbuf, &recoff, &runoff, &wlflag, &wlhead, &wloff, &candbuf, &keepbuf, &plancnt, &fixbuf,
                          &rg_misc, &rg_blk, &rg_blkoff, &rg_rs, &rg_rl, &rg_E, &rg_L, &rg_V, &rg_tab[0], &rg_tab[1], &rg_off[0], &rg_off[1], &rg_long[0], &rg_long[1], &rg_tmax[0], &rg_tmax[1], &rg_hist, &rg_depth,
-                         &exc_pos, &exc_byte, &exc_sorted, &exc_sa, &exc_lcp, &exc_bits, &exc_blk, &exc_off, &exc_list, &exc_list2, &exc_pmin, &exc_roff,
+                         &exc_pos, &exc_byte, &exc_sorted, &exc_sa, &exc_lcp, &exc_bits, &exc_blk, &exc_off, &exc_list, &exc_list2, &exc_pmin, &exc_roff, &exc_all_sa, &exc_all_lcp,
                          &cumbuf, &dmapbuf, &rawtab, &presbuf, &rawtot, &valsbuf, &startbuf, &grouptab, &gcur, &leafcnt, &leafoff, &leafbase, &leafcur, &bigflag, &bigoff,
                          &segst[0], &segst[1], &segsz[0], &segsz[1], &tunits, &upre, &tdesc, &wunits, &wpre, &wdesc, &wslow,
                          &optA, &optB, &optC, &optD, &optE, &stitchoffs, &wideoffs,
@@ -392,7 +398,7 @@ public:
         if (helper) helper->release_build_arrays(false);
         (void)hipSetDevice(device);
         if (also_text) { release(text); resident_text_len = 0; }
-        DevBuf* big[] = {&recA, &recB, &keyA, &keyB, &idxA, &idxB, &packedbuf, &runends, &startbuf, &wmaskbuf, &wcntbuf, &fixbuf, &exc_sa, &exc_lcp, &exc_bits,
+        DevBuf* big[] = {&recA, &recB, &keyA, &keyB, &idxA, &idxB, &packedbuf, &runends, &startbuf, &wmaskbuf, &wcntbuf, &fixbuf, &exc_sa, &exc_lcp, &exc_bits, &exc_all_sa, &exc_all_lcp,
                          &headsA, &headsB, &rankbuf, &dposbuf, &deferbuf, &unresbuf, &posbitsbuf, &depthA, &depthB, &period,
                          &recoff, &runoff, &candbuf, &keepbuf, &optA, &optB, &optC, &optD, &optE};
         for (auto* b : big) if (b->cap >= ((size_t)16 << 20)) release(*b);
@@ -1739,6 +1745,7 @@ public:
     {
         last_overlapped = 0; last_doublings = 0; dbl_entries = 0;
         if (helper) helper->dbl_entries = 0;
+        if (!exc_disable) { last_exc_retry = 0; last_exc_taken = 0; }          // (the retry of a build keeps what that build recorded)
         const int rc = sort_build(d_in, n, flags, shard_index, num_shards, d_sa, d_lcp, cap, num_suffixes_out, st_out);
         before_doubling = nullptr;
         last_doublings = dbl_entries + (helper ? helper->dbl_entries : 0);       // (both chains: the helper has been joined)
@@ -2406,11 +2413,20 @@ public:
         rc2 = exc_reinsert(*this, B.d_text, B.n, bsa, blcp, m, (const uint32_t*)exc_sorted.p, nexc, B.caller_sa, B.caller_lcp, B.cap, &affected, esh, &s_final);
         HIP_TRY(sync_reads());                              // (ep: a host vector)
         if (rc2 == SUFR_HIP_E_UNSUPPORTED && err.empty()) {
-            // more suffixes looked at the listed bytes than the whole-text sort takes: the general code table, from the caller's text
-            exc_disable = true;
-            rc2 = sort_device_u32(B.d_in_caller, B.n, B.flags, B.shard_index, B.num_shards, B.caller_sa, B.caller_lcp, B.cap, B.num_suffixes_out, B.st_out);
-            exc_disable = false;
+            // more suffixes looked at the listed bytes than the whole-text sort takes (or than sufr_hip_set_exc_max_affected
+            // allows): the general code table, from the caller's text.  exc_reinsert may have given up before it put the listed
+            // bytes back: they go back here, so that nothing is pending while the text is built again.
             rebuilt = true;
+            if (exc_pending) {
+                hipLaunchKernelGGL(k_exc_restore, dim3((exc_pending + 255) / 256), dim3(256), 0, stream, B.d_text,
+                                   (const uint32_t*)exc_pos.p, (const uint8_t*)exc_byte.p, exc_pending);
+                HIP_TRY(hipGetLastError());
+                exc_pending = 0;
+            }
+            if (B.num_shards > 1) return retry_whole_text(B);
+            exc_disable = true;
+            rc2 = sort_device_u32(B.d_in_caller, B.n, B.flags, 0, 1, B.caller_sa, B.caller_lcp, B.cap, B.num_suffixes_out, B.st_out);
+            exc_disable = false;
             return rc2;
         }
         if (rc2 == SUFR_HIP_E_CAPACITY && B.num_suffixes_out) *B.num_suffixes_out = s_final;      // (what the call needs)
@@ -2422,6 +2438,75 @@ public:
         }
         B.mql_count = (uint32_t)s_final;
         HIP_TRY(hipEventRecord(ev[10], stream));
+        return 0;
+    }
+
+    // ---- the retry of a SHARDED build.  This rank's first-digit range was chosen on the 3-bit digits of the text with 'N' for the
+    // listed bytes, and the ranks that do not retry keep the suffixes whose TRUE first D bytes lie in their ranges (exc_true_in).
+    // The general code table has other digits (4- or 5-bit codes, fewer characters), so a range chosen on its histogram would
+    // not fit between the neighbours': suffixes would be lost or repeated.  Instead the rank builds the WHOLE text with the
+    // general table as one shard into arrays of its own, and hands out the ranks whose true first D bytes lie in
+    // [raw_lo, raw_hi) -- contiguous, because the arrays are in the order of the bytes (a capped build: of its first L >= 8 > D
+    // symbols); both ends by binary search, a probe = one rank and the D bytes at it.  Cost: the time of a one-GPU build of the
+    // text and two arrays of all its suffixes on this rank, for a text that the whole-text sort cannot take.
+    static uint64_t true_prefix_of_digit(uint32_t raw, int D)              // exc_digit_prefix (sufr_exc.inc) on the host
+    {
+        static const uint8_t bytes[8] = {0, '$', '%', 'A', 'C', 'G', 'N', 'T'};
+        uint64_t v = 0;
+        for (int i = D - 1; i >= 0; i--) { const uint32_t c = (raw >> (3 * i)) & 7u; v = (v << 9) | (c ? (uint64_t)bytes[c] + 1u : 0u); }
+        return v;
+    }
+    // first rank of sa[0, s) whose suffix has D-byte prefix (9 bits a byte, byte + 1, 0 past the text: exc_true_prefix) >= bound
+    int first_rank_at_or_above(const uint32_t* sa, uint64_t s, uint64_t n, int D, uint64_t bound, uint64_t& rank)
+    {
+        uint64_t lo = 0, hi = s;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            uint32_t p = 0;
+            uint8_t b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            HIP_TRY(hipMemcpyAsync(&p, sa + mid, 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (p >= n) { set_error("a suffix array entry past the text"); return SUFR_HIP_E_HIP; }
+            const uint64_t have = n - p < (uint64_t)D ? n - p : (uint64_t)D;
+            HIP_TRY(hipMemcpyAsync(b, (const uint8_t*)text.p + p, (size_t)have, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            uint64_t v = 0;
+            for (int i = 0; i < D; i++) v = (v << 9) | ((uint64_t)i < have ? (uint64_t)b[i] + 1u : 0u);
+            if (v < bound) lo = mid + 1; else hi = mid;
+        }
+        rank = lo;
+        return 0;
+    }
+    int retry_whole_text(Build& B)
+    {
+        const int D = B.mbits / B.kp.b;
+        const uint64_t all = B.eligible_total;             // ('N' starts a suffix iff the byte it stands for does: the count is the true text's)
+        int rc;
+        if (D < 1 || D > 7) { set_error("first digit of " + std::to_string(D) + " characters"); return SUFR_HIP_E_UNSUPPORTED; }
+        if ((rc = ensure(exc_all_sa, all * 4 + 64)) || (rc = ensure(exc_all_lcp, all * 4 + 64))) return rc;
+        const uint32_t* const wsa = (const uint32_t*)exc_all_sa.p; const uint32_t* const wlcp = (const uint32_t*)exc_all_lcp.p;
+        uint64_t s_all = 0;
+        sufr_hip_stats wst;
+        memset(&wst, 0, sizeof wst);
+        exc_disable = true;
+        rc = sort_device_u32(B.d_in_caller, B.n, B.flags, 0, 1, (uint32_t*)exc_all_sa.p, (uint32_t*)exc_all_lcp.p, all, &s_all, &wst);
+        exc_disable = false;
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));
+        uint64_t first = 0, last = s_all;
+        if (B.raw_lo && (rc = first_rank_at_or_above(wsa, s_all, B.n, D, true_prefix_of_digit(B.raw_lo, D), first))) return rc;
+        if (!(B.raw_hi >> (3 * D)) && (rc = first_rank_at_or_above(wsa, s_all, B.n, D, true_prefix_of_digit(B.raw_hi, D), last))) return rc;
+        const uint64_t mine = last > first ? last - first : 0;
+        if (debug) fprintf(stderr, "[sufr_hip debug] retry of shard %u of %u: ranks [%llu, %llu) of %llu\n", B.shard_index, B.num_shards,
+                           (unsigned long long)first, (unsigned long long)last, (unsigned long long)s_all);
+        if (B.num_suffixes_out) *B.num_suffixes_out = mine;
+        wst.num_suffixes = mine; wst.top_lo = B.st.top_lo; wst.top_hi = B.st.top_hi;      // (the shard's own; the rest: the build that made the arrays)
+        if (B.st_out) *B.st_out = wst;
+        if (mine == 0) return 0;
+        if ((rc = check_capacity(mine, B.cap, B.caller_sa, B.caller_lcp))) return rc;
+        HIP_TRY(hipMemcpyAsync(B.caller_sa, wsa + first, mine * 4, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(B.caller_lcp, wlcp + first, mine * 4, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         return 0;
     }
 

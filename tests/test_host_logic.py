@@ -269,3 +269,21 @@ def test_integration_md_names_every_export():
             if name not in text:
                 missing.append(name)
     assert not missing, missing
+
+
+def test_stubbed_exc_limit_answers_no_device(tmp_path):
+    """the host-only build's stubs of the listed-byte retry's limit and getters (sufr_host_stubs.cpp), linked into a plain C
+    client without a sanitizer: the setter answers SUFR_HIP_E_NO_DEVICE for every value, the getters 0"""
+    from pathlib import Path
+    ROOT = Path(__file__).resolve().parent.parent
+    obj = tmp_path / "stubs.o"; client = tmp_path / "stub_client.o"; out = tmp_path / "stub_client"
+    steps = [["g++", "-std=c++17", "-Wall", "-Werror", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-c",
+              str(ROOT / "sufr_amd" / "csrc" / "sufr_host_stubs.cpp"), "-o", str(obj)],
+             ["gcc", "-std=c99", "-Wall", "-Werror", "-O1", "-I", str(ROOT / "include"), "-c", str(ROOT / "tests" / "c_abi" / "stub_client.c"), "-o", str(client)],
+             ["g++", str(client), str(obj), "-o", str(out)]]
+    for cmd in steps:
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip() == "stubs: no device -2, exc_retry 0, exc_taken 0"
