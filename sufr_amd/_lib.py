@@ -110,6 +110,18 @@ EDIT_BOTH_STRANDS = 0x1
 EDIT_LOCAL_MINIMA = 0x2
 # every symbol include/sufr_align.h declares
 ALIGN_EXPORTS = ["sufr_file_edit_trace", "sufr_hip_edit_trace_device", "sufr_hip_edit_trace", "sufr_hip_set_trace_scratch"]
+# every symbol include/sufr_kmer.h declares
+KMER_EXPORTS = ["sufr_file_kmers", "sufr_file_unique_lengths", "sufr_hip_kmers_device", "sufr_hip_unique_lengths_device",
+                "sufr_hip_set_kmer_tile"]
+KMER_BY_POSITION = 0x1
+
+
+class KmerStats(C.Structure):
+    """sufr_kmer_stats"""
+    _fields_ = [("whole", C.c_uint64), ("distinct", C.c_uint64), ("unique", C.c_uint64), ("max_count", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class FileMeta(C.Structure):
@@ -263,6 +275,13 @@ def lib() -> C.CDLL:
     L.sufr_hip_edit_trace.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
     L.sufr_hip_edit_trace.restype = C.c_int
     L.sufr_hip_set_trace_scratch.argtypes = [vp, u64]; L.sufr_hip_set_trace_scratch.restype = C.c_int
+    # include/sufr_kmer.h
+    L.sufr_file_kmers.argtypes = [vp, u64, u32, u64, vp, vp, C.POINTER(KmerStats), C.c_int]; L.sufr_file_kmers.restype = C.c_int
+    L.sufr_file_unique_lengths.argtypes = [vp, u32, vp, C.c_int]; L.sufr_file_unique_lengths.restype = C.c_int
+    L.sufr_hip_kmers_device.argtypes = [vp, vp, vp, vp, u64, u64, u32, u64, vp, vp, C.POINTER(KmerStats)]
+    L.sufr_hip_kmers_device.restype = C.c_int
+    L.sufr_hip_unique_lengths_device.argtypes = [vp, vp, vp, vp, u64, u32, vp]; L.sufr_hip_unique_lengths_device.restype = C.c_int
+    L.sufr_hip_set_kmer_tile.argtypes = [vp, u64]; L.sufr_hip_set_kmer_tile.restype = C.c_int
     _lib = L
     return L
 
@@ -307,6 +326,11 @@ class Context:
     def set_trace_scratch(self, nbytes: int = 0):
         """Alignment traceback: device bytes the rows of a chunk of records may take (sufr_hip_set_trace_scratch; 0: the default)."""
         self.check(lib().sufr_hip_set_trace_scratch(self._h, nbytes))
+
+    def set_kmer_tile(self, ranks: int = 0):
+        """k-mer counts: ranks one workgroup folds at a time (sufr_hip_set_kmer_tile; 0: the default).  Rounded up to 256 and
+        held to 16384; it changes no result."""
+        self.check(lib().sufr_hip_set_kmer_tile(self._h, ranks))
 
     @property
     def window_repairs(self) -> int:

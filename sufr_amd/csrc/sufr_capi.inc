@@ -11,6 +11,9 @@ struct sufr_hip_ctx {
     sufr::DevBuf ecnt, ekeys, ekeys2, ehist;  // k-difference (sufr_edit.inc): ends per candidate, the two key buffers of the sort, its digit counts
     sufr::DevBuf tsc, trows, tmisc;    // alignment traceback (sufr_trace.inc): the scalars of a call, the rows of a chunk, its scan sums and run counts
     uint64_t trace_scratch = 0;        // sufr_hip_set_trace_scratch: bytes of row storage (0: the default)
+    sufr::DevBuf kbits, ksum, kstarts; // k-mer counts (sufr_kmer.inc): head / whole words, tile summaries and carries and stats, sequence starts
+    std::vector<uint64_t> kmer_starts; // the sequence starts kstarts holds
+    uint32_t kmer_tile = 0;            // sufr_hip_set_kmer_tile: ranks per tile (0: the default)
     bool wide(uint64_t n) const { return n >= sufr::SUFR_MAX_TEXT_LEN || (wide_window && n > wide_window); }
 };
 
@@ -216,7 +219,8 @@ void sufr_hip_destroy(sufr_hip_ctx* ctx)
     (void)hipSetDevice(ctx->pl.device);
     for (sufr::DevBuf* b : {&ctx->wtext, &ctx->wsa, &ctx->wlcp, &ctx->wblk, &ctx->mtmp, &ctx->mpoff, &ctx->mbytes,
                             &ctx->xq, &ctx->xoff, &ctx->xlo, &ctx->xhi, &ctx->xcand, &ctx->xsum,
-                            &ctx->ecnt, &ctx->ekeys, &ctx->ekeys2, &ctx->ehist, &ctx->tsc, &ctx->trows, &ctx->tmisc}) ctx->pl.release(*b);
+                            &ctx->ecnt, &ctx->ekeys, &ctx->ekeys2, &ctx->ehist, &ctx->tsc, &ctx->trows, &ctx->tmisc,
+                            &ctx->kbits, &ctx->ksum, &ctx->kstarts}) ctx->pl.release(*b);
     ctx->pl.destroy();
     delete ctx;
 }

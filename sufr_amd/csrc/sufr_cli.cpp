@@ -24,6 +24,9 @@
 #include "../../include/sufr_approx.h"
 #include "../../include/sufr_edit.h"
 #include "../../include/sufr_align.h"
+#include "../../include/sufr_kmer.h"
+
+#include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <fstream>
@@ -75,6 +78,13 @@ int usage(FILE* f)
             "                                       [-d|--edits N (2)] [--max-occ N (0: no limit)] [-b|--both-strands]\n"
             "                                       [-l|--local-minima] [-a|--abs] [-q|--reads FASTA/FASTQ] [-o OUT]\n"
             "                                       [-c|--cigar: two more columns, the start (as the end) and the CIGAR (= X I D)]\n"
+            "  kmers|km     <SUFR>                  k-mer spectrum of the indexed text from its LCP array: one line per non-empty bin,\n"
+            "                                       count  kmers (the last bin as >=BINS), then # whole, # distinct, # unique, # max_count\n"
+            "                                       -k K [-b|--bins BINS (256)] [--device ID: on that GPU; otherwise on the host]\n"
+            "                                       [--occ FILE: the count of the k-mer at every text position] [--unique FILE: the length\n"
+            "                                       at which the substring at every text position becomes unique]; both files hold one raw\n"
+            "                                       little-endian entry of the index width (4 or 8 bytes) per text position, 0 where the\n"
+            "                                       position is not indexed or the k-mer / substring runs over the end of its sequence\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -727,6 +737,100 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     return cmd_summarize(a);
 }
 
+// sufr kmers: the spectrum to standard output (or -o), the by-position arrays to --occ / --unique
+int run_kmers(int argc, char** argv, int first, int threads)
+{
+    std::string file, output, occ_path, uniq_path;
+    uint64_t k = 0, bins = 256;
+    bool have_k = false;
+    int device = -1;
+    auto need = [&](int& i, const char* opt) -> const char* {
+        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
+        return argv[++i];
+    };
+    for (int i = first; i < argc; i++) {
+        const std::string s = argv[i];
+        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
+        else if (s == "-k") { k = strtoull(need(i, "-k"), nullptr, 10); have_k = true; }
+        else if (s == "-b" || s == "--bins") bins = strtoull(need(i, "-b"), nullptr, 10);
+        else if (s == "--device") device = atoi(need(i, "--device"));
+        else if (s == "--occ") occ_path = need(i, "--occ");
+        else if (s == "--unique") uniq_path = need(i, "--unique");
+        else if (s == "-o" || s == "--output") output = need(i, "-o");
+        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+        else if (file.empty()) file = s;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+    }
+    if (file.empty() || !have_k) { fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n", file.empty() ? "<SUFR>" : "-k <K>"); return 2; }
+    sufr_file* f = open_or_die(file);
+    sufr_file_meta m;
+    sufr_file_metadata(f, &m);
+    const uint64_t w = (uint64_t)m.index_width, n = m.text_len, s = m.len_suffixes;
+    std::vector<uint64_t> hist(bins ? bins : 1, 0);
+    std::vector<uint8_t> occ(occ_path.empty() ? 0 : n * w + 8), uniq(uniq_path.empty() ? 0 : n * w + 8);
+    sufr_kmer_stats st{0, 0, 0, 0};
+    int rc = 0;
+    std::string err;
+    if (device < 0) {
+        rc = sufr_file_kmers(f, k, SUFR_KMER_BY_POSITION, bins, hist.data(), occ_path.empty() ? nullptr : occ.data(), &st, threads);
+        if (!rc && !uniq_path.empty()) rc = sufr_file_unique_lengths(f, SUFR_KMER_BY_POSITION, uniq.data(), threads);
+    } else {
+        sufr_hip_ctx* ctx = sufr_hip_create(device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
+        sufr_hip_index* ix = nullptr;
+        std::vector<uint64_t> starts(m.num_sequences);
+        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
+        void *d_lcp = nullptr, *d_hist = nullptr, *d_out = nullptr;
+        rc = sufr_hip_index_load(ctx, f, &ix);
+        const bool want_out = !occ_path.empty() || !uniq_path.empty();
+        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess || hipMalloc(&d_hist, hist.size() * 8) != hipSuccess ||
+                    (want_out && hipMalloc(&d_out, n * w + 8) != hipSuccess) ||
+                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
+            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array and the outputs";
+        }
+        if (!rc) rc = sufr_hip_kmers_device(ctx, ix, d_lcp, starts.data(), starts.size(), k, SUFR_KMER_BY_POSITION, bins, d_hist,
+                                            occ_path.empty() ? nullptr : d_out, &st);
+        if (!rc && (hipMemcpy(hist.data(), d_hist, hist.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                    (!occ_path.empty() && n && hipMemcpy(occ.data(), d_out, n * w, hipMemcpyDeviceToHost) != hipSuccess))) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
+        if (!rc && !uniq_path.empty()) {
+            rc = sufr_hip_unique_lengths_device(ctx, ix, d_lcp, starts.data(), starts.size(), SUFR_KMER_BY_POSITION, d_out);
+            if (!rc) rc = sufr_hip_synchronize(ctx);
+            if (!rc && n && hipMemcpy(uniq.data(), d_out, n * w, hipMemcpyDeviceToHost) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
+        }
+        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
+        if (d_lcp) (void)hipFree(d_lcp);
+        if (d_hist) (void)hipFree(d_hist);
+        if (d_out) (void)hipFree(d_out);
+        if (ix) sufr_hip_index_free(ix);
+        sufr_hip_destroy(ctx);
+    }
+    sufr_file_close(f);
+    if (rc) {
+        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "kmers does not support files built with a seed mask, and a file built with a max query length only up to that k (no --unique)"
+                             : rc == SUFR_HIP_E_INVALID ? "kmers: k and the number of bins must be at least 1" : "kmers failed";
+        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
+        return 1;
+    }
+    OutFile out;
+    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); return 1; }
+    for (uint64_t i = 0; i < bins; i++) {
+        if (!hist[i]) continue;
+        if (i + 1 == bins) fprintf(out.f, ">=%llu\t%llu\n", (unsigned long long)bins, (unsigned long long)hist[i]);
+        else fprintf(out.f, "%llu\t%llu\n", (unsigned long long)(i + 1), (unsigned long long)hist[i]);
+    }
+    fprintf(out.f, "# whole\t%llu\n# distinct\t%llu\n# unique\t%llu\n# max_count\t%llu\n", (unsigned long long)st.whole,
+            (unsigned long long)st.distinct, (unsigned long long)st.unique, (unsigned long long)st.max_count);
+    auto dump = [&](const std::string& path, const std::vector<uint8_t>& a) {
+        if (path.empty()) return true;
+        FILE* fh = fopen(path.c_str(), "wb");
+        const bool ok = fh && fwrite(a.data(), 1, n * w, fh) == n * w;
+        if (fh) fclose(fh);
+        if (!ok) fprintf(stderr, "Error: %s: cannot write\n", path.c_str());
+        return ok;
+    };
+    return dump(occ_path, occ) && dump(uniq_path, uniq) ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -779,6 +883,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "locate" || s == "lo")) return run_query("locate", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "match" || s == "ma")) return run_query("match", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "mems" || s == "me")) return run_query("mems", argc, argv, i + 1, threads);
+        else if (!have_cmd && (s == "kmers" || s == "km")) return run_kmers(argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "edit" || s == "ed")) return run_query("edit", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);

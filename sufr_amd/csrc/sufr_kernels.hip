@@ -3000,3 +3000,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_edit.inc"
 #include "../../include/sufr_align.h"
 #include "sufr_trace.inc"
+#include "../../include/sufr_kmer.h"
+#include "sufr_kmer.inc"

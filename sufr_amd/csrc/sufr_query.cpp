@@ -843,3 +843,140 @@ int sufr_file_edit_trace(const sufr_file* f, const uint8_t* queries, const uint6
 }
 
 }  // extern "C"
+
+// ---- k-mer spectra, occurrence maps and unique lengths (include/sufr_kmer.h) ---------------------
+#include "../../include/sufr_kmer.h"
+#include "sufr_kmer_scan.h"
+
+namespace {
+
+// what both calls refuse, in the order of the device path
+int kmer_args(const sufr_file* f, bool capped)
+{
+    if (!f) return SUFR_HIP_E_INVALID;
+    if (f->meta.seed_mask_len) return SUFR_HIP_E_UNSUPPORTED;
+    if (capped) return SUFR_HIP_E_UNSUPPORTED;
+    return 0;
+}
+
+bool kmer_starts_ok(const sufr_file& f)
+{
+    const std::vector<uint64_t>& st = f.seq_starts;
+    if (st.empty()) return true;
+    bool ok = st[0] == 0;
+    for (size_t i = 0; ok && i < st.size(); i++) ok = st[i] < f.meta.text_len && (i == 0 || st[i] > st[i - 1]);
+    return ok;
+}
+
+void kmer_put(void* out, int width, uint64_t i, uint64_t v)
+{
+    if (width == 4) { const uint32_t x = (uint32_t)v; memcpy((uint8_t*)out + i * 4, &x, 4); }
+    else memcpy((uint8_t*)out + i * 8, &v, 8);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_kmers(const sufr_file* f, uint64_t k, uint32_t flags, uint64_t bins, uint64_t* hist, void* occ, sufr_kmer_stats* stats,
+                    int threads)
+{
+    if (stats) *stats = sufr_kmer_stats{0, 0, 0, 0};
+    if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0 && k > f->meta.max_query_len)) return rc;
+    if (k == 0 || (hist && bins == 0)) return SUFR_HIP_E_INVALID;
+    if (hist) memset(hist, 0, bins * 8);
+    const uint64_t s = f->meta.len_suffixes, n = f->meta.text_len;
+    const int width = f->meta.index_width;
+    const bool by_position = (flags & SUFR_KMER_BY_POSITION) != 0;
+    if (occ && by_position) memset(occ, 0, n * (uint64_t)width);
+    if (!s) return 0;
+    if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
+    const uint64_t* starts = f->seq_starts.data();
+    const uint64_t num = f->seq_starts.size();
+    // pass 1: the whole flags (one bit per rank) and the summary of every chunk; the chunks hold whole words
+    const uint64_t chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk;
+    std::vector<uint64_t> wbits((s + 63) / 64, 0);
+    std::vector<sufr::KmerSum> sums(nchunks);
+    auto head = [&](uint64_t r) { return r == 0 || rdT(f->lcp, width, r) < k; };
+    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
+        sufr::KmerSum run = sufr::kmer_identity();
+        for (uint64_t r0 = b; r0 < e; r0 += 64) {
+            uint64_t H = 0, W = 0;
+            for (uint64_t r = r0; r < e && r < r0 + 64; r++) {
+                if (head(r)) H |= (uint64_t)1 << (r - r0);
+                if (sufr::kmer_whole(starts, num, n, rdT(f->sa, width, r), k)) W |= (uint64_t)1 << (r - r0);
+            }
+            wbits[r0 / 64] = W;
+            run = sufr::kmer_combine(run, sufr::kmer_word_sum(H, W));
+        }
+        sums[b / chunk] = run;
+    });
+    // the carries of the chunks, in both directions
+    std::vector<uint64_t> cin(nchunks), cout(nchunks);
+    sufr::KmerSum run = sufr::kmer_identity();
+    for (uint64_t c = 0; c < nchunks; c++) { cin[c] = sufr::kmer_carry_in(run, 0); run = sufr::kmer_combine(run, sums[c]); }
+    run = sufr::kmer_identity();
+    for (uint64_t c = nchunks; c > 0; c--) { cout[c - 1] = sufr::kmer_carry_out(run, 0); run = sufr::kmer_combine(sums[c - 1], run); }
+    // pass 2: every chunk walks its intervals; an interval is credited by the chunk that holds its head
+    std::mutex mu;
+    sufr_kmer_stats total{0, 0, 0, 0};
+    const uint64_t private_bins = hist ? (bins < 4096 ? bins : 4096) : 0;
+    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
+        const uint64_t c = b / chunk;
+        std::vector<uint64_t> mine(private_bins, 0), big;
+        sufr_kmer_stats st{0, 0, 0, 0};
+        auto whole = [&](uint64_t r) { return (wbits[r / 64] >> (r & 63)) & 1; };
+        uint64_t a = b;                                   // start of the interval piece being walked
+        bool headed = head(b);                            // ... and whether its head is in this chunk
+        while (a < e) {
+            uint64_t z = a + 1, cnt = whole(a);
+            while (z < e && !head(z)) { cnt += whole(z); z++; }
+            uint64_t tot = cnt;
+            if (!headed) tot += cin[c];
+            if (z == e) tot += cout[c];
+            if (occ) for (uint64_t r = a; r < z; r++) {
+                if (!by_position) kmer_put(occ, width, r, whole(r) ? tot : 0);
+                else if (whole(r)) kmer_put(occ, width, rdT(f->sa, width, r), tot);
+            }
+            if (headed && tot) {
+                st.whole += tot; st.distinct++; st.unique += tot == 1;
+                if (tot > st.max_count) st.max_count = tot;
+                const uint64_t bin = hist ? sufr::kmer_bin(tot, bins) : 0;
+                if (hist && bin < private_bins) mine[bin]++; else if (hist) big.push_back(bin);
+            }
+            a = z; headed = true;
+        }
+        std::lock_guard<std::mutex> g(mu);
+        total.whole += st.whole; total.distinct += st.distinct; total.unique += st.unique;
+        if (st.max_count > total.max_count) total.max_count = st.max_count;
+        for (uint64_t i = 0; i < private_bins; i++) hist[i] += mine[i];
+        for (const uint64_t bin : big) hist[bin]++;
+    });
+    if (stats) *stats = total;
+    return 0;
+}
+
+int sufr_file_unique_lengths(const sufr_file* f, uint32_t flags, void* out, int threads)
+{
+    if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0)) return rc;
+    const uint64_t s = f->meta.len_suffixes, n = f->meta.text_len;
+    const int width = f->meta.index_width;
+    const bool by_position = (flags & SUFR_KMER_BY_POSITION) != 0;
+    if (by_position && out) memset(out, 0, n * (uint64_t)width);
+    if (!s) return 0;
+    if (!kmer_starts_ok(*f) || !out) return SUFR_HIP_E_INVALID;
+    const uint64_t* starts = f->seq_starts.data();
+    const uint64_t num = f->seq_starts.size();
+    parallel_chunks(s, (uint64_t)1 << 16, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t r = b; r < e; r++) {
+            const uint64_t x = rdT(f->lcp, width, r), y = r + 1 < s ? rdT(f->lcp, width, r + 1) : 0, p = rdT(f->sa, width, r);
+            const uint64_t u = 1 + (x > y ? x : y);
+            const uint64_t v = sufr::kmer_whole(starts, num, n, p, u) ? u : 0;
+            if (!by_position) kmer_put(out, width, r, v);
+            else if (v) kmer_put(out, width, p, v);
+        }
+    });
+    return 0;
+}
+
+}  // extern "C"

@@ -219,6 +219,12 @@ def _file_error(fn: str, noun: str):
     return error
 
 
+def _kmer_error(fn: str, rc: int) -> SufrHipError:
+    msg = {-6: "files built with a seed mask are not supported, and a build with max_query_len has its LCP capped there",
+           -1: "invalid argument (k and bins must be at least 1, the sequence starts must ascend from 0)"}.get(rc, "failed")
+    return SufrHipError(rc, f"{fn}: " + msg)
+
+
 def _as_bytes(q) -> bytes:
     return q.encode() if isinstance(q, str) else bytes(q)
 
@@ -498,6 +504,39 @@ class SufrFile:
         recs = self.edit_arrays(qb, off, max_edits, max_occ, both_strands, local_minima, threads=threads)
         return _align_hits(len(off) - 1, recs, self.edit_trace_arrays(qb, off, *recs, threads=threads))
 
+    # -- k-mer spectra, occurrence maps, unique lengths (include/sufr_kmer.h) -------------------------------------------
+    def _index_dtype(self):
+        return np.uint32 if self.index_width == 4 else np.uint64
+
+    def kmers(self, k: int, bins: int = 256, occ: Optional[str] = None, threads: int = 0):
+        """(hist, stats, occ) of the k-mers at the indexed positions: hist[i] distinct k-mers of count i + 1 (the last bin:
+        `bins` and more), stats a dict of whole / distinct / unique / max_count, occ None or, with occ="rank" / "position",
+        the count of the k-mer at every rank (parallel to the suffix array) or text position (0 where not indexed)."""
+        from ._lib import KMER_BY_POSITION, KmerStats
+        if occ not in (None, "rank", "position"):
+            raise ValueError('occ is None, "rank" or "position"')
+        hist = np.zeros(max(bins, 1), dtype=np.uint64)
+        st = KmerStats()
+        out = None if occ is None else np.zeros(max(self.text_len if occ == "position" else self.len_suffixes, 1), dtype=self._index_dtype())
+        rc = lib().sufr_file_kmers(self._h, k, KMER_BY_POSITION if occ == "position" else 0, bins, hist.ctypes.data,
+                                   out.ctypes.data if out is not None else None, C.byref(st), threads)
+        if rc != 0:
+            raise _kmer_error("sufr_file_kmers", rc)
+        if out is not None:
+            out = out[:self.text_len if occ == "position" else self.len_suffixes]
+        return hist[:bins], st.as_dict(), out
+
+    def unique_lengths(self, by_position: bool = False, threads: int = 0) -> np.ndarray:
+        """The length at which the substring at every rank (or, by_position, text position) becomes unique: 1 + max(LCP[r],
+        LCP[r + 1]), 0 where that runs over the end of its sequence (and, by position, where nothing is indexed)."""
+        from ._lib import KMER_BY_POSITION
+        count = self.text_len if by_position else self.len_suffixes
+        out = np.zeros(max(count, 1), dtype=self._index_dtype())
+        rc = lib().sufr_file_unique_lengths(self._h, KMER_BY_POSITION if by_position else 0, out.ctypes.data, threads)
+        if rc != 0:
+            raise _kmer_error("sufr_file_unique_lengths", rc)
+        return out[:count]
+
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
 
@@ -597,6 +636,7 @@ class DeviceIndex:
         h = C.c_void_p()
         ctx.check(lib().sufr_hip_index_load(ctx.handle, f._h, C.byref(h)))
         ix = cls(ctx, h)
+        ix.text_len = f.text_len
         ix.index_width = lib().sufr_hip_index_width(h)     # (= f.index_width: the file format's rule)
         return ix
 
@@ -617,6 +657,7 @@ class DeviceIndex:
         ctx.check(lib().sufr_hip_index_wrap(ctx.handle, text.data_ptr(), text.numel(), sa.data_ptr(), sa.numel(), flags,
                                             max_query_len, seed_mask.encode() if seed_mask else None, C.byref(h)))
         ix = cls(ctx, h, keep=(text, sa))
+        ix.text_len = text.numel()
         ix.index_width = lib().sufr_hip_index_width(h)     # 8 iff the array was taken as 64-bit
         assert ix.index_width == (8 if wide else 4)
         return ix
@@ -768,6 +809,47 @@ class DeviceIndex:
         for t in range(len(qi)):
             out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[po[t]:po[t + 1]].copy()))
         return out
+
+    # -- k-mer spectra, occurrence maps, unique lengths (include/sufr_kmer.h) ------------------------------------------
+    def _kmer_inputs(self, lcp, seq_starts):
+        import torch
+        wide = getattr(self, "index_width", 4) == 8
+        if not lcp.is_cuda or lcp.dtype not in ((torch.int64, torch.uint64) if wide else (torch.int32, torch.uint32)):
+            raise ValueError("the LCP array is a CUDA tensor of the index's width")
+        torch.cuda.current_stream(lcp.device).synchronize()
+        st = None if seq_starts is None else np.ascontiguousarray(seq_starts, dtype=np.uint64)
+        return torch.int64 if wide else torch.int32, st, (st.ctypes.data if st is not None and st.size else None), (st.size if st is not None else 0)
+
+    def kmers_device(self, lcp, k: int, bins: int = 256, occ: Optional[str] = None, seq_starts=None):
+        """SufrFile.kmers on the device.  lcp: the LCP array as a torch CUDA tensor of the index's width (s entries);
+        seq_starts: the sequence starts (host integers; None: one sequence).  Returns (hist int64 tensor, stats dict, occ
+        tensor of the index's width or None), complete on return."""
+        import torch
+        from ._lib import KMER_BY_POSITION, KmerStats
+        if occ not in (None, "rank", "position"):
+            raise ValueError('occ is None, "rank" or "position"')
+        dt, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        hist = torch.empty(max(bins, 1), dtype=torch.int64, device=lcp.device)
+        count = None if occ is None else (lcp.numel() if occ == "rank" else self.text_len)
+        out = None if occ is None else torch.empty(max(count, 1), dtype=dt, device=lcp.device)
+        stats = KmerStats()
+        self.ctx.check(lib().sufr_hip_kmers_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, k,
+                                                   KMER_BY_POSITION if occ == "position" else 0, bins, hist.data_ptr(),
+                                                   out.data_ptr() if out is not None else None, C.byref(stats)))
+        self.ctx.synchronize()
+        return hist[:bins], stats.as_dict(), (out[:count] if out is not None else None)
+
+    def unique_lengths_device(self, lcp, by_position: bool = False, seq_starts=None):
+        """SufrFile.unique_lengths on the device: a tensor of the index's width, complete on return."""
+        import torch
+        from ._lib import KMER_BY_POSITION
+        dt, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        count = lcp.numel() if not by_position else self.text_len
+        out = torch.empty(max(count, 1), dtype=dt, device=lcp.device)
+        self.ctx.check(lib().sufr_hip_unique_lengths_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n,
+                                                            KMER_BY_POSITION if by_position else 0, out.data_ptr()))
+        self.ctx.synchronize()
+        return out[:count]
 
     # -- MEMs (include/sufr_mem.h) -----------------------------------------------------------------------------------
     def mems_device(self, qbytes, offsets, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
