@@ -630,6 +630,7 @@ class DeviceIndex:
 
     def __init__(self, ctx: Context, handle, keep=()):
         self.ctx, self._h, self._keep = ctx, handle, keep
+        self.index_width = lib().sufr_hip_index_width(handle)      # 4 or 8: the width of the positions of this handle
 
     @classmethod
     def load(cls, ctx: Context, f: SufrFile) -> "DeviceIndex":
@@ -637,7 +638,7 @@ class DeviceIndex:
         ctx.check(lib().sufr_hip_index_load(ctx.handle, f._h, C.byref(h)))
         ix = cls(ctx, h)
         ix.text_len = f.text_len
-        ix.index_width = lib().sufr_hip_index_width(h)     # (= f.index_width: the file format's rule)
+        assert ix.index_width == f.index_width              # (the file format's rule)
         return ix
 
     @classmethod
@@ -658,7 +659,7 @@ class DeviceIndex:
                                             max_query_len, seed_mask.encode() if seed_mask else None, C.byref(h)))
         ix = cls(ctx, h, keep=(text, sa))
         ix.text_len = text.numel()
-        ix.index_width = lib().sufr_hip_index_width(h)     # 8 iff the array was taken as 64-bit
+        # 8 iff the array was taken as 64-bit
         assert ix.index_width == (8 if wide else 4)
         return ix
 
@@ -707,8 +708,8 @@ class DeviceIndex:
 
     def locate_device(self, lo, hi, max_hits: int = 0, capacity: Optional[int] = None):
         """Positions behind rank ranges that are on the device (torch int64 tensors from search_device): returns
-        (offsets int64[nq + 1], positions int32 holding u32 values); query i owns positions[offsets[i]:offsets[i + 1]],
-        in rank order, at most max_hits of them (0: all)."""
+        (offsets int64[nq + 1], positions); query i owns positions[offsets[i]:offsets[i + 1]], in rank order, at most max_hits
+        of them (0: all).  The positions have the index's width: int32 holding u32 values, or int64 for a 64-bit index."""
         import torch
         nq = lo.numel()
         off = torch.empty(nq + 1, dtype=torch.int64, device=lo.device)
@@ -717,7 +718,7 @@ class DeviceIndex:
         if capacity is None:                                   # size the output from the counts
             cnt = hi - lo
             capacity = int((cnt.clamp(max=max_hits) if max_hits else cnt).sum())
-        pos = torch.empty(max(capacity, 1), dtype=torch.int64 if getattr(self, "index_width", 4) == 8 else torch.int32,
+        pos = torch.empty(max(capacity, 1), dtype=torch.int64 if self.index_width == 8 else torch.int32,
                           device=lo.device)
         self.ctx.check(lib().sufr_hip_locate_batch_device(self.ctx.handle, self._h, lo.data_ptr(), hi.data_ptr(), nq, max_hits,
                                                          off.data_ptr(), pos.data_ptr(), capacity, C.byref(total)))
@@ -725,13 +726,14 @@ class DeviceIndex:
         return off, pos[:total.value]
 
     def locate(self, queries: Sequence, max_query_len: Optional[int] = None, max_hits: int = 0) -> List[np.ndarray]:
-        """Text positions of every query's matches in rank order (uint32 arrays), searched and gathered on the device."""
+        """Text positions of every query's matches in rank order (unsigned arrays of the index's width), searched and gathered
+        on the device."""
         import torch
         qb, off = pack_queries(queries)
         dev = torch.device("cuda", self.ctx.device)
         lo, hi = self.search_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_query_len)
         o, p = self.locate_device(lo, hi, max_hits)
-        o = o.cpu().numpy(); p = p.cpu().numpy().view(np.uint32)
+        o = o.cpu().numpy(); p = p.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
         return [p[o[i]:o[i + 1]] for i in range(len(queries))]
 
     def count(self, queries: Sequence, max_query_len: Optional[int] = None) -> List[CountResult]:
@@ -803,7 +805,7 @@ class DeviceIndex:
         qi, qo, ln, lo, hi = self.smems_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), min_len)
         po, pos = self.locate_device(lo, hi, max_hits)
         po = po.cpu().numpy()
-        pos = pos.cpu().numpy().view(np.uint64 if getattr(self, "index_width", 4) == 8 else np.uint32)
+        pos = pos.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
         qi, qo, ln, lo, hi = (t.cpu().numpy() for t in (qi, qo, ln, lo, hi))
         out: List[List[SmemHit]] = [[] for _ in queries]
         for t in range(len(qi)):
@@ -813,7 +815,7 @@ class DeviceIndex:
     # -- k-mer spectra, occurrence maps, unique lengths (include/sufr_kmer.h) ------------------------------------------
     def _kmer_inputs(self, lcp, seq_starts):
         import torch
-        wide = getattr(self, "index_width", 4) == 8
+        wide = self.index_width == 8
         if not lcp.is_cuda or lcp.dtype not in ((torch.int64, torch.uint64) if wide else (torch.int32, torch.uint32)):
             raise ValueError("the LCP array is a CUDA tensor of the index's width")
         torch.cuda.current_stream(lcp.device).synchronize()

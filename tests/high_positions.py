@@ -1,0 +1,341 @@
+"""Query answers at text positions beyond 2^31 and 2^32 without a multi-gigabyte build (a helper, not a test module).
+
+A suffix array may index only some positions of its text (that is what a --dna build leaves behind, with the bitmap of the
+indexed positions).  So a text can be a long filler of 0x00 that is not indexed, followed by a small indexed region that
+ends in `$` at the end of the text.  Suffix comparisons never look left of a suffix's start and the region is the tail of the
+text, so the order of its suffixes (and their LCPs) is that of the region alone: SA = SA(region) + filler.  Every query answer
+is then translation-invariant: against a twin text of a short filler plus the same region, rank ranges, lengths, distances and
+CIGARs are equal and every text position differs by the same constant.
+
+The precondition is the twin's filler: TWIN_FILLER bytes exceed the longest query (MAX_QUERY) plus 15 edits plus the 8-byte
+loads, so every window, left-extension check and traceback that reaches left of the region sees filler in both texts, never
+the start of the text.  The filler byte is 0x00 because a file hole reads as zeros: on the host the filler is a hole in a
+sparse file that the reader maps, on the device one torch.zeros.
+
+  region()          the 40 000-byte region with its SA and LCP (the oracle's), built once
+  GEOMETRIES        twin, u32_across_2_31, u32_top, u64_across_2_32: filler and index width; the boundary is the region's middle
+  write_sparse()    the version-6 .sufr file of a geometry, the filler never written
+  batch()           the queries, the same for every geometry
+  answers()         every host operation on a SufrFile as a dict of plain lists, text positions shifted back to the twin's
+  compare()         exact equality of two such dicts, the first difference in the message
+  assert_witness_is_not_empty()   records on both sides of the boundary, spans over it, all four CIGAR operations
+"""
+from __future__ import annotations
+
+import functools
+import os
+import struct
+from dataclasses import dataclass
+from types import SimpleNamespace
+
+import numpy as np
+
+from sufr_amd import SufrFile, pack_queries
+
+R = 40_000                      # the region
+MID = R // 2                    # its middle byte: the boundary of every geometry lies here
+TWIN_FILLER = 4096
+MAX_QUERY = 1000
+SEG_LEN, SEG_AT = 1200, (3_000, MID - 600, 30_000)      # the planted segment: before, across and after the middle
+A_RUN = (MID - 3_000, MID - 2_000)                      # 1 000 A ending 2 000 before the middle
+N_RUN = (MID + 5_000, MID + 5_400)                      # 400 N after it: positions that are not indexed
+DELIMS = (10_000, 33_000)                               # one % on each side: three sequences
+SEQ_NAMES = ("s0", "s1", "s2")
+SPARSE_LIMIT = 64 << 20                                 # more blocks than this: the filesystem has no holes
+assert TWIN_FILLER > MAX_QUERY + 15 + 8
+
+
+@dataclass(frozen=True)
+class Geometry:
+    name: str
+    filler: int
+    width: int
+
+    @property
+    def n(self) -> int:
+        return self.filler + R
+
+    @property
+    def shift(self) -> int:                             # what a text position is ahead of the twin's
+        return self.filler - TWIN_FILLER
+
+    @property
+    def boundary(self) -> int:
+        return self.filler + MID
+
+    @property
+    def seq_starts(self):
+        return [0, self.filler + DELIMS[0] + 1, self.filler + DELIMS[1] + 1]
+
+
+GEOMETRIES = {g.name: g for g in (
+    Geometry("twin", TWIN_FILLER, 4),
+    Geometry("u32_across_2_31", (1 << 31) - MID, 4),            # n = 2^31 + R/2: positions that are negative in int32
+    Geometry("u32_top", (1 << 32) - 2 - R, 4),                  # n = 2^32 - 2: the largest 32-bit text
+    Geometry("u64_across_2_32", (1 << 32) - MID, 8),            # n = 2^32 + R/2
+)}
+LARGE = [name for name in GEOMETRIES if name != "twin"]
+WIDTH_FLIP = Geometry("first_64_bit_length", (1 << 32) - 1 - R, 8)   # n = 2^32 - 1: the shortest text with 64-bit arrays
+assert GEOMETRIES["u32_across_2_31"].boundary == 1 << 31 and GEOMETRIES["u64_across_2_32"].boundary == 1 << 32
+assert GEOMETRIES["u32_top"].n == (1 << 32) - 2 and GEOMETRIES["twin"].n == 44_096
+
+
+@functools.lru_cache(maxsize=None)
+def region(seed: int = 20):
+    """text (uint8 array, R bytes ending in $), sa, lcp (uint64 arrays of the indexed positions: A C G T $), built once"""
+    from oracle_helper import Oracle
+    rng = np.random.default_rng(seed)
+    t = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, R)].copy()
+    seg = t[SEG_AT[0]:SEG_AT[0] + SEG_LEN].copy()
+    for at in SEG_AT:
+        t[at:at + SEG_LEN] = seg
+    t[A_RUN[0]:A_RUN[1]] = ord("A")
+    t[N_RUN[0]:N_RUN[1]] = ord("N")
+    t[list(DELIMS)] = ord("%")
+    t[-1] = ord("$")
+    assert SEG_AT[1] < MID < SEG_AT[1] + SEG_LEN and A_RUN[1] == MID - 2000 and DELIMS[0] < MID < DELIMS[1] and N_RUN[0] > MID
+    sa, lcp, _ = Oracle().build(t, is_dna=True)
+    assert sa.size == R - (N_RUN[1] - N_RUN[0]) - len(DELIMS)
+    t.setflags(write=False)
+    return SimpleNamespace(text=t, sa=sa.astype(np.uint64), lcp=lcp.astype(np.uint64))
+
+
+def arrays(geo: Geometry, reg=None):
+    """SA + filler and LCP at the geometry's width (unsigned)"""
+    reg = reg or region()
+    dt = np.uint32 if geo.width == 4 else np.uint64
+    sa = reg.sa + np.uint64(geo.filler)
+    assert int(sa.max()) == geo.n - 1 and (geo.width == 8 or int(sa.max()) < 1 << 32)
+    return sa.astype(dt), reg.lcp.astype(dt)
+
+
+def write_sparse(path, geo: Geometry, indexed: bool = True) -> int:
+    """The version-6 file of the geometry as sufr_file_open parses it: the 60-byte header, the sequence starts at the index
+    width, the mask length, text, SA, LCP, names.  Header, region, arrays and names are written at their offsets; the filler
+    stays a hole.  indexed=False: the header and the names only (no suffixes).  Returns the bytes of disk blocks in use."""
+    W = geo.width
+    dt = "<u4" if W == 4 else "<u8"
+    sa, lcp = arrays(geo) if indexed else (np.zeros(0, dtype=dt), np.zeros(0, dtype=dt))
+    starts = np.asarray(geo.seq_starts, dtype=dt)
+    text_pos = 60 + starts.size * W + 8
+    sa_pos = text_pos + geo.n
+    lcp_pos = sa_pos + sa.size * W
+    names = struct.pack("<Q", len(SEQ_NAMES)) + b"".join(struct.pack("<Q", len(s)) + s.encode() for s in SEQ_NAMES)
+    header = bytes([6, 1, 0, 0]) + struct.pack("<7Q", geo.n, text_pos, sa_pos, lcp_pos, sa.size, 0, starts.size)
+    assert len(header) == 60
+    fd = os.open(str(path), os.O_CREAT | os.O_WRONLY | os.O_TRUNC, 0o644)
+    try:
+        os.ftruncate(fd, lcp_pos + lcp.size * W + len(names))
+        os.pwrite(fd, header + starts.tobytes() + struct.pack("<Q", 0), 0)
+        if indexed:
+            os.pwrite(fd, region().text.tobytes(), text_pos + geo.filler)
+            os.pwrite(fd, sa.astype(dt).tobytes(), sa_pos)
+            os.pwrite(fd, lcp.astype(dt).tobytes(), lcp_pos)
+        os.pwrite(fd, names, lcp_pos + lcp.size * W)
+    finally:
+        os.close(fd)
+    return os.stat(str(path)).st_blocks * 512
+
+
+def open_checked(path, geo: Geometry, indexed: bool = True) -> SufrFile:
+    f = SufrFile(path)
+    assert f.index_width == geo.width and f.text_len == geo.n and f.is_dna, (geo.name, f.index_width, f.text_len)
+    assert f.len_suffixes == (region().sa.size if indexed else 0)
+    assert f.sequence_starts == geo.seq_starts and f.sequence_names == list(SEQ_NAMES)
+    return f
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the queries
+# ---------------------------------------------------------------------------------------------------------------------
+SMALL = 3                       # batch()[:SMALL]: the second batch size of the k-difference sort (its key has fewer bits)
+ALIGN_SLICE = slice(0, 50)
+
+
+def _substitute(rng, read: bytes, rate: float = 0.02) -> bytes:
+    q = bytearray(read)
+    for j in np.nonzero(rng.random(len(q)) < rate)[0]:
+        q[j] = (b"ACGT".replace(bytes([q[j]]), b""))[int(rng.integers(0, 3))] if q[j] in b"ACGT" else ord("A")
+    return bytes(q)
+
+
+@functools.lru_cache(maxsize=None)
+def batch(seed: int = 7):
+    """About 700 queries: reads of 1-200 symbols cut from the region at 2 % substitutions (every one at least 12 long but
+    for a handful, which keeps the records of d = 3 in the tens of thousands), reads over the middle, at both ends of the
+    region and beyond the end of the text, reads with an inserted and a deleted symbol, A x 30, the empty query and a
+    900-symbol prefix of the planted segment."""
+    rng = np.random.default_rng(seed)
+    text = region().text.tobytes()
+    seg = text[SEG_AT[0]:SEG_AT[0] + SEG_LEN]
+    qs = [seg[:900], b"A" * 30, _substitute(rng, text[MID - 60:MID + 70]), b""]            # the first SMALL: see above
+    for length in (1, 2, 3, 4, 5, 6, 8, 10):
+        at = int(rng.integers(0, R - length))
+        qs.append(text[at:at + length])
+    for _ in range(600):
+        length = int(rng.integers(12, 201))
+        at = int(rng.integers(0, R - length + 1))
+        qs.append(_substitute(rng, text[at:at + length]))
+    for _ in range(40):                                                                     # over the boundary byte
+        length = int(rng.integers(20, 201))
+        at = MID - int(rng.integers(1, length - 1))
+        qs.append(_substitute(rng, text[at:at + length]))
+    for length in (16, 40, 150):                                                            # the ends of the region
+        qs += [text[:length], b"ACGT" + text[:length], text[R - length:], text[R - length:] + b"ACGT", text[R - length:R - 1]]
+    for _ in range(12):                                                                     # I and D in the CIGARs
+        length = int(rng.integers(60, 181))
+        at = int(rng.integers(0, R - length + 1)) if _ % 3 else MID - length // 2
+        q = bytearray(text[at:at + length])
+        del q[length // 3]
+        q.insert(2 * length // 3, b"ACGT"[(b"ACGT".index(q[2 * length // 3]) + 1) % 4] if q[2 * length // 3] in b"ACGT" else ord("C"))
+        qs.append(bytes(q))
+    assert max(len(q) for q in qs) <= MAX_QUERY
+    return tuple(qs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the answers
+# ---------------------------------------------------------------------------------------------------------------------
+SEARCH_MQL = (None, 6)
+LOCATE_HITS = (0, 3)
+SMEM_COMBOS = ((12, 4), (1, 0))                         # (min_len, max_hits)
+MEM_COMBOS = ((15, 0, True), (15, 5, False))            # (min_len, max_occ, both strands)
+APPROX_COMBOS = ((3, 0, True), (1, 50, False))          # (d, max_occ, both strands)
+EDIT_COMBOS = ((3, 0, True, False), (3, 0, True, True)) # (d, max_occ, both strands, local minima)
+KMER_KS = (1, 21, 64)
+KMER_BINS = 64
+
+
+def _ints(a, shift: int = 0):
+    if hasattr(a, "cpu"):                               # (a torch tensor, wherever it lives)
+        a = a.cpu().numpy()
+    return (np.asarray(a).astype(np.int64) - shift).tolist()
+
+
+def hit_ranges(lo, hi, max_hits: int):
+    """(offsets, ranks) of the first max_hits ranks (0: all) of every range"""
+    lo, hi = np.asarray(lo).astype(np.int64), np.asarray(hi).astype(np.int64)
+    cnt = hi - lo
+    if max_hits:
+        cnt = np.minimum(cnt, max_hits)
+    off = np.concatenate([[0], np.cumsum(cnt)])
+    ranks = np.concatenate([np.arange(a, a + c) for a, c in zip(lo, cnt)] + [np.zeros(0, dtype=np.int64)])
+    return off, ranks.astype(np.int64)
+
+
+def answers(f: SufrFile, shift: int, queries=None) -> dict:
+    """Every host operation on the file as plain lists; `shift` is taken off every text-position column (locate and SMEM
+    positions, MEM and k-mismatch positions, k-difference ends, traceback starts) and off nothing else.  Output by position
+    needs n entries on the host (17 to 34 GB at the large geometries) and is left to the device tests."""
+    queries = list(batch() if queries is None else queries)
+    qb, off = pack_queries(queries)
+    sa = f.suffix_array
+    out = {}
+    for mql in SEARCH_MQL:
+        lo, hi = f.search_batch(queries, mql)
+        out[f"search mql={mql}"] = [_ints(lo), _ints(hi)]
+        if mql is None:
+            for max_hits in LOCATE_HITS:
+                o, ranks = hit_ranges(lo, hi, max_hits)
+                out[f"locate max_hits={max_hits}"] = [_ints(o), _ints(sa[ranks], shift)]
+    out["locate api"] = [[(p.suffix - shift, p.rank, p.sequence_name, p.suffix - p.sequence_position == f.sequence_starts[SEQ_NAMES.index(p.sequence_name)])
+                          for p in r.positions] for r in f.locate(queries[SMALL:SMALL + 30])]
+    out["matching statistics"] = _ints(np.concatenate(f.matching_statistics(queries)))
+    for min_len, max_hits in SMEM_COMBOS:
+        qi, qo, ln, lo, hi = f.smem_arrays(qb, off, min_len)
+        o, ranks = hit_ranges(lo, hi, max_hits)
+        out[f"smems min_len={min_len} max_hits={max_hits}"] = [_ints(qi), _ints(qo), _ints(ln), _ints(lo), _ints(hi), _ints(o), _ints(sa[ranks], shift)]
+    for min_len, occ, both in MEM_COMBOS:
+        qi, qo, st, ln, pos = f.mem_arrays(qb, off, min_len, occ, both)
+        out[f"mems min_len={min_len} max_occ={occ} both={both}"] = [_ints(qi), _ints(qo), _ints(st), _ints(ln), _ints(pos, shift)]
+    for d, occ, both in APPROX_COMBOS:
+        qi, st, pos, mm = f.approx_arrays(qb, off, d, occ, both)
+        out[f"approx d={d} max_occ={occ} both={both}"] = [_ints(qi), _ints(st), _ints(pos, shift), _ints(mm)]
+    for d, occ, both, minima in EDIT_COMBOS:
+        for count in (len(queries), SMALL):
+            sqb, soff = pack_queries(queries[:count])
+            recs = f.edit_arrays(sqb, soff, d, occ, both, minima)
+            start, coff, cigar = f.edit_trace_arrays(sqb, soff, *recs)
+            tag = f"d={d} max_occ={occ} both={both} minima={minima} queries={'all' if count == len(queries) else count}"
+            out["edit " + tag] = [_ints(recs[0]), _ints(recs[1]), _ints(recs[2], shift), _ints(recs[3])]
+            out["trace " + tag] = [_ints(start, shift), _ints(coff), _ints(cigar)]
+    out["align"] = [[(h.query, h.strand, h.end - shift, h.edits, h.start - shift, h.cigar) for h in hits]
+                    for hits in f.align(queries[ALIGN_SLICE], 3, 0, True, True)]
+    for k in KMER_KS:
+        hist, stats, occ = f.kmers(k, KMER_BINS, "rank")
+        out[f"kmers k={k}"] = [_ints(hist), sorted(stats.items()), _ints(occ)]
+    out["unique lengths"] = _ints(f.unique_lengths())
+    return out
+
+
+def by_position(f: SufrFile, k: int) -> dict:
+    """k-mer counts and unique lengths by text position over the region (the twin only: n entries each)"""
+    assert f.text_len == GEOMETRIES["twin"].n
+    return {f"kmers k={k} by position": _ints(f.kmers(k, KMER_BINS, "position")[2][TWIN_FILLER:]),
+            "unique lengths by position": _ints(f.unique_lengths(True)[TWIN_FILLER:])}
+
+
+def _first_difference(got, want, path=()):
+    if isinstance(got, (list, tuple)) and isinstance(want, (list, tuple)):
+        for i, (g, w) in enumerate(zip(got, want)):
+            d = _first_difference(g, w, path + (i,))
+            if d:
+                return d
+        return (path, f"{len(got)} entries", f"{len(want)} entries") if len(got) != len(want) else None
+    return None if got == want else (path, got, want)
+
+
+def compare(got: dict, want: dict, geometry: str, keys=None):
+    """got == want, exactly, key by key; the message names the operation, the geometry, the index of the first difference and
+    got / want there (text positions as the twin has them: the shift is already taken off)"""
+    for key in (keys if keys is not None else want):
+        assert key in got, f"{geometry}: no answer for {key!r}"
+        if got[key] != want[key]:
+            path, g, w = _first_difference(got[key], want[key])
+            raise AssertionError(f"{key} at {geometry}: first difference at index {list(path)}: got {g!r}, want {w!r} (positions shifted to the twin's)")
+
+
+def assert_witness_is_not_empty(want: dict, queries=None):
+    """What keeps a comparison from being empty, decided by the twin's answers alone: every operation with a position column
+    has records strictly on both sides of the boundary; MEMs, k-mismatch, k-difference and traceback have a record whose span
+    [start, end) holds the boundary byte; the CIGARs hold all of = X I D."""
+    from sufr_amd.sufr_file import cigar_string
+    queries = list(batch() if queries is None else queries)
+    B = GEOMETRIES["twin"].boundary
+    lens = np.array([len(q) for q in queries], dtype=np.int64)
+
+    def sides(name, pos):
+        pos = np.asarray(pos, dtype=np.int64)
+        assert (pos < B).any() and (pos > B).any(), f"{name}: no record on one side of the boundary"
+
+    def spans(name, start, end):                                  # [start, end)
+        start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+        assert ((start <= B) & (B < end)).any(), f"{name}: no record spans the boundary byte"
+
+    for key, v in want.items():
+        op = key.split()[0]
+        if key.startswith("locate max_hits"):
+            sides(key, v[1])
+        elif op == "smems":
+            sides(key, v[6])
+        elif op == "mems":
+            sides(key, v[4])
+            spans(key, v[4], np.asarray(v[4]) + np.asarray(v[3]))
+        elif op == "approx":
+            sides(key, v[2])
+            spans(key, v[2], np.asarray(v[2]) + lens[np.asarray(v[0], dtype=np.int64)])
+        elif op == "edit":
+            t = want["trace" + key[4:]]
+            sides(key, v[2])
+            sides("trace" + key[4:], t[0])
+            spans(key, t[0], np.asarray(v[2]) + 1)
+            if key.endswith("queries=all"):                       # (the slice of SMALL queries: sides and spans only)
+                ops = set("".join(c for c in cigar_string(t[2]) if not c.isdigit()))
+                assert ops == set("=XID"), (key, ops)
+    flat = [h for hits in want["align"] for h in hits]
+    assert flat and any(h[4] <= B <= h[2] for h in flat)
+    assert any(h[2] < B for h in flat) and any(h[4] > B for h in flat), "align: no record on one side of the boundary"
+    assert any(p[0] < B for r in want["locate api"] for p in r) and any(p[0] > B for r in want["locate api"] for p in r)
+    assert all(p[3] for r in want["locate api"] for p in r)       # suffix = sequence start + sequence position
+    assert {p[2] for r in want["locate api"] for p in r} == set(SEQ_NAMES)
+    assert max(want["matching statistics"]) >= 900 and sum(want["kmers k=21"][0]) > 0
