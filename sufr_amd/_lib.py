@@ -124,6 +124,19 @@ class KmerStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# every symbol include/sufr_repeat.h declares
+REPEAT_EXPORTS = ["sufr_file_repeats", "sufr_hip_repeats_device", "sufr_hip_set_repeat_tile"]
+REPEAT_KINDS = {"branching": 0, "maximal": 1, "super": 2, "supermaximal": 2}
+
+
+class RepeatStats(C.Structure):
+    """sufr_repeat_stats"""
+    _fields_ = [("records", C.c_uint64), ("longest", C.c_uint64), ("longest_rank", C.c_uint64), ("max_count", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class FileMeta(C.Structure):
     """sufr_file_meta"""
     _fields_ = [("version", C.c_uint8), ("is_dna", C.c_uint8), ("allow_ambiguity", C.c_uint8),
@@ -282,6 +295,12 @@ def lib() -> C.CDLL:
     L.sufr_hip_kmers_device.restype = C.c_int
     L.sufr_hip_unique_lengths_device.argtypes = [vp, vp, vp, vp, u64, u32, vp]; L.sufr_hip_unique_lengths_device.restype = C.c_int
     L.sufr_hip_set_kmer_tile.argtypes = [vp, u64]; L.sufr_hip_set_kmer_tile.restype = C.c_int
+    # include/sufr_repeat.h
+    L.sufr_file_repeats.argtypes = [vp, u32, u64, u64, u64, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(RepeatStats), C.c_int]
+    L.sufr_file_repeats.restype = C.c_int
+    L.sufr_hip_repeats_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, u64, u64, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(RepeatStats)]
+    L.sufr_hip_repeats_device.restype = C.c_int
+    L.sufr_hip_set_repeat_tile.argtypes = [vp, u64]; L.sufr_hip_set_repeat_tile.restype = C.c_int
     _lib = L
     return L
 
@@ -331,6 +350,11 @@ class Context:
         """k-mer counts: ranks one workgroup folds at a time (sufr_hip_set_kmer_tile; 0: the default).  Rounded up to 256 and
         held to 16384; it changes no result."""
         self.check(lib().sufr_hip_set_kmer_tile(self._h, ranks))
+
+    def set_repeat_tile(self, ranks: int = 0):
+        """Repeats: ranks one workgroup takes at a time (sufr_hip_set_repeat_tile; 0: the default).  Rounded up to 256 and
+        held to 16384; it changes no result."""
+        self.check(lib().sufr_hip_set_repeat_tile(self._h, ranks))
 
     @property
     def window_repairs(self) -> int:

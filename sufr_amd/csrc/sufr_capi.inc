@@ -14,6 +14,8 @@ struct sufr_hip_ctx {
     sufr::DevBuf kbits, ksum, kstarts; // k-mer counts (sufr_kmer.inc): head / whole words, tile summaries and carries and stats, sequence starts
     std::vector<uint64_t> kmer_starts; // the sequence starts kstarts holds
     uint32_t kmer_tile = 0;            // sufr_hip_set_kmer_tile: ranks per tile (0: the default)
+    sufr::DevBuf rell, rpyr, rbits, rsum;  // repeats (sufr_repeat.inc): the clipped LCP, the coarser levels of its min pyramid, flag words and prefixes, tile sums and stats
+    uint32_t repeat_tile = 0;          // sufr_hip_set_repeat_tile: ranks per tile (0: the default)
     bool wide(uint64_t n) const { return n >= sufr::SUFR_MAX_TEXT_LEN || (wide_window && n > wide_window); }
 };
 
@@ -220,7 +222,7 @@ void sufr_hip_destroy(sufr_hip_ctx* ctx)
     for (sufr::DevBuf* b : {&ctx->wtext, &ctx->wsa, &ctx->wlcp, &ctx->wblk, &ctx->mtmp, &ctx->mpoff, &ctx->mbytes,
                             &ctx->xq, &ctx->xoff, &ctx->xlo, &ctx->xhi, &ctx->xcand, &ctx->xsum,
                             &ctx->ecnt, &ctx->ekeys, &ctx->ekeys2, &ctx->ehist, &ctx->tsc, &ctx->trows, &ctx->tmisc,
-                            &ctx->kbits, &ctx->ksum, &ctx->kstarts}) ctx->pl.release(*b);
+                            &ctx->kbits, &ctx->ksum, &ctx->kstarts, &ctx->rell, &ctx->rpyr, &ctx->rbits, &ctx->rsum}) ctx->pl.release(*b);
     ctx->pl.destroy();
     delete ctx;
 }

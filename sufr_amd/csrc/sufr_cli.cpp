@@ -25,6 +25,7 @@
 #include "../../include/sufr_edit.h"
 #include "../../include/sufr_align.h"
 #include "../../include/sufr_kmer.h"
+#include "../../include/sufr_repeat.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -85,6 +86,11 @@ int usage(FILE* f)
             "                                       at which the substring at every text position becomes unique]; both files hold one raw\n"
             "                                       little-endian entry of the index width (4 or 8 bytes) per text position, 0 where the\n"
             "                                       position is not indexed or the k-mer / substring runs over the end of its sequence\n"
+            "  repeats|rp   <SUFR>                  repeats of the indexed text from its LCP array, one line each in rank order:\n"
+            "                                       length  count  occurrences (seq:pos, ascending by text position), then # records,\n"
+            "                                       # longest, # longest_rank, # max_count\n"
+            "                                       -l MINLEN [-c MINCOUNT (2)] [-C MAXCOUNT (0: no limit)] [--kind branching|maximal|super]\n"
+            "                                       [--max-positions P (16; 0: all)] [--device ID: on that GPU; otherwise on the host] [-o OUT]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -831,6 +837,108 @@ int run_kmers(int argc, char** argv, int first, int threads)
     return dump(occ_path, occ) && dump(uniq_path, uniq) ? 0 : 1;
 }
 
+// sufr repeats: the records to standard output (or -o), the stats as # lines behind them
+int run_repeats(int argc, char** argv, int first, int threads)
+{
+    std::string file, output, kind_name = "branching";
+    uint64_t min_len = 0, min_count = 2, max_count = 0, max_positions = 16;
+    int device = -1;
+    auto need = [&](int& i, const char* opt) -> const char* {
+        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
+        return argv[++i];
+    };
+    for (int i = first; i < argc; i++) {
+        const std::string s = argv[i];
+        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
+        else if (s == "-l" || s == "--min-len") min_len = strtoull(need(i, "-l"), nullptr, 10);
+        else if (s == "-c" || s == "--min-count") min_count = strtoull(need(i, "-c"), nullptr, 10);
+        else if (s == "-C" || s == "--max-count") max_count = strtoull(need(i, "-C"), nullptr, 10);
+        else if (s == "--kind") kind_name = need(i, "--kind");
+        else if (s == "--max-positions") max_positions = strtoull(need(i, "--max-positions"), nullptr, 10);
+        else if (s == "--device") device = atoi(need(i, "--device"));
+        else if (s == "-o" || s == "--output") output = need(i, "-o");
+        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+        else if (file.empty()) file = s;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+    }
+    if (file.empty() || !min_len) { fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n", file.empty() ? "<SUFR>" : "-l <MINLEN>"); return 2; }
+    uint32_t kind;
+    if (kind_name == "branching") kind = SUFR_REPEAT_BRANCHING;
+    else if (kind_name == "maximal") kind = SUFR_REPEAT_MAXIMAL;
+    else if (kind_name == "super" || kind_name == "supermaximal") kind = SUFR_REPEAT_SUPERMAXIMAL;
+    else { fprintf(stderr, "error: invalid value '%s' for '--kind': branching, maximal or super\n", kind_name.c_str()); return 2; }
+    sufr_file* f = open_or_die(file);
+    sufr_file_meta m;
+    sufr_file_metadata(f, &m);
+    const uint64_t w = (uint64_t)m.index_width, s = m.len_suffixes;
+    std::vector<uint64_t> rank, count, length;
+    sufr_repeat_stats st{0, 0, 0, 0};
+    uint64_t total = 0;
+    int rc = 0;
+    std::string err;
+    if (device < 0) {
+        rc = sufr_file_repeats(f, kind, min_len, min_count, max_count, 0, nullptr, nullptr, nullptr, &total, &st, threads);
+        if (rc == SUFR_HIP_E_CAPACITY) {
+            rank.resize(total); count.resize(total); length.resize(total);
+            rc = sufr_file_repeats(f, kind, min_len, min_count, max_count, total, rank.data(), count.data(), length.data(), &total, &st, threads);
+        }
+    } else {
+        sufr_hip_ctx* ctx = sufr_hip_create(device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
+        sufr_hip_index* ix = nullptr;
+        std::vector<uint64_t> starts(m.num_sequences);
+        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
+        void *d_lcp = nullptr, *d_out = nullptr;
+        rc = sufr_hip_index_load(ctx, f, &ix);
+        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess ||
+                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
+            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array";
+        }
+        if (!rc) rc = sufr_hip_repeats_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, 0, nullptr,
+                                              nullptr, nullptr, &total, &st);
+        if (rc == SUFR_HIP_E_CAPACITY) {
+            rank.resize(total); count.resize(total); length.resize(total);
+            rc = 0;
+            if (hipMalloc(&d_out, total * 24) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the records"; }
+            uint64_t* o = (uint64_t*)d_out;
+            if (!rc) rc = sufr_hip_repeats_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, total, o,
+                                                  o + total, o + 2 * total, &total, &st);
+            if (!rc) rc = sufr_hip_synchronize(ctx);
+            if (!rc && (hipMemcpy(rank.data(), o, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(count.data(), o + total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(length.data(), o + 2 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess)) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
+        }
+        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
+        if (d_lcp) (void)hipFree(d_lcp);
+        if (d_out) (void)hipFree(d_out);
+        if (ix) sufr_hip_index_free(ix);
+        sufr_hip_destroy(ctx);
+    }
+    if (rc) {
+        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "repeats does not support files built with a seed mask or with a max query length"
+                             : rc == SUFR_HIP_E_INVALID ? "repeats: invalid argument (the minimum length must be at least 1, the sequence starts must ascend from 0)" : "repeats failed";
+        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
+        sufr_file_close(f);
+        return 1;
+    }
+    OutFile out;
+    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); sufr_file_close(f); return 1; }
+    std::vector<uint64_t> pos;
+    for (uint64_t i = 0; i < total; i++) {
+        pos.resize(count[i]);
+        for (uint64_t j = 0; j < count[i]; j++) pos[j] = sufr_file_suffix(f, rank[i] + j);
+        std::sort(pos.begin(), pos.end());
+        fprintf(out.f, "%llu\t%llu\t", (unsigned long long)length[i], (unsigned long long)count[i]);
+        const uint64_t show = max_positions && max_positions < count[i] ? max_positions : count[i];
+        for (uint64_t j = 0; j < show; j++) fprintf(out.f, "%s%s", j ? " " : "", place(f, false, pos[j]).c_str());
+        fputc('\n', out.f);
+    }
+    fprintf(out.f, "# records\t%llu\n# longest\t%llu\n# longest_rank\t%llu\n# max_count\t%llu\n", (unsigned long long)st.records,
+            (unsigned long long)st.longest, (unsigned long long)st.longest_rank, (unsigned long long)st.max_count);
+    sufr_file_close(f);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -884,6 +992,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "match" || s == "ma")) return run_query("match", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "mems" || s == "me")) return run_query("mems", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "kmers" || s == "km")) return run_kmers(argc, argv, i + 1, threads);
+        else if (!have_cmd && (s == "repeats" || s == "rp")) return run_repeats(argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "edit" || s == "ed")) return run_query("edit", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);

@@ -20,6 +20,7 @@
 #include "../../include/sufr_edit.h"
 #include "../../include/sufr_align.h"
 #include "../../include/sufr_kmer.h"
+#include "../../include/sufr_repeat.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -137,5 +138,15 @@ int sufr_hip_kmers_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*,
                           void*, sufr_kmer_stats* stats_out) { if (stats_out) *stats_out = sufr_kmer_stats{0, 0, 0, 0}; return no_device(ctx); }
 int sufr_hip_unique_lengths_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const uint64_t*, uint64_t, uint32_t, void*) { return no_device(ctx); }
 int sufr_hip_set_kmer_tile(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
+
+// ---- include/sufr_repeat.h: the device side (the host side is sufr_query.cpp) ---------------------------------------
+int sufr_hip_repeats_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint64_t, uint64_t,
+                            uint64_t, void*, void*, void*, uint64_t* total_out, sufr_repeat_stats* stats_out)
+{
+    if (total_out) *total_out = 0;
+    if (stats_out) *stats_out = sufr_repeat_stats{0, 0, 0, 0};
+    return no_device(ctx);
+}
+int sufr_hip_set_repeat_tile(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
 
 }  // extern "C"

@@ -3002,3 +3002,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_trace.inc"
 #include "../../include/sufr_kmer.h"
 #include "sufr_kmer.inc"
+#include "../../include/sufr_repeat.h"
+#include "sufr_repeat.inc"

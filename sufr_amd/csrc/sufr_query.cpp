@@ -980,3 +980,135 @@ int sufr_file_unique_lengths(const sufr_file* f, uint32_t flags, void* out, int 
 }
 
 }  // extern "C"
+
+// ---- repeats of the indexed text (include/sufr_repeat.h) ----------------------------------------
+#include "../../include/sufr_repeat.h"
+#include "sufr_repeat_scan.h"
+
+namespace {
+
+// what the searches of sufr_repeat_scan.h read: l (the file's LCP with one sequence, a clipped copy otherwise), the coarser
+// levels of the min pyramid and the suffix array
+struct RepeatHostAcc {
+    const uint8_t *sa_bytes, *lcp;
+    int width;
+    const uint64_t *ell, *up;
+    uint64_t s;
+    uint64_t at(uint32_t level, uint64_t off, uint64_t i) const          // off: rep_level_offset(s, level)
+    {
+        if (level) return up[off + i];
+        return ell ? ell[i] : (i ? rdT(lcp, width, i) : 0);
+    }
+    uint64_t sa(uint64_t r) const { return rdT(sa_bytes, width, r); }
+};
+
+struct RepeatRec { uint64_t rank, count, length; };
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_repeats(const sufr_file* f, uint32_t kind, uint64_t min_len, uint64_t min_count, uint64_t max_count, uint64_t cap,
+                      uint64_t* rank, uint64_t* count, uint64_t* length, uint64_t* total_out, sufr_repeat_stats* stats, int threads)
+{
+    if (stats) *stats = sufr_repeat_stats{0, 0, 0, 0};
+    if (total_out) *total_out = 0;
+    if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0)) return rc;
+    if (min_len == 0 || kind > SUFR_REPEAT_SUPERMAXIMAL) return SUFR_HIP_E_INVALID;
+    if (min_count < 2) min_count = 2;
+    const uint64_t s = f->meta.len_suffixes, n = f->meta.text_len;
+    const int width = f->meta.index_width;
+    if (!s) return 0;
+    if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
+    const uint64_t* starts = f->seq_starts.data();
+    const uint64_t num = f->seq_starts.size();
+    const uint8_t* text = f->text;
+    // pass 1: l (several sequences only), the "differs from the previous rank" and "sequence start" flags, level 1
+    const uint64_t chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk, nwords = (s + 63) / 64;
+    const uint32_t levels = sufr::rep_levels(s);
+    std::vector<uint64_t> ell(num > 1 ? s : 0), dw(nwords, 0), sw(nwords, 0), dp(nwords), sp(nwords);
+    std::vector<uint64_t> up(sufr::rep_level_offset(s, levels + 1));
+    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
+        bool pstart = false;
+        uint8_t plam = 0;
+        uint64_t proom = 0;
+        if (b) {                                          // the rank before the chunk belongs to another chunk: load it
+            const uint64_t pp = rdT(f->sa, width, b - 1);
+            pstart = sufr::rep_is_start(starts, num, n, pp);
+            plam = pstart ? 0 : text[pp - 1];
+            proom = sufr::rep_room(starts, num, n, pp);
+        }
+        for (uint64_t r0 = b; r0 < e; r0 += 64) {
+            uint64_t D = 0, S = 0, low = ~(uint64_t)0;
+            for (uint64_t r = r0; r < e && r < r0 + 64; r++) {
+                const uint64_t p = rdT(f->sa, width, r);
+                const bool start = sufr::rep_is_start(starts, num, n, p);
+                const uint8_t lam = start ? 0 : text[p - 1];
+                const uint64_t room = sufr::rep_room(starts, num, n, p);
+                const uint64_t v = r == 0 ? 0 : num > 1 ? sufr::rep_clip(rdT(f->lcp, width, r), proom, room) : rdT(f->lcp, width, r);
+                if (num > 1) ell[r] = v;
+                if (v < low) low = v;
+                if (r && (start || pstart || lam != plam)) D |= (uint64_t)1 << (r - r0);
+                if (start) S |= (uint64_t)1 << (r - r0);
+                pstart = start; plam = lam; proom = room;
+            }
+            dw[r0 / 64] = D; sw[r0 / 64] = S;
+            if (levels) up[r0 / 64] = low;
+        }
+    });
+    uint64_t nd = 0, ns = 0;
+    for (uint64_t i = 0; i < nwords; i++) {
+        dp[i] = nd; sp[i] = ns;
+        nd += (uint64_t)__builtin_popcountll(dw[i]); ns += (uint64_t)__builtin_popcountll(sw[i]);
+    }
+    for (uint32_t k = 2; k <= levels; k++) {
+        const uint64_t* in = up.data() + sufr::rep_level_offset(s, k - 1);
+        uint64_t* out = up.data() + sufr::rep_level_offset(s, k);
+        const uint64_t n_in = sufr::rep_level_size(s, k - 1), n_out = sufr::rep_level_size(s, k);
+        for (uint64_t i = 0; i < n_out; i++) {
+            uint64_t low = ~(uint64_t)0;
+            for (uint64_t j = i * 64; j < n_in && j < i * 64 + 64; j++) if (in[j] < low) low = in[j];
+            out[i] = low;
+        }
+    }
+    // pass 2: every chunk decides its own ranks; the records of the chunks, one after the other, are in representative order
+    const RepeatHostAcc acc{f->sa, f->lcp, width, num > 1 ? ell.data() : nullptr, up.data(), s};
+    const bool fill = cap > 0;                            // a counting call keeps no records
+    std::vector<std::vector<RepeatRec>> recs(nchunks);
+    std::vector<uint64_t> kept(nchunks, 0);
+    struct Best { uint64_t len, rep, rank, max_count; };
+    std::vector<Best> best(nchunks, Best{0, 0, 0, 0});
+    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
+        std::vector<RepeatRec>& mine = recs[b / chunk];
+        Best& bt = best[b / chunk];
+        for (uint64_t r = b ? b : 1; r < e; r++) {
+            const uint64_t v = acc.at(0, 0, r);
+            if (v < min_len) continue;
+            const uint64_t a = sufr::rep_search_left(acc, s, r, v);
+            if (a == sufr::REP_NONE || acc.at(0, 0, a) == v) continue;          // not the representative
+            const uint64_t z = sufr::rep_search_right(acc, s, r, v);
+            if (!sufr::rep_keep(acc, text, dw.data(), dp.data(), sw.data(), sp.data(), kind, min_count, max_count, a, z, v)) continue;
+            kept[b / chunk]++;
+            if (fill) mine.push_back(RepeatRec{a, z - a, v});
+            if (sufr::rep_better(v, r, bt.len, bt.rep)) { bt.len = v; bt.rep = r; bt.rank = a; }
+            if (z - a > bt.max_count) bt.max_count = z - a;
+        }
+    });
+    sufr_repeat_stats st{0, 0, 0, 0};
+    uint64_t best_rep = 0;
+    for (uint64_t c = 0; c < nchunks; c++) {
+        st.records += kept[c];
+        if (sufr::rep_better(best[c].len, best[c].rep, st.longest, best_rep)) { st.longest = best[c].len; best_rep = best[c].rep; st.longest_rank = best[c].rank; }
+        if (best[c].max_count > st.max_count) st.max_count = best[c].max_count;
+    }
+    if (stats) *stats = st;
+    if (total_out) *total_out = st.records;
+    if (st.records > cap) return SUFR_HIP_E_CAPACITY;
+    if (st.records && (!rank || !count || !length)) return SUFR_HIP_E_INVALID;
+    uint64_t o = 0;
+    for (uint64_t c = 0; c < nchunks; c++)
+        for (const RepeatRec& x : recs[c]) { rank[o] = x.rank; count[o] = x.count; length[o] = x.length; o++; }
+    return 0;
+}
+
+}  // extern "C"

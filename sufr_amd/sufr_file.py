@@ -225,6 +225,13 @@ def _kmer_error(fn: str, rc: int) -> SufrHipError:
     return SufrHipError(rc, f"{fn}: " + msg)
 
 
+def _repeat_error(fn: str, rc: int) -> SufrHipError:
+    msg = {-6: "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported",
+           -5: "more records than the arrays hold",
+           -1: "invalid argument (min_len must be at least 1, the kind 0, 1 or 2, the sequence starts must ascend from 0)"}.get(rc, "failed")
+    return SufrHipError(rc, f"{fn}: " + msg)
+
+
 def _as_bytes(q) -> bytes:
     return q.encode() if isinstance(q, str) else bytes(q)
 
@@ -536,6 +543,26 @@ class SufrFile:
         if rc != 0:
             raise _kmer_error("sufr_file_unique_lengths", rc)
         return out[:count]
+
+    # -- repeats of the indexed text (include/sufr_repeat.h) ------------------------------------------------------------
+    def repeats(self, kind="branching", min_len: int = 1, min_count: int = 2, max_count: int = 0, threads: int = 0):
+        """(rank, count, length, stats): the repeats of the indexed text as three parallel uint64 arrays in ascending order of
+        their representative rank -- the occurrences of record i are suffix_array[rank[i] : rank[i] + count[i]] -- and a
+        dict of records / longest / longest_rank / max_count.  kind: "branching" (0, every LCP interval), "maximal" (1) or
+        "super" (2).  One call counts, one fills."""
+        from ._lib import REPEAT_KINDS, RepeatStats
+        kind = REPEAT_KINDS.get(kind, kind)
+        total, st = C.c_uint64(0), RepeatStats()
+        rc = lib().sufr_file_repeats(self._h, kind, min_len, min_count, max_count, 0, None, None, None, C.byref(total), C.byref(st), threads)
+        if rc not in (0, -5):
+            raise _repeat_error("sufr_file_repeats", rc)
+        out = [np.zeros(max(total.value, 1), dtype=np.uint64) for _ in range(3)]
+        if total.value:
+            rc = lib().sufr_file_repeats(self._h, kind, min_len, min_count, max_count, total.value, out[0].ctypes.data, out[1].ctypes.data,
+                                         out[2].ctypes.data, C.byref(total), C.byref(st), threads)
+            if rc != 0:
+                raise _repeat_error("sufr_file_repeats", rc)
+        return out[0][:total.value], out[1][:total.value], out[2][:total.value], st.as_dict()
 
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
@@ -852,6 +879,27 @@ class DeviceIndex:
                                                             KMER_BY_POSITION if by_position else 0, out.data_ptr()))
         self.ctx.synchronize()
         return out[:count]
+
+    # -- repeats of the indexed text (include/sufr_repeat.h) -----------------------------------------------------------
+    def repeats_device(self, lcp, kind="branching", min_len: int = 1, min_count: int = 2, max_count: int = 0, seq_starts=None):
+        """SufrFile.repeats on the device.  lcp and seq_starts as in kmers_device.  Returns (rank, count, length) as int64
+        CUDA tensors and the stats dict, complete on return.  One call counts, one fills."""
+        import torch
+        from ._lib import REPEAT_KINDS, RepeatStats
+        kind = REPEAT_KINDS.get(kind, kind)
+        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        total, stats = C.c_uint64(0), RepeatStats()
+        rc = lib().sufr_hip_repeats_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count, max_count, 0,
+                                           None, None, None, C.byref(total), C.byref(stats))
+        if rc != -5:
+            self.ctx.check(rc)
+        out = [torch.empty(max(total.value, 1), dtype=torch.int64, device=lcp.device) for _ in range(3)]
+        if total.value:
+            self.ctx.check(lib().sufr_hip_repeats_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count,
+                                                         max_count, total.value, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                         C.byref(total), C.byref(stats)))
+            self.ctx.synchronize()
+        return out[0][:total.value], out[1][:total.value], out[2][:total.value], stats.as_dict()
 
     # -- MEMs (include/sufr_mem.h) -----------------------------------------------------------------------------------
     def mems_device(self, qbytes, offsets, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
