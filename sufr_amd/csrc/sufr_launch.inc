@@ -1675,7 +1675,8 @@ public:
         {
             const uint32_t gmax = leaf_nt == 1024 ? 1024u : 2048u;
             const uint32_t grid = wub < gmax ? wub : gmax;       // workgroups loop over the windows
-            const size_t lds = (size_t)LEAF_CAP * 12 + msd_map_bytes_host(dm.rows) + (leaf_dna3 ? 0 : (size_t)LEAF_CS_MAX * 8) +
+            const size_t lds = (size_t)LEAF_CAP * 12 + (size_t)LEAF_KEY_PAD * 8 + msd_map_bytes_host(dm.rows) +
+                               (leaf_dna3 ? (size_t)DNA3_HALF_ENTRIES * 2 : (size_t)LEAF_CS_MAX * 8) +
                                128 + ((size_t)1 << leaf_t1) * 4;
 #define SUFR_LEAF(NT_, T1_, D3_)                                                                                         \
             {                                                                                                            \

@@ -1509,17 +1509,19 @@ k_group_sort_big(uint64_t* kA, uint32_t* iA, uint64_t* kB, uint32_t* iB,
 //   fast path   one counting pass (LDS atomics) on  leaf ordinal | a monotone digest of the next characters
 //               (<= LEAF_T1 bits), then every record ranks itself inside its bucket by comparing whole keys --
 //               buckets hold one to three records on ordinary text, so the window ends up ordered by the entire
-//               64-bit key.  The digest: DNA3 (the fixed 3-bit code table): A C G T -> 0 1 2 3 by bit tricks on
-//               six characters at once (dna3_digest12, sufr_runkey.h); otherwise the range coder of CharModel
-//               (table look-ups in LDS).  Any monotone function of the key will do: the members of a bucket
-//               are ranked by their whole keys.
-//               The members of a bucket read each other's keys four at a time, all E records of a thread in
-//               flight together (a loop per record paid an LDS round trip per member);
+//               64-bit key.  The digest: DNA3 (the fixed 3-bit code table): A C G T -> 0 1 2 3 of six characters,
+//               as two reads of a table of three-character halves in LDS (dna3_digest12 and dna3_half_entry,
+//               sufr_runkey.h); otherwise the range coder of CharModel (table look-ups in LDS).  Any monotone
+//               function of the key will do: the members of a bucket are ranked by their whole keys.
+//               Every record reads the four key slots from its bucket's start, RB records of a thread in flight
+//               together (a loop per record paid an LDS round trip per member), and counts the members before
+//               it (leaf_rank4, sufr_runkey.h) -- unclamped and unmasked: what follows a bucket is larger;
 //   fallback    a window with a bucket of more than `bmax` records (long repeats) is left to k_leaf_sort_lsd.
 // Either way the window is ordered by at least the key bits above `lowbit`, which is what k_finish needs.
 // The loads of the next window are issued before the current one is copied out.
 // ---------------------------------------------------------------------------------------------
 static constexpr int LEAF_CS_MAX = 1024;       // entries of the combined-character table of the range coder
+static constexpr int LEAF_KEY_PAD = 4;         // key slots behind a window: the ranking reads up to three past its last record
 
 template <int NT, int E, int LEAF_T1, bool DNA3>          // LEAF_T1: bits of the counting digit (2^T1 LDS counters)
 __global__ void __launch_bounds__(NT)
@@ -1535,15 +1537,20 @@ k_leaf_sort(const Rec* __restrict__ in, Rec* __restrict__ out_rec, const uint4* 
     const uint32_t W = (uint32_t)*wtotal;
     uint32_t win = blockIdx.x;
     if (win >= W) return;
-    uint64_t* s_key = reinterpret_cast<uint64_t*>(smem);                                  // CAP
-    const LdsMap map = msd_load_map<NT>(dm, smem + (size_t)CAP * 8);
+    constexpr int KEYS = CAP + LEAF_KEY_PAD;
+    uint64_t* s_key = reinterpret_cast<uint64_t*>(smem);                                  // KEYS: the window + the ranking's sentinels
+    const LdsMap map = msd_load_map<NT>(dm, smem + (size_t)KEYS * 8);
     // range coder over `cs` characters at a time: s_cum[v] = interval {low, high} of the cs-character string v
     const int cs = cm.b * 3 <= 10 ? 3 : (cm.b * 2 <= 10 ? 2 : 1);
     const uint32_t ncomb = 1u << (cm.b * cs);
-    uint2* s_cum = reinterpret_cast<uint2*>(smem + (size_t)CAP * 8 + msd_map_bytes(dm.rows));    // ncomb <= LEAF_CS_MAX
+    uint2* s_cum = reinterpret_cast<uint2*>(smem + (size_t)KEYS * 8 + msd_map_bytes(dm.rows));   // ncomb <= LEAF_CS_MAX
     uint32_t* s_idx = reinterpret_cast<uint32_t*>(s_cum + (DNA3 ? 0 : LEAF_CS_MAX));     // CAP
     uint32_t* s_misc = s_idx + CAP;                                                       // 32
     uint32_t* s_cnt = s_misc + 32;                                                        // NB1 (fast path)
+    uint16_t* s_dg = reinterpret_cast<uint16_t*>(s_cnt + NB1);                            // DNA3_HALF_ENTRIES (DNA3)
+    if constexpr (DNA3) {
+        for (uint32_t v = threadIdx.x; v < DNA3_HALF_ENTRIES; v += NT) s_dg[v] = dna3_half_entry(v);
+    }
     if constexpr (!DNA3) {
         for (uint32_t v = threadIdx.x; v < ncomb; v += NT) {
             uint32_t lo = 0, wd32 = 0xffffffffu;
@@ -1609,7 +1616,10 @@ k_leaf_sort(const Rec* __restrict__ in, Rec* __restrict__ out_rec, const uint4* 
                         if constexpr (DNA3) {
                             // the six characters below the leaf prefix (zeros below the key's last character)
                             const uint32_t t = (uint32_t)((key[e] << (64 - hibit)) >> 46);
-                            dg = abl == 1 ? 0u : dna3_digest12(t) >> (12 - (kbits > 12 ? 12 : kbits));
+                            // (two table reads, sufr_runkey.h; a digit of six bits or fewer takes the first three characters only)
+                            const uint32_t hi = s_dg[t >> 9];
+                            const uint32_t d12 = kbits > 6 ? dna3_digest12_halves(hi, s_dg[t & 511u]) : (hi & 63u) << 6;
+                            dg = abl == 1 ? 0u : d12 >> (12 - (kbits > 12 ? 12 : kbits));
                             if (kbits > 12) dg <<= kbits - 12;
                         } else {
                             uint32_t lo = 0, wd32 = 0xffffffffu;
@@ -1658,74 +1668,86 @@ k_leaf_sort(const Rec* __restrict__ in, Rec* __restrict__ out_rec, const uint4* 
             if (fast) {
                 // every record goes to its bucket's range in arrival order; a bucket of one record (most of them) is
                 // final, the members of a larger one rank themselves by their whole keys and move once more
-                uint32_t pos[E], lo_[E], sz_[E];
+                // (kept per record: ls = the bucket's start | its size << 16 -- a window holds fewer than 2^14 records -- and dr,
+                // whose high bits are the arrival rank)
+                uint32_t ls[E];
 #pragma unroll
                 for (int e = 0; e < E; e++) {
-                    pos[e] = 0; lo_[e] = 0; sz_[e] = 0;
+                    ls[e] = 0;
                     if ((uint32_t)e * NT + threadIdx.x < cnt) {
                         const uint32_t d = dr[e] & (NB1 - 1u);
-                        lo_[e] = s_cnt[d];
-                        sz_[e] = (d + 1u < (uint32_t)NB1 ? s_cnt[d + 1u] : cnt) - lo_[e];
-                        pos[e] = lo_[e] + (dr[e] >> LEAF_T1);
-                        s_key[pos[e]] = key[e]; s_idx[pos[e]] = idx[e];
+                        const uint32_t lo = s_cnt[d];
+                        const uint32_t sz = (d + 1u < (uint32_t)NB1 ? s_cnt[d + 1u] : cnt) - lo;
+                        ls[e] = lo | (sz << 16);
+                        const uint32_t p = lo + (dr[e] >> LEAF_T1);
+                        s_key[p] = key[e]; s_idx[p] = idx[e];
                     }
                 }
+                // the ranking reads four slots at a time from a bucket's start whatever its size, unclamped and unmasked.  That is
+                // right only while every key past a bucket is LARGER AS A WHOLE 64-BIT KEY than the bucket's members, which rests on
+                // three things together: (1) k_pack_windows keeps a window inside one segment, so all records of a window agree on
+                // the key bits above `hibit`; (2) below them the counting digit is  leaf ordinal | digest,  and dense_digit is
+                // monotone in the raw digit at `hibit`, the digest monotone in the bits below it -- a larger digit means a larger
+                // key; (3) past the window's last record lie these sentinels, the largest key, which a slot past its bucket tests
+                // with `less` only (leaf_mate_before: a < sz <= i).  A window that spanned two segments would break (1) and with it
+                // the ranking, silently.  The reads stay inside the key area: lo + 3 <= cnt + 2 < CAP + LEAF_KEY_PAD
+                if (threadIdx.x < LEAF_KEY_PAD - 1) s_key[cnt + threadIdx.x] = ~0ull;
                 __syncthreads();
-                uint32_t np[E];
+                uint32_t cr[E];                             // rank inside the bucket
                 if (abl != 2) {
-                    // the first four members of every bucket of two or more, RB records' reads in flight together
+                    // the first four slots, RB records' reads in flight together.  Straight-line: a bucket of one record ranks itself
+                    // first (nothing in its four slots is before it).  A slot of a row past the window's end (ls == 0) reads the
+                    // window's first four keys and compares them with a key[e] that load_window never assigned (whatever the
+                    // register holds, the previous window's key at most): a rank that nothing below uses, since ls == 0 fails both
+                    // size tests
                     constexpr int RB = NT >= 1024 ? 2 : 4;          // (1024 threads: 128 registers per lane)
 #pragma unroll
                     for (int h = 0; h < E; h += RB) {
                         uint64_t kt[RB][4];
 #pragma unroll
                         for (int q = 0; q < RB; q++) {
-                            const int e = h + q;
-                            if (e < E && sz_[e] > 1u) {
+                            if (h + q < E) {
 #pragma unroll
-                                for (int i = 0; i < 4; i++) kt[q][i] = s_key[lo_[e] + min((uint32_t)i, sz_[e] - 1u)];
+                                for (int i = 0; i < 4; i++) kt[q][i] = s_key[(ls[h + q] & 0xffffu) + (uint32_t)i];
                             }
                         }
 #pragma unroll
                         for (int q = 0; q < RB; q++) {
                             const int e = h + q;
-                            if (e < E) {
-                                np[e] = pos[e];
-                                if (sz_[e] > 1u) {
-                                    uint32_t c = 0;
-#pragma unroll
-                                    for (int i = 0; i < 4; i++) {
-                                        // (bitwise, not && / ||: the short-circuit forms compile to nested exec-mask regions, three
-                                        // SALU instructions for every VALU one in a kernel whose vector and scalar issue are its bound)
-                                        const uint32_t at = lo_[e] + (uint32_t)i;
-                                        const uint32_t lt = (uint32_t)(kt[q][i] < key[e]) | ((uint32_t)(kt[q][i] == key[e]) & (uint32_t)(at < pos[e]));
-                                        c += (uint32_t)((uint32_t)i < sz_[e]) & lt;
-                                    }
-                                    np[e] = lo_[e] + c;
-                                }
-                            }
+                            if (e < E) cr[e] = leaf_rank4(kt[q], key[e], 0u, dr[e] >> LEAF_T1);
+                            // (one record's compares at a time: interleaved, their lane masks outnumber the scalar registers)
+                            __builtin_amdgcn_sched_barrier(0);
                         }
                     }
-                    // larger buckets: the rest of their members, one by one
+                    // larger buckets: the rest of their members, four at a time (1024 threads: one, for the registers)
+                    constexpr uint32_t TB = NT >= 1024 ? 1 : 4;
 #pragma unroll
                     for (int e = 0; e < E; e++) {
-                        if (sz_[e] > 4u) {
+                        if (ls[e] > (4u << 16 | 0xffffu)) {
+                            const uint32_t lo = ls[e] & 0xffffu, sz = ls[e] >> 16, a = dr[e] >> LEAF_T1;
                             uint32_t c = 0;
-                            for (uint32_t i = lo_[e] + 4u; i < lo_[e] + sz_[e]; i++) {
-                                const uint64_t k2 = s_key[i];
-                                c += (uint32_t)(k2 < key[e]) | ((uint32_t)(k2 == key[e]) & (uint32_t)(i < pos[e]));
+                            for (uint32_t i = 4u; i < sz; i += TB) {
+                                uint64_t kb[TB];
+#pragma unroll
+                                for (uint32_t j = 0; j < TB; j++) kb[j] = s_key[lo + i + j];
+#pragma unroll
+                                for (uint32_t j = 0; j < TB; j++) c += leaf_mate_before(kb[j], key[e], i + j, a);
                             }
-                            np[e] += c;
+                            cr[e] += c;
                         }
                     }
                 } else {
 #pragma unroll
-                    for (int e = 0; e < E; e++) np[e] = pos[e];
+                    for (int e = 0; e < E; e++) cr[e] = dr[e] >> LEAF_T1;
                 }
                 __syncthreads();
 #pragma unroll
-                for (int e = 0; e < E; e++)
-                    if (np[e] != pos[e]) { s_key[np[e]] = key[e]; s_idx[np[e]] = idx[e]; }
+                for (int e = 0; e < E; e++) {
+                    if ((uint32_t)(ls[e] > (1u << 16 | 0xffffu)) & (uint32_t)(cr[e] != dr[e] >> LEAF_T1)) {
+                        const uint32_t p = (ls[e] & 0xffffu) + cr[e];
+                        s_key[p] = key[e]; s_idx[p] = idx[e];
+                    }
+                }
                 __syncthreads();
             } else {
                 if (threadIdx.x == 0) wslow[win] = 1u;      // k_leaf_sort_lsd takes this window

@@ -328,4 +328,34 @@ SUFR_HD uint32_t dna3_digest12(uint32_t t)
     return (P & 0xfu) | ((P >> 2) & 0xf0u) | ((P >> 4) & 0xf00u);
 }
 
+// The same digest from a table of halves.  Entry x of the table (DNA3_HALF_ENTRIES of them, three characters each): the 6-bit
+// value of the three characters in bits [5:0], and in bits [13:8] what a half BELOW this one keeps of its own value -- 63, or 0
+// if one of the three characters cuts the tail.  Both fields are read off dna3_digest12 itself (the half on top of "pad pad
+// pad", which adds nothing, and on top of "T T T", which adds 63 unless the tail is cut), so the two cannot drift apart.
+static constexpr uint32_t DNA3_HALF_ENTRIES = 512;
+SUFR_HD uint16_t dna3_half_entry(uint32_t x)
+{
+    return (uint16_t)((dna3_digest12(x << 9) >> 6) | ((dna3_digest12((x << 9) | 0x1ffu) & 63u) << 8));
+}
+// digest of six characters from the entries of their two halves / of the first three alone (its top six bits)
+SUFR_HD uint32_t dna3_digest12_halves(uint32_t hi, uint32_t lo) { return ((hi & 63u) << 6) | (lo & (hi >> 8)); }
+
+// Ranking inside a counting bucket of the leaf sort.  The members lie in arrival order; the record with arrival rank `a` and key
+// `key` goes behind every member that is smaller by (key, arrival rank): member i counts if  k_i <= key  (i < a)  or
+// k_i < key  (i >= a, which takes the record itself out) -- two orderings and one mask operation per member instead of "less,
+// or equal and earlier"; no  key + 1, which wraps for keys that use all 64 bits (the general code table, capped builds).
+// (bitwise, not && / || / ?: -- those compile to exec-mask regions or to selects of materialised 0 / 1 values)
+SUFR_HD uint32_t leaf_mate_before(uint64_t ki, uint64_t key, uint32_t i, uint32_t a)
+{
+    return (uint32_t)((ki < key) | ((ki <= key) & (i < a)));
+}
+// four slots from slot i0 of the bucket at once.  A slot past the bucket needs no mask if it holds a key above `key` (it is
+// tested with  k_i < key,  because a < sz <= i): in the kernel the members of the next buckets or the sentinels
+SUFR_HD uint32_t leaf_rank4(const uint64_t* k, uint64_t key, uint32_t i0, uint32_t a)
+{
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < 4u; j++) c += leaf_mate_before(k[j], key, i0 + j, a);
+    return c;
+}
+
 }  // namespace sufr
