@@ -19,6 +19,21 @@ sparse file that the reader maps, on the device one torch.zeros.
   answers()         every host operation on a SufrFile as a dict of plain lists, text positions shifted back to the twin's
   compare()         exact equality of two such dicts, the first difference in the message
   assert_witness_is_not_empty()   records on both sides of the boundary, spans over it, all four CIGAR operations
+
+Repeats (include/sufr_repeat.h) get a region of their own.  The one place where the sequence starts enter a repeat is the
+clip l[r] = min(LCP[r], d(SA[r-1]), d(SA[r])), d(p) = brk(p) - p, and the region above has no rank at which l[r] < LCP[r]: its two
+`%` are followed by unrelated random text, so no two suffixes agree through a break and a wrong d() changes no answer there.
+repeat_region() is the same text with the 61 bytes around the first `%` copied over those around the second, so that suffixes
+on both sides of the boundary agree through a `%`, and the repeat files have two more sequence starts that no byte marks,
+inside the first and the third copy of the planted segment (the sequence starts are positional: sufr_repeat.h), which cut
+its 1200-byte repeat.  Every rank range, count, length and stat is translation-invariant as above; the left symbol of the
+region's first position is the filler byte in every geometry.
+
+  repeat_region()   that region with its SA and LCP (the oracle's), built once
+  REPEAT_GEOMETRIES the four fillers and widths again, with the five sequence starts (REPEAT_NAMES)
+  repeat_answers()  the records, stats and occurrences of every kind and filter of REPEAT_FILTERS as plain lists
+  repeat_witness()  the twin's repeat answers, held to the serial witness of tests/test_repeat_host.py and shown not to be empty
+  assert_repeat_witness_is_not_empty()   records on both sides of and across the boundary, clipped ranks decided from either side
 """
 from __future__ import annotations
 
@@ -109,18 +124,21 @@ def arrays(geo: Geometry, reg=None):
     return sa.astype(dt), reg.lcp.astype(dt)
 
 
-def write_sparse(path, geo: Geometry, indexed: bool = True) -> int:
+def write_sparse(path, geo: Geometry, indexed: bool = True, reg=None, names=SEQ_NAMES) -> int:
     """The version-6 file of the geometry as sufr_file_open parses it: the 60-byte header, the sequence starts at the index
     width, the mask length, text, SA, LCP, names.  Header, region, arrays and names are written at their offsets; the filler
-    stays a hole.  indexed=False: the header and the names only (no suffixes).  Returns the bytes of disk blocks in use."""
+    stays a hole.  indexed=False: the header and the names only (no suffixes).  reg, names: another region than region()
+    and the names of the geometry's sequences.  Returns the bytes of disk blocks in use."""
     W = geo.width
     dt = "<u4" if W == 4 else "<u8"
-    sa, lcp = arrays(geo) if indexed else (np.zeros(0, dtype=dt), np.zeros(0, dtype=dt))
+    reg = reg or region()
+    assert len(names) == len(geo.seq_starts)
+    sa, lcp = arrays(geo, reg) if indexed else (np.zeros(0, dtype=dt), np.zeros(0, dtype=dt))
     starts = np.asarray(geo.seq_starts, dtype=dt)
     text_pos = 60 + starts.size * W + 8
     sa_pos = text_pos + geo.n
     lcp_pos = sa_pos + sa.size * W
-    names = struct.pack("<Q", len(SEQ_NAMES)) + b"".join(struct.pack("<Q", len(s)) + s.encode() for s in SEQ_NAMES)
+    names = struct.pack("<Q", len(names)) + b"".join(struct.pack("<Q", len(s)) + s.encode() for s in names)
     header = bytes([6, 1, 0, 0]) + struct.pack("<7Q", geo.n, text_pos, sa_pos, lcp_pos, sa.size, 0, starts.size)
     assert len(header) == 60
     fd = os.open(str(path), os.O_CREAT | os.O_WRONLY | os.O_TRUNC, 0o644)
@@ -128,7 +146,7 @@ def write_sparse(path, geo: Geometry, indexed: bool = True) -> int:
         os.ftruncate(fd, lcp_pos + lcp.size * W + len(names))
         os.pwrite(fd, header + starts.tobytes() + struct.pack("<Q", 0), 0)
         if indexed:
-            os.pwrite(fd, region().text.tobytes(), text_pos + geo.filler)
+            os.pwrite(fd, reg.text.tobytes(), text_pos + geo.filler)
             os.pwrite(fd, sa.astype(dt).tobytes(), sa_pos)
             os.pwrite(fd, lcp.astype(dt).tobytes(), lcp_pos)
         os.pwrite(fd, names, lcp_pos + lcp.size * W)
@@ -137,11 +155,11 @@ def write_sparse(path, geo: Geometry, indexed: bool = True) -> int:
     return os.stat(str(path)).st_blocks * 512
 
 
-def open_checked(path, geo: Geometry, indexed: bool = True) -> SufrFile:
+def open_checked(path, geo: Geometry, indexed: bool = True, reg=None, names=SEQ_NAMES) -> SufrFile:
     f = SufrFile(path)
     assert f.index_width == geo.width and f.text_len == geo.n and f.is_dna, (geo.name, f.index_width, f.text_len)
-    assert f.len_suffixes == (region().sa.size if indexed else 0)
-    assert f.sequence_starts == geo.seq_starts and f.sequence_names == list(SEQ_NAMES)
+    assert f.len_suffixes == ((reg or region()).sa.size if indexed else 0)
+    assert f.sequence_starts == geo.seq_starts and f.sequence_names == list(names)
     return f
 
 
@@ -339,3 +357,155 @@ def assert_witness_is_not_empty(want: dict, queries=None):
     assert all(p[3] for r in want["locate api"] for p in r)       # suffix = sequence start + sequence position
     assert {p[2] for r in want["locate api"] for p in r} == set(SEQ_NAMES)
     assert max(want["matching statistics"]) >= 900 and sum(want["kmers k=21"][0]) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# repeats: a region with clipped ranks, five sequences (two starts that no byte marks), the answers and their witness
+# ---------------------------------------------------------------------------------------------------------------------
+COPY = 30                                               # bytes on either side of the first % that also surround the second
+POSITIONAL_STARTS = (SEG_AT[0] + 600, SEG_AT[2] + 900)  # inside the first and the third copy of the planted segment
+REPEAT_NAMES = ("s0", "s1", "s2", "s3", "s4")
+REPEAT_KINDS = (0, 1, 2)
+REPEAT_FILTERS = ((1, 2, 0), (12, 2, 0), (25, 2, 0), (20, 3, 0), (1, 2, 2), (SEG_LEN, 2, 0))    # (min_len, min_count, max_count)
+REPEAT_MAX_SHOWN = 16                                   # records of at most this many occurrences have a position column
+SMALLEST_TILE = 256
+
+
+@dataclass(frozen=True)
+class RepeatGeometry(Geometry):
+    @property
+    def seq_starts(self):
+        return [0] + [self.filler + x for x in (POSITIONAL_STARTS[0], DELIMS[0] + 1, POSITIONAL_STARTS[1], DELIMS[1] + 1)]
+
+
+REPEAT_GEOMETRIES = {g.name: RepeatGeometry(g.name, g.filler, g.width) for g in GEOMETRIES.values()}
+assert SEG_AT[0] < POSITIONAL_STARTS[0] < SEG_AT[0] + SEG_LEN < DELIMS[0] and DELIMS[0] + COPY < SEG_AT[1]
+assert SEG_AT[2] < POSITIONAL_STARTS[1] < SEG_AT[2] + SEG_LEN < DELIMS[1] - COPY and N_RUN[1] < SEG_AT[2]
+
+
+@functools.lru_cache(maxsize=None)
+def repeat_region():
+    """region() with text[DELIMS[0] - 30 : DELIMS[0] + 31] copied over text[DELIMS[1] - 30 : DELIMS[1] + 31]: text, sa, lcp as
+    region() gives them, built once"""
+    from oracle_helper import Oracle
+    t = region().text.copy()
+    t[DELIMS[1] - COPY:DELIMS[1] + COPY + 1] = t[DELIMS[0] - COPY:DELIMS[0] + COPY + 1]
+    assert t[DELIMS[1]] == ord("%") and t[-1] == ord("$") and int((t == ord("%")).sum()) == len(DELIMS)
+    sa, lcp, _ = Oracle().build(t, is_dna=True)
+    assert sa.size == region().sa.size == R - (N_RUN[1] - N_RUN[0]) - len(DELIMS)
+    t.setflags(write=False)
+    return SimpleNamespace(text=t, sa=sa.astype(np.uint64), lcp=lcp.astype(np.uint64))
+
+
+def write_repeat_file(path, geo: RepeatGeometry) -> int:
+    return write_sparse(path, geo, reg=repeat_region(), names=REPEAT_NAMES)
+
+
+def open_repeat_file(path, geo: RepeatGeometry) -> SufrFile:
+    return open_checked(path, geo, reg=repeat_region(), names=REPEAT_NAMES)
+
+
+def repeat_key(kind: int, min_len: int, min_count: int, max_count: int) -> str:
+    return f"repeats kind={kind} min_len={min_len} min_count={min_count} max_count={max_count}"
+
+
+def repeat_occurrences(rank, count, occurrences, shift: int):
+    """[offsets, positions]: of every record with at most REPEAT_MAX_SHOWN occurrences, SA[rank : rank + count] - shift in
+    ascending order; `occurrences` maps an int64 array of ranks to the suffix array's entries there"""
+    rank, count = np.asarray(rank).astype(np.int64), np.asarray(count).astype(np.int64)
+    shown = count <= REPEAT_MAX_SHOWN
+    off, ranks = hit_ranges(rank[shown], rank[shown] + count[shown], 0)
+    pos = np.asarray(occurrences(ranks)).astype(np.int64) - shift if ranks.size else np.zeros(0, dtype=np.int64)
+    record = np.repeat(np.arange(off.size - 1), np.diff(off))
+    return [_ints(off), pos[np.lexsort((pos, record))].tolist()]
+
+
+def repeat_answers(source, shift: int, occurrences=None, threads: int = 0, filters=REPEAT_FILTERS) -> dict:
+    """The repeats of every kind and filter as plain lists: rank, count, length, the stats as sorted items, and the position
+    column of repeat_occurrences(), the only one that takes the shift.  source: a SufrFile, or a callable
+    (kind, min_len, min_count, max_count) -> (rank, count, length, stats) together with `occurrences` (see above)."""
+    if isinstance(source, SufrFile):
+        f, sa = source, source.suffix_array
+        source = lambda kind, ml, mc, xc: f.repeats(kind, ml, mc, xc, threads=threads)
+        occurrences = lambda ranks: np.asarray(sa[ranks])
+    out = {}
+    for kind in REPEAT_KINDS:
+        for ml, mc, xc in filters:
+            rank, count, length, stats = source(kind, ml, mc, xc)
+            out[repeat_key(kind, ml, mc, xc)] = [_ints(rank), _ints(count), _ints(length), sorted(stats.items())] + \
+                repeat_occurrences(_ints(rank), _ints(count), occurrences, shift)
+    return out
+
+
+def clipped_ranks(f: SufrFile):
+    """Of the twin: the ranks r >= 1 with l[r] < LCP[r], and for each the positions SA[r-1], SA[r] and their rooms
+    brk(p) - p (int64 arrays), from the arrays and the sequence starts alone"""
+    from test_repeat_host import brk_of, clipped
+    sa = np.asarray(f.suffix_array).astype(np.int64)
+    lcp = np.asarray(f.lcp).astype(np.int64)
+    room = brk_of(f)[sa] - sa
+    r = 1 + np.nonzero(clipped(f)[1:-1] < lcp[1:])[0]
+    return r, sa[r - 1], sa[r], room[r - 1], room[r]
+
+
+def assert_repeat_witness_is_not_empty(want: dict, f: SufrFile) -> dict:
+    """What keeps a comparison of repeats from being empty, decided by the twin's file and answers alone (B is the twin's
+    boundary).  Returns the counts it looked at."""
+    from test_repeat_host import left_codes
+    B = REPEAT_GEOMETRIES["twin"].boundary
+    assert f.text_len == REPEAT_GEOMETRIES["twin"].n and f.sequence_starts == REPEAT_GEOMETRIES["twin"].seq_starts
+    seen = {}
+    for kind in REPEAT_KINDS:
+        for flt in ((1, 2, 0), (12, 2, 0)):
+            assert len(want[repeat_key(kind, *flt)][0]) > 0, (kind, flt)
+        # the positional starts cut the planted 1200-byte repeat: the clip at work
+        assert want[repeat_key(kind, SEG_LEN, 2, 0)][:3] == [[], [], []], kind
+        assert dict(want[repeat_key(kind, SEG_LEN, 2, 0)][3]) == dict(records=0, longest=0, longest_rank=0, max_count=0), kind
+        seen[f"records kind={kind}"] = len(want[repeat_key(kind, 1, 2, 0)][0])
+        _, _, length, _, off, pos = want[repeat_key(kind, 1, 2, 0)]
+        off, pos = np.asarray(off), np.asarray(pos, dtype=np.int64)
+        first, last = pos[off[:-1]], pos[off[1:] - 1]                  # (the positions of a record ascend; none has no occurrence)
+        assert ((first < B) & (last > B)).any(), f"kind {kind}: no record with occurrences on both sides of the boundary"
+    spans = counts = False
+    for key, (rank, count, length, _, off, pos) in want.items():
+        shown = np.asarray(count) <= REPEAT_MAX_SHOWN
+        lens = np.repeat(np.asarray(length, dtype=np.int64)[shown], np.diff(off))
+        p = np.asarray(pos, dtype=np.int64)
+        spans = spans or bool(((p <= B) & (B < p + lens)).any())
+        counts = counts or max(count, default=0) > SMALLEST_TILE
+    assert spans, "no occurrence whose span holds the boundary byte"
+    assert counts, "no record with more occurrences than the smallest tile has ranks"
+    r, p_prev, p_cur, room_prev, room_cur = clipped_ranks(f)
+    low_decides = ((room_prev < room_cur) & (p_prev < B) & (p_cur > B)) | ((room_cur < room_prev) & (p_cur < B) & (p_prev > B))
+    high_decides = ((room_prev < room_cur) & (p_prev > B) & (p_cur < B)) | ((room_cur < room_prev) & (p_cur > B) & (p_prev < B))
+    straddle = (p_prev < B) != (p_cur < B)
+    below = np.where(room_prev < room_cur, p_prev, p_cur) < B         # where the position of the smaller room lies
+    seen.update({"clipped ranks": int(r.size), "equal rooms": int((room_prev == room_cur).sum()),
+                 "the smaller room below the boundary": int((below & (room_prev != room_cur)).sum()),
+                 "the smaller room above the boundary": int((~below & (room_prev != room_cur)).sum()),
+                 "the smaller room below the boundary, the other position above": int(low_decides.sum()),
+                 "the smaller room above the boundary, the other position below": int(high_decides.sum()),
+                 "pairs that straddle the boundary": int(straddle.sum())})
+    assert all(seen.values()), seen
+    assert B not in p_prev and B not in p_cur
+    lam = left_codes(f)
+    starts = lam[lam >= 256] - 256
+    assert 0x00 in lam and ord("N") in lam and np.unique(starts).size >= 4, "left symbols: no filler byte, no N or fewer than four sequence starts"
+    seen["sequence starts among the left symbols"] = int(np.unique(starts).size)
+    return seen
+
+
+def repeat_witness(f: SufrFile):
+    """(answers, counts): the twin's repeat answers, every key held exactly to the stack pass of tests/test_repeat_host.py
+    (which reads nothing of the library but the arrays) and shown not to be empty, and the counts that
+    assert_repeat_witness_is_not_empty() looked at"""
+    from test_repeat_host import witness_serial
+    want = repeat_answers(f, 0)
+    sa = np.asarray(f.suffix_array)
+    for kind in REPEAT_KINDS:
+        for flt in REPEAT_FILTERS:
+            rank, count, length, stats = witness_serial(f, kind, *flt)
+            serial = [_ints(rank), _ints(count), _ints(length), sorted(stats.items())] + repeat_occurrences(rank, count, lambda ranks: sa[ranks], 0)
+            compare(want, {repeat_key(kind, *flt): serial}, "the twin against the serial witness")
+    counts = assert_repeat_witness_is_not_empty(want, f)
+    return want, counts

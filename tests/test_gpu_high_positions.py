@@ -60,12 +60,13 @@ def _unsigned(t: torch.Tensor) -> np.ndarray:
     return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize]).astype(np.int64)
 
 
-def place(ctx, geo: hp.Geometry, tables=(True, False)):
+def place(ctx, geo: hp.Geometry, tables=(True, False), reg=None):
     """the geometry on the device: text, suffix array and LCP tensors and one wrapped index per entry of `tables` (with and
-    without the prefix table)"""
-    sa, lcp = hp.arrays(geo)
+    without the prefix table); reg: another region than hp.region()"""
+    reg = reg or hp.region()
+    sa, lcp = hp.arrays(geo, reg)
     text = torch.zeros(geo.n, dtype=torch.uint8, device="cuda")
-    text[geo.filler:] = torch.from_numpy(hp.region().text.copy()).cuda()
+    text[geo.filler:] = torch.from_numpy(reg.text.copy()).cuda()
     d_sa, d_lcp = _signed(sa, geo.width).cuda(), _signed(lcp, geo.width).cuda()
     assert d_sa.dtype == (torch.int32 if geo.width == 4 else torch.int64)
     if geo.name in ("u32_across_2_31", "u32_top"):

@@ -535,6 +535,26 @@ def test_popcount_prefix_equals_a_direct_count(shim):
                     assert shim.shim_rep_left_diverse(words.ctypes.data, prefix.ctypes.data, lo, hi) == int(cum[hi] - cum[lo + 1] > 0 if hi > lo + 1 else 0)
 
 
+def test_room_and_sequence_start_at_positions_beyond_2_31_and_2_32(shim):
+    """rep_room and rep_is_start with the sequence starts of tests/high_positions.py, which lie beyond 2^31 and on both sides
+    of 2^32, against a bisection in Python integers: at and next to every start, the boundary and both ends of the text"""
+    import bisect
+    from high_positions import REPEAT_GEOMETRIES
+    vp, u64 = C.c_void_p, C.c_uint64
+    shim.shim_rep_room.argtypes = [vp, u64, u64, u64]; shim.shim_rep_room.restype = u64
+    shim.shim_rep_is_start.argtypes = [vp, u64, u64, u64]; shim.shim_rep_is_start.restype = C.c_int
+    for geo in REPEAT_GEOMETRIES.values():
+        starts = geo.seq_starts
+        st = np.array(starts, dtype=np.uint64)
+        for p in sorted({x + d for x in starts[1:] + [geo.filler, geo.boundary, geo.n - 2] for d in (-2, -1, 0, 1)} | {0, 1}):
+            i = bisect.bisect_right(starts, p)
+            room = (starts[i] - 1 if i < len(starts) else geo.n - 1) - p
+            assert shim.shim_rep_room(st.ctypes.data, st.size, geo.n, p) == room, (geo.name, p)
+            assert shim.shim_rep_is_start(st.ctypes.data, st.size, geo.n, p) == int(p in starts), (geo.name, p)
+    top = REPEAT_GEOMETRIES["u64_across_2_32"].seq_starts
+    assert top[2] < 1 << 32 < top[3]
+
+
 def test_shared_arithmetic_under_the_sanitizers(tmp_path):
     """the same shim as a stand-alone program with AddressSanitizer and UBSan: host code, run as it is"""
     exe = tmp_path / "repeat_shim_main"
