@@ -137,6 +137,18 @@ class RepeatStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# every symbol include/sufr_lz.h declares
+LZ_EXPORTS = ["sufr_file_lpf", "sufr_file_lz", "sufr_hip_lpf_device", "sufr_hip_lz_device", "sufr_hip_set_lz_tile"]
+
+
+class LzStats(C.Structure):
+    """sufr_lz_stats"""
+    _fields_ = [("factors", C.c_uint64), ("literals", C.c_uint64), ("longest", C.c_uint64), ("longest_start", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class FileMeta(C.Structure):
     """sufr_file_meta"""
     _fields_ = [("version", C.c_uint8), ("is_dna", C.c_uint8), ("allow_ambiguity", C.c_uint8),
@@ -301,6 +313,13 @@ def lib() -> C.CDLL:
     L.sufr_hip_repeats_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, u64, u64, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(RepeatStats)]
     L.sufr_hip_repeats_device.restype = C.c_int
     L.sufr_hip_set_repeat_tile.argtypes = [vp, u64]; L.sufr_hip_set_repeat_tile.restype = C.c_int
+    # include/sufr_lz.h
+    L.sufr_file_lpf.argtypes = [vp, vp, vp, C.c_int]; L.sufr_file_lpf.restype = C.c_int
+    L.sufr_file_lz.argtypes = [vp, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(LzStats), C.c_int]; L.sufr_file_lz.restype = C.c_int
+    L.sufr_hip_lpf_device.argtypes = [vp, vp, vp, vp, u64, vp, vp]; L.sufr_hip_lpf_device.restype = C.c_int
+    L.sufr_hip_lz_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(LzStats)]
+    L.sufr_hip_lz_device.restype = C.c_int
+    L.sufr_hip_set_lz_tile.argtypes = [vp, u64, u64]; L.sufr_hip_set_lz_tile.restype = C.c_int
     _lib = L
     return L
 
@@ -355,6 +374,11 @@ class Context:
         """Repeats: ranks one workgroup takes at a time (sufr_hip_set_repeat_tile; 0: the default).  Rounded up to 256 and
         held to 16384; it changes no result."""
         self.check(lib().sufr_hip_set_repeat_tile(self._h, ranks))
+
+    def set_lz_tile(self, ranks: int = 0, positions: int = 0):
+        """LPF and LZ77: ranks one workgroup of the LPF pass takes at a time and text positions one workgroup of the parse
+        takes at a time (sufr_hip_set_lz_tile; 0: the default).  Rounded up to 256 and held to 16384; they change no result."""
+        self.check(lib().sufr_hip_set_lz_tile(self._h, ranks, positions))
 
     @property
     def window_repairs(self) -> int:

@@ -26,6 +26,7 @@
 #include "../../include/sufr_align.h"
 #include "../../include/sufr_kmer.h"
 #include "../../include/sufr_repeat.h"
+#include "../../include/sufr_lz.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -91,6 +92,11 @@ int usage(FILE* f)
             "                                       # longest, # longest_rank, # max_count\n"
             "                                       -l MINLEN [-c MINCOUNT (2)] [-C MAXCOUNT (0: no limit)] [--kind branching|maximal|super]\n"
             "                                       [--max-positions P (16; 0: all)] [--device ID: on that GPU; otherwise on the host] [-o OUT]\n"
+            "  lz           <SUFR>                  the LZ77 factors of the text from its SA and LCP, one line each in text order:\n"
+            "                                       seq:offset  length  source-seq:offset (* for a literal), then # factors, # literals,\n"
+            "                                       # longest, # longest_start\n"
+            "                                       [--lpf: one line per text position instead: seq:offset  longest previous factor  source]\n"
+            "                                       [--device ID: on that GPU; otherwise on the host] [-t THREADS] [-o OUT]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -939,6 +945,113 @@ int run_repeats(int argc, char** argv, int first, int threads)
     return 0;
 }
 
+// sufr lz: the factors to standard output (or -o), the stats as # lines behind them; --lpf: the
+// per-position table
+int run_lz(int argc, char** argv, int first, int threads)
+{
+    std::string file, output;
+    bool table = false;
+    int device = -1;
+    auto need = [&](int& i, const char* opt) -> const char* {
+        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
+        return argv[++i];
+    };
+    for (int i = first; i < argc; i++) {
+        const std::string s = argv[i];
+        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
+        else if (s == "--lpf") table = true;
+        else if (s == "-t" || s == "--threads") threads = atoi(need(i, "-t"));
+        else if (s == "--device") device = atoi(need(i, "--device"));
+        else if (s == "-o" || s == "--output") output = need(i, "-o");
+        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+        else if (file.empty()) file = s;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+    }
+    if (file.empty()) { fprintf(stderr, "error: the following required arguments were not provided:\n  <SUFR>\n"); return 2; }
+    sufr_file* f = open_or_die(file);
+    sufr_file_meta m;
+    sufr_file_metadata(f, &m);
+    const uint64_t w = (uint64_t)m.index_width, s = m.len_suffixes, n = m.text_len;
+    std::vector<uint64_t> start, length, source;          // the factors, or (--lpf) length and source by position
+    sufr_lz_stats st{0, 0, 0, 0};
+    uint64_t total = 0;
+    int rc = 0;
+    std::string err;
+    std::vector<uint8_t> raw(table ? 2 * n * w + 8 : 0);  // --lpf: LPF, then SRC, in the index width
+    if (device < 0) {
+        if (table) rc = sufr_file_lpf(f, raw.data(), raw.data() + n * w, threads);
+        else {
+            rc = sufr_file_lz(f, 0, nullptr, nullptr, nullptr, &total, &st, threads);
+            if (rc == SUFR_HIP_E_CAPACITY) {
+                start.resize(total); length.resize(total); source.resize(total);
+                rc = sufr_file_lz(f, total, start.data(), length.data(), source.data(), &total, &st, threads);
+            }
+        }
+    } else {
+        sufr_hip_ctx* ctx = sufr_hip_create(device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
+        sufr_hip_index* ix = nullptr;
+        std::vector<uint64_t> starts(m.num_sequences);
+        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
+        void *d_lcp = nullptr, *d_out = nullptr;
+        rc = sufr_hip_index_load(ctx, f, &ix);
+        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess ||
+                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
+            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array";
+        }
+        if (!rc && table) {
+            if (hipMalloc(&d_out, 2 * n * w + 8) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the table"; }
+            if (!rc) rc = sufr_hip_lpf_device(ctx, ix, d_lcp, starts.data(), starts.size(), d_out, (uint8_t*)d_out + n * w);
+            if (!rc) rc = sufr_hip_synchronize(ctx);
+            if (!rc && hipMemcpy(raw.data(), d_out, 2 * n * w, hipMemcpyDeviceToHost) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
+        } else if (!rc) {
+            rc = sufr_hip_lz_device(ctx, ix, d_lcp, starts.data(), starts.size(), 0, nullptr, nullptr, nullptr, &total, &st);
+            if (rc == SUFR_HIP_E_CAPACITY) {
+                start.resize(total); length.resize(total); source.resize(total);
+                rc = 0;
+                if (hipMalloc(&d_out, total * 24) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the records"; }
+                uint64_t* o = (uint64_t*)d_out;
+                if (!rc) rc = sufr_hip_lz_device(ctx, ix, d_lcp, starts.data(), starts.size(), total, o, o + total, o + 2 * total, &total, &st);
+                if (!rc) rc = sufr_hip_synchronize(ctx);
+                if (!rc && (hipMemcpy(start.data(), o, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                            hipMemcpy(length.data(), o + total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                            hipMemcpy(source.data(), o + 2 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess)) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
+            }
+        }
+        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
+        if (d_lcp) (void)hipFree(d_lcp);
+        if (d_out) (void)hipFree(d_out);
+        if (ix) sufr_hip_index_free(ix);
+        sufr_hip_destroy(ctx);
+    }
+    if (rc) {
+        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "lz does not support files built with a seed mask or with a max query length"
+                             : rc == SUFR_HIP_E_INVALID ? "lz: invalid argument (the sequence starts must ascend from 0)" : "lz failed";
+        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
+        sufr_file_close(f);
+        return 1;
+    }
+    OutFile out;
+    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); sufr_file_close(f); return 1; }
+    if (table) {
+        const uint64_t none = w == 4 ? 0xFFFFFFFFull : ~0ull;
+        for (uint64_t p = 0; p < n; p++) {
+            uint64_t l = 0, q = 0;
+            memcpy(&l, raw.data() + p * w, w);
+            memcpy(&q, raw.data() + (n + p) * w, w);
+            fprintf(out.f, "%s\t%llu\t%s\n", place(f, false, p).c_str(), (unsigned long long)l, q == none ? "*" : place(f, false, q).c_str());
+        }
+    } else {
+        for (uint64_t i = 0; i < total; i++)
+            fprintf(out.f, "%s\t%llu\t%s\n", place(f, false, start[i]).c_str(), (unsigned long long)length[i],
+                    source[i] == ~0ull ? "*" : place(f, false, source[i]).c_str());
+        fprintf(out.f, "# factors\t%llu\n# literals\t%llu\n# longest\t%llu\n# longest_start\t%llu\n", (unsigned long long)st.factors,
+                (unsigned long long)st.literals, (unsigned long long)st.longest, (unsigned long long)st.longest_start);
+    }
+    sufr_file_close(f);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -993,6 +1106,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "mems" || s == "me")) return run_query("mems", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "kmers" || s == "km")) return run_kmers(argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "repeats" || s == "rp")) return run_repeats(argc, argv, i + 1, threads);
+        else if (!have_cmd && s == "lz") return run_lz(argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "edit" || s == "ed")) return run_query("edit", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);

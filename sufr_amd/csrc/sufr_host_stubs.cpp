@@ -21,6 +21,7 @@
 #include "../../include/sufr_align.h"
 #include "../../include/sufr_kmer.h"
 #include "../../include/sufr_repeat.h"
+#include "../../include/sufr_lz.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -148,5 +149,16 @@ int sufr_hip_repeats_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void
     return no_device(ctx);
 }
 int sufr_hip_set_repeat_tile(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
+
+// ---- include/sufr_lz.h: the device side (the host side is sufr_query.cpp) -------------------------------------------
+int sufr_hip_lpf_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const uint64_t*, uint64_t, void*, void*) { return no_device(ctx); }
+int sufr_hip_lz_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const uint64_t*, uint64_t, uint64_t, void*, void*, void*,
+                       uint64_t* total_out, sufr_lz_stats* stats_out)
+{
+    if (total_out) *total_out = 0;
+    if (stats_out) *stats_out = sufr_lz_stats{0, 0, 0, 0};
+    return no_device(ctx);
+}
+int sufr_hip_set_lz_tile(sufr_hip_ctx* ctx, uint64_t, uint64_t) { return no_device(ctx); }
 
 }  // extern "C"

@@ -3004,3 +3004,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_kmer.inc"
 #include "../../include/sufr_repeat.h"
 #include "sufr_repeat.inc"
+#include "../../include/sufr_lz.h"
+#include "sufr_lz.inc"

@@ -1112,3 +1112,113 @@ int sufr_file_repeats(const sufr_file* f, uint32_t kind, uint64_t min_len, uint6
 }
 
 }  // extern "C"
+
+// ---- longest previous factors and the LZ77 parse (include/sufr_lz.h) ---------------------------
+#include "../../include/sufr_lz.h"
+#include "sufr_lz_scan.h"
+
+namespace {
+
+// what the searches and the range minimum of sufr_lz_scan.h read: a mapped array of the file and the coarser levels of its
+// min pyramid
+struct LzHostAcc {
+    const uint8_t* bytes;
+    int width;
+    const uint64_t* up;
+    uint64_t at(uint32_t level, uint64_t off, uint64_t i) const { return level ? up[off + i] : rdT(bytes, width, i); }
+};
+
+// the coarser levels of the min pyramid over a mapped array of s entries
+std::vector<uint64_t> lz_pyramid(const uint8_t* bytes, int width, uint64_t s, int threads)
+{
+    const uint32_t levels = sufr::rep_levels(s);
+    std::vector<uint64_t> up(sufr::rep_level_offset(s, levels + 1));
+    if (!levels) return up;
+    parallel_chunks(s, (uint64_t)1 << 16, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t r0 = b; r0 < e; r0 += 64) {
+            uint64_t low = ~(uint64_t)0;
+            for (uint64_t r = r0; r < e && r < r0 + 64; r++) { const uint64_t v = rdT(bytes, width, r); if (v < low) low = v; }
+            up[r0 / 64] = low;
+        }
+    });
+    for (uint32_t k = 2; k <= levels; k++) {
+        const uint64_t* in = up.data() + sufr::rep_level_offset(s, k - 1);
+        uint64_t* out = up.data() + sufr::rep_level_offset(s, k);
+        const uint64_t n_in = sufr::rep_level_size(s, k - 1), n_out = sufr::rep_level_size(s, k);
+        for (uint64_t i = 0; i < n_out; i++) {
+            uint64_t low = ~(uint64_t)0;
+            for (uint64_t j = i * 64; j < n_in && j < i * 64 + 64; j++) if (in[j] < low) low = in[j];
+            out[i] = low;
+        }
+    }
+    return up;
+}
+
+// the refusals of both calls
+int lz_args(const sufr_file* f)
+{
+    if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0)) return rc;
+    if (f->meta.len_suffixes && !kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
+    return 0;
+}
+
+// LPF and SRC of every position, n entries of `width` bytes each (either may be null); put: kmer_put
+void lz_host_lpf(const sufr_file& f, void* lpf, void* src, int width, int threads)
+{
+    const uint64_t s = f.meta.len_suffixes, n = f.meta.text_len;
+    if (lpf) memset(lpf, 0, n * (uint64_t)width);
+    if (src) memset(src, 0xFF, n * (uint64_t)width);
+    if (!s || (!lpf && !src)) return;
+    const int fw = f.meta.index_width;
+    const std::vector<uint64_t> up_sa = lz_pyramid(f.sa, fw, s, threads), up_lcp = lz_pyramid(f.lcp, fw, s, threads);
+    const LzHostAcc sa{f.sa, fw, up_sa.data()}, lcp{f.lcp, fw, up_lcp.data()};
+    const uint64_t* starts = f.seq_starts.data();
+    const uint64_t num = f.seq_starts.size();
+    parallel_chunks(s, (uint64_t)1 << 14, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t r = b; r < e; r++) {
+            const uint64_t p = rdT(f.sa, fw, r);
+            const sufr::LzEntry x = sufr::lz_rank(sa, lcp, s, r, p, sufr::rep_room(starts, num, n, p));
+            if (lpf) kmer_put(lpf, width, p, x.lpf);
+            if (src) kmer_put(src, width, p, x.src);      // (LZ_NONE is all ones of either width)
+        }
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_lpf(const sufr_file* f, void* lpf, void* src, int threads)
+{
+    if (const int rc = lz_args(f)) return rc;
+    lz_host_lpf(*f, lpf, src, f->meta.index_width, threads);
+    return 0;
+}
+
+int sufr_file_lz(const sufr_file* f, uint64_t cap, uint64_t* start, uint64_t* length, uint64_t* source, uint64_t* total_out,
+                 sufr_lz_stats* stats, int threads)
+{
+    if (stats) *stats = sufr_lz_stats{0, 0, 0, 0};
+    if (total_out) *total_out = 0;
+    if (const int rc = lz_args(f)) return rc;
+    const uint64_t n = f->meta.text_len;
+    if (!n) return 0;
+    std::vector<uint64_t> lpf(n), src(n);
+    lz_host_lpf(*f, lpf.data(), src.data(), 8, threads);
+    // the parse is a plain serial walk: once for the total and the stats, once more to fill
+    sufr_lz_stats st{0, 0, 0, 0};
+    for (uint64_t p = 0; p < n; p += sufr::lz_step(lpf[p])) {
+        st.factors++;
+        if (!lpf[p]) st.literals++;
+        if (sufr::lz_step(lpf[p]) > st.longest) { st.longest = sufr::lz_step(lpf[p]); st.longest_start = p; }
+    }
+    if (stats) *stats = st;
+    if (total_out) *total_out = st.factors;
+    if (st.factors > cap) return SUFR_HIP_E_CAPACITY;
+    if (!start || !length || !source) return SUFR_HIP_E_INVALID;
+    uint64_t o = 0;
+    for (uint64_t p = 0; p < n; p += sufr::lz_step(lpf[p]), o++) { start[o] = p; length[o] = sufr::lz_step(lpf[p]); source[o] = lpf[p] ? src[p] : sufr::LZ_NONE; }
+    return 0;
+}
+
+}  // extern "C"

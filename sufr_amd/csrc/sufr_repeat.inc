@@ -48,9 +48,9 @@ struct RepAcc {
 
 // RepAcc behind a window of l and of level 1 in LDS: ranks [w0, w1) and their words (w0 a multiple of 64).  A search reads
 // the window first -- a scan step is then an LDS read, not a dependent global load -- and what lies outside it from memory.
-template <typename T>
+template <typename T, typename G = RepAcc<T>>         // (G: what lies behind the window; sufr_lz.inc stages its own arrays)
 struct RepStaged {
-    RepAcc<T> g;
+    G g;
     const T *s_l, *s_l1;
     uint64_t w0, len, v0, vlen;                         // the window of level 0 and of level 1: first index and entries
     __device__ __forceinline__ uint64_t at(uint32_t level, uint64_t off, uint64_t i) const

@@ -232,6 +232,13 @@ def _repeat_error(fn: str, rc: int) -> SufrHipError:
     return SufrHipError(rc, f"{fn}: " + msg)
 
 
+def _lz_error(fn: str, rc: int) -> SufrHipError:
+    msg = {-6: "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported",
+           -5: "more factors than the arrays hold",
+           -1: "invalid argument (the sequence starts must ascend from 0)"}.get(rc, "failed")
+    return SufrHipError(rc, f"{fn}: " + msg)
+
+
 def _as_bytes(q) -> bytes:
     return q.encode() if isinstance(q, str) else bytes(q)
 
@@ -562,6 +569,34 @@ class SufrFile:
                                          out[2].ctypes.data, C.byref(total), C.byref(st), threads)
             if rc != 0:
                 raise _repeat_error("sufr_file_repeats", rc)
+        return out[0][:total.value], out[1][:total.value], out[2][:total.value], st.as_dict()
+
+    # -- longest previous factors and the LZ77 parse (include/sufr_lz.h) ------------------------------------------------
+    def lpf(self, threads: int = 0):
+        """(lpf, src): for every text position the length of the longest break-free string that also starts at an earlier
+        indexed position, and such a position; arrays of the index width, src all ones where lpf is 0."""
+        n = self.text_len
+        out = [np.zeros(max(n, 1), dtype=self._index_dtype()) for _ in range(2)]
+        rc = lib().sufr_file_lpf(self._h, out[0].ctypes.data, out[1].ctypes.data, threads)
+        if rc != 0:
+            raise _lz_error("sufr_file_lpf", rc)
+        return out[0][:n], out[1][:n]
+
+    def lz(self, threads: int = 0):
+        """(start, length, source, stats): the LZ77 factors of the text in text order as three parallel uint64 arrays
+        (source all ones: a literal of length 1) and a dict of factors / literals / longest / longest_start.  One call
+        counts, one fills."""
+        from ._lib import LzStats
+        total, st = C.c_uint64(0), LzStats()
+        rc = lib().sufr_file_lz(self._h, 0, None, None, None, C.byref(total), C.byref(st), threads)
+        if rc not in (0, -5):
+            raise _lz_error("sufr_file_lz", rc)
+        out = [np.zeros(max(total.value, 1), dtype=np.uint64) for _ in range(3)]
+        if total.value:
+            rc = lib().sufr_file_lz(self._h, total.value, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, C.byref(total),
+                                    C.byref(st), threads)
+            if rc != 0:
+                raise _lz_error("sufr_file_lz", rc)
         return out[0][:total.value], out[1][:total.value], out[2][:total.value], st.as_dict()
 
     def _sequence_of(self, suffix: int) -> int:
@@ -898,6 +933,35 @@ class DeviceIndex:
             self.ctx.check(lib().sufr_hip_repeats_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count,
                                                          max_count, total.value, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
                                                          C.byref(total), C.byref(stats)))
+            self.ctx.synchronize()
+        return out[0][:total.value], out[1][:total.value], out[2][:total.value], stats.as_dict()
+
+    # -- longest previous factors and the LZ77 parse (include/sufr_lz.h) -----------------------------------------------
+    def lpf_device(self, lcp, seq_starts=None):
+        """SufrFile.lpf on the device.  lcp and seq_starts as in kmers_device.  Returns (lpf, src) as CUDA tensors of the
+        index's width, complete on return."""
+        import torch
+        dt, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        n = self.text_len
+        out = [torch.empty(max(n, 1), dtype=dt, device=lcp.device) for _ in range(2)]
+        self.ctx.check(lib().sufr_hip_lpf_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, out[0].data_ptr(), out[1].data_ptr()))
+        self.ctx.synchronize()
+        return out[0][:n], out[1][:n]
+
+    def lz_device(self, lcp, seq_starts=None):
+        """SufrFile.lz on the device.  Returns (start, length, source) as int64 CUDA tensors (source -1: a literal) and the
+        stats dict, complete on return.  One call counts, one fills."""
+        import torch
+        from ._lib import LzStats
+        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        total, stats = C.c_uint64(0), LzStats()
+        rc = lib().sufr_hip_lz_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, 0, None, None, None, C.byref(total), C.byref(stats))
+        if rc != -5:
+            self.ctx.check(rc)
+        out = [torch.empty(max(total.value, 1), dtype=torch.int64, device=lcp.device) for _ in range(3)]
+        if total.value:
+            self.ctx.check(lib().sufr_hip_lz_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, total.value, out[0].data_ptr(),
+                                                    out[1].data_ptr(), out[2].data_ptr(), C.byref(total), C.byref(stats)))
             self.ctx.synchronize()
         return out[0][:total.value], out[1][:total.value], out[2][:total.value], stats.as_dict()
 
