@@ -149,6 +149,19 @@ class LzStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# every symbol include/sufr_shared.h declares
+SHARED_EXPORTS = ["sufr_file_shared", "sufr_file_common", "sufr_hip_shared_device", "sufr_hip_common_device"]
+
+
+class SharedStats(C.Structure):
+    """sufr_shared_stats"""
+    _fields_ = [("records", C.c_uint64), ("longest", C.c_uint64), ("longest_rank", C.c_uint64), ("max_count", C.c_uint64),
+                ("max_seqs", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class FileMeta(C.Structure):
     """sufr_file_meta"""
     _fields_ = [("version", C.c_uint8), ("is_dna", C.c_uint8), ("allow_ambiguity", C.c_uint8),
@@ -320,6 +333,14 @@ def lib() -> C.CDLL:
     L.sufr_hip_lz_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(LzStats)]
     L.sufr_hip_lz_device.restype = C.c_int
     L.sufr_hip_set_lz_tile.argtypes = [vp, u64, u64]; L.sufr_hip_set_lz_tile.restype = C.c_int
+    # include/sufr_shared.h
+    L.sufr_file_shared.argtypes = [vp, u32, u64, u64, u64, u64, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(SharedStats), C.c_int]
+    L.sufr_file_shared.restype = C.c_int
+    L.sufr_file_common.argtypes = [vp, vp, C.c_int]; L.sufr_file_common.restype = C.c_int
+    L.sufr_hip_shared_device.argtypes = [vp, vp, vp, vp, u64, u32, u64, u64, u64, u64, u64, u64, vp, vp, vp, vp, C.POINTER(u64),
+                                         C.POINTER(SharedStats)]
+    L.sufr_hip_shared_device.restype = C.c_int
+    L.sufr_hip_common_device.argtypes = [vp, vp, vp, vp, u64, vp]; L.sufr_hip_common_device.restype = C.c_int
     _lib = L
     return L
 

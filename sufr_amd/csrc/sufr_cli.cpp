@@ -27,6 +27,7 @@
 #include "../../include/sufr_kmer.h"
 #include "../../include/sufr_repeat.h"
 #include "../../include/sufr_lz.h"
+#include "../../include/sufr_shared.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -92,6 +93,11 @@ int usage(FILE* f)
             "                                       # longest, # longest_rank, # max_count\n"
             "                                       -l MINLEN [-c MINCOUNT (2)] [-C MAXCOUNT (0: no limit)] [--kind branching|maximal|super]\n"
             "                                       [--max-positions P (16; 0: all)] [--device ID: on that GPU; otherwise on the host] [-o OUT]\n"
+            "  shared       <SUFR>                  the lines of repeats with one more column, the number of different sequences the\n"
+            "                                       occurrences lie in: length  count  seqs  occurrences, then the # lines and # max_seqs\n"
+            "                                       the options of repeats, [-q|--min-seqs Q (0: no limit)] [--max-seqs Q (0: no limit)]\n"
+            "                                       [--common: instead one line q  length per q = 1 .. sequences, the longest substring\n"
+            "                                       common to at least q sequences; takes only --device and -o]\n"
             "  lz           <SUFR>                  the LZ77 factors of the text from its SA and LCP, one line each in text order:\n"
             "                                       seq:offset  length  source-seq:offset (* for a literal), then # factors, # literals,\n"
             "                                       # longest, # longest_start\n"
@@ -945,6 +951,130 @@ int run_repeats(int argc, char** argv, int first, int threads)
     return 0;
 }
 
+// sufr shared: the records of sufr repeats with the seqs column, or (--common) the k-common profile
+int run_shared(int argc, char** argv, int first, int threads)
+{
+    std::string file, output, kind_name = "branching";
+    uint64_t min_len = 0, min_count = 2, max_count = 0, min_seqs = 0, max_seqs = 0, max_positions = 16;
+    bool profile = false;
+    int device = -1;
+    auto need = [&](int& i, const char* opt) -> const char* {
+        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
+        return argv[++i];
+    };
+    for (int i = first; i < argc; i++) {
+        const std::string s = argv[i];
+        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
+        else if (s == "-l" || s == "--min-len") min_len = strtoull(need(i, "-l"), nullptr, 10);
+        else if (s == "-c" || s == "--min-count") min_count = strtoull(need(i, "-c"), nullptr, 10);
+        else if (s == "-C" || s == "--max-count") max_count = strtoull(need(i, "-C"), nullptr, 10);
+        else if (s == "-q" || s == "--min-seqs") min_seqs = strtoull(need(i, "-q"), nullptr, 10);
+        else if (s == "--max-seqs") max_seqs = strtoull(need(i, "--max-seqs"), nullptr, 10);
+        else if (s == "--kind") kind_name = need(i, "--kind");
+        else if (s == "--common") profile = true;
+        else if (s == "--max-positions") max_positions = strtoull(need(i, "--max-positions"), nullptr, 10);
+        else if (s == "--device") device = atoi(need(i, "--device"));
+        else if (s == "-o" || s == "--output") output = need(i, "-o");
+        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+        else if (file.empty()) file = s;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+    }
+    if (file.empty() || (!min_len && !profile)) { fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n", file.empty() ? "<SUFR>" : "-l <MINLEN>"); return 2; }
+    if (max_seqs && min_seqs > max_seqs) { fprintf(stderr, "error: invalid value '%llu' for '--min-seqs': larger than --max-seqs\n", (unsigned long long)min_seqs); return 2; }
+    uint32_t kind;
+    if (kind_name == "branching") kind = SUFR_REPEAT_BRANCHING;
+    else if (kind_name == "maximal") kind = SUFR_REPEAT_MAXIMAL;
+    else if (kind_name == "super" || kind_name == "supermaximal") kind = SUFR_REPEAT_SUPERMAXIMAL;
+    else { fprintf(stderr, "error: invalid value '%s' for '--kind': branching, maximal or super\n", kind_name.c_str()); return 2; }
+    sufr_file* f = open_or_die(file);
+    sufr_file_meta m;
+    sufr_file_metadata(f, &m);
+    const uint64_t w = (uint64_t)m.index_width, s = m.len_suffixes, num = m.num_sequences ? m.num_sequences : 1;
+    std::vector<uint64_t> rank, count, length, seqs, common(profile ? num : 0);
+    sufr_shared_stats st{0, 0, 0, 0, 0};
+    uint64_t total = 0;
+    int rc = 0;
+    std::string err;
+    if (device < 0) {
+        if (profile) rc = sufr_file_common(f, common.data(), threads);
+        else {
+            rc = sufr_file_shared(f, kind, min_len, min_count, max_count, min_seqs, max_seqs, 0, nullptr, nullptr, nullptr, nullptr, &total, &st, threads);
+            if (rc == SUFR_HIP_E_CAPACITY) {
+                rank.resize(total); count.resize(total); length.resize(total); seqs.resize(total);
+                rc = sufr_file_shared(f, kind, min_len, min_count, max_count, min_seqs, max_seqs, total, rank.data(), count.data(), length.data(),
+                                      seqs.data(), &total, &st, threads);
+            }
+        }
+    } else {
+        sufr_hip_ctx* ctx = sufr_hip_create(device);
+        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
+        sufr_hip_index* ix = nullptr;
+        std::vector<uint64_t> starts(m.num_sequences);
+        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
+        void *d_lcp = nullptr, *d_out = nullptr;
+        rc = sufr_hip_index_load(ctx, f, &ix);
+        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess ||
+                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
+            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array";
+        }
+        if (!rc && profile) {
+            if (hipMalloc(&d_out, num * 8) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the profile"; }
+            if (!rc) rc = sufr_hip_common_device(ctx, ix, d_lcp, starts.data(), starts.size(), d_out);
+            if (!rc) rc = sufr_hip_synchronize(ctx);
+            if (!rc && hipMemcpy(common.data(), d_out, num * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
+        } else if (!rc) {
+            rc = sufr_hip_shared_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, min_seqs, max_seqs, 0,
+                                        nullptr, nullptr, nullptr, nullptr, &total, &st);
+            if (rc == SUFR_HIP_E_CAPACITY) {
+                rank.resize(total); count.resize(total); length.resize(total); seqs.resize(total);
+                rc = 0;
+                if (hipMalloc(&d_out, total * 32) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the records"; }
+                uint64_t* o = (uint64_t*)d_out;
+                if (!rc) rc = sufr_hip_shared_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, min_seqs,
+                                                     max_seqs, total, o, o + total, o + 2 * total, o + 3 * total, &total, &st);
+                if (!rc) rc = sufr_hip_synchronize(ctx);
+                if (!rc && (hipMemcpy(rank.data(), o, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                            hipMemcpy(count.data(), o + total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                            hipMemcpy(length.data(), o + 2 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                            hipMemcpy(seqs.data(), o + 3 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess)) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
+            }
+        }
+        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
+        if (d_lcp) (void)hipFree(d_lcp);
+        if (d_out) (void)hipFree(d_out);
+        if (ix) sufr_hip_index_free(ix);
+        sufr_hip_destroy(ctx);
+    }
+    if (rc) {
+        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "shared does not support files built with a seed mask or with a max query length"
+                             : rc == SUFR_HIP_E_INVALID ? "shared: invalid argument (the minimum length must be at least 1, the sequence starts must ascend from 0)" : "shared failed";
+        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
+        sufr_file_close(f);
+        return 1;
+    }
+    OutFile out;
+    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); sufr_file_close(f); return 1; }
+    if (profile) {
+        for (uint64_t q = 0; q < num; q++) fprintf(out.f, "%llu\t%llu\n", (unsigned long long)(q + 1), (unsigned long long)common[q]);
+        sufr_file_close(f);
+        return 0;
+    }
+    std::vector<uint64_t> pos;
+    for (uint64_t i = 0; i < total; i++) {
+        pos.resize(count[i]);
+        for (uint64_t j = 0; j < count[i]; j++) pos[j] = sufr_file_suffix(f, rank[i] + j);
+        std::sort(pos.begin(), pos.end());
+        fprintf(out.f, "%llu\t%llu\t%llu\t", (unsigned long long)length[i], (unsigned long long)count[i], (unsigned long long)seqs[i]);
+        const uint64_t show = max_positions && max_positions < count[i] ? max_positions : count[i];
+        for (uint64_t j = 0; j < show; j++) fprintf(out.f, "%s%s", j ? " " : "", place(f, false, pos[j]).c_str());
+        fputc('\n', out.f);
+    }
+    fprintf(out.f, "# records\t%llu\n# longest\t%llu\n# longest_rank\t%llu\n# max_count\t%llu\n# max_seqs\t%llu\n", (unsigned long long)st.records,
+            (unsigned long long)st.longest, (unsigned long long)st.longest_rank, (unsigned long long)st.max_count, (unsigned long long)st.max_seqs);
+    sufr_file_close(f);
+    return 0;
+}
+
 // sufr lz: the factors to standard output (or -o), the stats as # lines behind them; --lpf: the
 // per-position table
 int run_lz(int argc, char** argv, int first, int threads)
@@ -1106,6 +1236,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "mems" || s == "me")) return run_query("mems", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "kmers" || s == "km")) return run_kmers(argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "repeats" || s == "rp")) return run_repeats(argc, argv, i + 1, threads);
+        else if (!have_cmd && s == "shared") return run_shared(argc, argv, i + 1, threads);
         else if (!have_cmd && s == "lz") return run_lz(argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "edit" || s == "ed")) return run_query("edit", argc, argv, i + 1, threads);

@@ -22,6 +22,7 @@
 #include "../../include/sufr_kmer.h"
 #include "../../include/sufr_repeat.h"
 #include "../../include/sufr_lz.h"
+#include "../../include/sufr_shared.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -160,5 +161,15 @@ int sufr_hip_lz_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, co
     return no_device(ctx);
 }
 int sufr_hip_set_lz_tile(sufr_hip_ctx* ctx, uint64_t, uint64_t) { return no_device(ctx); }
+
+// ---- include/sufr_shared.h: the device side (the host side is sufr_query.cpp) ---------------------------------------
+int sufr_hip_shared_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint64_t, uint64_t,
+                           uint64_t, uint64_t, uint64_t, void*, void*, void*, void*, uint64_t* total_out, sufr_shared_stats* stats_out)
+{
+    if (total_out) *total_out = 0;
+    if (stats_out) *stats_out = sufr_shared_stats{0, 0, 0, 0, 0};
+    return no_device(ctx);
+}
+int sufr_hip_common_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const uint64_t*, uint64_t, void*) { return no_device(ctx); }
 
 }  // extern "C"

@@ -3006,3 +3006,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_repeat.inc"
 #include "../../include/sufr_lz.h"
 #include "sufr_lz.inc"
+#include "../../include/sufr_shared.h"
+#include "sufr_shared.inc"

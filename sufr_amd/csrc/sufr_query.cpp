@@ -1004,30 +1004,28 @@ struct RepeatHostAcc {
 
 struct RepeatRec { uint64_t rank, count, length; };
 
-}  // namespace
+// pass 1 of the calls that search the clipped LCP (repeats, shared): l (several sequences only), the "differs from the
+// previous rank" and "sequence start" flag words with their popcount prefixes, and the coarser levels of the min pyramid
+struct RepeatHostPrep {
+    std::vector<uint64_t> ell, dw, sw, dp, sp, up;
+    RepeatHostAcc acc(const sufr_file* f) const
+    {
+        return RepeatHostAcc{f->sa, f->lcp, f->meta.index_width, f->seq_starts.size() > 1 ? ell.data() : nullptr, up.data(), f->meta.len_suffixes};
+    }
+};
 
-extern "C" {
-
-int sufr_file_repeats(const sufr_file* f, uint32_t kind, uint64_t min_len, uint64_t min_count, uint64_t max_count, uint64_t cap,
-                      uint64_t* rank, uint64_t* count, uint64_t* length, uint64_t* total_out, sufr_repeat_stats* stats, int threads)
+void repeat_host_prepare(const sufr_file* f, int threads, RepeatHostPrep& P)
 {
-    if (stats) *stats = sufr_repeat_stats{0, 0, 0, 0};
-    if (total_out) *total_out = 0;
-    if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0)) return rc;
-    if (min_len == 0 || kind > SUFR_REPEAT_SUPERMAXIMAL) return SUFR_HIP_E_INVALID;
-    if (min_count < 2) min_count = 2;
-    const uint64_t s = f->meta.len_suffixes, n = f->meta.text_len;
-    const int width = f->meta.index_width;
-    if (!s) return 0;
-    if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
     const uint64_t* starts = f->seq_starts.data();
     const uint64_t num = f->seq_starts.size();
     const uint8_t* text = f->text;
-    // pass 1: l (several sequences only), the "differs from the previous rank" and "sequence start" flags, level 1
-    const uint64_t chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk, nwords = (s + 63) / 64;
+    const uint64_t s = f->meta.len_suffixes, n = f->meta.text_len;
+    const int width = f->meta.index_width;
+    const uint64_t chunk = (uint64_t)1 << 16, nwords = (s + 63) / 64;
     const uint32_t levels = sufr::rep_levels(s);
-    std::vector<uint64_t> ell(num > 1 ? s : 0), dw(nwords, 0), sw(nwords, 0), dp(nwords), sp(nwords);
-    std::vector<uint64_t> up(sufr::rep_level_offset(s, levels + 1));
+    std::vector<uint64_t>&ell = P.ell, &dw = P.dw, &sw = P.sw, &dp = P.dp, &sp = P.sp, &up = P.up;
+    ell.assign(num > 1 ? s : 0, 0); dw.assign(nwords, 0); sw.assign(nwords, 0); dp.assign(nwords, 0); sp.assign(nwords, 0);
+    up.assign(sufr::rep_level_offset(s, levels + 1), 0);
     parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
         bool pstart = false;
         uint8_t plam = 0;
@@ -1071,8 +1069,31 @@ int sufr_file_repeats(const sufr_file* f, uint32_t kind, uint64_t min_len, uint6
             out[i] = low;
         }
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_repeats(const sufr_file* f, uint32_t kind, uint64_t min_len, uint64_t min_count, uint64_t max_count, uint64_t cap,
+                      uint64_t* rank, uint64_t* count, uint64_t* length, uint64_t* total_out, sufr_repeat_stats* stats, int threads)
+{
+    if (stats) *stats = sufr_repeat_stats{0, 0, 0, 0};
+    if (total_out) *total_out = 0;
+    if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0)) return rc;
+    if (min_len == 0 || kind > SUFR_REPEAT_SUPERMAXIMAL) return SUFR_HIP_E_INVALID;
+    if (min_count < 2) min_count = 2;
+    const uint64_t s = f->meta.len_suffixes;
+    if (!s) return 0;
+    if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
+    const uint8_t* text = f->text;
+    // pass 1: l (several sequences only), the "differs from the previous rank" and "sequence start" flags, the pyramid
+    const uint64_t chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk;
+    RepeatHostPrep prep;
+    repeat_host_prepare(f, threads, prep);
+    const std::vector<uint64_t>&dw = prep.dw, &dp = prep.dp, &sw = prep.sw, &sp = prep.sp;
     // pass 2: every chunk decides its own ranks; the records of the chunks, one after the other, are in representative order
-    const RepeatHostAcc acc{f->sa, f->lcp, width, num > 1 ? ell.data() : nullptr, up.data(), s};
+    const RepeatHostAcc acc = prep.acc(f);
     const bool fill = cap > 0;                            // a counting call keeps no records
     std::vector<std::vector<RepeatRec>> recs(nchunks);
     std::vector<uint64_t> kept(nchunks, 0);
@@ -1218,6 +1239,142 @@ int sufr_file_lz(const sufr_file* f, uint64_t cap, uint64_t* start, uint64_t* le
     if (!start || !length || !source) return SUFR_HIP_E_INVALID;
     uint64_t o = 0;
     for (uint64_t p = 0; p < n; p += sufr::lz_step(lpf[p]), o++) { start[o] = p; length[o] = sufr::lz_step(lpf[p]); source[o] = lpf[p] ? src[p] : sufr::LZ_NONE; }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- sequence counts of repeats and k-common substrings (include/sufr_shared.h) ------------------
+#include "../../include/sufr_shared.h"
+#include "sufr_shared_scan.h"
+
+namespace {
+
+struct SharedRec { uint64_t rank, count, length, seqs; };
+
+// the refusals both calls share
+int shared_args(const sufr_file* f)
+{
+    if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0)) return rc;
+    return 0;
+}
+
+// P[0..s]: the exclusive prefix of H, H[j] the pairs (prev[r], r) with q(r) = j.  D and prev by one serial pass with a
+// last-seen table; the pairs threaded over chunks of ranks, added with atomics (integer adds commute); a serial prefix.
+std::vector<uint64_t> shared_host_prefix(const sufr_file* f, const RepeatHostAcc& acc, int threads)
+{
+    const uint64_t s = f->meta.len_suffixes, num = f->seq_starts.size();
+    const uint64_t* starts = f->seq_starts.data();
+    const int width = f->meta.index_width;
+    std::vector<uint64_t> prev(s), last(num ? num : 1, sufr::REP_NONE), P(s + 1, 0);
+    for (uint64_t r = 0; r < s; r++) {
+        const uint64_t d = sufr::shr_doc(starts, num, rdT(f->sa, width, r));
+        prev[r] = last[d];
+        last[d] = r;
+    }
+    uint64_t* H = P.data();
+    parallel_chunks(s, (uint64_t)1 << 14, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t r = b; r < e; r++)
+            if (prev[r] != sufr::REP_NONE) __atomic_fetch_add(&H[sufr::shr_pair(acc, s, prev[r], r)], (uint64_t)1, __ATOMIC_RELAXED);
+    });
+    uint64_t run = 0;
+    for (uint64_t j = 0; j <= s; j++) { const uint64_t h = P[j]; P[j] = run; run += h; }
+    return P;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_shared(const sufr_file* f, uint32_t kind, uint64_t min_len, uint64_t min_count, uint64_t max_count, uint64_t min_seqs,
+                     uint64_t max_seqs, uint64_t cap, uint64_t* rank, uint64_t* count, uint64_t* length, uint64_t* seqs,
+                     uint64_t* total_out, sufr_shared_stats* stats, int threads)
+{
+    if (stats) *stats = sufr_shared_stats{0, 0, 0, 0, 0};
+    if (total_out) *total_out = 0;
+    if (const int rc = shared_args(f)) return rc;
+    if (min_len == 0 || kind > SUFR_REPEAT_SUPERMAXIMAL || (max_seqs && min_seqs > max_seqs)) return SUFR_HIP_E_INVALID;
+    if (min_count < 2) min_count = 2;
+    const uint64_t s = f->meta.len_suffixes;
+    if (!s) return 0;
+    if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
+    const uint8_t* text = f->text;
+    const uint64_t chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk;
+    RepeatHostPrep prep;
+    repeat_host_prepare(f, threads, prep);
+    const std::vector<uint64_t>&dw = prep.dw, &dp = prep.dp, &sw = prep.sw, &sp = prep.sp;
+    const RepeatHostAcc acc = prep.acc(f);
+    const std::vector<uint64_t> P = shared_host_prefix(f, acc, threads);
+    // the find pass of sufr_file_repeats with one more column and one more filter
+    const bool fill = cap > 0;                            // a counting call keeps no records
+    std::vector<std::vector<SharedRec>> recs(nchunks);
+    std::vector<uint64_t> kept(nchunks, 0);
+    struct Best { uint64_t len, rep, rank, max_count, max_seqs; };
+    std::vector<Best> best(nchunks, Best{0, 0, 0, 0, 0});
+    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
+        std::vector<SharedRec>& mine = recs[b / chunk];
+        Best& bt = best[b / chunk];
+        for (uint64_t r = b ? b : 1; r < e; r++) {
+            const uint64_t v = acc.at(0, 0, r);
+            if (v < min_len) continue;
+            const uint64_t a = sufr::rep_search_left(acc, s, r, v);
+            if (a == sufr::REP_NONE || acc.at(0, 0, a) == v) continue;          // not the representative
+            const uint64_t z = sufr::rep_search_right(acc, s, r, v);
+            if (!sufr::rep_keep(acc, text, dw.data(), dp.data(), sw.data(), sp.data(), kind, min_count, max_count, a, z, v)) continue;
+            const uint64_t q = sufr::shr_seqs(P.data(), a, z);
+            if (!sufr::shr_keep(q, min_seqs, max_seqs)) continue;
+            kept[b / chunk]++;
+            if (fill) mine.push_back(SharedRec{a, z - a, v, q});
+            if (sufr::rep_better(v, r, bt.len, bt.rep)) { bt.len = v; bt.rep = r; bt.rank = a; }
+            if (z - a > bt.max_count) bt.max_count = z - a;
+            if (q > bt.max_seqs) bt.max_seqs = q;
+        }
+    });
+    sufr_shared_stats st{0, 0, 0, 0, 0};
+    uint64_t best_rep = 0;
+    for (uint64_t c = 0; c < nchunks; c++) {
+        st.records += kept[c];
+        if (sufr::rep_better(best[c].len, best[c].rep, st.longest, best_rep)) { st.longest = best[c].len; best_rep = best[c].rep; st.longest_rank = best[c].rank; }
+        if (best[c].max_count > st.max_count) st.max_count = best[c].max_count;
+        if (best[c].max_seqs > st.max_seqs) st.max_seqs = best[c].max_seqs;
+    }
+    if (stats) *stats = st;
+    if (total_out) *total_out = st.records;
+    if (st.records > cap) return SUFR_HIP_E_CAPACITY;
+    if (st.records && (!rank || !count || !length || !seqs)) return SUFR_HIP_E_INVALID;
+    uint64_t o = 0;
+    for (uint64_t c = 0; c < nchunks; c++)
+        for (const SharedRec& x : recs[c]) { rank[o] = x.rank; count[o] = x.count; length[o] = x.length; seqs[o] = x.seqs; o++; }
+    return 0;
+}
+
+int sufr_file_common(const sufr_file* f, uint64_t* common, int threads)
+{
+    if (const int rc = shared_args(f)) return rc;
+    if (!common) return SUFR_HIP_E_INVALID;
+    const uint64_t s = f->meta.len_suffixes, num = f->seq_starts.size() ? f->seq_starts.size() : 1;
+    for (uint64_t i = 0; i < num; i++) common[i] = 0;
+    if (!s) return 0;
+    if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
+    RepeatHostPrep prep;
+    repeat_host_prepare(f, threads, prep);
+    const RepeatHostAcc acc = prep.acc(f);
+    const std::vector<uint64_t> P = shared_host_prefix(f, acc, threads);
+    // common[k - 1] first holds the longest interval of exactly k sequences (a maximum: the order of the updates is
+    // immaterial), then the suffix maximum
+    parallel_chunks(s, (uint64_t)1 << 16, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t r = b ? b : 1; r < e; r++) {
+            const uint64_t v = acc.at(0, 0, r);
+            if (!v) continue;
+            const uint64_t a = sufr::rep_search_left(acc, s, r, v);
+            if (a == sufr::REP_NONE || acc.at(0, 0, a) == v) continue;          // not the representative
+            const uint64_t z = sufr::rep_search_right(acc, s, r, v);
+            uint64_t* at = &common[sufr::shr_seqs(P.data(), a, z) - 1];
+            uint64_t cur = __atomic_load_n(at, __ATOMIC_RELAXED);
+            while (v > cur && !__atomic_compare_exchange_n(at, &cur, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+        }
+    });
+    for (uint64_t i = num - 1; i > 0; i--) if (common[i] > common[i - 1]) common[i - 1] = common[i];
     return 0;
 }
 

@@ -256,9 +256,20 @@ __global__ __launch_bounds__(1024) void k_rep_best(const uint64_t* __restrict__ 
 
 namespace {
 
+// what the calls that search the clipped LCP share (repeats; sufr_shared.inc): the tiling, the accessor over l and its
+// pyramid, the flag words with their prefixes, and the tile sums of the search pass
 template <typename T>
-int repeats_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const sufr::KmerSeqs& q, const sufr::RepFilter& flt,
-                uint64_t cap, void* d_rank, void* d_count, void* d_length, uint64_t* total_out, sufr_repeat_stats* stats_out)
+struct RepPrep {
+    uint32_t tile, nw, levels, grid;
+    uint64_t ntiles, nwords, wgs;
+    sufr::RepAcc<T> acc;
+    sufr::RepBits bits;
+    uint64_t *t_cnt, *t_best, *d_stats;                  // ntiles + 1 kept counts (then bases), 4 candidates per tile, 4 stats
+};
+
+// the fold, the scans of the popcount totals and the coarser levels, enqueued on the context's stream
+template <typename T>
+int repeats_prepare(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const sufr::KmerSeqs& q, RepPrep<T>& P)
 {
     sufr::Pipeline& pl = ctx->pl;
     const uint64_t s = ix->ix.s;
@@ -295,8 +306,24 @@ int repeats_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, 
         hipLaunchKernelGGL(sufr::k_rep_level<T>, dim3((uint32_t)(need < wgs ? need : wgs)), dim3(256), 0, pl.stream,
                            (const T*)(up + sufr::rep_level_offset(s, k - 1)), n_in, up + sufr::rep_level_offset(s, k), n_out);
     }
-    const sufr::RepAcc<T> acc{clipped ? (const T*)ell : (const T*)d_lcp, (const T*)up, sa, s};
-    const sufr::RepBits bits{dw, dp, sw, sp};
+    P = RepPrep<T>{tile, nw, levels, grid, ntiles, nwords, wgs, sufr::RepAcc<T>{clipped ? (const T*)ell : (const T*)d_lcp, (const T*)up, sa, s},
+                   sufr::RepBits{dw, dp, sw, sp}, t_cnt, t_best, d_stats};
+    return 0;
+}
+
+template <typename T>
+int repeats_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const sufr::KmerSeqs& q, const sufr::RepFilter& flt,
+                uint64_t cap, void* d_rank, void* d_count, void* d_length, uint64_t* total_out, sufr_repeat_stats* stats_out)
+{
+    sufr::Pipeline& pl = ctx->pl;
+    RepPrep<T> P;
+    int rc;
+    if ((rc = repeats_prepare<T>(ctx, ix, d_lcp, q, P))) return rc;
+    const uint32_t tile = P.tile, grid = P.grid;
+    const uint64_t ntiles = P.ntiles;
+    const sufr::RepAcc<T> acc = P.acc;
+    const sufr::RepBits bits = P.bits;
+    uint64_t *t_cnt = P.t_cnt, *t_best = P.t_best, *d_stats = P.d_stats;
     hipLaunchKernelGGL((sufr::k_rep_find<T, false>), dim3(grid), dim3(256), 0, pl.stream, acc, ix->ix.text, bits, flt, tile, ntiles, t_cnt, t_best,
                        (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
     hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, t_cnt, ntiles, t_cnt + ntiles);

@@ -232,6 +232,14 @@ def _repeat_error(fn: str, rc: int) -> SufrHipError:
     return SufrHipError(rc, f"{fn}: " + msg)
 
 
+def _shared_error(fn: str, rc: int) -> SufrHipError:
+    msg = {-6: "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported",
+           -5: "more records than the arrays hold",
+           -1: "invalid argument (min_len must be at least 1, the kind 0, 1 or 2, min_seqs at most max_seqs, the sequence starts "
+               "must ascend from 0)"}.get(rc, "failed")
+    return SufrHipError(rc, f"{fn}: " + msg)
+
+
 def _lz_error(fn: str, rc: int) -> SufrHipError:
     msg = {-6: "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported",
            -5: "more factors than the arrays hold",
@@ -599,6 +607,36 @@ class SufrFile:
                 raise _lz_error("sufr_file_lz", rc)
         return out[0][:total.value], out[1][:total.value], out[2][:total.value], st.as_dict()
 
+    # -- sequence counts of repeats and k-common substrings (include/sufr_shared.h) --------------------------------------
+    def shared(self, kind="branching", min_len: int = 1, min_count: int = 2, max_count: int = 0, min_seqs: int = 0, max_seqs: int = 0,
+               threads: int = 0):
+        """(rank, count, length, seqs, stats): the records of `repeats` with the number of different sequences among the
+        occurrences of each, kept where min_seqs <= seqs <= max_seqs (0: open), and a dict of records / longest /
+        longest_rank / max_count / max_seqs.  With min_seqs = num_sequences, `longest` is the longest substring common to all
+        sequences; max_seqs = 1 keeps the repeats private to one sequence.  One call counts, one fills."""
+        from ._lib import REPEAT_KINDS, SharedStats
+        kind = REPEAT_KINDS.get(kind, kind)
+        total, st = C.c_uint64(0), SharedStats()
+        args = (self._h, kind, min_len, min_count, max_count, min_seqs, max_seqs)
+        rc = lib().sufr_file_shared(*args, 0, None, None, None, None, C.byref(total), C.byref(st), threads)
+        if rc not in (0, -5):
+            raise _shared_error("sufr_file_shared", rc)
+        out = [np.zeros(max(total.value, 1), dtype=np.uint64) for _ in range(4)]
+        if total.value:
+            rc = lib().sufr_file_shared(*args, total.value, *(o.ctypes.data for o in out), C.byref(total), C.byref(st), threads)
+            if rc != 0:
+                raise _shared_error("sufr_file_shared", rc)
+        return (*(o[:total.value] for o in out), st.as_dict())
+
+    def common(self, threads: int = 0):
+        """common[q - 1], q = 1 .. num_sequences: the length of the longest break-free string with indexed occurrences in at
+        least q of the sequences (0: none); a uint64 array, non-increasing."""
+        out = np.zeros(max(self.num_sequences, 1), dtype=np.uint64)
+        rc = lib().sufr_file_common(self._h, out.ctypes.data, threads)
+        if rc != 0:
+            raise _shared_error("sufr_file_common", rc)
+        return out
+
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
 
@@ -964,6 +1002,35 @@ class DeviceIndex:
                                                     out[1].data_ptr(), out[2].data_ptr(), C.byref(total), C.byref(stats)))
             self.ctx.synchronize()
         return out[0][:total.value], out[1][:total.value], out[2][:total.value], stats.as_dict()
+
+    # -- sequence counts of repeats and k-common substrings (include/sufr_shared.h) -------------------------------------
+    def shared_device(self, lcp, kind="branching", min_len: int = 1, min_count: int = 2, max_count: int = 0, min_seqs: int = 0,
+                      max_seqs: int = 0, seq_starts=None):
+        """SufrFile.shared on the device.  lcp and seq_starts as in kmers_device.  Returns (rank, count, length, seqs) as
+        int64 CUDA tensors and the stats dict, complete on return.  One call counts, one fills."""
+        import torch
+        from ._lib import REPEAT_KINDS, SharedStats
+        kind = REPEAT_KINDS.get(kind, kind)
+        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        total, stats = C.c_uint64(0), SharedStats()
+        args = (self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count, max_count, min_seqs, max_seqs)
+        rc = lib().sufr_hip_shared_device(*args, 0, None, None, None, None, C.byref(total), C.byref(stats))
+        if rc != -5:
+            self.ctx.check(rc)
+        out = [torch.empty(max(total.value, 1), dtype=torch.int64, device=lcp.device) for _ in range(4)]
+        if total.value:
+            self.ctx.check(lib().sufr_hip_shared_device(*args, total.value, *(o.data_ptr() for o in out), C.byref(total), C.byref(stats)))
+            self.ctx.synchronize()
+        return (*(o[:total.value] for o in out), stats.as_dict())
+
+    def common_device(self, lcp, seq_starts=None):
+        """SufrFile.common on the device: an int64 CUDA tensor of one entry per sequence, complete on return."""
+        import torch
+        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        out = torch.empty(max(st_n if st_ptr else 0, 1), dtype=torch.int64, device=lcp.device)
+        self.ctx.check(lib().sufr_hip_common_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, out.data_ptr()))
+        self.ctx.synchronize()
+        return out
 
     # -- MEMs (include/sufr_mem.h) -----------------------------------------------------------------------------------
     def mems_device(self, qbytes, offsets, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
