@@ -272,7 +272,7 @@ int kmers_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, co
     bool ok = hipMemsetAsync(d_stats, 0, 32, pl.stream) == hipSuccess;
     if (by_position && d_occ) ok = ok && hipMemsetAsync(d_occ, 0, q.n * sizeof(T), pl.stream) == hipSuccess;
     if (!ok) { pl.set_error("kmers: memset failed"); return SUFR_HIP_E_HIP; }
-    const T* sa = (const T*)(ix->ix.sa64 ? (const void*)ix->ix.sa64 : (const void*)ix->ix.sa);
+    const T* sa = index_sa<T>(ix);
     const uint64_t wgs = batch_grid(pl);
     const uint32_t grid = (uint32_t)(ntiles < wgs ? ntiles : wgs);
     hipLaunchKernelGGL(sufr::k_kmer_fold<T>, dim3(grid), dim3(256), 0, pl.stream, sa, (const T*)d_lcp, s, q, k, tile, ntiles, hbits, wbits,
@@ -324,8 +324,7 @@ int sufr_hip_kmers_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const voi
     const bool by_position = (flags & SUFR_KMER_BY_POSITION) != 0;
     if (!ix->ix.s) return kmer_nothing(pl, by_position ? d_occ : nullptr, ix->ix.n * (uint64_t)ix->sa_width);
     if ((rc = kmer_prepare(ctx, ix, d_lcp, seq_starts, num_sequences, "kmers", q))) return rc;
-    return ix->sa_width == 8 ? kmers_run<uint64_t>(ctx, ix, d_lcp, q, k, by_position, bins, d_hist, d_occ, stats_out)
-                             : kmers_run<uint32_t>(ctx, ix, d_lcp, q, k, by_position, bins, d_hist, d_occ, stats_out);
+    return by_width(ix, [&](auto w) { return kmers_run<decltype(w)>(ctx, ix, d_lcp, q, k, by_position, bins, d_hist, d_occ, stats_out); });
 }
 
 int sufr_hip_unique_lengths_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const uint64_t* seq_starts,
@@ -333,13 +332,8 @@ int sufr_hip_unique_lengths_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, 
 {
     if (!ctx || !ix) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
-    pl.err.clear();
     int rc;
-    if ((rc = query_check(ctx, ix, "unique lengths"))) return rc;
-    if (ix->built_mql > 0) {
-        pl.set_error("unique_lengths: the index was built with max_query_len " + std::to_string(ix->built_mql) + ", its LCP is capped");
-        return SUFR_HIP_E_UNSUPPORTED;
-    }
+    if ((rc = lcp_refusals(ctx, ix, "unique lengths", "unique_lengths"))) return rc;
     sufr::KmerSeqs q;
     const bool by_position = (flags & SUFR_KMER_BY_POSITION) != 0;
     if (!ix->ix.s) return kmer_nothing(pl, by_position ? d_out : nullptr, ix->ix.n * (uint64_t)ix->sa_width);
@@ -348,12 +342,12 @@ int sufr_hip_unique_lengths_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, 
     const uint64_t s = ix->ix.s, wgs = batch_grid(pl), need = (s + 255) / 256;
     const uint32_t grid = (uint32_t)(need < wgs ? need : wgs);
     if (by_position && hipMemsetAsync(d_out, 0, q.n * (uint64_t)ix->sa_width, pl.stream) != hipSuccess) { pl.set_error("unique_lengths: memset failed"); return SUFR_HIP_E_HIP; }
-    if (ix->sa_width == 8)
-        hipLaunchKernelGGL(sufr::k_unique_len<uint64_t>, dim3(grid), dim3(256), 0, pl.stream, ix->ix.sa64, (const uint64_t*)d_lcp, s, q,
-                           (uint32_t)by_position, (uint64_t*)d_out);
-    else
-        hipLaunchKernelGGL(sufr::k_unique_len<uint32_t>, dim3(grid), dim3(256), 0, pl.stream, ix->ix.sa, (const uint32_t*)d_lcp, s, q,
-                           (uint32_t)by_position, (uint32_t*)d_out);
+    by_width(ix, [&](auto w) {
+        using T = decltype(w);
+        hipLaunchKernelGGL(sufr::k_unique_len<T>, dim3(grid), dim3(256), 0, pl.stream, index_sa<T>(ix), (const T*)d_lcp, s, q, (uint32_t)by_position,
+                           (T*)d_out);
+        return 0;
+    });
     return launch_status(pl, "unique_lengths");
 }
 

@@ -23,6 +23,14 @@
 #define SUFR_HD static inline
 #endif
 #endif
+// SUFR_HD for a member function defined in its class (there `static` would mean something else, and `inline` is implied)
+#ifndef SUFR_HD_MEMBER
+#if defined(__HIPCC__)
+#define SUFR_HD_MEMBER __host__ __device__ inline __attribute__((always_inline))
+#else
+#define SUFR_HD_MEMBER
+#endif
+#endif
 
 namespace sufr {
 

@@ -12,7 +12,8 @@
 // k_lz_lpf       a lane per rank: two searches, two range minima, the binary search of the sequence starts for d(p), then
 //                the scatter of LPF and SRC to position SA[r] (the buffers are zeroed / NONE-filled first, so positions that
 //                are not indexed read as defined).  The SA and the LCP of up to LZ_STAGE ranks of the tile and their level-1
-//                entries are staged in LDS (RepStaged over LzAcc), so that a scan step is an LDS read.
+//                entries are staged in LDS (RepStaged over LzAcc, the window by rep_tile_window; one loop fills both
+//                arrays), so that a scan step is an LDS read.
 // k_lz_table     the parse, table phase.  A workgroup per tile of B text positions: every position's entry (the last
 //                in-tile position on its chain, the hops to it) by pointer doubling in LDS -- one 32-bit word per position,
 //                updated in place: a word is always a true (position on the chain, hops to it) pair, a round composes two
@@ -26,7 +27,8 @@
 //                (entry k is written after entry k was read: k never runs ahead of the chain), then a lane per factor.
 //                Counting run: the tile's literals and its longest factor.  Writing run: (start, length, source) behind the
 //                tile's base, in text order.
-// k_lz_best      one workgroup: the stats from the tiles' candidates by comparisons of (length, start); no atomics.
+// k_lz_best      one workgroup: the stats from the tiles' candidates by comparisons of (length, start); no atomics.  (Not
+//                k_rep_best: it sums a column and has three.)  The host tail of the counted call is report_total.
 // No scratch; LDS: k_lz_lpf 16.5 KB (32-bit arrays) or 33 KB (64-bit), k_lz_table 64 KB, k_lz_emit 32 KB.
 
 #include "sufr_lz_scan.h"
@@ -69,18 +71,17 @@ __global__ __launch_bounds__(256) void k_lz_lpf(LzAcc<T> gsa, LzAcc<T> glcp, uin
 {
     __shared__ T s_sa[LZ_STAGE], s_lcp[LZ_STAGE], s_sa1[LZ_STAGE / 64], s_lcp1[LZ_STAGE / 64];
     RepStaged<T, LzAcc<T>> sa{gsa, s_sa, s_sa1, 0, 0, 0, 0}, lcp{glcp, s_lcp, s_lcp1, 0, 0, 0, 0};
-    const bool has_l1 = s > 64;                          // (level 1 exists)
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         for (uint32_t it = 0; it < tile; it += 256) {
             const uint64_t r = t * tile + it + threadIdx.x;
             if (r - threadIdx.x >= s) break;             // (uniform: past the end of the array)
-            if (it % LZ_STAGE == 0) {                    // (uniform) the next window of the tile: LZ_STAGE ranks, or what is left
-                const uint64_t w0 = t * tile + it, left = tile - it < LZ_STAGE ? tile - it : LZ_STAGE,
-                               len = w0 + left < s ? left : s - w0, vlen = has_l1 ? (len + 63) / 64 : 0;
+            if (it % LZ_STAGE == 0) {                    // (uniform) the next window of the tile, of both arrays
+                const RepWindow win = rep_tile_window(t, tile, it, LZ_STAGE, s);
                 __syncthreads();                         // (the lanes are done with the window before)
-                for (uint64_t i = threadIdx.x; i < len; i += 256) { s_sa[i] = gsa.l0[w0 + i]; s_lcp[i] = glcp.l0[w0 + i]; }
-                if (threadIdx.x < vlen) { s_sa1[threadIdx.x] = gsa.up[(w0 >> 6) + threadIdx.x]; s_lcp1[threadIdx.x] = glcp.up[(w0 >> 6) + threadIdx.x]; }
-                sa.w0 = lcp.w0 = w0; sa.len = lcp.len = len; sa.v0 = lcp.v0 = w0 >> 6; sa.vlen = lcp.vlen = vlen;
+                // (one loop fills both arrays: two calls of RepStaged::stage cost the 64-bit kernel four VGPRs)
+                for (uint64_t i = threadIdx.x; i < win.len; i += 256) { s_sa[i] = gsa.l0[win.w0 + i]; s_lcp[i] = glcp.l0[win.w0 + i]; }
+                if (threadIdx.x < win.vlen) { s_sa1[threadIdx.x] = gsa.up[(win.w0 >> 6) + threadIdx.x]; s_lcp1[threadIdx.x] = glcp.up[(win.w0 >> 6) + threadIdx.x]; }
+                sa.w0 = lcp.w0 = win.w0; sa.len = lcp.len = win.len; sa.v0 = lcp.v0 = win.w0 >> 6; sa.vlen = lcp.vlen = win.vlen;
                 __syncthreads();
             }
             if (r < s) {
@@ -250,7 +251,7 @@ int lz_lpf_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, c
     if (const int rc = pl.ensure(ctx->lzpyr, 2 * plen * sizeof(T))) return rc;
     T* up_sa = (T*)ctx->lzpyr.p;
     T* up_lcp = up_sa + plen;
-    const T* sa = (const T*)(ix->ix.sa64 ? (const void*)ix->ix.sa64 : (const void*)ix->ix.sa);
+    const T* sa = index_sa<T>(ix);
     const uint64_t wgs = batch_grid(pl);
     if (levels) {
         const uint64_t n1 = sufr::rep_level_size(s, 1), need = (n1 + 3) / 4;
@@ -303,22 +304,15 @@ int lz_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const
     hipLaunchKernelGGL((sufr::k_lz_emit<T, false>), dim3(grid), dim3(256), 0, pl.stream, (const T*)lpf, (const T*)src, n, B, ntiles,
                        (const uint32_t*)t_entry, (const uint64_t*)t_base, t_stat, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
     hipLaunchKernelGGL(sufr::k_lz_best, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)t_stat, ntiles, (const uint64_t*)d_total, d_stats);
-    if ((rc = launch_status(pl, "lz"))) return rc;
     unsigned long long h[4];
-    if ((rc = read_totals(pl, d_stats, 4, h, "lz", "reading the total failed"))) return rc;
+    rc = report_total(pl, "lz", "factors", d_stats, 4, h, cap, total_out, d_start && d_length && d_source);
 #ifdef SUFR_HIP_PROBES
     float ms = 0;
     if (stamp && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) fprintf(stderr, "lz: chain kernel %.3f ms (%llu tiles of %u positions)\n", ms, (unsigned long long)ntiles, B);
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
 #endif
-    if (total_out) *total_out = h[0];
     if (stats_out) *stats_out = sufr_lz_stats{h[0], h[1], h[2], h[3]};
-    if (h[0] > cap) {
-        pl.set_error("lz: " + std::to_string(h[0]) + " factors, room for " + std::to_string(cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    if (!h[0]) return 0;
-    if (!d_start || !d_length || !d_source) { pl.set_error("lz: no output arrays"); return SUFR_HIP_E_INVALID; }
+    if (rc || !h[0]) return rc;
     hipLaunchKernelGGL((sufr::k_lz_emit<T, true>), dim3(grid), dim3(256), 0, pl.stream, (const T*)lpf, (const T*)src, n, B, ntiles,
                        (const uint32_t*)t_entry, (const uint64_t*)t_base, t_stat, (uint64_t*)d_start, (uint64_t*)d_length, (uint64_t*)d_source);
     return launch_status(pl, "lz");
@@ -328,13 +322,7 @@ int lz_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const
 int lz_prepare(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const uint64_t* seq_starts, uint64_t num_sequences, const char* what,
                sufr::KmerSeqs& q)
 {
-    sufr::Pipeline& pl = ctx->pl;
-    pl.err.clear();
-    if (const int rc = query_check(ctx, ix, "longest previous factors")) return rc;
-    if (ix->built_mql > 0) {
-        pl.set_error(std::string(what) + ": the index was built with max_query_len " + std::to_string(ix->built_mql) + ", its LCP is capped");
-        return SUFR_HIP_E_UNSUPPORTED;
-    }
+    if (const int rc = lcp_refusals(ctx, ix, "longest previous factors", what)) return rc;
     return kmer_prepare(ctx, ix, d_lcp, seq_starts, num_sequences, what, q);
 }
 
@@ -358,8 +346,7 @@ int sufr_hip_lpf_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void*
     if (!ctx || !ix) return SUFR_HIP_E_INVALID;
     sufr::KmerSeqs q;
     if (const int rc = lz_prepare(ctx, ix, d_lcp, seq_starts, num_sequences, "lpf", q)) return rc;
-    return ix->sa_width == 8 ? lz_lpf_run<uint64_t>(ctx, ix, d_lcp, q, (uint64_t*)d_lpf, (uint64_t*)d_src, "lpf")
-                             : lz_lpf_run<uint32_t>(ctx, ix, d_lcp, q, (uint32_t*)d_lpf, (uint32_t*)d_src, "lpf");
+    return by_width(ix, [&](auto w) { return lz_lpf_run(ctx, ix, d_lcp, q, (decltype(w)*)d_lpf, (decltype(w)*)d_src, "lpf"); });
 }
 
 int sufr_hip_lz_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const uint64_t* seq_starts, uint64_t num_sequences,
@@ -371,8 +358,7 @@ int sufr_hip_lz_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* 
     sufr::KmerSeqs q;
     if (const int rc = lz_prepare(ctx, ix, d_lcp, seq_starts, num_sequences, "lz", q)) return rc;
     if (!ix->ix.n) return 0;
-    return ix->sa_width == 8 ? lz_run<uint64_t>(ctx, ix, d_lcp, q, cap, d_start, d_length, d_source, total_out, stats_out)
-                             : lz_run<uint32_t>(ctx, ix, d_lcp, q, cap, d_start, d_length, d_source, total_out, stats_out);
+    return by_width(ix, [&](auto w) { return lz_run<decltype(w)>(ctx, ix, d_lcp, q, cap, d_start, d_length, d_source, total_out, stats_out); });
 }
 
 }  // extern "C"

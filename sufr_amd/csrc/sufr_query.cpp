@@ -984,6 +984,7 @@ int sufr_file_unique_lengths(const sufr_file* f, uint32_t flags, void* out, int 
 // ---- repeats of the indexed text (include/sufr_repeat.h) ----------------------------------------
 #include "../../include/sufr_repeat.h"
 #include "sufr_repeat_scan.h"
+#include "sufr_shared_scan.h"
 
 namespace {
 
@@ -1001,8 +1002,6 @@ struct RepeatHostAcc {
     }
     uint64_t sa(uint64_t r) const { return rdT(sa_bytes, width, r); }
 };
-
-struct RepeatRec { uint64_t rank, count, length; };
 
 // pass 1 of the calls that search the clipped LCP (repeats, shared): l (several sequences only), the "differs from the
 // previous rank" and "sequence start" flag words with their popcount prefixes, and the coarser levels of the min pyramid
@@ -1059,16 +1058,57 @@ void repeat_host_prepare(const sufr_file* f, int threads, RepeatHostPrep& P)
         dp[i] = nd; sp[i] = ns;
         nd += (uint64_t)__builtin_popcountll(dw[i]); ns += (uint64_t)__builtin_popcountll(sw[i]);
     }
-    for (uint32_t k = 2; k <= levels; k++) {
-        const uint64_t* in = up.data() + sufr::rep_level_offset(s, k - 1);
-        uint64_t* out = up.data() + sufr::rep_level_offset(s, k);
-        const uint64_t n_in = sufr::rep_level_size(s, k - 1), n_out = sufr::rep_level_size(s, k);
-        for (uint64_t i = 0; i < n_out; i++) {
-            uint64_t low = ~(uint64_t)0;
-            for (uint64_t j = i * 64; j < n_in && j < i * 64 + 64; j++) if (in[j] < low) low = in[j];
-            out[i] = low;
+    for (uint32_t k = 2; k <= levels; k++)
+        sufr::rep_level_up(up.data() + sufr::rep_level_offset(s, k - 1), sufr::rep_level_size(s, k - 1), up.data() + sufr::rep_level_offset(s, k),
+                           sufr::rep_level_size(s, k));
+}
+
+struct RepeatHostFilter { uint32_t kind; uint64_t min_len, min_count, max_count, min_seqs, max_seqs; };
+
+// where the find pass leaves its records (seqs: only with P), and what it met: the kept ranks and their RepBest
+struct RepeatHostOut {
+    uint64_t cap, *rank, *count, *length, *seqs;
+    uint64_t records;
+    sufr::RepBest best;
+};
+
+// pass 2 of repeats (P null: no sequences are counted, best.seq stays 0) and of shared: every chunk decides its own ranks;
+// the records of the chunks, one after the other, are in representative order.  A counting call (fill false) keeps none.
+// Then the capacity rule and the copy-out.
+int repeat_host_find(const sufr_file* f, const RepeatHostPrep& prep, const uint64_t* P, const RepeatHostFilter& flt, bool fill, int threads,
+                     RepeatHostOut& out)
+{
+    struct Rec { uint64_t rank, count, length, seqs; };
+    const uint64_t s = f->meta.len_suffixes, chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk;
+    const RepeatHostAcc acc = prep.acc(f);
+    std::vector<std::vector<Rec>> recs(nchunks);
+    std::vector<uint64_t> kept(nchunks, 0);
+    std::vector<sufr::RepBest> best(nchunks, sufr::RepBest{0, 0, 0, 0, 0});
+    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t r = b ? b : 1; r < e; r++)
+            sufr::rep_interval(acc, s, r, flt.min_len, [&](uint64_t a, uint64_t z, uint64_t v) {
+                if (!sufr::rep_keep(acc, f->text, prep.dw.data(), prep.dp.data(), prep.sw.data(), prep.sp.data(), flt.kind, flt.min_count,
+                                    flt.max_count, a, z, v)) return;
+                const uint64_t q = P ? sufr::shr_seqs(P, a, z) : 0;
+                if (P && !sufr::shr_keep(q, flt.min_seqs, flt.max_seqs)) return;
+                kept[b / chunk]++;
+                if (fill) recs[b / chunk].push_back(Rec{a, z - a, v, q});
+                best[b / chunk].take(v, r, a, z - a, q);
+            });
+    });
+    out.records = 0;
+    out.best = sufr::RepBest{0, 0, 0, 0, 0};
+    for (uint64_t c = 0; c < nchunks; c++) { out.records += kept[c]; out.best.merge(best[c]); }
+    if (out.records > out.cap) return SUFR_HIP_E_CAPACITY;
+    if (out.records && (!out.rank || !out.count || !out.length || (P && !out.seqs))) return SUFR_HIP_E_INVALID;
+    uint64_t o = 0;
+    for (uint64_t c = 0; c < nchunks; c++)
+        for (const Rec& x : recs[c]) {
+            out.rank[o] = x.rank; out.count[o] = x.count; out.length[o] = x.length;
+            if (P) out.seqs[o] = x.seqs;
+            o++;
         }
-    }
+    return 0;
 }
 
 }  // namespace
@@ -1082,54 +1122,16 @@ int sufr_file_repeats(const sufr_file* f, uint32_t kind, uint64_t min_len, uint6
     if (total_out) *total_out = 0;
     if (const int rc = kmer_args(f, f && f->meta.max_query_len > 0)) return rc;
     if (min_len == 0 || kind > SUFR_REPEAT_SUPERMAXIMAL) return SUFR_HIP_E_INVALID;
-    if (min_count < 2) min_count = 2;
-    const uint64_t s = f->meta.len_suffixes;
-    if (!s) return 0;
+    if (!f->meta.len_suffixes) return 0;
     if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
-    const uint8_t* text = f->text;
     // pass 1: l (several sequences only), the "differs from the previous rank" and "sequence start" flags, the pyramid
-    const uint64_t chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk;
     RepeatHostPrep prep;
     repeat_host_prepare(f, threads, prep);
-    const std::vector<uint64_t>&dw = prep.dw, &dp = prep.dp, &sw = prep.sw, &sp = prep.sp;
-    // pass 2: every chunk decides its own ranks; the records of the chunks, one after the other, are in representative order
-    const RepeatHostAcc acc = prep.acc(f);
-    const bool fill = cap > 0;                            // a counting call keeps no records
-    std::vector<std::vector<RepeatRec>> recs(nchunks);
-    std::vector<uint64_t> kept(nchunks, 0);
-    struct Best { uint64_t len, rep, rank, max_count; };
-    std::vector<Best> best(nchunks, Best{0, 0, 0, 0});
-    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
-        std::vector<RepeatRec>& mine = recs[b / chunk];
-        Best& bt = best[b / chunk];
-        for (uint64_t r = b ? b : 1; r < e; r++) {
-            const uint64_t v = acc.at(0, 0, r);
-            if (v < min_len) continue;
-            const uint64_t a = sufr::rep_search_left(acc, s, r, v);
-            if (a == sufr::REP_NONE || acc.at(0, 0, a) == v) continue;          // not the representative
-            const uint64_t z = sufr::rep_search_right(acc, s, r, v);
-            if (!sufr::rep_keep(acc, text, dw.data(), dp.data(), sw.data(), sp.data(), kind, min_count, max_count, a, z, v)) continue;
-            kept[b / chunk]++;
-            if (fill) mine.push_back(RepeatRec{a, z - a, v});
-            if (sufr::rep_better(v, r, bt.len, bt.rep)) { bt.len = v; bt.rep = r; bt.rank = a; }
-            if (z - a > bt.max_count) bt.max_count = z - a;
-        }
-    });
-    sufr_repeat_stats st{0, 0, 0, 0};
-    uint64_t best_rep = 0;
-    for (uint64_t c = 0; c < nchunks; c++) {
-        st.records += kept[c];
-        if (sufr::rep_better(best[c].len, best[c].rep, st.longest, best_rep)) { st.longest = best[c].len; best_rep = best[c].rep; st.longest_rank = best[c].rank; }
-        if (best[c].max_count > st.max_count) st.max_count = best[c].max_count;
-    }
-    if (stats) *stats = st;
-    if (total_out) *total_out = st.records;
-    if (st.records > cap) return SUFR_HIP_E_CAPACITY;
-    if (st.records && (!rank || !count || !length)) return SUFR_HIP_E_INVALID;
-    uint64_t o = 0;
-    for (uint64_t c = 0; c < nchunks; c++)
-        for (const RepeatRec& x : recs[c]) { rank[o] = x.rank; count[o] = x.count; length[o] = x.length; o++; }
-    return 0;
+    RepeatHostOut out{cap, rank, count, length, nullptr, 0, {}};
+    const int rc = repeat_host_find(f, prep, nullptr, RepeatHostFilter{kind, min_len, min_count < 2 ? 2 : min_count, max_count, 0, 0}, cap > 0, threads, out);
+    if (stats) *stats = sufr_repeat_stats{out.records, out.best.len, out.best.rank, out.best.cnt};
+    if (total_out) *total_out = out.records;
+    return rc;
 }
 
 }  // extern "C"
@@ -1162,16 +1164,9 @@ std::vector<uint64_t> lz_pyramid(const uint8_t* bytes, int width, uint64_t s, in
             up[r0 / 64] = low;
         }
     });
-    for (uint32_t k = 2; k <= levels; k++) {
-        const uint64_t* in = up.data() + sufr::rep_level_offset(s, k - 1);
-        uint64_t* out = up.data() + sufr::rep_level_offset(s, k);
-        const uint64_t n_in = sufr::rep_level_size(s, k - 1), n_out = sufr::rep_level_size(s, k);
-        for (uint64_t i = 0; i < n_out; i++) {
-            uint64_t low = ~(uint64_t)0;
-            for (uint64_t j = i * 64; j < n_in && j < i * 64 + 64; j++) if (in[j] < low) low = in[j];
-            out[i] = low;
-        }
-    }
+    for (uint32_t k = 2; k <= levels; k++)
+        sufr::rep_level_up(up.data() + sufr::rep_level_offset(s, k - 1), sufr::rep_level_size(s, k - 1), up.data() + sufr::rep_level_offset(s, k),
+                           sufr::rep_level_size(s, k));
     return up;
 }
 
@@ -1250,8 +1245,6 @@ int sufr_file_lz(const sufr_file* f, uint64_t cap, uint64_t* start, uint64_t* le
 
 namespace {
 
-struct SharedRec { uint64_t rank, count, length, seqs; };
-
 // the refusals both calls share
 int shared_args(const sufr_file* f)
 {
@@ -1294,58 +1287,17 @@ int sufr_file_shared(const sufr_file* f, uint32_t kind, uint64_t min_len, uint64
     if (total_out) *total_out = 0;
     if (const int rc = shared_args(f)) return rc;
     if (min_len == 0 || kind > SUFR_REPEAT_SUPERMAXIMAL || (max_seqs && min_seqs > max_seqs)) return SUFR_HIP_E_INVALID;
-    if (min_count < 2) min_count = 2;
-    const uint64_t s = f->meta.len_suffixes;
-    if (!s) return 0;
+    if (!f->meta.len_suffixes) return 0;
     if (!kmer_starts_ok(*f)) return SUFR_HIP_E_INVALID;
-    const uint8_t* text = f->text;
-    const uint64_t chunk = (uint64_t)1 << 16, nchunks = (s + chunk - 1) / chunk;
     RepeatHostPrep prep;
     repeat_host_prepare(f, threads, prep);
-    const std::vector<uint64_t>&dw = prep.dw, &dp = prep.dp, &sw = prep.sw, &sp = prep.sp;
-    const RepeatHostAcc acc = prep.acc(f);
-    const std::vector<uint64_t> P = shared_host_prefix(f, acc, threads);
-    // the find pass of sufr_file_repeats with one more column and one more filter
-    const bool fill = cap > 0;                            // a counting call keeps no records
-    std::vector<std::vector<SharedRec>> recs(nchunks);
-    std::vector<uint64_t> kept(nchunks, 0);
-    struct Best { uint64_t len, rep, rank, max_count, max_seqs; };
-    std::vector<Best> best(nchunks, Best{0, 0, 0, 0, 0});
-    parallel_chunks(s, chunk, threads, [&](uint64_t b, uint64_t e) {
-        std::vector<SharedRec>& mine = recs[b / chunk];
-        Best& bt = best[b / chunk];
-        for (uint64_t r = b ? b : 1; r < e; r++) {
-            const uint64_t v = acc.at(0, 0, r);
-            if (v < min_len) continue;
-            const uint64_t a = sufr::rep_search_left(acc, s, r, v);
-            if (a == sufr::REP_NONE || acc.at(0, 0, a) == v) continue;          // not the representative
-            const uint64_t z = sufr::rep_search_right(acc, s, r, v);
-            if (!sufr::rep_keep(acc, text, dw.data(), dp.data(), sw.data(), sp.data(), kind, min_count, max_count, a, z, v)) continue;
-            const uint64_t q = sufr::shr_seqs(P.data(), a, z);
-            if (!sufr::shr_keep(q, min_seqs, max_seqs)) continue;
-            kept[b / chunk]++;
-            if (fill) mine.push_back(SharedRec{a, z - a, v, q});
-            if (sufr::rep_better(v, r, bt.len, bt.rep)) { bt.len = v; bt.rep = r; bt.rank = a; }
-            if (z - a > bt.max_count) bt.max_count = z - a;
-            if (q > bt.max_seqs) bt.max_seqs = q;
-        }
-    });
-    sufr_shared_stats st{0, 0, 0, 0, 0};
-    uint64_t best_rep = 0;
-    for (uint64_t c = 0; c < nchunks; c++) {
-        st.records += kept[c];
-        if (sufr::rep_better(best[c].len, best[c].rep, st.longest, best_rep)) { st.longest = best[c].len; best_rep = best[c].rep; st.longest_rank = best[c].rank; }
-        if (best[c].max_count > st.max_count) st.max_count = best[c].max_count;
-        if (best[c].max_seqs > st.max_seqs) st.max_seqs = best[c].max_seqs;
-    }
-    if (stats) *stats = st;
-    if (total_out) *total_out = st.records;
-    if (st.records > cap) return SUFR_HIP_E_CAPACITY;
-    if (st.records && (!rank || !count || !length || !seqs)) return SUFR_HIP_E_INVALID;
-    uint64_t o = 0;
-    for (uint64_t c = 0; c < nchunks; c++)
-        for (const SharedRec& x : recs[c]) { rank[o] = x.rank; count[o] = x.count; length[o] = x.length; seqs[o] = x.seqs; o++; }
-    return 0;
+    const std::vector<uint64_t> P = shared_host_prefix(f, prep.acc(f), threads);
+    RepeatHostOut out{cap, rank, count, length, seqs, 0, {}};
+    const int rc = repeat_host_find(f, prep, P.data(), RepeatHostFilter{kind, min_len, min_count < 2 ? 2 : min_count, max_count, min_seqs, max_seqs},
+                                    cap > 0, threads, out);
+    if (stats) *stats = sufr_shared_stats{out.records, out.best.len, out.best.rank, out.best.cnt, out.best.seq};
+    if (total_out) *total_out = out.records;
+    return rc;
 }
 
 int sufr_file_common(const sufr_file* f, uint64_t* common, int threads)
@@ -1363,16 +1315,12 @@ int sufr_file_common(const sufr_file* f, uint64_t* common, int threads)
     // common[k - 1] first holds the longest interval of exactly k sequences (a maximum: the order of the updates is
     // immaterial), then the suffix maximum
     parallel_chunks(s, (uint64_t)1 << 16, threads, [&](uint64_t b, uint64_t e) {
-        for (uint64_t r = b ? b : 1; r < e; r++) {
-            const uint64_t v = acc.at(0, 0, r);
-            if (!v) continue;
-            const uint64_t a = sufr::rep_search_left(acc, s, r, v);
-            if (a == sufr::REP_NONE || acc.at(0, 0, a) == v) continue;          // not the representative
-            const uint64_t z = sufr::rep_search_right(acc, s, r, v);
-            uint64_t* at = &common[sufr::shr_seqs(P.data(), a, z) - 1];
-            uint64_t cur = __atomic_load_n(at, __ATOMIC_RELAXED);
-            while (v > cur && !__atomic_compare_exchange_n(at, &cur, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-        }
+        for (uint64_t r = b ? b : 1; r < e; r++)
+            sufr::rep_interval(acc, s, r, 1, [&](uint64_t a, uint64_t z, uint64_t v) {
+                uint64_t* at = &common[sufr::shr_seqs(P.data(), a, z) - 1];
+                uint64_t cur = __atomic_load_n(at, __ATOMIC_RELAXED);
+                while (v > cur && !__atomic_compare_exchange_n(at, &cur, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+            });
     });
     for (uint64_t i = num - 1; i > 0; i--) if (common[i] > common[i - 1]) common[i - 1] = common[i];
     return 0;

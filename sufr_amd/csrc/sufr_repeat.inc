@@ -15,19 +15,27 @@
 // k_locate_scan  (sufr_search.inc) one workgroup: the tile totals to bases, twice.
 // k_rep_addbase  the tile bases onto the word prefixes (s / 64 entries).
 // k_rep_level    one launch per level >= 2: a wave per entry, 64 entries of the level below.
-// k_rep_find     a lane per rank with l[r] >= min_len: the left search with <= (the rank is the representative iff the
-//                value found is smaller, and that index is a), then the right search for b, the count filter and the kind.
-//                The l of up to 4096 ranks of the tile, and their level-1 entries, are staged in LDS and searched there
-//                first (RepStaged); a search that leaves the window reads the pyramid in memory and descends again.
-//                Counting run: kept ranks per tile and the tile's longest / largest count.  Writing run: the same decisions,
-//                compacted in rank order behind the tile's base.  The cost of a rank is bounded by 2 x 64 x levels reads per
-//                search whatever b - a is; only the supermaximal walk (rep_supermaximal) is longer, and says when.
-// k_rep_best     one workgroup: the stats from the tiles' candidates -- comparisons of (length, representative), no atomics,
-//                so nothing depends on an order.
+// k_rep_find     <T, MODE, SEQS>, the one find pass of repeats (SEQS false) and of shared and common (sufr_shared.inc, SEQS
+//                true).  A lane per rank: rep_interval -- l[r] >= min_len, the left search with <= (the rank is the
+//                representative iff the value found is smaller, and that index is a), the right search for b -- then the
+//                count filter and the kind (rep_keep) and, with SEQS, seqs from two reads of P and its filter.  The l of up
+//                to 4096 ranks of the tile, and their level-1 entries, are staged in LDS and searched there first
+//                (RepStaged::stage over rep_tile_window); a search that leaves the window reads the pyramid in memory and
+//                descends again.  REP_COUNT: kept ranks per tile and the tile's RepBest (longest / largest count / largest
+//                seqs), reduced over lanes, waves and the workgroup by RepBest::merge.  REP_WRITE: the same decisions,
+//                compacted in rank order behind the tile's base.  REP_PROFILE (SEQS only): an atomic max per interval that
+//                raises its entry.  The cost of a rank is bounded by 2 x 64 x levels reads per search whatever b - a is; only
+//                the supermaximal walk (rep_supermaximal) is longer, and says when.
+// k_rep_best     <NCOL> one workgroup: the stats from the tiles' candidates by RepBest::merge -- comparisons of (length,
+//                representative), no atomics, so nothing depends on an order.
 // A workgroup takes tiles t = blockIdx.x, blockIdx.x + gridDim.x, ...; no scratch; k_rep_find holds 16.4 KB of LDS (32-bit
-// arrays) or 32.7 KB (64-bit), the others under 33 KB.
+// arrays) or 32.7 KB (64-bit) without SEQS, 16.8 / 33.5 KB with it; k_rep_best 32 KB (4 columns) or 40 KB (5).
+// Host: repeats_prepare (the fold, the scans, the levels: RepPrep, which also owns the scratch of the find pass) and
+// repeats_find<T, SEQS> (counting launch, k_locate_scan, k_rep_best, report_total, writing launch), which sufr_shared.inc calls
+// with SEQS set.
 
 #include "sufr_repeat_scan.h"
+#include "sufr_shared_scan.h"
 
 namespace sufr {
 
@@ -46,13 +54,33 @@ struct RepAcc {
     __device__ __forceinline__ uint64_t sa(uint64_t r) const { return (uint64_t)sa_[r]; }
 };
 
-// RepAcc behind a window of l and of level 1 in LDS: ranks [w0, w1) and their words (w0 a multiple of 64).  A search reads
-// the window first -- a scan step is then an LDS read, not a dependent global load -- and what lies outside it from memory.
+// a window of level 0 and of the level-1 entries above it: ranks [w0, w0 + len), w0 a multiple of 64, and vlen words
+struct RepWindow { uint64_t w0, len, vlen; };
+
+// len ranks from w0 on of an array of s (level 1 exists when s > 64)
+__device__ __forceinline__ RepWindow rep_window(uint64_t w0, uint64_t len, uint64_t s) { return RepWindow{w0, len, s > 64 ? (len + 63) / 64 : 0}; }
+
+// the window of tile t at step `it` (a multiple of `stage`): `stage` ranks, or what is left of the tile or of the array
+__device__ __forceinline__ RepWindow rep_tile_window(uint64_t t, uint32_t tile, uint32_t it, uint32_t stage, uint64_t s)
+{
+    const uint64_t w0 = t * tile + it, left = tile - it < stage ? tile - it : stage;
+    return rep_window(w0, w0 + left < s ? left : s - w0, s);
+}
+
+// RepAcc behind a window of l and of level 1 in LDS.  A search reads the window first -- a scan step is then an LDS read,
+// not a dependent global load -- and what lies outside it from memory.
 template <typename T, typename G = RepAcc<T>>         // (G: what lies behind the window; sufr_lz.inc stages its own arrays)
 struct RepStaged {
     G g;
-    const T *s_l, *s_l1;
+    T *s_l, *s_l1;
     uint64_t w0, len, v0, vlen;                         // the window of level 0 and of level 1: first index and entries
+    // fills the window, all 256 lanes of the workgroup; the caller's barriers stand before and after
+    __device__ __forceinline__ void stage(const RepWindow& win)
+    {
+        for (uint64_t i = threadIdx.x; i < win.len; i += 256) s_l[i] = (T)g.at(0, 0, win.w0 + i);
+        if (threadIdx.x < win.vlen) s_l1[threadIdx.x] = (T)g.at(1, 0, (win.w0 >> 6) + threadIdx.x);
+        w0 = win.w0; len = win.len; v0 = win.w0 >> 6; vlen = win.vlen;
+    }
     __device__ __forceinline__ uint64_t at(uint32_t level, uint64_t off, uint64_t i) const
     {
         // (the empty asm keeps the compiler from folding the LDS read and the global read into one flat load of a selected
@@ -154,102 +182,117 @@ __global__ __launch_bounds__(256) void k_rep_level(const T* __restrict__ in, uin
     }
 }
 
-struct RepFilter { uint32_t kind; uint64_t min_len, min_count, max_count; };
+// kind, min_len and the count filter of sufr_repeat.h; min_seqs / max_seqs: the filter of sufr_shared.h (0, 0 where no
+// sequences are counted)
+struct RepFilter { uint32_t kind; uint64_t min_len, min_count, max_count, min_seqs, max_seqs; };
+enum { REP_COUNT = 0, REP_WRITE = 1, REP_PROFILE = 2 };
 
-// WRITE false: t_cnt[t] = kept ranks of tile t, t_best[4 t ..] = {longest, its representative, its rank, largest count}.
-// WRITE true: t_cnt[t] is the tile's base; the records go to o_rank / o_count / o_len in rank order.
-template <typename T, bool WRITE>
-__global__ __launch_bounds__(256) void k_rep_find(RepAcc<T> gacc, const uint8_t* __restrict__ text, RepBits bits, RepFilter flt, uint32_t tile,
-                                                  uint64_t ntiles, uint64_t* __restrict__ t_cnt, uint64_t* __restrict__ t_best,
-                                                  uint64_t* __restrict__ o_rank, uint64_t* __restrict__ o_count, uint64_t* __restrict__ o_len)
+// a RepBest as NCOL words `stride` apart: len, rep, rank, cnt and, with 5 columns, seq
+template <int NCOL>
+__device__ __forceinline__ RepBest rep_best_get(const uint64_t* p, uint32_t stride = 1)
 {
+    return RepBest{p[0], p[stride], p[2 * stride], p[3 * stride], NCOL > 4 ? p[4 * stride] : 0};
+}
+template <int NCOL>
+__device__ __forceinline__ void rep_best_put(uint64_t* p, const RepBest& b, uint32_t stride = 1)
+{
+    p[0] = b.len; p[stride] = b.rep; p[2 * stride] = b.rank; p[3 * stride] = b.cnt;
+    if (NCOL > 4) p[4 * stride] = b.seq;
+}
+
+// The find pass of repeats (SEQS false: 4 columns; P, o_seqs, best and the seqs filter are not looked at) and of shared and
+// common (SEQS true: 5 columns; seqs from two reads of P, then its filter).
+// REP_COUNT: t_cnt[t] = kept ranks of tile t, t_best[NCOL t ..] = the tile's RepBest.  REP_WRITE: t_cnt[t] is the tile's
+// base; the records go to o_rank / o_count / o_len (/ o_seqs) in rank order.  REP_PROFILE (SEQS only): best[k - 1] = the
+// longest interval of exactly k sequences (nbest entries, zeroed before the launch) -- the entry is read first and the atomic
+// max issued only when v is larger: the value only grows, so a stale read costs at most an atomic that changes nothing.
+template <typename T, int MODE, bool SEQS>
+__global__ __launch_bounds__(256) void k_rep_find(RepAcc<T> gacc, const uint8_t* __restrict__ text, RepBits bits, const T* __restrict__ P,
+                                                  RepFilter flt, uint32_t tile, uint64_t ntiles, uint64_t* __restrict__ t_cnt,
+                                                  uint64_t* __restrict__ t_best, uint64_t* __restrict__ o_rank, uint64_t* __restrict__ o_count,
+                                                  uint64_t* __restrict__ o_len, uint64_t* __restrict__ o_seqs, uint64_t* __restrict__ best, uint64_t nbest)
+{
+    static_assert(MODE != REP_PROFILE || SEQS, "the profile is one of sequence counts");
+    constexpr int NCOL = SEQS ? 5 : 4;
     __shared__ uint32_t s_w[4];
-    __shared__ uint64_t s_b[4][4];
+    __shared__ uint64_t s_b[4][NCOL];
     __shared__ T s_l[REP_STAGE], s_l1[REP_STAGE / 64];
     RepStaged<T> acc{gacc, s_l, s_l1, 0, 0, 0, 0};
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint64_t s = gacc.s;
-    const bool has_l1 = s > 64;                          // (level 1 exists)
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        uint64_t running = WRITE ? t_cnt[t] : 0;
-        uint64_t b_len = 0, b_rep = 0, b_rank = 0, b_cnt = 0;
+        uint64_t running = MODE == REP_WRITE ? t_cnt[t] : 0;
+        RepBest b{0, 0, 0, 0, 0};
         for (uint32_t it = 0; it < tile; it += 256) {
             const uint64_t r = t * tile + it + threadIdx.x;
             if (r - threadIdx.x >= s) break;             // (uniform: past the end of the array)
-            if (it % REP_STAGE == 0) {                   // (uniform) the next window of the tile: REP_STAGE ranks, or what is left
-                const uint64_t w0 = t * tile + it, left = tile - it < REP_STAGE ? tile - it : REP_STAGE,
-                               len = w0 + left < s ? left : s - w0, vlen = has_l1 ? (len + 63) / 64 : 0;
+            if (it % REP_STAGE == 0) {                   // (uniform) the next window of the tile
                 __syncthreads();                         // (the lanes are done with the window before)
-                for (uint64_t i = threadIdx.x; i < len; i += 256) s_l[i] = (T)gacc.at(0, 0, w0 + i);
-                if (threadIdx.x < vlen) s_l1[threadIdx.x] = (T)gacc.at(1, 0, (w0 >> 6) + threadIdx.x);
-                acc.w0 = w0; acc.len = len; acc.v0 = w0 >> 6; acc.vlen = vlen;
+                acc.stage(rep_tile_window(t, tile, it, REP_STAGE, s));
                 __syncthreads();
             }
             bool keep = false;
-            uint64_t a = 0, z = 0, v = 0;
-            if (r >= 1 && r < s) {
-                v = acc.at(0, 0, r);
-                if (v >= flt.min_len) {
-                    a = rep_search_left(acc, s, r, v);
-                    if (a != REP_NONE && acc.at(0, 0, a) < v) {
-                        z = rep_search_right(acc, s, r, v);
-                        keep = rep_keep(acc, text, bits.dw, bits.dp, bits.sw, bits.sp, flt.kind, flt.min_count, flt.max_count, a, z, v);
-                    }
-                }
+            uint64_t a = 0, z = 0, v = 0, q = 0;
+            if (r >= 1 && r < s)
+                rep_interval(acc, s, r, flt.min_len, [&](uint64_t ia, uint64_t iz, uint64_t iv) {
+                    a = ia; z = iz; v = iv;
+                    keep = rep_keep(acc, text, bits.dw, bits.dp, bits.sw, bits.sp, flt.kind, flt.min_count, flt.max_count, a, z, v);
+                    if (SEQS && keep) { q = shr_seqs(P, a, z); keep = shr_keep(q, flt.min_seqs, flt.max_seqs); }
+                });
+            if (MODE == REP_PROFILE) {
+                if (keep && q - 1 < nbest && __hip_atomic_load(&best[q - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v)
+                    atomicMax((unsigned long long*)&best[q - 1], (unsigned long long)v);
+                continue;
             }
             uint32_t tot;
             const uint32_t at = rep_wg_exscan(keep ? 1u : 0u, s_w, tot);
             if (keep) {
-                if (WRITE) { const uint64_t o = running + at; o_rank[o] = a; o_count[o] = z - a; o_len[o] = v; }
-                else {
-                    if (v > b_len) { b_len = v; b_rep = r; b_rank = a; }      // (a lane's ranks ascend: ties keep the first)
-                    if (z - a > b_cnt) b_cnt = z - a;
-                }
+                if (MODE == REP_WRITE) {
+                    const uint64_t o = running + at;
+                    o_rank[o] = a; o_count[o] = z - a; o_len[o] = v;
+                    if (SEQS) o_seqs[o] = q;
+                } else b.take(v, r, a, z - a, q);
             }
             running += tot;
         }
-        if (!WRITE) {
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint64_t l2 = __shfl_down(b_len, o), r2 = __shfl_down(b_rep, o), a2 = __shfl_down(b_rank, o), c2 = __shfl_down(b_cnt, o);
-                if (rep_better(l2, r2, b_len, b_rep)) { b_len = l2; b_rep = r2; b_rank = a2; }
-                if (c2 > b_cnt) b_cnt = c2;
-            }
-            if (lane == 0) { s_b[w][0] = b_len; s_b[w][1] = b_rep; s_b[w][2] = b_rank; s_b[w][3] = b_cnt; }
+        if (MODE == REP_COUNT) {
+            for (int o = 32; o > 0; o >>= 1)
+                b.merge(RepBest{__shfl_down(b.len, o), __shfl_down(b.rep, o), __shfl_down(b.rank, o), __shfl_down(b.cnt, o),
+                                SEQS ? __shfl_down(b.seq, o) : 0});
+            if (lane == 0) rep_best_put<NCOL>(s_b[w], b);
             __syncthreads();
             if (threadIdx.x == 0) {
-                for (uint32_t k = 1; k < 4; k++) {
-                    if (rep_better(s_b[k][0], s_b[k][1], b_len, b_rep)) { b_len = s_b[k][0]; b_rep = s_b[k][1]; b_rank = s_b[k][2]; }
-                    if (s_b[k][3] > b_cnt) b_cnt = s_b[k][3];
-                }
+                for (uint32_t k = 1; k < 4; k++) b.merge(rep_best_get<NCOL>(s_b[k]));
                 t_cnt[t] = running;
-                t_best[4 * t] = b_len; t_best[4 * t + 1] = b_rep; t_best[4 * t + 2] = b_rank; t_best[4 * t + 3] = b_cnt;
+                rep_best_put<NCOL>(t_best + NCOL * t, b);
             }
             __syncthreads();                             // (s_b is reused by the next tile)
         }
     }
 }
 
-// stats = {records, longest, longest_rank, max_count}; *total: the sum of the tile counts
+// stats = {records, longest, longest_rank, max_count (, max_seqs)}; *total: the sum of the tile counts
+template <int NCOL>
 __global__ __launch_bounds__(1024) void k_rep_best(const uint64_t* __restrict__ t_best, uint64_t ntiles, const uint64_t* __restrict__ total,
                                                    uint64_t* __restrict__ stats)
 {
-    __shared__ uint64_t s_l[1024], s_r[1024], s_a[1024], s_c[1024];
+    __shared__ uint64_t s_v[NCOL * 1024];                // column c of lane i at s_v[c * 1024 + i]
     const uint32_t i = threadIdx.x;
-    uint64_t b_len = 0, b_rep = 0, b_rank = 0, b_cnt = 0;
-    for (uint64_t t = i; t < ntiles; t += 1024) {
-        if (rep_better(t_best[4 * t], t_best[4 * t + 1], b_len, b_rep)) { b_len = t_best[4 * t]; b_rep = t_best[4 * t + 1]; b_rank = t_best[4 * t + 2]; }
-        if (t_best[4 * t + 3] > b_cnt) b_cnt = t_best[4 * t + 3];
-    }
-    s_l[i] = b_len; s_r[i] = b_rep; s_a[i] = b_rank; s_c[i] = b_cnt;
+    RepBest b{0, 0, 0, 0, 0};
+    for (uint64_t t = i; t < ntiles; t += 1024) b.merge(rep_best_get<NCOL>(t_best + NCOL * t));
+    rep_best_put<NCOL>(s_v + i, b, 1024);
     __syncthreads();
     for (uint32_t o = 512; o > 0; o >>= 1) {
         if (i < o) {
-            if (rep_better(s_l[i + o], s_r[i + o], s_l[i], s_r[i])) { s_l[i] = s_l[i + o]; s_r[i] = s_r[i + o]; s_a[i] = s_a[i + o]; }
-            if (s_c[i + o] > s_c[i]) s_c[i] = s_c[i + o];
+            b.merge(rep_best_get<NCOL>(s_v + i + o, 1024));
+            rep_best_put<NCOL>(s_v + i, b, 1024);
         }
         __syncthreads();
     }
-    if (i == 0) { stats[0] = *total; stats[1] = s_l[0]; stats[2] = s_a[0]; stats[3] = s_c[0]; }
+    if (i == 0) {
+        stats[0] = *total; stats[1] = b.len; stats[2] = b.rank; stats[3] = b.cnt;
+        if (NCOL > 4) stats[4] = b.seq;
+    }
 }
 
 }  // namespace sufr
@@ -264,7 +307,7 @@ struct RepPrep {
     uint64_t ntiles, nwords, wgs;
     sufr::RepAcc<T> acc;
     sufr::RepBits bits;
-    uint64_t *t_cnt, *t_best, *d_stats;                  // ntiles + 1 kept counts (then bases), 4 candidates per tile, 4 stats
+    uint64_t *t_cnt, *t_best, *d_stats;                  // ntiles + 1 kept counts (then bases), 5 columns per tile, 5 stats
 };
 
 // the fold, the scans of the popcount totals and the coarser levels, enqueued on the context's stream
@@ -279,17 +322,18 @@ int repeats_prepare(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_l
     const bool clipped = q.num > 1;
     int rc;
     // rbits: the "differs" words, the "start" words and their prefixes; rsum: per tile the two popcount totals (each with
-    // its grand total behind it), the kept counts (and their total), the four candidates; then the four stats
-    if ((rc = pl.ensure(ctx->rbits, nwords * 32)) || (rc = pl.ensure(ctx->rsum, (ntiles * 7 + 3 + 4) * 8)) ||
+    // its grand total behind it), the kept counts (and their total), the five columns of a candidate (repeats uses four of
+    // them); then the five stats
+    if ((rc = pl.ensure(ctx->rbits, nwords * 32)) || (rc = pl.ensure(ctx->rsum, (ntiles * 8 + 3 + 5) * 8)) ||
         (rc = pl.ensure(ctx->rpyr, (sufr::rep_level_offset(s, levels + 1) + 1) * sizeof(T))) ||
         (clipped && (rc = pl.ensure(ctx->rell, s * sizeof(T))))) return rc;
     uint64_t* dw = (uint64_t*)ctx->rbits.p;
     uint64_t *sw = dw + nwords, *dp = sw + nwords, *sp = dp + nwords;
     uint64_t* t_d = (uint64_t*)ctx->rsum.p;
-    uint64_t *t_s = t_d + ntiles + 1, *t_cnt = t_s + ntiles + 1, *t_best = t_cnt + ntiles + 1, *d_stats = t_best + 4 * ntiles;
+    uint64_t *t_s = t_d + ntiles + 1, *t_cnt = t_s + ntiles + 1, *t_best = t_cnt + ntiles + 1, *d_stats = t_best + 5 * ntiles;
     T* up = (T*)ctx->rpyr.p;
     T* ell = clipped ? (T*)ctx->rell.p : nullptr;
-    const T* sa = (const T*)(ix->ix.sa64 ? (const void*)ix->ix.sa64 : (const void*)ix->ix.sa);
+    const T* sa = index_sa<T>(ix);
     const uint64_t wgs = batch_grid(pl);
     const uint32_t grid = (uint32_t)(ntiles < wgs ? ntiles : wgs);
     hipLaunchKernelGGL(sufr::k_rep_fold<T>, dim3(grid), dim3(256), 0, pl.stream, sa, (const T*)d_lcp, ix->ix.text, s, q, tile, ntiles, ell,
@@ -311,37 +355,38 @@ int repeats_prepare(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_l
     return 0;
 }
 
+// The counted find of repeats (SEQS false) and shared (SEQS true, P the prefix of sufr_shared.inc): the counting launch, the
+// tile counts to bases, the stats, the report (one synchronisation), the writing launch.  h: the NCOL stats as read, zeros
+// when they were not.
+template <typename T, bool SEQS>
+int repeats_find(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const RepPrep<T>& R, const T* P, const sufr::RepFilter& flt, const char* tag,
+                 uint64_t cap, void* d_rank, void* d_count, void* d_length, void* d_seqs, uint64_t* total_out, unsigned long long* h)
+{
+    constexpr int NCOL = SEQS ? 5 : 4;
+    sufr::Pipeline& pl = ctx->pl;
+    uint64_t* const none = nullptr;
+    hipLaunchKernelGGL((sufr::k_rep_find<T, sufr::REP_COUNT, SEQS>), dim3(R.grid), dim3(256), 0, pl.stream, R.acc, ix->ix.text, R.bits, P, flt, R.tile,
+                       R.ntiles, R.t_cnt, R.t_best, none, none, none, none, none, (uint64_t)0);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, R.t_cnt, R.ntiles, R.t_cnt + R.ntiles);
+    hipLaunchKernelGGL(sufr::k_rep_best<NCOL>, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)R.t_best, R.ntiles,
+                       (const uint64_t*)(R.t_cnt + R.ntiles), R.d_stats);
+    const int rc = report_total(pl, tag, "records", R.d_stats, NCOL, h, cap, total_out, d_rank && d_count && d_length && (!SEQS || d_seqs));
+    if (rc || !h[0]) return rc;
+    hipLaunchKernelGGL((sufr::k_rep_find<T, sufr::REP_WRITE, SEQS>), dim3(R.grid), dim3(256), 0, pl.stream, R.acc, ix->ix.text, R.bits, P, flt, R.tile,
+                       R.ntiles, R.t_cnt, R.t_best, (uint64_t*)d_rank, (uint64_t*)d_count, (uint64_t*)d_length, (uint64_t*)d_seqs, none, (uint64_t)0);
+    return launch_status(pl, tag);
+}
+
 template <typename T>
 int repeats_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const sufr::KmerSeqs& q, const sufr::RepFilter& flt,
                 uint64_t cap, void* d_rank, void* d_count, void* d_length, uint64_t* total_out, sufr_repeat_stats* stats_out)
 {
-    sufr::Pipeline& pl = ctx->pl;
-    RepPrep<T> P;
-    int rc;
-    if ((rc = repeats_prepare<T>(ctx, ix, d_lcp, q, P))) return rc;
-    const uint32_t tile = P.tile, grid = P.grid;
-    const uint64_t ntiles = P.ntiles;
-    const sufr::RepAcc<T> acc = P.acc;
-    const sufr::RepBits bits = P.bits;
-    uint64_t *t_cnt = P.t_cnt, *t_best = P.t_best, *d_stats = P.d_stats;
-    hipLaunchKernelGGL((sufr::k_rep_find<T, false>), dim3(grid), dim3(256), 0, pl.stream, acc, ix->ix.text, bits, flt, tile, ntiles, t_cnt, t_best,
-                       (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, t_cnt, ntiles, t_cnt + ntiles);
-    hipLaunchKernelGGL(sufr::k_rep_best, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)t_best, ntiles, (const uint64_t*)(t_cnt + ntiles), d_stats);
-    if ((rc = launch_status(pl, "repeats"))) return rc;
+    RepPrep<T> R;
+    if (const int rc = repeats_prepare<T>(ctx, ix, d_lcp, q, R)) return rc;
     unsigned long long h[4];
-    if ((rc = read_totals(pl, d_stats, 4, h, "repeats", "reading the total failed"))) return rc;
-    if (total_out) *total_out = h[0];
+    const int rc = repeats_find<T, false>(ctx, ix, R, (const T*)nullptr, flt, "repeats", cap, d_rank, d_count, d_length, nullptr, total_out, h);
     if (stats_out) *stats_out = sufr_repeat_stats{h[0], h[1], h[2], h[3]};
-    if (h[0] > cap) {
-        pl.set_error("repeats: " + std::to_string(h[0]) + " records, room for " + std::to_string(cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    if (!h[0]) return 0;
-    if (!d_rank || !d_count || !d_length) { pl.set_error("repeats: no output arrays"); return SUFR_HIP_E_INVALID; }
-    hipLaunchKernelGGL((sufr::k_rep_find<T, true>), dim3(grid), dim3(256), 0, pl.stream, acc, ix->ix.text, bits, flt, tile, ntiles, t_cnt, t_best,
-                       (uint64_t*)d_rank, (uint64_t*)d_count, (uint64_t*)d_length);
-    return launch_status(pl, "repeats");
+    return rc;
 }
 
 }  // namespace
@@ -364,21 +409,15 @@ int sufr_hip_repeats_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const v
     if (total_out) *total_out = 0;
     if (!ctx || !ix) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
-    pl.err.clear();
     int rc;
-    if ((rc = query_check(ctx, ix, "repeats"))) return rc;
-    if (ix->built_mql > 0) {
-        pl.set_error("repeats: the index was built with max_query_len " + std::to_string(ix->built_mql) + ", its LCP is capped");
-        return SUFR_HIP_E_UNSUPPORTED;
-    }
+    if ((rc = lcp_refusals(ctx, ix, "repeats", "repeats"))) return rc;
     if (min_len == 0) { pl.set_error("repeats: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
     if (kind > SUFR_REPEAT_SUPERMAXIMAL) { pl.set_error("repeats: unknown kind " + std::to_string(kind)); return SUFR_HIP_E_INVALID; }
     if (!ix->ix.s) return 0;
     sufr::KmerSeqs q;
     if ((rc = kmer_prepare(ctx, ix, d_lcp, seq_starts, num_sequences, "repeats", q))) return rc;
-    const sufr::RepFilter flt{kind, min_len, min_count < 2 ? 2 : min_count, max_count};
-    return ix->sa_width == 8 ? repeats_run<uint64_t>(ctx, ix, d_lcp, q, flt, cap, d_rank, d_count, d_length, total_out, stats_out)
-                             : repeats_run<uint32_t>(ctx, ix, d_lcp, q, flt, cap, d_rank, d_count, d_length, total_out, stats_out);
+    const sufr::RepFilter flt{kind, min_len, min_count < 2 ? 2 : min_count, max_count, 0, 0};
+    return by_width(ix, [&](auto w) { return repeats_run<decltype(w)>(ctx, ix, d_lcp, q, flt, cap, d_rank, d_count, d_length, total_out, stats_out); });
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // sufr_repeat_scan.h -- the arithmetic behind the repeats of the indexed text (include/sufr_repeat.h):
 // the clipped LCP, the index arithmetic of a min pyramid over it, the two nearest-smaller-value searches that walk the
-// pyramid, the popcount-prefix count of flagged ranks and the supermaximal walk.  Plain integer code that the kernels of
-// sufr_repeat.inc, the host path of sufr_query.cpp and tests/repeat_shim.cpp all compile (SUFR_HD, the way of
-// sufr_kmer_scan.h); there is no second copy of it.
+// pyramid, the decision "is this rank the representative of an interval, and of which" (rep_interval), the popcount-prefix
+// count of flagged ranks, the supermaximal walk and the reduction of a find pass's candidates (RepBest).  Plain integer
+// code that the kernels of sufr_repeat.inc, the host path of sufr_query.cpp and tests/repeat_shim.cpp all compile (SUFR_HD,
+// the way of sufr_kmer_scan.h); there is no second copy of it.
 //
 // The pyramid.  Level 0 is l[0..s), the clipped LCP.  Entry i of level k >= 1 is the minimum of entries [64 i, 64 i + 64) of
 // level k - 1, so level k has ceil(s / 64^k) entries; levels are kept while the one below has more than 64 entries, and the
@@ -181,10 +182,51 @@ SUFR_HD bool rep_keep(const A& acc, const uint8_t* text, const uint64_t* dw, con
     return rep_supermaximal(acc, text, dw, dp, sw, sp, a, b, v);
 }
 
+// If rank r, 1 <= r < s, is the representative of an interval of value v = l[r] >= min_len -- the nearest l <= v on its left
+// is smaller (an equal one is an earlier rank of the same interval, and the representative) -- then fn(a, z, v) with that
+// interval [a, z).  What is done with an interval is a callable and not code behind a returned flag so that in a kernel it
+// stays inside the branch that found the interval: behind a flag the lanes of a wave meet again first, and the writing
+// form of k_rep_find was 4 % slower for it.
+template <typename A, typename F>
+SUFR_HD void rep_interval(const A& acc, uint64_t s, uint64_t r, uint64_t min_len, F fn)
+{
+    const uint64_t v = acc.at(0, 0, r);
+    if (v >= min_len) {
+        const uint64_t a = rep_search_left(acc, s, r, v);
+        if (a != REP_NONE && acc.at(0, 0, a) < v) fn(a, rep_search_right(acc, s, r, v), v);
+    }
+}
+
+// out[i] = min of in[64 i .. 64 i + 64): one coarser level of a pyramid, serially (the device has k_rep_level)
+SUFR_HD void rep_level_up(const uint64_t* in, uint64_t n_in, uint64_t* out, uint64_t n_out)
+{
+    for (uint64_t i = 0; i < n_out; i++) {
+        uint64_t low = ~(uint64_t)0;
+        for (uint64_t j = i * 64; j < n_in && j < i * 64 + 64; j++) if (in[j] < low) low = in[j];
+        out[i] = low;
+    }
+}
+
 // the better of two "longest" candidates (len, rep): longer wins, ties go to the smaller representative; len 0: none
 SUFR_HD bool rep_better(uint64_t len, uint64_t rep, uint64_t than_len, uint64_t than_rep)
 {
     return len > than_len || (len == than_len && len && rep < than_rep);
 }
+
+// what a find pass keeps of the intervals it met: the longest (len, its representative, its first rank), the largest count
+// and the largest number of sequences (0 where the call has no such column).  All zero: nothing met.  merge is commutative
+// and associative -- rep_better is a strict order on (len, rep) and the other two are maxima -- so lanes, waves, tiles and
+// chunks may be combined in any order.
+struct RepBest {
+    uint64_t len, rep, rank, cnt, seq;
+    SUFR_HD_MEMBER void merge(const RepBest& o)
+    {
+        if (rep_better(o.len, o.rep, len, rep)) { len = o.len; rep = o.rep; rank = o.rank; }
+        if (o.cnt > cnt) cnt = o.cnt;
+        if (o.seq > seq) seq = o.seq;
+    }
+    // the interval [a, a + count) of value v with representative r, seen in `seqs` sequences
+    SUFR_HD_MEMBER void take(uint64_t v, uint64_t r, uint64_t a, uint64_t count, uint64_t seqs) { merge(RepBest{v, r, a, count, seqs}); }
+};
 
 }  // namespace sufr

@@ -18,9 +18,9 @@
 // sufr_trace.inc, included after it, add only their own rules (DESIGN.md section 10, "The shared front end").
 // Device: search_compare / common_prefix, the range search (search_seed, search_lower, search_range), last_le, wg_scan,
 // scan_chunk, the locate scan (k_locate_counts / k_locate_scan / k_locate_apply), k_mem_bitmap and k_mem_revcomp.
-// Host: query_check, read_totals, scan_total; the batch of a call (take_batch = batch_extent + double_batch, mem_bitmap);
-// candidate_starts; the record epilogue (records_fit, any_null, launch_status); the staging of the host-pointer entry
-// points (stage_batch / unstage_batch, staged_records).
+// Host: query_check, lcp_refusals, index_sa, by_width, read_totals, scan_total; the batch of a call (take_batch =
+// batch_extent + double_batch, mem_bitmap); candidate_starts; the record epilogue (records_fit, any_null, launch_status,
+// report_total); the staging of the host-pointer entry points (stage_batch / unstage_batch, staged_records).
 
 namespace sufr {
 
@@ -459,6 +459,27 @@ int query_check(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const char* masked 
     return 0;
 }
 
+// the preamble of the calls that read the whole LCP (repeats, shared and common, lpf and lz, unique lengths): query_check,
+// then the refusal of an index whose LCP was capped by max_query_len; `what` names the call in that text
+int lcp_refusals(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const char* masked_name, const char* what)
+{
+    ctx->pl.err.clear();
+    if (const int rc = query_check(ctx, ix, masked_name)) return rc;
+    if (ix->built_mql > 0) {
+        ctx->pl.set_error(std::string(what) + ": the index was built with max_query_len " + std::to_string(ix->built_mql) + ", its LCP is capped");
+        return SUFR_HIP_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// the suffix array in the width the index has
+template <typename T>
+const T* index_sa(const sufr_hip_index* ix) { return (const T*)(ix->ix.sa64 ? (const void*)ix->ix.sa64 : (const void*)ix->ix.sa); }
+
+// fn(uint32_t()) or fn(uint64_t()), by the width of the index: fn is a generic lambda that takes its T from the argument
+template <typename F>
+int by_width(const sufr_hip_index* ix, F fn) { return ix->sa_width == 8 ? fn(uint64_t()) : fn(uint32_t()); }
+
 // the workgroups of the kernels that loop over a batch (latency-bound lanes: 8 workgroups of 4 waves per CU)
 uint32_t batch_grid(const sufr::Pipeline& pl) { return (pl.num_cus ? pl.num_cus : 256u) * 8u; }
 
@@ -592,6 +613,20 @@ int launch_status(sufr::Pipeline& pl, const char* tag)
     if (e == hipSuccess) return 0;
     pl.set_error(std::string(tag) + ": " + hipGetErrorString(e));
     return SUFR_HIP_E_HIP;
+}
+
+// The report of a counted call between its counting and its writing launches: what the launches left behind, the ncols
+// stats of the device into h (h[0] the total; one synchronisation; zeros when it fails), the total against the caller's room
+// and, when there is something to write, the caller's arrays.  0: h[0] records are to be written (none: nothing is left to do).
+int report_total(sufr::Pipeline& pl, const char* tag, const char* noun, const void* d_stats, int ncols, unsigned long long* h, uint64_t cap,
+                 uint64_t* total_out, bool have_outputs)
+{
+    for (int k = 0; k < ncols; k++) h[k] = 0;
+    int rc;
+    if ((rc = launch_status(pl, tag)) || (rc = read_totals(pl, d_stats, ncols, h, tag, "reading the total failed")) ||
+        (rc = records_fit(pl, tag, noun, h[0], cap, total_out))) return rc;
+    if (h[0] && !have_outputs) { pl.set_error(std::string(tag) + ": no output arrays"); return SUFR_HIP_E_INVALID; }
+    return 0;
 }
 
 // The host-pointer entry points stage their batch in one allocation, queries | offsets (at o_at) | what the caller lays

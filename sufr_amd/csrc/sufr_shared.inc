@@ -14,21 +14,18 @@
 // k_shr_pairs    a lane per sorted key j: if key j - 1 has the same sequence the pair is (prev, r); q = shr_pair (one range
 //                minimum, one search, each bounded by 2 x 64 x levels reads) and H[q] += 1 by a global atomic add -- integer
 //                adds commute, the result depends on no order; the one atomic add of this file.  Per 256 keys the l of up to
-//                REP_STAGE ranks from the first pair's prev on is staged in LDS behind RepStaged when the keys of the step are
-//                near enough for that to serve them (one sequence: always; many sequences: the ranks of one sequence lie far
-//                apart and nothing is staged); a pair whose range leaves the window reads the pyramid in memory.  The window
-//                is a copy: it changes no result.
+//                REP_STAGE ranks from the first pair's prev on is staged in LDS (RepStaged::stage) when the keys of the step
+//                are near enough for that to serve them (one sequence: always; many sequences: the ranks of one sequence lie
+//                far apart and nothing is staged); a pair whose range leaves the window reads the pyramid in memory.  The
+//                window is a copy: it changes no result.
 // k_shr_scan     the exclusive prefix of H inside every tile, in place, and the tile totals; k_locate_scan (sufr_search.inc)
 //                turns the totals into bases; k_shr_addbase adds them: P, s + 1 entries of the index width.
-// k_shr_find     the decisions of k_rep_find (rep_keep for the kind), then seqs from two reads of P and its filter.  MODE 0
-//                counts: kept ranks per tile, the tile's longest / largest count / largest seqs.  MODE 1 writes, compacted in
-//                rank order behind the tile's base.  MODE 2 is the profile: every representative raises best[seqs - 1] to v --
-//                the entry is read first and the atomic max issued only when v is larger: the value only grows, so a stale
-//                read costs at most an atomic that changes nothing.
-// k_shr_best     one workgroup: the stats from the tiles' candidates by comparisons, no atomics.
+// k_rep_find     (sufr_repeat.inc) with SEQS set: the find pass of repeats with seqs from two reads of P, its filter and its
+//                column; counting, writing, or the profile (every representative raises best[seqs - 1] to v).  The counted
+//                find is repeats_find<T, true>; k_rep_best<5> gives its stats.
 // k_shr_suffix   one workgroup: the suffix maximum of best into d_common.
-// A workgroup takes tiles t = blockIdx.x, blockIdx.x + gridDim.x, ...; no scratch, no MFMA.  LDS: k_shr_pairs and k_shr_find
-// 16.6 KB (32-bit arrays) or 33.2 KB (64-bit), k_shr_best 40 KB, k_shr_suffix 8 KB, k_shr_scan 32 bytes.
+// A workgroup takes tiles t = blockIdx.x, blockIdx.x + gridDim.x, ...; no scratch, no MFMA.  LDS: k_shr_pairs 16.6 KB (32-bit
+// arrays) or 33.2 KB (64-bit), k_shr_suffix 8 KB, k_shr_scan 32 bytes.
 
 #include "sufr_shared_scan.h"
 
@@ -51,7 +48,6 @@ __global__ __launch_bounds__(256) void k_shr_pairs(RepAcc<T> gacc, const uint64_
     __shared__ T s_l[REP_STAGE], s_l1[REP_STAGE / 64];
     RepStaged<T> acc{gacc, s_l, s_l1, 0, 0, 0, 0};
     const uint64_t s = gacc.s;
-    const bool has_l1 = s > 64;                          // (level 1 exists)
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         for (uint32_t it = 0; it < tile; it += 256) {
             const uint64_t j0 = t * tile + it, j = j0 + threadIdx.x;
@@ -66,11 +62,8 @@ __global__ __launch_bounds__(256) void k_shr_pairs(RepAcc<T> gacc, const uint64_
                 const uint64_t span = shr_key_doc(kl) == shr_key_doc(k0) ? shr_key_rank(kl) + 1 - w0 : REP_STAGE;
                 uint64_t len = span > 4 * (uint64_t)REP_STAGE ? 0 : span < REP_STAGE ? span : REP_STAGE;
                 if (len > s - w0) len = s - w0;
-                const uint64_t vlen = has_l1 ? (len + 63) / 64 : 0;
                 __syncthreads();                         // (the lanes are done with the window before)
-                for (uint64_t i = threadIdx.x; i < len; i += 256) s_l[i] = (T)gacc.at(0, 0, w0 + i);
-                if (threadIdx.x < vlen) s_l1[threadIdx.x] = (T)gacc.at(1, 0, (w0 >> 6) + threadIdx.x);
-                acc.w0 = w0; acc.len = len; acc.v0 = w0 >> 6; acc.vlen = vlen;
+                acc.stage(rep_window(w0, len, s));
                 __syncthreads();
             }
             if (j >= 1 && j < s) {
@@ -107,119 +100,6 @@ __global__ __launch_bounds__(256) void k_shr_addbase(T* __restrict__ x, uint64_t
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) x[i] = (T)((uint64_t)x[i] + t_base[i / tile]);
 }
 
-struct ShrFilter { RepFilter rep; uint64_t min_seqs, max_seqs; };
-enum { SHR_COUNT = 0, SHR_WRITE = 1, SHR_PROFILE = 2 };
-
-// SHR_COUNT: t_cnt[t] = kept ranks of tile t, t_best[5 t ..] = {longest, its representative, its rank, largest count, largest
-// seqs}.  SHR_WRITE: t_cnt[t] is the tile's base; the records go to o_rank / o_count / o_len / o_seqs in rank order.
-// SHR_PROFILE: best[k - 1] = the longest interval of exactly k sequences (nbest entries, zeroed before the launch).
-template <typename T, int MODE>
-__global__ __launch_bounds__(256) void k_shr_find(RepAcc<T> gacc, const uint8_t* __restrict__ text, RepBits bits, const T* __restrict__ P,
-                                                  ShrFilter flt, uint32_t tile, uint64_t ntiles, uint64_t* __restrict__ t_cnt,
-                                                  uint64_t* __restrict__ t_best, uint64_t* __restrict__ o_rank, uint64_t* __restrict__ o_count,
-                                                  uint64_t* __restrict__ o_len, uint64_t* __restrict__ o_seqs, uint64_t* __restrict__ best, uint64_t nbest)
-{
-    __shared__ uint32_t s_w[4];
-    __shared__ uint64_t s_b[4][5];
-    __shared__ T s_l[REP_STAGE], s_l1[REP_STAGE / 64];
-    RepStaged<T> acc{gacc, s_l, s_l1, 0, 0, 0, 0};
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint64_t s = gacc.s;
-    const bool has_l1 = s > 64;                          // (level 1 exists)
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        uint64_t running = MODE == SHR_WRITE ? t_cnt[t] : 0;
-        uint64_t b_len = 0, b_rep = 0, b_rank = 0, b_cnt = 0, b_seq = 0;
-        for (uint32_t it = 0; it < tile; it += 256) {
-            const uint64_t r = t * tile + it + threadIdx.x;
-            if (r - threadIdx.x >= s) break;             // (uniform: past the end of the array)
-            if (it % REP_STAGE == 0) {                   // (uniform) the next window of the tile: REP_STAGE ranks, or what is left
-                const uint64_t w0 = t * tile + it, left = tile - it < REP_STAGE ? tile - it : REP_STAGE,
-                               len = w0 + left < s ? left : s - w0, vlen = has_l1 ? (len + 63) / 64 : 0;
-                __syncthreads();                         // (the lanes are done with the window before)
-                for (uint64_t i = threadIdx.x; i < len; i += 256) s_l[i] = (T)gacc.at(0, 0, w0 + i);
-                if (threadIdx.x < vlen) s_l1[threadIdx.x] = (T)gacc.at(1, 0, (w0 >> 6) + threadIdx.x);
-                acc.w0 = w0; acc.len = len; acc.v0 = w0 >> 6; acc.vlen = vlen;
-                __syncthreads();
-            }
-            bool keep = false;
-            uint64_t a = 0, z = 0, v = 0, q = 0;
-            if (r >= 1 && r < s) {
-                v = acc.at(0, 0, r);
-                if (v >= flt.rep.min_len) {
-                    a = rep_search_left(acc, s, r, v);
-                    if (a != REP_NONE && acc.at(0, 0, a) < v) {
-                        z = rep_search_right(acc, s, r, v);
-                        keep = rep_keep(acc, text, bits.dw, bits.dp, bits.sw, bits.sp, flt.rep.kind, flt.rep.min_count, flt.rep.max_count, a, z, v);
-                        if (keep) { q = shr_seqs(P, a, z); keep = shr_keep(q, flt.min_seqs, flt.max_seqs); }
-                    }
-                }
-            }
-            if (MODE == SHR_PROFILE) {
-                if (keep && q - 1 < nbest && __hip_atomic_load(&best[q - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v)
-                    atomicMax((unsigned long long*)&best[q - 1], (unsigned long long)v);
-                continue;
-            }
-            uint32_t tot;
-            const uint32_t at = rep_wg_exscan(keep ? 1u : 0u, s_w, tot);
-            if (keep) {
-                if (MODE == SHR_WRITE) { const uint64_t o = running + at; o_rank[o] = a; o_count[o] = z - a; o_len[o] = v; o_seqs[o] = q; }
-                else {
-                    if (v > b_len) { b_len = v; b_rep = r; b_rank = a; }      // (a lane's ranks ascend: ties keep the first)
-                    if (z - a > b_cnt) b_cnt = z - a;
-                    if (q > b_seq) b_seq = q;
-                }
-            }
-            running += tot;
-        }
-        if (MODE == SHR_COUNT) {
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint64_t l2 = __shfl_down(b_len, o), r2 = __shfl_down(b_rep, o), a2 = __shfl_down(b_rank, o), c2 = __shfl_down(b_cnt, o),
-                               q2 = __shfl_down(b_seq, o);
-                if (rep_better(l2, r2, b_len, b_rep)) { b_len = l2; b_rep = r2; b_rank = a2; }
-                if (c2 > b_cnt) b_cnt = c2;
-                if (q2 > b_seq) b_seq = q2;
-            }
-            if (lane == 0) { s_b[w][0] = b_len; s_b[w][1] = b_rep; s_b[w][2] = b_rank; s_b[w][3] = b_cnt; s_b[w][4] = b_seq; }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                for (uint32_t k = 1; k < 4; k++) {
-                    if (rep_better(s_b[k][0], s_b[k][1], b_len, b_rep)) { b_len = s_b[k][0]; b_rep = s_b[k][1]; b_rank = s_b[k][2]; }
-                    if (s_b[k][3] > b_cnt) b_cnt = s_b[k][3];
-                    if (s_b[k][4] > b_seq) b_seq = s_b[k][4];
-                }
-                t_cnt[t] = running;
-                t_best[5 * t] = b_len; t_best[5 * t + 1] = b_rep; t_best[5 * t + 2] = b_rank; t_best[5 * t + 3] = b_cnt; t_best[5 * t + 4] = b_seq;
-            }
-            __syncthreads();                             // (s_b is reused by the next tile)
-        }
-    }
-}
-
-// stats = {records, longest, longest_rank, max_count, max_seqs}; *total: the sum of the tile counts
-__global__ __launch_bounds__(1024) void k_shr_best(const uint64_t* __restrict__ t_best, uint64_t ntiles, const uint64_t* __restrict__ total,
-                                                   uint64_t* __restrict__ stats)
-{
-    __shared__ uint64_t s_l[1024], s_r[1024], s_a[1024], s_c[1024], s_q[1024];
-    const uint32_t i = threadIdx.x;
-    uint64_t b_len = 0, b_rep = 0, b_rank = 0, b_cnt = 0, b_seq = 0;
-    for (uint64_t t = i; t < ntiles; t += 1024) {
-        if (rep_better(t_best[5 * t], t_best[5 * t + 1], b_len, b_rep)) { b_len = t_best[5 * t]; b_rep = t_best[5 * t + 1]; b_rank = t_best[5 * t + 2]; }
-        if (t_best[5 * t + 3] > b_cnt) b_cnt = t_best[5 * t + 3];
-        if (t_best[5 * t + 4] > b_seq) b_seq = t_best[5 * t + 4];
-    }
-    s_l[i] = b_len; s_r[i] = b_rep; s_a[i] = b_rank; s_c[i] = b_cnt; s_q[i] = b_seq;
-    __syncthreads();
-    for (uint32_t o = 512; o > 0; o >>= 1) {
-        if (i < o) {
-            if (rep_better(s_l[i + o], s_r[i + o], s_l[i], s_r[i])) { s_l[i] = s_l[i + o]; s_r[i] = s_r[i + o]; s_a[i] = s_a[i + o]; }
-            if (s_c[i + o] > s_c[i]) s_c[i] = s_c[i + o];
-            if (s_q[i + o] > s_q[i]) s_q[i] = s_q[i + o];
-        }
-        __syncthreads();
-    }
-    if (i == 0) { stats[0] = *total; stats[1] = s_l[0]; stats[2] = s_a[0]; stats[3] = s_c[0]; stats[4] = s_q[0]; }
-}
-
 // common[k] = max best[k ..): lane i takes entries [i per, i per + per)
 __global__ __launch_bounds__(1024) void k_shr_suffix(const uint64_t* __restrict__ best, uint64_t num, uint64_t* __restrict__ common)
 {
@@ -247,7 +127,7 @@ namespace {
 template <typename T>
 struct ShrPrep {
     const T* P;                                          // the exclusive prefix of H, s + 1 entries
-    uint64_t *t_cnt, *t_best, *d_stats, *best;           // ntiles + 1 kept counts (then bases), 5 candidates per tile, 5 stats, num entries
+    uint64_t* best;                                      // the profile's maxima, num entries
 #ifdef SUFR_HIP_PROBES
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // (probes build: before the sort, between the sort and the pairs, after the pairs)
     bool stamp = false;
@@ -256,7 +136,7 @@ struct ShrPrep {
 
 // Scratch of the context, grown on demand and freed with it: shkeys, the two key buffers (16 s bytes); shhist, the digit
 // counts of a radix pass (256 * SCAN_WGS + 1 words); shpre, H and then P ((s + 1) entries of the index width); shsum, the
-// tile sums of the prefix, the kept counts, the candidates, the stats and the profile's maxima.
+// tile sums of the prefix and the profile's maxima (the find pass has its sums in RepPrep).
 // Enqueues the passes of repeats_prepare, the keys, the sort, the pairs and the prefix.
 template <typename T>
 int shared_prepare(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const sufr::KmerSeqs& q, uint64_t num, RepPrep<T>& R, ShrPrep<T>& S)
@@ -267,18 +147,17 @@ int shared_prepare(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lc
     if ((rc = repeats_prepare<T>(ctx, ix, d_lcp, q, R))) return rc;
     const uint64_t ntiles = R.ntiles, np = s + 1, nptiles = (np + R.tile - 1) / R.tile;
     if ((rc = pl.ensure(ctx->shkeys, s * 16)) || (rc = pl.ensure(ctx->shhist, ((uint64_t)256 * sufr::SCAN_WGS + 1) * 8)) ||
-        (rc = pl.ensure(ctx->shpre, np * sizeof(T))) || (rc = pl.ensure(ctx->shsum, (nptiles + 1 + ntiles + 1 + 5 * ntiles + 5 + num) * 8))) return rc;
+        (rc = pl.ensure(ctx->shpre, np * sizeof(T))) || (rc = pl.ensure(ctx->shsum, (nptiles + 1 + num) * 8))) return rc;
     uint64_t* ka = (uint64_t*)ctx->shkeys.p;
     uint64_t* kb = ka + s;
     T* H = (T*)ctx->shpre.p;
     uint64_t* t_h = (uint64_t*)ctx->shsum.p;
     S.P = H;
-    S.t_cnt = t_h + nptiles + 1; S.t_best = S.t_cnt + ntiles + 1; S.d_stats = S.t_best + 5 * ntiles; S.best = S.d_stats + 5;
-    const T* sa = (const T*)(ix->ix.sa64 ? (const void*)ix->ix.sa64 : (const void*)ix->ix.sa);
+    S.best = t_h + nptiles + 1;
     if (hipMemsetAsync(H, 0, np * sizeof(T), pl.stream) != hipSuccess) { pl.set_error("shared: memset failed"); return SUFR_HIP_E_HIP; }
     {
         const uint64_t need = (s + 255) / 256;
-        hipLaunchKernelGGL(sufr::k_shr_keys<T>, dim3((uint32_t)(need < R.wgs ? need : R.wgs)), dim3(256), 0, pl.stream, sa, s, q, ka);
+        hipLaunchKernelGGL(sufr::k_shr_keys<T>, dim3((uint32_t)(need < R.wgs ? need : R.wgs)), dim3(256), 0, pl.stream, index_sa<T>(ix), s, q, ka);
     }
 #ifdef SUFR_HIP_PROBES
     S.stamp = hipEventCreate(&S.ev[0]) == hipSuccess && hipEventCreate(&S.ev[1]) == hipSuccess && hipEventCreate(&S.ev[2]) == hipSuccess &&
@@ -304,38 +183,22 @@ int shared_prepare(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lc
 }
 
 template <typename T>
-int shared_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const sufr::KmerSeqs& q, const sufr::ShrFilter& flt, uint64_t cap,
+int shared_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const sufr::KmerSeqs& q, const sufr::RepFilter& flt, uint64_t cap,
                void* d_rank, void* d_count, void* d_length, void* d_seqs, uint64_t* total_out, sufr_shared_stats* stats_out)
 {
-    sufr::Pipeline& pl = ctx->pl;
     RepPrep<T> R;
     ShrPrep<T> S;
-    int rc;
-    if ((rc = shared_prepare<T>(ctx, ix, d_lcp, q, 0, R, S))) return rc;
-    hipLaunchKernelGGL((sufr::k_shr_find<T, sufr::SHR_COUNT>), dim3(R.grid), dim3(256), 0, pl.stream, R.acc, ix->ix.text, R.bits, S.P, flt, R.tile,
-                       R.ntiles, S.t_cnt, S.t_best, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, S.t_cnt, R.ntiles, S.t_cnt + R.ntiles);
-    hipLaunchKernelGGL(sufr::k_shr_best, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)S.t_best, R.ntiles, (const uint64_t*)(S.t_cnt + R.ntiles), S.d_stats);
-    if ((rc = launch_status(pl, "shared"))) return rc;
+    if (const int rc = shared_prepare<T>(ctx, ix, d_lcp, q, 0, R, S)) return rc;
     unsigned long long h[5];
-    if ((rc = read_totals(pl, S.d_stats, 5, h, "shared", "reading the total failed"))) return rc;
+    const int rc = repeats_find<T, true>(ctx, ix, R, S.P, flt, "shared", cap, d_rank, d_count, d_length, d_seqs, total_out, h);
 #ifdef SUFR_HIP_PROBES
     float ms_sort = 0, ms_pairs = 0;                      // (probes build: the sort's and the pair pass's own times, to standard error)
     if (S.stamp && hipEventElapsedTime(&ms_sort, S.ev[0], S.ev[1]) == hipSuccess && hipEventElapsedTime(&ms_pairs, S.ev[1], S.ev[2]) == hipSuccess)
         fprintf(stderr, "shared: sort %.3f ms, pairs %.3f ms (%llu ranks)\n", ms_sort, ms_pairs, (unsigned long long)ix->ix.s);
     for (hipEvent_t e : S.ev) if (e) (void)hipEventDestroy(e);
 #endif
-    if (total_out) *total_out = h[0];
     if (stats_out) *stats_out = sufr_shared_stats{h[0], h[1], h[2], h[3], h[4]};
-    if (h[0] > cap) {
-        pl.set_error("shared: " + std::to_string(h[0]) + " records, room for " + std::to_string(cap));
-        return SUFR_HIP_E_CAPACITY;
-    }
-    if (!h[0]) return 0;
-    if (!d_rank || !d_count || !d_length || !d_seqs) { pl.set_error("shared: no output arrays"); return SUFR_HIP_E_INVALID; }
-    hipLaunchKernelGGL((sufr::k_shr_find<T, sufr::SHR_WRITE>), dim3(R.grid), dim3(256), 0, pl.stream, R.acc, ix->ix.text, R.bits, S.P, flt, R.tile,
-                       R.ntiles, S.t_cnt, S.t_best, (uint64_t*)d_rank, (uint64_t*)d_count, (uint64_t*)d_length, (uint64_t*)d_seqs, (uint64_t*)nullptr, (uint64_t)0);
-    return launch_status(pl, "shared");
+    return rc;
 }
 
 template <typename T>
@@ -347,9 +210,10 @@ int common_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, c
     int rc;
     if ((rc = shared_prepare<T>(ctx, ix, d_lcp, q, num, R, S))) return rc;
     if (hipMemsetAsync(S.best, 0, num * 8, pl.stream) != hipSuccess) { pl.set_error("common: memset failed"); return SUFR_HIP_E_HIP; }
-    const sufr::ShrFilter flt{sufr::RepFilter{SUFR_REPEAT_BRANCHING, 1, 2, 0}, 0, 0};
-    hipLaunchKernelGGL((sufr::k_shr_find<T, sufr::SHR_PROFILE>), dim3(R.grid), dim3(256), 0, pl.stream, R.acc, ix->ix.text, R.bits, S.P, flt, R.tile,
-                       R.ntiles, S.t_cnt, S.t_best, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, S.best, num);
+    const sufr::RepFilter flt{SUFR_REPEAT_BRANCHING, 1, 2, 0, 0, 0};
+    uint64_t* const none = nullptr;
+    hipLaunchKernelGGL((sufr::k_rep_find<T, sufr::REP_PROFILE, true>), dim3(R.grid), dim3(256), 0, pl.stream, R.acc, ix->ix.text, R.bits, S.P, flt, R.tile,
+                       R.ntiles, R.t_cnt, R.t_best, none, none, none, none, S.best, num);
     hipLaunchKernelGGL(sufr::k_shr_suffix, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)S.best, num, (uint64_t*)d_common);
 #ifdef SUFR_HIP_PROBES
     for (hipEvent_t e : S.ev) if (e) (void)hipEventDestroy(e);      // (only sufr_hip_shared_device prints the stamps)
@@ -361,11 +225,7 @@ int common_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, c
 int shared_refusals(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t num_sequences, const char* what)
 {
     sufr::Pipeline& pl = ctx->pl;
-    if (const int rc = query_check(ctx, ix, what)) return rc;
-    if (ix->built_mql > 0) {
-        pl.set_error(std::string(what) + ": the index was built with max_query_len " + std::to_string(ix->built_mql) + ", its LCP is capped");
-        return SUFR_HIP_E_UNSUPPORTED;
-    }
+    if (const int rc = lcp_refusals(ctx, ix, what, what)) return rc;
     if (ix->ix.s >> sufr::SHR_RANK_BITS || num_sequences >> sufr::SHR_DOC_BITS) {
         pl.set_error(std::string(what) + ": 2^40 suffixes or 2^24 sequences, or more");
         return SUFR_HIP_E_UNSUPPORTED;
@@ -386,7 +246,6 @@ int sufr_hip_shared_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const vo
     if (total_out) *total_out = 0;
     if (!ctx || !ix) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
-    pl.err.clear();
     int rc;
     if ((rc = shared_refusals(ctx, ix, num_sequences, "shared"))) return rc;
     if (min_len == 0) { pl.set_error("shared: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
@@ -395,9 +254,8 @@ int sufr_hip_shared_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const vo
     if (!ix->ix.s) return 0;
     sufr::KmerSeqs q;
     if ((rc = kmer_prepare(ctx, ix, d_lcp, seq_starts, num_sequences, "shared", q))) return rc;
-    const sufr::ShrFilter flt{sufr::RepFilter{kind, min_len, min_count < 2 ? 2 : min_count, max_count}, min_seqs, max_seqs};
-    return ix->sa_width == 8 ? shared_run<uint64_t>(ctx, ix, d_lcp, q, flt, cap, d_rank, d_count, d_length, d_seqs, total_out, stats_out)
-                             : shared_run<uint32_t>(ctx, ix, d_lcp, q, flt, cap, d_rank, d_count, d_length, d_seqs, total_out, stats_out);
+    const sufr::RepFilter flt{kind, min_len, min_count < 2 ? 2 : min_count, max_count, min_seqs, max_seqs};
+    return by_width(ix, [&](auto w) { return shared_run<decltype(w)>(ctx, ix, d_lcp, q, flt, cap, d_rank, d_count, d_length, d_seqs, total_out, stats_out); });
 }
 
 int sufr_hip_common_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const uint64_t* seq_starts, uint64_t num_sequences,
@@ -405,7 +263,6 @@ int sufr_hip_common_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const vo
 {
     if (!ctx || !ix) return SUFR_HIP_E_INVALID;
     sufr::Pipeline& pl = ctx->pl;
-    pl.err.clear();
     int rc;
     if ((rc = shared_refusals(ctx, ix, num_sequences, "common"))) return rc;
     sufr::KmerSeqs q;
@@ -416,7 +273,7 @@ int sufr_hip_common_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const vo
         if (hipMemsetAsync(d_common, 0, num * 8, pl.stream) != hipSuccess) { pl.set_error("common: memset failed"); return SUFR_HIP_E_HIP; }
         return 0;
     }
-    return ix->sa_width == 8 ? common_run<uint64_t>(ctx, ix, d_lcp, q, num, d_common) : common_run<uint32_t>(ctx, ix, d_lcp, q, num, d_common);
+    return by_width(ix, [&](auto w) { return common_run<decltype(w)>(ctx, ix, d_lcp, q, num, d_common); });
 }
 
 }  // extern "C"

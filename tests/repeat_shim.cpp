@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 #include "../sufr_amd/csrc/sufr_repeat_scan.h"
 
@@ -28,17 +29,11 @@ uint64_t shim_rep_level_size(uint64_t s, uint32_t k) { return sufr::rep_level_si
 void shim_rep_pyramid(const uint64_t* ell, uint64_t s, uint64_t* up)
 {
     const uint32_t levels = sufr::rep_levels(s);
-    for (uint32_t k = 1; k <= levels; k++) {
-        const uint64_t* in = k == 1 ? ell : up + sufr::rep_level_offset(s, k - 1);
-        uint64_t* out = up + sufr::rep_level_offset(s, k);
-        const uint64_t n_in = sufr::rep_level_size(s, k - 1), n_out = sufr::rep_level_size(s, k);
-        for (uint64_t i = 0; i < n_out; i++) {
-            uint64_t low = ~(uint64_t)0;
-            for (uint64_t j = i * 64; j < n_in && j < i * 64 + 64; j++) if (in[j] < low) low = in[j];
-            out[i] = low;
-        }
-    }
+    for (uint32_t k = 1; k <= levels; k++)
+        sufr::rep_level_up(k == 1 ? ell : up + sufr::rep_level_offset(s, k - 1), sufr::rep_level_size(s, k - 1), up + sufr::rep_level_offset(s, k),
+                           sufr::rep_level_size(s, k));
 }
+void shim_rep_level_up(const uint64_t* in, uint64_t n_in, uint64_t* out, uint64_t n_out) { sufr::rep_level_up(in, n_in, out, n_out); }
 
 uint64_t shim_rep_search_left(const uint64_t* ell, const uint64_t* up, uint64_t s, uint64_t r, uint64_t v)
 {
@@ -53,6 +48,29 @@ void shim_rep_search_all(const uint64_t* ell, const uint64_t* up, uint64_t s, ui
 {
     const ShimAcc acc{ell, up, s};
     for (uint64_t r = 0; r < s; r++) { left[r] = sufr::rep_search_left(acc, s, r, ell[r]); right[r] = sufr::rep_search_right(acc, s, r, ell[r]); }
+}
+
+// rep_interval of every rank 1 <= r < s: is_rep[r] (0 / 1) and, for a representative, a[r], z[r], v[r]; rank 0 is none
+void shim_rep_interval_all(const uint64_t* ell, const uint64_t* up, uint64_t s, uint64_t min_len, uint8_t* is_rep, uint64_t* a, uint64_t* z, uint64_t* v)
+{
+    const ShimAcc acc{ell, up, s};
+    if (s) is_rep[0] = 0;
+    for (uint64_t r = 1; r < s; r++) {
+        is_rep[r] = 0;
+        sufr::rep_interval(acc, s, r, min_len, [&](uint64_t ia, uint64_t iz, uint64_t iv) { is_rep[r] = 1; a[r] = ia; z[r] = iz; v[r] = iv; });
+    }
+}
+
+// the RepBest of n candidates (5 words each: len, rep, rank, cnt, seq), merged as `parts` runs of take, then a merge of the
+// runs from the last to the first; out: 5 words
+void shim_rep_best(const uint64_t* cand, uint64_t n, uint64_t parts, uint64_t* out)
+{
+    if (!parts) parts = 1;
+    std::vector<sufr::RepBest> part(parts, sufr::RepBest{0, 0, 0, 0, 0});
+    for (uint64_t i = 0; i < n; i++) part[i % parts].take(cand[5 * i], cand[5 * i + 1], cand[5 * i + 2], cand[5 * i + 3], cand[5 * i + 4]);
+    sufr::RepBest b{0, 0, 0, 0, 0};
+    for (uint64_t k = parts; k > 0; k--) b.merge(part[k - 1]);
+    out[0] = b.len; out[1] = b.rep; out[2] = b.rank; out[3] = b.cnt; out[4] = b.seq;
 }
 
 // flags[0..s) (bytes 0 / 1) as words and their exclusive popcount prefix ((s + 63) / 64 entries each)
@@ -107,8 +125,65 @@ int main()
                 if (right[r - 1] != want) { printf("right: s %llu kind %d rank %llu\n", (unsigned long long)s, kind, (unsigned long long)(r - 1)); return 1; }
                 st.push_back(r - 1);
             }
+            // rep_interval: r is a representative iff the nearest <= on its left is strictly smaller (and ell[r] >= min_len)
+            for (const uint64_t min_len : {(uint64_t)1, (uint64_t)3}) {
+                std::vector<uint8_t> is_rep(s + 1);
+                std::vector<uint64_t> ia(s + 1), iz(s + 1), iv(s + 1);
+                shim_rep_interval_all(ell.data(), up.data(), s, min_len, is_rep.data(), ia.data(), iz.data(), iv.data());
+                st.clear();
+                for (uint64_t r = 0; r < s; r++) {
+                    while (!st.empty() && ell[st.back()] > ell[r]) st.pop_back();
+                    const bool want = r >= 1 && ell[r] >= min_len && !st.empty() && ell[st.back()] < ell[r];
+                    if ((is_rep[r] != 0) != want || (want && (ia[r] != st.back() || iz[r] != right[r] || iv[r] != ell[r]))) {
+                        printf("interval: s %llu kind %d min_len %llu rank %llu\n", (unsigned long long)s, kind, (unsigned long long)min_len, (unsigned long long)r);
+                        return 1;
+                    }
+                    st.push_back(r);
+                }
+                cases += s;
+            }
+            // rep_level_up: every level of the pyramid is the 64-wise minimum of the one below, entry by entry
+            for (uint32_t k = 1; k <= shim_rep_levels(s); k++) {
+                const uint64_t* in = k == 1 ? ell.data() : up.data() + sufr::rep_level_offset(s, k - 1);
+                const uint64_t n_in = shim_rep_level_size(s, k - 1), n_out = shim_rep_level_size(s, k);
+                std::vector<uint64_t> got(n_out + 1, 77);
+                shim_rep_level_up(in, n_in, got.data(), n_out);
+                for (uint64_t i = 0; i < n_out; i++) {
+                    const uint64_t want = *std::min_element(in + i * 64, in + std::min(n_in, i * 64 + 64));
+                    if (got[i] != want || up[sufr::rep_level_offset(s, k) + i] != want) { printf("level_up: s %llu level %u entry %llu\n", (unsigned long long)s, k, (unsigned long long)i); return 1; }
+                }
+                if (got[n_out] != 77) { printf("level_up: wrote past the end\n"); return 1; }
+                cases += n_out;
+            }
             cases += 2 * s + 1;
         }
+    // RepBest: the merge of random candidates, whatever their split into parts, is the first of a sort by (longer, smaller
+    // representative) with the maxima of the counts and of the sequence counts; few different lengths, so ties abound
+    for (int round = 0; round < 200; round++) {
+        const uint64_t n = rnd() % 40;
+        std::vector<uint64_t> cand(5 * n + 5);
+        for (uint64_t i = 0; i < n; i++) {
+            cand[5 * i] = rnd() % 4;
+            cand[5 * i + 1] = 1 + i * 7 % 41 + 41 * (rnd() % 2);      // (every representative once)
+            cand[5 * i + 2] = 1000 + i;                               // (every rank once: a rank from the wrong candidate shows)
+            cand[5 * i + 3] = rnd() % 9; cand[5 * i + 4] = rnd() % 5;
+        }
+        std::vector<uint64_t> order(n);
+        for (uint64_t i = 0; i < n; i++) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
+            return cand[5 * x] != cand[5 * y] ? cand[5 * x] > cand[5 * y] : cand[5 * x + 1] < cand[5 * y + 1];
+        });
+        uint64_t want[5] = {0, 0, 0, 0, 0};
+        if (n && cand[5 * order[0]]) { want[0] = cand[5 * order[0]]; want[1] = cand[5 * order[0] + 1]; want[2] = cand[5 * order[0] + 2]; }
+        for (uint64_t i = 0; i < n; i++) { want[3] = std::max(want[3], cand[5 * i + 3]); want[4] = std::max(want[4], cand[5 * i + 4]); }
+        for (const uint64_t parts : {(uint64_t)1, (uint64_t)3, (uint64_t)64}) {
+            uint64_t got[5];
+            shim_rep_best(cand.data(), n, parts, got);
+            for (int c = 0; c < 5; c++)
+                if (got[c] != want[c]) { printf("best: round %d parts %llu column %d\n", round, (unsigned long long)parts, c); return 1; }
+            cases++;
+        }
+    }
     for (const uint64_t s : {0ull, 1ull, 63ull, 64ull, 65ull, 128ull, 1000ull}) {
         std::vector<uint8_t> flags(s + 1);
         for (uint64_t r = 0; r < s; r++) flags[r] = rnd() % 3 == 0;

@@ -184,6 +184,51 @@ def test_pairs_and_intervals_across_tiles(ctx, oracle, tmp_path):
         ctx.set_repeat_tile(0)
 
 
+def test_shared_with_open_seqs_is_repeats_plus_a_column(ctx, oracle, tmp_path):
+    """one find kernel serves both calls: with min_seqs = max_seqs = 0 shared keeps what repeats keeps, in its order, and the
+    counting calls agree -- on the three indexes of uniprot.sufr (32- and 64-bit arrays) and on the two small collections of
+    test_pairs_and_intervals_across_tiles, whose intervals cross the tiles and the staged windows"""
+    rng = np.random.default_rng(8)
+    piece = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 80)]
+    same = oracle_file(oracle, tmp_path, np.concatenate([np.concatenate([piece, np.frombuffer(b"%", dtype=np.uint8)])] * 40)[:-1], "same", is_dna=True)
+    body = np.full(3002, ord("A"), dtype=np.uint8)
+    body[[1000, 2001]] = ord("%")
+    a3 = oracle_file(oracle, tmp_path, body, "a3", is_dna=True)
+    assert same.num_sequences == 40 and same.len_suffixes > 12 * T and a3.num_sequences == 3 and a3.len_suffixes > 8 * T
+    uni = SufrFile(EXP / "uniprot.sufr")
+    cases = [(f"uniprot {tag}", uni, ix, lcp) for tag, ix, lcp in indexes(ctx, uni)]
+    cases += [(name, f, DeviceIndex.load(ctx, f), _dev(np.asarray(f.lcp))) for name, f in (("same", same), ("a3", a3))]
+    L = sufr_amd.lib()
+    seen = 0
+    try:
+        for name, f, ix, lcp in cases:
+            st_h = np.array(f.sequence_starts, dtype=np.uint64)
+            head = (ctx.handle, ix._h, lcp.data_ptr(), st_h.ctypes.data, st_h.size)
+            for tile in (T, 0):
+                ctx.set_repeat_tile(tile)
+                for kind in KINDS:
+                    for ml in (1, 5):
+                        for mc, xc in ((2, 0), (3, 4)):
+                            tag = (name, tile, kind, ml, mc, xc)
+                            shr = ix.shared_device(lcp, kind, ml, mc, xc, 0, 0, f.sequence_starts)
+                            rep = ix.repeats_device(lcp, kind, ml, mc, xc, f.sequence_starts)
+                            for i in range(3):
+                                assert np.array_equal(_u64(shr[i]), _u64(rep[i])), (tag, i)
+                            assert _u64(shr[3]).size == _u64(rep[0]).size and {k: shr[4][k] for k in rep[3]} == rep[3], (tag, shr[4], rep[3])
+                            # the counting calls: no room and no arrays
+                            ts, tr = C.c_uint64(0), C.c_uint64(0)
+                            rs = L.sufr_hip_shared_device(*head, kind, ml, mc, xc, 0, 0, 0, None, None, None, None, C.byref(ts), None)
+                            rr = L.sufr_hip_repeats_device(*head, kind, ml, mc, xc, 0, None, None, None, C.byref(tr), None)
+                            assert ts.value == tr.value == rep[3]["records"], (tag, ts.value, tr.value)
+                            assert rs == rr == (-5 if tr.value else 0), (tag, rs, rr)       # (E_CAPACITY; nothing kept: nothing to refuse)
+                            seen += tr.value
+        assert seen > 0
+    finally:
+        ctx.set_repeat_tile(0)
+        for _, _, ix, _ in cases:
+            ix.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the digits of the sort
 # ---------------------------------------------------------------------------------------------------------------------
