@@ -33,6 +33,7 @@
 
 #include <algorithm>
 #include <fstream>
+#include <optional>
 #include <sstream>
 #include <time.h>
 
@@ -132,6 +133,14 @@ int usage(FILE* f)
     return f == stderr ? 2 : 0;
 }
 
+// need(i, opt): the value of the option at argv[i], the argument behind it; without one the usage error and exit status 2
+auto value_reader(int argc, char** argv)
+{
+    return [argc, argv](int& i, const char* opt) -> const char* {
+        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
+        return argv[++i];
+    };
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // query sub-commands (sufr/src/lib.rs:292-646)
@@ -196,54 +205,78 @@ sufr_file* open_or_die(const std::string& path)
     return f;
 }
 
+// an open .sufr file, closed on every way out
+struct OpenFile {
+    sufr_file* f;
+    explicit OpenFile(const std::string& path) : f(open_or_die(path)) {}
+    ~OpenFile() { sufr_file_close(f); }
+    operator sufr_file*() const { return f; }
+    OpenFile(const OpenFile&) = delete;
+    OpenFile& operator=(const OpenFile&) = delete;
+};
+
+// A context on one device with the index of an open file on it: what every sub-command but create runs on with --device.
+// Not up(): error() is the library's text.  Index, then context are released with the object.
+struct DeviceIndex {
+    sufr_hip_ctx* ctx;
+    sufr_hip_index* ix = nullptr;
+    int rc = SUFR_HIP_E_HIP;                    // of the load (the context did not come up: E_HIP)
+    DeviceIndex(int device, sufr_file* f) : ctx(sufr_hip_create(device)) { if (ctx) rc = sufr_hip_index_load(ctx, f, &ix); }
+    ~DeviceIndex()
+    {
+        if (ix) sufr_hip_index_free(ix);
+        if (ctx) sufr_hip_destroy(ctx);
+    }
+    bool up() const { return ctx && rc == 0; }
+    const char* error() const { return sufr_hip_last_error(ctx); }     // (no context: the text of the failed create)
+    DeviceIndex(const DeviceIndex&) = delete;
+    DeviceIndex& operator=(const DeviceIndex&) = delete;
+};
+
 // Rank range of every query: one by one on the host, or as one batch on a GPU (text + suffix array copied to HBM first:
-// worth it for many queries; the answers are the same, tests/test_gpu_query.py)
+// worth it for many queries; the answers are the same, tests/test_gpu_query.py).  false: an error, printed
 struct Hit { bool found; uint64_t lo, hi; };
-std::vector<Hit> search_all(sufr_file* f, const QueryArgs& a, const std::vector<std::string>& queries)
+bool search_all(sufr_file* f, const QueryArgs& a, const std::vector<std::string>& queries, std::vector<Hit>& hits)
 {
-    std::vector<Hit> hits(queries.size(), Hit{false, 0, 0});
     std::string bytes;
     std::vector<uint64_t> off(queries.size() + 1, 0), lo(queries.size(), 0), hi(queries.size(), 0);
     for (size_t i = 0; i < queries.size(); i++) { bytes += queries[i]; off[i + 1] = bytes.size(); }
-    if (a.device < 0) {
+    if (a.device < 0)
         sufr_file_search_batch(f, (const uint8_t*)bytes.data(), off.data(), queries.size(), a.has_mql, a.mql, lo.data(), hi.data(), a.threads);
-        for (size_t i = 0; i < queries.size(); i++) hits[i] = Hit{hi[i] > lo[i], lo[i], hi[i]};
-        return hits;
+    else {
+        DeviceIndex dev(a.device, f);
+        if (!dev.up() || sufr_hip_search_batch(dev.ctx, dev.ix, (const uint8_t*)bytes.data(), off.data(), queries.size(), a.has_mql, a.mql,
+                                               lo.data(), hi.data()) != 0) {
+            fprintf(stderr, "Error: %s\n", dev.error());
+            return false;
+        }
     }
-    sufr_hip_ctx* ctx = sufr_hip_create(a.device);
-    if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); exit(1); }
-    sufr_hip_index* ix = nullptr;
-    if (sufr_hip_index_load(ctx, f, &ix) != 0 ||
-        sufr_hip_search_batch(ctx, ix, (const uint8_t*)bytes.data(), off.data(), queries.size(), a.has_mql, a.mql, lo.data(), hi.data()) != 0) {
-        fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx));
-        exit(1);
-    }
+    hits.resize(queries.size());
     for (size_t i = 0; i < queries.size(); i++) hits[i] = Hit{hi[i] > lo[i], lo[i], hi[i]};
-    sufr_hip_index_free(ix);
-    sufr_hip_destroy(ctx);
-    return hits;
+    return true;
 }
 
 int cmd_count(const QueryArgs& a)
 {
-    sufr_file* f = open_or_die(a.file);
+    OpenFile f(a.file);
     OutFile out;
     if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
     const std::vector<std::string> queries = expand_queries(a.positional);
-    const std::vector<Hit> hits = search_all(f, a, queries);
+    std::vector<Hit> hits;
+    if (!search_all(f, a, queries, hits)) return 1;
     for (size_t i = 0; i < queries.size(); i++)
         fprintf(out.f, "%s %llu\n", queries[i].c_str(), (unsigned long long)(hits[i].found ? hits[i].hi - hits[i].lo : 0));
-    sufr_file_close(f);
     return 0;
 }
 
 int cmd_locate(const QueryArgs& a)
 {
-    sufr_file* f = open_or_die(a.file);
+    OpenFile f(a.file);
     OutFile out;
     if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
     const std::vector<std::string> queries = expand_queries(a.positional);
-    const std::vector<Hit> hits = search_all(f, a, queries);
+    std::vector<Hit> hits;
+    if (!search_all(f, a, queries, hits)) return 1;
     for (size_t qi = 0; qi < queries.size(); qi++) {
         const std::string& q = queries[qi];
         const uint64_t lo = hits[qi].lo, hi = hits[qi].hi;
@@ -279,19 +312,19 @@ int cmd_locate(const QueryArgs& a)
         if (!buf.empty()) fprintf(out.f, "%s %s\n", prev.c_str(), buf.c_str());
         fprintf(out.f, "//\n");
     }
-    sufr_file_close(f);
     return 0;
 }
 
 int cmd_extract(const QueryArgs& a)
 {
-    sufr_file* f = open_or_die(a.file);
+    OpenFile f(a.file);
     OutFile out;
     if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
     sufr_file_meta m; sufr_file_metadata(f, &m);
     const uint8_t* text = sufr_file_text(f);
     const std::vector<std::string> queries = expand_queries(a.positional);
-    const std::vector<Hit> hits = search_all(f, a, queries);
+    std::vector<Hit> hits;
+    if (!search_all(f, a, queries, hits)) return 1;
     for (size_t qi = 0; qi < queries.size(); qi++) {
         const std::string& q = queries[qi];
         const uint64_t lo = hits[qi].lo, hi = hits[qi].hi;
@@ -318,7 +351,6 @@ int cmd_extract(const QueryArgs& a)
             fputc('\n', out.f);
         }
     }
-    sufr_file_close(f);
     return 0;
 }
 
@@ -348,13 +380,13 @@ bool parse_ranks(const std::string& arg, std::vector<uint64_t>& out, std::string
 
 int cmd_list(const QueryArgs& a)
 {
-    sufr_file* f = open_or_die(a.file);
+    OpenFile f(a.file);
     OutFile out;
     if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
     std::vector<uint64_t> ranks;
     for (const std::string& r : a.positional) {
         std::string err;
-        if (!parse_ranks(r, ranks, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); sufr_file_close(f); return 1; }
+        if (!parse_ranks(r, ranks, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
     }
     sufr_file_meta m; sufr_file_metadata(f, &m);
     const uint8_t* text = sufr_file_text(f);
@@ -381,7 +413,6 @@ int cmd_list(const QueryArgs& a)
             else fprintf(stderr, "Invalid rank: %llu\n", (unsigned long long)r);
         }
     }
-    sufr_file_close(f);
     return 0;
 }
 
@@ -401,7 +432,7 @@ std::vector<std::string> wrap_text(const std::string& s, size_t width)
 
 int cmd_summarize(const QueryArgs& a)
 {
-    sufr_file* f = open_or_die(a.file);
+    OpenFile f(a.file);
     sufr_file_meta m; sufr_file_metadata(f, &m);
     std::vector<std::pair<std::string, std::vector<std::string>>> rows;     // name, value lines
     auto row = [&](const std::string& k, const std::string& v) { rows.push_back({k, {v}}); };
@@ -445,7 +476,6 @@ int cmd_summarize(const QueryArgs& a)
             printf("| %-*s | %-*s |\n", (int)w0, i == 0 ? r.first.c_str() : "", (int)w1, r.second[i].c_str());
         printf("%s\n", rule.c_str());
     }
-    sufr_file_close(f);
     return 0;
 }
 
@@ -470,15 +500,14 @@ bool named_queries(const QueryArgs& a, std::vector<std::string>& names, std::vec
 }
 
 // What match, mems, approx and edit hold while they run: the .sufr file, the output, the named queries packed into one
-// batch and, with --device, the context and the index on it.  Everything is released on every way out.
+// batch and, with --device, the index on that device.  Everything is released on every way out.
 struct QuerySession {
     sufr_file* f = nullptr;
     OutFile out;
     std::vector<std::string> names;
     std::string bytes;                          // the queries, one after the other ...
     std::vector<uint64_t> off;                  // ... query i is bytes [off[i], off[i + 1])
-    sufr_hip_ctx* ctx = nullptr;
-    sufr_hip_index* ix = nullptr;
+    std::optional<DeviceIndex> dev;
 
     bool open(const QueryArgs& a)
     {
@@ -493,20 +522,14 @@ struct QuerySession {
         off.assign(seqs.size() + 1, 0);
         for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
         if (a.device < 0) return true;
-        ctx = sufr_hip_create(a.device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return false; }
-        if (sufr_hip_index_load(ctx, f, &ix) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(ctx)); return false; }
+        dev.emplace(a.device, f);
+        if (!dev->up()) { fprintf(stderr, "Error: %s\n", dev->error()); return false; }
         return true;
     }
     const uint8_t* q() const { return (const uint8_t*)bytes.data(); }
     uint64_t nq() const { return off.size() - 1; }
     // the device is not held while the records are printed: the output may be large
-    void release_device()
-    {
-        if (ix) sufr_hip_index_free(ix);
-        if (ctx) sufr_hip_destroy(ctx);
-        ix = nullptr; ctx = nullptr;
-    }
+    void release_device() { dev.reset(); }
     ~QuerySession() { release_device(); if (f) sufr_file_close(f); }
     QuerySession() = default;
     QuerySession(const QuerySession&) = delete;
@@ -520,11 +543,11 @@ struct QuerySession {
         for (;;) {
             const int rc = call(cap, &total);
             if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-            if (rc == SUFR_HIP_E_UNSUPPORTED && !(ok_unsupported && ctx && strstr(sufr_hip_last_error(ctx), ok_unsupported))) {
+            if (rc == SUFR_HIP_E_UNSUPPORTED && !(ok_unsupported && dev && strstr(dev->error(), ok_unsupported))) {
                 fprintf(stderr, "Error: %s: %s does not support files built with a seed mask\n", a.file.c_str(), cmd);
                 return false;
             }
-            if (rc != 0) { fprintf(stderr, "Error: %s\n", ctx ? sufr_hip_last_error(ctx) : (std::string(cmd) + " failed").c_str()); return false; }
+            if (rc != 0) { fprintf(stderr, "Error: %s\n", dev ? dev->error() : (std::string(cmd) + " failed").c_str()); return false; }
             return true;
         }
     }
@@ -557,7 +580,7 @@ int cmd_match(const QueryArgs& a)
     std::vector<uint32_t> qo, len;
     if (!s.until_fits(a, "match", s.bytes.size() / 8 + 16, total, [&](uint64_t cap, uint64_t* tot) {
             qi.resize(cap); lo.resize(cap); hi.resize(cap); qo.resize(cap); len.resize(cap);
-            return s.ix ? sufr_hip_smems(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(),
+            return s.dev ? sufr_hip_smems(s.dev->ctx, s.dev->ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(),
                                          lo.data(), hi.data(), tot)
                         : sufr_file_smems(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(), lo.data(),
                                           hi.data(), tot, a.threads);
@@ -601,7 +624,7 @@ int cmd_mems(const QueryArgs& a)
     std::vector<uint8_t> st;
     if (!s.until_fits(a, "mems", s.bytes.size() / 4 + 16, total, [&](uint64_t cap, uint64_t* tot) {
             qi.resize(cap); pos.resize(cap); qo.resize(cap); len.resize(cap); st.resize(cap);
-            return s.ix ? sufr_hip_mems(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, a.max_occ, flags, cap, qi.data(), qo.data(),
+            return s.dev ? sufr_hip_mems(s.dev->ctx, s.dev->ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, a.max_occ, flags, cap, qi.data(), qo.data(),
                                         st.data(), len.data(), pos.data(), tot)
                         : sufr_file_mems(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, a.max_occ, flags, cap, qi.data(), qo.data(),
                                          st.data(), len.data(), pos.data(), tot, a.threads);
@@ -626,7 +649,7 @@ int cmd_approx(const QueryArgs& a)
     std::vector<uint8_t> st, mm;
     if (!s.until_fits(a, "approx", 4 * s.nq() + 16, total, [&](uint64_t cap, uint64_t* tot) {
             qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
-            return s.ix ? sufr_hip_approx(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.mismatches, a.max_occ, flags, cap, qi.data(),
+            return s.dev ? sufr_hip_approx(s.dev->ctx, s.dev->ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.mismatches, a.max_occ, flags, cap, qi.data(),
                                           st.data(), pos.data(), mm.data(), tot)
                         : sufr_file_approx(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.mismatches, a.max_occ, flags, cap, qi.data(), st.data(),
                                            pos.data(), mm.data(), tot, a.threads);
@@ -653,7 +676,7 @@ int cmd_edit(const QueryArgs& a)
     std::vector<uint8_t> st, ed;
     if (!s.until_fits(a, "edit", (2 * a.edits + 1) * s.nq() + 16, total, [&](uint64_t cap, uint64_t* tot) {
             qi.resize(cap); end.resize(cap); st.resize(cap); ed.resize(cap);
-            return s.ix ? sufr_hip_edit(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.edits, a.max_occ, flags, cap, qi.data(), st.data(),
+            return s.dev ? sufr_hip_edit(s.dev->ctx, s.dev->ix, s.q(), s.off.data(), s.nq(), (uint32_t)a.edits, a.max_occ, flags, cap, qi.data(), st.data(),
                                         end.data(), ed.data(), tot)
                         : sufr_file_edit(s.f, s.q(), s.off.data(), s.nq(), (uint32_t)a.edits, a.max_occ, flags, cap, qi.data(), st.data(), end.data(),
                                          ed.data(), tot, a.threads);
@@ -665,13 +688,13 @@ int cmd_edit(const QueryArgs& a)
         char err[512] = "";
         uint64_t runs = 0;
         for (int pass = 0; pass < 2; pass++) {
-            const int rc = s.ix ? sufr_hip_edit_trace(s.ctx, s.ix, s.q(), s.off.data(), s.nq(), total, qi.data(), st.data(), end.data(), ed.data(),
+            const int rc = s.dev ? sufr_hip_edit_trace(s.dev->ctx, s.dev->ix, s.q(), s.off.data(), s.nq(), total, qi.data(), st.data(), end.data(), ed.data(),
                                                       cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs)
                                 : sufr_file_edit_trace(s.f, s.q(), s.off.data(), s.nq(), total, qi.data(), st.data(), end.data(), ed.data(),
                                                        cigar.size(), start.data(), coff.data(), cigar.empty() ? nullptr : cigar.data(), &runs,
                                                        a.threads, err, sizeof err);
             if (rc == SUFR_HIP_E_CAPACITY && pass == 0) { cigar.resize(runs); continue; }
-            if (rc != 0) { fprintf(stderr, "Error: %s\n", s.ctx ? sufr_hip_last_error(s.ctx) : err); return 1; }
+            if (rc != 0) { fprintf(stderr, "Error: %s\n", s.dev ? s.dev->error() : err); return 1; }
             break;
         }
     }
@@ -695,10 +718,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     QueryArgs a;
     a.threads = threads;
     std::vector<std::string> pos;
-    auto need = [&](int& i, const char* opt) -> const char* {
-        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
-        return argv[++i];
-    };
+    auto need = value_reader(argc, argv);
     const bool is_list = cmd == "list", is_extract = cmd == "extract", is_locate = cmd == "locate", is_sum = cmd == "summarize";
     const bool is_edit = cmd == "edit";
     const bool is_approx = cmd == "approx" || is_edit;
@@ -755,93 +775,210 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     return cmd_summarize(a);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the analyses of the indexed text from its LCP array: kmers, repeats, shared, lz
+// ---------------------------------------------------------------------------------------------------------------
+// What the four hold while they run: the arguments they share, the .sufr file with its metadata and sequence starts, the
+// output and, with --device, the index on that device and every device allocation (the LCP array is the first).  The
+// first failure stays in `rc` (with a text of the session's own in `err` for allocations and copies) and turns the steps
+// after it into no-ops, so a command reads top to bottom and asks once, in computed().  Everything is released on every
+// way out.
+struct AnalysisSession {
+    std::string file, output;
+    int device = -1;
+    sufr_file* f = nullptr;
+    sufr_file_meta m;
+    std::vector<uint64_t> starts;               // of the sequences: what the *_device calls take beside the LCP array
+    std::optional<DeviceIndex> dev;
+    void* d_lcp = nullptr;
+    std::vector<void*> allocations;
+    OutFile out;
+    int rc = 0;
+    std::string err;
+
+    // the arguments behind the sub-command: own(s, i, need) takes the command's options, the rest is the same for all four.
+    // Returns the exit status, or -1 to go on
+    template <typename Own>
+    int parse(int argc, char** argv, int first, Own own)
+    {
+        auto need = value_reader(argc, argv);
+        for (int i = first; i < argc; i++) {
+            const std::string s = argv[i];
+            if (s == "-h" || s == "--help") { usage(stdout); return 0; }
+            else if (own(s, i, need)) {}
+            else if (s == "--device") device = atoi(need(i, "--device"));
+            else if (s == "-o" || s == "--output") output = need(i, "-o");
+            else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+            else if (file.empty()) file = s;
+            else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
+        }
+        return -1;
+    }
+    static int missing(const char* what) { fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n", what); return 2; }
+
+    // the file and, with --device, the index and the LCP array on it.  false: no file or no context, printed
+    bool open()
+    {
+        f = open_or_die(file);
+        sufr_file_metadata(f, &m);
+        starts.resize(m.num_sequences);
+        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
+        if (device < 0) return true;
+        dev.emplace(device, f);
+        if (!dev->ctx) { fprintf(stderr, "Error: %s\n", dev->error()); return false; }
+        rc = dev->rc;
+        const uint64_t bytes = m.len_suffixes * (uint64_t)m.index_width;
+        if (!rc && hipSetDevice(device) != hipSuccess) fail("device memory for the LCP array");
+        d_lcp = alloc(bytes + 8, "the LCP array");
+        if (!rc && bytes && hipMemcpy(d_lcp, sufr_file_lcp_array(f), bytes, hipMemcpyHostToDevice) != hipSuccess) fail("device memory for the LCP array");
+        return true;
+    }
+    void fail(const std::string& text) { rc = SUFR_HIP_E_HIP; err = text; }
+    // device memory that lives as long as the session (nullptr after a failure)
+    void* alloc(uint64_t bytes, const char* what)
+    {
+        void* p = nullptr;
+        if (rc) return p;
+        if (hipMalloc(&p, bytes) != hipSuccess) { fail(std::string("device memory for ") + what); return nullptr; }
+        allocations.push_back(p);
+        return p;
+    }
+    // call() -> rc enqueues on the device; then the context is synchronised and the results are copied to the host
+    struct Back { void* host; const void* device; uint64_t bytes; };
+    template <typename Call>
+    void on_device(Call call, const std::vector<Back>& results)
+    {
+        if (!rc) rc = call();
+        if (!rc) rc = sufr_hip_synchronize(dev->ctx);
+        for (const Back& b : results)
+            if (!rc && b.device && b.bytes && hipMemcpy(b.host, b.device, b.bytes, hipMemcpyDeviceToHost) != hipSuccess) fail("copying the results");
+    }
+    // The records of a call that counts, then fills: `ncols` parallel uint64 columns, cols[i] sized to `total` on return.
+    // host / device(cap, columns, &total) -> rc are the two entry points; the one of this session is called with cap 0 and
+    // null columns, and where that says E_CAPACITY once more with room for `total`: host columns, or one device block of
+    // total * ncols entries (column i at i * total) that is copied back.  A count of 0 ends it after the first call
+    template <typename Host, typename Device>
+    void counted(size_t ncols, std::vector<uint64_t>* cols, uint64_t& total, Host host, Device device)
+    {
+        uint64_t* c[4] = {nullptr, nullptr, nullptr, nullptr};
+        auto call = [&](uint64_t cap) { return dev ? device(cap, c, &total) : host(cap, c, &total); };
+        if (rc) return;
+        rc = call(0);
+        if (rc != SUFR_HIP_E_CAPACITY) return;
+        rc = 0;
+        const uint64_t n = total;
+        for (size_t i = 0; i < ncols; i++) { cols[i].resize(n); c[i] = cols[i].data(); }
+        if (!dev) { rc = call(n); return; }
+        uint64_t* block = (uint64_t*)alloc(n * 8 * ncols, "the records");
+        if (!block) return;
+        std::vector<Back> back;
+        for (size_t i = 0; i < ncols; i++) { c[i] = block + i * n; back.push_back({cols[i].data(), c[i], n * 8}); }
+        on_device([&]() { return call(n); }, back);
+    }
+    // the device is not held while the output is written: it may be large
+    void release_device()
+    {
+        for (void* p : allocations) (void)hipFree(p);
+        allocations.clear();
+        dev.reset();
+    }
+    // After the calls: a failure is reported as "Error: <file>: <text>" -- the session's own text, on the device the
+    // library's, else the command's text for the code -- and the output is opened only after a success.  false: exit status 1
+    bool computed(const char* unsupported, const char* invalid, const char* failed)
+    {
+        if (rc && err.empty() && dev) err = dev->error();
+        release_device();
+        if (rc) {
+            if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? unsupported : rc == SUFR_HIP_E_INVALID ? invalid : failed;
+            fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
+            return false;
+        }
+        if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); return false; }
+        return true;
+    }
+    ~AnalysisSession() { release_device(); if (f) sufr_file_close(f); }
+    AnalysisSession() = default;
+    AnalysisSession(const AnalysisSession&) = delete;
+    AnalysisSession& operator=(const AnalysisSession&) = delete;
+};
+
+// --kind of repeats and shared.  false: the usage error, printed
+bool repeat_kind(const std::string& name, uint32_t& kind)
+{
+    if (name == "branching") kind = SUFR_REPEAT_BRANCHING;
+    else if (name == "maximal") kind = SUFR_REPEAT_MAXIMAL;
+    else if (name == "super" || name == "supermaximal") kind = SUFR_REPEAT_SUPERMAXIMAL;
+    else { fprintf(stderr, "error: invalid value '%s' for '--kind': branching, maximal or super\n", name.c_str()); return false; }
+    return true;
+}
+
+// one record of repeats / shared: length, count, (seqs,) the first max_positions occurrences in text order (0: all)
+void print_repeat(FILE* out, const sufr_file* f, uint64_t rank, uint64_t count, uint64_t length, const uint64_t* seqs, uint64_t max_positions)
+{
+    std::vector<uint64_t> pos(count);
+    for (uint64_t j = 0; j < count; j++) pos[j] = sufr_file_suffix(f, rank + j);
+    std::sort(pos.begin(), pos.end());
+    fprintf(out, "%llu\t%llu\t", (unsigned long long)length, (unsigned long long)count);
+    if (seqs) fprintf(out, "%llu\t", (unsigned long long)*seqs);
+    const uint64_t show = max_positions && max_positions < count ? max_positions : count;
+    for (uint64_t j = 0; j < show; j++) fprintf(out, "%s%s", j ? " " : "", place(f, false, pos[j]).c_str());
+    fputc('\n', out);
+}
+
+// the stats behind the records: one "# key<TAB>value" line each
+void print_stats(FILE* out, std::initializer_list<std::pair<const char*, uint64_t>> stats)
+{
+    for (const auto& s : stats) fprintf(out, "# %s\t%llu\n", s.first, (unsigned long long)s.second);
+}
+
 // sufr kmers: the spectrum to standard output (or -o), the by-position arrays to --occ / --unique
 int run_kmers(int argc, char** argv, int first, int threads)
 {
-    std::string file, output, occ_path, uniq_path;
+    AnalysisSession s;
+    std::string occ_path, uniq_path;
     uint64_t k = 0, bins = 256;
     bool have_k = false;
-    int device = -1;
-    auto need = [&](int& i, const char* opt) -> const char* {
-        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
-        return argv[++i];
-    };
-    for (int i = first; i < argc; i++) {
-        const std::string s = argv[i];
-        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
-        else if (s == "-k") { k = strtoull(need(i, "-k"), nullptr, 10); have_k = true; }
-        else if (s == "-b" || s == "--bins") bins = strtoull(need(i, "-b"), nullptr, 10);
-        else if (s == "--device") device = atoi(need(i, "--device"));
-        else if (s == "--occ") occ_path = need(i, "--occ");
-        else if (s == "--unique") uniq_path = need(i, "--unique");
-        else if (s == "-o" || s == "--output") output = need(i, "-o");
-        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-        else if (file.empty()) file = s;
-        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-    }
-    if (file.empty() || !have_k) { fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n", file.empty() ? "<SUFR>" : "-k <K>"); return 2; }
-    sufr_file* f = open_or_die(file);
-    sufr_file_meta m;
-    sufr_file_metadata(f, &m);
-    const uint64_t w = (uint64_t)m.index_width, n = m.text_len, s = m.len_suffixes;
+    const int parsed = s.parse(argc, argv, first, [&](const std::string& o, int& i, auto& need) {
+        if (o == "-k") { k = strtoull(need(i, "-k"), nullptr, 10); have_k = true; }
+        else if (o == "-b" || o == "--bins") bins = strtoull(need(i, "-b"), nullptr, 10);
+        else if (o == "--occ") occ_path = need(i, "--occ");
+        else if (o == "--unique") uniq_path = need(i, "--unique");
+        else return false;
+        return true;
+    });
+    if (parsed >= 0) return parsed;
+    if (s.file.empty() || !have_k) return s.missing(s.file.empty() ? "<SUFR>" : "-k <K>");
+    if (!s.open()) return 1;
+    const uint64_t nw = s.m.text_len * (uint64_t)s.m.index_width;       // bytes of a by-position array
+    const bool want_occ = !occ_path.empty(), want_uniq = !uniq_path.empty();
     std::vector<uint64_t> hist(bins ? bins : 1, 0);
-    std::vector<uint8_t> occ(occ_path.empty() ? 0 : n * w + 8), uniq(uniq_path.empty() ? 0 : n * w + 8);
+    std::vector<uint8_t> occ(want_occ ? nw + 8 : 0), uniq(want_uniq ? nw + 8 : 0);
     sufr_kmer_stats st{0, 0, 0, 0};
-    int rc = 0;
-    std::string err;
-    if (device < 0) {
-        rc = sufr_file_kmers(f, k, SUFR_KMER_BY_POSITION, bins, hist.data(), occ_path.empty() ? nullptr : occ.data(), &st, threads);
-        if (!rc && !uniq_path.empty()) rc = sufr_file_unique_lengths(f, SUFR_KMER_BY_POSITION, uniq.data(), threads);
+    if (!s.dev) {
+        s.rc = sufr_file_kmers(s.f, k, SUFR_KMER_BY_POSITION, bins, hist.data(), want_occ ? occ.data() : nullptr, &st, threads);
+        if (!s.rc && want_uniq) s.rc = sufr_file_unique_lengths(s.f, SUFR_KMER_BY_POSITION, uniq.data(), threads);
     } else {
-        sufr_hip_ctx* ctx = sufr_hip_create(device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
-        sufr_hip_index* ix = nullptr;
-        std::vector<uint64_t> starts(m.num_sequences);
-        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
-        void *d_lcp = nullptr, *d_hist = nullptr, *d_out = nullptr;
-        rc = sufr_hip_index_load(ctx, f, &ix);
-        const bool want_out = !occ_path.empty() || !uniq_path.empty();
-        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess || hipMalloc(&d_hist, hist.size() * 8) != hipSuccess ||
-                    (want_out && hipMalloc(&d_out, n * w + 8) != hipSuccess) ||
-                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
-            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array and the outputs";
-        }
-        if (!rc) rc = sufr_hip_kmers_device(ctx, ix, d_lcp, starts.data(), starts.size(), k, SUFR_KMER_BY_POSITION, bins, d_hist,
-                                            occ_path.empty() ? nullptr : d_out, &st);
-        if (!rc && (hipMemcpy(hist.data(), d_hist, hist.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                    (!occ_path.empty() && n && hipMemcpy(occ.data(), d_out, n * w, hipMemcpyDeviceToHost) != hipSuccess))) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
-        if (!rc && !uniq_path.empty()) {
-            rc = sufr_hip_unique_lengths_device(ctx, ix, d_lcp, starts.data(), starts.size(), SUFR_KMER_BY_POSITION, d_out);
-            if (!rc) rc = sufr_hip_synchronize(ctx);
-            if (!rc && n && hipMemcpy(uniq.data(), d_out, n * w, hipMemcpyDeviceToHost) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
-        }
-        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
-        if (d_lcp) (void)hipFree(d_lcp);
-        if (d_hist) (void)hipFree(d_hist);
-        if (d_out) (void)hipFree(d_out);
-        if (ix) sufr_hip_index_free(ix);
-        sufr_hip_destroy(ctx);
+        void* d_hist = s.alloc(hist.size() * 8, "the outputs");
+        void* d_out = want_occ || want_uniq ? s.alloc(nw + 8, "the outputs") : nullptr;       // the occurrence map, then the unique lengths
+        s.on_device([&]() { return sufr_hip_kmers_device(s.dev->ctx, s.dev->ix, s.d_lcp, s.starts.data(), s.starts.size(), k, SUFR_KMER_BY_POSITION,
+                                                         bins, d_hist, want_occ ? d_out : nullptr, &st); },
+                    {{hist.data(), d_hist, hist.size() * 8}, {occ.data(), want_occ ? d_out : nullptr, nw}});
+        if (want_uniq)
+            s.on_device([&]() { return sufr_hip_unique_lengths_device(s.dev->ctx, s.dev->ix, s.d_lcp, s.starts.data(), s.starts.size(),
+                                                                      SUFR_KMER_BY_POSITION, d_out); }, {{uniq.data(), d_out, nw}});
     }
-    sufr_file_close(f);
-    if (rc) {
-        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "kmers does not support files built with a seed mask, and a file built with a max query length only up to that k (no --unique)"
-                             : rc == SUFR_HIP_E_INVALID ? "kmers: k and the number of bins must be at least 1" : "kmers failed";
-        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
-        return 1;
-    }
-    OutFile out;
-    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); return 1; }
+    if (!s.computed("kmers does not support files built with a seed mask, and a file built with a max query length only up to that k (no --unique)",
+                    "kmers: k and the number of bins must be at least 1", "kmers failed")) return 1;
     for (uint64_t i = 0; i < bins; i++) {
         if (!hist[i]) continue;
-        if (i + 1 == bins) fprintf(out.f, ">=%llu\t%llu\n", (unsigned long long)bins, (unsigned long long)hist[i]);
-        else fprintf(out.f, "%llu\t%llu\n", (unsigned long long)(i + 1), (unsigned long long)hist[i]);
+        if (i + 1 == bins) fprintf(s.out.f, ">=%llu\t%llu\n", (unsigned long long)bins, (unsigned long long)hist[i]);
+        else fprintf(s.out.f, "%llu\t%llu\n", (unsigned long long)(i + 1), (unsigned long long)hist[i]);
     }
-    fprintf(out.f, "# whole\t%llu\n# distinct\t%llu\n# unique\t%llu\n# max_count\t%llu\n", (unsigned long long)st.whole,
-            (unsigned long long)st.distinct, (unsigned long long)st.unique, (unsigned long long)st.max_count);
+    print_stats(s.out.f, {{"whole", st.whole}, {"distinct", st.distinct}, {"unique", st.unique}, {"max_count", st.max_count}});
     auto dump = [&](const std::string& path, const std::vector<uint8_t>& a) {
         if (path.empty()) return true;
         FILE* fh = fopen(path.c_str(), "wb");
-        const bool ok = fh && fwrite(a.data(), 1, n * w, fh) == n * w;
+        const bool ok = fh && fwrite(a.data(), 1, nw, fh) == nw;
         if (fh) fclose(fh);
         if (!ok) fprintf(stderr, "Error: %s: cannot write\n", path.c_str());
         return ok;
@@ -852,226 +989,92 @@ int run_kmers(int argc, char** argv, int first, int threads)
 // sufr repeats: the records to standard output (or -o), the stats as # lines behind them
 int run_repeats(int argc, char** argv, int first, int threads)
 {
-    std::string file, output, kind_name = "branching";
+    AnalysisSession s;
+    std::string kind_name = "branching";
     uint64_t min_len = 0, min_count = 2, max_count = 0, max_positions = 16;
-    int device = -1;
-    auto need = [&](int& i, const char* opt) -> const char* {
-        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
-        return argv[++i];
-    };
-    for (int i = first; i < argc; i++) {
-        const std::string s = argv[i];
-        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
-        else if (s == "-l" || s == "--min-len") min_len = strtoull(need(i, "-l"), nullptr, 10);
-        else if (s == "-c" || s == "--min-count") min_count = strtoull(need(i, "-c"), nullptr, 10);
-        else if (s == "-C" || s == "--max-count") max_count = strtoull(need(i, "-C"), nullptr, 10);
-        else if (s == "--kind") kind_name = need(i, "--kind");
-        else if (s == "--max-positions") max_positions = strtoull(need(i, "--max-positions"), nullptr, 10);
-        else if (s == "--device") device = atoi(need(i, "--device"));
-        else if (s == "-o" || s == "--output") output = need(i, "-o");
-        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-        else if (file.empty()) file = s;
-        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-    }
-    if (file.empty() || !min_len) { fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n", file.empty() ? "<SUFR>" : "-l <MINLEN>"); return 2; }
+    const int parsed = s.parse(argc, argv, first, [&](const std::string& o, int& i, auto& need) {
+        if (o == "-l" || o == "--min-len") min_len = strtoull(need(i, "-l"), nullptr, 10);
+        else if (o == "-c" || o == "--min-count") min_count = strtoull(need(i, "-c"), nullptr, 10);
+        else if (o == "-C" || o == "--max-count") max_count = strtoull(need(i, "-C"), nullptr, 10);
+        else if (o == "--kind") kind_name = need(i, "--kind");
+        else if (o == "--max-positions") max_positions = strtoull(need(i, "--max-positions"), nullptr, 10);
+        else return false;
+        return true;
+    });
+    if (parsed >= 0) return parsed;
+    if (s.file.empty() || !min_len) return s.missing(s.file.empty() ? "<SUFR>" : "-l <MINLEN>");
     uint32_t kind;
-    if (kind_name == "branching") kind = SUFR_REPEAT_BRANCHING;
-    else if (kind_name == "maximal") kind = SUFR_REPEAT_MAXIMAL;
-    else if (kind_name == "super" || kind_name == "supermaximal") kind = SUFR_REPEAT_SUPERMAXIMAL;
-    else { fprintf(stderr, "error: invalid value '%s' for '--kind': branching, maximal or super\n", kind_name.c_str()); return 2; }
-    sufr_file* f = open_or_die(file);
-    sufr_file_meta m;
-    sufr_file_metadata(f, &m);
-    const uint64_t w = (uint64_t)m.index_width, s = m.len_suffixes;
-    std::vector<uint64_t> rank, count, length;
+    if (!repeat_kind(kind_name, kind)) return 2;
+    if (!s.open()) return 1;
+    std::vector<uint64_t> cols[3];                        // rank, count, length
     sufr_repeat_stats st{0, 0, 0, 0};
     uint64_t total = 0;
-    int rc = 0;
-    std::string err;
-    if (device < 0) {
-        rc = sufr_file_repeats(f, kind, min_len, min_count, max_count, 0, nullptr, nullptr, nullptr, &total, &st, threads);
-        if (rc == SUFR_HIP_E_CAPACITY) {
-            rank.resize(total); count.resize(total); length.resize(total);
-            rc = sufr_file_repeats(f, kind, min_len, min_count, max_count, total, rank.data(), count.data(), length.data(), &total, &st, threads);
-        }
-    } else {
-        sufr_hip_ctx* ctx = sufr_hip_create(device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
-        sufr_hip_index* ix = nullptr;
-        std::vector<uint64_t> starts(m.num_sequences);
-        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
-        void *d_lcp = nullptr, *d_out = nullptr;
-        rc = sufr_hip_index_load(ctx, f, &ix);
-        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess ||
-                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
-            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array";
-        }
-        if (!rc) rc = sufr_hip_repeats_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, 0, nullptr,
-                                              nullptr, nullptr, &total, &st);
-        if (rc == SUFR_HIP_E_CAPACITY) {
-            rank.resize(total); count.resize(total); length.resize(total);
-            rc = 0;
-            if (hipMalloc(&d_out, total * 24) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the records"; }
-            uint64_t* o = (uint64_t*)d_out;
-            if (!rc) rc = sufr_hip_repeats_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, total, o,
-                                                  o + total, o + 2 * total, &total, &st);
-            if (!rc) rc = sufr_hip_synchronize(ctx);
-            if (!rc && (hipMemcpy(rank.data(), o, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(count.data(), o + total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(length.data(), o + 2 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess)) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
-        }
-        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
-        if (d_lcp) (void)hipFree(d_lcp);
-        if (d_out) (void)hipFree(d_out);
-        if (ix) sufr_hip_index_free(ix);
-        sufr_hip_destroy(ctx);
-    }
-    if (rc) {
-        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "repeats does not support files built with a seed mask or with a max query length"
-                             : rc == SUFR_HIP_E_INVALID ? "repeats: invalid argument (the minimum length must be at least 1, the sequence starts must ascend from 0)" : "repeats failed";
-        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
-        sufr_file_close(f);
-        return 1;
-    }
-    OutFile out;
-    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); sufr_file_close(f); return 1; }
-    std::vector<uint64_t> pos;
-    for (uint64_t i = 0; i < total; i++) {
-        pos.resize(count[i]);
-        for (uint64_t j = 0; j < count[i]; j++) pos[j] = sufr_file_suffix(f, rank[i] + j);
-        std::sort(pos.begin(), pos.end());
-        fprintf(out.f, "%llu\t%llu\t", (unsigned long long)length[i], (unsigned long long)count[i]);
-        const uint64_t show = max_positions && max_positions < count[i] ? max_positions : count[i];
-        for (uint64_t j = 0; j < show; j++) fprintf(out.f, "%s%s", j ? " " : "", place(f, false, pos[j]).c_str());
-        fputc('\n', out.f);
-    }
-    fprintf(out.f, "# records\t%llu\n# longest\t%llu\n# longest_rank\t%llu\n# max_count\t%llu\n", (unsigned long long)st.records,
-            (unsigned long long)st.longest, (unsigned long long)st.longest_rank, (unsigned long long)st.max_count);
-    sufr_file_close(f);
+    s.counted(3, cols, total,
+              [&](uint64_t cap, uint64_t** c, uint64_t* tot) { return sufr_file_repeats(s.f, kind, min_len, min_count, max_count, cap, c[0], c[1], c[2], tot, &st, threads); },
+              [&](uint64_t cap, uint64_t** c, uint64_t* tot) {
+                  return sufr_hip_repeats_device(s.dev->ctx, s.dev->ix, s.d_lcp, s.starts.data(), s.starts.size(), kind, min_len, min_count, max_count,
+                                                 cap, c[0], c[1], c[2], tot, &st);
+              });
+    if (!s.computed("repeats does not support files built with a seed mask or with a max query length",
+                    "repeats: invalid argument (the minimum length must be at least 1, the sequence starts must ascend from 0)", "repeats failed")) return 1;
+    for (uint64_t i = 0; i < total; i++) print_repeat(s.out.f, s.f, cols[0][i], cols[1][i], cols[2][i], nullptr, max_positions);
+    print_stats(s.out.f, {{"records", st.records}, {"longest", st.longest}, {"longest_rank", st.longest_rank}, {"max_count", st.max_count}});
     return 0;
 }
 
 // sufr shared: the records of sufr repeats with the seqs column, or (--common) the k-common profile
 int run_shared(int argc, char** argv, int first, int threads)
 {
-    std::string file, output, kind_name = "branching";
+    AnalysisSession s;
+    std::string kind_name = "branching";
     uint64_t min_len = 0, min_count = 2, max_count = 0, min_seqs = 0, max_seqs = 0, max_positions = 16;
     bool profile = false;
-    int device = -1;
-    auto need = [&](int& i, const char* opt) -> const char* {
-        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
-        return argv[++i];
-    };
-    for (int i = first; i < argc; i++) {
-        const std::string s = argv[i];
-        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
-        else if (s == "-l" || s == "--min-len") min_len = strtoull(need(i, "-l"), nullptr, 10);
-        else if (s == "-c" || s == "--min-count") min_count = strtoull(need(i, "-c"), nullptr, 10);
-        else if (s == "-C" || s == "--max-count") max_count = strtoull(need(i, "-C"), nullptr, 10);
-        else if (s == "-q" || s == "--min-seqs") min_seqs = strtoull(need(i, "-q"), nullptr, 10);
-        else if (s == "--max-seqs") max_seqs = strtoull(need(i, "--max-seqs"), nullptr, 10);
-        else if (s == "--kind") kind_name = need(i, "--kind");
-        else if (s == "--common") profile = true;
-        else if (s == "--max-positions") max_positions = strtoull(need(i, "--max-positions"), nullptr, 10);
-        else if (s == "--device") device = atoi(need(i, "--device"));
-        else if (s == "-o" || s == "--output") output = need(i, "-o");
-        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-        else if (file.empty()) file = s;
-        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-    }
-    if (file.empty() || (!min_len && !profile)) { fprintf(stderr, "error: the following required arguments were not provided:\n  %s\n", file.empty() ? "<SUFR>" : "-l <MINLEN>"); return 2; }
+    const int parsed = s.parse(argc, argv, first, [&](const std::string& o, int& i, auto& need) {
+        if (o == "-l" || o == "--min-len") min_len = strtoull(need(i, "-l"), nullptr, 10);
+        else if (o == "-c" || o == "--min-count") min_count = strtoull(need(i, "-c"), nullptr, 10);
+        else if (o == "-C" || o == "--max-count") max_count = strtoull(need(i, "-C"), nullptr, 10);
+        else if (o == "-q" || o == "--min-seqs") min_seqs = strtoull(need(i, "-q"), nullptr, 10);
+        else if (o == "--max-seqs") max_seqs = strtoull(need(i, "--max-seqs"), nullptr, 10);
+        else if (o == "--kind") kind_name = need(i, "--kind");
+        else if (o == "--common") profile = true;
+        else if (o == "--max-positions") max_positions = strtoull(need(i, "--max-positions"), nullptr, 10);
+        else return false;
+        return true;
+    });
+    if (parsed >= 0) return parsed;
+    if (s.file.empty() || (!min_len && !profile)) return s.missing(s.file.empty() ? "<SUFR>" : "-l <MINLEN>");
     if (max_seqs && min_seqs > max_seqs) { fprintf(stderr, "error: invalid value '%llu' for '--min-seqs': larger than --max-seqs\n", (unsigned long long)min_seqs); return 2; }
     uint32_t kind;
-    if (kind_name == "branching") kind = SUFR_REPEAT_BRANCHING;
-    else if (kind_name == "maximal") kind = SUFR_REPEAT_MAXIMAL;
-    else if (kind_name == "super" || kind_name == "supermaximal") kind = SUFR_REPEAT_SUPERMAXIMAL;
-    else { fprintf(stderr, "error: invalid value '%s' for '--kind': branching, maximal or super\n", kind_name.c_str()); return 2; }
-    sufr_file* f = open_or_die(file);
-    sufr_file_meta m;
-    sufr_file_metadata(f, &m);
-    const uint64_t w = (uint64_t)m.index_width, s = m.len_suffixes, num = m.num_sequences ? m.num_sequences : 1;
-    std::vector<uint64_t> rank, count, length, seqs, common(profile ? num : 0);
+    if (!repeat_kind(kind_name, kind)) return 2;
+    if (!s.open()) return 1;
+    const uint64_t num = s.m.num_sequences ? s.m.num_sequences : 1;
+    std::vector<uint64_t> cols[4], common(profile ? num : 0);      // rank, count, length, seqs
     sufr_shared_stats st{0, 0, 0, 0, 0};
     uint64_t total = 0;
-    int rc = 0;
-    std::string err;
-    if (device < 0) {
-        if (profile) rc = sufr_file_common(f, common.data(), threads);
-        else {
-            rc = sufr_file_shared(f, kind, min_len, min_count, max_count, min_seqs, max_seqs, 0, nullptr, nullptr, nullptr, nullptr, &total, &st, threads);
-            if (rc == SUFR_HIP_E_CAPACITY) {
-                rank.resize(total); count.resize(total); length.resize(total); seqs.resize(total);
-                rc = sufr_file_shared(f, kind, min_len, min_count, max_count, min_seqs, max_seqs, total, rank.data(), count.data(), length.data(),
-                                      seqs.data(), &total, &st, threads);
-            }
-        }
-    } else {
-        sufr_hip_ctx* ctx = sufr_hip_create(device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
-        sufr_hip_index* ix = nullptr;
-        std::vector<uint64_t> starts(m.num_sequences);
-        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
-        void *d_lcp = nullptr, *d_out = nullptr;
-        rc = sufr_hip_index_load(ctx, f, &ix);
-        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess ||
-                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
-            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array";
-        }
-        if (!rc && profile) {
-            if (hipMalloc(&d_out, num * 8) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the profile"; }
-            if (!rc) rc = sufr_hip_common_device(ctx, ix, d_lcp, starts.data(), starts.size(), d_out);
-            if (!rc) rc = sufr_hip_synchronize(ctx);
-            if (!rc && hipMemcpy(common.data(), d_out, num * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
-        } else if (!rc) {
-            rc = sufr_hip_shared_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, min_seqs, max_seqs, 0,
-                                        nullptr, nullptr, nullptr, nullptr, &total, &st);
-            if (rc == SUFR_HIP_E_CAPACITY) {
-                rank.resize(total); count.resize(total); length.resize(total); seqs.resize(total);
-                rc = 0;
-                if (hipMalloc(&d_out, total * 32) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the records"; }
-                uint64_t* o = (uint64_t*)d_out;
-                if (!rc) rc = sufr_hip_shared_device(ctx, ix, d_lcp, starts.data(), starts.size(), kind, min_len, min_count, max_count, min_seqs,
-                                                     max_seqs, total, o, o + total, o + 2 * total, o + 3 * total, &total, &st);
-                if (!rc) rc = sufr_hip_synchronize(ctx);
-                if (!rc && (hipMemcpy(rank.data(), o, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                            hipMemcpy(count.data(), o + total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                            hipMemcpy(length.data(), o + 2 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                            hipMemcpy(seqs.data(), o + 3 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess)) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
-            }
-        }
-        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
-        if (d_lcp) (void)hipFree(d_lcp);
-        if (d_out) (void)hipFree(d_out);
-        if (ix) sufr_hip_index_free(ix);
-        sufr_hip_destroy(ctx);
+    if (!profile)
+        s.counted(4, cols, total,
+                  [&](uint64_t cap, uint64_t** c, uint64_t* tot) {
+                      return sufr_file_shared(s.f, kind, min_len, min_count, max_count, min_seqs, max_seqs, cap, c[0], c[1], c[2], c[3], tot, &st, threads);
+                  },
+                  [&](uint64_t cap, uint64_t** c, uint64_t* tot) {
+                      return sufr_hip_shared_device(s.dev->ctx, s.dev->ix, s.d_lcp, s.starts.data(), s.starts.size(), kind, min_len, min_count, max_count,
+                                                    min_seqs, max_seqs, cap, c[0], c[1], c[2], c[3], tot, &st);
+                  });
+    else if (!s.dev) s.rc = sufr_file_common(s.f, common.data(), threads);
+    else {
+        void* d_out = s.alloc(num * 8, "the profile");
+        s.on_device([&]() { return sufr_hip_common_device(s.dev->ctx, s.dev->ix, s.d_lcp, s.starts.data(), s.starts.size(), d_out); },
+                    {{common.data(), d_out, num * 8}});
     }
-    if (rc) {
-        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "shared does not support files built with a seed mask or with a max query length"
-                             : rc == SUFR_HIP_E_INVALID ? "shared: invalid argument (the minimum length must be at least 1, the sequence starts must ascend from 0)" : "shared failed";
-        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
-        sufr_file_close(f);
-        return 1;
-    }
-    OutFile out;
-    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); sufr_file_close(f); return 1; }
+    if (!s.computed("shared does not support files built with a seed mask or with a max query length",
+                    "shared: invalid argument (the minimum length must be at least 1, the sequence starts must ascend from 0)", "shared failed")) return 1;
     if (profile) {
-        for (uint64_t q = 0; q < num; q++) fprintf(out.f, "%llu\t%llu\n", (unsigned long long)(q + 1), (unsigned long long)common[q]);
-        sufr_file_close(f);
+        for (uint64_t q = 0; q < num; q++) fprintf(s.out.f, "%llu\t%llu\n", (unsigned long long)(q + 1), (unsigned long long)common[q]);
         return 0;
     }
-    std::vector<uint64_t> pos;
-    for (uint64_t i = 0; i < total; i++) {
-        pos.resize(count[i]);
-        for (uint64_t j = 0; j < count[i]; j++) pos[j] = sufr_file_suffix(f, rank[i] + j);
-        std::sort(pos.begin(), pos.end());
-        fprintf(out.f, "%llu\t%llu\t%llu\t", (unsigned long long)length[i], (unsigned long long)count[i], (unsigned long long)seqs[i]);
-        const uint64_t show = max_positions && max_positions < count[i] ? max_positions : count[i];
-        for (uint64_t j = 0; j < show; j++) fprintf(out.f, "%s%s", j ? " " : "", place(f, false, pos[j]).c_str());
-        fputc('\n', out.f);
-    }
-    fprintf(out.f, "# records\t%llu\n# longest\t%llu\n# longest_rank\t%llu\n# max_count\t%llu\n# max_seqs\t%llu\n", (unsigned long long)st.records,
-            (unsigned long long)st.longest, (unsigned long long)st.longest_rank, (unsigned long long)st.max_count, (unsigned long long)st.max_seqs);
-    sufr_file_close(f);
+    for (uint64_t i = 0; i < total; i++) print_repeat(s.out.f, s.f, cols[0][i], cols[1][i], cols[2][i], &cols[3][i], max_positions);
+    print_stats(s.out.f, {{"records", st.records}, {"longest", st.longest}, {"longest_rank", st.longest_rank}, {"max_count", st.max_count},
+                          {"max_seqs", st.max_seqs}});
     return 0;
 }
 
@@ -1079,106 +1082,50 @@ int run_shared(int argc, char** argv, int first, int threads)
 // per-position table
 int run_lz(int argc, char** argv, int first, int threads)
 {
-    std::string file, output;
+    AnalysisSession s;
     bool table = false;
-    int device = -1;
-    auto need = [&](int& i, const char* opt) -> const char* {
-        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
-        return argv[++i];
-    };
-    for (int i = first; i < argc; i++) {
-        const std::string s = argv[i];
-        if (s == "-h" || s == "--help") { usage(stdout); return 0; }
-        else if (s == "--lpf") table = true;
-        else if (s == "-t" || s == "--threads") threads = atoi(need(i, "-t"));
-        else if (s == "--device") device = atoi(need(i, "--device"));
-        else if (s == "-o" || s == "--output") output = need(i, "-o");
-        else if (s.size() > 1 && s[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-        else if (file.empty()) file = s;
-        else { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
-    }
-    if (file.empty()) { fprintf(stderr, "error: the following required arguments were not provided:\n  <SUFR>\n"); return 2; }
-    sufr_file* f = open_or_die(file);
-    sufr_file_meta m;
-    sufr_file_metadata(f, &m);
-    const uint64_t w = (uint64_t)m.index_width, s = m.len_suffixes, n = m.text_len;
-    std::vector<uint64_t> start, length, source;          // the factors, or (--lpf) length and source by position
+    const int parsed = s.parse(argc, argv, first, [&](const std::string& o, int& i, auto& need) {
+        if (o == "--lpf") table = true;
+        else if (o == "-t" || o == "--threads") threads = atoi(need(i, "-t"));
+        else return false;
+        return true;
+    });
+    if (parsed >= 0) return parsed;
+    if (s.file.empty()) return s.missing("<SUFR>");
+    if (!s.open()) return 1;
+    const uint64_t w = (uint64_t)s.m.index_width, n = s.m.text_len;
+    std::vector<uint64_t> cols[3];                        // the factors: start, length, source
+    std::vector<uint8_t> raw(table ? 2 * n * w + 8 : 0);  // --lpf: LPF, then SRC, by position in the index width
     sufr_lz_stats st{0, 0, 0, 0};
     uint64_t total = 0;
-    int rc = 0;
-    std::string err;
-    std::vector<uint8_t> raw(table ? 2 * n * w + 8 : 0);  // --lpf: LPF, then SRC, in the index width
-    if (device < 0) {
-        if (table) rc = sufr_file_lpf(f, raw.data(), raw.data() + n * w, threads);
-        else {
-            rc = sufr_file_lz(f, 0, nullptr, nullptr, nullptr, &total, &st, threads);
-            if (rc == SUFR_HIP_E_CAPACITY) {
-                start.resize(total); length.resize(total); source.resize(total);
-                rc = sufr_file_lz(f, total, start.data(), length.data(), source.data(), &total, &st, threads);
-            }
-        }
-    } else {
-        sufr_hip_ctx* ctx = sufr_hip_create(device);
-        if (!ctx) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); sufr_file_close(f); return 1; }
-        sufr_hip_index* ix = nullptr;
-        std::vector<uint64_t> starts(m.num_sequences);
-        for (uint64_t i = 0; i < m.num_sequences; i++) starts[i] = sufr_file_sequence_start(f, i);
-        void *d_lcp = nullptr, *d_out = nullptr;
-        rc = sufr_hip_index_load(ctx, f, &ix);
-        if (!rc && (hipSetDevice(device) != hipSuccess || hipMalloc(&d_lcp, s * w + 8) != hipSuccess ||
-                    (s && hipMemcpy(d_lcp, sufr_file_lcp_array(f), s * w, hipMemcpyHostToDevice) != hipSuccess))) {
-            rc = SUFR_HIP_E_HIP; err = "device memory for the LCP array";
-        }
-        if (!rc && table) {
-            if (hipMalloc(&d_out, 2 * n * w + 8) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the table"; }
-            if (!rc) rc = sufr_hip_lpf_device(ctx, ix, d_lcp, starts.data(), starts.size(), d_out, (uint8_t*)d_out + n * w);
-            if (!rc) rc = sufr_hip_synchronize(ctx);
-            if (!rc && hipMemcpy(raw.data(), d_out, 2 * n * w, hipMemcpyDeviceToHost) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
-        } else if (!rc) {
-            rc = sufr_hip_lz_device(ctx, ix, d_lcp, starts.data(), starts.size(), 0, nullptr, nullptr, nullptr, &total, &st);
-            if (rc == SUFR_HIP_E_CAPACITY) {
-                start.resize(total); length.resize(total); source.resize(total);
-                rc = 0;
-                if (hipMalloc(&d_out, total * 24) != hipSuccess) { rc = SUFR_HIP_E_HIP; err = "device memory for the records"; }
-                uint64_t* o = (uint64_t*)d_out;
-                if (!rc) rc = sufr_hip_lz_device(ctx, ix, d_lcp, starts.data(), starts.size(), total, o, o + total, o + 2 * total, &total, &st);
-                if (!rc) rc = sufr_hip_synchronize(ctx);
-                if (!rc && (hipMemcpy(start.data(), o, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                            hipMemcpy(length.data(), o + total, total * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                            hipMemcpy(source.data(), o + 2 * total, total * 8, hipMemcpyDeviceToHost) != hipSuccess)) { rc = SUFR_HIP_E_HIP; err = "copying the results"; }
-            }
-        }
-        if (rc && err.empty()) err = sufr_hip_last_error(ctx);
-        if (d_lcp) (void)hipFree(d_lcp);
-        if (d_out) (void)hipFree(d_out);
-        if (ix) sufr_hip_index_free(ix);
-        sufr_hip_destroy(ctx);
+    if (!table)
+        s.counted(3, cols, total,
+                  [&](uint64_t cap, uint64_t** c, uint64_t* tot) { return sufr_file_lz(s.f, cap, c[0], c[1], c[2], tot, &st, threads); },
+                  [&](uint64_t cap, uint64_t** c, uint64_t* tot) {
+                      return sufr_hip_lz_device(s.dev->ctx, s.dev->ix, s.d_lcp, s.starts.data(), s.starts.size(), cap, c[0], c[1], c[2], tot, &st);
+                  });
+    else if (!s.dev) s.rc = sufr_file_lpf(s.f, raw.data(), raw.data() + n * w, threads);
+    else {
+        uint8_t* d_out = (uint8_t*)s.alloc(2 * n * w + 8, "the table");
+        s.on_device([&]() { return sufr_hip_lpf_device(s.dev->ctx, s.dev->ix, s.d_lcp, s.starts.data(), s.starts.size(), d_out, d_out + n * w); },
+                    {{raw.data(), d_out, 2 * n * w}});
     }
-    if (rc) {
-        if (err.empty()) err = rc == SUFR_HIP_E_UNSUPPORTED ? "lz does not support files built with a seed mask or with a max query length"
-                             : rc == SUFR_HIP_E_INVALID ? "lz: invalid argument (the sequence starts must ascend from 0)" : "lz failed";
-        fprintf(stderr, "Error: %s: %s\n", file.c_str(), err.c_str());
-        sufr_file_close(f);
-        return 1;
-    }
-    OutFile out;
-    if (!out.open(output)) { fprintf(stderr, "Error: %s: cannot create\n", output.c_str()); sufr_file_close(f); return 1; }
+    if (!s.computed("lz does not support files built with a seed mask or with a max query length",
+                    "lz: invalid argument (the sequence starts must ascend from 0)", "lz failed")) return 1;
     if (table) {
         const uint64_t none = w == 4 ? 0xFFFFFFFFull : ~0ull;
         for (uint64_t p = 0; p < n; p++) {
             uint64_t l = 0, q = 0;
             memcpy(&l, raw.data() + p * w, w);
             memcpy(&q, raw.data() + (n + p) * w, w);
-            fprintf(out.f, "%s\t%llu\t%s\n", place(f, false, p).c_str(), (unsigned long long)l, q == none ? "*" : place(f, false, q).c_str());
+            fprintf(s.out.f, "%s\t%llu\t%s\n", place(s.f, false, p).c_str(), (unsigned long long)l, q == none ? "*" : place(s.f, false, q).c_str());
         }
-    } else {
-        for (uint64_t i = 0; i < total; i++)
-            fprintf(out.f, "%s\t%llu\t%s\n", place(f, false, start[i]).c_str(), (unsigned long long)length[i],
-                    source[i] == ~0ull ? "*" : place(f, false, source[i]).c_str());
-        fprintf(out.f, "# factors\t%llu\n# literals\t%llu\n# longest\t%llu\n# longest_start\t%llu\n", (unsigned long long)st.factors,
-                (unsigned long long)st.literals, (unsigned long long)st.longest, (unsigned long long)st.longest_start);
+        return 0;
     }
-    sufr_file_close(f);
+    for (uint64_t i = 0; i < total; i++)
+        fprintf(s.out.f, "%s\t%llu\t%s\n", place(s.f, false, cols[0][i]).c_str(), (unsigned long long)cols[1][i],
+                cols[2][i] == ~0ull ? "*" : place(s.f, false, cols[2][i]).c_str());
+    print_stats(s.out.f, {{"factors", st.factors}, {"literals", st.literals}, {"longest", st.longest}, {"longest_start", st.longest_start}});
     return 0;
 }
 
@@ -1200,10 +1147,7 @@ int main(int argc, char** argv)
     a.num_partitions = 16;
     a.random_seed = 42;
 
-    auto need = [&](int& i, const char* opt) -> const char* {
-        if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", opt); exit(2); }
-        return argv[++i];
-    };
+    auto need = value_reader(argc, argv);
     for (int i = 1; i < argc; i++) {
         std::string s = argv[i];
         if (s == "-h" || s == "--help") return usage(stdout);

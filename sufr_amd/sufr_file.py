@@ -14,6 +14,7 @@ import builtins
 import ctypes as C
 import datetime
 from dataclasses import dataclass, field
+from functools import partial
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -219,32 +220,47 @@ def _file_error(fn: str, noun: str):
     return error
 
 
-def _kmer_error(fn: str, rc: int) -> SufrHipError:
-    msg = {-6: "files built with a seed mask are not supported, and a build with max_query_len has its LCP capped there",
-           -1: "invalid argument (k and bins must be at least 1, the sequence starts must ascend from 0)"}.get(rc, "failed")
-    return SufrHipError(rc, f"{fn}: " + msg)
+_CAPPED = "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported"
+_LCP_ERRORS = {            # the analyses of the LCP array, by family: the text of every code the library gives a reason for
+    "kmer": {-6: "files built with a seed mask are not supported, and a build with max_query_len has its LCP capped there",
+             -1: "invalid argument (k and bins must be at least 1, the sequence starts must ascend from 0)"},
+    "repeat": {-6: _CAPPED, -5: "more records than the arrays hold",
+               -1: "invalid argument (min_len must be at least 1, the kind 0, 1 or 2, the sequence starts must ascend from 0)"},
+    "shared": {-6: _CAPPED, -5: "more records than the arrays hold",
+               -1: "invalid argument (min_len must be at least 1, the kind 0, 1 or 2, min_seqs at most max_seqs, the sequence starts "
+                   "must ascend from 0)"},
+    "lz": {-6: _CAPPED, -5: "more factors than the arrays hold", -1: "invalid argument (the sequence starts must ascend from 0)"},
+}
 
 
-def _repeat_error(fn: str, rc: int) -> SufrHipError:
-    msg = {-6: "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported",
-           -5: "more records than the arrays hold",
-           -1: "invalid argument (min_len must be at least 1, the kind 0, 1 or 2, the sequence starts must ascend from 0)"}.get(rc, "failed")
-    return SufrHipError(rc, f"{fn}: " + msg)
+def _lcp_check(family: str, fn: str, rc: int):
+    """Raises the SufrHipError of the host call `fn` of a family of _LCP_ERRORS unless rc is 0."""
+    if rc != 0:
+        raise SufrHipError(rc, f"{fn}: " + _LCP_ERRORS[family].get(rc, "failed"))
 
 
-def _shared_error(fn: str, rc: int) -> SufrHipError:
-    msg = {-6: "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported",
-           -5: "more records than the arrays hold",
-           -1: "invalid argument (min_len must be at least 1, the kind 0, 1 or 2, min_seqs at most max_seqs, the sequence starts "
-               "must ascend from 0)"}.get(rc, "failed")
-    return SufrHipError(rc, f"{fn}: " + msg)
+def _address(a):
+    """Of a numpy array or a torch tensor, as the library takes it."""
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
 
 
-def _lz_error(fn: str, rc: int) -> SufrHipError:
-    msg = {-6: "files built with a seed mask or with a max_query_len (their LCP is capped) are not supported",
-           -5: "more factors than the arrays hold",
-           -1: "invalid argument (the sequence starts must ascend from 0)"}.get(rc, "failed")
-    return SufrHipError(rc, f"{fn}: " + msg)
+def _counted(ncols: int, call, alloc, check, filled=lambda: None):
+    """The `ncols` record columns of a call that counts, then fills, cut to the total.  call(cap, addresses, total) returns the
+    library's code: made once with cap 0 and no columns (-5 there says only that there are records) and, unless the total is
+    0, once more with the columns alloc(total) made.  check(rc) raises on a failure; filled() runs after a good fill."""
+    total = C.c_uint64(0)
+    rc = call(0, (None,) * ncols, total)
+    if rc != -5:
+        check(rc)
+    out = alloc(max(total.value, 1))
+    if total.value:
+        check(call(total.value, [_address(a) for a in out], total))
+        filled()
+    return tuple(a[:total.value] for a in out)
+
+
+def _host_columns(ncols: int):
+    return lambda n: [np.zeros(n, dtype=np.uint64) for _ in range(ncols)]
 
 
 def _as_bytes(q) -> bytes:
@@ -542,8 +558,7 @@ class SufrFile:
         out = None if occ is None else np.zeros(max(self.text_len if occ == "position" else self.len_suffixes, 1), dtype=self._index_dtype())
         rc = lib().sufr_file_kmers(self._h, k, KMER_BY_POSITION if occ == "position" else 0, bins, hist.ctypes.data,
                                    out.ctypes.data if out is not None else None, C.byref(st), threads)
-        if rc != 0:
-            raise _kmer_error("sufr_file_kmers", rc)
+        _lcp_check("kmer", "sufr_file_kmers", rc)
         if out is not None:
             out = out[:self.text_len if occ == "position" else self.len_suffixes]
         return hist[:bins], st.as_dict(), out
@@ -555,8 +570,7 @@ class SufrFile:
         count = self.text_len if by_position else self.len_suffixes
         out = np.zeros(max(count, 1), dtype=self._index_dtype())
         rc = lib().sufr_file_unique_lengths(self._h, KMER_BY_POSITION if by_position else 0, out.ctypes.data, threads)
-        if rc != 0:
-            raise _kmer_error("sufr_file_unique_lengths", rc)
+        _lcp_check("kmer", "sufr_file_unique_lengths", rc)
         return out[:count]
 
     # -- repeats of the indexed text (include/sufr_repeat.h) ------------------------------------------------------------
@@ -567,17 +581,11 @@ class SufrFile:
         "super" (2).  One call counts, one fills."""
         from ._lib import REPEAT_KINDS, RepeatStats
         kind = REPEAT_KINDS.get(kind, kind)
-        total, st = C.c_uint64(0), RepeatStats()
-        rc = lib().sufr_file_repeats(self._h, kind, min_len, min_count, max_count, 0, None, None, None, C.byref(total), C.byref(st), threads)
-        if rc not in (0, -5):
-            raise _repeat_error("sufr_file_repeats", rc)
-        out = [np.zeros(max(total.value, 1), dtype=np.uint64) for _ in range(3)]
-        if total.value:
-            rc = lib().sufr_file_repeats(self._h, kind, min_len, min_count, max_count, total.value, out[0].ctypes.data, out[1].ctypes.data,
-                                         out[2].ctypes.data, C.byref(total), C.byref(st), threads)
-            if rc != 0:
-                raise _repeat_error("sufr_file_repeats", rc)
-        return out[0][:total.value], out[1][:total.value], out[2][:total.value], st.as_dict()
+        st = RepeatStats()
+        cols = _counted(3, lambda cap, at, total: lib().sufr_file_repeats(self._h, kind, min_len, min_count, max_count, cap, *at,
+                                                                          C.byref(total), C.byref(st), threads),
+                        _host_columns(3), partial(_lcp_check, "repeat", "sufr_file_repeats"))
+        return (*cols, st.as_dict())
 
     # -- longest previous factors and the LZ77 parse (include/sufr_lz.h) ------------------------------------------------
     def lpf(self, threads: int = 0):
@@ -586,8 +594,7 @@ class SufrFile:
         n = self.text_len
         out = [np.zeros(max(n, 1), dtype=self._index_dtype()) for _ in range(2)]
         rc = lib().sufr_file_lpf(self._h, out[0].ctypes.data, out[1].ctypes.data, threads)
-        if rc != 0:
-            raise _lz_error("sufr_file_lpf", rc)
+        _lcp_check("lz", "sufr_file_lpf", rc)
         return out[0][:n], out[1][:n]
 
     def lz(self, threads: int = 0):
@@ -595,17 +602,10 @@ class SufrFile:
         (source all ones: a literal of length 1) and a dict of factors / literals / longest / longest_start.  One call
         counts, one fills."""
         from ._lib import LzStats
-        total, st = C.c_uint64(0), LzStats()
-        rc = lib().sufr_file_lz(self._h, 0, None, None, None, C.byref(total), C.byref(st), threads)
-        if rc not in (0, -5):
-            raise _lz_error("sufr_file_lz", rc)
-        out = [np.zeros(max(total.value, 1), dtype=np.uint64) for _ in range(3)]
-        if total.value:
-            rc = lib().sufr_file_lz(self._h, total.value, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, C.byref(total),
-                                    C.byref(st), threads)
-            if rc != 0:
-                raise _lz_error("sufr_file_lz", rc)
-        return out[0][:total.value], out[1][:total.value], out[2][:total.value], st.as_dict()
+        st = LzStats()
+        cols = _counted(3, lambda cap, at, total: lib().sufr_file_lz(self._h, cap, *at, C.byref(total), C.byref(st), threads),
+                        _host_columns(3), partial(_lcp_check, "lz", "sufr_file_lz"))
+        return (*cols, st.as_dict())
 
     # -- sequence counts of repeats and k-common substrings (include/sufr_shared.h) --------------------------------------
     def shared(self, kind="branching", min_len: int = 1, min_count: int = 2, max_count: int = 0, min_seqs: int = 0, max_seqs: int = 0,
@@ -616,25 +616,18 @@ class SufrFile:
         sequences; max_seqs = 1 keeps the repeats private to one sequence.  One call counts, one fills."""
         from ._lib import REPEAT_KINDS, SharedStats
         kind = REPEAT_KINDS.get(kind, kind)
-        total, st = C.c_uint64(0), SharedStats()
-        args = (self._h, kind, min_len, min_count, max_count, min_seqs, max_seqs)
-        rc = lib().sufr_file_shared(*args, 0, None, None, None, None, C.byref(total), C.byref(st), threads)
-        if rc not in (0, -5):
-            raise _shared_error("sufr_file_shared", rc)
-        out = [np.zeros(max(total.value, 1), dtype=np.uint64) for _ in range(4)]
-        if total.value:
-            rc = lib().sufr_file_shared(*args, total.value, *(o.ctypes.data for o in out), C.byref(total), C.byref(st), threads)
-            if rc != 0:
-                raise _shared_error("sufr_file_shared", rc)
-        return (*(o[:total.value] for o in out), st.as_dict())
+        st = SharedStats()
+        cols = _counted(4, lambda cap, at, total: lib().sufr_file_shared(self._h, kind, min_len, min_count, max_count, min_seqs, max_seqs,
+                                                                         cap, *at, C.byref(total), C.byref(st), threads),
+                        _host_columns(4), partial(_lcp_check, "shared", "sufr_file_shared"))
+        return (*cols, st.as_dict())
 
     def common(self, threads: int = 0):
         """common[q - 1], q = 1 .. num_sequences: the length of the longest break-free string with indexed occurrences in at
         least q of the sequences (0: none); a uint64 array, non-increasing."""
         out = np.zeros(max(self.num_sequences, 1), dtype=np.uint64)
         rc = lib().sufr_file_common(self._h, out.ctypes.data, threads)
-        if rc != 0:
-            raise _shared_error("sufr_file_common", rc)
+        _lcp_check("shared", "sufr_file_common", rc)
         return out
 
     def _sequence_of(self, suffix: int) -> int:
@@ -913,7 +906,10 @@ class DeviceIndex:
         return out
 
     # -- k-mer spectra, occurrence maps, unique lengths (include/sufr_kmer.h) ------------------------------------------
-    def _kmer_inputs(self, lcp, seq_starts):
+    def _lcp_inputs(self, lcp, seq_starts):
+        """What every *_device analysis takes: the LCP tensor checked (on the GPU, of the index's width, its producer
+        finished) and the sequence starts as the library reads them.  Returns (dtype of the width, starts, their address, their
+        count)."""
         import torch
         wide = self.index_width == 8
         if not lcp.is_cuda or lcp.dtype not in ((torch.int64, torch.uint64) if wide else (torch.int32, torch.uint32)):
@@ -921,6 +917,13 @@ class DeviceIndex:
         torch.cuda.current_stream(lcp.device).synchronize()
         st = None if seq_starts is None else np.ascontiguousarray(seq_starts, dtype=np.uint64)
         return torch.int64 if wide else torch.int32, st, (st.ctypes.data if st is not None and st.size else None), (st.size if st is not None else 0)
+
+    def _counted_device(self, lcp, ncols, call):
+        """_counted for int64 columns on the LCP tensor's device; the error text is the context's, the records are complete on
+        return."""
+        import torch
+        return _counted(ncols, call, lambda n: [torch.empty(n, dtype=torch.int64, device=lcp.device) for _ in range(ncols)],
+                        self.ctx.check, self.ctx.synchronize)
 
     def kmers_device(self, lcp, k: int, bins: int = 256, occ: Optional[str] = None, seq_starts=None):
         """SufrFile.kmers on the device.  lcp: the LCP array as a torch CUDA tensor of the index's width (s entries);
@@ -930,7 +933,7 @@ class DeviceIndex:
         from ._lib import KMER_BY_POSITION, KmerStats
         if occ not in (None, "rank", "position"):
             raise ValueError('occ is None, "rank" or "position"')
-        dt, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        dt, st, st_ptr, st_n = self._lcp_inputs(lcp, seq_starts)
         hist = torch.empty(max(bins, 1), dtype=torch.int64, device=lcp.device)
         count = None if occ is None else (lcp.numel() if occ == "rank" else self.text_len)
         out = None if occ is None else torch.empty(max(count, 1), dtype=dt, device=lcp.device)
@@ -945,7 +948,7 @@ class DeviceIndex:
         """SufrFile.unique_lengths on the device: a tensor of the index's width, complete on return."""
         import torch
         from ._lib import KMER_BY_POSITION
-        dt, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        dt, st, st_ptr, st_n = self._lcp_inputs(lcp, seq_starts)
         count = lcp.numel() if not by_position else self.text_len
         out = torch.empty(max(count, 1), dtype=dt, device=lcp.device)
         self.ctx.check(lib().sufr_hip_unique_lengths_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n,
@@ -957,29 +960,20 @@ class DeviceIndex:
     def repeats_device(self, lcp, kind="branching", min_len: int = 1, min_count: int = 2, max_count: int = 0, seq_starts=None):
         """SufrFile.repeats on the device.  lcp and seq_starts as in kmers_device.  Returns (rank, count, length) as int64
         CUDA tensors and the stats dict, complete on return.  One call counts, one fills."""
-        import torch
         from ._lib import REPEAT_KINDS, RepeatStats
         kind = REPEAT_KINDS.get(kind, kind)
-        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
-        total, stats = C.c_uint64(0), RepeatStats()
-        rc = lib().sufr_hip_repeats_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count, max_count, 0,
-                                           None, None, None, C.byref(total), C.byref(stats))
-        if rc != -5:
-            self.ctx.check(rc)
-        out = [torch.empty(max(total.value, 1), dtype=torch.int64, device=lcp.device) for _ in range(3)]
-        if total.value:
-            self.ctx.check(lib().sufr_hip_repeats_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count,
-                                                         max_count, total.value, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                                         C.byref(total), C.byref(stats)))
-            self.ctx.synchronize()
-        return out[0][:total.value], out[1][:total.value], out[2][:total.value], stats.as_dict()
+        _, st, st_ptr, st_n = self._lcp_inputs(lcp, seq_starts)
+        stats = RepeatStats()
+        cols = self._counted_device(lcp, 3, lambda cap, at, total: lib().sufr_hip_repeats_device(
+            self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count, max_count, cap, *at, C.byref(total), C.byref(stats)))
+        return (*cols, stats.as_dict())
 
     # -- longest previous factors and the LZ77 parse (include/sufr_lz.h) -----------------------------------------------
     def lpf_device(self, lcp, seq_starts=None):
         """SufrFile.lpf on the device.  lcp and seq_starts as in kmers_device.  Returns (lpf, src) as CUDA tensors of the
         index's width, complete on return."""
         import torch
-        dt, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        dt, st, st_ptr, st_n = self._lcp_inputs(lcp, seq_starts)
         n = self.text_len
         out = [torch.empty(max(n, 1), dtype=dt, device=lcp.device) for _ in range(2)]
         self.ctx.check(lib().sufr_hip_lpf_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, out[0].data_ptr(), out[1].data_ptr()))
@@ -989,44 +983,31 @@ class DeviceIndex:
     def lz_device(self, lcp, seq_starts=None):
         """SufrFile.lz on the device.  Returns (start, length, source) as int64 CUDA tensors (source -1: a literal) and the
         stats dict, complete on return.  One call counts, one fills."""
-        import torch
         from ._lib import LzStats
-        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
-        total, stats = C.c_uint64(0), LzStats()
-        rc = lib().sufr_hip_lz_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, 0, None, None, None, C.byref(total), C.byref(stats))
-        if rc != -5:
-            self.ctx.check(rc)
-        out = [torch.empty(max(total.value, 1), dtype=torch.int64, device=lcp.device) for _ in range(3)]
-        if total.value:
-            self.ctx.check(lib().sufr_hip_lz_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, total.value, out[0].data_ptr(),
-                                                    out[1].data_ptr(), out[2].data_ptr(), C.byref(total), C.byref(stats)))
-            self.ctx.synchronize()
-        return out[0][:total.value], out[1][:total.value], out[2][:total.value], stats.as_dict()
+        _, st, st_ptr, st_n = self._lcp_inputs(lcp, seq_starts)
+        stats = LzStats()
+        cols = self._counted_device(lcp, 3, lambda cap, at, total: lib().sufr_hip_lz_device(
+            self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, cap, *at, C.byref(total), C.byref(stats)))
+        return (*cols, stats.as_dict())
 
     # -- sequence counts of repeats and k-common substrings (include/sufr_shared.h) -------------------------------------
     def shared_device(self, lcp, kind="branching", min_len: int = 1, min_count: int = 2, max_count: int = 0, min_seqs: int = 0,
                       max_seqs: int = 0, seq_starts=None):
         """SufrFile.shared on the device.  lcp and seq_starts as in kmers_device.  Returns (rank, count, length, seqs) as
         int64 CUDA tensors and the stats dict, complete on return.  One call counts, one fills."""
-        import torch
         from ._lib import REPEAT_KINDS, SharedStats
         kind = REPEAT_KINDS.get(kind, kind)
-        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
-        total, stats = C.c_uint64(0), SharedStats()
-        args = (self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count, max_count, min_seqs, max_seqs)
-        rc = lib().sufr_hip_shared_device(*args, 0, None, None, None, None, C.byref(total), C.byref(stats))
-        if rc != -5:
-            self.ctx.check(rc)
-        out = [torch.empty(max(total.value, 1), dtype=torch.int64, device=lcp.device) for _ in range(4)]
-        if total.value:
-            self.ctx.check(lib().sufr_hip_shared_device(*args, total.value, *(o.data_ptr() for o in out), C.byref(total), C.byref(stats)))
-            self.ctx.synchronize()
-        return (*(o[:total.value] for o in out), stats.as_dict())
+        _, st, st_ptr, st_n = self._lcp_inputs(lcp, seq_starts)
+        stats = SharedStats()
+        cols = self._counted_device(lcp, 4, lambda cap, at, total: lib().sufr_hip_shared_device(
+            self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, kind, min_len, min_count, max_count, min_seqs, max_seqs, cap, *at,
+            C.byref(total), C.byref(stats)))
+        return (*cols, stats.as_dict())
 
     def common_device(self, lcp, seq_starts=None):
         """SufrFile.common on the device: an int64 CUDA tensor of one entry per sequence, complete on return."""
         import torch
-        _, st, st_ptr, st_n = self._kmer_inputs(lcp, seq_starts)
+        _, st, st_ptr, st_n = self._lcp_inputs(lcp, seq_starts)
         out = torch.empty(max(st_n if st_ptr else 0, 1), dtype=torch.int64, device=lcp.device)
         self.ctx.check(lib().sufr_hip_common_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, out.data_ptr()))
         self.ctx.synchronize()

@@ -319,3 +319,24 @@ def test_cli_kmers_on_the_device_prints_the_host_bytes(tmp_path):
             occ, uniq = tmp_path / f"{where}.occ", tmp_path / f"{where}.uniq"
             outs[where] = (run("kmers", "-k", k, *opts, "--occ", occ, "--unique", uniq, EXP / name).stdout, occ.read_bytes(), uniq.read_bytes())
         assert outs["host"] == outs["device"] and outs["host"][0]
+
+
+def test_cli_kmers_side_files_and_output_file_on_the_device(tmp_path):
+    from test_match_host import run
+    for asked in ((), ("occ",), ("unique",)):
+        outs = {}
+        for where, opts in (("host", []), ("device", ["--device", 0])):
+            d = tmp_path / (where + "-" + "-".join(asked))
+            d.mkdir()
+            files = [x for name in asked for x in (f"--{name}", d / name)]
+            outs[where] = (run("kmers", "-k", 4, *opts, *files, EXP / "uniprot.sufr").stdout, {p.name: p.read_bytes() for p in d.iterdir()})
+        assert outs["host"] == outs["device"] and outs["host"][0] and sorted(outs["host"][1]) == sorted(asked)
+    host, dev = tmp_path / "host.tsv", tmp_path / "dev.tsv"
+    assert run("kmers", "-k", 4, "-o", host, EXP / "uniprot.sufr").stdout == run("kmers", "-k", 4, "-o", dev, "--device", 0, EXP / "uniprot.sufr").stdout == ""
+    assert host.read_bytes() == dev.read_bytes() != b""
+
+
+def test_cli_kmers_on_the_device_refuses_a_masked_file():
+    from test_match_host import run
+    r = run("kmers", "-k", 3, "--device", 0, EXP / "uniprot-masked.sufr", check=False)
+    assert r.returncode == 1 and r.stderr.startswith("Error: ") and "uniprot-masked.sufr" in r.stderr

@@ -382,6 +382,23 @@ def test_cli_kmers_prints_the_witness_spectrum(tmp_path):
     assert out.read_text() == spectrum_text(hist, stats, 256)
 
 
+def test_cli_kmers_writes_exactly_the_side_files_asked_for(tmp_path):
+    f = SufrFile(EXP / "uniprot.sufr")
+    hist, stats, occ_want = f.kmers(4, occ="position")
+    uniq_want = f.unique_lengths(by_position=True)
+    want = spectrum_text(hist, stats, 256)
+    for asked in ((), ("occ",), ("unique",)):
+        d = tmp_path / ("-".join(asked) or "neither")
+        d.mkdir()
+        opts = [x for name in asked for x in (f"--{name}", d / name)]
+        assert run("kmers", "-k", 4, *opts, EXP / "uniprot.sufr").stdout == want
+        assert sorted(p.name for p in d.iterdir()) == sorted(asked)
+        if "occ" in asked:
+            assert np.array_equal(np.fromfile(d / "occ", dtype="<u4"), occ_want)
+        if "unique" in asked:
+            assert np.array_equal(np.fromfile(d / "unique", dtype="<u4"), uniq_want)
+
+
 def test_cli_kmers_errors_and_help():
     r = run("kmers", "-k", 3, EXP / "uniprot-masked.sufr", check=False)
     assert r.returncode == 1 and r.stderr.startswith("Error: ") and "seed mask" in r.stderr

@@ -300,3 +300,12 @@ def test_cli_lz_on_the_device_prints_the_host_bytes():
         assert host.count("\n") > 4 and host == run("lz", "--device", 0, EXP / name).stdout
     host = run("lz", "--lpf", EXP / "2d.sufr").stdout
     assert host.count("\n") > 4 and host == run("lz", "--lpf", "--device", 0, EXP / "2d.sufr").stdout
+
+
+def test_cli_lz_on_the_device_to_a_file_and_refused(tmp_path):
+    from test_match_host import run
+    a, b = tmp_path / "host.tsv", tmp_path / "dev.tsv"
+    assert run("lz", "-o", a, EXP / "uniprot.sufr").stdout == run("lz", "-o", b, "--device", 0, EXP / "uniprot.sufr").stdout == ""
+    assert a.read_bytes() == b.read_bytes() != b""
+    r = run("lz", "--device", 0, EXP / "uniprot-masked.sufr", check=False)
+    assert r.returncode == 1 and r.stderr.startswith("Error: ") and "uniprot-masked.sufr" in r.stderr

@@ -297,3 +297,14 @@ def test_cli_repeats_on_the_device_prints_the_host_bytes():
                        ("3.sufr", ["-l", 1, "--kind", "super", "--max-positions", 0])):
         host = run("repeats", *opts, EXP / name).stdout
         assert host.count("\n") > 4 and host == run("repeats", *opts, "--device", 0, EXP / name).stdout
+
+
+def test_cli_repeats_on_the_device_without_records_to_a_file_and_refused(tmp_path):
+    from test_match_host import run
+    host = run("repeats", "-l", 100000, EXP / "uniprot.sufr").stdout
+    assert host.count("\n") == 4 and host == run("repeats", "-l", 100000, "--device", 0, EXP / "uniprot.sufr").stdout
+    a, b = tmp_path / "host.tsv", tmp_path / "dev.tsv"
+    assert run("repeats", "-l", 6, "-o", a, EXP / "uniprot.sufr").stdout == run("repeats", "-l", 6, "-o", b, "--device", 0, EXP / "uniprot.sufr").stdout == ""
+    assert a.read_bytes() == b.read_bytes() != b""
+    r = run("repeats", "-l", 3, "--device", 0, EXP / "uniprot-masked.sufr", check=False)
+    assert r.returncode == 1 and r.stderr.startswith("Error: ") and "uniprot-masked.sufr" in r.stderr

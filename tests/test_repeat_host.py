@@ -603,3 +603,10 @@ def test_cli_repeats_prints_the_witness_records(tmp_path):
     assert run("repeats", EXP / "3.sufr", check=False).returncode == 2           # no -l
     assert run("repeats", "-l", 3, "--kind", "tandem", EXP / "3.sufr", check=False).returncode == 2
     assert "repeats|rp" in run("--help").stdout
+
+
+def test_cli_repeats_without_records_and_refused(tmp_path):
+    assert run("repeats", "-l", 100000, EXP / "uniprot.sufr").stdout == "# records\t0\n# longest\t0\n# longest_rank\t0\n# max_count\t0\n"
+    out = tmp_path / "r.tsv"                                                     # the output is opened after the call: none after a refusal
+    r = run("repeats", "-l", 3, "-o", out, EXP / "uniprot-masked.sufr", check=False)
+    assert r.returncode == 1 and r.stderr.startswith("Error: ") and not out.exists()

@@ -407,3 +407,17 @@ def test_cli_shared_on_the_device_prints_the_host_bytes():
                        ("3.sufr", ["-l", 1, "--kind", "super", "--max-positions", 0, "--max-seqs", 2]), ("2.sufr", ["--common"])):
         host = run("shared", *opts, EXP / name).stdout
         assert host.count("\n") >= 2 and host == run("shared", *opts, "--device", 0, EXP / name).stdout
+
+
+def test_cli_shared_on_the_device_without_records_to_a_file_and_refused(tmp_path):
+    from test_match_host import run
+    opts = ["-l", 100000, "-q", 2]
+    host = run("shared", *opts, EXP / "uniprot.sufr").stdout
+    assert host.count("\n") == 5 and host == run("shared", *opts, "--device", 0, EXP / "uniprot.sufr").stdout
+    a, b = tmp_path / "host.tsv", tmp_path / "dev.tsv"
+    opts = ["-l", 6, "-q", 2]
+    assert run("shared", *opts, "-o", a, EXP / "uniprot.sufr").stdout == run("shared", *opts, "-o", b, "--device", 0, EXP / "uniprot.sufr").stdout == ""
+    assert a.read_bytes() == b.read_bytes() != b""
+    for opts in (["-l", 3], ["--common"]):
+        r = run("shared", *opts, "--device", 0, EXP / "uniprot-masked.sufr", check=False)
+        assert r.returncode == 1 and r.stderr.startswith("Error: ") and "uniprot-masked.sufr" in r.stderr

@@ -518,3 +518,8 @@ def test_cli_shared_prints_the_python_records(tmp_path):
     assert run("shared", "-l", 3, "--min-seq", 2, EXP / "3.sufr", check=False).returncode == 2
     assert run("shared", "-l", 3, "-q", check=False).returncode == 2
     assert "shared " in run("--help").stdout
+
+
+def test_cli_shared_without_records():
+    assert run("shared", "-l", 100000, "-q", 2, EXP / "uniprot.sufr").stdout == \
+        "# records\t0\n# longest\t0\n# longest_rank\t0\n# max_count\t0\n# max_seqs\t0\n"
