@@ -34,6 +34,27 @@ region's first position is the filler byte in every geometry.
   repeat_answers()  the records, stats and occurrences of every kind and filter of REPEAT_FILTERS as plain lists
   repeat_witness()  the twin's repeat answers, held to the serial witness of tests/test_repeat_host.py and shown not to be empty
   assert_repeat_witness_is_not_empty()   records on both sides of and across the boundary, clipped ranks decided from either side
+
+The sequence counts and the k-common profile (include/sufr_shared.h) and the longest previous factors and the LZ77 parse
+(include/sufr_lz.h) use the repeat region and its five sequences as they are: LPF is clipped by d(p), and seqs is only worth
+comparing with several sequences on either side of the boundary.  Of all analyses these two depend most on absolute
+positions: LPF compares them (SA[j] < p), scatters by them (lpf[p], src[p]) and returns them (src), the parse walks them, and
+seqs is decided by doc(SA[r]), a bisection of the sequence starts.  Rank, count, length, seqs, the stats, the profile, LPF
+and the parse's longest factor are translation-invariant; occurrences, SRC and longest_start differ by the shift, and every
+filler position is one more literal: factors and literals grow by the shift.
+
+Host LPF and LZ output by position is left out at the large geometries, for the reason given for k-mers in answers():
+sufr_file_lpf fills n entries per array (17 to 34 GB) and sufr_file_lz walks two n-entry u64 vectors (69 GB).  What the host
+and the kernels share of it, lz_rank of sufr_lz_scan.h, needs no n-entry array and is run on the shifted arrays through
+tests/lz_shim.cpp (tests/test_query_high_positions.py); the n-entry outputs are checked on the device.
+
+  SHARED_FILTERS    five filters on length, count and seqs; every one has records of kinds 0 and 1 on the twin
+  shared_answers()  the records (with seqs), stats and occurrences of every kind and filter, and the profile under "common"
+  shared_witness()  the twin's shared answers, held to the records of repeat_witness(), to len(set(docs)) and to a filter in Python
+  lz_answers_by_rank()   LPF and SRC of the region's positions as plain lists, the shift off SRC, no source as -1
+  lz_witness()      the twin's LPF, SRC and parse, held to the text alone (witness_lpf_at at lz_sample(), check_parse)
+  assert_lz_shared_witness_is_not_empty()   targets, sources and copies on both sides of and across the boundary, positions that
+                    the clip decides, every value of seqs, the records whose seqs a truncated position would change
 """
 from __future__ import annotations
 
@@ -509,3 +530,173 @@ def repeat_witness(f: SufrFile):
             compare(want, {repeat_key(kind, *flt): serial}, "the twin against the serial witness")
     counts = assert_repeat_witness_is_not_empty(want, f)
     return want, counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sequence counts and the k-common profile, longest previous factors and the LZ77 parse: the repeat region again
+# ---------------------------------------------------------------------------------------------------------------------
+SHARED_FILTERS = ((1, 2, 0, 0, 0), (12, 2, 0, 2, 0), (20, 3, 0, 0, 1), (1, 2, 0, 5, 0), (8, 2, 0, 3, 4))   # (min_len, min_count, max_count, min_seqs, max_seqs)
+LZ_SAMPLE_STEP = 40
+
+
+def shared_key(kind: int, min_len: int, min_count: int, max_count: int, min_seqs: int, max_seqs: int) -> str:
+    return f"shared kind={kind} min_len={min_len} min_count={min_count} max_count={max_count} min_seqs={min_seqs} max_seqs={max_seqs}"
+
+
+def shared_answers(source, shift: int, occurrences=None, common=None, threads: int = 0, filters=SHARED_FILTERS) -> dict:
+    """The shared records of every kind and filter as plain lists: rank, count, length, seqs, the stats as sorted items, and
+    the position column of repeat_occurrences(), the only one that takes the shift; under "common" the profile.  source: a
+    SufrFile, or a callable (kind, min_len, min_count, max_count, min_seqs, max_seqs) -> (rank, count, length, seqs, stats)
+    together with `occurrences` (see repeat_occurrences) and `common`, a callable that returns the profile."""
+    if isinstance(source, SufrFile):
+        f, sa = source, source.suffix_array
+        source = lambda kind, *flt: f.shared(kind, *flt, threads=threads)
+        occurrences = lambda ranks: np.asarray(sa[ranks])
+        common = lambda: f.common(threads=threads)
+    out = {}
+    for kind in REPEAT_KINDS:
+        for flt in filters:
+            rank, count, length, seqs, stats = source(kind, *flt)
+            out[shared_key(kind, *flt)] = [_ints(rank), _ints(count), _ints(length), _ints(seqs), sorted(stats.items())] + \
+                repeat_occurrences(_ints(rank), _ints(count), occurrences, shift)
+    out["common"] = _ints(common())
+    return out
+
+
+def lz_answers_by_rank(lpf_of_region, src_of_region, shift: int) -> dict:
+    """LPF and SRC of the region's positions (the last R entries of either array by position; numpy arrays or tensors of the
+    index width, signed or not) as plain lists: SRC with the shift taken off, no source (all ones of the width) as -1"""
+    def unsigned(a):
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+    lpf, src = unsigned(lpf_of_region), unsigned(src_of_region)
+    assert lpf.size == src.size == R and lpf.dtype == src.dtype
+    none = src == np.iinfo(src.dtype).max
+    return {"lpf of the region": lpf.astype(np.int64).tolist(),
+            "src of the region": np.where(none, -1, src.astype(np.int64) - shift).tolist()}
+
+
+def docs_by_rank(f: SufrFile) -> np.ndarray:
+    """the sequence of every rank's position, by bisection of the sequence starts"""
+    return np.searchsorted(np.asarray(f.sequence_starts, dtype=np.int64), np.asarray(f.suffix_array).astype(np.int64), side="right") - 1
+
+
+def _filter_shared(rows, ml, mc, xc, mq, xq):
+    """rows of (rank, count, length, seqs) in record order -> the rows a filter keeps and their stats"""
+    kept = [(a, c, ln, q) for a, c, ln, q in rows if ln >= ml and c >= max(mc, 2) and (xc == 0 or c <= xc) and q >= mq and (xq == 0 or q <= xq)]
+    top = max((ln for _, _, ln, _ in kept), default=0)
+    stats = dict(records=len(kept), longest=top, longest_rank=next((a for a, _, ln, _ in kept if ln == top), 0),
+                 max_count=max((c for _, c, _, _ in kept), default=0), max_seqs=max((q for _, _, _, q in kept), default=0))
+    return kept, stats
+
+
+def shared_witness(f: SufrFile, repeats: dict = None) -> dict:
+    """The twin's shared answers, held to what reads nothing of the library but the arrays: with open filters rank, count and
+    length are the records that repeat_witness() has held to the serial stack pass (`repeats`: its answers, computed when
+    not given); seqs of every record is len(set(docs[a : a + c])); every filter's answer is that list filtered here, with
+    its stats and occurrences; common[q - 1] is the longest record of kind 0 in at least q sequences."""
+    from test_shared_host import docs_of
+    twin = REPEAT_GEOMETRIES["twin"]
+    assert f.text_len == twin.n and f.sequence_starts == twin.seq_starts
+    repeats = repeats if repeats is not None else repeat_witness(f)[0]
+    want = shared_answers(f, 0)
+    docs = docs_of(f)
+    assert np.array_equal(docs, docs_by_rank(f))
+    sa = np.asarray(f.suffix_array)
+    for kind in REPEAT_KINDS:
+        rank, count, length, seqs, _ = f.shared(kind, 1, 2, 0, 0, 0)
+        rows = list(zip(_ints(rank), _ints(count), _ints(length), _ints(seqs)))
+        assert [list(col) for col in zip(*rows)][:3] == repeats[repeat_key(kind, 1, 2, 0)][:3], f"kind {kind}: not the records of repeats"
+        for a, c, _, q in rows:
+            assert q == len(set(docs[a:a + c].tolist())), (kind, a, c, q)
+        for flt in SHARED_FILTERS:
+            kept, stats = _filter_shared(rows, *flt)
+            cols = [[row[i] for row in kept] for i in range(4)]
+            filtered = cols + [sorted(stats.items())] + repeat_occurrences(cols[0], cols[1], lambda ranks: sa[ranks], 0)
+            compare(want, {shared_key(kind, *flt): filtered}, "the twin against its own records filtered in Python")
+        if kind == 0:
+            profile = [max((ln for _, _, ln, q in rows if q >= k), default=0) for k in range(1, len(twin.seq_starts) + 1)]
+            assert want["common"] == profile == [1000, 600, 300, 10, 8], (want["common"], profile)
+    return want
+
+
+def lz_sample():
+    """the twin's positions at which the text-only witness of LPF is asked: every 40th from 5 before the region on, the 600
+    around the boundary, 50 on either side of each of the five sequence starts"""
+    twin = REPEAT_GEOMETRIES["twin"]
+    some = set(range(twin.filler - 5, twin.n, LZ_SAMPLE_STEP)) | set(range(twin.boundary - 300, twin.boundary + 300))
+    for s in twin.seq_starts:
+        some |= set(range(max(s - 50, 0), s + 50))
+    return sorted(some)
+
+
+def lz_witness(f: SufrFile) -> dict:
+    """The twin's LPF, SRC and parse from the host path, held to the text alone: LPF at lz_sample() equals witness_lpf_at of
+    tests/test_lz_host.py (no suffix order, no LCP); every source is an earlier indexed position that spells the same
+    bytes, and there is none exactly where LPF is 0; check_parse holds the factors to the greedy walk over that LPF, to the
+    text they rebuild and to the breaks.  Returns the answers of lz_answers_by_rank() and, under "lz", start, length,
+    source (-1: a literal) and the stats as sorted items."""
+    from test_lz_host import FF, check_parse, host_lpf, witness_lpf_at
+    twin = REPEAT_GEOMETRIES["twin"]
+    assert f.text_len == twin.n and f.sequence_starts == twin.seq_starts
+    lpf, src = host_lpf(f)
+    some = lz_sample()
+    assert np.array_equal(lpf[some], witness_lpf_at(f, some)), "the host's LPF is not the text's at a sampled position"
+    assert np.array_equal(src == -1, lpf == 0)
+    tb = bytes(f.text)
+    indexed = set(np.asarray(f.suffix_array).tolist())
+    for p in np.nonzero(lpf)[0].tolist():
+        q, ln = int(src[p]), int(lpf[p])
+        assert 0 <= q < p and q in indexed and tb[q:q + ln] == tb[p:p + ln], (p, q, ln)
+    start, length, source, st = check_parse(f, lpf)
+    raw = f.lpf()
+    want = lz_answers_by_rank(raw[0][twin.filler:], raw[1][twin.filler:], 0)
+    assert want["lpf of the region"] == lpf[twin.filler:].tolist() and want["src of the region"] == src[twin.filler:].tolist()
+    want["lz"] = [_ints(start), _ints(length), np.where(source == FF, -1, source.astype(np.int64)).tolist(), sorted(st.items())]
+    want["lpf of the twin"], want["src of the twin"] = lpf.tolist(), src.tolist()
+    return want
+
+
+def assert_lz_shared_witness_is_not_empty(f: SufrFile, lz: dict, shared: dict) -> dict:
+    """What keeps the comparisons of LPF, the parse and the shared records from being empty, decided by the twin's file and
+    answers alone (B is the twin's boundary).  Returns the counts it looked at."""
+    from test_repeat_host import brk_of
+    twin = REPEAT_GEOMETRIES["twin"]
+    B, F = twin.boundary, twin.filler
+    assert f.text_len == twin.n and f.sequence_starts == twin.seq_starts
+    lpf, src = np.array(lz["lpf of the twin"], dtype=np.int64), np.array(lz["src of the twin"], dtype=np.int64)
+    p = np.nonzero(lpf)[0]
+    q, ln = src[p], lpf[p]
+    room = brk_of(f) - np.arange(twin.n)
+    clip = p[ln == room[p]]
+    seen = {"lpf nonzero": int(p.size), "lpf nonzero in the filler": int((p < F).sum()), "lpf max": int(lpf.max()),
+            "lpf above the boundary, source below": int(((p > B) & (q < B)).sum()),
+            "lpf and source above the boundary": int(((p > B) & (q > B)).sum()),
+            "lpf and source below the boundary": int(((p < B) & (q < B)).sum()),
+            "lpf targets that span the boundary byte": int(((p <= B) & (B < p + ln)).sum()),
+            "lpf sources that span the boundary byte": int(((q <= B) & (B < q + ln)).sum()),
+            "lpf self-overlapping copies": int((q + ln > p).sum()),
+            "lpf decided by the clip": int(clip.size), "lpf decided by the clip above the boundary": int((clip > B).sum()),
+            "lpf decided by the clip below the boundary": int((clip < B).sum())}
+    start, length, source, st = lz["lz"]
+    start, length, source, st = np.array(start, dtype=np.int64), np.array(length, dtype=np.int64), np.array(source, dtype=np.int64), dict(st)
+    across = (start <= B) & (B < start + length)
+    seen.update({"lz factors": st["factors"], "lz literals of the filler": int((start < F).sum()), "lz literals": st["literals"],
+                 "lz longest": st["longest"], "lz longest_start": st["longest_start"], "lz factors that span the boundary byte": int(across.sum()),
+                 "lz copies that start below the boundary": int(((source >= 0) & (start < B)).sum()),
+                 "lz copies that start above the boundary": int(((source >= 0) & (start > B)).sum())})
+    assert (source[start < F] == -1).all() and across.sum() == 1 and int(start[across][0]) == st["longest_start"] and int(length[across][0]) == st["longest"]
+    rank, count, _, seqs = (np.array(col, dtype=np.int64) for col in shared[shared_key(0, *SHARED_FILTERS[0])][:4])
+    for k in range(1, len(twin.seq_starts) + 1):
+        seen[f"shared kind=0 records with seqs={k}"] = int((seqs == k).sum())
+    seen["shared kind=0 records with 1 < seqs < count"] = int(((seqs > 1) & (seqs < count)).sum())
+    for kind in (0, 1):
+        for flt in SHARED_FILTERS:
+            assert len(shared[shared_key(kind, *flt)][0]) > 0, (kind, flt)
+    # a position of B and more that is truncated to 32 bits at u64_across_2_32 lands in the filler: sequence 0
+    sa, docs = np.asarray(f.suffix_array).astype(np.int64), docs_by_rank(f)
+    wrapped = np.where(sa >= B, 0, docs)
+    seen["shared kind=0 records whose seqs changes if positions from the boundary on read as sequence 0"] = \
+        sum(1 for a, c, k in zip(rank.tolist(), count.tolist(), seqs.tolist()) if len(set(wrapped[a:a + c].tolist())) != k)
+    assert all(v for key, v in seen.items() if key != "lpf nonzero in the filler") and seen["lpf nonzero in the filler"] == 0, seen
+    return seen

@@ -7,14 +7,22 @@ out on the host; tests/test_gpu_high_positions.py checks it on the device.
 
 The repeats of the indexed text (include/sufr_repeat.h) have a region and five sequences of their own, in which sequence
 starts clip the LCP on both sides of the boundary; tests/test_gpu_repeat_high_positions.py holds the device to the same
-witness."""
+witness.
+
+The sequence counts and the k-common profile (include/sufr_shared.h) use that region too, on the host and through the CLI.
+LPF and the LZ77 parse by position have n entries on the host as well (sufr_file_lpf: 17 to 34 GB; sufr_file_lz: two n-entry
+u64 vectors, 69 GB) and are left out; the decision of one rank that the host path and the kernels share (lz_rank of
+sufr_lz_scan.h) runs on the shifted arrays through tests/lz_shim.cpp, and tests/test_gpu_lz_shared_high_positions.py holds
+the device to the same witness."""
 import subprocess
 
+import numpy as np
 import pytest
 
 import high_positions as hp
 import sufr_amd
 from high_positions import GEOMETRIES, LARGE, REPEAT_GEOMETRIES
+from test_lz_host import NONE as LZ_NONE, pyramid, shim  # noqa: F401 (shim: the fixture that builds tests/lz_shim.cpp)
 
 
 def run(*args):
@@ -147,7 +155,8 @@ def test_host_repeats_equal_the_twin(repeat_files, repeat_witness, name):
 
 
 def _repeat_lines(stdout: str, shift: int):
-    """`sufr repeats` output: (records, stats lines).  A record is (length, count, [(name, position) ...]) with the shift taken
+    """`sufr repeats` and `sufr shared` output: (records, stats lines).  A record is (length, count, [(name, position) ...]),
+    of `sufr shared` (length, count, seqs, [(name, position) ...]), with the shift taken
     off the positions within the first sequence, which begins at 0 and holds the filler, and off nothing else: the other
     sequences begin behind the filler, so the positions within them are printed as the twin's."""
     records, stats = [], []
@@ -155,9 +164,9 @@ def _repeat_lines(stdout: str, shift: int):
         if line.startswith("#"):
             stats.append(line)
             continue
-        length, count, where = line.split("\t")
+        *columns, where = line.split("\t")                            # (`sufr shared` has a third column, seqs, before the places)
         places = [w.rsplit(":", 1) for w in where.split(" ")]
-        records.append((length, count, [(nm, str(int(x) - shift) if nm == hp.REPEAT_NAMES[0] else x) for nm, x in places]))
+        records.append((*columns, [(nm, str(int(x) - shift) if nm == hp.REPEAT_NAMES[0] else x) for nm, x in places]))
     return records, stats
 
 
@@ -188,3 +197,109 @@ def test_cli_repeats_beyond_2_32(repeat_files):
         keep = lambda s: [[w for w in line.split("\t")[2].split(" ") if not w.startswith(hp.REPEAT_NAMES[0] + ":")]
                           for line in s.splitlines() if not line.startswith("#")]
         assert keep(got) == keep(want)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sequence counts, the k-common profile, longest previous factors and the LZ77 parse: the repeat region again
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lz_shared_witness(repeat_files, repeat_witness):
+    """(shared answers, LZ answers, counts) of the twin, each held to what reads only the arrays or only the text"""
+    with hp.open_repeat_file(repeat_files["twin"][0], REPEAT_GEOMETRIES["twin"]) as f:
+        shared = hp.shared_witness(f, repeat_witness[0])
+        lz = hp.lz_witness(f)
+        return shared, lz, hp.assert_lz_shared_witness_is_not_empty(f, lz, shared)
+
+
+def test_the_lz_and_shared_witness_is_held_to_the_arrays_and_the_text_and_its_counts_are_pinned(lz_shared_witness):
+    """(asserted in the fixture, from the twin alone)  The counts of the committed region are pinned, so that the region
+    cannot drift unseen: LPF has targets and sources on either side of the boundary and spans over it, self-overlapping
+    copies and positions that the clip decides on both sides; the one factor that spans the boundary byte is the longest;
+    every value of seqs occurs, and 12 123 records of kind 0 would change their seqs if a position from the boundary on read
+    as sequence 0, which is what a position of 2^32 and more truncated to 32 bits does at u64_across_2_32"""
+    shared, lz, counts = lz_shared_witness
+    print(counts)
+    assert counts == {
+        "lpf nonzero": 39591, "lpf nonzero in the filler": 0, "lpf max": 1200,
+        "lpf above the boundary, source below": 13854, "lpf and source above the boundary": 5742, "lpf and source below the boundary": 19994,
+        "lpf targets that span the boundary byte": 601, "lpf sources that span the boundary byte": 4, "lpf self-overlapping copies": 1020,
+        "lpf decided by the clip": 950, "lpf decided by the clip above the boundary": 937, "lpf decided by the clip below the boundary": 13,
+        "lz factors": 9934, "lz literals of the filler": 4096, "lz literals": 4505, "lz longest": 1197, "lz longest_start": 23499,
+        "lz factors that span the boundary byte": 1, "lz copies that start below the boundary": 2987, "lz copies that start above the boundary": 2442,
+        "shared kind=0 records with seqs=1": 4775, "shared kind=0 records with seqs=2": 11326, "shared kind=0 records with seqs=3": 4738,
+        "shared kind=0 records with seqs=4": 2361, "shared kind=0 records with seqs=5": 1913, "shared kind=0 records with 1 < seqs < count": 12182,
+        "shared kind=0 records whose seqs changes if positions from the boundary on read as sequence 0": 12123}
+    sizes = [[len(shared[hp.shared_key(kind, *flt)][0]) for kind in hp.REPEAT_KINDS] for flt in hp.SHARED_FILTERS]
+    assert sizes == [[25113, 20729, 7459], [1531, 25, 21], [980, 980, 0], [1913, 1913, 0], [1008, 628, 41]]
+    assert shared["common"] == [1000, 600, 300, 10, 8] and len(shared) == 16
+    # every factor is a literal or a copy that starts on one side of the boundary (none starts at the boundary byte)
+    assert counts["lz copies that start below the boundary"] + counts["lz copies that start above the boundary"] == counts["lz factors"] - counts["lz literals"]
+    assert REPEAT_GEOMETRIES["twin"].boundary == 24096 and len(hp.lz_sample()) > 1500
+
+
+@pytest.mark.parametrize("name", LARGE)
+def test_host_shared_and_common_equal_the_twin(repeat_files, lz_shared_witness, name):
+    geo = REPEAT_GEOMETRIES[name]
+    path = sparse_or_skip(repeat_files, name)
+    with hp.open_repeat_file(path, geo) as f:
+        assert int(f.suffix_array.max()) == geo.n - 1 and int(f.suffix_array.min()) == geo.filler
+        assert f.sequence_starts[1] > geo.filler and (name != "u64_across_2_32" or f.sequence_starts[3] > 1 << 32 > f.sequence_starts[2])
+        for threads in (1, 0):
+            hp.compare(hp.shared_answers(f, geo.shift, threads=threads), lz_shared_witness[0], f"{name} (threads={threads})")
+
+
+SHARED_CLI = (("-l", 12, "--kind", "maximal", "-q", 2), ("-l", 1, "--kind", "super", "-c", 3, "--max-positions", 0))
+
+
+def test_cli_shared_beyond_2_32(repeat_files):
+    """`sufr shared` on the u64_across_2_32 file against the twin, as test_cli_repeats_beyond_2_32 reads `sufr repeats`: the
+    seqs column is found from absolute positions on both sides of 2^32 and must be the twin's; a position of 2^32 and more
+    that is truncated lands in the filler, is counted for the first sequence and printed within it.  The profile of
+    `--common` has no position at all: byte for byte the twin's."""
+    geo = REPEAT_GEOMETRIES["u64_across_2_32"]
+    path = sparse_or_skip(repeat_files, geo.name)
+    starts = dict(zip(hp.REPEAT_NAMES, geo.seq_starts))
+    for opts in SHARED_CLI:
+        got, want = run("shared", *opts, path).stdout, run("shared", *opts, repeat_files["twin"][0]).stdout
+        (g_rec, g_stats), (w_rec, w_stats) = _repeat_lines(got, geo.shift), _repeat_lines(want, 0)
+        assert g_stats == w_stats and len(w_stats) == 5 and g_rec == w_rec and w_rec and all(len(rec) == 4 for rec in w_rec), opts
+        assert {int(rec[2]) for rec in w_rec} >= {2, 3}, opts                       # records in two and in three sequences
+        printed = [(nm, int(x)) for *_, places in _repeat_lines(got, 0)[0] for nm, x in places]
+        first = [x for nm, x in printed if nm == hp.REPEAT_NAMES[0]]
+        assert first and min(first) >= geo.filler == (1 << 32) - hp.MID and max(first) < starts["s1"]
+        # (decided by the twin's records and the test's own starts: what keeps the comparison from being empty)
+        assert max(starts[nm] + x for nm, x in printed) > 1 << 32 and {nm for nm, _ in printed} == set(hp.REPEAT_NAMES), opts
+        keep = lambda s: [[w for w in line.split("\t")[3].split(" ") if not w.startswith(hp.REPEAT_NAMES[0] + ":")]
+                          for line in s.splitlines() if not line.startswith("#")]
+        assert keep(got) == keep(want)
+    got, want = run("shared", "--common", path).stdout, run("shared", "--common", repeat_files["twin"][0]).stdout
+    assert got == want == "1\t1000\n2\t600\n3\t300\n4\t10\n5\t8\n"
+
+
+@pytest.mark.parametrize("name", LARGE)
+def test_lpf_rank_decisions_at_shifted_positions(shim, repeat_files, lz_shared_witness, name):
+    """lz_rank of sufr_lz_scan.h -- the arithmetic the host path and the kernels share -- on SA(region) + filler through
+    tests/lz_shim.cpp: the min pyramid over the suffix array's values, the two searches by value (SA[j] <= p - 1, SA[j] < p),
+    the two range minima and the clip by rooms computed here from the geometry's sequence starts.  No n-entry array is
+    needed, so this holds at every large geometry; LPF by rank is the twin's, SRC the twin's plus the shift.  At the two
+    32-bit geometries once more with the pyramid's entries narrowed to uint32 and widened again, which is what the device
+    stores: a later failure of the device test is then not one of this arithmetic."""
+    geo, twin = REPEAT_GEOMETRIES[name], REPEAT_GEOMETRIES["twin"]
+    reg = hp.repeat_region()
+    sa = np.ascontiguousarray(reg.sa + np.uint64(geo.filler))
+    lcp = np.ascontiguousarray(reg.lcp)
+    breaks = np.array(sorted({geo.n - 1} | {s - 1 for s in geo.seq_starts[1:]}), dtype=np.uint64)
+    room = np.ascontiguousarray(breaks[np.searchsorted(breaks, sa, side="left")] - sa)
+    assert int(sa.max()) == geo.n - 1 and int(room.min()) == 0 and int(room.max()) < hp.R
+    lpf_twin = np.array(lz_shared_witness[1]["lpf of the twin"], dtype=np.int64)
+    src_twin = np.array(lz_shared_witness[1]["src of the twin"], dtype=np.int64)
+    at = (reg.sa + np.uint64(twin.filler)).astype(np.int64)
+    want_lpf, want_src = lpf_twin[at], np.where(src_twin[at] < 0, -1, src_twin[at] + geo.shift)
+    assert (want_lpf > 0).sum() == 39591 and (want_src >= geo.boundary).any() and ((want_src >= 0) & (want_src < geo.boundary)).any()
+    up_sa, up_lcp = pyramid(shim, sa), pyramid(shim, lcp)
+    narrowed = [up_sa] + ([up_sa.astype(np.uint32).astype(np.uint64)] if geo.width == 4 else [])
+    for up in narrowed:
+        lpf, src = np.zeros(sa.size, dtype=np.uint64), np.zeros(sa.size, dtype=np.uint64)
+        shim.shim_lz_rank_all(sa.ctypes.data, up.ctypes.data, lcp.ctypes.data, up_lcp.ctypes.data, sa.size, room.ctypes.data, lpf.ctypes.data, src.ctypes.data)
+        assert np.array_equal(lpf.astype(np.int64), want_lpf), name
+        assert np.array_equal(np.where(src == LZ_NONE, -1, src.astype(np.int64)), want_src), name
