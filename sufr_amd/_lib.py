@@ -162,6 +162,19 @@ class SharedStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# every symbol include/sufr_bwt.h declares
+BWT_EXPORTS = ["sufr_file_bwt", "sufr_file_bwt_runs", "sufr_file_lf", "sufr_hip_bwt_device", "sufr_hip_bwt_runs_device", "sufr_hip_lf_device",
+               "sufr_hip_set_bwt_tile"]
+
+
+class BwtStats(C.Structure):
+    """sufr_bwt_stats"""
+    _fields_ = [("runs", C.c_uint64), ("records", C.c_uint64), ("longest", C.c_uint64), ("longest_rank", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class FileMeta(C.Structure):
     """sufr_file_meta"""
     _fields_ = [("version", C.c_uint8), ("is_dna", C.c_uint8), ("allow_ambiguity", C.c_uint8),
@@ -341,6 +354,15 @@ def lib() -> C.CDLL:
                                          C.POINTER(SharedStats)]
     L.sufr_hip_shared_device.restype = C.c_int
     L.sufr_hip_common_device.argtypes = [vp, vp, vp, vp, u64, vp]; L.sufr_hip_common_device.restype = C.c_int
+    # include/sufr_bwt.h
+    L.sufr_file_bwt.argtypes = [vp, vp, vp, C.c_int]; L.sufr_file_bwt.restype = C.c_int
+    L.sufr_file_bwt_runs.argtypes = [vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(BwtStats), C.c_int]; L.sufr_file_bwt_runs.restype = C.c_int
+    L.sufr_file_lf.argtypes = [vp, vp, C.c_int]; L.sufr_file_lf.restype = C.c_int
+    L.sufr_hip_bwt_device.argtypes = [vp, vp, vp, vp]; L.sufr_hip_bwt_device.restype = C.c_int
+    L.sufr_hip_bwt_runs_device.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(BwtStats)]
+    L.sufr_hip_bwt_runs_device.restype = C.c_int
+    L.sufr_hip_lf_device.argtypes = [vp, vp, vp]; L.sufr_hip_lf_device.restype = C.c_int
+    L.sufr_hip_set_bwt_tile.argtypes = [vp, u64]; L.sufr_hip_set_bwt_tile.restype = C.c_int
     _lib = L
     return L
 
@@ -400,6 +422,11 @@ class Context:
         """LPF and LZ77: ranks one workgroup of the LPF pass takes at a time and text positions one workgroup of the parse
         takes at a time (sufr_hip_set_lz_tile; 0: the default).  Rounded up to 256 and held to 16384; they change no result."""
         self.check(lib().sufr_hip_set_lz_tile(self._h, ranks, positions))
+
+    def set_bwt_tile(self, ranks: int = 0):
+        """BWT, runs and LF: ranks one workgroup takes at a time (sufr_hip_set_bwt_tile; 0: the default).  Rounded up to 256
+        and held to 16384; it changes no result."""
+        self.check(lib().sufr_hip_set_bwt_tile(self._h, ranks))
 
     @property
     def window_repairs(self) -> int:

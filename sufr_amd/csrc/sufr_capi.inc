@@ -18,6 +18,8 @@ struct sufr_hip_ctx {
     uint32_t repeat_tile = 0;          // sufr_hip_set_repeat_tile: ranks per tile (0: the default)
     sufr::DevBuf lzpyr, lzarr, lztab, lzsum;  // LPF and LZ77 (sufr_lz.inc): the two min pyramids, LPF and SRC, the parse tables, tile entries / bases / candidates and stats
     uint32_t lz_rank_tile = 0, lz_pos_tile = 0;  // sufr_hip_set_lz_tile: ranks per LPF tile, positions per parse tile (0: the default)
+    sufr::DevBuf bwtbytes, bwtsum, bwttab;  // BWT, runs and LF (sufr_bwt.inc): the BWT bytes, tile summaries / carries / counts and stats, the tiles' bases per occurring byte value
+    uint32_t bwt_tile = 0;             // sufr_hip_set_bwt_tile: ranks per tile (0: the default)
     sufr::DevBuf shkeys, shhist, shpre, shsum;  // sequence counts (sufr_shared.inc): the two key buffers of the sort, its digit counts, H / P, tile sums and candidates and stats and the profile
     bool wide(uint64_t n) const { return n >= sufr::SUFR_MAX_TEXT_LEN || (wide_window && n > wide_window); }
 };
@@ -227,6 +229,7 @@ void sufr_hip_destroy(sufr_hip_ctx* ctx)
                             &ctx->ecnt, &ctx->ekeys, &ctx->ekeys2, &ctx->ehist, &ctx->tsc, &ctx->trows, &ctx->tmisc,
                             &ctx->kbits, &ctx->ksum, &ctx->kstarts, &ctx->rell, &ctx->rpyr, &ctx->rbits, &ctx->rsum,
                             &ctx->lzpyr, &ctx->lzarr, &ctx->lztab, &ctx->lzsum,
+                            &ctx->bwtbytes, &ctx->bwtsum, &ctx->bwttab,
                             &ctx->shkeys, &ctx->shhist, &ctx->shpre, &ctx->shsum}) ctx->pl.release(*b);
     ctx->pl.destroy();
     delete ctx;

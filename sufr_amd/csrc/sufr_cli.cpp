@@ -27,6 +27,7 @@
 #include "../../include/sufr_kmer.h"
 #include "../../include/sufr_repeat.h"
 #include "../../include/sufr_lz.h"
+#include "../../include/sufr_bwt.h"
 #include "../../include/sufr_shared.h"
 
 #include <hip/hip_runtime_api.h>
@@ -103,6 +104,15 @@ int usage(FILE* f)
             "                                       seq:offset  length  source-seq:offset (* for a literal), then # factors, # literals,\n"
             "                                       # longest, # longest_start\n"
             "                                       [--lpf: one line per text position instead: seq:offset  longest previous factor  source]\n"
+            "                                       [--device ID: on that GPU; otherwise on the host] [-t THREADS] [-o OUT]\n"
+            "  bwt          <SUFR>                  the Burrows-Wheeler transform of the indexed text from its SA (the byte in front of\n"
+            "                                       every indexed suffix, in rank order): one line symbol  count per occurring byte\n"
+            "                                       (printable bytes as themselves, others as \\xHH), then # ranks, # runs, # longest,\n"
+            "                                       # longest_rank of its equal-letter runs\n"
+            "                                       [--runs [--min-len L (1)]: in front of the # lines one line per run of at least L ranks:\n"
+            "                                       rank  length  symbol  seq:offset of its first suffix]\n"
+            "                                       [--bwt FILE: the raw bytes, one per rank] [--lf FILE: the LF mapping, one raw little-endian\n"
+            "                                       entry of the index width (4 or 8 bytes) per rank]\n"
             "                                       [--device ID: on that GPU; otherwise on the host] [-t THREADS] [-o OUT]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
@@ -776,9 +786,9 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// the analyses of the indexed text from its LCP array: kmers, repeats, shared, lz
+// the analyses of the indexed text from its arrays: kmers, repeats, shared, lz (SA + LCP) and bwt (SA + text)
 // ---------------------------------------------------------------------------------------------------------------
-// What the four hold while they run: the arguments they share, the .sufr file with its metadata and sequence starts, the
+// What they hold while they run: the arguments they share, the .sufr file with its metadata and sequence starts, the
 // output and, with --device, the index on that device and every device allocation (the LCP array is the first).  The
 // first failure stays in `rc` (with a text of the session's own in `err` for allocations and copies) and turns the steps
 // after it into no-ops, so a command reads top to bottom and asks once, in computed().  Everything is released on every
@@ -791,12 +801,13 @@ struct AnalysisSession {
     std::vector<uint64_t> starts;               // of the sequences: what the *_device calls take beside the LCP array
     std::optional<DeviceIndex> dev;
     void* d_lcp = nullptr;
+    bool need_lcp = true;                       // false: the command reads no LCP array (bwt), none is copied to the device
     std::vector<void*> allocations;
     OutFile out;
     int rc = 0;
     std::string err;
 
-    // the arguments behind the sub-command: own(s, i, need) takes the command's options, the rest is the same for all four.
+    // the arguments behind the sub-command: own(s, i, need) takes the command's options, the rest is the same for all.
     // Returns the exit status, or -1 to go on
     template <typename Own>
     int parse(int argc, char** argv, int first, Own own)
@@ -827,6 +838,7 @@ struct AnalysisSession {
         dev.emplace(device, f);
         if (!dev->ctx) { fprintf(stderr, "Error: %s\n", dev->error()); return false; }
         rc = dev->rc;
+        if (!need_lcp) return true;
         const uint64_t bytes = m.len_suffixes * (uint64_t)m.index_width;
         if (!rc && hipSetDevice(device) != hipSuccess) fail("device memory for the LCP array");
         d_lcp = alloc(bytes + 8, "the LCP array");
@@ -1129,6 +1141,78 @@ int run_lz(int argc, char** argv, int first, int threads)
     return 0;
 }
 
+// a byte as sufr bwt prints it: printable bytes as themselves, the others (the space and the backslash among them) as \xHH
+std::string shown_byte(uint64_t c)
+{
+    char buf[8];
+    if (c > 0x20 && c < 0x7F && c != '\\') snprintf(buf, sizeof buf, "%c", (int)c);
+    else snprintf(buf, sizeof buf, "\\x%02X", (unsigned)c);
+    return buf;
+}
+
+// sufr bwt: the byte counts of the BWT and the run stats to standard output (or -o), with --runs the run
+// records in front of the stats; the BWT and the LF array to --bwt / --lf
+int run_bwt(int argc, char** argv, int first, int threads)
+{
+    AnalysisSession s;
+    s.need_lcp = false;
+    std::string bwt_path, lf_path;
+    uint64_t min_len = 1;
+    bool runs = false;
+    const int parsed = s.parse(argc, argv, first, [&](const std::string& o, int& i, auto& need) {
+        if (o == "--runs") runs = true;
+        else if (o == "--min-len") min_len = strtoull(need(i, "--min-len"), nullptr, 10);
+        else if (o == "--bwt") bwt_path = need(i, "--bwt");
+        else if (o == "--lf") lf_path = need(i, "--lf");
+        else if (o == "-t" || o == "--threads") threads = atoi(need(i, "-t"));
+        else return false;
+        return true;
+    });
+    if (parsed >= 0) return parsed;
+    if (s.file.empty()) return s.missing("<SUFR>");
+    if (!s.open()) return 1;
+    const uint64_t ns = s.m.len_suffixes, lf_bytes = ns * (uint64_t)s.m.index_width;
+    const bool want_lf = !lf_path.empty();
+    std::vector<uint8_t> bwt(ns + 8), lf(want_lf ? lf_bytes + 8 : 0);
+    std::vector<uint64_t> counts(256, 0), cols[4];       // the runs: rank, length, symbol, first
+    sufr_bwt_stats st{0, 0, 0, 0};
+    uint64_t total = 0;
+    if (!s.dev) {
+        s.rc = sufr_file_bwt(s.f, bwt.data(), counts.data(), threads);
+        if (!s.rc && want_lf) s.rc = sufr_file_lf(s.f, lf.data(), threads);
+    } else {
+        uint8_t* d_counts = (uint8_t*)s.alloc(256 * 8 + ns + 8, "the outputs");       // the counts, then the BWT
+        s.on_device([&]() { return sufr_hip_bwt_device(s.dev->ctx, s.dev->ix, d_counts + 256 * 8, d_counts); },
+                    {{counts.data(), d_counts, 256 * 8}, {bwt.data(), d_counts ? d_counts + 256 * 8 : nullptr, ns}});
+        if (want_lf) {
+            void* d_lf = s.alloc(lf_bytes + 8, "the outputs");
+            s.on_device([&]() { return sufr_hip_lf_device(s.dev->ctx, s.dev->ix, d_lf); }, {{lf.data(), d_lf, lf_bytes}});
+        }
+    }
+    // (the stats come from the runs call: without --runs it only counts, with a filter that keeps nothing but the longest)
+    s.counted(4, cols, total,
+              [&](uint64_t cap, uint64_t** c, uint64_t* tot) { return sufr_file_bwt_runs(s.f, runs ? min_len : ~0ull, cap, c[0], c[1], c[2], c[3], tot, &st, threads); },
+              [&](uint64_t cap, uint64_t** c, uint64_t* tot) {
+                  return sufr_hip_bwt_runs_device(s.dev->ctx, s.dev->ix, runs ? min_len : ~0ull, cap, c[0], c[1], c[2], c[3], tot, &st);
+              });
+    if (!s.computed("bwt failed", "bwt: invalid argument", "bwt failed")) return 1;
+    for (uint64_t c = 0; c < 256; c++)
+        if (counts[c]) fprintf(s.out.f, "%s\t%llu\n", shown_byte(c).c_str(), (unsigned long long)counts[c]);
+    for (uint64_t i = 0; runs && i < total; i++)
+        fprintf(s.out.f, "%llu\t%llu\t%s\t%s\n", (unsigned long long)cols[0][i], (unsigned long long)cols[1][i], shown_byte(cols[2][i]).c_str(),
+                place(s.f, false, cols[3][i]).c_str());
+    print_stats(s.out.f, {{"ranks", ns}, {"runs", st.runs}, {"longest", st.longest}, {"longest_rank", st.longest_rank}});
+    auto dump = [&](const std::string& path, const std::vector<uint8_t>& a, uint64_t bytes) {
+        if (path.empty()) return true;
+        FILE* fh = fopen(path.c_str(), "wb");
+        const bool ok = fh && fwrite(a.data(), 1, bytes, fh) == bytes;
+        if (fh) fclose(fh);
+        if (!ok) fprintf(stderr, "Error: %s: cannot write\n", path.c_str());
+        return ok;
+    };
+    return dump(bwt_path, bwt, ns) && dump(lf_path, lf, lf_bytes) ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -1182,6 +1266,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && (s == "repeats" || s == "rp")) return run_repeats(argc, argv, i + 1, threads);
         else if (!have_cmd && s == "shared") return run_shared(argc, argv, i + 1, threads);
         else if (!have_cmd && s == "lz") return run_lz(argc, argv, i + 1, threads);
+        else if (!have_cmd && s == "bwt") return run_bwt(argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "edit" || s == "ed")) return run_query("edit", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);

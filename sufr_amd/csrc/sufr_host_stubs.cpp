@@ -23,6 +23,7 @@
 #include "../../include/sufr_repeat.h"
 #include "../../include/sufr_lz.h"
 #include "../../include/sufr_shared.h"
+#include "../../include/sufr_bwt.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -171,5 +172,17 @@ int sufr_hip_shared_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*
     return no_device(ctx);
 }
 int sufr_hip_common_device(sufr_hip_ctx* ctx, const sufr_hip_index*, const void*, const uint64_t*, uint64_t, void*) { return no_device(ctx); }
+
+// ---- include/sufr_bwt.h: the device side (the host side is sufr_query.cpp) ------------------------------------------
+int sufr_hip_bwt_device(sufr_hip_ctx* ctx, const sufr_hip_index*, void*, void*) { return no_device(ctx); }
+int sufr_hip_bwt_runs_device(sufr_hip_ctx* ctx, const sufr_hip_index*, uint64_t, uint64_t, void*, void*, void*, void*, uint64_t* total_out,
+                             sufr_bwt_stats* stats_out)
+{
+    if (total_out) *total_out = 0;
+    if (stats_out) *stats_out = sufr_bwt_stats{0, 0, 0, 0};
+    return no_device(ctx);
+}
+int sufr_hip_lf_device(sufr_hip_ctx* ctx, const sufr_hip_index*, void*) { return no_device(ctx); }
+int sufr_hip_set_bwt_tile(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
 
 }  // extern "C"

@@ -3008,3 +3008,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_lz.inc"
 #include "../../include/sufr_shared.h"
 #include "sufr_shared.inc"
+#include "../../include/sufr_bwt.h"
+#include "sufr_bwt.inc"

@@ -1327,3 +1327,172 @@ int sufr_file_common(const sufr_file* f, uint64_t* common, int threads)
 }
 
 }  // extern "C"
+
+// ---- the BWT of the indexed text, its runs and the LF mapping (include/sufr_bwt.h) --------------
+#include "../../include/sufr_bwt.h"
+#include "sufr_bwt_scan.h"
+
+namespace {
+
+// The ranks are cut into tiles of this many, whatever the number of workers: a worker takes whole tiles, what crosses a tile's
+// end goes through per-tile summaries (sufr_bwt_scan.h), and so every result is the same for every thread count.
+constexpr uint64_t BWT_HOST_TILE = (uint64_t)1 << 16;
+
+// BWT[b, e) into out[b, e) (where out is not null) and its byte counts added to hist (256 entries, where not null)
+void bwt_host_range(const sufr_file& f, uint64_t b, uint64_t e, uint8_t* out, uint64_t* hist)
+{
+    const uint64_t n = f.meta.text_len;
+    const int fw = f.meta.index_width;
+    for (uint64_t r = b; r < e; r++) {
+        const uint8_t c = f.text[sufr::bwt_source(rdT(f.sa, fw, r), n)];
+        if (out) out[r] = c;
+        if (hist) hist[c]++;
+    }
+}
+
+std::vector<uint8_t> bwt_host_bytes(const sufr_file& f, int threads)
+{
+    std::vector<uint8_t> bwt(f.meta.len_suffixes);
+    parallel_chunks(bwt.size(), BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) { bwt_host_range(f, b, e, bwt.data(), nullptr); });
+    return bwt;
+}
+
+// ext[t] of sufr_bwt_scan.h for the tiles of BWT_HOST_TILE ranks: the summaries in parallel, then one sweep from the last tile
+std::vector<uint64_t> bwt_host_carry(const std::vector<uint8_t>& bwt, int threads)
+{
+    const uint64_t s = bwt.size(), ntiles = (s + BWT_HOST_TILE - 1) / BWT_HOST_TILE;
+    std::vector<uint64_t> pre(ntiles), ext(ntiles, 0);
+    parallel_chunks(s, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t i = b + 1;
+        while (i < e && bwt[i] == bwt[b]) i++;
+        pre[b / BWT_HOST_TILE] = i - b;
+    });
+    for (uint64_t t = ntiles - 1; t-- > 0;) {
+        const uint64_t nb = (t + 1) * BWT_HOST_TILE, nlen = s - nb < BWT_HOST_TILE ? s - nb : BWT_HOST_TILE;
+        const sufr::BwtLink k = sufr::bwt_link(bwt[nb - 1], bwt[nb], pre[t + 1], nlen);
+        ext[t] = k.add + k.pass * ext[t + 1];
+    }
+    return ext;
+}
+
+// fn(rank, length) for every run whose head lies in tile [b, e), in ascending rank; nothing beyond the tile is read but the
+// byte in front of it
+template <typename F>
+void bwt_host_tile_runs(const std::vector<uint8_t>& bwt, uint64_t b, uint64_t e, uint64_t ext, F fn)
+{
+    uint64_t head = b;                                   // the head of the run the scan is in; a run that enters from the left is skipped
+    bool mine = b == 0 || bwt[b] != bwt[b - 1];
+    for (uint64_t i = b + 1; i <= e; i++) {
+        if (i < e && bwt[i] == bwt[i - 1]) continue;
+        if (mine) fn(head, sufr::bwt_run_length(head - b, i - b, e - b, ext));
+        head = i; mine = true;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_bwt(const sufr_file* f, uint8_t* bwt, uint64_t* counts, int threads)
+{
+    if (!f) return SUFR_HIP_E_INVALID;
+    if (counts) memset(counts, 0, 256 * sizeof(uint64_t));
+    if (!bwt && !counts) return 0;
+    parallel_chunks(f->meta.len_suffixes, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t hist[256] = {0};
+        bwt_host_range(*f, b, e, bwt, counts ? hist : nullptr);
+        if (counts) for (int c = 0; c < 256; c++) if (hist[c]) __atomic_fetch_add(&counts[c], hist[c], __ATOMIC_RELAXED);      // (sums: any order)
+    });
+    return 0;
+}
+
+int sufr_file_bwt_runs(const sufr_file* f, uint64_t min_len, uint64_t cap, uint64_t* rank, uint64_t* length, uint64_t* symbol, uint64_t* first,
+                       uint64_t* total_out, sufr_bwt_stats* stats, int threads)
+{
+    if (stats) *stats = sufr_bwt_stats{0, 0, 0, 0};
+    if (total_out) *total_out = 0;
+    if (!f) return SUFR_HIP_E_INVALID;
+    const uint64_t s = f->meta.len_suffixes, ntiles = (s + BWT_HOST_TILE - 1) / BWT_HOST_TILE;
+    if (!s) return 0;
+    min_len = sufr::bwt_min_len(min_len);
+    const std::vector<uint8_t> bwt = bwt_host_bytes(*f, threads);
+    const std::vector<uint64_t> ext = bwt_host_carry(bwt, threads);
+    // per tile: the kept heads (then their exclusive scan), the heads, the longest run and its rank
+    std::vector<uint64_t> kept(ntiles + 1, 0), heads(ntiles, 0), b_len(ntiles, 0), b_at(ntiles, 0);
+    parallel_chunks(s, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        const uint64_t t = b / BWT_HOST_TILE;
+        uint64_t n_heads = 0, n_kept = 0, best = 0, best_at = 0;     // (summed here, stored once: neighbouring tiles share cache lines)
+        bwt_host_tile_runs(bwt, b, e, ext[t], [&](uint64_t a, uint64_t len) {
+            n_heads++;
+            if (len >= min_len) n_kept++;
+            if (sufr::rep_better(len, a, best, best_at)) { best = len; best_at = a; }
+        });
+        heads[t] = n_heads; kept[t] = n_kept; b_len[t] = best; b_at[t] = best_at;
+    });
+    sufr_bwt_stats st{0, 0, 0, 0};
+    for (uint64_t t = 0; t < ntiles; t++) {
+        const uint64_t k = kept[t];
+        kept[t] = st.records; st.records += k; st.runs += heads[t];
+        if (sufr::rep_better(b_len[t], b_at[t], st.longest, st.longest_rank)) { st.longest = b_len[t]; st.longest_rank = b_at[t]; }
+    }
+    if (stats) *stats = st;
+    if (total_out) *total_out = st.records;
+    if (st.records > cap) return SUFR_HIP_E_CAPACITY;
+    if (!st.records) return 0;
+    if (!rank || !length || !symbol || !first) return SUFR_HIP_E_INVALID;
+    const int fw = f->meta.index_width;
+    parallel_chunks(s, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        const uint64_t t = b / BWT_HOST_TILE;
+        uint64_t o = kept[t];
+        bwt_host_tile_runs(bwt, b, e, ext[t], [&](uint64_t a, uint64_t len) {
+            if (len < min_len) return;
+            rank[o] = a; length[o] = len; symbol[o] = bwt[a]; first[o] = rdT(f->sa, fw, a);
+            o++;
+        });
+    });
+    return 0;
+}
+
+int sufr_file_lf(const sufr_file* f, void* lf, int threads)
+{
+    if (!f) return SUFR_HIP_E_INVALID;
+    const uint64_t s = f->meta.len_suffixes, ntiles = (s + BWT_HOST_TILE - 1) / BWT_HOST_TILE;
+    if (!s || !lf) return 0;
+    const std::vector<uint8_t> bwt = bwt_host_bytes(*f, threads);
+    // a column per byte value that occurs; tab[t K + col]: the tile's count, then C[c] + the ranks of c before the tile
+    // (a worker counts and ranks in arrays of its own and touches a row of the table once: neighbouring rows share cache lines)
+    uint64_t counts[256] = {0};
+    std::mutex mu;
+    parallel_chunks(s, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t hist[256] = {0};
+        for (uint64_t r = b; r < e; r++) hist[bwt[r]]++;
+        std::lock_guard<std::mutex> g(mu);
+        for (int c = 0; c < 256; c++) counts[c] += hist[c];
+    });
+    uint32_t col[256], K = 0;
+    for (int c = 0; c < 256; c++) col[c] = counts[c] ? K++ : 0;
+    std::vector<uint64_t> tab(ntiles * K, 0);
+    parallel_chunks(s, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t hist[256] = {0};
+        for (uint64_t r = b; r < e; r++) hist[bwt[r]]++;
+        uint64_t* row = tab.data() + b / BWT_HOST_TILE * K;
+        for (int c = 0; c < 256; c++) if (counts[c]) row[col[c]] = hist[c];
+    });
+    uint64_t below = 0;                                  // C[c]
+    for (int c = 0; c < 256; c++) {
+        if (!counts[c]) continue;
+        uint64_t run = below;
+        for (uint64_t t = 0; t < ntiles; t++) { const uint64_t k = tab[t * K + col[c]]; tab[t * K + col[c]] = run; run += k; }
+        below += counts[c];
+    }
+    const int w = f->meta.index_width;
+    parallel_chunks(s, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        const uint64_t* row = tab.data() + b / BWT_HOST_TILE * K;
+        uint64_t next[256];                              // the rank of the next occurrence of every byte value
+        for (int c = 0; c < 256; c++) next[c] = counts[c] ? row[col[c]] : 0;
+        for (uint64_t r = b; r < e; r++) kmer_put(lf, w, r, next[bwt[r]]++);
+    });
+    return 0;
+}
+
+}  // extern "C"

@@ -239,6 +239,12 @@ def _lcp_check(family: str, fn: str, rc: int):
         raise SufrHipError(rc, f"{fn}: " + _LCP_ERRORS[family].get(rc, "failed"))
 
 
+def _bwt_check(fn: str, rc: int):
+    """Raises the SufrHipError of the host call `fn` of include/sufr_bwt.h unless rc is 0 (it has no refusals)."""
+    if rc != 0:
+        raise SufrHipError(rc, f"{fn}: " + {-5: "more records than the arrays hold", -1: "invalid argument"}.get(rc, "failed"))
+
+
 def _address(a):
     """Of a numpy array or a torch tensor, as the library takes it."""
     return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
@@ -630,6 +636,34 @@ class SufrFile:
         _lcp_check("shared", "sufr_file_common", rc)
         return out
 
+    # -- the BWT, its runs and the LF mapping (include/sufr_bwt.h) -------------------------------------------------------
+    def bwt(self, threads: int = 0):
+        """(bwt, counts): the byte in front of every indexed suffix in rank order (cyclic at the text's start) as a uint8
+        array of len_suffixes entries, and how often each of the 256 byte values occurs in it (uint64).  Every file is a valid
+        input."""
+        s = self.len_suffixes
+        out, counts = np.zeros(max(s, 1), dtype=np.uint8), np.zeros(256, dtype=np.uint64)
+        _bwt_check("sufr_file_bwt", lib().sufr_file_bwt(self._h, out.ctypes.data, counts.ctypes.data, threads))
+        return out[:s], counts
+
+    def bwt_runs(self, min_len: int = 1, threads: int = 0):
+        """(rank, length, symbol, first, stats): the maximal runs of equal BWT bytes of at least min_len ranks as four parallel
+        uint64 arrays in ascending rank (first: suffix_array[rank]) and a dict of runs (r, whatever min_len) / records /
+        longest / longest_rank.  One call counts, one fills."""
+        from ._lib import BwtStats
+        st = BwtStats()
+        cols = _counted(4, lambda cap, at, total: lib().sufr_file_bwt_runs(self._h, min_len, cap, *at, C.byref(total), C.byref(st), threads),
+                        _host_columns(4), partial(_bwt_check, "sufr_file_bwt_runs"))
+        return (*cols, st.as_dict())
+
+    def lf(self, threads: int = 0) -> np.ndarray:
+        """LF[r] = C[bwt[r]] + the ranks before r with the same BWT byte: a permutation of the ranks, of the index width.
+        Where every position is indexed and the order is exact, suffix_array[lf[r]] == (suffix_array[r] - 1) % text_len."""
+        s = self.len_suffixes
+        out = np.zeros(max(s, 1), dtype=self._index_dtype())
+        _bwt_check("sufr_file_lf", lib().sufr_file_lf(self._h, out.ctypes.data, threads))
+        return out[:s]
+
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
 
@@ -730,7 +764,7 @@ class DeviceIndex:
         h = C.c_void_p()
         ctx.check(lib().sufr_hip_index_load(ctx.handle, f._h, C.byref(h)))
         ix = cls(ctx, h)
-        ix.text_len = f.text_len
+        ix.text_len, ix.len_suffixes = f.text_len, f.len_suffixes
         assert ix.index_width == f.index_width              # (the file format's rule)
         return ix
 
@@ -751,7 +785,7 @@ class DeviceIndex:
         ctx.check(lib().sufr_hip_index_wrap(ctx.handle, text.data_ptr(), text.numel(), sa.data_ptr(), sa.numel(), flags,
                                             max_query_len, seed_mask.encode() if seed_mask else None, C.byref(h)))
         ix = cls(ctx, h, keep=(text, sa))
-        ix.text_len = text.numel()
+        ix.text_len, ix.len_suffixes = text.numel(), sa.numel()
         # 8 iff the array was taken as 64-bit
         assert ix.index_width == (8 if wide else 4)
         return ix
@@ -1012,6 +1046,41 @@ class DeviceIndex:
         self.ctx.check(lib().sufr_hip_common_device(self.ctx.handle, self._h, lcp.data_ptr(), st_ptr, st_n, out.data_ptr()))
         self.ctx.synchronize()
         return out
+
+    # -- the BWT, its runs and the LF mapping (include/sufr_bwt.h) ------------------------------------------------------
+    def _device(self):
+        import torch
+        return torch.device("cuda", self.ctx.device)
+
+    def bwt_device(self):
+        """SufrFile.bwt on the device: (bwt uint8 CUDA tensor, counts int64 CUDA tensor of 256 entries), complete on return."""
+        import torch
+        s = self.len_suffixes
+        out = torch.empty(max(s, 4), dtype=torch.uint8, device=self._device())
+        counts = torch.empty(256, dtype=torch.int64, device=self._device())
+        self.ctx.check(lib().sufr_hip_bwt_device(self.ctx.handle, self._h, out.data_ptr(), counts.data_ptr()))
+        self.ctx.synchronize()
+        return out[:s], counts
+
+    def bwt_runs_device(self, min_len: int = 1):
+        """SufrFile.bwt_runs on the device: (rank, length, symbol, first) as int64 CUDA tensors and the stats dict, complete on
+        return.  One call counts, one fills."""
+        import torch
+        from ._lib import BwtStats
+        stats = BwtStats()
+        cols = _counted(4, lambda cap, at, total: lib().sufr_hip_bwt_runs_device(self.ctx.handle, self._h, min_len, cap, *at, C.byref(total),
+                                                                                 C.byref(stats)),
+                        lambda n: [torch.empty(n, dtype=torch.int64, device=self._device()) for _ in range(4)], self.ctx.check, self.ctx.synchronize)
+        return (*cols, stats.as_dict())
+
+    def lf_device(self):
+        """SufrFile.lf on the device: a CUDA tensor of the index's width, complete on return and the same bits on every run."""
+        import torch
+        s = self.len_suffixes
+        out = torch.empty(max(s, 1), dtype=torch.int64 if self.index_width == 8 else torch.int32, device=self._device())
+        self.ctx.check(lib().sufr_hip_lf_device(self.ctx.handle, self._h, out.data_ptr()))
+        self.ctx.synchronize()
+        return out[:s]
 
     # -- MEMs (include/sufr_mem.h) -----------------------------------------------------------------------------------
     def mems_device(self, qbytes, offsets, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
