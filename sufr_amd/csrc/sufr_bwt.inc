@@ -10,16 +10,16 @@
 //                  LDS and from there to memory as whole dwords.  A 256-bin histogram of the tile by LDS atomics (counts do
 //                  not depend on the order) goes to the global counts; the tile's run summary (first and last symbol, the
 //                  length of the run at either end) by LDS atomic min / max.
-// k_bwt_carry      one workgroup sweeps the summaries from the last tile to the first, 256 tiles a round (a scan of BwtLink
-//                  by shuffles): ext[t], the ranks beyond tile t that continue its last run.
+// k_bwt_carry      one workgroup sweeps the summaries from the last tile to the first (a backward tile_sweep of BwtLinkOp;
+//                  sufr_scan.inc, DESIGN.md section 10.2): ext[t], the ranks beyond tile t that continue its last run.
 // k_bwt_runs       a workgroup per tile over the BWT bytes: the run heads as ballot words in LDS, the next head of a head by a
 //                  walk over those words, its length by bwt_run_length -- no lane reads beyond its tile.  Counting run: the
 //                  tile's heads, kept heads and longest run.  Writing run: the kept heads' records behind the tile's base (a
 //                  popcount prefix over the kept words).  Between the two, k_locate_scan (sufr_search.inc) turns the kept
-//                  counts into bases and k_lz_best (sufr_lz.inc) the candidates into the stats.
+//                  counts into bases and k_tile_best (sufr_repeat.inc) the candidates into the stats.
 // k_bwt_cols       the 256 counts into C[c] and the column of every byte value that occurs.
 // k_bwt_tile_hist  a workgroup per tile: the counts of the tile, one table column per occurring byte value.
-// k_bwt_col_scan   a workgroup per column: the exclusive scan of the column down the tiles, 256 tiles a round.
+// k_bwt_col_scan   a workgroup per column: the exclusive scan of the column down the tiles, a forward tile_sweep.
 // k_bwt_rank       a workgroup per tile, a wave per quarter of it: the quarters' histograms give every wave its bases in LDS,
 //                  then each wave takes 64 ranks at a time -- the lanes with the same symbol by eight ballots over the symbol
 //                  bits, the rank from the base and the popcount of the lanes below, the base advanced by the group's lowest
@@ -84,39 +84,24 @@ __global__ __launch_bounds__(256) void k_bwt_gather(const T* __restrict__ sa, co
     }
 }
 
+struct BwtLinkOp {
+    using V = BwtLink;
+    static __device__ __forceinline__ V identity() { return BwtLink{0, 1}; }
+    static __device__ __forceinline__ V combine(const V& near, const V& far) { return bwt_chain(near, far); }
+};
+
 // ext[t]: the ranks beyond the end of tile t that continue its last run
-__global__ __launch_bounds__(256) void k_bwt_carry(const BwtTile* __restrict__ sums, uint64_t ntiles, uint32_t tile, uint64_t s, uint64_t* __restrict__ ext)
+__global__ __launch_bounds__(1024) void k_bwt_carry(const BwtTile* __restrict__ sums, uint64_t ntiles, uint32_t tile, uint64_t s, uint64_t* __restrict__ ext)
 {
-    __shared__ uint64_t s_a[4], s_p[4], s_x;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint64_t carry = 0;                                  // ext of the tile right of this round's (the last tile's link passes nothing)
-    for (uint64_t hi = ntiles; hi > 0;) {                // a round: tiles [hi - cnt, hi), lane i takes tile hi - 1 - i
-        const uint32_t cnt = (uint32_t)(hi < 256 ? hi : 256);
-        const bool act = threadIdx.x < cnt;
-        const uint64_t t = hi - 1 - (act ? threadIdx.x : 0);
-        BwtLink f{0, 0};
-        if (act && t + 1 < ntiles) {
-            const BwtTile cur = sums[t], nx = sums[t + 1];
-            const uint64_t nb = (t + 1) * tile;
-            f = bwt_link(cur.syms >> 8, nx.syms & 255u, nx.pre, s - nb < tile ? s - nb : tile);
-        }
-        // inclusive scan in lane order: f becomes the link from the round's carry to this lane's ext
-        for (int o = 1; o < 64; o <<= 1) {
-            const BwtLink far{__shfl_up(f.add, o), __shfl_up(f.pass, o)};
-            if (lane >= (uint32_t)o) f = bwt_chain(f, far);
-        }
-        if (lane == 63) { s_a[w] = f.add; s_p[w] = f.pass; }
-        __syncthreads();
-        uint64_t x = carry;
-        for (uint32_t k = 0; k < w; k++) x = s_a[k] + s_p[k] * x;
-        x = f.add + f.pass * x;
-        if (act) ext[t] = x;
-        if (threadIdx.x == cnt - 1) s_x = x;
-        __syncthreads();
-        carry = s_x;
-        hi -= cnt;
-        __syncthreads();                                 // (s_a, s_p and s_x are the next round's)
-    }
+    __shared__ BwtLink s_l[16];
+    // the link of tile t: what tile t + 1 gives its open run (behind the last tile there is nothing: ext = 0 passes through)
+    const auto link = [&](uint64_t t) {
+        if (t + 1 >= ntiles) return BwtLinkOp::identity();
+        const BwtTile cur = sums[t], nx = sums[t + 1];
+        const uint64_t nb = (t + 1) * tile;
+        return bwt_link(cur.syms >> 8, nx.syms & 255u, nx.pre, s - nb < tile ? s - nb : tile);
+    };
+    tile_sweep<BwtLinkOp, true>(ntiles, link, [&](uint64_t t, const BwtLink& own, const BwtLink& after) { ext[t] = bwt_chain(own, after).add; }, s_l);
 }
 
 // WRITE false: t_cnt[t] = the kept heads of tile t, t_stat[3 t ..] = {heads, longest, longest_rank} of the runs that start in
@@ -128,7 +113,9 @@ __global__ __launch_bounds__(256) void k_bwt_runs(const T* __restrict__ sa, cons
                                                   uint64_t* __restrict__ o_sym, uint64_t* __restrict__ o_first)
 {
     __shared__ uint32_t s_w[BWT_TILE_MAX / 4];
-    __shared__ uint64_t s_hd[BWT_TILE_MAX / 64], s_kp[BWT_TILE_MAX / 64], s_pf[BWT_TILE_MAX / 64], s_sc[4], s_b4[4][4];
+    using Stat = SumBestOp<2>;
+    __shared__ uint64_t s_hd[BWT_TILE_MAX / 64], s_kp[BWT_TILE_MAX / 64], s_pf[BWT_TILE_MAX / 64], s_sc[4];
+    __shared__ Stat::V s_b4[4];
     const uint8_t* s_b = (const uint8_t*)s_w;
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(256) void k_bwt_runs(const T* __restrict__ sa, cons
             if (lane == 0) s_hd[(it >> 6) + w] = m;
         }
         __syncthreads();
-        uint64_t heads = 0, kept = 0, b_len = 0, b_at = 0;
+        Stat::V b = Stat::identity();                    // {heads, kept heads, longest, longest_rank}
         // the length of the run whose head is at i
         auto run_length = [&](uint32_t i) {
             uint32_t word = i >> 6;
@@ -158,29 +145,16 @@ __global__ __launch_bounds__(256) void k_bwt_runs(const T* __restrict__ sa, cons
             uint64_t l = 0;
             if (head) {
                 l = run_length(i);
-                heads++;
-                if (rep_better(l, base + i, b_len, b_at)) { b_len = l; b_at = base + i; }      // (a lane's ranks ascend: ties keep the first)
+                b.sum[0]++;
+                if (rep_better(l, base + i, b.len, b.at)) { b.len = l; b.at = base + i; }      // (a lane's ranks ascend: ties keep the first)
             }
             const uint64_t m = __ballot(head && l >= min_len);
             if (WRITE) { if (lane == 0) s_kp[(it >> 6) + w] = m; }
-            else if (lane == 0) kept += (uint64_t)__builtin_popcountll(m);
+            else if (lane == 0) b.sum[1] += (uint64_t)__builtin_popcountll(m);
         }
         if (!WRITE) {
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint64_t l2 = __shfl_down(b_len, o), a2 = __shfl_down(b_at, o);
-                heads += __shfl_down(heads, o);
-                kept += __shfl_down(kept, o);
-                if (rep_better(l2, a2, b_len, b_at)) { b_len = l2; b_at = a2; }
-            }
-            if (lane == 0) { s_b4[w][0] = heads; s_b4[w][1] = kept; s_b4[w][2] = b_len; s_b4[w][3] = b_at; }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                for (uint32_t k = 1; k < 4; k++) {
-                    heads += s_b4[k][0]; kept += s_b4[k][1];
-                    if (rep_better(s_b4[k][2], s_b4[k][3], b_len, b_at)) { b_len = s_b4[k][2]; b_at = s_b4[k][3]; }
-                }
-                t_cnt[t] = kept; t_stat[3 * t] = heads; t_stat[3 * t + 1] = b_len; t_stat[3 * t + 2] = b_at;
-            }
+            b = wg_reduce_op<Stat, 4>(b, s_b4);
+            if (threadIdx.x == 0) { t_cnt[t] = b.sum[1]; t_stat[3 * t] = b.sum[0]; t_stat[3 * t + 1] = b.len; t_stat[3 * t + 2] = b.at; }
         } else {
             __syncthreads();
             uint64_t v[1] = {threadIdx.x < nwords ? (uint64_t)__builtin_popcountll(s_kp[threadIdx.x]) : 0}, tot[1];
@@ -233,17 +207,12 @@ __global__ __launch_bounds__(256) void k_bwt_tile_hist(const uint8_t* __restrict
 }
 
 // column blockIdx.x of tab, in place: the exclusive scan down the tiles
-__global__ __launch_bounds__(256) void k_bwt_col_scan(uint64_t* __restrict__ tab, uint64_t ntiles, uint32_t K)
+__global__ __launch_bounds__(1024) void k_bwt_col_scan(uint64_t* __restrict__ tab, uint64_t ntiles, uint32_t K)
 {
-    __shared__ uint64_t s_sc[4];
-    uint64_t carry = 0;
-    for (uint64_t t0 = 0; t0 < ntiles; t0 += 256) {
-        const uint64_t t = t0 + threadIdx.x;
-        uint64_t v[1] = {t < ntiles ? tab[t * K + blockIdx.x] : 0}, tot[1];
-        wg_scan(v, tot, s_sc);
-        if (t < ntiles) tab[t * K + blockIdx.x] = carry + v[0];
-        carry += tot[0];
-    }
+    __shared__ uint64_t s_sc[16];
+    uint64_t* col = tab + blockIdx.x;
+    tile_sweep<SumOp<uint64_t>, false>(
+        ntiles, [&](uint64_t t) { return col[t * K]; }, [&](uint64_t t, uint64_t, uint64_t before) { col[t * K] = before; }, s_sc);
 }
 
 // lf[r] = C[c] + the ranks before r with the symbol c of r: cbase, the tile's row of tab, the quarters before r's and the
@@ -327,15 +296,15 @@ int bwt_runs_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t min_len, 
     uint64_t *t_cnt = ext + ntiles, *d_total = t_cnt + ntiles, *t_stat = d_total + 1, *d_stats = t_stat + 3 * ntiles;
     sufr::BwtTile* sums = (sufr::BwtTile*)(d_stats + 4);
     bwt_gather<T>(ctx, ix, bwt, nullptr, sums);
-    hipLaunchKernelGGL(sufr::k_bwt_carry, dim3(1), dim3(256), 0, pl.stream, (const sufr::BwtTile*)sums, ntiles, tile, s, ext);
+    hipLaunchKernelGGL(sufr::k_bwt_carry, dim3(1), dim3(1024), 0, pl.stream, (const sufr::BwtTile*)sums, ntiles, tile, s, ext);
     const uint64_t wgs = batch_grid(pl);
     const uint32_t grid = (uint32_t)(ntiles < wgs ? ntiles : wgs);
     const T* sa = index_sa<T>(ix);
     hipLaunchKernelGGL((sufr::k_bwt_runs<T, false>), dim3(grid), dim3(256), 0, pl.stream, sa, (const uint8_t*)bwt, s, tile, ntiles, (const uint64_t*)ext,
                        min_len, t_cnt, t_stat, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
     hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, t_cnt, ntiles, d_total);
-    // k_lz_best: {the total, the sum of the first column, the best (length, rank)} = {records, runs, longest, longest_rank}
-    hipLaunchKernelGGL(sufr::k_lz_best, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)t_stat, ntiles, (const uint64_t*)d_total, d_stats);
+    // {the total, the sum of the first column, the best (length, rank)} = {records, runs, longest, longest_rank}
+    hipLaunchKernelGGL(sufr::k_tile_best<sufr::SumBestOp<1>>, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)t_stat, ntiles, (const uint64_t*)d_total, d_stats);
     unsigned long long h[4];
     rc = report_total(pl, "bwt_runs", "records", d_stats, 4, h, cap, total_out, d_rank && d_length && d_symbol && d_first);
     if (stats_out) *stats_out = sufr_bwt_stats{h[1], h[0], h[2], h[3]};
@@ -371,7 +340,7 @@ int bwt_lf_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, T* lf)
     const uint32_t grid = (uint32_t)(ntiles < wgs ? ntiles : wgs);
     hipLaunchKernelGGL(sufr::k_bwt_cols, dim3(1), dim3(256), 0, pl.stream, (const unsigned long long*)counts, cbase, col);
     hipLaunchKernelGGL(sufr::k_bwt_tile_hist, dim3(grid), dim3(256), 0, pl.stream, (const uint8_t*)bwt, s, tile, ntiles, (const uint32_t*)col, K, tab);
-    hipLaunchKernelGGL(sufr::k_bwt_col_scan, dim3(K), dim3(256), 0, pl.stream, tab, ntiles, K);
+    hipLaunchKernelGGL(sufr::k_bwt_col_scan, dim3(K), dim3(1024), 0, pl.stream, tab, ntiles, K);
     hipLaunchKernelGGL(sufr::k_bwt_rank<T>, dim3(grid), dim3(256), 0, pl.stream, (const uint8_t*)bwt, s, tile, ntiles, (const uint64_t*)cbase,
                        (const uint32_t*)col, K, (const uint64_t*)tab, lf);
     return launch_status(pl, "lf");

@@ -2989,6 +2989,7 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_exc.inc"
 #include "sufr_capi.inc"
 #include "../../include/sufr_query.h"
+#include "sufr_scan.inc"
 #include "sufr_search.inc"
 #include "../../include/sufr_match.h"
 #include "sufr_match.inc"

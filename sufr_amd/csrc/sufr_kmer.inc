@@ -6,13 +6,13 @@
 // carries, the count of one rank of a 64-rank word -- is sufr_kmer_scan.h, which the host path and tests/kmer_shim.cpp
 // compile too; this file only moves the data.
 //
+// The scans and the sweep are those of sufr_scan.inc (DESIGN.md section 10.2) over KmerOp.
 // k_kmer_fold    one pass over SA and LCP.  A wave takes 64 consecutive ranks: head = (r == 0 or LCP[r] < k), whole =
 //                (brk(SA[r]) - SA[r] >= k, a binary search of the sequence starts), two __ballot words per wave, stored
-//                (s / 4 bytes in all).  A tile is up to 256 words, one per lane: their summaries are combined over the
-//                workgroup (kmer_wg_scan: shuffles inside a wave, 4 wave sums through LDS) into one summary per tile.
-// k_kmer_carry   one workgroup of 1024 lanes over the tile summaries, in both directions, like k_locate_scan over its sums:
-//                carry_in[t] = whole ranks of the interval open at the start of tile t, carry_out[t] = whole ranks after its
-//                end up to the next head.
+//                (s / 4 bytes in all).  A tile is up to 256 words, one per lane: the total of wg_scan_op over their
+//                summaries is the tile's.
+// k_kmer_carry   two tile_sweeps over the tile summaries: forward, carry_in[t] = whole ranks of the interval open at the
+//                start of tile t; backward, carry_out[t] = whole ranks after its end up to the next head.
 // k_kmer_apply   one pass over the words (no SA, no LCP).  The same workgroup scan gives every word its carries; after that
 //                a rank's count is bit arithmetic on the two words of its wave.  occ goes out by rank, or through SA into a
 //                zeroed by-position buffer (non-zero values only).  Every interval is credited once, by the lane of its
@@ -31,42 +31,19 @@ static constexpr uint32_t KMER_LDS_BINS = 1024;         // histogram bins a work
 
 struct KmerSeqs { const uint64_t* starts; uint64_t num, n; };
 
-struct KmerScan { KmerSum before, after, total; };      // the lanes before / after this one in the workgroup, and all of them
-
-// s_k: 12 words of LDS, free again on return
-__device__ __forceinline__ KmerScan kmer_wg_scan(const KmerSum& mine, uint64_t* s_k)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    KmerSum f = mine, b = mine;                         // inclusive: lanes 0 .. lane, lanes lane .. 63
-    for (int o = 1; o < 64; o <<= 1) {
-        const KmerSum u{__shfl_up(f.pre, o), __shfl_up(f.post, o), __shfl_up(f.has, o)};
-        if (lane >= (uint32_t)o) f = kmer_combine(u, f);
-        const KmerSum d{__shfl_down(b.pre, o), __shfl_down(b.post, o), __shfl_down(b.has, o)};
-        if (lane + (uint32_t)o < 64u) b = kmer_combine(b, d);
-    }
-    if (lane == 63) { s_k[w] = f.pre; s_k[4 + w] = f.post; s_k[8 + w] = f.has; }
-    KmerSum fe{__shfl_up(f.pre, 1), __shfl_up(f.post, 1), __shfl_up(f.has, 1)};
-    KmerSum be{__shfl_down(b.pre, 1), __shfl_down(b.post, 1), __shfl_down(b.has, 1)};
-    if (lane == 0) fe = kmer_identity();
-    if (lane == 63) be = kmer_identity();
-    __syncthreads();
-    KmerSum pw = kmer_identity(), sw = kmer_identity(), tot = kmer_identity();
-    for (uint32_t k = 0; k < 4; k++) {
-        const KmerSum t{s_k[k], s_k[4 + k], (uint32_t)s_k[8 + k]};
-        if (k < w) pw = kmer_combine(pw, t);
-        if (k > w) sw = kmer_combine(sw, t);
-        tot = kmer_combine(tot, t);
-    }
-    __syncthreads();                                    // (s_k is reused by the next tile)
-    return KmerScan{kmer_combine(pw, fe), kmer_combine(be, sw), tot};
-}
+struct KmerOp {
+    using V = KmerSum;
+    static __device__ __forceinline__ V identity() { return kmer_identity(); }
+    static __device__ __forceinline__ V combine(const V& a, const V& b) { return kmer_combine(a, b); }
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_kmer_fold(const T* __restrict__ sa, const T* __restrict__ lcp, uint64_t s, KmerSeqs q, uint64_t k,
                                                    uint32_t tile, uint64_t ntiles, uint64_t* __restrict__ hbits, uint64_t* __restrict__ wbits,
                                                    uint64_t* __restrict__ t_pre, uint64_t* __restrict__ t_post, uint64_t* __restrict__ t_has)
 {
-    __shared__ uint64_t s_h[256], s_w[256], s_k[12];
+    __shared__ uint64_t s_h[256], s_w[256];
+    __shared__ KmerSum s_k[4];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = tile >> 6;      // (tile: a multiple of 256)
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         for (uint32_t j = w; j < nw; j += 4) {
@@ -81,7 +58,7 @@ __global__ __launch_bounds__(256) void k_kmer_fold(const T* __restrict__ sa, con
         }
         __syncthreads();
         const KmerSum mine = threadIdx.x < nw ? kmer_word_sum(s_h[threadIdx.x], s_w[threadIdx.x]) : kmer_identity();
-        const KmerScan sc = kmer_wg_scan(mine, s_k);
+        const WgScan<KmerSum> sc = wg_scan_op<KmerOp, 4>(mine, s_k);
         if (threadIdx.x == 0) { t_pre[t] = sc.total.pre; t_post[t] = sc.total.post; t_has[t] = sc.total.has; }
     }
 }
@@ -90,44 +67,10 @@ __global__ __launch_bounds__(1024) void k_kmer_carry(const uint64_t* __restrict_
                                                      const uint64_t* __restrict__ t_has, uint64_t ntiles, uint64_t* __restrict__ cin,
                                                      uint64_t* __restrict__ cout)
 {
-    __shared__ uint64_t s_pre[1024], s_post[1024];
-    __shared__ uint32_t s_has[1024];
-    const uint32_t i = threadIdx.x;
-    const uint64_t per = (ntiles + 1023) / 1024, b0 = (uint64_t)i * per < ntiles ? (uint64_t)i * per : ntiles,
-                   b1 = b0 + per < ntiles ? b0 + per : ntiles;
-    KmerSum mine = kmer_identity();
-    for (uint64_t b = b0; b < b1; b++) mine = kmer_combine(mine, KmerSum{t_pre[b], t_post[b], (uint32_t)t_has[b]});
-    // the lanes before this one ...
-    s_pre[i] = mine.pre; s_post[i] = mine.post; s_has[i] = mine.has;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {
-        KmerSum v{s_pre[i], s_post[i], s_has[i]};
-        if (i >= o) v = kmer_combine(KmerSum{s_pre[i - o], s_post[i - o], s_has[i - o]}, v);
-        __syncthreads();
-        s_pre[i] = v.pre; s_post[i] = v.post; s_has[i] = v.has;
-        __syncthreads();
-    }
-    KmerSum run = i ? KmerSum{s_pre[i - 1], s_post[i - 1], s_has[i - 1]} : kmer_identity();
-    __syncthreads();
-    for (uint64_t b = b0; b < b1; b++) {
-        cin[b] = kmer_carry_in(run, 0);
-        run = kmer_combine(run, KmerSum{t_pre[b], t_post[b], (uint32_t)t_has[b]});
-    }
-    // ... and the lanes after it
-    s_pre[i] = mine.pre; s_post[i] = mine.post; s_has[i] = mine.has;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {
-        KmerSum v{s_pre[i], s_post[i], s_has[i]};
-        if (i + o < 1024) v = kmer_combine(v, KmerSum{s_pre[i + o], s_post[i + o], s_has[i + o]});
-        __syncthreads();
-        s_pre[i] = v.pre; s_post[i] = v.post; s_has[i] = v.has;
-        __syncthreads();
-    }
-    run = i < 1023 ? KmerSum{s_pre[i + 1], s_post[i + 1], s_has[i + 1]} : kmer_identity();
-    for (uint64_t b = b1; b > b0; b--) {
-        cout[b - 1] = kmer_carry_out(run, 0);
-        run = kmer_combine(KmerSum{t_pre[b - 1], t_post[b - 1], (uint32_t)t_has[b - 1]}, run);
-    }
+    __shared__ KmerSum s_k[16];
+    const auto load = [&](uint64_t t) { return KmerSum{t_pre[t], t_post[t], (uint32_t)t_has[t]}; };
+    tile_sweep<KmerOp, false>(ntiles, load, [&](uint64_t t, const KmerSum&, const KmerSum& before) { cin[t] = kmer_carry_in(before, 0); }, s_k);
+    tile_sweep<KmerOp, true>(ntiles, load, [&](uint64_t t, const KmerSum&, const KmerSum& after) { cout[t] = kmer_carry_out(after, 0); }, s_k);
 }
 
 // stats: whole, distinct, unique, max_count
@@ -138,7 +81,8 @@ __global__ __launch_bounds__(256) void k_kmer_apply(const T* __restrict__ sa, ui
                                                     T* __restrict__ occ, uint32_t by_position, uint64_t bins,
                                                     unsigned long long* __restrict__ hist, unsigned long long* __restrict__ stats)
 {
-    __shared__ uint64_t s_h[256], s_w[256], s_ci[256], s_co[256], s_k[12];
+    __shared__ uint64_t s_h[256], s_w[256], s_ci[256], s_co[256];
+    __shared__ KmerSum s_k[4];
     __shared__ unsigned long long s_bins[KMER_LDS_BINS];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, nw = tile >> 6;
     const bool private_bins = hist && bins <= KMER_LDS_BINS;
@@ -149,7 +93,7 @@ __global__ __launch_bounds__(256) void k_kmer_apply(const T* __restrict__ sa, ui
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         uint64_t H = 0, W = 0;
         if (threadIdx.x < nw) { H = hbits[t * nw + threadIdx.x]; W = wbits[t * nw + threadIdx.x]; }
-        const KmerScan sc = kmer_wg_scan(threadIdx.x < nw ? kmer_word_sum(H, W) : kmer_identity(), s_k);
+        const WgScan<KmerSum> sc = wg_scan_op<KmerOp, 4, true>(threadIdx.x < nw ? kmer_word_sum(H, W) : kmer_identity(), s_k);
         s_h[threadIdx.x] = H; s_w[threadIdx.x] = W;
         s_ci[threadIdx.x] = kmer_carry_in(sc.before, cin[t]);
         s_co[threadIdx.x] = kmer_carry_out(sc.after, cout[t]);

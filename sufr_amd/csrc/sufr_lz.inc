@@ -27,8 +27,9 @@
 //                (entry k is written after entry k was read: k never runs ahead of the chain), then a lane per factor.
 //                Counting run: the tile's literals and its longest factor.  Writing run: (start, length, source) behind the
 //                tile's base, in text order.
-// k_lz_best      one workgroup: the stats from the tiles' candidates by comparisons of (length, start); no atomics.  (Not
-//                k_rep_best: it sums a column and has three.)  The host tail of the counted call is report_total.
+// k_tile_best    (sufr_repeat.inc, over SumBestOp<1>) one workgroup: the stats from the tiles' candidates -- the sum of the
+//                literals, the best (length, start); no atomics.  The tail of k_lz_emit is wg_reduce_op over the same
+//                operator (sufr_scan.inc, DESIGN.md section 10.2).  The host tail of the counted call is report_total.
 // No scratch; LDS: k_lz_lpf 16.5 KB (32-bit arrays) or 33 KB (64-bit), k_lz_table 64 KB, k_lz_emit 32 KB.
 
 #include "sufr_lz_scan.h"
@@ -153,8 +154,8 @@ __global__ __launch_bounds__(256) void k_lz_emit(const T* __restrict__ lpf, cons
 {
     __shared__ uint16_t s_st[LZ_TILE_MAX];
     __shared__ uint32_t s_cnt;
-    __shared__ uint64_t s_b[4][3];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    using Stat = SumBestOp<1>;
+    __shared__ Stat::V s_b[4];
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const uint32_t e0 = t_entry[t];                  // (uniform)
         if (e0 == LZ_NO_ENTRY) {
@@ -180,56 +181,21 @@ __global__ __launch_bounds__(256) void k_lz_emit(const T* __restrict__ lpf, cons
         __syncthreads();
         const uint32_t cnt = s_cnt;
         const uint64_t out = t_base[t];
-        uint64_t lit = 0, b_len = 0, b_at = 0;
+        Stat::V b = Stat::identity();                    // {literals, longest, longest_start}
         for (uint32_t k = threadIdx.x; k < cnt; k += 256) {
             const uint64_t p = base + s_st[k], l = (uint64_t)lpf[p];
             if (WRITE) { o_start[out + k] = p; o_len[out + k] = lz_step(l); o_src[out + k] = l ? (uint64_t)src[p] : LZ_NONE; }
             else {
-                if (!l) lit++;
-                if (lz_step(l) > b_len) { b_len = lz_step(l); b_at = p; }      // (a lane's positions ascend: ties keep the first)
+                if (!l) b.sum[0]++;
+                if (lz_step(l) > b.len) { b.len = lz_step(l); b.at = p; }      // (a lane's positions ascend: ties keep the first)
             }
         }
         if (!WRITE) {
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint64_t l2 = __shfl_down(b_len, o), a2 = __shfl_down(b_at, o);
-                lit += __shfl_down(lit, o);
-                if (rep_better(l2, a2, b_len, b_at)) { b_len = l2; b_at = a2; }
-            }
-            if (lane == 0) { s_b[w][0] = lit; s_b[w][1] = b_len; s_b[w][2] = b_at; }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                for (uint32_t k = 1; k < 4; k++) {
-                    lit += s_b[k][0];
-                    if (rep_better(s_b[k][1], s_b[k][2], b_len, b_at)) { b_len = s_b[k][1]; b_at = s_b[k][2]; }
-                }
-                t_stat[3 * t] = lit; t_stat[3 * t + 1] = b_len; t_stat[3 * t + 2] = b_at;
-            }
+            b = wg_reduce_op<Stat, 4>(b, s_b);
+            if (threadIdx.x == 0) Stat::stats(t_stat + 3 * t, b);
         }
-        __syncthreads();                                 // (s_st, s_cnt and s_b are the next tile's)
+        __syncthreads();                                 // (s_st and s_cnt are the next tile's)
     }
-}
-
-// stats = {factors, literals, longest, longest_start}
-__global__ __launch_bounds__(1024) void k_lz_best(const uint64_t* __restrict__ t_stat, uint64_t ntiles, const uint64_t* __restrict__ total,
-                                                  uint64_t* __restrict__ stats)
-{
-    __shared__ uint64_t s_c[1024], s_l[1024], s_a[1024];
-    const uint32_t i = threadIdx.x;
-    uint64_t lit = 0, b_len = 0, b_at = 0;
-    for (uint64_t t = i; t < ntiles; t += 1024) {
-        lit += t_stat[3 * t];
-        if (rep_better(t_stat[3 * t + 1], t_stat[3 * t + 2], b_len, b_at)) { b_len = t_stat[3 * t + 1]; b_at = t_stat[3 * t + 2]; }
-    }
-    s_c[i] = lit; s_l[i] = b_len; s_a[i] = b_at;
-    __syncthreads();
-    for (uint32_t o = 512; o > 0; o >>= 1) {
-        if (i < o) {
-            s_c[i] += s_c[i + o];
-            if (rep_better(s_l[i + o], s_a[i + o], s_l[i], s_a[i])) { s_l[i] = s_l[i + o]; s_a[i] = s_a[i + o]; }
-        }
-        __syncthreads();
-    }
-    if (i == 0) { stats[0] = *total; stats[1] = s_c[0]; stats[2] = s_l[0]; stats[3] = s_a[0]; }
 }
 
 }  // namespace sufr
@@ -303,7 +269,7 @@ int lz_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_lcp, const
 #endif
     hipLaunchKernelGGL((sufr::k_lz_emit<T, false>), dim3(grid), dim3(256), 0, pl.stream, (const T*)lpf, (const T*)src, n, B, ntiles,
                        (const uint32_t*)t_entry, (const uint64_t*)t_base, t_stat, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(sufr::k_lz_best, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)t_stat, ntiles, (const uint64_t*)d_total, d_stats);
+    hipLaunchKernelGGL(sufr::k_tile_best<sufr::SumBestOp<1>>, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)t_stat, ntiles, (const uint64_t*)d_total, d_stats);
     unsigned long long h[4];
     rc = report_total(pl, "lz", "factors", d_stats, 4, h, cap, total_out, d_start && d_length && d_source);
 #ifdef SUFR_HIP_PROBES

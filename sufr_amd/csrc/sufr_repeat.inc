@@ -22,17 +22,18 @@
 //                to 4096 ranks of the tile, and their level-1 entries, are staged in LDS and searched there first
 //                (RepStaged::stage over rep_tile_window); a search that leaves the window reads the pyramid in memory and
 //                descends again.  REP_COUNT: kept ranks per tile and the tile's RepBest (longest / largest count / largest
-//                seqs), reduced over lanes, waves and the workgroup by RepBest::merge.  REP_WRITE: the same decisions,
+//                seqs), reduced over the workgroup by wg_reduce_op over RepBestOp.  REP_WRITE: the same decisions,
 //                compacted in rank order behind the tile's base.  REP_PROFILE (SEQS only): an atomic max per interval that
 //                raises its entry.  The cost of a rank is bounded by 2 x 64 x levels reads per search whatever b - a is; only
 //                the supermaximal walk (rep_supermaximal) is longer, and says when.
-// k_rep_best     <NCOL> one workgroup: the stats from the tiles' candidates by RepBest::merge -- comparisons of (length,
-//                representative), no atomics, so nothing depends on an order.
+// k_tile_best    <Op> one workgroup: the stats from the tiles' candidates by tile_reduce -- RepBestOp<4 or 5> here,
+//                SumBestOp<1> for sufr_lz.inc and sufr_bwt.inc.
+// The scans and reductions are those of sufr_scan.inc (DESIGN.md section 10.2).
 // A workgroup takes tiles t = blockIdx.x, blockIdx.x + gridDim.x, ...; no scratch; k_rep_find holds 16.4 KB of LDS (32-bit
-// arrays) or 32.7 KB (64-bit) without SEQS, 16.8 / 33.5 KB with it; k_rep_best 32 KB (4 columns) or 40 KB (5).
+// arrays) or 32.7 KB (64-bit) without SEQS, 16.8 / 33.5 KB with it; k_tile_best 16 candidates.
 // Host: repeats_prepare (the fold, the scans, the levels: RepPrep, which also owns the scratch of the find pass) and
-// repeats_find<T, SEQS> (counting launch, k_locate_scan, k_rep_best, report_total, writing launch), which sufr_shared.inc calls
-// with SEQS set.
+// repeats_find<T, SEQS> (counting launch, k_locate_scan, k_tile_best, report_total, writing launch), which sufr_shared.inc
+// calls with SEQS set.
 
 #include "sufr_repeat_scan.h"
 #include "sufr_shared_scan.h"
@@ -94,21 +95,6 @@ struct RepStaged {
 
 struct RepBits { const uint64_t *dw, *dp, *sw, *sp; };   // "differs" words and prefix, "sequence start" words and prefix
 
-// exclusive prefix of x over the 256 lanes of a workgroup and its total; s_w: 4 words of LDS, free again on return
-__device__ __forceinline__ uint32_t rep_wg_exscan(uint32_t x, uint32_t* s_w, uint32_t& total)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t inc = x;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += u; }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-    for (uint32_t k = 0; k < 4; k++) { const uint32_t t = s_w[k]; if (k < w) base += t; total += t; }
-    __syncthreads();
-    return base + inc - x;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void k_rep_fold(const T* __restrict__ sa, const T* __restrict__ lcp, const uint8_t* __restrict__ text,
                                                   uint64_t s, KmerSeqs q, uint32_t tile, uint64_t ntiles, T* __restrict__ ell,
@@ -153,11 +139,10 @@ __global__ __launch_bounds__(256) void k_rep_fold(const T* __restrict__ sa, cons
             }
         }
         __syncthreads();
-        uint32_t td, ts;
         const uint32_t cd = threadIdx.x < nw ? s_pd[threadIdx.x] : 0, cs = threadIdx.x < nw ? s_ps[threadIdx.x] : 0;
-        const uint32_t ed = rep_wg_exscan(cd, s_w, td), es = rep_wg_exscan(cs, s_w, ts);
-        if (threadIdx.x < nw) { dp[t * nw + threadIdx.x] = ed; sp[t * nw + threadIdx.x] = es; }
-        if (threadIdx.x == 0) { t_d[t] = td; t_s[t] = ts; }
+        const WgScan<uint32_t> d = wg_scan_op<SumOp<uint32_t>, 4>(cd, s_w), e = wg_scan_op<SumOp<uint32_t>, 4>(cs, s_w);
+        if (threadIdx.x < nw) { dp[t * nw + threadIdx.x] = d.before; sp[t * nw + threadIdx.x] = e.before; }
+        if (threadIdx.x == 0) { t_d[t] = d.total; t_s[t] = e.total; }
     }
 }
 
@@ -200,6 +185,49 @@ __device__ __forceinline__ void rep_best_put(uint64_t* p, const RepBest& b, uint
     if (NCOL > 4) p[4 * stride] = b.seq;
 }
 
+// RepBest::merge over the NCOL words of a candidate (commutative: sufr_repeat_scan.h).  get / stats: what k_tile_best reads
+// of a tile and writes behind the total -- {longest, longest_rank, max_count (, max_seqs)}
+template <int NCOL>
+struct RepBestOp {
+    static constexpr int COLS = NCOL;
+    struct V { uint64_t c[NCOL]; };
+    static __device__ __forceinline__ V make(const RepBest& b) { V v; rep_best_put<NCOL>(v.c, b); return v; }
+    static __device__ __forceinline__ V identity() { return make(RepBest{0, 0, 0, 0, 0}); }
+    static __device__ __forceinline__ V combine(const V& a, const V& b)
+    {
+        RepBest x = rep_best_get<NCOL>(a.c);
+        x.merge(rep_best_get<NCOL>(b.c));
+        return make(x);
+    }
+    static __device__ __forceinline__ V get(const uint64_t* p) { return make(rep_best_get<NCOL>(p)); }
+    static __device__ __forceinline__ void stats(uint64_t* out, const V& v)
+    {
+        out[0] = v.c[0]; out[1] = v.c[2]; out[2] = v.c[3];
+        if (NCOL > 4) out[3] = v.c[4];
+    }
+};
+
+// NSUM sums and the best (length, at) by rep_better: longer wins, ties go to the smaller `at` -- a total order on the
+// candidates of length > 0.  rep_better never prefers a length of 0, so between two values of length 0 combine keeps the
+// left one's `at`: the operator is commutative as long as every value of length 0 carries at = 0, like the identity.  The
+// lane loops of k_lz_emit and k_bwt_runs set `at` only together with a length > 0, so that holds for them and for the
+// tiles they write.  The tails of those two kernels, and with one sum their candidates per tile.
+template <int NSUM>
+struct SumBestOp {
+    static constexpr int COLS = NSUM + 2;
+    struct V { uint64_t sum[NSUM], len, at; };
+    static __device__ __forceinline__ V identity() { V v; for (int n = 0; n < NSUM; n++) v.sum[n] = 0; v.len = v.at = 0; return v; }
+    static __device__ __forceinline__ V combine(const V& a, const V& b)
+    {
+        V v = a;
+        for (int n = 0; n < NSUM; n++) v.sum[n] += b.sum[n];
+        if (rep_better(b.len, b.at, a.len, a.at)) { v.len = b.len; v.at = b.at; }
+        return v;
+    }
+    static __device__ __forceinline__ V get(const uint64_t* p) { V v; for (int n = 0; n < NSUM; n++) v.sum[n] = p[n]; v.len = p[NSUM]; v.at = p[NSUM + 1]; return v; }
+    static __device__ __forceinline__ void stats(uint64_t* out, const V& v) { for (int n = 0; n < NSUM; n++) out[n] = v.sum[n]; out[NSUM] = v.len; out[NSUM + 1] = v.at; }
+};
+
 // The find pass of repeats (SEQS false: 4 columns; P, o_seqs, best and the seqs filter are not looked at) and of shared and
 // common (SEQS true: 5 columns; seqs from two reads of P, then its filter).
 // REP_COUNT: t_cnt[t] = kept ranks of tile t, t_best[NCOL t ..] = the tile's RepBest.  REP_WRITE: t_cnt[t] is the tile's
@@ -214,11 +242,11 @@ __global__ __launch_bounds__(256) void k_rep_find(RepAcc<T> gacc, const uint8_t*
 {
     static_assert(MODE != REP_PROFILE || SEQS, "the profile is one of sequence counts");
     constexpr int NCOL = SEQS ? 5 : 4;
+    using Best = RepBestOp<NCOL>;
     __shared__ uint32_t s_w[4];
-    __shared__ uint64_t s_b[4][NCOL];
+    __shared__ typename Best::V s_b[4];
     __shared__ T s_l[REP_STAGE], s_l1[REP_STAGE / 64];
     RepStaged<T> acc{gacc, s_l, s_l1, 0, 0, 0, 0};
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint64_t s = gacc.s;
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         uint64_t running = MODE == REP_WRITE ? t_cnt[t] : 0;
@@ -244,55 +272,35 @@ __global__ __launch_bounds__(256) void k_rep_find(RepAcc<T> gacc, const uint8_t*
                     atomicMax((unsigned long long*)&best[q - 1], (unsigned long long)v);
                 continue;
             }
-            uint32_t tot;
-            const uint32_t at = rep_wg_exscan(keep ? 1u : 0u, s_w, tot);
+            const WgScan<uint32_t> sc = wg_scan_op<SumOp<uint32_t>, 4>(keep ? 1u : 0u, s_w);
             if (keep) {
                 if (MODE == REP_WRITE) {
-                    const uint64_t o = running + at;
+                    const uint64_t o = running + sc.before;
                     o_rank[o] = a; o_count[o] = z - a; o_len[o] = v;
                     if (SEQS) o_seqs[o] = q;
                 } else b.take(v, r, a, z - a, q);
             }
-            running += tot;
+            running += sc.total;
         }
         if (MODE == REP_COUNT) {
-            for (int o = 32; o > 0; o >>= 1)
-                b.merge(RepBest{__shfl_down(b.len, o), __shfl_down(b.rep, o), __shfl_down(b.rank, o), __shfl_down(b.cnt, o),
-                                SEQS ? __shfl_down(b.seq, o) : 0});
-            if (lane == 0) rep_best_put<NCOL>(s_b[w], b);
-            __syncthreads();
+            const typename Best::V best = wg_reduce_op<Best, 4>(Best::make(b), s_b);
             if (threadIdx.x == 0) {
-                for (uint32_t k = 1; k < 4; k++) b.merge(rep_best_get<NCOL>(s_b[k]));
                 t_cnt[t] = running;
-                rep_best_put<NCOL>(t_best + NCOL * t, b);
+                for (int c = 0; c < NCOL; c++) t_best[NCOL * t + c] = best.c[c];
             }
-            __syncthreads();                             // (s_b is reused by the next tile)
         }
     }
 }
 
-// stats = {records, longest, longest_rank, max_count (, max_seqs)}; *total: the sum of the tile counts
-template <int NCOL>
-__global__ __launch_bounds__(1024) void k_rep_best(const uint64_t* __restrict__ t_best, uint64_t ntiles, const uint64_t* __restrict__ total,
-                                                   uint64_t* __restrict__ stats)
+// stats[0] = *total (the sum of the tile counts), then Op::stats of the combination of the tiles' candidates (Op::COLS
+// words per tile): comparisons and sums, no atomics, so nothing depends on an order
+template <typename Op>
+__global__ __launch_bounds__(1024) void k_tile_best(const uint64_t* __restrict__ t_best, uint64_t ntiles, const uint64_t* __restrict__ total,
+                                                    uint64_t* __restrict__ stats)
 {
-    __shared__ uint64_t s_v[NCOL * 1024];                // column c of lane i at s_v[c * 1024 + i]
-    const uint32_t i = threadIdx.x;
-    RepBest b{0, 0, 0, 0, 0};
-    for (uint64_t t = i; t < ntiles; t += 1024) b.merge(rep_best_get<NCOL>(t_best + NCOL * t));
-    rep_best_put<NCOL>(s_v + i, b, 1024);
-    __syncthreads();
-    for (uint32_t o = 512; o > 0; o >>= 1) {
-        if (i < o) {
-            b.merge(rep_best_get<NCOL>(s_v + i + o, 1024));
-            rep_best_put<NCOL>(s_v + i, b, 1024);
-        }
-        __syncthreads();
-    }
-    if (i == 0) {
-        stats[0] = *total; stats[1] = b.len; stats[2] = b.rank; stats[3] = b.cnt;
-        if (NCOL > 4) stats[4] = b.seq;
-    }
+    __shared__ typename Op::V s_v[16];
+    const typename Op::V v = tile_reduce<Op>(ntiles, [&](uint64_t t) { return Op::get(t_best + Op::COLS * t); }, s_v);
+    if (threadIdx.x == 0) { stats[0] = *total; Op::stats(stats + 1, v); }
 }
 
 }  // namespace sufr
@@ -368,7 +376,7 @@ int repeats_find(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const RepPrep<T>& 
     hipLaunchKernelGGL((sufr::k_rep_find<T, sufr::REP_COUNT, SEQS>), dim3(R.grid), dim3(256), 0, pl.stream, R.acc, ix->ix.text, R.bits, P, flt, R.tile,
                        R.ntiles, R.t_cnt, R.t_best, none, none, none, none, none, (uint64_t)0);
     hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, R.t_cnt, R.ntiles, R.t_cnt + R.ntiles);
-    hipLaunchKernelGGL(sufr::k_rep_best<NCOL>, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)R.t_best, R.ntiles,
+    hipLaunchKernelGGL(sufr::k_tile_best<sufr::RepBestOp<NCOL>>, dim3(1), dim3(1024), 0, pl.stream, (const uint64_t*)R.t_best, R.ntiles,
                        (const uint64_t*)(R.t_cnt + R.ntiles), R.d_stats);
     const int rc = report_total(pl, tag, "records", R.d_stats, NCOL, h, cap, total_out, d_rank && d_count && d_length && (!SEQS || d_seqs));
     if (rc || !h[0]) return rc;

@@ -16,8 +16,8 @@
 //
 // This file owns what every query kernel shares; sufr_match.inc, sufr_mem.inc, sufr_approx.inc, sufr_edit.inc and
 // sufr_trace.inc, included after it, add only their own rules (DESIGN.md section 10, "The shared front end").
-// Device: search_compare / common_prefix, the range search (search_seed, search_lower, search_range), last_le, wg_scan,
-// scan_chunk, the locate scan (k_locate_counts / k_locate_scan / k_locate_apply), k_mem_bitmap and k_mem_revcomp.
+// Device: search_compare / common_prefix, the range search (search_seed, search_lower, search_range), last_le, scan_chunk
+// (wg_scan and the sweep behind k_locate_scan are sufr_scan.inc), the locate scan (k_locate_counts / k_locate_scan / k_locate_apply), k_mem_bitmap and k_mem_revcomp.
 // Host: query_check, lcp_refusals, index_sa, by_width, read_totals, scan_total; the batch of a call (take_batch =
 // batch_extent + double_batch, mem_bitmap); candidate_starts; the record epilogue (records_fit, any_null, launch_status,
 // report_total); the staging of the host-pointer entry points (stage_batch / unstage_batch, staged_records).
@@ -240,35 +240,6 @@ __device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ arr, ui
     return a;
 }
 
-// exclusive scan of N per-lane values over the 256 lanes of a workgroup (v: in place), tot: the workgroup totals;
-// s_w: 4 * N words of LDS, free again on return
-template <int N>
-__device__ __forceinline__ void wg_scan(uint64_t (&v)[N], uint64_t (&tot)[N], uint64_t* s_w)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint64_t inc[N];
-#pragma unroll
-    for (int n = 0; n < N; n++) inc[n] = v[n];
-    for (int o = 1; o < 64; o <<= 1) {
-#pragma unroll
-        for (int n = 0; n < N; n++) { const uint64_t u = __shfl_up(inc[n], o); if (lane >= (uint32_t)o) inc[n] += u; }
-    }
-    if (lane == 63) {
-#pragma unroll
-        for (int n = 0; n < N; n++) s_w[4 * n + w] = inc[n];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < N; n++) { inc[n] -= v[n]; v[n] = 0; tot[n] = 0; }
-    for (uint32_t k = 0; k < 4; k++) {
-#pragma unroll
-        for (int n = 0; n < N; n++) { if (k < w) v[n] += s_w[4 * n + k]; tot[n] += s_w[4 * n + k]; }
-    }
-    __syncthreads();                                   // (s_w is reused by the next tile)
-#pragma unroll
-    for (int n = 0; n < N; n++) v[n] += inc[n];
-}
-
 __global__ __launch_bounds__(256) void k_locate_counts(const uint64_t* __restrict__ lo, const uint64_t* __restrict__ hi, uint64_t nq,
                                                        uint64_t max_hits, uint64_t* __restrict__ off, uint64_t* __restrict__ blocksum)
 {
@@ -286,23 +257,13 @@ __global__ __launch_bounds__(256) void k_locate_counts(const uint64_t* __restric
     if (threadIdx.x == 0) blocksum[blockIdx.x] = tot[0];
 }
 
+// blocksum[0 .. nblk): the exclusive scan, in place; *total: the sum (tile_sweep of sufr_scan.inc)
 __global__ __launch_bounds__(1024) void k_locate_scan(uint64_t* __restrict__ blocksum, uint64_t nblk, uint64_t* __restrict__ total)
 {
-    __shared__ uint64_t s_p[1024];
-    const uint64_t per = (nblk + 1023) / 1024, b0 = threadIdx.x * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-    uint64_t sum = 0;
-    for (uint64_t b = b0; b < b1; b++) sum += blocksum[b];
-    s_p[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint64_t v = threadIdx.x >= (unsigned)o ? s_p[threadIdx.x - o] : 0;
-        __syncthreads();
-        s_p[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint64_t run = s_p[threadIdx.x] - sum;
-    for (uint64_t b = b0; b < b1; b++) { const uint64_t c = blocksum[b]; blocksum[b] = run; run += c; }
-    if (threadIdx.x == 1023) *total = s_p[1023];
+    __shared__ uint64_t s_p[16];
+    const uint64_t sum = tile_sweep<SumOp<uint64_t>, false>(
+        nblk, [&](uint64_t b) { return blocksum[b]; }, [&](uint64_t b, uint64_t, uint64_t before) { blocksum[b] = before; }, s_p);
+    if (threadIdx.x == 0) *total = sum;
 }
 
 __global__ __launch_bounds__(256) void k_locate_apply(uint64_t* __restrict__ off, uint64_t nq, const uint64_t* __restrict__ blocksum,

@@ -22,10 +22,11 @@
 //                turns the totals into bases; k_shr_addbase adds them: P, s + 1 entries of the index width.
 // k_rep_find     (sufr_repeat.inc) with SEQS set: the find pass of repeats with seqs from two reads of P, its filter and its
 //                column; counting, writing, or the profile (every representative raises best[seqs - 1] to v).  The counted
-//                find is repeats_find<T, true>; k_rep_best<5> gives its stats.
-// k_shr_suffix   one workgroup: the suffix maximum of best into d_common.
+//                find is repeats_find<T, true>; k_tile_best over RepBestOp<5> gives its stats.
+// k_shr_suffix   one workgroup: the suffix maximum of best into d_common, a backward tile_sweep (sufr_scan.inc, DESIGN.md
+//                section 10.2) of MaxOp.
 // A workgroup takes tiles t = blockIdx.x, blockIdx.x + gridDim.x, ...; no scratch, no MFMA.  LDS: k_shr_pairs 16.6 KB (32-bit
-// arrays) or 33.2 KB (64-bit), k_shr_suffix 8 KB, k_shr_scan 32 bytes.
+// arrays) or 33.2 KB (64-bit), k_shr_suffix 128 bytes, k_shr_scan 32 bytes.
 
 #include "sufr_shared_scan.h"
 
@@ -100,24 +101,12 @@ __global__ __launch_bounds__(256) void k_shr_addbase(T* __restrict__ x, uint64_t
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) x[i] = (T)((uint64_t)x[i] + t_base[i / tile]);
 }
 
-// common[k] = max best[k ..): lane i takes entries [i per, i per + per)
+// common[k] = max best[k ..)
 __global__ __launch_bounds__(1024) void k_shr_suffix(const uint64_t* __restrict__ best, uint64_t num, uint64_t* __restrict__ common)
 {
-    __shared__ uint64_t s_m[1024];
-    const uint32_t i = threadIdx.x;
-    const uint64_t per = (num + 1023) / 1024, b0 = i * per < num ? i * per : num, b1 = b0 + per < num ? b0 + per : num;
-    uint64_t m = 0;
-    for (uint64_t k = b0; k < b1; k++) if (best[k] > m) m = best[k];
-    s_m[i] = m;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {            // s_m[i] = max of the lanes i ..
-        const uint64_t u = i + o < 1024 ? s_m[i + o] : 0;
-        __syncthreads();
-        if (u > s_m[i]) s_m[i] = u;
-        __syncthreads();
-    }
-    uint64_t run = i + 1 < 1024 ? s_m[i + 1] : 0;
-    for (uint64_t k = b1; k > b0; k--) { if (best[k - 1] > run) run = best[k - 1]; common[k - 1] = run; }
+    __shared__ uint64_t s_m[16];
+    tile_sweep<MaxOp, true>(
+        num, [&](uint64_t k) { return best[k]; }, [&](uint64_t k, uint64_t own, uint64_t after) { common[k] = own > after ? own : after; }, s_m);
 }
 
 }  // namespace sufr

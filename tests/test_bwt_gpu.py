@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 EXP = GOLDEN / "expected"
 T = 256                                                               # the smallest tile: one workgroup of ranks
 TILES = (0, T)
-ROUND = 256                                                           # tiles one round of the carry sweep takes
+LANES = 1024                                                          # lanes of the one workgroup that sweeps the tile summaries
 
 
 @pytest.fixture(scope="module")
@@ -172,25 +172,62 @@ def test_all_byte_values_and_a_sorted_array(ctx):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# more tiles than one round of the carry sweep takes, and more than one tile per workgroup
+# more tiles than the sweeps have lanes, and more than one tile per workgroup
 # ---------------------------------------------------------------------------------------------------------------------
-def test_more_tiles_than_rounds_of_the_carry(ctx):
-    """2 x 256 x 256 + 300 ranks at tile 256: three rounds of the sweep, the last one partial; a run over 200 whole tiles
-    crosses from one round into the next, and a run of one whole tile ends where the second round hands over to the third"""
-    n = 2 * ROUND * T + 300
+def per_lane(ntiles: int) -> int:
+    """tiles in the block of one lane of a sweep (tile_sweep of sufr_scan.inc: lane i takes tiles [i per, (i + 1) per))"""
+    return (ntiles + LANES - 1) // LANES
+
+
+def test_more_tiles_than_lanes_of_the_carry_sweep(ctx):
+    """2049 x 256 + 44 ranks at tile 256: 2050 tiles, three to a lane of the sweep, the upper lanes without any and the last
+    tile ragged; a run over 200 whole tiles crosses the boundaries of more than 60 lanes' blocks, and a run of exactly one
+    whole tile ends exactly where one lane's block hands over to the next"""
+    n = 2049 * T + 44
     ntiles = (n + T - 1) // T
-    assert ntiles == 2 * ROUND + 2
+    per = per_lane(ntiles)
+    assert ntiles == 2050 and per == 3 and n % T != 0 and (ntiles + per - 1) // per < LANES
     bwt = runs_of(b"ACGT", n, 6.0, seed=9)
-    hand = (ntiles - ROUND) * T                                      # the first rank of the first round's lowest tile (rounds go from the end)
+    hand = 500 * per * T                                             # the first rank of lane 500's block
     bwt[hand - 200 * T - 7:hand + 3 * T + 9] = ord("T"); bwt[hand - 200 * T - 8] = ord("A"); bwt[hand + 3 * T + 9] = ord("C")
-    hand2 = (ntiles - 2 * ROUND) * T
+    hand2 = 100 * per * T
     bwt[hand2 - T:hand2] = ord("G"); bwt[hand2 - T - 1] = ord("A"); bwt[hand2] = ord("C")               # a whole tile up to the hand-over
     sa = rotation(n, hand)
     want = witness(text_for(bwt, sa), sa)
     assert np.array_equal(want[0], bwt) and want[3]["longest"] == 203 * T + 16 and edges(want[2], T)[2] >= 200
+    rank, length = want[2][0].astype(np.int64), want[2][1].astype(np.int64)
+    long_run = int(np.argmax(length))
+    assert (rank[long_run] + length[long_run]) // (per * T) - rank[long_run] // (per * T) > 60       # block boundaries inside the long run
+    assert ((rank == hand2 - T) & (length == T)).any() and hand2 % (per * T) == 0
     for name, ix in wrapped(ctx, text_for(bwt, sa), sa):
         check_index(ctx, ix, want, min_lens=(1, 3), tiles=(T,) if name == "wide" else TILES, tag=name)
         ix.close()
+
+
+@pytest.mark.parametrize("ntiles,per", [(1023, 1), (1024, 1), (1025, 2), (2050, 3)])
+def test_sweeps_at_the_lane_count_of_the_workgroup(ctx, ntiles, per):
+    """as many tiles of 256 as the sweeps have lanes, one fewer, one more and twice as many and a bit (from 1025 on the upper
+    lanes have no tile); the last tile ragged.  One run over every tile, one run per tile that ends exactly at the tile's
+    edge, and random runs"""
+    n = (ntiles - 1) * T + 77
+    assert (n + T - 1) // T == ntiles and per_lane(ntiles) == per and (ntiles <= LANES or (ntiles + per - 1) // per < LANES)
+    one = np.full(n, ord("A"), dtype=np.uint8)
+    one[0] = ord("C")
+    at_edges = np.repeat(np.frombuffer(b"AC", dtype=np.uint8)[np.arange(ntiles) % 2], T)[:n].copy()
+    at_edges[::T] = ord("G")                                          # (a single rank at every tile's start, the rest of the tile one run)
+    sa = rotation(n, 3 * T + 5)
+    for tag, bwt in (("one", one), ("edges", at_edges), ("random", runs_of(b"ACGT$N", n, 40.0, seed=ntiles))):
+        text = text_for(bwt, sa)
+        want = witness(text, sa)
+        assert np.array_equal(want[0], bwt)
+        rank, length = want[2][0].astype(np.int64), want[2][1].astype(np.int64)
+        if tag == "one":
+            assert edges(want[2], T)[2] == ntiles - 2 and int(length.max()) == n - 1
+        if tag == "edges":
+            assert set(((rank + length)[(rank + length) % T == 0] // T).tolist()) == set(range(1, ntiles))
+        for name, ix in wrapped(ctx, text, sa):
+            check_index(ctx, ix, want, tiles=(T,), tag=(ntiles, tag, name))
+            ix.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

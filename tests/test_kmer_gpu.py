@@ -238,6 +238,74 @@ def test_more_than_one_tile_per_workgroup(ctx, tmp_path):
     ix.close(); f.close(); db.close()
 
 
+def kmer_witness(sa: np.ndarray, lcp: np.ndarray, n: int, k: int, bins: int):
+    """(histogram, stats, occ by rank, occ by position) of one sequence of n symbols, by numpy"""
+    sa, lcp = sa.astype(np.int64), lcp.astype(np.int64)
+    interval = np.cumsum(np.concatenate([[True], lcp[1:] < k])) - 1
+    whole = n - 1 - sa >= k
+    count = np.bincount(interval, weights=whole).astype(np.int64)
+    by_rank = np.where(whole, count[interval], 0).astype(np.uint64)
+    by_pos = np.zeros(n, dtype=np.uint64)
+    by_pos[sa] = by_rank
+    seen = count[count > 0]
+    hist = np.bincount(np.minimum(seen, bins) - 1, minlength=bins).astype(np.uint64)
+    stats = dict(whole=int(whole.sum()), distinct=int(seen.size), unique=int((seen == 1).sum()), max_count=int(seen.max()) if seen.size else 0)
+    return hist, stats, by_rank, by_pos
+
+
+@pytest.mark.parametrize("ntiles,per", [(1023, 1), (1024, 1), (1025, 2), (2050, 3)])
+def test_one_interval_over_every_block_of_the_sweep(ctx, ntiles, per):
+    """A^n $ written down (SA descends, LCP = 0, 0, 1, ..., n - 1) with as many tiles of 256 as the carry sweep has lanes, one
+    fewer, one more, and twice as many and a bit: at k = 1 one interval covers every tile but the first rank, so no tile
+    but the first holds a head and both carries cross every boundary between two lanes' blocks; at k = 256 that interval
+    begins exactly at a tile edge and a single rank ends there"""
+    s = (ntiles - 1) * T + 77
+    n = s - 1
+    assert (s + T - 1) // T == ntiles and (ntiles + 1023) // 1024 == per
+    text = np.concatenate([np.full(n, ord("A"), dtype=np.uint8), np.frombuffer(b"$", dtype=np.uint8)])
+    sa = np.arange(n, -1, -1, dtype=np.int64)
+    lcp = np.concatenate([[0], np.arange(n, dtype=np.int64)])
+    heads = lcp[1:] < 1
+    assert longest_interval(lcp, 1) == n and not heads[T - 1:].any()         # has == 0 in every tile but the first
+    assert boundary_ks(lcp, T)[0] == T and longest_interval(lcp, T) == s - T and lcp[T - 1] < T and lcp[T] < T      # [T - 1, T) and [T, s)
+    d_text = torch.from_numpy(text).cuda()
+    ctx.set_kmer_tile(T)
+    try:
+        for wide in (False, True):
+            ix = DeviceIndex.wrap(ctx, d_text, _dev(sa.astype(np.uint32), wide), prefix_table=False)
+            d_lcp = _dev(lcp.astype(np.uint32), wide)
+            for k in (1, T, 3):
+                hist, stats, by_rank, by_pos = kmer_witness(sa, lcp, s, k, 256)
+                assert stats["max_count"] == n - k + 1
+                for occ, want in (("rank", by_rank), ("position", by_pos)):
+                    dh, dst, do = ix.kmers_device(d_lcp, k, 256, occ)
+                    assert np.array_equal(_host(dh), hist) and dst == stats and np.array_equal(_host(do), want), (wide, k, occ, dst, stats)
+            ix.close()
+    finally:
+        ctx.set_kmer_tile(0)
+
+
+def test_a_sorted_text_of_more_tiles_than_the_sweep_has_lanes(ctx, tmp_path):
+    """525 000 bases sorted on the device, against the host path through a written file: 2051 tiles of 256, three to a lane"""
+    x, _ = synth.syn_elegans(525_000, seed=6, n_seqs=1, device="cuda")
+    norm = torch.where((x >= 97) & (x <= 122), x - 32, x).contiguous()
+    db = sufr_amd.DeviceBuilder(0)
+    sa, lcp = db.sort(norm, is_dna=True)
+    assert ((sa.numel() + T - 1) // T + 1023) // 1024 == 3
+    _write(tmp_path / "x.sufr", norm.cpu().numpy(), sa.cpu().numpy().view(np.uint32).copy(), lcp.cpu().numpy().view(np.uint32).copy())
+    f = SufrFile(tmp_path / "x.sufr")
+    want = {(k, occ): f.kmers(k, 256, occ, threads=16) for k in (3, 12) for occ in ("rank", "position")}
+    db.ctx.set_kmer_tile(T)
+    for wide, d_sa, d_lcp in ((False, sa, lcp), (True, sa.to(torch.int64), lcp.to(torch.int64))):      # (both are below 2^31)
+        ix = DeviceIndex.wrap(db.ctx, norm, d_sa, is_dna=True, prefix_table=False)
+        for (k, occ), (h, st, o) in want.items():
+            dh, dst, do = ix.kmers_device(d_lcp, k, 256, occ)
+            assert np.array_equal(_host(dh), h) and dst == st and np.array_equal(_host(do), o.astype(np.uint64)), (wide, k, occ)
+        ix.close()
+    db.ctx.set_kmer_tile(0)
+    f.close(); db.close()
+
+
 def test_outputs_are_left_untouched_outside_their_entries(ctx):
     f = SufrFile(EXP / "long_dna_sequence.sufr")
     assert f.len_suffixes < f.text_len                               # (the Ns are not indexed)

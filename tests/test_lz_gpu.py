@@ -12,6 +12,7 @@ import torch
 import sufr_amd
 from sufr_amd import DeviceIndex, SufrFile, synth
 from oracle_helper import GOLDEN
+from test_gpu_match import _write
 from test_kmer_gpu import _dev, indexes, oracle_file
 from test_lz_host import FF, distinct_file, fibonacci, letters
 
@@ -194,6 +195,32 @@ def test_other_texts(ctx, oracle, tmp_path):
     assert f.len_suffixes < f.text_len - 300 and at.sum() >= 300 and (source[at] == FF).all()      # a tile and more of literals at positions that are not indexed
 
 
+def test_more_parse_tiles_than_the_stats_reduction_has_lanes(tmp_path):
+    """524 621 bases sorted on the device, against the host path through a written file: 2050 parse tiles of 256 positions,
+    two or three to every lane of the reduction that gives the stats (the last tile ragged), and as many rank tiles"""
+    n = 2049 * T + 77
+    x, _ = synth.syn_elegans(n - 1, seed=7, n_seqs=1, device="cuda")
+    norm = torch.where((x >= 97) & (x <= 122), x - 32, x).contiguous()
+    assert norm.numel() == n and (n + T - 1) // T == 2050
+    db = sufr_amd.DeviceBuilder(0)
+    sa, lcp = db.sort(norm, is_dna=True)
+    _write(tmp_path / "x.sufr", norm.cpu().numpy(), sa.cpu().numpy().view(np.uint32).copy(), lcp.cpu().numpy().view(np.uint32).copy())
+    f = SufrFile(tmp_path / "x.sufr")
+    want = f.lz(threads=16)
+    entered = set((want[0] // T).tolist())
+    assert want[3]["factors"] > 2050 and 1024 < len(entered) and {0, 2049} <= entered          # more entered tiles than lanes, the last one too
+    db.ctx.set_lz_tile(T, T)
+    for wide, d_sa, d_lcp in ((False, sa, lcp), (True, sa.to(torch.int64), lcp.to(torch.int64))):      # (both are below 2^31)
+        ix = DeviceIndex.wrap(db.ctx, norm, d_sa, is_dna=True, prefix_table=False)
+        got = ix.lz_device(d_lcp, f.sequence_starts)
+        for i in range(3):
+            assert np.array_equal(got[i].cpu().numpy().view(np.uint64), want[i]), (wide, i)
+        assert got[3] == want[3], (wide, got[3], want[3])
+        ix.close()
+    db.ctx.set_lz_tile(0, 0)
+    f.close(); db.close()
+
+
 def test_pairwise_different_bytes_are_all_literals(ctx, tmp_path):
     """255 pairwise different bytes and the sentinel: there are no more different bytes than that"""
     f = distinct_file(tmp_path / "distinct.sufr", 255)
@@ -230,6 +257,7 @@ def test_capacity_and_untouched_outputs(ctx):
     # either array of the table alone
     n = f.text_len
     one = torch.full((n,), 7, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()                                         # (the fill runs on torch's stream, the call on the context's own)
     ctx.check(L.sufr_hip_lpf_device(*args, one.data_ptr(), None))
     ctx.synchronize()
     assert np.array_equal(_unsigned(one), f.lpf()[0].astype(np.uint64))

@@ -256,6 +256,35 @@ def test_two_digits_the_second_partial(ctx, oracle, tmp_path):
     ix.close()
 
 
+def test_more_sequences_than_the_suffix_sweep_has_lanes(ctx, oracle, tmp_path):
+    """2050 short sequences: the profile has three entries to a lane of the suffix-maximum sweep (the upper lanes have none),
+    and the maxima that set common[] for small and for large sequence counts lie in different lanes' blocks"""
+    rng = np.random.default_rng(12)
+    ac = np.frombuffer(b"ACGT", dtype=np.uint8)
+    sep = np.frombuffer(b"%", dtype=np.uint8)
+    families = [(2, ac[rng.integers(0, 4, 9)]), (5, ac[rng.integers(0, 4, 11)]), (41, ac[rng.integers(0, 4, 14)])]      # every 2nd, 5th, 41st
+    parts = []
+    for i in range(2050):
+        s = ac[rng.integers(0, 4, int(rng.integers(3, 12)))]
+        for every, fam in families:
+            if i % every == 0:
+                s = np.concatenate([s, fam, ac[rng.integers(0, 4, 2)]])
+        parts += [s, sep]
+    f = oracle_file(oracle, tmp_path, np.concatenate(parts[:-1]), "d2050", is_dna=True)
+    num, per = f.num_sequences, (2050 + 1023) // 1024
+    assert num == 2050 and per == 3 and (num + per - 1) // per < 1024
+    common = f.common()
+    steps = np.nonzero(common[:-1] != common[1:])[0]                 # common[k] > common[k + 1]: entry k of the profile is a maximum of its own
+    assert common[49] >= 14 > common[409] >= 11 > common[1024] >= 9 and len(set((steps // per).tolist())) >= 3
+    assert (steps % per != per - 1).any() and (steps >= 1024).any()  # (inside a lane's block, and beyond the lane count)
+    for tag, ix, lcp in indexes(ctx, f):                               # loaded, wrapped, and wrapped with 64-bit arrays
+        for tile in (T, 0):
+            ctx.set_repeat_tile(tile)
+            assert same_as_host(f, ix, lcp, (0,), (4,), ((2, 0, 0, 0), (2, 0, 400, 0)), tag=(tag, tile)) > 0
+        ctx.set_repeat_tile(0)
+        ix.close()
+
+
 def _write_collection(path, text: np.ndarray, sa: np.ndarray, lcp: np.ndarray, starts: np.ndarray):
     err = C.create_string_buffer(256)
     st = np.ascontiguousarray(starts, dtype=np.uint64)
