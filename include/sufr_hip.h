@@ -146,6 +146,14 @@ int  sufr_hip_overlapped(const sufr_hip_ctx *ctx);
 /* how many times the context's last build handed a level to prefix doubling: both chains, added up after the helper was joined
  * (a windowed build: all windows) */
 uint64_t sufr_hip_doublings(const sufr_hip_ctx *ctx);
+/* Tie runs (suffixes that agree on all key characters) of exactly two members are compared directly, in front of the tie level,
+ * instead of being keyed: an exact build only.  mode 0: the default -- when the pairs hold a large enough share of the tie
+ * records --, 1: always, 2: never (the build of the versions before this call).  The arrays do not depend on it.  Additive, ABI
+ * version 3.  Another mode is refused with SUFR_HIP_E_INVALID. */
+int  sufr_hip_set_pair_walk(sufr_hip_ctx *ctx, uint32_t mode);
+/* The context's last build (a windowed build: all windows): `resolved` pairs were finished by the direct comparison, `left_tied`
+ * were compared and handed back to the tie level -- they agree for 4096 characters more.  Either pointer may be null. */
+int  sufr_hip_pairs_walked(const sufr_hip_ctx *ctx, uint64_t *resolved, uint64_t *left_tied);
 /* A --dna build of a text with a few bytes outside {$ % A C G N T} runs on 'N' in their place and re-places the suffixes whose
  * comparisons reached such a byte (sufr_exc.inc).  With more than max_affected of them the text is built again with the general
  * code table -- same arrays, more time.  0: the default, 2^22, which is also the most: the whole-text sort of the affected

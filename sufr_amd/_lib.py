@@ -80,7 +80,7 @@ FLAG_SA_U64 = 0x200               # sufr_hip_index_wrap only: 64-bit suffix arra
 # every symbol include/sufr_hip.h declares
 EXPORTS = [
     "sufr_hip_abi_version", "sufr_hip_device_count", "sufr_hip_create", "sufr_hip_destroy",
-    "sufr_hip_last_error", "sufr_hip_set_stream", "sufr_hip_synchronize", "sufr_hip_set_window", "sufr_hip_set_window_retry", "sufr_hip_set_array_budget", "sufr_hip_window_repairs", "sufr_hip_set_overlap_min", "sufr_hip_overlapped", "sufr_hip_doublings", "sufr_hip_set_exc_max_affected", "sufr_hip_exc_retry", "sufr_hip_exc_taken", "sufr_hip_normalize", "sufr_hip_sort_device_u32",
+    "sufr_hip_last_error", "sufr_hip_set_stream", "sufr_hip_synchronize", "sufr_hip_set_window", "sufr_hip_set_window_retry", "sufr_hip_set_array_budget", "sufr_hip_window_repairs", "sufr_hip_set_overlap_min", "sufr_hip_overlapped", "sufr_hip_doublings", "sufr_hip_set_pair_walk", "sufr_hip_pairs_walked", "sufr_hip_set_exc_max_affected", "sufr_hip_exc_retry", "sufr_hip_exc_taken", "sufr_hip_normalize", "sufr_hip_sort_device_u32",
     "sufr_hip_sort_device_u64", "sufr_hip_stitch_device_u32", "sufr_hip_stitch_device_u64", "sufr_hip_build_u32", "sufr_hip_build_u64", "sufr_hip_lcp_pair",
     "sufr_read_sequence_file", "sufr_sequence_data_free", "sufr_write_file", "sufr_hip_create_file", "sufr_hip_create_from_sequence",
     "sufr_hip_shard_build", "sufr_write_frame", "sufr_hip_shard_write", "sufr_hip_create_from_sequence_multi",
@@ -229,6 +229,8 @@ def lib() -> C.CDLL:
     L.sufr_hip_set_overlap_min.argtypes = [vp, u64]; L.sufr_hip_set_overlap_min.restype = C.c_int
     L.sufr_hip_overlapped.argtypes = [vp]; L.sufr_hip_overlapped.restype = C.c_int
     L.sufr_hip_doublings.argtypes = [vp]; L.sufr_hip_doublings.restype = u64
+    L.sufr_hip_set_pair_walk.argtypes = [vp, C.c_uint32]; L.sufr_hip_set_pair_walk.restype = C.c_int
+    L.sufr_hip_pairs_walked.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]; L.sufr_hip_pairs_walked.restype = C.c_int
     L.sufr_hip_set_exc_max_affected.argtypes = [vp, u64]; L.sufr_hip_set_exc_max_affected.restype = C.c_int
     L.sufr_hip_exc_retry.argtypes = [vp]; L.sufr_hip_exc_retry.restype = C.c_int
     L.sufr_hip_exc_taken.argtypes = [vp]; L.sufr_hip_exc_taken.restype = u64
@@ -447,6 +449,19 @@ class Context:
     def doublings(self) -> int:
         """How many times the last build handed a level to prefix doubling (both chains; a windowed build: all windows)."""
         return int(lib().sufr_hip_doublings(self._h))
+
+    def set_pair_walk(self, mode: int = 0):
+        """Tie runs of exactly two suffixes compared directly in front of the tie level (sufr_hip_set_pair_walk; 0: when the
+        pairs hold a large enough share of the tie records, 1: always, 2: never).  The arrays do not depend on it."""
+        self.check(lib().sufr_hip_set_pair_walk(self._h, mode))
+
+    @property
+    def pairs_walked(self):
+        """(resolved, left_tied) of the last build: tie pairs the direct comparison finished, and pairs it handed back to the
+        tie level because they agree for 4096 characters more (a windowed build: all windows)."""
+        r, t = C.c_uint64(0), C.c_uint64(0)
+        self.check(lib().sufr_hip_pairs_walked(self._h, C.byref(r), C.byref(t)))
+        return int(r.value), int(t.value)
 
     def set_exc_max_affected(self, max_affected: int = 0):
         """Suffixes that may have looked at a byte outside the DNA table before a --dna build goes to the general code table

@@ -295,6 +295,22 @@ int sufr_hip_set_overlap_min(sufr_hip_ctx* ctx, uint64_t min_records)
 int sufr_hip_overlapped(const sufr_hip_ctx* ctx) { return ctx ? (int)ctx->pl.last_overlapped : 0; }
 uint64_t sufr_hip_doublings(const sufr_hip_ctx* ctx) { return ctx ? ctx->pl.last_doublings : 0; }
 
+int sufr_hip_set_pair_walk(sufr_hip_ctx* ctx, uint32_t mode)
+{
+    if (!ctx) return SUFR_HIP_E_INVALID;
+    if (mode > 2u) { ctx->pl.set_error("pair walk mode " + std::to_string(mode) + ": 0 (default), 1 (always) or 2 (never)"); return SUFR_HIP_E_INVALID; }
+    ctx->pl.opt_pair_walk = mode;
+    return 0;
+}
+
+int sufr_hip_pairs_walked(const sufr_hip_ctx* ctx, uint64_t* resolved, uint64_t* left_tied)
+{
+    if (!ctx) return SUFR_HIP_E_INVALID;
+    if (resolved) *resolved = ctx->pl.last_pairs_resolved;
+    if (left_tied) *left_tied = ctx->pl.last_pairs_left;
+    return 0;
+}
+
 int sufr_hip_set_exc_max_affected(sufr_hip_ctx* ctx, uint64_t max_affected)
 {
     if (!ctx) return SUFR_HIP_E_INVALID;

@@ -62,6 +62,13 @@ uint64_t sufr_hip_window_repairs(const sufr_hip_ctx*) { return 0; }
 int sufr_hip_set_overlap_min(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
 int sufr_hip_overlapped(const sufr_hip_ctx*) { return 0; }
 uint64_t sufr_hip_doublings(const sufr_hip_ctx*) { return 0; }
+int sufr_hip_set_pair_walk(sufr_hip_ctx* ctx, uint32_t) { return no_device(ctx); }
+int sufr_hip_pairs_walked(const sufr_hip_ctx*, uint64_t* resolved, uint64_t* left_tied)
+{
+    if (resolved) *resolved = 0;
+    if (left_tied) *left_tied = 0;
+    return 0;
+}
 int sufr_hip_set_exc_max_affected(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
 int sufr_hip_exc_retry(const sufr_hip_ctx*) { return 0; }
 uint64_t sufr_hip_exc_taken(const sufr_hip_ctx*) { return 0; }

@@ -28,6 +28,7 @@
 
 #include "sufr_device.h"
 #include "sufr_runkey.h"
+#include "sufr_tiepairs.h"
 
 namespace sufr {
 // phase stamps (probes build): cycles per phase of the last wave of every workgroup, summed; printed with SUFR_HIP_DEBUG=1
@@ -1646,6 +1647,24 @@ __device__ __forceinline__ uint64_t walk_lcp_packed(const uint8_t* __restrict__ 
     return lim;
 }
 
+// Two suffixes compared directly from positions a and b on (their shared depth already added): the one walk of the finisher's
+// pairs, of its walk keys and of the pair path in front of the tie level (k_pair_walk), so that the three cannot drift apart.
+//   k       characters the two share from there on, at most WALK_CAP
+//   parted  false: they agree for WALK_CAP characters and both go on -- still tied, WALK_CAP characters deeper
+//   a_first (parted) the suffix at a sorts first: the smaller character where they part, or, where one of them ends, the one
+//           that ends first (a proper prefix of the other)
+struct PairWalk { uint64_t k; bool parted, a_first; };
+__device__ __forceinline__ PairWalk walk_pair(const uint8_t* __restrict__ text, uint64_t n, const KeyParams& kp, uint64_t a, uint64_t b)
+{
+    const uint64_t lim = n - (a > b ? a : b);        // characters both suffixes have
+    uint32_t ca = 0, cb = 0;
+    PairWalk w;
+    w.k = kp.packed ? walk_lcp_packed(kp.packed, kp.b, n, a, b, WALK_CAP, ca, cb) : walk_lcp(text, n, a, b, WALK_CAP);
+    w.parted = !(w.k == WALK_CAP && w.k < lim);
+    w.a_first = w.parted && (w.k == lim ? a > b : (kp.packed ? ca < cb : text[a + w.k] < text[b + w.k]));
+    return w;
+}
+
 // Walk keys: a member of a tie group keyed by its common prefix L with the group's FIRST member (the reference),
 // beyond the depth all members share.  A member that leaves the reference's text earlier than another is smaller than
 // it iff its character there is below the reference's: {below the reference, L ascending} < reference < {above, L
@@ -1900,17 +1919,13 @@ k_finish(const uint64_t* __restrict__ keys, const uint32_t* idxs,
             if (__ballot(ph0 || ph1) != 0ull) {
                 auto walk = [&](uint32_t slot, uint32_t mine, uint32_t dnew) {
                     const uint32_t other = si[slot + 1];
-                    const uint64_t a = (uint64_t)mine + dnew, b = (uint64_t)other + dnew;
-                    const uint64_t lim = n - (a > b ? a : b);        // characters both suffixes have
-                    uint32_t ca = 0, cb = 0;
-                    const uint64_t k = kp.packed ? walk_lcp_packed(kp.packed, kp.b, n, a, b, WALK_CAP, ca, cb)
-                                                 : walk_lcp(text, n, a, b, WALK_CAP);
-                    if (k == WALK_CAP && k < lim) {                  // not parted yet: stays a pair, WALK_CAP deeper
+                    const PairWalk w = walk_pair(text, n, kp, (uint64_t)mine + dnew, (uint64_t)other + dnew);
+                    if (!w.parted) {                                 // not parted yet: stays a pair, WALK_CAP deeper
                         sg[slot] = 0xffffffffu; sg[slot + 1] = 0xffffffffu;
                         return;
                     }
-                    // the suffix that ends first (a proper prefix of the other) sorts first
-                    const bool mine_first = k == lim ? a > b : (kp.packed ? ca < cb : text[a + k] < text[b + k]);
+                    const uint64_t k = w.k;
+                    const bool mine_first = w.a_first;
                     si[slot] = mine_first ? mine : other;
                     si[slot + 1] = mine_first ? other : mine;
                     sg[slot] = 0u;
@@ -1945,14 +1960,9 @@ k_finish(const uint64_t* __restrict__ keys, const uint32_t* idxs,
         if (walk_next) {
             // the reference: the member in the group's first slot (slots hold the sorted records by now)
             auto wkey = [&](uint32_t mine, uint32_t ref, uint32_t d) -> uint64_t {
-                const uint64_t a = (uint64_t)mine + d, r2 = (uint64_t)ref + d;
-                const uint64_t lim = n - (a > r2 ? a : r2);
-                uint32_t ca = 0, cb = 0;
-                const uint64_t L = kp.packed ? walk_lcp_packed(kp.packed, kp.b, n, a, r2, WALK_CAP, ca, cb)
-                                             : walk_lcp(text, n, a, r2, WALK_CAP);
-                if (L == WALK_CAP && L < lim) return walk_key(true, false, 0);      // agrees with the reference so far
-                const bool below = L == lim ? a > r2 : (kp.packed ? ca < cb : text[a + L] < text[r2 + L]);
-                return walk_key(false, below, L);
+                const PairWalk w = walk_pair(text, n, kp, (uint64_t)mine + d, (uint64_t)ref + d);
+                if (!w.parted) return walk_key(true, false, 0);      // agrees with the reference so far
+                return walk_key(false, w.a_first, w.k);
             };
             if (act0) {
                 dd0 += advance(k0);
@@ -2191,6 +2201,137 @@ k_build_ties(const unsigned long long* __restrict__ wmask, const uint32_t* __res
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The pair path in front of the tie level.  Most tie runs of a genome are PAIRS -- the two copies of a segmental duplication
+// -- and a run key, ~20 characters, parts only about one pair in seven at 1 % divergence: for the others the gather, the
+// packing into the dense level, the window plan and the ranking round were spent to arrive at the finisher's pair walk.  Here
+// the pairs are listed straight from the tie bitmaps (sufr_tiepairs.h) and walked one lane per pair; a pair that parts within
+// WALK_CAP characters is final and leaves the bitmaps, every other run goes through the tie level as before.
+// Scalars of the path, u64 slots: 64 partial sums of the tie members, 64 of the pairs resolved (a slot per wave, modulo 64:
+// one counter would serialise ~10^5 atomics on one address), then the number of pairs (the total of the scan).
+// ---------------------------------------------------------------------------------------------
+static constexpr uint32_t PSC_MEMBERS = 0, PSC_RESOLVED = 64, PSC_PAIRS = 128, PSC_N = 129;
+
+// The path is taken when it pays: always / never by the caller's word (force = 1 / the kernels are not launched), else when
+// the pairs hold at least min_permille thousandths of the tie members.  Every lane reads one partial sum.
+__device__ __forceinline__ bool pair_path_taken(const unsigned long long* __restrict__ psc, uint32_t force, uint32_t min_permille)
+{
+    if (force) return true;
+    unsigned long long mem = psc[PSC_MEMBERS + lane_id()];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mem += shfl64(mem, (int)(lane_id() ^ (uint32_t)o));
+    return 2ull * psc[PSC_PAIRS] * 1000ull >= mem * (unsigned long long)min_permille;
+}
+
+__device__ __forceinline__ TieMask128 window_pair_heads(const unsigned long long* __restrict__ wmask, uint32_t w, uint32_t nwin)
+{
+    const ulonglong2 mm = *reinterpret_cast<const ulonglong2*>(wmask + (size_t)w * 4);
+    TieMask128 none = {0ull, 0ull};
+    if ((mm.x | mm.y) == 0ull) return none;
+    const ulonglong2 hh = *reinterpret_cast<const ulonglong2*>(wmask + (size_t)w * 4 + 2);
+    uint32_t next = 0;
+    if (((mm.y >> 62) != 0ull) && w + 1 < nwin)          // (only a run in the last two slots can reach the next window)
+        next = tie_next_bits(wmask[(size_t)(w + 1) * 4], wmask[(size_t)(w + 1) * 4 + 2]);
+    return tie_pair_heads(mm.x, mm.y, hh.x, hh.y, next);
+}
+
+// A workgroup takes 256 windows, a thread each.  exclusive = pairs of the workgroup's windows below this thread's, total = all of
+// them (a wave scan over shuffles, the four wave totals through LDS).
+__device__ __forceinline__ uint32_t block_scan_256(uint32_t v, uint32_t& total)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t ln = lane_id(), wv = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up(inc, o, WAVE); if (ln >= (uint32_t)o) inc += t; }
+    if (ln == 63u) s_wave[wv] = inc;
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t k = 0; k < wv; k++) before += s_wave[k];
+    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    return before + inc - v;
+}
+
+// pairs per workgroup of 256 windows (the counts the list's offsets are scanned from), and the partial sums of the tie members
+// (a count per window and an atomic per wave were measured at 0.60 ms for 11.7 M windows, six times the read of the bitmaps)
+__global__ void __launch_bounds__(256)
+k_pair_counts(const unsigned long long* __restrict__ wmask, uint32_t nwin, uint32_t* __restrict__ blkcnt,
+              unsigned long long* __restrict__ psc)
+{
+    __shared__ uint32_t s_mem[4];
+    const uint32_t w = blockIdx.x * 256 + threadIdx.x;
+    uint32_t mem = 0, cnt = 0;
+    if (w < nwin) {
+        mem = (uint32_t)(__popcll(wmask[(size_t)w * 4]) + __popcll(wmask[(size_t)w * 4 + 1]));
+        if (mem) cnt = tie_mask_count(window_pair_heads(wmask, w, nwin));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mem += (uint32_t)__shfl_down(mem, o, WAVE);
+    if (lane_id() == 0) s_mem[threadIdx.x >> 6] = mem;
+    uint32_t total;
+    (void)block_scan_256(cnt, total);               // (its barrier orders s_mem too)
+    if (threadIdx.x == 0) {
+        blkcnt[blockIdx.x] = total;
+        const uint32_t m = s_mem[0] + s_mem[1] + s_mem[2] + s_mem[3];
+        if (m) atomicAdd(&psc[PSC_MEMBERS + (blockIdx.x & 63u)], (unsigned long long)m);
+    }
+}
+
+// the rank of every pair head, densely: the pairs of workgroup b's windows from blkoff[b] on, in rank order (what lies beyond
+// `cap` stays with the tie level)
+__global__ void __launch_bounds__(256)
+k_pair_list(const unsigned long long* __restrict__ wmask, uint32_t nwin, const uint32_t* __restrict__ blkcnt,
+            const uint32_t* __restrict__ blkoff, const unsigned long long* __restrict__ psc, uint32_t force, uint32_t min_permille,
+            uint32_t cap, uint32_t* __restrict__ pairlist)
+{
+    if (!pair_path_taken(psc, force, min_permille)) return;
+    if (!blkcnt[blockIdx.x]) return;                // (the whole workgroup)
+    const uint32_t w = blockIdx.x * 256 + threadIdx.x;
+    TieMask128 ph = {0ull, 0ull};
+    if (w < nwin) ph = window_pair_heads(wmask, w, nwin);
+    uint32_t total;
+    uint32_t e = blkoff[blockIdx.x] + block_scan_256(tie_mask_count(ph), total);
+    for (uint64_t left = ph.lo; left && e < cap; left &= left - 1) pairlist[e++] = w * 128u + (uint32_t)__builtin_ctzll(left);
+    for (uint64_t left = ph.hi; left && e < cap; left &= left - 1) pairlist[e++] = w * 128u + 64u + (uint32_t)__builtin_ctzll(left);
+}
+
+// One lane per pair, no LDS: the two suffixes at ranks r and r + 1 share their K key characters and are compared from there on
+// (walk_pair, the finisher's own walk).  Parted: both ranks are final -- SA in order, LCP[r + 1]; LCP[r] belongs to the level
+// above, as for every run head -- and their bits leave the bitmaps (atomically: the pairs of a window are on different lanes).
+// Not parted within WALK_CAP characters (copies longer than that, tails inside a run of one symbol): nothing is written, the
+// pair goes through the tie level, whose run keys cross a run in one step.
+__global__ void __launch_bounds__(256)
+k_pair_walk(const uint32_t* __restrict__ pairlist, unsigned long long* __restrict__ psc, uint32_t force, uint32_t min_permille,
+            uint32_t cap, const uint8_t* __restrict__ text, uint64_t n, KeyParams kp, uint32_t K, uint32_t* SA,
+            uint32_t* __restrict__ LCP, unsigned long long* wmask)
+{
+    if (!pair_path_taken(psc, force, min_permille)) return;
+    const unsigned long long listed = psc[PSC_PAIRS] < cap ? psc[PSC_PAIRS] : (unsigned long long)cap;
+    uint32_t done = 0;
+    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < listed; e += (uint64_t)gridDim.x * 256) {
+        const uint32_t r = pairlist[e];
+        const uint32_t s0 = SA[r], s1 = SA[r + 1];
+        const PairWalk w = walk_pair(text, n, kp, (uint64_t)s0 + K, (uint64_t)s1 + K);
+        if (!w.parted) continue;
+        if (!w.a_first) { SA[r] = s1; SA[r + 1] = s0; }
+        LCP[r + 1] = K + (uint32_t)w.k;
+        // position p: member bit in word 4 (p / 128) + (p / 64) % 2, head bit two words further
+        const size_t at = (size_t)(r >> 7) * 4 + ((r >> 6) & 1u);
+        const uint32_t bit = r & 63u;
+        atomicAnd(&wmask[at + 2], ~(1ull << bit));
+        if (bit != 63u) atomicAnd(&wmask[at], ~(3ull << bit));
+        else {
+            const uint32_t r1 = r + 1;
+            atomicAnd(&wmask[at], ~(1ull << 63));
+            atomicAnd(&wmask[(size_t)(r1 >> 7) * 4 + ((r1 >> 6) & 1u)], ~1ull);
+        }
+        done++;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) done += (uint32_t)__shfl_down(done, o, WAVE);
+    if (lane_id() == 0 && done) atomicAdd(&psc[PSC_RESOLVED + (((blockIdx.x * 256 + threadIdx.x) >> 6) & 63u)], (unsigned long long)done);
 }
 
 // heads[off[w]] = head position of window w's large group (off = exclusive scan of the window flags)

@@ -73,7 +73,7 @@ public:
     DevBuf recA, recB;                   // 12-byte records of the MSD levels, ping-pong
     DevBuf rankbuf, dposbuf, deferbuf, unresbuf, posbitsbuf, dblf[7], dblg[6];   // prefix doubling (sufr_dbl.inc)
     DevBuf headsA, headsB, sizes, starts, partials;
-    DevBuf tilefirst, runends, tileany, nexttile, nextblk, depthA, depthB, period, remapbuf, flagsbuf, packedbuf, wmaskbuf, wcntbuf, recoff, runoff, wlflag, wlhead, wloff, candbuf, keepbuf, plancnt, fixbuf;
+    DevBuf tilefirst, runends, tileany, nexttile, nextblk, depthA, depthB, period, remapbuf, flagsbuf, packedbuf, wmaskbuf, wcntbuf, recoff, runoff, wlflag, wlhead, wloff, candbuf, keepbuf, plancnt, fixbuf, pairsc, pairbuf;
     DevBuf rg_misc, rg_blk, rg_blkoff, rg_rs, rg_rl, rg_E, rg_L, rg_V, rg_tab[2], rg_off[2], rg_long[2], rg_tmax[2], rg_hist, rg_depth;   // run buckets (sufr_runs.inc)
     // MSD levels: digit maps, group / sub-bucket tables, segment lists, tile and window plans
     DevBuf cumbuf, dmapbuf, identbuf[16], grouptab, gcur, leafcnt, leafoff, leafbase, leafcur, bigflag, bigoff;
@@ -89,6 +89,13 @@ public:
     bool overlap_chains = true;    // probes: off = one chain after the other (rounds 1-5)
     static constexpr uint64_t OVERLAP_MIN_DEFAULT = (uint64_t)1 << 22;
     uint64_t opt_overlap_min = 0;  // left-over records from which their chain runs on the helper (sufr_hip_set_overlap_min; 0: the default, ~0: never)
+    // The pair path in front of the tie level (tie_level): tie runs of exactly two members are walked directly instead of being
+    // keyed.  Taken when the pairs hold at least PAIR_MIN_PERMILLE thousandths of the tie records.
+    // (the value: profiles/pair_walk_ab.txt, "threshold" -- measured on one MI355X: at ~15 per mille, the 100 Mb C. elegans stand-in,
+    // the path costs 0.014 ms of 1.17; at 96, the --dna build of the human stand-in, it saves 3.4 ms of 153.8; 50 lies between)
+    static constexpr uint32_t PAIR_MIN_PERMILLE = 50;
+    uint32_t opt_pair_walk = 0;    // sufr_hip_set_pair_walk: 0 the default (by the share of pairs), 1 always, 2 never
+    uint64_t last_pairs_resolved = 0, last_pairs_left = 0;   // the last build: pairs the path finished / walked and handed back (windowed builds: all windows)
     uint32_t last_overlapped = 0;  // the last build ran the left-over chain on the helper (windowed builds: one of the windows did)
     uint64_t dbl_entries = 0;      // entries into run_doubling by this pipeline in the current build
     uint64_t last_doublings = 0;   // ... of the last build, both chains (windowed builds: all windows)
@@ -370,7 +377,7 @@ public:
         (void)hipSetDevice(device);
         DevBuf* all[] = {&text, &bytehist, &lut, &table, &bintot, &binbase, &scalars, &keyA, &keyB, &idxA,
                          &idxB, &recA, &recB, &headsA, &headsB, &sizes, &starts, &partials, &sa32, &lcp32,
-                         &tilefirst, &runends, &tileany, &nexttile, &nextblk, &depthA, &depthB, &period, &remapbuf, &flagsbuf, &packedbuf, &wmaskbuf, &wcntbuf, &recoff, &runoff, &wlflag, &wlhead, &wloff, &candbuf, &keepbuf, &plancnt, &fixbuf,
+                         &tilefirst, &runends, &tileany, &nexttile, &nextblk, &depthA, &depthB, &period, &remapbuf, &flagsbuf, &packedbuf, &wmaskbuf, &wcntbuf, &recoff, &runoff, &wlflag, &wlhead, &wloff, &candbuf, &keepbuf, &plancnt, &fixbuf, &pairsc, &pairbuf,
                          &rg_misc, &rg_blk, &rg_blkoff, &rg_rs, &rg_rl, &rg_E, &rg_L, &rg_V, &rg_tab[0], &rg_tab[1], &rg_off[0], &rg_off[1], &rg_long[0], &rg_long[1], &rg_tmax[0], &rg_tmax[1], &rg_hist, &rg_depth,
                          &exc_pos, &exc_byte, &exc_sorted, &exc_sa, &exc_lcp, &exc_bits, &exc_blk, &exc_off, &exc_list, &exc_list2, &exc_pmin, &exc_roff, &exc_all_sa, &exc_all_lcp,
                          &cumbuf, &dmapbuf, &rawtab, &presbuf, &rawtot, &valsbuf, &startbuf, &grouptab, &gcur, &leafcnt, &leafoff, &leafbase, &leafcur, &bigflag, &bigoff,
@@ -400,7 +407,7 @@ public:
         if (also_text) { release(text); resident_text_len = 0; }
         DevBuf* big[] = {&recA, &recB, &keyA, &keyB, &idxA, &idxB, &packedbuf, &runends, &startbuf, &wmaskbuf, &wcntbuf, &fixbuf, &exc_sa, &exc_lcp, &exc_bits, &exc_all_sa, &exc_all_lcp,
                          &headsA, &headsB, &rankbuf, &dposbuf, &deferbuf, &unresbuf, &posbitsbuf, &depthA, &depthB, &period,
-                         &recoff, &runoff, &candbuf, &keepbuf, &optA, &optB, &optC, &optD, &optE};
+                         &recoff, &runoff, &candbuf, &keepbuf, &pairbuf, &optA, &optB, &optC, &optD, &optE};
         for (auto* b : big) if (b->cap >= ((size_t)16 << 20)) release(*b);
         for (auto& b : dblf) release(b);
         for (auto& b : dblg) release(b);
@@ -1744,7 +1751,7 @@ public:
                         uint32_t num_shards, uint32_t* d_sa, uint32_t* d_lcp, uint64_t cap,
                         uint64_t* num_suffixes_out, sufr_hip_stats* st_out)
     {
-        last_overlapped = 0; last_doublings = 0; dbl_entries = 0;
+        last_overlapped = 0; last_doublings = 0; dbl_entries = 0; last_pairs_resolved = 0; last_pairs_left = 0;
         if (helper) helper->dbl_entries = 0;
         if (!exc_disable) { last_exc_retry = 0; last_exc_taken = 0; }          // (the retry of a build keeps what that build recorded)
         const int rc = sort_build(d_in, n, flags, shard_index, num_shards, d_sa, d_lcp, cap, num_suffixes_out, st_out);
@@ -2648,6 +2655,8 @@ public:
         if ((rc = ensure(fixbuf, (size_t)fixcap * 4))) return rc;
         HIP_TRY(zero_later(wmaskbuf.p, (size_t)nwin * 32));
         HIP_TRY(zero_later(sc(SC_NFIX), 8));
+        if ((rc = ensure(pairsc, (size_t)PSC_N * 8))) return rc;
+        HIP_TRY(zero_later(pairsc.p, (size_t)PSC_N * 8));    // (the pair path's sums: tie_level)
         HIP_TRY(zero_flush());
         fo.SA = B.d_sa; fo.LCP = B.d_lcp; fo.wmask = (unsigned long long*)wmaskbuf.p; fo.fixlist = (uint32_t*)fixbuf.p;
         fo.nfix = (uint32_t*)sc(SC_NFIX); fo.fixcap = fixcap; fo.b = kp.b; fo.K = kp.K;
@@ -2761,8 +2770,7 @@ public:
         // LCP of every window's (and left-over group's) first record with the record before it
         hipLaunchKernelGGL(k_fix_window_lcp, dim3(1024), dim3(256), 0, stream, (const uint32_t*)fixbuf.p,
                            (const uint32_t*)sc(SC_NFIX), fixcap, (const Rec*)xr[1], B.d_lcp, kp.b, kp.K);
-        hipLaunchKernelGGL(k_tie_counts, dim3((nwin + 255) / 256), dim3(256), 0, stream,
-                           (const unsigned long long*)wmaskbuf.p, nwin, (uint32_t*)wcntbuf.p, B.wcnt_stride);
+        // (the counts of the tie bitmaps, k_tie_counts, are taken in tie_level: behind the pair path, which clears bits)
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ev[7], stream));
         B.st.num_levels = 1;
@@ -2876,9 +2884,38 @@ public:
         int rc;
         uint32_t* cnt = (uint32_t*)wcntbuf.p;
         const uint32_t* icur = d_sa;                   // tie members lie in SA in key order
-        // wcnt = [records per window | runs per window]: two exclusive scans give the dense offsets
         if ((rc = ensure(recoff, (size_t)nwin * 4))) return rc;
         if ((rc = ensure(runoff, (size_t)nwin * 4))) return rc;
+        // The pair path (exact builds): count the tie pairs per window, scan, list their ranks, walk them -- all queued ahead
+        // of the round trip below, under which the walk runs.  Whether the path pays is decided on the device, from the share of
+        // pairs among the tie records (pair_path_taken); the list holds m0 / 8 pairs, what lies beyond it stays with the level.
+        // (probes: with the finisher's pair walk switched off the path is off too -- the switch measures a build without walks)
+        const bool pair_path = !mql_fast && opt_pair_walk != 2u && !(finish_opts & (1u << 29));
+        const uint32_t pair_cap = m0 / 8u + 4096u;
+        unsigned long long psums[PSC_N];
+        if (pair_path) {
+            if ((rc = ensure(pairbuf, (size_t)pair_cap * 4))) return rc;
+            const uint32_t nblk = (nwin + 255u) / 256u;            // a workgroup per 256 windows
+            uint32_t* blkcnt = (uint32_t*)runoff.p; uint32_t* blkoff = (uint32_t*)recoff.p;       // (free until the scans below)
+            unsigned long long* psc = (unsigned long long*)pairsc.p;
+            const uint32_t force = opt_pair_walk == 1u ? 1u : 0u;
+            hipLaunchKernelGGL(k_pair_counts, dim3(nblk), dim3(256), 0, stream,
+                               (const unsigned long long*)wmaskbuf.p, nwin, blkcnt, psc);
+            if ((rc = scan_u32(blkcnt, nblk, blkoff, psc + PSC_PAIRS))) return rc;
+            hipLaunchKernelGGL(k_pair_list, dim3(nblk), dim3(256), 0, stream,
+                               (const unsigned long long*)wmaskbuf.p, nwin, (const uint32_t*)blkcnt, (const uint32_t*)blkoff,
+                               (const unsigned long long*)psc, force, PAIR_MIN_PERMILLE, pair_cap, (uint32_t*)pairbuf.p);
+            uint32_t grid = (pair_cap + 255u) / 256u;
+            if (grid > 8192u) grid = 8192u;                   // (the lanes stride over the list: its length is known on the device only)
+            hipLaunchKernelGGL(k_pair_walk, dim3(grid), dim3(256), 0, stream, (const uint32_t*)pairbuf.p, psc, force,
+                               PAIR_MIN_PERMILLE, pair_cap, (const uint8_t*)d_text, n, kp, (uint32_t)kp.K, d_sa, d_lcp,
+                               (unsigned long long*)wmaskbuf.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(read_at_sync(psums, psc, sizeof psums));
+        }
+        // wcnt = [records per window | runs per window]: two exclusive scans give the dense offsets
+        hipLaunchKernelGGL(k_tie_counts, dim3((nwin + 255) / 256), dim3(256), 0, stream,
+                           (const unsigned long long*)wmaskbuf.p, nwin, cnt, wcnt_stride);
         if ((rc = scan_u32((const uint32_t*)cnt, nwin, (uint32_t*)recoff.p, sc(SC_TMP0)))) return rc;
         unsigned long long tot2[2] = {0, 0};          // records in tie runs, tie runs, (and the fix-list length)
         if ((rc = scan_u32((const uint32_t*)(cnt + wcnt_stride), nwin, (uint32_t*)runoff.p, sc(SC_TMP1)))) return rc;
@@ -2889,6 +2926,16 @@ public:
         if ((uint32_t)nf > B.fixcap) { set_error("internal error: window list overflow"); return SUFR_HIP_E_HIP; }
         const unsigned long long tot_rec = tot2[0], tot_run = tot2[1];
         const uint32_t m2 = (uint32_t)tot_rec, L2 = (uint32_t)tot_run;
+        if (pair_path) {
+            unsigned long long members = 0, resolved = 0;
+            for (uint32_t i = 0; i < 64; i++) { members += psums[PSC_MEMBERS + i]; resolved += psums[PSC_RESOLVED + i]; }
+            const unsigned long long pairs = psums[PSC_PAIRS];
+            const bool taken = opt_pair_walk == 1u || 2ull * pairs * 1000ull >= members * (unsigned long long)PAIR_MIN_PERMILLE;   // (pair_path_taken)
+            const unsigned long long walked = taken ? (pairs < pair_cap ? pairs : (unsigned long long)pair_cap) : 0ull;
+            last_pairs_resolved += resolved; last_pairs_left += walked - resolved;
+            if (debug) fprintf(stderr, "[sufr_hip debug] pair path: tie records=%llu pairs=%llu %s resolved=%llu handed back=%llu\n",
+                               members, pairs, taken ? "walked" : "(too few: not walked)", resolved, walked - resolved);
+        }
         if (debug) fprintf(stderr, "[sufr_hip debug] tie level: runs=%u records=%u\n", L2, m2);
         if (m2 == 0) return 0;
         st.num_levels++;

@@ -641,8 +641,8 @@ int sort_device_wide(Pipeline& pl, const void* d_in, uint64_t n, uint32_t flags,
     pl.wide_text_len = 0;                                    // (set again when the build succeeds: what the shard stitch checks)
     // (sufr_hip_overlapped / sufr_hip_doublings speak of the whole build: every window's build adds to them)
     // (so do sufr_hip_exc_retry -- the largest over the windows -- and sufr_hip_exc_taken -- the last window that took ranks out)
-    struct Chains { Pipeline& p; uint32_t overlapped = 0; uint64_t doublings = 0; uint32_t exc_retry = 0; uint64_t exc_taken = 0;
-                    ~Chains() { p.last_overlapped = overlapped; p.last_doublings = doublings; p.last_exc_retry = exc_retry; p.last_exc_taken = exc_taken; } } chains{pl};
+    struct Chains { Pipeline& p; uint32_t overlapped = 0; uint64_t doublings = 0; uint32_t exc_retry = 0; uint64_t exc_taken = 0, pairs_resolved = 0, pairs_left = 0;
+                    ~Chains() { p.last_pairs_resolved = pairs_resolved; p.last_pairs_left = pairs_left; p.last_overlapped = overlapped; p.last_doublings = doublings; p.last_exc_retry = exc_retry; p.last_exc_taken = exc_taken; } } chains{pl};
     WidePlan plan = wide_plan(n, window, margin);
     // the order of the build: a window must hold every symbol a comparison of its own suffixes looks at
     WideOrder wo = {0, 0u, nullptr, 0u};
@@ -747,6 +747,7 @@ int sort_device_wide(Pipeline& pl, const void* d_in, uint64_t n, uint32_t flags,
             sufr_hip_stats wst;
             rc = pl.sort_device_u32(t + base, len, wflags, 0, 1, (uint32_t*)pl.sa32.p, (uint32_t*)pl.lcp32.p, len, &s, &wst);
             chains.overlapped |= pl.last_overlapped; chains.doublings += pl.last_doublings;
+            chains.pairs_resolved += pl.last_pairs_resolved; chains.pairs_left += pl.last_pairs_left;
             if (pl.last_exc_retry > chains.exc_retry) chains.exc_retry = pl.last_exc_retry;
             if (pl.last_exc_taken) chains.exc_taken = pl.last_exc_taken;
             if (rc) return rc;
