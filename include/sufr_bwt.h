@@ -3,7 +3,7 @@
  * array and the text alone; on the host and on the GPU (part of libsufr_hip.so).  The other analyses
  * (sufr_kmer.h, sufr_repeat.h, sufr_lz.h, sufr_shared.h) read SA + LCP; this header is the hand-over to FM-index tools,
  * run-length indexes and compressors: the arrays they are made of, and r, the number of runs, beside the z of sufr_lz.h.
- * The backward search itself is not part of the library.
+ * The library's own FM-index over these arrays, with backward search and locate, is sufr_fm.h.
  *
  * Definitions.  T, n, SA[0..s) and the index width w are exactly as in sufr_kmer.h.  No LCP array and no sequence starts
  * are needed; nothing here assumes that SA is sorted, only that its entries are text positions.

@@ -175,6 +175,20 @@ class BwtStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# every symbol include/sufr_fm.h declares
+FM_EXPORTS = ["sufr_file_fm_build", "sufr_fm_free", "sufr_fm_get_info", "sufr_fm_search_batch", "sufr_fm_locate_batch", "sufr_hip_fm_build",
+              "sufr_hip_fm_free", "sufr_hip_fm_get_info", "sufr_hip_fm_search_batch_device", "sufr_hip_fm_locate_batch_device"]
+
+
+class FmInfo(C.Structure):
+    """sufr_fm_info"""
+    _fields_ = [("ranks", C.c_uint64), ("symbols", C.c_uint64), ("block", C.c_uint64), ("stride", C.c_uint64), ("sample", C.c_uint64),
+                ("samples", C.c_uint64), ("bytes", C.c_uint64), ("width", C.c_uint32), ("end_byte", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class FileMeta(C.Structure):
     """sufr_file_meta"""
     _fields_ = [("version", C.c_uint8), ("is_dna", C.c_uint8), ("allow_ambiguity", C.c_uint8),
@@ -365,6 +379,18 @@ def lib() -> C.CDLL:
     L.sufr_hip_bwt_runs_device.restype = C.c_int
     L.sufr_hip_lf_device.argtypes = [vp, vp, vp]; L.sufr_hip_lf_device.restype = C.c_int
     L.sufr_hip_set_bwt_tile.argtypes = [vp, u64]; L.sufr_hip_set_bwt_tile.restype = C.c_int
+    # include/sufr_fm.h
+    L.sufr_file_fm_build.argtypes = [vp, u64, C.POINTER(vp), C.c_int]; L.sufr_file_fm_build.restype = C.c_int
+    L.sufr_fm_free.argtypes = [vp]; L.sufr_fm_free.restype = None
+    L.sufr_fm_get_info.argtypes = [vp, C.POINTER(FmInfo)]; L.sufr_fm_get_info.restype = C.c_int
+    L.sufr_fm_search_batch.argtypes = [vp, vp, vp, u64, vp, vp, C.c_int]; L.sufr_fm_search_batch.restype = C.c_int
+    L.sufr_fm_locate_batch.argtypes = [vp, vp, vp, u64, u64, vp, vp, u64, C.POINTER(u64), C.c_int]; L.sufr_fm_locate_batch.restype = C.c_int
+    L.sufr_hip_fm_build.argtypes = [vp, vp, u64, C.POINTER(vp)]; L.sufr_hip_fm_build.restype = C.c_int
+    L.sufr_hip_fm_free.argtypes = [vp]; L.sufr_hip_fm_free.restype = None
+    L.sufr_hip_fm_get_info.argtypes = [vp, C.POINTER(FmInfo)]; L.sufr_hip_fm_get_info.restype = C.c_int
+    L.sufr_hip_fm_search_batch_device.argtypes = [vp, vp, vp, vp, u64, vp, vp]; L.sufr_hip_fm_search_batch_device.restype = C.c_int
+    L.sufr_hip_fm_locate_batch_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]
+    L.sufr_hip_fm_locate_batch_device.restype = C.c_int
     _lib = L
     return L
 

@@ -28,6 +28,7 @@
 #include "../../include/sufr_repeat.h"
 #include "../../include/sufr_lz.h"
 #include "../../include/sufr_bwt.h"
+#include "../../include/sufr_fm.h"
 #include "../../include/sufr_shared.h"
 
 #include <hip/hip_runtime_api.h>
@@ -114,6 +115,12 @@ int usage(FILE* f)
             "                                       [--bwt FILE: the raw bytes, one per rank] [--lf FILE: the LF mapping, one raw little-endian\n"
             "                                       entry of the index width (4 or 8 bytes) per rank]\n"
             "                                       [--device ID: on that GPU; otherwise on the host] [-t THREADS] [-o OUT]\n"
+            "  fm           <SUFR> <QUERY>...       count, or with --locate locate, through an FM-index built from the file: backward\n"
+            "                                       search over checkpointed BWT blocks and a sampled suffix array instead of text and\n"
+            "                                       suffix array; the lines are those of count / locate.  Refused unless every text\n"
+            "                                       position is indexed, without seed mask and max_query_len, and the last byte occurs once\n"
+            "                                       [--locate [-a]] [-s|--sample Q (32): keep every suffix at a multiple of Q]\n"
+            "                                       [--max-hits N (0: all)] [-q|--reads FILE] [--device ID] [-t THREADS] [-o OUT]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -173,6 +180,8 @@ struct QueryArgs {
     uint64_t edits = 2;                         // edit: -d
     bool local_minima = false;                  // edit: -l
     bool cigar = false;                         // edit: -c
+    bool locate = false;                        // fm: --locate
+    uint64_t sample = 32;                       // fm: -s
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -279,6 +288,48 @@ int cmd_count(const QueryArgs& a)
     return 0;
 }
 
+// The lines of `sufr locate`: query qi has count(qi) hits (0: not found), suffix(qi, k) is the text position of hit k in rank
+// order.  `sufr fm --locate` prints through here too, with positions that no suffix array was read for.
+template <typename Count, typename Suffix>
+void print_located(sufr_file* f, FILE* out, bool abs, const std::vector<std::string>& queries, Count count, Suffix suffix)
+{
+    for (size_t qi = 0; qi < queries.size(); qi++) {
+        const std::string& q = queries[qi];
+        const uint64_t hits = count(qi);
+        if (!hits) {
+            fprintf(stderr, "%s not found\n", q.c_str());
+            continue;
+        }
+        if (abs) {
+            std::string line = q;
+            for (uint64_t k = 0; k < hits; k++) line += " " + std::to_string(suffix(qi, k));
+            fprintf(out, "%s\n", line.c_str());
+            continue;
+        }
+        // by sequence name, then position inside the sequence (lib.rs:513-518)
+        struct Pos { std::string name; uint64_t at; };
+        std::vector<Pos> ps;
+        for (uint64_t k = 0; k < hits; k++) {
+            const uint64_t sfx = suffix(qi, k);
+            const uint64_t i = sufr_file_sequence_of(f, sfx);
+            ps.push_back({sufr_file_sequence_name(f, i), sfx - sufr_file_sequence_start(f, i)});
+        }
+        std::stable_sort(ps.begin(), ps.end(), [](const Pos& x, const Pos& y) { return x.name != y.name ? x.name < y.name : x.at < y.at; });
+        fprintf(out, "%s\n", q.c_str());
+        std::string prev, buf;
+        for (const Pos& p : ps) {
+            if (p.name != prev) {
+                if (!buf.empty()) fprintf(out, "%s %s\n", prev.c_str(), buf.c_str());
+                prev = p.name; buf.clear();
+            }
+            if (!buf.empty()) buf += ",";
+            buf += std::to_string(p.at);
+        }
+        if (!buf.empty()) fprintf(out, "%s %s\n", prev.c_str(), buf.c_str());
+        fprintf(out, "//\n");
+    }
+}
+
 int cmd_locate(const QueryArgs& a)
 {
     OpenFile f(a.file);
@@ -287,41 +338,8 @@ int cmd_locate(const QueryArgs& a)
     const std::vector<std::string> queries = expand_queries(a.positional);
     std::vector<Hit> hits;
     if (!search_all(f, a, queries, hits)) return 1;
-    for (size_t qi = 0; qi < queries.size(); qi++) {
-        const std::string& q = queries[qi];
-        const uint64_t lo = hits[qi].lo, hi = hits[qi].hi;
-        if (!hits[qi].found) {
-            fprintf(stderr, "%s not found\n", q.c_str());
-            continue;
-        }
-        if (a.abs) {
-            std::string line = q;
-            for (uint64_t r = lo; r < hi; r++) line += " " + std::to_string(sufr_file_suffix(f, r));
-            fprintf(out.f, "%s\n", line.c_str());
-            continue;
-        }
-        // by sequence name, then position inside the sequence (lib.rs:513-518)
-        struct Pos { std::string name; uint64_t at; };
-        std::vector<Pos> ps;
-        for (uint64_t r = lo; r < hi; r++) {
-            const uint64_t sfx = sufr_file_suffix(f, r);
-            const uint64_t i = sufr_file_sequence_of(f, sfx);
-            ps.push_back({sufr_file_sequence_name(f, i), sfx - sufr_file_sequence_start(f, i)});
-        }
-        std::stable_sort(ps.begin(), ps.end(), [](const Pos& x, const Pos& y) { return x.name != y.name ? x.name < y.name : x.at < y.at; });
-        fprintf(out.f, "%s\n", q.c_str());
-        std::string prev, buf;
-        for (const Pos& p : ps) {
-            if (p.name != prev) {
-                if (!buf.empty()) fprintf(out.f, "%s %s\n", prev.c_str(), buf.c_str());
-                prev = p.name; buf.clear();
-            }
-            if (!buf.empty()) buf += ",";
-            buf += std::to_string(p.at);
-        }
-        if (!buf.empty()) fprintf(out.f, "%s %s\n", prev.c_str(), buf.c_str());
-        fprintf(out.f, "//\n");
-    }
+    print_located(f, out.f, a.abs, queries, [&](size_t qi) { return hits[qi].found ? hits[qi].hi - hits[qi].lo : 0; },
+                  [&](size_t qi, uint64_t k) { return sufr_file_suffix(f, hits[qi].lo + k); });
     return 0;
 }
 
@@ -507,6 +525,87 @@ bool named_queries(const QueryArgs& a, std::vector<std::string>& names, std::vec
         sufr_sequence_data_free(&sd);
     }
     return true;
+}
+
+// sufr fm: count, or with --locate locate, through an FM-index built from the file (include/sufr_fm.h): the lines are those
+// of `sufr count` / `sufr locate`, the path reads neither the text nor the suffix array once the index stands.
+int cmd_fm(const QueryArgs& a)
+{
+    OpenFile f(a.file);
+    OutFile out;
+    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    sufr_file_meta m;
+    sufr_file_metadata(f, &m);
+    const char* why = m.len_suffixes != m.text_len || !m.text_len ? "the file leaves text positions out (every position must be indexed: --dna needs --allow-ambiguity)"
+                      : m.seed_mask_len                           ? "the file was built with a seed mask"
+                      : m.max_query_len                           ? "the file was built with a max_query_len"
+                                                                  : nullptr;
+    const char* twice = "the last byte of the text occurs more than once";
+    if (why) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), why); return 1; }
+    std::vector<std::string> names, queries;
+    if (!named_queries(a, names, queries)) return 1;
+    const uint64_t nq = queries.size(), sample = a.locate ? (a.sample ? a.sample : 1) : 0;
+    std::string bytes;
+    std::vector<uint64_t> off(nq + 1, 0), lo(nq, 0), hi(nq, 0), loff(nq + 1, 0), pos64;
+    for (size_t i = 0; i < nq; i++) { bytes += queries[i]; off[i + 1] = bytes.size(); }
+    const int w = m.index_width;
+    auto hits_of = [&](size_t i) { const uint64_t h = hi[i] - lo[i]; return a.max_hits && h > a.max_hits ? a.max_hits : h; };
+    uint64_t total = 0;
+    std::vector<uint8_t> pos;                   // the positions, w bytes each
+    if (a.device < 0) {
+        sufr_fm* fm = nullptr;
+        int rc = sufr_file_fm_build(f, sample, &fm, a.threads);
+        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : "the build failed"); return 1; }
+        rc = sufr_fm_search_batch(fm, (const uint8_t*)bytes.data(), off.data(), nq, lo.data(), hi.data(), a.threads);
+        if (!rc && a.locate) {
+            for (size_t i = 0; i < nq; i++) total += hits_of(i);
+            pos.resize((total + 1) * w);
+            rc = sufr_fm_locate_batch(fm, lo.data(), hi.data(), nq, a.max_hits, loff.data(), pos.data(), total, &total, a.threads);
+        }
+        sufr_fm_free(fm);
+        if (rc) { fprintf(stderr, "Error: the FM-index search failed (%d)\n", rc); return 1; }
+    } else {
+        DeviceIndex dev(a.device, f);
+        if (!dev.up()) { fprintf(stderr, "Error: %s\n", dev.error()); return 1; }
+        sufr_hip_fm* fm = nullptr;
+        int rc = sufr_hip_fm_build(dev.ctx, dev.ix, sample, &fm);
+        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : dev.error()); return 1; }
+        sufr_hip_index_free(dev.ix);            // text and suffix array leave the device: the FM-index answers alone
+        dev.ix = nullptr;
+        // one allocation: queries | offsets | lo | hi | the offsets of locate; the positions once their number is known
+        const uint64_t o_at = (bytes.size() + 7) / 8 * 8, lo_at = o_at + (nq + 1) * 8, hi_at = lo_at + nq * 8, l_at = hi_at + nq * 8;
+        uint8_t *d = nullptr, *d_pos = nullptr;
+        bool ok = hipMalloc((void**)&d, l_at + (nq + 1) * 8) == hipSuccess && (bytes.empty() || hipMemcpy(d, bytes.data(), bytes.size(), hipMemcpyHostToDevice) == hipSuccess) &&
+                  hipMemcpy(d + o_at, off.data(), (nq + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
+        rc = ok ? sufr_hip_fm_search_batch_device(dev.ctx, fm, d, d + o_at, nq, d + lo_at, d + hi_at) : SUFR_HIP_E_HIP;
+        if (!rc) rc = sufr_hip_synchronize(dev.ctx);
+        ok = !rc && (!nq || (hipMemcpy(lo.data(), d + lo_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+                             hipMemcpy(hi.data(), d + hi_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess));
+        if (ok && a.locate) {
+            for (size_t i = 0; i < nq; i++) total += hits_of(i);
+            pos.resize((total + 1) * w);
+            ok = hipMalloc((void**)&d_pos, (total + 1) * w) == hipSuccess;
+            rc = ok ? sufr_hip_fm_locate_batch_device(dev.ctx, fm, d + lo_at, d + hi_at, nq, a.max_hits, d + l_at, d_pos, total, &total) : SUFR_HIP_E_HIP;
+            if (!rc) rc = sufr_hip_synchronize(dev.ctx);
+            ok = ok && !rc && hipMemcpy(loff.data(), d + l_at, (nq + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+                 (!total || hipMemcpy(pos.data(), d_pos, total * w, hipMemcpyDeviceToHost) == hipSuccess);
+        }
+        if (!ok) fprintf(stderr, "Error: %s\n", rc ? dev.error() : "device memory for the query batch");
+        if (d_pos) (void)hipFree(d_pos);
+        if (d) (void)hipFree(d);
+        sufr_hip_fm_free(fm);
+        if (!ok) return 1;
+    }
+    if (!a.locate) {
+        for (size_t i = 0; i < nq; i++) fprintf(out.f, "%s %llu\n", names[i].c_str(), (unsigned long long)(hi[i] - lo[i]));
+        return 0;
+    }
+    print_located(f, out.f, a.abs, names, [&](size_t qi) { return loff[qi + 1] - loff[qi]; }, [&](size_t qi, uint64_t k) {
+        uint64_t p = 0;
+        memcpy(&p, pos.data() + (loff[qi] + k) * w, w);               // (little-endian entries of 4 or 8 bytes)
+        return p;
+    });
+    return 0;
 }
 
 // What match, mems, approx and edit hold while they run: the .sufr file, the output, the named queries packed into one
@@ -730,19 +829,23 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     std::vector<std::string> pos;
     auto need = value_reader(argc, argv);
     const bool is_list = cmd == "list", is_extract = cmd == "extract", is_locate = cmd == "locate", is_sum = cmd == "summarize";
-    const bool is_edit = cmd == "edit";
+    const bool is_edit = cmd == "edit", is_fm = cmd == "fm";
     const bool is_approx = cmd == "approx" || is_edit;
     const bool is_mems = cmd == "mems";
     const bool is_match = cmd == "match" || is_mems || is_approx;
     for (int i = first; i < argc; i++) {
         const std::string s = argv[i];
         if (s == "-h" || s == "--help") { usage(stdout); return 0; }
-        else if (!is_list && !is_sum && !is_match && (s == "-m" || s == "--max-query-len")) { a.has_mql = true; a.mql = strtoull(need(i, "-m"), nullptr, 10); }
+        else if (is_fm && s == "--locate") a.locate = true;
+        else if (is_fm && (s == "-s" || s == "--sample")) a.sample = strtoull(need(i, "-s"), nullptr, 10);
+        else if (is_fm && s == "--max-hits") a.max_hits = strtoull(need(i, "--max-hits"), nullptr, 10);
+        else if (is_fm && (s == "-t" || s == "--threads")) a.threads = atoi(need(i, "-t"));
+        else if (!is_list && !is_sum && !is_match && !is_fm && (s == "-m" || s == "--max-query-len")) { a.has_mql = true; a.mql = strtoull(need(i, "-m"), nullptr, 10); }
         else if (!is_sum && (s == "-o" || s == "--output")) a.output = need(i, "-o");
         else if (!is_list && !is_sum && ((s == "-l" && !is_edit) || s == "--low-memory")) {}   // access mode only: the file is mapped (edit: -l is --local-minima)
         else if (!is_sum && (s == "-v" || s == "--very-low-memory")) {}
         else if (!is_list && !is_sum && s == "--device") a.device = atoi(need(i, "--device"));
-        else if ((is_locate || is_match) && (s == "-a" || s == "--abs")) a.abs = true;
+        else if ((is_locate || is_match || is_fm) && (s == "-a" || s == "--abs")) a.abs = true;
         else if (is_match && !is_approx && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
         else if ((is_mems || is_approx) && s == "--max-occ") a.max_occ = strtoull(need(i, "--max-occ"), nullptr, 10);
         else if ((is_mems || is_approx) && (s == "-b" || s == "--both-strands")) a.both_strands = true;
@@ -751,7 +854,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         else if (is_edit && (s == "-c" || s == "--cigar")) a.cigar = true;
         else if (is_approx && !is_edit && (s == "-d" || s == "--mismatches")) a.mismatches = strtoull(need(i, "-d"), nullptr, 10);
         else if (is_match && !is_mems && !is_approx && (s == "-n" || s == "--max-hits")) a.max_hits = strtoull(need(i, "-n"), nullptr, 10);
-        else if (is_match && (s == "-q" || s == "--reads")) a.reads = need(i, "-q");
+        else if ((is_match || is_fm) && (s == "-q" || s == "--reads")) a.reads = need(i, "-q");
         else if (is_extract && (s == "-p" || s == "--prefix-len")) { a.has_prefix = true; a.prefix_len = strtoull(need(i, "-p"), nullptr, 10); }
         else if (is_extract && (s == "-s" || s == "--suffix-len")) { a.has_suffix = true; a.suffix_len = strtoull(need(i, "-s"), nullptr, 10); }
         else if (is_list && (s == "-r" || s == "--show-rank")) a.show_rank = true;
@@ -770,12 +873,13 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     if (pos.empty()) { fprintf(stderr, "error: the following required arguments were not provided:\n  <%s>\n", is_list ? "FILE" : "SUFR"); return 2; }
     a.file = pos[0];
     a.positional.assign(pos.begin() + 1, pos.end());
-    if (!is_list && !is_sum && a.positional.empty() && !(is_match && !a.reads.empty())) {
+    if (!is_list && !is_sum && a.positional.empty() && !((is_match || is_fm) && !a.reads.empty())) {
         fprintf(stderr, "error: the following required arguments were not provided:\n  <QUERY>...\n");
         return 2;
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
+    if (is_fm) return cmd_fm(a);
     if (is_edit) return cmd_edit(a);
     if (is_approx) return cmd_approx(a);
     if (is_mems) return cmd_mems(a);
@@ -1267,6 +1371,7 @@ int main(int argc, char** argv)
         else if (!have_cmd && s == "shared") return run_shared(argc, argv, i + 1, threads);
         else if (!have_cmd && s == "lz") return run_lz(argc, argv, i + 1, threads);
         else if (!have_cmd && s == "bwt") return run_bwt(argc, argv, i + 1, threads);
+        else if (!have_cmd && s == "fm") return run_query("fm", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "approx" || s == "ap")) return run_query("approx", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "edit" || s == "ed")) return run_query("edit", argc, argv, i + 1, threads);
         else if (!have_cmd && (s == "extract" || s == "ex")) return run_query("extract", argc, argv, i + 1, threads);

@@ -1,0 +1,439 @@
+// sufr_fm.inc -- the FM-index over the BWT of a device-resident index: its build, the backward search and the locate that
+// reads neither the text nor the suffix array (included by sufr_kernels.hip after sufr_bwt.inc; include/sufr_fm.h, DESIGN.md
+// section 23).  The layout and the arithmetic are sufr_fm_scan.h, which the host path compiles too.
+//
+// Build.  The BWT goes to scratch of the context by k_bwt_gather, which also counts the bytes; one synchronisation reads the
+// counts and the end byte, which decide the refusal, K and with it the shape of a block.  The tiles of the build are those of
+// sufr_hip_set_bwt_tile cut down to whole blocks and whole mark words (fm_tile); there is one tile more than the ranks need
+// where they fill the last one, for the trailing block.  k_bwt_cols, k_bwt_tile_hist and k_bwt_col_scan (sufr_bwt.inc) leave the
+// number of ranks of every occurring byte value before every tile.  Then
+// k_fm_blocks      a workgroup per tile, the tile's bytes in LDS: a lane per (block, byte value) counts the value in the block
+//                  with fm_eq_bytes, a lane per byte value adds the counts up from the tile's base and writes the checkpoints
+//                  of every block, all lanes copy the bytes.  With samples: the marks SA[r] % q == 0 as ballot words, and the
+//                  number of marks of the tile (an LDS sum: no order in it).
+// k_locate_scan    (sufr_search.inc) the tiles' mark counts into bases and the number of samples: the second synchronisation.
+// k_fm_samples     a workgroup per tile: the marks before every word (a popcount prefix over the tile's words behind the
+//                  tile's base) and the kept values in rank order -- the count and write passes of the runs of sufr_bwt.inc.
+// No result comes from the arrival order of an atomic: two builds give the same bytes.
+//
+// k_fm_search      a lane per query.  A step needs occ at lo and at hi, two independent blocks: in the one-line shape (32 bytes
+//                  of counts and 96 of BWT in 128) both blocks are loaded whole, twelve 16-byte loads and the two counts in
+//                  flight before any is used; in the wide shapes the two blocks are read side by side, 16 bytes at a time, up
+//                  to the rank.  C and the columns are in LDS.  The steps of a query depend on each other; nothing is read
+//                  behind the query or behind a block.
+// k_fm_locate      k_locate_counts / k_locate_scan / k_locate_apply size the output as for sufr_hip_locate_batch_device; then a
+//                  lane per hit walks LF steps to a marked rank and stores kept + steps.
+// No scratch.  LDS: k_fm_blocks 34 KB, k_fm_samples 4 KB, k_fm_search and k_fm_locate 3 KB.
+
+#include "sufr_fm_scan.h"
+
+struct sufr_hip_fm {
+    int device = 0;
+    sufr::FmView V{};                  // device addresses
+    uint64_t samples = 0;
+    void *blocks = nullptr, *marks = nullptr, *kept = nullptr, *tabs = nullptr;      // the allocations: tabs = C (257 u64), col (256 u32)
+};
+
+namespace sufr {
+
+static constexpr uint32_t FM_PAIRS_MAX = BWT_TILE_MAX / 4;            // (block, byte value) pairs of a tile: B >= K w >= 4 K
+
+// the one-line shape: the constants the compiler may fold
+template <bool LINE> __device__ __forceinline__ uint32_t fm_B(const FmShape& sh) { return LINE ? 96u : sh.B; }
+template <bool LINE> __device__ __forceinline__ uint32_t fm_stride(const FmShape& sh) { return LINE ? 128u : sh.stride; }
+template <bool LINE> __device__ __forceinline__ uint32_t fm_cbytes(const FmShape& sh) { return LINE ? 32u : sh.cbytes; }
+static inline bool fm_is_line(const FmShape& sh) { return sh.B == 96 && sh.stride == 128 && sh.cbytes == 32 && sh.w == 4; }
+
+__device__ __forceinline__ uint64_t fm_ld(const uint8_t* p, uint32_t w) { return w == 4 ? (uint64_t)*(const uint32_t*)p : *(const uint64_t*)p; }
+
+// how many of the bytes [at, at + 16) of a block's BWT, of which the first rem count, equal the byte of pat
+__device__ __forceinline__ uint32_t fm_eq16(const uint4& x, uint32_t pat, uint32_t rem, uint32_t at)
+{
+    const uint32_t have = rem > at ? rem - at : 0;
+    return fm_eq_bytes(x.x, pat, have) + fm_eq_bytes(x.y, pat, have > 4 ? have - 4 : 0) + fm_eq_bytes(x.z, pat, have > 8 ? have - 8 : 0) +
+           fm_eq_bytes(x.w, pat, have > 12 ? have - 12 : 0);
+}
+
+// a = C[c] + occ(c, a) and b = C[c] + occ(c, b) for the byte value c of column k; base = C[c]
+template <bool LINE>
+__device__ __forceinline__ void fm_occ_pair(const FmView& V, uint32_t c, uint32_t k, uint64_t base, uint64_t& a, uint64_t& b)
+{
+    const uint32_t B = fm_B<LINE>(V.sh), pat = c * 0x01010101u;
+    const uint8_t* pa = V.blocks + a / B * fm_stride<LINE>(V.sh);
+    const uint8_t* pb = V.blocks + b / B * fm_stride<LINE>(V.sh);
+    const uint32_t ra = (uint32_t)(a % B), rb = (uint32_t)(b % B), w = LINE ? 4u : V.sh.w;
+    uint64_t na = fm_ld(pa + k * w, w), nb = fm_ld(pb + k * w, w);
+    const uint4* va = (const uint4*)(pa + fm_cbytes<LINE>(V.sh));
+    const uint4* vb = (const uint4*)(pb + fm_cbytes<LINE>(V.sh));
+    if (LINE) {
+        uint4 xa[6], xb[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) { xa[i] = va[i]; xb[i] = vb[i]; }
+#pragma unroll
+        for (int i = 0; i < 6; i++) { na += fm_eq16(xa[i], pat, ra, 16u * i); nb += fm_eq16(xb[i], pat, rb, 16u * i); }
+    } else {
+        const uint32_t far = ra > rb ? ra : rb;
+        for (uint32_t at = 0; at < far; at += 16) {      // (at < rem <= B: inside the block)
+            const uint4 zero = make_uint4(0, 0, 0, 0);
+            const uint4 xa = at < ra ? va[at / 16] : zero, xb = at < rb ? vb[at / 16] : zero;
+            na += fm_eq16(xa, pat, ra, at);
+            nb += fm_eq16(xb, pat, rb, at);
+        }
+    }
+    a = base + na;
+    b = base + nb;
+}
+
+// base + occ(c, r) for the byte value c of column k, r = the block at p plus rem ranks: the one occ of an LF step
+template <bool LINE>
+__device__ __forceinline__ uint64_t fm_occ_one(const FmView& V, uint32_t c, uint32_t k, uint64_t base, const uint8_t* p, uint32_t rem)
+{
+    const uint32_t pat = c * 0x01010101u, w = LINE ? 4u : V.sh.w;
+    uint64_t n = fm_ld(p + k * w, w);
+    const uint4* v = (const uint4*)(p + fm_cbytes<LINE>(V.sh));
+    if (LINE) {
+        uint4 x[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) x[i] = v[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) n += fm_eq16(x[i], pat, rem, 16u * i);
+    } else {
+        for (uint32_t at = 0; at < rem; at += 16) n += fm_eq16(v[at / 16], pat, rem, at);      // (at < rem <= B: inside the block)
+    }
+    return base + n;
+}
+
+// C and the columns of an index into LDS (257 and 256 entries), by the 256 lanes of a workgroup
+__device__ __forceinline__ void fm_stage_tables(const FmView& V, uint64_t* s_C, uint32_t* s_col)
+{
+    s_C[threadIdx.x] = V.C[threadIdx.x];
+    s_col[threadIdx.x] = V.col[threadIdx.x];
+    if (threadIdx.x == 0) s_C[256] = V.C[256];
+    __syncthreads();
+}
+
+template <bool LINE>
+__global__ __launch_bounds__(256) void k_fm_search(FmView V, const uint8_t* __restrict__ queries, const uint64_t* __restrict__ qoff, uint64_t nq,
+                                                   uint64_t* __restrict__ lo_out, uint64_t* __restrict__ hi_out)
+{
+    __shared__ uint64_t s_C[257];
+    __shared__ uint32_t s_col[256];
+    fm_stage_tables(V, s_C, s_col);
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    const uint8_t* P = queries + qoff[i];
+    const uint64_t m = qoff[i + 1] - qoff[i];
+    uint64_t a = 0, b = m ? 0 : V.s;                                 // (the empty query: every rank)
+    if (m) {
+        uint32_t c = P[m - 1], next = m > 1 ? P[m - 2] : 0;
+        if (s_col[c] != FM_NO_COL) { a = s_C[c]; b = s_C[c + 1]; }
+        for (uint64_t j = m - 1; j-- > 0 && a < b;) {
+            c = next;
+            next = j ? P[j - 1] : 0;                              // (the byte of the next step is under way while this one's blocks are)
+            const uint32_t k = s_col[c];
+            if (k == FM_NO_COL || c == V.e) { a = b = 0; break; }      // (the end byte stands only at the last place)
+            fm_occ_pair<LINE>(V, c, k, s_C[c], a, b);
+        }
+    }
+    const bool found = a < b;
+    lo_out[i] = found ? a : 0;
+    hi_out[i] = found ? b : 0;
+}
+
+template <bool LINE>
+__global__ __launch_bounds__(256) void k_fm_locate(FmView V, const uint64_t* __restrict__ lo, const uint64_t* __restrict__ off, uint64_t nq,
+                                                   uint64_t total, uint32_t* __restrict__ positions, uint64_t* __restrict__ positions64)
+{
+    __shared__ uint64_t s_C[257];
+    __shared__ uint32_t s_col[256];
+    fm_stage_tables(V, s_C, s_col);
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= total) return;
+    const uint64_t q = last_le(off, 0, nq, j);                       // the query whose slice holds output j
+    uint64_t r = lo[q] + (j - off[q]), p = ~(uint64_t)0;
+    const uint32_t B = fm_B<LINE>(V.sh);
+    if (r < V.s) {
+        for (uint64_t k = 0; k < V.q; k++) {
+            const FmMark mk = V.marks[r >> 6];
+            const uint8_t* pb = V.blocks + r / B * fm_stride<LINE>(V.sh);
+            const uint32_t rem = (uint32_t)(r % B);
+            const uint32_t c = pb[fm_cbytes<LINE>(V.sh) + rem];
+            if (fm_marked(mk, r)) { p = fm_ld(V.kept + fm_slot(mk, r) * V.sh.w, V.sh.w) + k; break; }
+            r = fm_occ_one<LINE>(V, c, s_col[c], s_C[c], pb, rem);
+        }
+    }
+    if (positions64) positions64[j] = p; else positions[j] = (uint32_t)p;
+}
+
+// The blocks of tile t and, with a sampling rate q, its mark words and t_cnt[t], the number of its marks.  tab: the ranks of
+// every column before the tile (k_bwt_col_scan)
+template <typename T>
+__global__ __launch_bounds__(256) void k_fm_blocks(const T* __restrict__ sa, const uint8_t* __restrict__ bwt, uint64_t s, uint32_t tile, uint64_t ntiles,
+                                                   FmShape sh, const uint32_t* __restrict__ col, const uint64_t* __restrict__ tab, uint64_t q,
+                                                   uint8_t* __restrict__ blocks, FmMark* __restrict__ marks, uint64_t* __restrict__ t_cnt)
+{
+    __shared__ uint32_t s_w[BWT_TILE_MAX / 4], s_cnt[FM_PAIRS_MAX], s_sym[256], s_marks;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t K = sh.K, B = sh.B, bw = B / 4;
+    if (col[threadIdx.x] != FM_NO_COL) s_sym[col[threadIdx.x]] = threadIdx.x;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t base = t * tile;
+        const uint32_t len = (uint32_t)(s - base < tile ? s - base : tile);
+        const uint32_t nblk = t + 1 < ntiles ? tile / B : len / B + 1;             // (the last tile is short: its last block is the trailing one)
+        const uint32_t* src = (const uint32_t*)(bwt + base);                         // (base is a multiple of 32, the array padded to a dword)
+        if (threadIdx.x == 0) s_marks = 0;
+        for (uint32_t i = threadIdx.x; i < nblk * bw; i += 256) {
+            uint32_t word = 4 * i < len ? src[i] : 0;
+            if (4 * i < len && len - 4 * i < 4) word &= (1u << (8 * (len - 4 * i))) - 1u;      // zero behind the array's end
+            s_w[i] = word;
+        }
+        __syncthreads();
+        for (uint32_t p = threadIdx.x; p < nblk * K; p += 256) {
+            const uint32_t j = p / K, pat = s_sym[p % K] * 0x01010101u;
+            const uint32_t have = len > j * B ? (len - j * B < B ? len - j * B : B) : 0;
+            uint32_t n = 0;
+            for (uint32_t i = 0; 4 * i < have; i++) n += fm_eq_bytes(s_w[j * bw + i], pat, have - 4 * i);
+            s_cnt[p] = n;
+        }
+        __syncthreads();
+        uint8_t* out = blocks + base / B * sh.stride;
+        if (threadIdx.x < sh.cbytes / sh.w) {             // a lane per count of a block, the unused ones behind the K zero
+            uint64_t run = threadIdx.x < K ? tab[t * K + threadIdx.x] : 0;
+            for (uint32_t j = 0; j < nblk; j++) {
+                uint8_t* at = out + (uint64_t)j * sh.stride + threadIdx.x * sh.w;
+                if (sh.w == 4) *(uint32_t*)at = (uint32_t)run; else *(uint64_t*)at = run;
+                if (threadIdx.x < K) run += s_cnt[j * K + threadIdx.x];
+            }
+        }
+        for (uint32_t i = threadIdx.x; i < nblk * bw; i += 256)
+            ((uint32_t*)(out + (uint64_t)(i / bw) * sh.stride + sh.cbytes))[i % bw] = s_w[i];
+        if (q) {
+            for (uint32_t it = 0; it < len; it += 256) {    // (uniform: every lane of a wave takes part in the ballot)
+                const uint32_t i = it + threadIdx.x;
+                const uint64_t m = __ballot(i < len && (uint64_t)sa[base + (i < len ? i : 0)] % q == 0);
+                if (lane == 0 && it + 64 * wave < len) {
+                    marks[(base >> 6) + (it >> 6) + wave].bits = m;
+                    atomicAdd(&s_marks, (uint32_t)__builtin_popcountll(m));           // (a sum: any order)
+                }
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) t_cnt[t] = s_marks;
+        }
+        __syncthreads();                                 // (the LDS arrays are the next tile's)
+    }
+}
+
+// t_cnt[t]: the marks before tile t (k_locate_scan).  The marks before every word of the tile, and the kept suffixes
+template <typename T>
+__global__ __launch_bounds__(256) void k_fm_samples(const T* __restrict__ sa, uint64_t s, uint32_t tile, uint64_t ntiles, const uint64_t* __restrict__ t_cnt,
+                                                    FmMark* __restrict__ marks, T* __restrict__ kept)
+{
+    __shared__ uint64_t s_bits[BWT_TILE_MAX / 64], s_pf[BWT_TILE_MAX / 64], s_sc[4];
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t base = t * tile;
+        const uint32_t len = (uint32_t)(s - base < tile ? s - base : tile), nwords = (len + 63) / 64;
+        const uint64_t bits = threadIdx.x < nwords ? marks[(base >> 6) + threadIdx.x].bits : 0;
+        uint64_t v[1] = {(uint64_t)__builtin_popcountll(bits)}, tot[1];
+        wg_scan(v, tot, s_sc);
+        const uint64_t before = t_cnt[t] + v[0];
+        if (threadIdx.x < nwords) marks[(base >> 6) + threadIdx.x].before = before;
+        s_bits[threadIdx.x] = bits;
+        s_pf[threadIdx.x] = before;
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < len; i += 256) {
+            const FmMark mk{s_bits[i >> 6], s_pf[i >> 6]};
+            if (fm_marked(mk, i)) kept[fm_slot(mk, i)] = sa[base + i];
+        }
+        __syncthreads();                                 // (the LDS arrays are the next tile's)
+    }
+}
+
+}  // namespace sufr
+
+namespace {
+
+uint64_t fm_device_bytes(const sufr_hip_fm* fm)
+{
+    const sufr::FmView& V = fm->V;
+    return sufr::fm_blocks(V.s, V.sh.B) * V.sh.stride + (V.q ? sufr::fm_mark_words(V.s) * sizeof(sufr::FmMark) + fm->samples * V.sh.w : 0) + 257 * 8 + 256 * 4;
+}
+
+int fm_alloc(sufr::Pipeline& pl, void** p, uint64_t bytes, const char* what)
+{
+    if (hipMalloc(p, bytes ? bytes : 1) == hipSuccess) return 0;
+    *p = nullptr;
+    (void)hipGetLastError();
+    pl.set_error(std::string("fm_build: hipMalloc of the ") + what + " (" + std::to_string(bytes) + " bytes) failed");
+    return SUFR_HIP_E_NOMEM;
+}
+
+template <typename T>
+int fm_build_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, sufr_hip_fm* fm)
+{
+    sufr::Pipeline& pl = ctx->pl;
+    const uint64_t s = ix->ix.s, n = ix->ix.n;
+    int rc;
+    // bwtsum: the 256 counts, the number of samples, then the tiles' mark counts (fm_tile gives more than half of the tile it
+    // is given, so there are 2 s / bwt_tile + 1 tiles at most)
+    if ((rc = pl.ensure(ctx->bwtbytes, s + 8)) || (rc = pl.ensure(ctx->bwtsum, (257 + 2 * s / bwt_tile(ctx) + 2) * 8))) return rc;
+    uint8_t* bwt = (uint8_t*)ctx->bwtbytes.p;
+    unsigned long long* counts = (unsigned long long*)ctx->bwtsum.p;
+    if (hipMemsetAsync(counts, 0, 256 * 8, pl.stream) != hipSuccess) { pl.set_error("fm_build: memset failed"); return SUFR_HIP_E_HIP; }
+    bwt_gather<T>(ctx, ix, bwt, counts, nullptr);
+    unsigned long long h[256];
+    uint8_t e = 0;
+    const bool copied = hipMemcpyAsync(&e, ix->ix.text + (n - 1), 1, hipMemcpyDeviceToHost, pl.stream) == hipSuccess &&
+                        hipMemcpyAsync(h, counts, 256 * 8, hipMemcpyDeviceToHost, pl.stream) == hipSuccess;
+    if (hipStreamSynchronize(pl.stream) != hipSuccess || !copied) { pl.set_error("fm_build: reading the byte counts and the end byte failed"); return SUFR_HIP_E_HIP; }
+    if ((rc = launch_status(pl, "fm_build"))) return rc;
+    if (h[e] != 1) {
+        pl.set_error("fm_build: the last byte of the text occurs " + std::to_string(h[e]) + " times among the indexed positions, not once");
+        return SUFR_HIP_E_UNSUPPORTED;
+    }
+    uint32_t K = 0;
+    for (int c = 0; c < 256; c++) K += h[c] ? 1 : 0;
+    sufr::FmView& V = fm->V;
+    V.s = s; V.q = sample; V.e = e; V.sh = sufr::fm_shape(K, (uint32_t)ix->sa_width);
+    const sufr::FmShape sh = V.sh;
+    const uint32_t tile = (uint32_t)sufr::fm_tile(sh.B, bwt_tile(ctx));
+    const uint64_t ntiles = s / tile + 1, nblocks = sufr::fm_blocks(s, sh.B), nwords = sufr::fm_mark_words(s);
+    if ((rc = pl.ensure(ctx->bwttab, ntiles * K * 8))) return rc;
+    uint64_t* d_total = (uint64_t*)ctx->bwtsum.p + 256;
+    uint64_t* t_cnt = d_total + 1;
+    if ((rc = fm_alloc(pl, &fm->blocks, nblocks * sh.stride, "blocks")) || (rc = fm_alloc(pl, &fm->tabs, 257 * 8 + 256 * 4, "tables")) ||
+        (sample && (rc = fm_alloc(pl, &fm->marks, nwords * sizeof(sufr::FmMark), "marks")))) return rc;
+    uint64_t* d_C = (uint64_t*)fm->tabs;
+    uint32_t* d_col = (uint32_t*)(d_C + 257);
+    V.blocks = (const uint8_t*)fm->blocks; V.marks = (const sufr::FmMark*)fm->marks; V.C = d_C; V.col = d_col;
+    if (hipMemcpyAsync(d_C + 256, &V.s, 8, hipMemcpyHostToDevice, pl.stream) != hipSuccess) { pl.set_error("fm_build: copying C[256] failed"); return SUFR_HIP_E_HIP; }
+    const uint64_t wgs = batch_grid(pl);
+    const uint32_t grid = (uint32_t)(ntiles < wgs ? ntiles : wgs);
+    const T* sa = index_sa<T>(ix);
+    uint64_t* tab = (uint64_t*)ctx->bwttab.p;
+    hipLaunchKernelGGL(sufr::k_bwt_cols, dim3(1), dim3(256), 0, pl.stream, (const unsigned long long*)counts, d_C, d_col);
+    hipLaunchKernelGGL(sufr::k_bwt_tile_hist, dim3(grid), dim3(256), 0, pl.stream, (const uint8_t*)bwt, s, tile, ntiles, (const uint32_t*)d_col, K, tab);
+    hipLaunchKernelGGL(sufr::k_bwt_col_scan, dim3(K), dim3(1024), 0, pl.stream, tab, ntiles, K);
+    hipLaunchKernelGGL(sufr::k_fm_blocks<T>, dim3(grid), dim3(256), 0, pl.stream, sa, (const uint8_t*)bwt, s, tile, ntiles, sh, (const uint32_t*)d_col,
+                       (const uint64_t*)tab, sample, (uint8_t*)fm->blocks, (sufr::FmMark*)fm->marks, t_cnt);
+    if (sample) {
+        hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, t_cnt, ntiles, d_total);
+        unsigned long long total = 0;
+        if ((rc = launch_status(pl, "fm_build")) || (rc = read_totals(pl, d_total, 1, &total, "fm_build", "counting the samples failed"))) return rc;
+        fm->samples = total;
+        if ((rc = fm_alloc(pl, &fm->kept, total * sh.w, "samples"))) return rc;
+        V.kept = (const uint8_t*)fm->kept;
+        hipLaunchKernelGGL(sufr::k_fm_samples<T>, dim3(grid), dim3(256), 0, pl.stream, sa, s, tile, ntiles, (const uint64_t*)t_cnt, (sufr::FmMark*)fm->marks,
+                           (T*)fm->kept);
+    }
+    if ((rc = launch_status(pl, "fm_build"))) return rc;
+    if (hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("fm_build: the build failed"); return SUFR_HIP_E_HIP; }      // nothing reads ix from here on
+    return 0;
+}
+
+int fm_check(sufr_hip_ctx* ctx, const sufr_hip_fm* fm)
+{
+    ctx->pl.err.clear();
+    if (fm->device != ctx->pl.device) { ctx->pl.set_error("the FM-index lives on another device"); return SUFR_HIP_E_INVALID; }
+    if (hipSetDevice(ctx->pl.device) != hipSuccess) { ctx->pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sufr_hip_fm_free(sufr_hip_fm* fm)
+{
+    if (!fm) return;
+    (void)hipSetDevice(fm->device);
+    for (void* p : {fm->blocks, fm->marks, fm->kept, fm->tabs}) if (p) (void)hipFree(p);
+    delete fm;
+}
+
+int sufr_hip_fm_build(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, sufr_hip_fm** out)
+{
+    if (!ctx || !ix || !out) return SUFR_HIP_E_INVALID;
+    *out = nullptr;
+    ctx->pl.err.clear();
+    if (const int rc = query_check(ctx, ix)) return rc;
+    const char* why = !ix->ix.n || ix->ix.s != ix->ix.n ? "the index leaves text positions out"
+                      : ix->ix.maskpos                 ? "the index was built with a seed mask"
+                      : ix->built_mql                  ? "the index was built with a max_query_len"
+                                                       : nullptr;
+    if (why) { ctx->pl.set_error(std::string("fm_build: ") + why); return SUFR_HIP_E_UNSUPPORTED; }
+    sufr_hip_fm* fm = new sufr_hip_fm;
+    fm->device = ctx->pl.device;
+    const int rc = by_width(ix, [&](auto w) { return fm_build_run<decltype(w)>(ctx, ix, sample, fm); });
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->pl.stream);                 // (nothing in flight writes what is freed)
+        sufr_hip_fm_free(fm);
+        return rc;
+    }
+    *out = fm;
+    return 0;
+}
+
+int sufr_hip_fm_get_info(const sufr_hip_fm* fm, sufr_fm_info* info)
+{
+    if (!fm || !info) return SUFR_HIP_E_INVALID;
+    const sufr::FmView& V = fm->V;
+    *info = sufr_fm_info{V.s, V.sh.K, V.sh.B, V.sh.stride, V.q, fm->samples, fm_device_bytes(fm), V.sh.w, V.e};
+    return 0;
+}
+
+int sufr_hip_fm_search_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const void* d_queries, const void* d_offsets, uint64_t num_queries,
+                                    void* d_rank_lo, void* d_rank_hi)
+{
+    if (!ctx || !fm || (num_queries && (!d_queries || !d_offsets || !d_rank_lo || !d_rank_hi))) return SUFR_HIP_E_INVALID;
+    if (const int rc = fm_check(ctx, fm)) return rc;
+    if (!num_queries) return 0;
+    const uint64_t blocks = (num_queries + 255) / 256;
+    if (blocks > 0x7fffffffull) { ctx->pl.set_error("fm_search: too many queries in one batch"); return SUFR_HIP_E_INVALID; }
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->pl.stream, fm->V, (const uint8_t*)d_queries, (const uint64_t*)d_offsets,
+                           num_queries, (uint64_t*)d_rank_lo, (uint64_t*)d_rank_hi);
+    };
+    if (sufr::fm_is_line(fm->V.sh)) launch(sufr::k_fm_search<true>); else launch(sufr::k_fm_search<false>);
+    return launch_status(ctx->pl, "fm_search");
+}
+
+int sufr_hip_fm_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const void* d_rank_lo, const void* d_rank_hi, uint64_t num_queries,
+                                    uint64_t max_hits, void* d_offsets, void* d_positions, uint64_t cap, uint64_t* total_out)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !fm || !d_offsets || (num_queries && (!d_rank_lo || !d_rank_hi))) return SUFR_HIP_E_INVALID;
+    sufr::Pipeline& pl = ctx->pl;
+    int rc;
+    if ((rc = fm_check(ctx, fm))) return rc;
+    if (!fm->V.q) { pl.set_error("fm_locate: the index was built without samples (sample == 0)"); return SUFR_HIP_E_UNSUPPORTED; }
+    const uint64_t nblk = (num_queries + sufr::LOC_BLK - 1) / sufr::LOC_BLK;
+    if ((rc = pl.ensure(pl.scalars, sufr::Pipeline::SC_N * 8)) || (rc = pl.ensure(pl.partials, (size_t)(nblk + 1) * 8))) return rc;
+    unsigned long long total = 0;
+    uint64_t* off = (uint64_t*)d_offsets;
+    if (num_queries) {
+        hipLaunchKernelGGL(sufr::k_locate_counts, dim3((uint32_t)nblk), dim3(256), 0, pl.stream, (const uint64_t*)d_rank_lo, (const uint64_t*)d_rank_hi,
+                           num_queries, max_hits, off, (uint64_t*)pl.partials.p);
+        hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, (uint64_t*)pl.partials.p, nblk, (uint64_t*)pl.sc(sufr::Pipeline::SC_TOTAL));
+        hipLaunchKernelGGL(sufr::k_locate_apply, dim3((uint32_t)((num_queries + 256) / 256)), dim3(256), 0, pl.stream, off, num_queries,
+                           (const uint64_t*)pl.partials.p, (const uint64_t*)pl.sc(sufr::Pipeline::SC_TOTAL));
+        if ((rc = read_totals(pl, pl.sc(sufr::Pipeline::SC_TOTAL), 1, &total, "fm_locate", "counting the matches failed"))) return rc;
+    } else if (hipMemsetAsync(d_offsets, 0, 8, pl.stream) != hipSuccess) { pl.set_error("fm_locate: memset failed"); return SUFR_HIP_E_HIP; }
+    if (total_out) *total_out = total;
+    if (total > cap) {
+        pl.set_error("fm_locate: " + std::to_string(total) + " positions, room for " + std::to_string(cap) + " (raise the capacity or set max_hits)");
+        return SUFR_HIP_E_CAPACITY;
+    }
+    if (!total) return 0;
+    if (!d_positions) return SUFR_HIP_E_INVALID;
+    const uint64_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffull) { pl.set_error("fm_locate: too many positions for one launch"); return SUFR_HIP_E_INVALID; }
+    const bool wide = fm->V.sh.w == 8;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, pl.stream, fm->V, (const uint64_t*)d_rank_lo, (const uint64_t*)off, num_queries,
+                           (uint64_t)total, wide ? (uint32_t*)nullptr : (uint32_t*)d_positions, wide ? (uint64_t*)d_positions : (uint64_t*)nullptr);
+    };
+    if (sufr::fm_is_line(fm->V.sh)) launch(sufr::k_fm_locate<true>); else launch(sufr::k_fm_locate<false>);
+    return launch_status(pl, "fm_locate");
+}
+
+}  // extern "C"

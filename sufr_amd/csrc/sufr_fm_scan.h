@@ -1,0 +1,128 @@
+// sufr_fm_scan.h -- the layout and the arithmetic of the FM-index over the BWT of the indexed text (include/sufr_fm.h,
+// DESIGN.md section 23): the shape of a block, the count of a byte value in the front of a block, occ, the backward search
+// of one query and the walk from a rank to a sampled suffix.  Plain integer code that the kernels of sufr_fm.inc and the host
+// path of sufr_query.cpp both compile (SUFR_HD, the way of sufr_bwt_scan.h); there is no second copy of it.  The kernels read
+// a block with wider loads than fm_occ does and count with the same fm_eq_bytes.
+//
+// Blocks.  Block j serves the ranks [j B, (j + 1) B): `cbytes` bytes of checkpoints -- for every byte value that occurs, in
+// the order of the values, the number of ranks before j B with that BWT byte, w bytes each (w: the index width) -- and behind
+// them the B bytes BWT[j B ..], zero where the array has ended.  There are s / B + 1 blocks, so that occ(c, s) has its
+// checkpoints where s is a multiple of B.  With cbytes = K w rounded up to 32,
+//     stride = the power of two that holds two cbytes, 128 at least;   B = stride - cbytes:
+// K <= 8 at w = 4 gives 32 + 96 in one aligned 128-byte line, the granularity of a gather, so an occ is
+// one line; 23 amino acids at w = 4 give 96 + 160 in 256, all 256 byte values 1024 + 1024 (w = 4) or 2048 + 2048 (w = 8).  B is
+// a multiple of 32 and never below cbytes: the BWT bytes are at least half of every block.
+//
+// Marks.  One FmMark per 64 ranks: bit i of `bits` says that SA[64 k + i] is a multiple of the sampling rate and was kept,
+// `before` is the number of kept values in front of rank 64 k.  16 bytes per 64 ranks at both index widths.
+#pragma once
+#include <stdint.h>
+
+#include "sufr_bwt_scan.h"
+
+namespace sufr {
+
+static constexpr uint32_t FM_NO_COL = 0xFFFFFFFFu;      // the column of a byte value that does not occur (BWT_NO_COL of sufr_bwt.inc)
+
+struct FmShape { uint32_t K, w, cbytes, B, stride; };
+
+SUFR_HD FmShape fm_shape(uint32_t K, uint32_t w)
+{
+    FmShape sh{K, w, (K * w + 31u) & ~31u, 0, 128};
+    if (sh.cbytes == 0) sh.cbytes = 32;                  // (an empty array: one block of no counts)
+    while (sh.stride < 2 * sh.cbytes) sh.stride *= 2;
+    sh.B = sh.stride - sh.cbytes;
+    return sh;
+}
+
+// The ranks of a tile of the build: whole blocks and whole mark words, `ranks` at most and one of each at least
+SUFR_HD uint64_t fm_tile(uint32_t B, uint64_t ranks)
+{
+    const uint64_t unit = B % 64 ? 2 * (uint64_t)B : B;  // (B is a multiple of 32)
+    return ranks < unit ? unit : ranks / unit * unit;
+}
+
+SUFR_HD uint64_t fm_blocks(uint64_t s, uint32_t B) { return s / B + 1; }
+SUFR_HD uint64_t fm_mark_words(uint64_t s) { return (s + 63) / 64; }
+
+struct FmMark { uint64_t bits, before; };
+
+// How many of the first `have` bytes of a dword (in memory order; 4 and more: all) equal the byte whose four copies are pat
+SUFR_HD uint32_t fm_eq_bytes(uint32_t word, uint32_t pat, uint32_t have)
+{
+    const uint32_t x = word ^ pat;
+    const uint32_t zero = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);        // 0x80 in every byte of x that is 0
+    return (uint32_t)__builtin_popcount(zero & (have >= 4 ? 0xFFFFFFFFu : (1u << (8 * have)) - 1u));
+}
+
+SUFR_HD uint64_t fm_rd(const uint8_t* p, uint32_t w)
+{
+    if (w == 4) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+    uint64_t v; __builtin_memcpy(&v, p, 8); return v;
+}
+
+// What a query reads.  C: 257 entries, C[c] the ranks with a smaller BWT byte, C[256] = s; col: 256 entries
+struct FmView {
+    const uint8_t* blocks;
+    const FmMark* marks;
+    const uint8_t* kept;                                 // the kept suffixes in rank order, w bytes each
+    const uint64_t* C;
+    const uint32_t* col;
+    uint64_t s, q;                                       // q: the sampling rate, 0 where there are no samples
+    FmShape sh;
+    uint32_t e;                                          // T[n - 1]
+};
+
+// occ(c, r) = #{ j < r : BWT[j] == c } for a byte value c that occurs and r <= s; nothing behind the block of r is read
+SUFR_HD uint64_t fm_occ(const FmView& V, uint32_t c, uint64_t r)
+{
+    const uint8_t* p = V.blocks + r / V.sh.B * V.sh.stride;
+    const uint32_t rem = (uint32_t)(r % V.sh.B), pat = c * 0x01010101u;
+    uint64_t n = fm_rd(p + V.col[c] * V.sh.w, V.sh.w);
+    p += V.sh.cbytes;
+    for (uint32_t i = 0; i < rem; i += 4) {
+        uint32_t word;
+        __builtin_memcpy(&word, p + i, 4);
+        n += fm_eq_bytes(word, pat, rem - i);
+    }
+    return n;
+}
+
+// May byte c stand at place i of a query of m bytes?  Not where it does not occur, and the end byte only at the last place:
+// the one row whose BWT byte is the end byte is the cyclic one
+SUFR_HD bool fm_byte_ok(const FmView& V, uint32_t c, uint64_t i, uint64_t m) { return V.col[c] != FM_NO_COL && (c != V.e || i + 1 == m); }
+
+// The rank range of P[0..m): lo == hi == 0 where it does not occur; every rank for the empty query, which every suffix
+// begins with (the answer of sufr_file_search)
+SUFR_HD void fm_search(const FmView& V, const uint8_t* P, uint64_t m, uint64_t& lo, uint64_t& hi)
+{
+    lo = hi = 0;
+    if (!m) { hi = V.s; return; }
+    if (!fm_byte_ok(V, P[m - 1], m - 1, m)) return;
+    uint64_t a = V.C[P[m - 1]], b = V.C[P[m - 1] + 1u];
+    for (uint64_t i = m - 1; i-- > 0 && a < b;) {
+        const uint32_t c = P[i];
+        if (!fm_byte_ok(V, c, i, m)) return;
+        a = V.C[c] + fm_occ(V, c, a);
+        b = V.C[c] + fm_occ(V, c, b);
+    }
+    if (a < b) { lo = a; hi = b; }
+}
+
+SUFR_HD bool fm_marked(const FmMark& mk, uint64_t r) { return (mk.bits >> (r & 63u)) & 1u; }
+SUFR_HD uint64_t fm_slot(const FmMark& mk, uint64_t r) { return mk.before + (uint64_t)__builtin_popcountll(mk.bits & (((uint64_t)1 << (r & 63u)) - 1)); }
+
+// SA[r] for r < s of an index with samples: LF steps to a kept rank, fewer than q of them (position 0 is kept, so the cyclic
+// row is never stepped through); ~0 where q steps find none, which only arrays that are no suffix array can cause
+SUFR_HD uint64_t fm_position(const FmView& V, uint64_t r)
+{
+    for (uint64_t k = 0; k < V.q; k++) {
+        const FmMark mk = V.marks[r >> 6];
+        if (fm_marked(mk, r)) return fm_rd(V.kept + fm_slot(mk, r) * V.sh.w, V.sh.w) + k;
+        const uint32_t c = V.blocks[r / V.sh.B * V.sh.stride + V.sh.cbytes + r % V.sh.B];
+        r = V.C[c] + fm_occ(V, c, r);
+    }
+    return ~(uint64_t)0;
+}
+
+}  // namespace sufr

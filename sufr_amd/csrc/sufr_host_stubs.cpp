@@ -24,6 +24,7 @@
 #include "../../include/sufr_lz.h"
 #include "../../include/sufr_shared.h"
 #include "../../include/sufr_bwt.h"
+#include "../../include/sufr_fm.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -191,5 +192,14 @@ int sufr_hip_bwt_runs_device(sufr_hip_ctx* ctx, const sufr_hip_index*, uint64_t,
 }
 int sufr_hip_lf_device(sufr_hip_ctx* ctx, const sufr_hip_index*, void*) { return no_device(ctx); }
 int sufr_hip_set_bwt_tile(sufr_hip_ctx* ctx, uint64_t) { return no_device(ctx); }
+
+// ---- include/sufr_fm.h: the device side (the host side is sufr_query.cpp) -------------------------------------------
+struct sufr_hip_fm { int unused; };
+int sufr_hip_fm_build(sufr_hip_ctx* ctx, const sufr_hip_index*, uint64_t, sufr_hip_fm** out) { if (out) *out = nullptr; return no_device(ctx); }
+void sufr_hip_fm_free(sufr_hip_fm*) {}
+int sufr_hip_fm_get_info(const sufr_hip_fm*, sufr_fm_info*) { return SUFR_HIP_E_NO_DEVICE; }
+int sufr_hip_fm_search_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const void*, const void*, uint64_t, void*, void*) { return no_device(ctx); }
+int sufr_hip_fm_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const void*, const void*, uint64_t, uint64_t, void*, void*, uint64_t,
+                                    uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 
 }  // extern "C"

@@ -1496,3 +1496,158 @@ int sufr_file_lf(const sufr_file* f, void* lf, int threads)
 }
 
 }  // extern "C"
+
+// ---- the FM-index over the BWT: backward search and locate without text and suffix array (include/sufr_fm.h, DESIGN.md
+// section 23) ---------------------------------------------------------------------------------------------------------
+#include "../../include/sufr_fm.h"
+#include "sufr_fm_scan.h"
+
+struct sufr_fm {
+    sufr::FmShape sh{};
+    uint64_t s = 0, q = 0, samples = 0;
+    uint32_t e = 0;
+    uint64_t C[257] = {0};
+    uint32_t col[256];
+    std::vector<uint8_t> blocks, kept;
+    std::vector<sufr::FmMark> marks;
+    sufr::FmView view() const { return sufr::FmView{blocks.data(), marks.data(), kept.data(), C, col, s, q, sh, e}; }
+};
+
+namespace {
+
+// what sufr_fm_info says of an index of this shape: the blocks, the marks, the kept values, C (257 u64) and the columns (256 u32)
+uint64_t fm_bytes(const sufr::FmShape& sh, uint64_t s, uint64_t q, uint64_t samples)
+{
+    return sufr::fm_blocks(s, sh.B) * sh.stride + (q ? sufr::fm_mark_words(s) * sizeof(sufr::FmMark) + samples * sh.w : 0) + 257 * 8 + 256 * 4;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_fm_build(const sufr_file* f, uint64_t sample, sufr_fm** out, int threads)
+{
+    if (!f || !out) return SUFR_HIP_E_INVALID;
+    *out = nullptr;
+    const uint64_t s = f->meta.len_suffixes, n = f->meta.text_len;
+    if (!n || s != n || f->meta.seed_mask_len || f->meta.max_query_len) return SUFR_HIP_E_UNSUPPORTED;
+    const std::vector<uint8_t> bwt = bwt_host_bytes(*f, threads);
+    uint64_t counts[256] = {0};
+    parallel_chunks(s, BWT_HOST_TILE, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t hist[256] = {0};
+        for (uint64_t r = b; r < e; r++) hist[bwt[r]]++;
+        for (int c = 0; c < 256; c++) if (hist[c]) __atomic_fetch_add(&counts[c], hist[c], __ATOMIC_RELAXED);      // (sums: any order)
+    });
+    sufr_fm* fm = new sufr_fm;
+    fm->s = s; fm->q = sample; fm->e = f->text[n - 1];
+    if (counts[fm->e] != 1) { delete fm; return SUFR_HIP_E_UNSUPPORTED; }
+    uint32_t K = 0, sym[256];
+    for (uint32_t c = 0; c < 256; c++) {
+        fm->C[c + 1] = fm->C[c] + counts[c];
+        fm->col[c] = counts[c] ? K : sufr::FM_NO_COL;
+        if (counts[c]) sym[K++] = c;
+    }
+    const int w = f->meta.index_width;
+    const sufr::FmShape sh = fm->sh = sufr::fm_shape(K, (uint32_t)w);
+    // tiles of whole blocks and whole mark words, whatever the number of workers; the last one is short, or empty where s is
+    // a multiple of the tile: it holds the trailing block.  tab[t K + k]: the ranks of tile t with byte sym[k], then of all
+    // the tiles before it
+    const uint64_t tile = sufr::fm_tile(sh.B, BWT_HOST_TILE), ntiles = s / tile + 1, nblocks = sufr::fm_blocks(s, sh.B);
+    std::vector<uint64_t> tab(ntiles * K, 0);
+    parallel_chunks(ntiles, 1, threads, [&](uint64_t t, uint64_t) {
+        uint64_t hist[256] = {0};
+        for (uint64_t r = t * tile, end = r + tile < s ? r + tile : s; r < end; r++) hist[bwt[r]]++;
+        for (uint32_t k = 0; k < K; k++) tab[t * K + k] = hist[sym[k]];
+    });
+    for (uint32_t k = 0; k < K; k++) {
+        uint64_t run = 0;
+        for (uint64_t t = 0; t < ntiles; t++) { const uint64_t v = tab[t * K + k]; tab[t * K + k] = run; run += v; }
+    }
+    fm->blocks.assign(nblocks * sh.stride, 0);
+    parallel_chunks(ntiles, 1, threads, [&](uint64_t t, uint64_t) {
+        uint64_t run[256] = {0};                                     // by byte value: the ranks before the block
+        for (uint32_t k = 0; k < K; k++) run[sym[k]] = tab[t * K + k];
+        const uint64_t j1 = (t + 1) * tile / sh.B < nblocks ? (t + 1) * tile / sh.B : nblocks;
+        for (uint64_t j = t * tile / sh.B; j < j1; j++) {
+            uint8_t* p = fm->blocks.data() + j * sh.stride;
+            for (uint32_t k = 0; k < K; k++) kmer_put(p, w, k, run[sym[k]]);
+            const uint64_t b = j * sh.B, len = s - b < sh.B ? s - b : sh.B;
+            memcpy(p + sh.cbytes, bwt.data() + b, len);
+            for (uint64_t i = 0; i < len; i++) run[bwt[b + i]]++;
+        }
+    });
+    if (sample) {
+        const uint64_t nwords = sufr::fm_mark_words(s);
+        fm->marks.assign(nwords, sufr::FmMark{0, 0});
+        std::vector<uint64_t> kept(ntiles + 1, 0);                   // per tile: the kept ranks, then those of the tiles before it
+        parallel_chunks(ntiles, 1, threads, [&](uint64_t t, uint64_t) {
+            uint64_t cnt = 0;
+            for (uint64_t r = t * tile, end = r + tile < s ? r + tile : s; r < end; r++)
+                if (rdT(f->sa, w, r) % sample == 0) { fm->marks[r >> 6].bits |= (uint64_t)1 << (r & 63u); cnt++; }
+            kept[t] = cnt;
+        });
+        for (uint64_t t = 0; t < ntiles; t++) { const uint64_t k = kept[t]; kept[t] = fm->samples; fm->samples += k; }
+        fm->kept.assign(fm->samples * w, 0);
+        parallel_chunks(ntiles, 1, threads, [&](uint64_t t, uint64_t) {
+            uint64_t o = kept[t];
+            for (uint64_t r = t * tile, end = r + tile < s ? r + tile : s; r < end; r++) {
+                if (!(r & 63u)) fm->marks[r >> 6].before = o;
+                if (sufr::fm_marked(fm->marks[r >> 6], r)) kmer_put(fm->kept.data(), w, o++, rdT(f->sa, w, r));
+            }
+        });
+    }
+    *out = fm;
+    return 0;
+}
+
+void sufr_fm_free(sufr_fm* fm) { delete fm; }
+
+int sufr_fm_get_info(const sufr_fm* fm, sufr_fm_info* info)
+{
+    if (!fm || !info) return SUFR_HIP_E_INVALID;
+    *info = sufr_fm_info{fm->s, fm->sh.K, fm->sh.B, fm->sh.stride, fm->q, fm->samples, fm_bytes(fm->sh, fm->s, fm->q, fm->samples), fm->sh.w, fm->e};
+    return 0;
+}
+
+int sufr_fm_search_batch(const sufr_fm* fm, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint64_t* rank_lo, uint64_t* rank_hi,
+                         int threads)
+{
+    if (!fm || (nq && (!offsets || !rank_lo || !rank_hi)) || (nq && offsets[nq] > offsets[0] && !queries)) return SUFR_HIP_E_INVALID;
+    for (uint64_t i = 0; i < nq; i++) if (offsets[i + 1] < offsets[i]) return SUFR_HIP_E_INVALID;
+    const sufr::FmView V = fm->view();
+    parallel_chunks(nq, 256, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t i = b; i < e; i++) sufr::fm_search(V, queries + offsets[i], offsets[i + 1] - offsets[i], rank_lo[i], rank_hi[i]);
+    }, 64);
+    return 0;
+}
+
+int sufr_fm_locate_batch(const sufr_fm* fm, const uint64_t* rank_lo, const uint64_t* rank_hi, uint64_t nq, uint64_t max_hits, uint64_t* offsets,
+                         void* positions, uint64_t cap, uint64_t* total_out, int threads)
+{
+    if (total_out) *total_out = 0;
+    if (!fm || !offsets || (nq && (!rank_lo || !rank_hi))) return SUFR_HIP_E_INVALID;
+    if (!fm->q) return SUFR_HIP_E_UNSUPPORTED;
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < nq; i++) {
+        if (rank_lo[i] > rank_hi[i] || rank_hi[i] > fm->s) return SUFR_HIP_E_INVALID;
+        const uint64_t hits = rank_hi[i] - rank_lo[i];
+        offsets[i] = total;
+        total += max_hits && hits > max_hits ? max_hits : hits;
+    }
+    offsets[nq] = total;
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!positions) return SUFR_HIP_E_INVALID;
+    const sufr::FmView V = fm->view();
+    parallel_chunks(total, 256, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t a = query_of(offsets, nq, b);
+        for (uint64_t g = b; g < e; g++) {
+            while (offsets[a + 1] <= g) a++;
+            kmer_put(positions, (int)V.sh.w, g, sufr::fm_position(V, rank_lo[a] + (g - offsets[a])));
+        }
+    }, 64);
+    return 0;
+}
+
+}  // extern "C"

@@ -664,6 +664,18 @@ class SufrFile:
         _bwt_check("sufr_file_lf", lib().sufr_file_lf(self._h, out.ctypes.data, threads))
         return out[:s]
 
+    # -- the FM-index over the BWT (include/sufr_fm.h) ---------------------------------------------------------------------
+    def fm(self, sample: int = 32, threads: int = 0) -> "FmIndex":
+        """An FM-index of this file on the host: it answers search_batch and locate without the text and the suffix array and
+        owns what it reads, so the file may be closed.  sample: every suffix at a multiple of it is kept for locate (0: none,
+        no locate).  Refused (-6) unless every position is indexed, there is no seed mask and no max_query_len, and the last
+        byte of the text occurs once."""
+        h = C.c_void_p()
+        rc = lib().sufr_file_fm_build(self._h, sample, C.byref(h), threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_file_fm_build: " + {-6: _FM_REFUSED}.get(rc, "failed"))
+        return FmIndex(h, self.index_width)
+
     def _sequence_of(self, suffix: int) -> int:
         return lib().sufr_file_sequence_of(self._h, suffix)
 
@@ -747,6 +759,159 @@ def pack_queries(queries: Sequence) -> Tuple[np.ndarray, np.ndarray]:
     if bs:
         off[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
     return np.frombuffer(b"".join(bs), dtype=np.uint8).copy(), off
+
+
+_FM_REFUSED = ("the FM-index takes an index of every text position (no --dna without --allow-ambiguity), built without a seed mask and "
+               "without a max_query_len, over a text whose last byte occurs once")
+
+
+def _fm_info(call, handle) -> dict:
+    from ._lib import FmInfo
+    info = FmInfo()
+    rc = call(handle, C.byref(info))
+    if rc != 0:
+        raise SufrHipError(rc, "reading the info of the FM-index failed")
+    return info.as_dict()
+
+
+def _counts(queries: Sequence, lo, hi) -> List[CountResult]:
+    return [CountResult(i, q if isinstance(q, str) else bytes(q).decode("latin-1"), int(hi[i] - lo[i])) for i, q in enumerate(queries)]
+
+
+class FmIndex:
+    """The FM-index of a .sufr file on the host (SufrFile.fm; include/sufr_fm.h): checkpointed BWT blocks, mark words and the
+    kept suffixes.  It reads neither the file's text nor its suffix array."""
+
+    def __init__(self, handle, index_width: int):
+        self._h, self.index_width = handle, index_width
+
+    @property
+    def info(self) -> dict:
+        """ranks, symbols (K), block (B), stride, sample, samples, bytes, width, end_byte (sufr_fm_info)"""
+        return _fm_info(lib().sufr_fm_get_info, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sufr_fm_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def search_packed(self, qbytes: np.ndarray, offsets: np.ndarray, threads: int = 0):
+        nq = len(offsets) - 1
+        lo, hi = np.zeros(nq, dtype=np.uint64), np.zeros(nq, dtype=np.uint64)
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        rc = lib().sufr_fm_search_batch(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, lo.ctypes.data, hi.ctypes.data, threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_fm_search_batch failed")
+        return lo, hi
+
+    def search_batch(self, queries: Sequence, threads: int = 0):
+        """rank_lo, rank_hi (uint64 arrays, lo == hi == 0: not found): the ranges of SufrFile.search_batch."""
+        return self.search_packed(*pack_queries(queries), threads)
+
+    def count(self, queries: Sequence, threads: int = 0) -> List[CountResult]:
+        return _counts(queries, *self.search_batch(queries, threads))
+
+    def locate_ranges(self, lo: np.ndarray, hi: np.ndarray, max_hits: int = 0, threads: int = 0):
+        """(offsets uint64[nq + 1], positions of the index width): query i owns positions[offsets[i]:offsets[i + 1]], the
+        suffixes of ranks lo[i] .. min(hi[i], lo[i] + max_hits) in rank order (max_hits 0: all)."""
+        lo, hi = np.ascontiguousarray(lo, dtype=np.uint64), np.ascontiguousarray(hi, dtype=np.uint64)
+        cnt = hi - lo
+        cap = int((np.minimum(cnt, np.uint64(max_hits)) if max_hits else cnt).sum())
+        off = np.zeros(lo.size + 1, dtype=np.uint64)
+        pos = np.zeros(max(cap, 1), dtype=np.uint64 if self.index_width == 8 else np.uint32)
+        total = C.c_uint64(0)
+        rc = lib().sufr_fm_locate_batch(self._h, lo.ctypes.data, hi.ctypes.data, lo.size, max_hits, off.ctypes.data, pos.ctypes.data, cap,
+                                        C.byref(total), threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_fm_locate_batch: " + {-6: "the index was built without samples (sample == 0)",
+                                                              -1: "invalid rank ranges"}.get(rc, "failed"))
+        return off, pos[:total.value]
+
+    def locate(self, queries: Sequence, max_hits: int = 0, threads: int = 0) -> List[np.ndarray]:
+        """Text positions of every query's matches in rank order (unsigned arrays of the index's width)."""
+        o, p = self.locate_ranges(*self.search_batch(queries, threads), max_hits, threads)
+        return [p[int(o[i]):int(o[i + 1])] for i in range(len(queries))]
+
+
+class DeviceFmIndex:
+    """The FM-index of a DeviceIndex in HBM (DeviceIndex.fm_device; include/sufr_fm.h).  It owns everything it reads: the
+    DeviceIndex may be closed and wrapped tensors overwritten.  The calls mirror DeviceIndex.search_device / locate_device."""
+
+    def __init__(self, ctx: Context, handle, index_width: int):
+        self.ctx, self._h, self.index_width = ctx, handle, index_width
+
+    @property
+    def info(self) -> dict:
+        return _fm_info(lib().sufr_hip_fm_get_info, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sufr_hip_fm_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def search_device(self, qbytes, offsets, wait: bool = True):
+        """torch CUDA tensors in (uint8 bytes, int64 offsets), int64 CUDA tensors (lo, hi) out; see DeviceIndex.search_device
+        for `wait` and the streams."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        lo = torch.empty(nq, dtype=torch.int64, device=offsets.device)
+        hi = torch.empty(nq, dtype=torch.int64, device=offsets.device)
+        self.ctx.check(lib().sufr_hip_fm_search_batch_device(self.ctx.handle, self._h, DeviceIndex._device_bytes(qbytes).data_ptr(), offsets.data_ptr(),
+                                                            nq, lo.data_ptr(), hi.data_ptr()))
+        if wait:
+            self.ctx.synchronize()
+        return lo, hi
+
+    def locate_device(self, lo, hi, max_hits: int = 0, capacity: Optional[int] = None):
+        """(offsets int64[nq + 1], positions) on the device for rank ranges on the device, as DeviceIndex.locate_device returns
+        them: int32 holding u32 values, or int64 for a 64-bit index.  Complete on return."""
+        import torch
+        nq = lo.numel()
+        off = torch.empty(nq + 1, dtype=torch.int64, device=lo.device)
+        total = C.c_uint64(0)
+        torch.cuda.current_stream(lo.device).synchronize()
+        if capacity is None:                                   # size the output from the counts
+            cnt = hi - lo
+            capacity = int((cnt.clamp(max=max_hits) if max_hits else cnt).sum())
+        pos = torch.empty(max(capacity, 1), dtype=torch.int64 if self.index_width == 8 else torch.int32, device=lo.device)
+        self.ctx.check(lib().sufr_hip_fm_locate_batch_device(self.ctx.handle, self._h, lo.data_ptr(), hi.data_ptr(), nq, max_hits, off.data_ptr(),
+                                                            pos.data_ptr(), capacity, C.byref(total)))
+        self.ctx.synchronize()
+        return off, pos[:total.value]
+
+    def _packed(self, queries: Sequence):
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        return torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev)
+
+    def search(self, queries: Sequence) -> Tuple[np.ndarray, np.ndarray]:
+        """rank_lo, rank_hi (uint64 arrays; lo == hi == 0 where the query does not occur)."""
+        lo, hi = self.search_device(*self._packed(queries))
+        return lo.cpu().numpy().view(np.uint64), hi.cpu().numpy().view(np.uint64)
+
+    def count(self, queries: Sequence) -> List[CountResult]:
+        return _counts(queries, *self.search(queries))
+
+    def locate(self, queries: Sequence, max_hits: int = 0) -> List[np.ndarray]:
+        """Text positions of every query's matches in rank order (unsigned arrays of the index's width)."""
+        o, p = self.locate_device(*self.search_device(*self._packed(queries)), max_hits)
+        o = o.cpu().numpy(); p = p.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
+        return [p[o[i]:o[i + 1]] for i in range(len(queries))]
 
 
 class DeviceIndex:
@@ -1081,6 +1246,16 @@ class DeviceIndex:
         self.ctx.check(lib().sufr_hip_lf_device(self.ctx.handle, self._h, out.data_ptr()))
         self.ctx.synchronize()
         return out[:s]
+
+    # -- the FM-index over the BWT (include/sufr_fm.h) -------------------------------------------------------------------
+    def fm_device(self, sample: int = 32) -> "DeviceFmIndex":
+        """SufrFile.fm on the device: the FM-index of this index in HBM, complete on return.  It owns everything it reads; this
+        index may be closed afterwards.  Refused (-6) as SufrFile.fm refuses."""
+        import torch
+        torch.cuda.current_stream(self._device()).synchronize()     # (wrapped tensors: their producer is done)
+        h = C.c_void_p()
+        self.ctx.check(lib().sufr_hip_fm_build(self.ctx.handle, self._h, sample, C.byref(h)))
+        return DeviceFmIndex(self.ctx, h, self.index_width)
 
     # -- MEMs (include/sufr_mem.h) -----------------------------------------------------------------------------------
     def mems_device(self, qbytes, offsets, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
