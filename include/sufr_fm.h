@@ -31,6 +31,30 @@
  *         then `block` = B bytes of the BWT; marks of 16 bytes per 64 ranks; the kept values (sufr_fm_scan.h).  K <= 8 at
  *         w == 4: 32 + 96 bytes in one aligned 128-byte line.  sufr_fm_info.bytes is all of it with the tables of C.
  *         No file format is defined for it.
+ *
+ * k-mismatch search by backtracking (declared in sufr_fm_approx.h).  For a query Q[0..m) and d = max_mismatches <=
+ * SUFR_FM_APPROX_MAX_MISMATCHES; fm_byte_ok(c, t, m) says that byte c may stand at place t: it occurs in the text, and it is
+ * e only where t == m - 1.
+ *   Node      (t, lo, hi, h): [lo, hi) is the rank range of a string X[t+1..m) with X[j] == Q[j] at all but h places.  The root
+ *         is (m - 1, 0, s, 0).  One step with byte c gives lo' = C[c] + occ(c, lo) and hi' = C[c] + occ(c, hi); from [0, s)
+ *         that is [C[c], C[c + 1]).  An empty range ends the branch.
+ *   Expanding a node with t >= 0.  If h < d: every byte value c != Q[t] that occurs and has fm_byte_ok(c, t, m), in ascending
+ *         order; each child (t - 1, ., ., h + 1) is expanded completely before the next.  After them the exact child with
+ *         c = Q[t], if fm_byte_ok(Q[t], t, m).  At every place the substitutions come before the exact continuation.
+ *   Leaf      a node with t == -1: (lo, hi, h).  The leaf ranges of one query are disjoint, because different substitution
+ *         sets spell different strings: every alignment appears once and nothing is deduplicated.  A leaf gives the records
+ *         (query, strand, position = SA[r], mismatches = h) for r = lo .. hi - 1, SA[r] by the sampled walk of Samples.
+ *   Order     (query, strand, leaf in the order above, rank), as four parallel arrays with the types of sufr_approx.h: query
+ *         u64, strand u8, position u64, mismatches u8.
+ *   Special   m == 0 gives no records.  m <= d is legal and allows up to m substitutions (sufr_file_approx refuses such
+ *         queries).  e can be the substituted byte only at place m - 1: the window that ends at n.  A query byte that does not
+ *         occur in the text can only be substituted.
+ *   SUFR_FM_APPROX_BOTH_STRANDS  the rule of SUFR_MEM_BOTH_STRANDS: the query is searched again as its reverse complement and
+ *         those records carry strand 1.
+ *   Equality  for every query with m >= d + 1 the record set is that of sufr_file_approx with max_occ == 0 on the same file
+ *         (complete there: s == n, no seed mask, no cap).
+ *   Errors    d > SUFR_FM_APPROX_MAX_MISMATCHES: SUFR_HIP_E_INVALID.  An index built with sample == 0: SUFR_HIP_E_UNSUPPORTED.
+ *         *total_out is always the record count; when it exceeds cap the call returns SUFR_HIP_E_CAPACITY and fills nothing.
  */
 #ifndef SUFR_FM_H
 #define SUFR_FM_H

@@ -178,6 +178,10 @@ class BwtStats(C.Structure):
 # every symbol include/sufr_fm.h declares
 FM_EXPORTS = ["sufr_file_fm_build", "sufr_fm_free", "sufr_fm_get_info", "sufr_fm_search_batch", "sufr_fm_locate_batch", "sufr_hip_fm_build",
               "sufr_hip_fm_free", "sufr_hip_fm_get_info", "sufr_hip_fm_search_batch_device", "sufr_hip_fm_locate_batch_device"]
+# every symbol include/sufr_fm_approx.h declares
+FM_APPROX_EXPORTS = ["sufr_fm_approx", "sufr_fm_approx_steps", "sufr_hip_fm_approx_device", "sufr_hip_fm_approx"]
+FM_APPROX_BOTH_STRANDS = 0x1
+FM_APPROX_MAX_MISMATCHES = 3
 
 
 class FmInfo(C.Structure):
@@ -391,6 +395,14 @@ def lib() -> C.CDLL:
     L.sufr_hip_fm_search_batch_device.argtypes = [vp, vp, vp, vp, u64, vp, vp]; L.sufr_hip_fm_search_batch_device.restype = C.c_int
     L.sufr_hip_fm_locate_batch_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]
     L.sufr_hip_fm_locate_batch_device.restype = C.c_int
+    # include/sufr_fm_approx.h
+    L.sufr_fm_approx.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, C.POINTER(u64), C.c_int]
+    L.sufr_fm_approx.restype = C.c_int
+    L.sufr_fm_approx_steps.argtypes = [vp, vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, C.c_int]; L.sufr_fm_approx_steps.restype = C.c_int
+    L.sufr_hip_fm_approx_device.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_fm_approx_device.restype = C.c_int
+    L.sufr_hip_fm_approx.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_fm_approx.restype = C.c_int
     _lib = L
     return L
 

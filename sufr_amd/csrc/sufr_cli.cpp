@@ -28,7 +28,7 @@
 #include "../../include/sufr_repeat.h"
 #include "../../include/sufr_lz.h"
 #include "../../include/sufr_bwt.h"
-#include "../../include/sufr_fm.h"
+#include "../../include/sufr_fm_approx.h"
 #include "../../include/sufr_shared.h"
 
 #include <hip/hip_runtime_api.h>
@@ -121,6 +121,9 @@ int usage(FILE* f)
             "                                       position is indexed, without seed mask and max_query_len, and the last byte occurs once\n"
             "                                       [--locate [-a]] [-s|--sample Q (32): keep every suffix at a multiple of Q]\n"
             "                                       [--max-hits N (0: all)] [-q|--reads FILE] [--device ID] [-t THREADS] [-o OUT]\n"
+            "                                       [-d|--mismatches D (at most 3) [-b|--both-strands] [-a]: instead every window of the\n"
+            "                                       text within D mismatches of a query, by backtracking on the FM-index alone; the lines\n"
+            "                                       are those of approx, in another order.  Needs samples: -s 0 is an error]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -182,6 +185,7 @@ struct QueryArgs {
     bool cigar = false;                         // edit: -c
     bool locate = false;                        // fm: --locate
     uint64_t sample = 32;                       // fm: -s
+    bool fm_approx = false;                     // fm: -d / --mismatches given (the distance is `mismatches`)
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -769,6 +773,53 @@ int cmd_approx(const QueryArgs& a)
     return 0;
 }
 
+// sufr fm --mismatches: the windows of the text within D mismatches of a query by backtracking on the
+// FM-index, which is all the search reads; the lines of `sufr approx` in (query, strand, leaf, rank) order.  The file stays
+// open for the sequence names of the output.
+int cmd_fm_approx(const QueryArgs& a)
+{
+    if (a.mismatches > SUFR_FM_APPROX_MAX_MISMATCHES) { fprintf(stderr, "Error: --mismatches must be at most %u\n", SUFR_FM_APPROX_MAX_MISMATCHES); return 1; }
+    if (!a.sample) { fprintf(stderr, "Error: --mismatches needs the sampled suffixes: -s must be at least 1\n"); return 1; }
+    QuerySession s;
+    if (!s.open(a)) return 1;
+    sufr_file_meta m;
+    sufr_file_metadata(s.f, &m);
+    const char* why = m.len_suffixes != m.text_len || !m.text_len ? "the file leaves text positions out (every position must be indexed: --dna needs --allow-ambiguity)"
+                      : m.seed_mask_len                           ? "the file was built with a seed mask"
+                      : m.max_query_len                           ? "the file was built with a max_query_len"
+                                                                  : nullptr;
+    const char* twice = "the last byte of the text occurs more than once";
+    if (why) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), why); return 1; }
+    if (!s.load(a)) return 1;
+    const uint32_t flags = a.both_strands ? SUFR_FM_APPROX_BOTH_STRANDS : 0, d = (uint32_t)a.mismatches;
+    sufr_fm* fm = nullptr;
+    sufr_hip_fm* dfm = nullptr;
+    if (s.dev) {
+        const int rc = sufr_hip_fm_build(s.dev->ctx, s.dev->ix, a.sample, &dfm);
+        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : s.dev->error()); return 1; }
+        sufr_hip_index_free(s.dev->ix);         // text and suffix array leave the device: the FM-index answers alone
+        s.dev->ix = nullptr;
+    } else {
+        const int rc = sufr_file_fm_build(s.f, a.sample, &fm, a.threads);
+        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : "the build failed"); return 1; }
+    }
+    uint64_t total = 0;
+    std::vector<uint64_t> qi, pos;
+    std::vector<uint8_t> st, mm;
+    const bool ok = s.until_fits(a, "fm", 4 * s.nq() + 16, total, [&](uint64_t cap, uint64_t* tot) {
+        qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
+        return dfm ? sufr_hip_fm_approx(s.dev->ctx, dfm, s.q(), s.off.data(), s.nq(), d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), tot)
+                   : sufr_fm_approx(fm, s.q(), s.off.data(), s.nq(), d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), tot, a.threads);
+    });
+    sufr_hip_fm_free(dfm);
+    sufr_fm_free(fm);
+    s.release_device();
+    if (!ok) return 1;
+    for (uint64_t t = 0; t < total; t++)
+        fprintf(s.out.f, "%s\t%c\t%s\t%u\n", s.names[qi[t]].c_str(), st[t] ? '-' : '+', place(s.f, a.abs, pos[t]).c_str(), (unsigned)mm[t]);
+    return 0;
+}
+
 // sufr edit: every text position where a query ends with at most -d edits, one line each in record
 // order (query, strand, end): name, strand (+ / -), the end as seq:offset (0-based) or absolute with --abs, edits.
 // -c: the records are traced back (on the device with --device); two more columns, the start in the
@@ -848,7 +899,8 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         else if ((is_locate || is_match || is_fm) && (s == "-a" || s == "--abs")) a.abs = true;
         else if (is_match && !is_approx && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
         else if ((is_mems || is_approx) && s == "--max-occ") a.max_occ = strtoull(need(i, "--max-occ"), nullptr, 10);
-        else if ((is_mems || is_approx) && (s == "-b" || s == "--both-strands")) a.both_strands = true;
+        else if ((is_mems || is_approx || is_fm) && (s == "-b" || s == "--both-strands")) a.both_strands = true;
+        else if (is_fm && (s == "-d" || s == "--mismatches")) { a.fm_approx = true; a.mismatches = strtoull(need(i, "-d"), nullptr, 10); }
         else if (is_edit && (s == "-d" || s == "--edits")) a.edits = strtoull(need(i, "-d"), nullptr, 10);
         else if (is_edit && (s == "-l" || s == "--local-minima")) a.local_minima = true;
         else if (is_edit && (s == "-c" || s == "--cigar")) a.cigar = true;
@@ -879,7 +931,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
-    if (is_fm) return cmd_fm(a);
+    if (is_fm) return a.fm_approx ? cmd_fm_approx(a) : cmd_fm(a);
     if (is_edit) return cmd_edit(a);
     if (is_approx) return cmd_approx(a);
     if (is_mems) return cmd_mems(a);

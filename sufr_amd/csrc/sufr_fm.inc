@@ -1,6 +1,6 @@
 // sufr_fm.inc -- the FM-index over the BWT of a device-resident index: its build, the backward search and the locate that
-// reads neither the text nor the suffix array (included by sufr_kernels.hip after sufr_bwt.inc; include/sufr_fm.h, DESIGN.md
-// section 23).  The layout and the arithmetic are sufr_fm_scan.h, which the host path compiles too.
+// reads neither the text nor the suffix array (included by sufr_kernels.hip after sufr_bwt.inc; include/sufr_fm.h and
+// sufr_fm_approx.h, DESIGN.md sections 23 and 24).  The layout and the arithmetic are sufr_fm_scan.h, which the host path compiles too.
 //
 // Build.  The BWT goes to scratch of the context by k_bwt_gather, which also counts the bytes; one synchronisation reads the
 // counts and the end byte, which decide the refusal, K and with it the shape of a block.  The tiles of the build are those of
@@ -23,7 +23,12 @@
 //                  behind the query or behind a block.
 // k_fm_locate      k_locate_counts / k_locate_scan / k_locate_apply size the output as for sufr_hip_locate_batch_device; then a
 //                  lane per hit walks LF steps to a marked rank and stores kept + steps.
-// No scratch.  LDS: k_fm_blocks 34 KB, k_fm_samples 4 KB, k_fm_search and k_fm_locate 3 KB.
+// k_fm_approx      k-mismatch search by backtracking (include/sufr_fm_approx.h, DESIGN.md section 24): a lane per (query, strand)
+//                  runs fm_approx_walk of sufr_fm_scan.h, the frame at work in registers and the at most three suspended
+//                  ones in LDS; a count pass (leaves and records of every item, scanned in the workgroup), k_locate_scan over
+//                  the workgroups' sums (the one synchronisation), a fill pass that stores every leaf at its slot, then
+//                  k_fm_locate with the leaves as its queries and k_fm_approx_expand for the other record columns.
+// No scratch.  LDS: k_fm_blocks 34 KB, k_fm_samples 4 KB, k_fm_search and k_fm_locate 3 KB, k_fm_approx 25 KB.
 
 #include "sufr_fm_scan.h"
 
@@ -163,6 +168,160 @@ __global__ __launch_bounds__(256) void k_fm_locate(FmView V, const uint64_t* __r
         }
     }
     if (positions64) positions64[j] = p; else positions[j] = (uint32_t)p;
+}
+
+// ---- k-mismatch search by backtracking (DESIGN.md section 24) --------------------------------------------------------------
+// What fm_approx_walk (sufr_fm_scan.h) asks of a lane.  One-line shape: the state of a frame is the set of columns whose child
+// range is not empty, a bit each (K <= 8), and next takes the lowest; wide shapes: the state is the next column, every column
+// is tried while the range is wide, and only the columns of the bytes BWT[lo .. hi) once it holds FM_FEW_RANKS ranks or fewer.
+// A child and an exact step are one fm_occ_pair.
+static constexpr uint64_t FM_FEW_RANKS = 16;
+template <bool LINE>
+struct FmLaneOps {
+    const FmView& V;
+    const uint64_t* s_C;
+    const uint32_t* s_col;
+    const uint8_t* s_sym;
+
+    __device__ __forceinline__ uint32_t col(uint32_t c) const { return s_col[c]; }
+    __device__ __forceinline__ uint32_t sym(uint32_t k) const { return s_sym[k]; }
+    __device__ __forceinline__ bool next(uint32_t& state, uint32_t& k, uint64_t lo, uint64_t hi) const
+    {
+        if (LINE) {
+            if (!state) return false;
+            k = (uint32_t)__builtin_ctz(state);
+            state &= state - 1;
+            return true;
+        }
+        k = state;
+        if (hi - lo <= FM_FEW_RANKS) {                   // only a byte of BWT[lo .. hi) has a child: the lowest such column from `state` on
+            k = FM_NO_COL;
+            const uint8_t* p = V.blocks + lo / V.sh.B * V.sh.stride + V.sh.cbytes;
+            const uint32_t rem = (uint32_t)(lo % V.sh.B), last = (uint32_t)(hi - lo) - 1;
+#pragma unroll
+            for (uint32_t j = 0; j < FM_FEW_RANKS; j++) {      // every load is of a rank of the range (the last one again behind it), none waits for another
+                const uint32_t at = rem + (j < last ? j : last);              // (FM_FEW_RANKS <= B: one block edge at most)
+                const uint32_t kr = s_col[p[at < V.sh.B ? at : at - V.sh.B + V.sh.stride]];
+                if (kr >= state && kr < k) k = kr;
+            }
+        }
+        if (k >= V.sh.K) return false;
+        state = k + 1;
+        return true;
+    }
+    __device__ __forceinline__ void child(uint32_t, uint32_t c, uint32_t k, uint64_t& a, uint64_t& b) const { fm_occ_pair<LINE>(V, c, k, s_C[c], a, b); }
+    __device__ __forceinline__ void exact(uint32_t, bool, uint32_t c, uint32_t k, uint64_t& a, uint64_t& b) const { fm_occ_pair<LINE>(V, c, k, s_C[c], a, b); }
+    // the columns with occ(c, lo) < occ(c, hi), lo < hi <= s.  A short range: the columns of the bytes BWT[lo .. hi) themselves;
+    // else the counts of the two lines, every column counted from the same twelve loads
+    __device__ __forceinline__ uint32_t begin(uint32_t, uint64_t lo, uint64_t hi) const
+    {
+        if (!LINE) return 0;
+        uint32_t mask = 0;
+        if (hi - lo <= FM_FEW_RANKS / 2) {
+            const uint8_t* p = V.blocks + lo / 96u * 128u + 32u;
+            const uint32_t rem = (uint32_t)(lo % 96u), last = (uint32_t)(hi - lo) - 1;
+#pragma unroll
+            for (uint32_t j = 0; j < FM_FEW_RANKS / 2; j++) {  // every load is of a rank of the range (the last one again behind it), none waits for another
+                const uint32_t at = rem + (j < last ? j : last);
+                mask |= 1u << s_col[p[at < 96u ? at : at + 32u]];           // (a byte of the array, which occurs; one block edge at most)
+            }
+            return mask;
+        }
+        const uint8_t* pa = V.blocks + lo / 96u * 128u;
+        const uint8_t* pb = V.blocks + hi / 96u * 128u;
+        const uint32_t ra = (uint32_t)(lo % 96u), rb = (uint32_t)(hi % 96u);
+        // the two lines 16 bytes at a time, every column counted from the same loads; the loop is kept rolled: unrolled, its
+        // 64 registers of line and the eight columns in flight brought the kernel to 203 VGPRs and 2 waves a SIMD
+        const uint4 ca0 = ((const uint4*)pa)[0], ca1 = ((const uint4*)pa)[1], cb0 = ((const uint4*)pb)[0], cb1 = ((const uint4*)pb)[1];
+        uint32_t diff[8] = {cb0.x - ca0.x, cb0.y - ca0.y, cb0.z - ca0.z, cb0.w - ca0.w, cb1.x - ca1.x, cb1.y - ca1.y, cb1.z - ca1.z, cb1.w - ca1.w};
+        uint32_t pat[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) pat[k] = s_sym[k] * 0x01010101u;      // (columns behind K: counts of 0 on both sides, any byte)
+#pragma unroll 1
+        for (uint32_t at = 0; at < 96u; at += 16u) {
+            const uint4 xa = *(const uint4*)(pa + 32u + at), xb = *(const uint4*)(pb + 32u + at);
+#pragma unroll
+            for (int k = 0; k < 8; k++) diff[k] += fm_eq16(xb, pat[k], rb, at) - fm_eq16(xa, pat[k], ra, at);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) if ((uint32_t)k < V.sh.K && diff[k]) mask |= 1u << k;
+        return mask;
+    }
+};
+
+// the suspended frames of the 256 lanes of a workgroup, by depth
+struct FmLaneStack {
+    uint64_t* s_t;
+    uint64_t* s_lo;
+    uint64_t* s_hi;
+    uint32_t* s_next;
+    __device__ __forceinline__ void put(uint32_t h, const FmFrame& f) const
+    {
+        const uint32_t at = h * 256 + threadIdx.x;
+        s_t[at] = f.t; s_lo[at] = f.lo; s_hi[at] = f.hi; s_next[at] = f.next;
+    }
+    __device__ __forceinline__ FmFrame get(uint32_t h) const
+    {
+        const uint32_t at = h * 256 + threadIdx.x;
+        return FmFrame{s_t[at], s_lo[at], s_hi[at], s_next[at]};
+    }
+};
+
+// What the two passes of k_fm_approx exchange.  item_*: for every item the leaves and the records of the items before it in
+// its workgroup; wg_*: per workgroup, after k_locate_scan those of the workgroups before it.  A leaf: its first rank, the
+// offset of its first record, item << 8 | substitutions
+struct FmApproxBufs {
+    uint64_t *item_leaf, *item_rec, *wg_leaf, *wg_rec;
+    uint64_t *leaf_lo, *leaf_off, *leaf_tag;
+    uint64_t nleaves;
+};
+
+// A lane per item (a query, or a strand of one).  Count pass: the leaves and the records of every item, scanned in the
+// workgroup.  Fill pass: the same walk, every leaf stored at its slot -- no order comes from an atomic.
+template <bool LINE, bool FILL>
+__global__ __launch_bounds__(256) void k_fm_approx(FmView V, const uint8_t* __restrict__ queries, const uint64_t* __restrict__ qoff, uint64_t nq,
+                                                   uint32_t d, FmApproxBufs o)
+{
+    __shared__ uint64_t s_C[257], s_w[8];
+    __shared__ uint32_t s_col[256];
+    __shared__ uint8_t s_sym[256];
+    __shared__ uint64_t s_t[FM_APPROX_MAX * 256], s_lo[FM_APPROX_MAX * 256], s_hi[FM_APPROX_MAX * 256];
+    __shared__ uint32_t s_next[FM_APPROX_MAX * 256];
+    s_sym[threadIdx.x] = 0;                              // (the columns behind K are read, masked, by FmLaneOps::begin)
+    __syncthreads();
+    if (V.col[threadIdx.x] != FM_NO_COL) s_sym[V.col[threadIdx.x]] = (uint8_t)threadIdx.x;
+    fm_stage_tables(V, s_C, s_col);
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const FmLaneOps<LINE> ops{V, s_C, s_col, s_sym};
+    const FmLaneStack st{s_t, s_lo, s_hi, s_next};
+    uint64_t cnt[2] = {0, 0}, tot[2];                    // leaves, records
+    if (FILL) {
+        if (i < nq) { cnt[0] = o.wg_leaf[blockIdx.x] + o.item_leaf[i]; cnt[1] = o.wg_rec[blockIdx.x] + o.item_rec[i]; }
+    }
+    if (i < nq) {
+        fm_approx_walk(V, queries + qoff[i], qoff[i + 1] - qoff[i], d, ops, st, [&](uint64_t lo, uint64_t hi, uint32_t h) {
+            if (FILL && cnt[0] < o.nleaves) { o.leaf_lo[cnt[0]] = lo; o.leaf_off[cnt[0]] = cnt[1]; o.leaf_tag[cnt[0]] = i << 8 | h; }
+            cnt[0]++;
+            cnt[1] += hi - lo;
+        });
+    }
+    if (FILL) return;
+    wg_scan(cnt, tot, s_w);
+    if (i < nq) { o.item_leaf[i] = cnt[0]; o.item_rec[i] = cnt[1]; }
+    if (threadIdx.x == 0) { o.wg_leaf[blockIdx.x] = tot[0]; o.wg_rec[blockIdx.x] = tot[1]; }
+}
+
+// query, strand and mismatches of record j from the leaf whose slice holds it (the positions are k_fm_locate's)
+__global__ __launch_bounds__(256) void k_fm_approx_expand(const uint64_t* __restrict__ leaf_off, const uint64_t* __restrict__ leaf_tag, uint64_t nleaves,
+                                                          uint64_t total, uint32_t both, uint64_t* __restrict__ out_query,
+                                                          uint8_t* __restrict__ out_strand, uint8_t* __restrict__ out_mism)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= total) return;
+    const uint64_t tag = leaf_tag[last_le(leaf_off, 0, nleaves, j)], a = tag >> 8;
+    out_query[j] = both ? a >> 1 : a;
+    out_strand[j] = (uint8_t)(both ? a & 1 : 0);
+    out_mism[j] = (uint8_t)tag;
 }
 
 // The blocks of tile t and, with a sampling rate q, its mark words and t_cnt[t], the number of its marks.  tab: the ranks of
@@ -434,6 +593,71 @@ int sufr_hip_fm_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, co
     };
     if (sufr::fm_is_line(fm->V.sh)) launch(sufr::k_fm_locate<true>); else launch(sufr::k_fm_locate<false>);
     return launch_status(pl, "fm_locate");
+}
+
+int sufr_hip_fm_approx_device(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const void* d_queries, const void* d_offsets, uint64_t num_queries,
+                              uint32_t max_mismatches, uint32_t flags, uint64_t cap, void* d_query, void* d_strand, void* d_position,
+                              void* d_mismatches, uint64_t* total_out)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !fm || (num_queries && (!d_queries || !d_offsets))) return SUFR_HIP_E_INVALID;
+    sufr::Pipeline& pl = ctx->pl;
+    int rc;
+    if ((rc = fm_check(ctx, fm))) return rc;
+    if (max_mismatches > SUFR_FM_APPROX_MAX_MISMATCHES) {
+        pl.set_error("fm_approx: max_mismatches must be at most " + std::to_string(SUFR_FM_APPROX_MAX_MISMATCHES));
+        return SUFR_HIP_E_INVALID;
+    }
+    if (!fm->V.q) { pl.set_error("fm_approx: the index was built without samples (sample == 0)"); return SUFR_HIP_E_UNSUPPORTED; }
+    if (!num_queries) return 0;
+    // one strand: the batch as it was given, nothing of it read here; both: the doubled batch of the seeded searches
+    QueryBatch b{(const uint8_t*)d_queries, (const uint64_t*)d_offsets, num_queries, 1, 0, false};
+    if ((flags & SUFR_FM_APPROX_BOTH_STRANDS) && ((rc = take_batch(ctx, nullptr, d_queries, d_offsets, num_queries, true, "fm_approx", b)) || !b.nb)) return rc;
+    const uint64_t wgs = (b.nq + 255) / 256;
+    if (wgs > 0x7fffffffull) { pl.set_error("fm_approx: too many queries in one batch"); return SUFR_HIP_E_INVALID; }
+    // xlo, xhi: per item; xsum: the workgroups' leaves, their records, the two totals
+    if ((rc = pl.ensure(ctx->xlo, b.nq * 8)) || (rc = pl.ensure(ctx->xhi, b.nq * 8)) || (rc = pl.ensure(ctx->xsum, (2 * wgs + 2) * 8))) return rc;
+    uint64_t* sums = (uint64_t*)ctx->xsum.p;
+    sufr::FmApproxBufs o{(uint64_t*)ctx->xlo.p, (uint64_t*)ctx->xhi.p, sums, sums + wgs, nullptr, nullptr, nullptr, 0};
+    const bool line = sufr::fm_is_line(fm->V.sh);
+    auto walk = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)wgs), dim3(256), 0, pl.stream, fm->V, b.q, b.qoff, b.nq, max_mismatches, o);
+    };
+    if (line) walk(sufr::k_fm_approx<true, false>); else walk(sufr::k_fm_approx<false, false>);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, o.wg_leaf, wgs, sums + 2 * wgs);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, o.wg_rec, wgs, sums + 2 * wgs + 1);
+    unsigned long long totals[2] = {0, 0};               // leaves, records
+    if ((rc = launch_status(pl, "fm_approx")) || (rc = read_totals(pl, sums + 2 * wgs, 2, totals, "fm_approx", "counting the records failed"))) return rc;
+    if ((rc = records_fit(pl, "fm_approx", "records", totals[1], cap, total_out)) || !totals[1]) return rc;
+    if (any_null({d_query, d_strand, d_position, d_mismatches})) return SUFR_HIP_E_INVALID;
+    const uint64_t nleaves = totals[0], nrec = totals[1], blocks = (nrec + 255) / 256;
+    if (blocks > 0x7fffffffull) { pl.set_error("fm_approx: too many records for one launch"); return SUFR_HIP_E_INVALID; }
+    if ((rc = pl.ensure(ctx->xcand, 3 * nleaves * 8))) return rc;
+    o.leaf_off = (uint64_t*)ctx->xcand.p; o.leaf_lo = o.leaf_off + nleaves; o.leaf_tag = o.leaf_lo + nleaves; o.nleaves = nleaves;
+    if (line) walk(sufr::k_fm_approx<true, true>); else walk(sufr::k_fm_approx<false, true>);
+    // the leaves are the queries of the locate, their record offsets its offsets; the positions are stored as u64
+    auto locate = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, pl.stream, fm->V, (const uint64_t*)o.leaf_lo, (const uint64_t*)o.leaf_off, nleaves,
+                           nrec, (uint32_t*)nullptr, (uint64_t*)d_position);
+    };
+    if (line) locate(sufr::k_fm_locate<true>); else locate(sufr::k_fm_locate<false>);
+    hipLaunchKernelGGL(sufr::k_fm_approx_expand, dim3((uint32_t)blocks), dim3(256), 0, pl.stream, (const uint64_t*)o.leaf_off, (const uint64_t*)o.leaf_tag,
+                       nleaves, nrec, (uint32_t)b.both, (uint64_t*)d_query, (uint8_t*)d_strand, (uint8_t*)d_mismatches);
+    return launch_status(pl, "fm_approx");
+}
+
+int sufr_hip_fm_approx(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const uint8_t* queries, const uint64_t* offsets, uint64_t num_queries,
+                       uint32_t max_mismatches, uint32_t flags, uint64_t cap, uint64_t* query, uint8_t* strand, uint64_t* position,
+                       uint8_t* mismatches, uint64_t* total_out)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !fm || (num_queries && !offsets)) return SUFR_HIP_E_INVALID;
+    if (const int rc = fm_check(ctx, fm)) return rc;
+    if (!num_queries) return sufr_hip_fm_approx_device(ctx, fm, nullptr, nullptr, 0, max_mismatches, flags, cap, nullptr, nullptr, nullptr, nullptr, total_out);
+    return staged_records(ctx, "FM k-mismatch", queries, offsets, num_queries, cap, {{query, 8}, {strand, 1}, {position, 8}, {mismatches, 1}}, 0, total_out,
+                          [&](const void* d_q, const void* d_off, void* const* col, uint64_t* total) {
+        return sufr_hip_fm_approx_device(ctx, fm, d_q, d_off, num_queries, max_mismatches, flags, cap, col[0], col[1], col[2], col[3], total);
+    });
 }
 
 }  // extern "C"

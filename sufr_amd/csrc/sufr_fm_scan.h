@@ -1,6 +1,6 @@
 // sufr_fm_scan.h -- the layout and the arithmetic of the FM-index over the BWT of the indexed text (include/sufr_fm.h,
 // DESIGN.md section 23): the shape of a block, the count of a byte value in the front of a block, occ, the backward search
-// of one query and the walk from a rank to a sampled suffix.  Plain integer code that the kernels of sufr_fm.inc and the host
+// of one query, the walk from a rank to a sampled suffix and the backtracking walk of the k-mismatch search (section 24).  Plain integer code that the kernels of sufr_fm.inc and the host
 // path of sufr_query.cpp both compile (SUFR_HD, the way of sufr_bwt_scan.h); there is no second copy of it.  The kernels read
 // a block with wider loads than fm_occ does and count with the same fm_eq_bytes.
 //
@@ -123,6 +123,86 @@ SUFR_HD uint64_t fm_position(const FmView& V, uint64_t r)
         r = V.C[c] + fm_occ(V, c, r);
     }
     return ~(uint64_t)0;
+}
+
+// ---- k-mismatch search by backtracking (include/sufr_fm.h) ---------------------------------------
+static constexpr uint32_t FM_APPROX_MAX = 3;             // SUFR_FM_APPROX_MAX_MISMATCHES: the walk keeps FM_APPROX_MAX suspended frames
+
+// One step for every byte value: at_lo[k] = occ(c_k, lo) and at_hi[k] = occ(c_k, hi) for the byte value c_k of every column
+// k < K, lo <= hi <= s, from the blocks of lo and of hi; where they are one block its bytes are counted once
+SUFR_HD void fm_occ_all(const FmView& V, uint64_t lo, uint64_t hi, uint64_t* at_lo, uint64_t* at_hi)
+{
+    const uint64_t ja = lo / V.sh.B, jb = hi / V.sh.B;
+    const uint8_t* pa = V.blocks + ja * V.sh.stride;
+    const uint8_t* pb = V.blocks + jb * V.sh.stride;
+    const uint32_t ra = (uint32_t)(lo % V.sh.B), rb = (uint32_t)(hi % V.sh.B);
+    for (uint32_t k = 0; k < V.sh.K; k++) at_lo[k] = fm_rd(pa + k * V.sh.w, V.sh.w);
+    for (uint32_t i = 0; i < ra; i++) at_lo[V.col[pa[V.sh.cbytes + i]]]++;
+    uint32_t from = 0;
+    if (ja == jb) { for (uint32_t k = 0; k < V.sh.K; k++) at_hi[k] = at_lo[k]; from = ra; }
+    else for (uint32_t k = 0; k < V.sh.K; k++) at_hi[k] = fm_rd(pb + k * V.sh.w, V.sh.w);
+    for (uint32_t i = from; i < rb; i++) at_hi[V.col[pb[V.sh.cbytes + i]]]++;
+}
+
+// A frame of the walk: the rank range [lo, hi) of X[t..m), the places 0 .. t - 1 still to go, and what its Ops made of the
+// columns it has yet to try as substitutions at place t - 1
+struct FmFrame { uint64_t t, lo, hi; uint32_t next; };
+
+// The walk of one query Q[0..m) with at most d <= FM_APPROX_MAX substitutions: leaf(lo, hi, h) for every leaf, in the order
+// of include/sufr_fm.h (at every place the substitutions in ascending byte order, each expanded completely, then the exact
+// continuation).  The frame at work is `f`, with h substitutions behind it; the h frames it descends from are suspended in
+// `st` (st.put(depth, frame), st.get(depth), depth < d).  A frame moves along its exact path once its substitutions are done,
+// so there are never more than d suspended frames, whatever m is, and no range is computed twice.
+//   Ops   col(c)               the column of byte value c, FM_NO_COL where it does not occur (V.col, from wherever it is kept)
+//         sym(k)               the byte value of column k
+//         begin(h, lo, hi)     called once when the frame of depth h < d arrives at a place with the range [lo, hi): prepares
+//                              the step of every column and returns the state of the columns to try
+//         next(state, k, lo, hi)   takes the next column to try out of the state of the frame with the range [lo, hi); false
+//                              when there is none left
+//         child(h, c, k, a, b) the step of [a, b) with byte c of column k, for a frame that begin(h, ..) prepared
+//         exact(h, prepared, c, k, a, b)   the same for the query's own byte; prepared: begin(h, ..) saw this range
+// Termination.  Every iteration of the loop does one of four things: it takes a column out of a frame's state (at most K
+// times between two moves of that frame), it pushes (h grows, h <= d), it moves the frame one place down (t shrinks; t is
+// never raised, a pushed frame starts below its parent), or it pops.  A frame is popped once and only frames that were
+// pushed are; pushes happen only at a (frame, place, column) triple, of which there are finitely many below every frame.
+template <class Ops, class Stack, class Leaf>
+SUFR_HD void fm_approx_walk(const FmView& V, const uint8_t* Q, uint64_t m, uint32_t d, Ops& ops, Stack& st, Leaf&& leaf)
+{
+    if (!m) return;
+    uint32_t h = 0;
+    FmFrame f{m, 0, V.s, d ? ops.begin(0, 0, V.s) : 0};
+    for (;;) {
+        bool alive = f.t != 0;
+        if (!alive) leaf(f.lo, f.hi, h);
+        else {
+            const uint64_t i = f.t - 1;                  // the place of this step
+            const uint32_t q = Q[i];
+            uint32_t k;
+            if (h < d && ops.next(f.next, k, f.lo, f.hi)) {
+                const uint32_t c = ops.sym(k);
+                if (c == q || (c == V.e && f.t != m)) continue;      // (fm_byte_ok: the end byte only at the last place)
+                uint64_t a = f.lo, b = f.hi;
+                ops.child(h, c, k, a, b);
+                if (a >= b) continue;
+                st.put(h, f);
+                h++;
+                f = FmFrame{i, a, b, h < d && i ? ops.begin(h, a, b) : 0};
+                continue;
+            }
+            const uint32_t kq = ops.col(q);
+            alive = kq != FM_NO_COL && (q != V.e || f.t == m);
+            if (alive) {
+                ops.exact(h, h < d, q, kq, f.lo, f.hi);
+                f.t = i;
+                alive = f.lo < f.hi;
+                if (alive && h < d && i) f.next = ops.begin(h, f.lo, f.hi);
+            }
+        }
+        if (!alive) {
+            if (!h) return;
+            f = st.get(--h);
+        }
+    }
 }
 
 }  // namespace sufr

@@ -24,7 +24,7 @@
 #include "../../include/sufr_lz.h"
 #include "../../include/sufr_shared.h"
 #include "../../include/sufr_bwt.h"
-#include "../../include/sufr_fm.h"
+#include "../../include/sufr_fm_approx.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -201,5 +201,10 @@ int sufr_hip_fm_get_info(const sufr_hip_fm*, sufr_fm_info*) { return SUFR_HIP_E_
 int sufr_hip_fm_search_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const void*, const void*, uint64_t, void*, void*) { return no_device(ctx); }
 int sufr_hip_fm_locate_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const void*, const void*, uint64_t, uint64_t, void*, void*, uint64_t,
                                     uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+// ---- include/sufr_fm_approx.h: the device side
+int sufr_hip_fm_approx_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const void*, const void*, uint64_t, uint32_t, uint32_t, uint64_t, void*, void*, void*,
+                              void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_fm_approx(sufr_hip_ctx* ctx, const sufr_hip_fm*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint32_t, uint64_t, uint64_t*, uint8_t*,
+                       uint64_t*, uint8_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 
 }  // extern "C"

@@ -3152,5 +3152,5 @@ k_widen(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t co
 #include "sufr_shared.inc"
 #include "../../include/sufr_bwt.h"
 #include "sufr_bwt.inc"
-#include "../../include/sufr_fm.h"
+#include "../../include/sufr_fm_approx.h"
 #include "sufr_fm.inc"

@@ -1499,7 +1499,7 @@ int sufr_file_lf(const sufr_file* f, void* lf, int threads)
 
 // ---- the FM-index over the BWT: backward search and locate without text and suffix array (include/sufr_fm.h, DESIGN.md
 // section 23) ---------------------------------------------------------------------------------------------------------
-#include "../../include/sufr_fm.h"
+#include "../../include/sufr_fm_approx.h"
 #include "sufr_fm_scan.h"
 
 struct sufr_fm {
@@ -1647,6 +1647,122 @@ int sufr_fm_locate_batch(const sufr_fm* fm, const uint64_t* rank_lo, const uint6
             kmer_put(positions, (int)V.sh.w, g, sufr::fm_position(V, rank_lo[a] + (g - offsets[a])));
         }
     }, 64);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- k-mismatch search on the FM-index by backtracking (include/sufr_fm_approx.h)------------------------
+namespace {
+
+// What fm_approx_walk asks of the host: begin prepares the step of every column with one fm_occ_all, next tries the columns
+// in order, child and a prepared exact step read what begin left
+struct FmHostOps {
+    const sufr::FmView& V;
+    uint32_t sym_of[256];
+    uint64_t at_lo[sufr::FM_APPROX_MAX][256], at_hi[sufr::FM_APPROX_MAX][256];      // by depth: occ of every column at lo and at hi
+    uint64_t steps = 0;
+    explicit FmHostOps(const sufr::FmView& v) : V(v)
+    {
+        for (uint32_t c = 0; c < 256; c++) if (V.col[c] != sufr::FM_NO_COL) sym_of[V.col[c]] = c;
+    }
+    uint32_t col(uint32_t c) const { return V.col[c]; }
+    uint32_t sym(uint32_t k) const { return sym_of[k]; }
+    uint32_t begin(uint32_t h, uint64_t lo, uint64_t hi) { steps++; sufr::fm_occ_all(V, lo, hi, at_lo[h], at_hi[h]); return 0; }
+    bool next(uint32_t& state, uint32_t& k, uint64_t, uint64_t) const { k = state; return state < V.sh.K ? (state++, true) : false; }
+    void child(uint32_t h, uint32_t c, uint32_t k, uint64_t& a, uint64_t& b) const { a = V.C[c] + at_lo[h][k]; b = V.C[c] + at_hi[h][k]; }
+    void exact(uint32_t h, bool prepared, uint32_t c, uint32_t k, uint64_t& a, uint64_t& b)
+    {
+        if (prepared) { child(h, c, k, a, b); return; }
+        steps++;
+        a = V.C[c] + sufr::fm_occ(V, c, a);
+        b = V.C[c] + sufr::fm_occ(V, c, b);
+    }
+};
+
+struct FmHostStack {
+    sufr::FmFrame fr[sufr::FM_APPROX_MAX];
+    void put(uint32_t h, const sufr::FmFrame& f) { fr[h] = f; }
+    sufr::FmFrame get(uint32_t h) const { return fr[h]; }
+};
+
+int fm_approx_args(const sufr_fm* fm, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t d)
+{
+    if (!fm || (nq && !offsets) || (nq && offsets[nq] > offsets[0] && !queries)) return SUFR_HIP_E_INVALID;
+    for (uint64_t i = 0; i < nq; i++) if (offsets[i + 1] < offsets[i]) return SUFR_HIP_E_INVALID;
+    if (d > SUFR_FM_APPROX_MAX_MISMATCHES) return SUFR_HIP_E_INVALID;
+    return fm->q ? 0 : SUFR_HIP_E_UNSUPPORTED;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_fm_approx(const sufr_fm* fm, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t max_mismatches, uint32_t flags,
+                   uint64_t cap, uint64_t* query, uint8_t* strand, uint64_t* position, uint8_t* mismatches, uint64_t* total_out, int threads)
+{
+    if (total_out) *total_out = 0;
+    if (const int rc = fm_approx_args(fm, queries, offsets, nq, max_mismatches)) return rc;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    const bool both = (flags & SUFR_FM_APPROX_BOTH_STRANDS) != 0;
+    std::vector<uint8_t> dbl;
+    std::vector<uint64_t> off;
+    const uint8_t* qb = strand_batch(queries, offsets, nq, both, dbl, off);
+    const uint64_t nq2 = off.size() - 1;
+    const sufr::FmView V = fm->view();
+    // Two passes of the same walk, as on the device.  Count: the records of every item (hi - lo of its leaves), no position
+    // walked and nothing kept; their exclusive scan gives every item its slice and the total, which decides E_CAPACITY before
+    // anything is filled.  Fill: every item writes its slice.  Workers take chunks of items in both.
+    std::vector<uint64_t> at(nq2 + 1, 0);
+    parallel_chunks(nq2, 16, threads, [&](uint64_t b, uint64_t e) {
+        FmHostOps ops(V);
+        FmHostStack st;
+        for (uint64_t a = b; a < e; a++)
+            sufr::fm_approx_walk(V, qb + off[a], off[a + 1] - off[a], max_mismatches, ops, st, [&](uint64_t lo, uint64_t hi, uint32_t) { at[a + 1] += hi - lo; });
+    }, 4);
+    for (uint64_t a = 0; a < nq2; a++) at[a + 1] += at[a];
+    const uint64_t total = at[nq2];
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!query || !strand || !position || !mismatches) return SUFR_HIP_E_INVALID;
+    parallel_chunks(nq2, 16, threads, [&](uint64_t b, uint64_t e) {
+        FmHostOps ops(V);
+        FmHostStack st;
+        for (uint64_t a = b; a < e; a++) {
+            if (at[a] == at[a + 1]) continue;
+            const QueryStrand qs = query_strand(both, a);
+            uint64_t t = at[a];
+            sufr::fm_approx_walk(V, qb + off[a], off[a + 1] - off[a], max_mismatches, ops, st, [&](uint64_t lo, uint64_t hi, uint32_t h) {
+                for (uint64_t r = lo; r < hi; r++, t++) {
+                    query[t] = qs.query; strand[t] = qs.strand; position[t] = sufr::fm_position(V, r); mismatches[t] = (uint8_t)h;
+                }
+            });
+        }
+    }, 4);
+    return 0;
+}
+
+int sufr_fm_approx_steps(const sufr_fm* fm, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t max_mismatches, uint32_t flags,
+                         uint64_t* leaves, uint64_t* steps, int threads)
+{
+    if (const int rc = fm_approx_args(fm, queries, offsets, nq, max_mismatches)) return rc;
+    if (!nq) return 0;
+    if (!leaves || !steps) return SUFR_HIP_E_INVALID;
+    const bool both = (flags & SUFR_FM_APPROX_BOTH_STRANDS) != 0;
+    std::vector<uint8_t> dbl;
+    std::vector<uint64_t> off;
+    const uint8_t* qb = strand_batch(queries, offsets, nq, both, dbl, off);
+    const sufr::FmView V = fm->view();
+    parallel_chunks(off.size() - 1, 16, threads, [&](uint64_t b, uint64_t e) {
+        FmHostOps ops(V);
+        FmHostStack st;
+        for (uint64_t a = b; a < e; a++) {
+            ops.steps = leaves[a] = 0;
+            sufr::fm_approx_walk(V, qb + off[a], off[a + 1] - off[a], max_mismatches, ops, st, [&](uint64_t, uint64_t, uint32_t) { leaves[a]++; });
+            steps[a] = ops.steps;
+        }
+    }, 4);
     return 0;
 }
 

@@ -490,14 +490,15 @@ int mem_bitmap(sufr_hip_ctx* ctx, const sufr_hip_index* ix)
 // (0: an empty batch, nothing to do), grid: the workgroups of the kernels that loop over it
 struct QueryBatch { const uint8_t* q; const uint64_t* qoff; uint64_t nq, nb; uint32_t grid; bool both; };
 
-// the batch as the caller gave it: the bitmap of the index, then the two ends of the offsets (one synchronisation)
+// the batch as the caller gave it: the bitmap of the index, then the two ends of the offsets (one synchronisation).  ix may
+// be null: a caller without text and suffix array (the FM-index of sufr_fm.inc), for which no bitmap is made
 int batch_extent(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets, uint64_t num_queries,
                  const char* tag, QueryBatch& b)
 {
     sufr::Pipeline& pl = ctx->pl;
     b = QueryBatch{(const uint8_t*)d_queries, (const uint64_t*)d_offsets, num_queries, 0, batch_grid(pl), false};
     if (!num_queries) return 0;
-    if (const int rc = mem_bitmap(ctx, ix)) return rc;
+    if (ix) if (const int rc = mem_bitmap(ctx, ix)) return rc;
     unsigned long long ends[2] = {0, 0};                             // offsets[0] and offsets[num_queries]
     bool ok = true;
     for (int k = 0; k < 2; k++)
@@ -518,6 +519,7 @@ int double_batch(sufr_hip_ctx* ctx, QueryBatch& b)
     return 0;
 }
 
+// batch_extent, then with both strands double_batch; ix may be null as for batch_extent
 int take_batch(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets, uint64_t num_queries, bool both,
                const char* tag, QueryBatch& b)
 {

@@ -839,6 +839,42 @@ class FmIndex:
         o, p = self.locate_ranges(*self.search_batch(queries, threads), max_hits, threads)
         return [p[int(o[i]):int(o[i + 1])] for i in range(len(queries))]
 
+    # -- k-mismatch search by backtracking (include/sufr_fm_approx.h) -------------------------------------------------------
+    def approx_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, max_mismatches: int = 2, both_strands: bool = False,
+                      cap: Optional[int] = None, threads: int = 0):
+        """(query, strand, position, mismatches) of every window of the text within `max_mismatches` (at most 3) substitutions
+        of a query of a packed batch, as SufrFile.approx_arrays returns them, in (query, strand, leaf, rank) order.  With a `cap`
+        too small the SufrHipError (code -5) carries the total in `.total`; without one the arrays are sized to fit."""
+        from ._lib import FM_APPROX_BOTH_STRANDS
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nq = len(offsets) - 1
+        flags = FM_APPROX_BOTH_STRANDS if both_strands else 0
+        return _sized_to_fit(
+            cap, 4 * nq + 16, lambda c: [np.zeros(c, dtype=d) for d in _APPROX_DTYPES],
+            lambda c, out, total: lib().sufr_fm_approx(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, max_mismatches, flags, c,
+                                                       *[a.ctypes.data for a in out], C.byref(total), threads),
+            lambda rc, total, c: SufrHipError(rc, "sufr_fm_approx: " + {
+                -5: f"{total} records, room for {c}", -6: "the index was built without samples (sample == 0)",
+                -1: "invalid argument (max_mismatches must be at most 3)"}.get(rc, "failed")))
+
+    def approx(self, queries: Sequence, max_mismatches: int = 2, both_strands: bool = False, threads: int = 0) -> List[List[ApproxHit]]:
+        """Where every query occurs with at most `max_mismatches` substitutions, by backtracking on the index alone: all of
+        them, each once, in (strand, leaf, rank) order."""
+        qb, off = pack_queries(queries)
+        return _approx_hits(len(off) - 1, self.approx_arrays(qb, off, max_mismatches, both_strands, threads=threads))
+
+    def approx_steps(self, queries: Sequence, max_mismatches: int = 2, both_strands: bool = False, threads: int = 0):
+        """(leaves, steps) of the walk of every (query, strand) item: what a batch costs (sufr_fm_approx_steps)."""
+        qb, off = pack_queries(queries)
+        items = (len(off) - 1) * (2 if both_strands else 1)
+        leaves, steps = np.zeros(items, dtype=np.uint64), np.zeros(items, dtype=np.uint64)
+        rc = lib().sufr_fm_approx_steps(self._h, qb.ctypes.data, off.ctypes.data, len(off) - 1, max_mismatches, 1 if both_strands else 0,
+                                        leaves.ctypes.data, steps.ctypes.data, threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_fm_approx_steps failed")
+        return leaves, steps
+
 
 class DeviceFmIndex:
     """The FM-index of a DeviceIndex in HBM (DeviceIndex.fm_device; include/sufr_fm.h).  It owns everything it reads: the
@@ -906,6 +942,32 @@ class DeviceFmIndex:
 
     def count(self, queries: Sequence) -> List[CountResult]:
         return _counts(queries, *self.search(queries))
+
+    # -- k-mismatch search by backtracking (include/sufr_fm_approx.h) -------------------------------------------------------
+    def approx_device(self, qbytes, offsets, max_mismatches: int = 2, both_strands: bool = False, cap: Optional[int] = None):
+        """FmIndex.approx_arrays for a packed batch of torch CUDA tensors (uint8 bytes, int64 offsets): (query int64, strand
+        uint8, position int64, mismatches uint8) tensors as DeviceIndex.approx_device returns them, in (query, strand, leaf,
+        rank) order, complete on return.  With a `cap` too small the SufrHipError (code -5) carries the total in `.total`."""
+        import torch
+        from ._lib import FM_APPROX_BOTH_STRANDS
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = max(offsets.numel() - 1, 0)
+        dev = qbytes.device
+        qbytes = DeviceIndex._device_bytes(qbytes)
+        flags = FM_APPROX_BOTH_STRANDS if both_strands else 0
+        out = _sized_to_fit(
+            cap, 4 * nq + 16, lambda c: [torch.empty(c, dtype=d, device=dev) for d in (torch.int64, torch.uint8, torch.int64, torch.uint8)],
+            lambda c, out, total: lib().sufr_hip_fm_approx_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), nq,
+                                                                  max_mismatches, flags, c, *[t.data_ptr() for t in out], C.byref(total)),
+            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
+        self.ctx.synchronize()
+        return out
+
+    def approx(self, queries: Sequence, max_mismatches: int = 2, both_strands: bool = False) -> List[List[ApproxHit]]:
+        """The k-mismatch occurrences of every query (FmIndex.approx), found on the device."""
+        qb, off = self._packed(queries)
+        recs = self.approx_device(qb, off, max_mismatches, both_strands)
+        return _approx_hits(off.numel() - 1, [t.cpu().numpy() for t in recs])
 
     def locate(self, queries: Sequence, max_hits: int = 0) -> List[np.ndarray]:
         """Text positions of every query's matches in rank order (unsigned arrays of the index's width)."""
