@@ -30,7 +30,7 @@
  *   Layout    blocks of `stride` bytes: the K counts (w bytes each, K: the byte values that occur) at the block's first rank,
  *         then `block` = B bytes of the BWT; marks of 16 bytes per 64 ranks; the kept values (sufr_fm_scan.h).  K <= 8 at
  *         w == 4: 32 + 96 bytes in one aligned 128-byte line.  sufr_fm_info.bytes is all of it with the tables of C.
- *         No file format is defined for it.
+ *         The file it is saved to and loaded from, and the text samples it may also keep, are in sufr_fm_text.h.
  *
  * k-mismatch search by backtracking (declared in sufr_fm_approx.h).  For a query Q[0..m) and d = max_mismatches <=
  * SUFR_FM_APPROX_MAX_MISMATCHES; fm_byte_ok(c, t, m) says that byte c may stand at place t: it occurs in the text, and it is

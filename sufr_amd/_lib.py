@@ -184,6 +184,22 @@ FM_APPROX_BOTH_STRANDS = 0x1
 FM_APPROX_MAX_MISMATCHES = 3
 
 
+# every symbol include/sufr_fm_text.h declares
+FM_TEXT_EXPORTS = ["sufr_file_fm_build_flags", "sufr_fm_get_text_info", "sufr_fm_extract_batch", "sufr_fm_save", "sufr_fm_load",
+                   "sufr_fm_num_sequences", "sufr_fm_sequence_start", "sufr_fm_sequence_name", "sufr_fm_set_sequences",
+                   "sufr_hip_fm_build_flags", "sufr_hip_fm_get_text_info", "sufr_hip_fm_extract_batch_device", "sufr_hip_fm_extract_batch",
+                   "sufr_hip_fm_upload", "sufr_hip_fm_download"]
+FM_TEXT = 0x1
+
+
+class FmTextInfo(C.Structure):
+    """sufr_fm_text_info"""
+    _fields_ = [("text_samples", C.c_uint64), ("text_bytes", C.c_uint64), ("file_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class FmInfo(C.Structure):
     """sufr_fm_info"""
     _fields_ = [("ranks", C.c_uint64), ("symbols", C.c_uint64), ("block", C.c_uint64), ("stride", C.c_uint64), ("sample", C.c_uint64),
@@ -403,6 +419,23 @@ def lib() -> C.CDLL:
     L.sufr_hip_fm_approx_device.restype = C.c_int
     L.sufr_hip_fm_approx.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, C.c_uint32, u64, vp, vp, vp, vp, C.POINTER(u64)]
     L.sufr_hip_fm_approx.restype = C.c_int
+    # include/sufr_fm_text.h
+    L.sufr_file_fm_build_flags.argtypes = [vp, u64, u32, C.POINTER(vp), C.c_int]; L.sufr_file_fm_build_flags.restype = C.c_int
+    L.sufr_fm_get_text_info.argtypes = [vp, C.POINTER(FmTextInfo)]; L.sufr_fm_get_text_info.restype = C.c_int
+    L.sufr_fm_extract_batch.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.c_int]; L.sufr_fm_extract_batch.restype = C.c_int
+    L.sufr_fm_save.argtypes = [vp, cp, vp, cp, C.c_size_t]; L.sufr_fm_save.restype = C.c_int
+    L.sufr_fm_load.argtypes = [cp, C.POINTER(vp), C.c_int, cp, C.c_size_t]; L.sufr_fm_load.restype = C.c_int
+    L.sufr_fm_num_sequences.argtypes = [vp]; L.sufr_fm_num_sequences.restype = u64
+    L.sufr_fm_sequence_start.argtypes = [vp, u64]; L.sufr_fm_sequence_start.restype = u64
+    L.sufr_fm_sequence_name.argtypes = [vp, u64]; L.sufr_fm_sequence_name.restype = cp
+    L.sufr_fm_set_sequences.argtypes = [vp, vp, C.POINTER(cp), u64]; L.sufr_fm_set_sequences.restype = C.c_int
+    L.sufr_hip_fm_build_flags.argtypes = [vp, vp, u64, u32, C.POINTER(vp)]; L.sufr_hip_fm_build_flags.restype = C.c_int
+    L.sufr_hip_fm_get_text_info.argtypes = [vp, C.POINTER(FmTextInfo)]; L.sufr_hip_fm_get_text_info.restype = C.c_int
+    L.sufr_hip_fm_extract_batch_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
+    L.sufr_hip_fm_extract_batch_device.restype = C.c_int
+    L.sufr_hip_fm_extract_batch.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]; L.sufr_hip_fm_extract_batch.restype = C.c_int
+    L.sufr_hip_fm_upload.argtypes = [vp, vp, C.POINTER(vp)]; L.sufr_hip_fm_upload.restype = C.c_int
+    L.sufr_hip_fm_download.argtypes = [vp, vp, C.POINTER(vp)]; L.sufr_hip_fm_download.restype = C.c_int
     _lib = L
     return L
 

@@ -29,6 +29,7 @@
 #include "../../include/sufr_lz.h"
 #include "../../include/sufr_bwt.h"
 #include "../../include/sufr_fm_approx.h"
+#include "../../include/sufr_fm_text.h"
 #include "../../include/sufr_shared.h"
 
 #include <hip/hip_runtime_api.h>
@@ -124,6 +125,12 @@ int usage(FILE* f)
             "                                       [-d|--mismatches D (at most 3) [-b|--both-strands] [-a]: instead every window of the\n"
             "                                       text within D mismatches of a query, by backtracking on the FM-index alone; the lines\n"
             "                                       are those of approx, in another order.  Needs samples: -s 0 is an error]\n"
+            "                                       [--save OUT.fm [--text]: build the index (on the GPU with --device) and write it to a\n"
+            "                                       file; --text keeps the text samples, with which the index gives the text back]\n"
+            "                                       [--index IN.fm instead of <SUFR>: load such a file (verified) and answer from it alone,\n"
+            "                                       on the GPU with --device; no .sufr is opened]\n"
+            "                                       [--extract [--prefix-len N] [--suffix-len N]: the lines of extract for the hits of every\n"
+            "                                       query, the bases read back from the BWT; implies --text]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -186,6 +193,8 @@ struct QueryArgs {
     bool locate = false;                        // fm: --locate
     uint64_t sample = 32;                       // fm: -s
     bool fm_approx = false;                     // fm: -d / --mismatches given (the distance is `mismatches`)
+    std::string fm_save, fm_index;              // fm: --save OUT.fm, --index IN.fm
+    bool fm_text = false, fm_extract = false;   // fm: --text, --extract
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -294,8 +303,24 @@ int cmd_count(const QueryArgs& a)
 
 // The lines of `sufr locate`: query qi has count(qi) hits (0: not found), suffix(qi, k) is the text position of hit k in rank
 // order.  `sufr fm --locate` prints through here too, with positions that no suffix array was read for.
-template <typename Count, typename Suffix>
-void print_located(sufr_file* f, FILE* out, bool abs, const std::vector<std::string>& queries, Count count, Suffix suffix)
+// the sequences of the text: of an open .sufr file, or those an FM-index file carries (SeqTable)
+struct SeqTable {
+    std::vector<uint64_t> starts;
+    std::vector<std::string> names;
+};
+uint64_t seq_of(const sufr_file* f, uint64_t p) { return sufr_file_sequence_of(f, p); }
+uint64_t seq_start(const sufr_file* f, uint64_t i) { return sufr_file_sequence_start(f, i); }
+const char* seq_name(const sufr_file* f, uint64_t i) { return sufr_file_sequence_name(f, i); }
+uint64_t seq_of(const SeqTable& t, uint64_t p)            // (sufr_file_sequence_of: the last sequence that starts at or before p)
+{
+    const size_t k = (size_t)(std::upper_bound(t.starts.begin(), t.starts.end(), p) - t.starts.begin());
+    return k ? k - 1 : 0;
+}
+uint64_t seq_start(const SeqTable& t, uint64_t i) { return i < t.starts.size() ? t.starts[i] : 0; }
+const char* seq_name(const SeqTable& t, uint64_t i) { return i < t.names.size() ? t.names[i].c_str() : ""; }
+
+template <typename Seqs, typename Count, typename Suffix>
+void print_located(const Seqs& f, FILE* out, bool abs, const std::vector<std::string>& queries, Count count, Suffix suffix)
 {
     for (size_t qi = 0; qi < queries.size(); qi++) {
         const std::string& q = queries[qi];
@@ -315,8 +340,8 @@ void print_located(sufr_file* f, FILE* out, bool abs, const std::vector<std::str
         std::vector<Pos> ps;
         for (uint64_t k = 0; k < hits; k++) {
             const uint64_t sfx = suffix(qi, k);
-            const uint64_t i = sufr_file_sequence_of(f, sfx);
-            ps.push_back({sufr_file_sequence_name(f, i), sfx - sufr_file_sequence_start(f, i)});
+            const uint64_t i = seq_of(f, sfx);
+            ps.push_back({seq_name(f, i), sfx - seq_start(f, i)});
         }
         std::stable_sort(ps.begin(), ps.end(), [](const Pos& x, const Pos& y) { return x.name != y.name ? x.name < y.name : x.at < y.at; });
         fprintf(out, "%s\n", q.c_str());
@@ -342,7 +367,7 @@ int cmd_locate(const QueryArgs& a)
     const std::vector<std::string> queries = expand_queries(a.positional);
     std::vector<Hit> hits;
     if (!search_all(f, a, queries, hits)) return 1;
-    print_located(f, out.f, a.abs, queries, [&](size_t qi) { return hits[qi].found ? hits[qi].hi - hits[qi].lo : 0; },
+    print_located(f.f, out.f, a.abs, queries, [&](size_t qi) { return hits[qi].found ? hits[qi].hi - hits[qi].lo : 0; },
                   [&](size_t qi, uint64_t k) { return sufr_file_suffix(f, hits[qi].lo + k); });
     return 0;
 }
@@ -531,6 +556,38 @@ bool named_queries(const QueryArgs& a, std::vector<std::string>& names, std::vec
     return true;
 }
 
+// Search and, with `locate`, locate of a packed batch on a device FM-index: lo, hi (nq each), loff (nq + 1), pos (total
+// entries of w bytes).  false: an error, printed
+bool fm_device_search(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const std::string& bytes, const std::vector<uint64_t>& off, bool locate, uint64_t max_hits,
+                      int w, std::vector<uint64_t>& lo, std::vector<uint64_t>& hi, std::vector<uint64_t>& loff, std::vector<uint8_t>& pos, uint64_t& total)
+{
+    const uint64_t nq = off.size() - 1;
+    auto hits_of = [&](size_t i) { const uint64_t h = hi[i] - lo[i]; return max_hits && h > max_hits ? max_hits : h; };
+    int rc;
+    // one allocation: queries | offsets | lo | hi | the offsets of locate; the positions once their number is known
+    const uint64_t o_at = (bytes.size() + 7) / 8 * 8, lo_at = o_at + (nq + 1) * 8, hi_at = lo_at + nq * 8, l_at = hi_at + nq * 8;
+    uint8_t *d = nullptr, *d_pos = nullptr;
+    bool ok = hipMalloc((void**)&d, l_at + (nq + 1) * 8) == hipSuccess && (bytes.empty() || hipMemcpy(d, bytes.data(), bytes.size(), hipMemcpyHostToDevice) == hipSuccess) &&
+              hipMemcpy(d + o_at, off.data(), (nq + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
+    rc = ok ? sufr_hip_fm_search_batch_device(ctx, fm, d, d + o_at, nq, d + lo_at, d + hi_at) : SUFR_HIP_E_HIP;
+    if (!rc) rc = sufr_hip_synchronize(ctx);
+    ok = !rc && (!nq || (hipMemcpy(lo.data(), d + lo_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+                         hipMemcpy(hi.data(), d + hi_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess));
+    if (ok && locate) {
+        for (size_t i = 0; i < nq; i++) total += hits_of(i);
+        pos.resize((total + 1) * w);
+        ok = hipMalloc((void**)&d_pos, (total + 1) * w) == hipSuccess;
+        rc = ok ? sufr_hip_fm_locate_batch_device(ctx, fm, d + lo_at, d + hi_at, nq, max_hits, d + l_at, d_pos, total, &total) : SUFR_HIP_E_HIP;
+        if (!rc) rc = sufr_hip_synchronize(ctx);
+        ok = ok && !rc && hipMemcpy(loff.data(), d + l_at, (nq + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+             (!total || hipMemcpy(pos.data(), d_pos, total * w, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    if (!ok) fprintf(stderr, "Error: %s\n", rc ? sufr_hip_last_error(ctx) : "device memory for the query batch");
+    if (d_pos) (void)hipFree(d_pos);
+    if (d) (void)hipFree(d);
+    return ok;
+}
+
 // sufr fm: count, or with --locate locate, through an FM-index built from the file (include/sufr_fm.h): the lines are those
 // of `sufr count` / `sufr locate`, the path reads neither the text nor the suffix array once the index stands.
 int cmd_fm(const QueryArgs& a)
@@ -576,27 +633,7 @@ int cmd_fm(const QueryArgs& a)
         if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : dev.error()); return 1; }
         sufr_hip_index_free(dev.ix);            // text and suffix array leave the device: the FM-index answers alone
         dev.ix = nullptr;
-        // one allocation: queries | offsets | lo | hi | the offsets of locate; the positions once their number is known
-        const uint64_t o_at = (bytes.size() + 7) / 8 * 8, lo_at = o_at + (nq + 1) * 8, hi_at = lo_at + nq * 8, l_at = hi_at + nq * 8;
-        uint8_t *d = nullptr, *d_pos = nullptr;
-        bool ok = hipMalloc((void**)&d, l_at + (nq + 1) * 8) == hipSuccess && (bytes.empty() || hipMemcpy(d, bytes.data(), bytes.size(), hipMemcpyHostToDevice) == hipSuccess) &&
-                  hipMemcpy(d + o_at, off.data(), (nq + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
-        rc = ok ? sufr_hip_fm_search_batch_device(dev.ctx, fm, d, d + o_at, nq, d + lo_at, d + hi_at) : SUFR_HIP_E_HIP;
-        if (!rc) rc = sufr_hip_synchronize(dev.ctx);
-        ok = !rc && (!nq || (hipMemcpy(lo.data(), d + lo_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-                             hipMemcpy(hi.data(), d + hi_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess));
-        if (ok && a.locate) {
-            for (size_t i = 0; i < nq; i++) total += hits_of(i);
-            pos.resize((total + 1) * w);
-            ok = hipMalloc((void**)&d_pos, (total + 1) * w) == hipSuccess;
-            rc = ok ? sufr_hip_fm_locate_batch_device(dev.ctx, fm, d + lo_at, d + hi_at, nq, a.max_hits, d + l_at, d_pos, total, &total) : SUFR_HIP_E_HIP;
-            if (!rc) rc = sufr_hip_synchronize(dev.ctx);
-            ok = ok && !rc && hipMemcpy(loff.data(), d + l_at, (nq + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-                 (!total || hipMemcpy(pos.data(), d_pos, total * w, hipMemcpyDeviceToHost) == hipSuccess);
-        }
-        if (!ok) fprintf(stderr, "Error: %s\n", rc ? dev.error() : "device memory for the query batch");
-        if (d_pos) (void)hipFree(d_pos);
-        if (d) (void)hipFree(d);
+        const bool ok = fm_device_search(dev.ctx, fm, bytes, off, a.locate, a.max_hits, w, lo, hi, loff, pos, total);
         sufr_hip_fm_free(fm);
         if (!ok) return 1;
     }
@@ -604,7 +641,7 @@ int cmd_fm(const QueryArgs& a)
         for (size_t i = 0; i < nq; i++) fprintf(out.f, "%s %llu\n", names[i].c_str(), (unsigned long long)(hi[i] - lo[i]));
         return 0;
     }
-    print_located(f, out.f, a.abs, names, [&](size_t qi) { return loff[qi + 1] - loff[qi]; }, [&](size_t qi, uint64_t k) {
+    print_located(f.f, out.f, a.abs, names, [&](size_t qi) { return loff[qi + 1] - loff[qi]; }, [&](size_t qi, uint64_t k) {
         uint64_t p = 0;
         memcpy(&p, pos.data() + (loff[qi] + k) * w, w);               // (little-endian entries of 4 or 8 bytes)
         return p;
@@ -820,6 +857,191 @@ int cmd_fm_approx(const QueryArgs& a)
     return 0;
 }
 
+// sufr fm with --save, --index or --extract (include/sufr_fm_text.h).  The index comes from a .sufr
+// file (built on the host, or on the GPU with --device) or from an index file (--index: loaded and verified; no .sufr is
+// opened, the sequence names are the file's); --save writes it; the queries are then answered by it alone, on the GPU with
+// --device (an index from a file is uploaded, one built there stays).  The lines are those of count, locate, approx
+// (--mismatches) and extract (--extract: the hits through locate, the bases through the FM extract).
+template <typename Seqs>
+std::string place_in(const Seqs& t, bool abs, uint64_t p)
+{
+    if (abs) return std::to_string(p);
+    const uint64_t i = seq_of(t, p);
+    return std::string(seq_name(t, i)) + ":" + std::to_string(p - seq_start(t, i));
+}
+
+int cmd_fm_index(const QueryArgs& a)
+{
+    if (a.fm_approx && a.mismatches > SUFR_FM_APPROX_MAX_MISMATCHES) { fprintf(stderr, "Error: --mismatches must be at most %u\n", SUFR_FM_APPROX_MAX_MISMATCHES); return 1; }
+    const bool from_file = !a.fm_index.empty(), want_text = a.fm_text || a.fm_extract;
+    const bool want_pos = a.locate || a.fm_approx || a.fm_extract || !a.fm_save.empty();
+    if (want_text && !a.sample) { fprintf(stderr, "Error: --text and --extract need the sampled suffixes: -s must be at least 1\n"); return 1; }
+    if (a.fm_approx && !a.sample) { fprintf(stderr, "Error: --mismatches needs the sampled suffixes: -s must be at least 1\n"); return 1; }
+    OutFile out;
+    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    // what is released on every way out
+    struct Held {
+        sufr_file* f = nullptr;
+        sufr_fm* fm = nullptr;
+        sufr_hip_ctx* ctx = nullptr;
+        sufr_hip_index* ix = nullptr;
+        sufr_hip_fm* dfm = nullptr;
+        ~Held()
+        {
+            if (dfm) sufr_hip_fm_free(dfm);
+            if (ix) sufr_hip_index_free(ix);
+            if (ctx) sufr_hip_destroy(ctx);
+            if (fm) sufr_fm_free(fm);
+            if (f) sufr_file_close(f);
+        }
+    } h;
+    char err[512] = {0};
+    SeqTable seqs;
+    if (a.device >= 0 && !(h.ctx = sufr_hip_create(a.device))) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
+    if (from_file) {
+        if (sufr_fm_load(a.fm_index.c_str(), &h.fm, a.threads, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
+        if (h.ctx && sufr_hip_fm_upload(h.ctx, h.fm, &h.dfm) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return 1; }
+        for (uint64_t i = 0; i < sufr_fm_num_sequences(h.fm); i++) {
+            seqs.starts.push_back(sufr_fm_sequence_start(h.fm, i));
+            seqs.names.push_back(sufr_fm_sequence_name(h.fm, i));
+        }
+    } else {
+        h.f = open_or_die(a.file);
+        sufr_file_meta m;
+        sufr_file_metadata(h.f, &m);
+        const char* why = m.len_suffixes != m.text_len || !m.text_len ? "the file leaves text positions out (every position must be indexed: --dna needs --allow-ambiguity)"
+                          : m.seed_mask_len                           ? "the file was built with a seed mask"
+                          : m.max_query_len                           ? "the file was built with a max_query_len"
+                                                                      : nullptr;
+        const char* twice = "the last byte of the text occurs more than once";
+        if (why) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), why); return 1; }
+        const uint64_t sample = want_pos ? a.sample : 0;
+        const uint32_t flags = want_text ? SUFR_FM_TEXT : 0;
+        int rc;
+        if (h.ctx) {
+            if ((rc = sufr_hip_index_load(h.ctx, h.f, &h.ix)) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return 1; }
+            rc = sufr_hip_fm_build_flags(h.ctx, h.ix, sample, flags, &h.dfm);
+            if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : sufr_hip_last_error(h.ctx)); return 1; }
+            sufr_hip_index_free(h.ix);          // text and suffix array leave the device: the FM-index answers alone
+            h.ix = nullptr;
+            if (!a.fm_save.empty() && sufr_hip_fm_download(h.ctx, h.dfm, &h.fm) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return 1; }
+        } else {
+            rc = sufr_file_fm_build_flags(h.f, sample, flags, &h.fm, a.threads);
+            if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : "the build failed"); return 1; }
+        }
+        for (uint64_t i = 0; i < m.num_sequences; i++) {
+            seqs.starts.push_back(sufr_file_sequence_start(h.f, i));
+            seqs.names.push_back(sufr_file_sequence_name(h.f, i));
+        }
+        if (!a.fm_save.empty() && sufr_fm_save(h.fm, a.fm_save.c_str(), h.f, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
+        sufr_file_close(h.f);                   // the index answers alone from here on
+        h.f = nullptr;
+    }
+    sufr_fm_info info;
+    sufr_fm_text_info tinfo;
+    if (h.dfm ? sufr_hip_fm_get_info(h.dfm, &info) || sufr_hip_fm_get_text_info(h.dfm, &tinfo) : sufr_fm_get_info(h.fm, &info) || sufr_fm_get_text_info(h.fm, &tinfo)) {
+        fprintf(stderr, "Error: reading the info of the FM-index failed\n");
+        return 1;
+    }
+    std::vector<std::string> names, queries;
+    if (!named_queries(a, names, queries)) return 1;
+    const uint64_t nq = queries.size();
+    if (!nq) return 0;                          // (--save alone)
+    if ((a.locate || a.fm_approx || a.fm_extract) && !info.sample) {
+        fprintf(stderr, "Error: %s: the index was saved without samples (-s 0): it counts only\n", a.file.c_str());
+        return 1;
+    }
+    if (a.fm_extract && !tinfo.text_samples) {
+        fprintf(stderr, "Error: %s: the index was saved without --text: it cannot give the text back\n", a.file.c_str());
+        return 1;
+    }
+    std::string bytes;
+    std::vector<uint64_t> off(nq + 1, 0);
+    for (size_t i = 0; i < nq; i++) { bytes += queries[i]; off[i + 1] = bytes.size(); }
+    const int w = (int)info.width;
+    if (a.fm_approx) {
+        const uint32_t flags = a.both_strands ? SUFR_FM_APPROX_BOTH_STRANDS : 0, d = (uint32_t)a.mismatches;
+        uint64_t total = 0, cap = 4 * nq + 16;
+        std::vector<uint64_t> qi, pos;
+        std::vector<uint8_t> st, mm;
+        for (;;) {
+            qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
+            const int rc = h.dfm ? sufr_hip_fm_approx(h.ctx, h.dfm, (const uint8_t*)bytes.data(), off.data(), nq, d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total)
+                                 : sufr_fm_approx(h.fm, (const uint8_t*)bytes.data(), off.data(), nq, d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total, a.threads);
+            if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
+            if (rc) { fprintf(stderr, "Error: %s\n", h.dfm ? sufr_hip_last_error(h.ctx) : "the FM-index search failed"); return 1; }
+            break;
+        }
+        for (uint64_t t = 0; t < total; t++)
+            fprintf(out.f, "%s\t%c\t%s\t%u\n", names[qi[t]].c_str(), st[t] ? '-' : '+', place_in(seqs, a.abs, pos[t]).c_str(), (unsigned)mm[t]);
+        return 0;
+    }
+    const bool locate = a.locate || a.fm_extract;
+    const uint64_t max_hits = a.fm_extract ? 0 : a.max_hits;
+    std::vector<uint64_t> lo(nq, 0), hi(nq, 0), loff(nq + 1, 0);
+    std::vector<uint8_t> pos;                   // the positions, w bytes each
+    uint64_t total = 0;
+    if (h.dfm) {
+        if (!fm_device_search(h.ctx, h.dfm, bytes, off, locate, max_hits, w, lo, hi, loff, pos, total)) return 1;
+    } else {
+        int rc = sufr_fm_search_batch(h.fm, (const uint8_t*)bytes.data(), off.data(), nq, lo.data(), hi.data(), a.threads);
+        if (!rc && locate) {
+            for (size_t i = 0; i < nq; i++) total += max_hits && hi[i] - lo[i] > max_hits ? max_hits : hi[i] - lo[i];
+            pos.resize((total + 1) * w);
+            rc = sufr_fm_locate_batch(h.fm, lo.data(), hi.data(), nq, max_hits, loff.data(), pos.data(), total, &total, a.threads);
+        }
+        if (rc) { fprintf(stderr, "Error: the FM-index search failed (%d)\n", rc); return 1; }
+    }
+    auto position = [&](uint64_t at) {
+        uint64_t p = 0;
+        memcpy(&p, pos.data() + at * w, w);                           // (little-endian entries of 4 or 8 bytes)
+        return p;
+    };
+    if (!locate) {
+        for (size_t i = 0; i < nq; i++) fprintf(out.f, "%s %llu\n", names[i].c_str(), (unsigned long long)(hi[i] - lo[i]));
+        return 0;
+    }
+    if (!a.fm_extract) {
+        print_located(seqs, out.f, a.abs, names, [&](size_t qi) { return loff[qi + 1] - loff[qi]; }, [&](size_t qi, uint64_t k) { return position(loff[qi] + k); });
+        return 0;
+    }
+    // the lines of cmd_extract: the range of every hit, then all of them read back in one batch
+    const uint64_t n = info.ranks;
+    struct Line { uint64_t seq, cstart, cend, at; };
+    std::vector<Line> lines(total);
+    std::vector<uint64_t> starts(total), ends(total), boff(total + 1, 0);
+    for (uint64_t t = 0; t < total; t++) {
+        const uint64_t sfx = position(t), i = seq_of(seqs, sfx), s0 = seq_start(seqs, i);
+        const uint64_t seq_end = i + 1 >= seqs.starts.size() ? n : seqs.starts[i + 1];
+        const uint64_t rel = sfx - s0, pre = a.has_prefix ? a.prefix_len : 0;
+        const uint64_t cstart = rel > pre ? rel - pre : 0;
+        uint64_t cend = a.has_suffix ? rel + a.suffix_len : seq_end;
+        if (cend > seq_end) cend = seq_end;
+        lines[t] = Line{i, cstart, cend, rel - cstart};
+        starts[t] = s0 + cstart;
+        ends[t] = starts[t] + (cend > cstart ? cend - cstart : 0);
+    }
+    uint64_t nbytes = 0;
+    for (uint64_t t = 0; t < total; t++) {      // (the clipping of the extract contract)
+        const uint64_t e = ends[t] < n ? ends[t] : n;
+        nbytes += e - (starts[t] < e ? starts[t] : e);
+    }
+    std::vector<uint8_t> text(nbytes + 1);
+    const int rc = h.dfm ? sufr_hip_fm_extract_batch(h.ctx, h.dfm, starts.data(), ends.data(), total, boff.data(), text.data(), nbytes, &nbytes)
+                         : sufr_fm_extract_batch(h.fm, starts.data(), ends.data(), total, boff.data(), text.data(), nbytes, &nbytes, a.threads);
+    if (rc) { fprintf(stderr, "Error: %s\n", h.dfm ? sufr_hip_last_error(h.ctx) : "the FM-index extract failed"); return 1; }
+    for (size_t qi = 0; qi < nq; qi++) {
+        if (loff[qi + 1] == loff[qi]) { fprintf(stderr, "%s not found\n", names[qi].c_str()); continue; }
+        for (uint64_t t = loff[qi]; t < loff[qi + 1]; t++) {
+            fprintf(out.f, ">%s:%llu-%llu %s %llu\n", seq_name(seqs, lines[t].seq), (unsigned long long)lines[t].cstart, (unsigned long long)lines[t].cend,
+                    names[qi].c_str(), (unsigned long long)lines[t].at);
+            fwrite(text.data() + boff[t], 1, (size_t)(boff[t + 1] - boff[t]), out.f);
+            fputc('\n', out.f);
+        }
+    }
+    return 0;
+}
+
 // sufr edit: every text position where a query ends with at most -d edits, one line each in record
 // order (query, strand, end): name, strand (+ / -), the end as seq:offset (0-based) or absolute with --abs, edits.
 // -c: the records are traced back (on the device with --device); two more columns, the start in the
@@ -889,6 +1111,12 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         if (s == "-h" || s == "--help") { usage(stdout); return 0; }
         else if (is_fm && s == "--locate") a.locate = true;
         else if (is_fm && (s == "-s" || s == "--sample")) a.sample = strtoull(need(i, "-s"), nullptr, 10);
+        else if (is_fm && s == "--save") a.fm_save = need(i, "--save");
+        else if (is_fm && s == "--index") a.fm_index = need(i, "--index");
+        else if (is_fm && s == "--text") a.fm_text = true;
+        else if (is_fm && s == "--extract") a.fm_extract = true;
+        else if (is_fm && s == "--prefix-len") { a.has_prefix = true; a.prefix_len = strtoull(need(i, "--prefix-len"), nullptr, 10); }
+        else if (is_fm && s == "--suffix-len") { a.has_suffix = true; a.suffix_len = strtoull(need(i, "--suffix-len"), nullptr, 10); }
         else if (is_fm && s == "--max-hits") a.max_hits = strtoull(need(i, "--max-hits"), nullptr, 10);
         else if (is_fm && (s == "-t" || s == "--threads")) a.threads = atoi(need(i, "-t"));
         else if (!is_list && !is_sum && !is_match && !is_fm && (s == "-m" || s == "--max-query-len")) { a.has_mql = true; a.mql = strtoull(need(i, "-m"), nullptr, 10); }
@@ -922,15 +1150,17 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         else if (!s.empty() && s[0] == '-' && s.size() > 1) { fprintf(stderr, "error: unexpected argument '%s'\n", s.c_str()); return 2; }
         else pos.push_back(s);
     }
+    if (!a.fm_index.empty()) pos.insert(pos.begin(), a.fm_index);      // (fm --index: the index file stands where the .sufr would)
     if (pos.empty()) { fprintf(stderr, "error: the following required arguments were not provided:\n  <%s>\n", is_list ? "FILE" : "SUFR"); return 2; }
     a.file = pos[0];
     a.positional.assign(pos.begin() + 1, pos.end());
-    if (!is_list && !is_sum && a.positional.empty() && !((is_match || is_fm) && !a.reads.empty())) {
+    if (!is_list && !is_sum && a.positional.empty() && !((is_match || is_fm) && !a.reads.empty()) && a.fm_save.empty()) {
         fprintf(stderr, "error: the following required arguments were not provided:\n  <QUERY>...\n");
         return 2;
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
+    if (is_fm && (!a.fm_index.empty() || !a.fm_save.empty() || a.fm_text || a.fm_extract)) return cmd_fm_index(a);
     if (is_fm) return a.fm_approx ? cmd_fm_approx(a) : cmd_fm(a);
     if (is_edit) return cmd_edit(a);
     if (is_approx) return cmd_approx(a);

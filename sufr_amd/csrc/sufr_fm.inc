@@ -28,15 +28,24 @@
 //                  ones in LDS; a count pass (leaves and records of every item, scanned in the workgroup), k_locate_scan over
 //                  the workgroups' sums (the one synchronisation), a fill pass that stores every leaf at its slot, then
 //                  k_fm_locate with the leaves as its queries and k_fm_approx_expand for the other record columns.
-// No scratch.  LDS: k_fm_blocks 34 KB, k_fm_samples 4 KB, k_fm_search and k_fm_locate 3 KB, k_fm_approx 25 KB.
+// k_fm_text_samples  with SUFR_FM_TEXT (include/sufr_fm_text.h, DESIGN.md section 25), behind k_fm_samples on the same tiles: the
+//                  rank of every kept position, text_kept[SA[r] / q] = r.  One writer per entry, no atomics.
+// k_fm_extract     k_fm_extract_counts (a lane per request: its clipped length and its chunks, scanned in the workgroup),
+//                  k_locate_scan over both sums (the one synchronisation, for the two totals), k_fm_extract_apply; then a lane
+//                  per chunk runs fm_extract_chunk of sufr_fm_scan.h: at most q LF steps from a text sample, each one fm_occ_one
+//                  in the block that also holds the step's BWT byte, the bytes gathered in a register and stored as dwords.
+// The copies (sufr_hip_fm_upload / _download) are allocations and copies.
+// No scratch.  LDS: k_fm_blocks 34 KB, k_fm_samples 4 KB, k_fm_search, k_fm_locate and k_fm_extract 3 KB, k_fm_approx 25 KB.
 
-#include "sufr_fm_scan.h"
+#include "../../include/sufr_fm_text.h"
+#include "sufr_fm_host.h"
 
 struct sufr_hip_fm {
     int device = 0;
     sufr::FmView V{};                  // device addresses
     uint64_t samples = 0;
     void *blocks = nullptr, *marks = nullptr, *kept = nullptr, *tabs = nullptr;      // the allocations: tabs = C (257 u64), col (256 u32)
+    void* text_kept = nullptr;         // SUFR_FM_TEXT: the rank of every kept position, `samples` entries of w bytes (sufr_fm_text.h)
 };
 
 namespace sufr {
@@ -407,6 +416,101 @@ __global__ __launch_bounds__(256) void k_fm_samples(const T* __restrict__ sa, ui
     }
 }
 
+// ---- text samples and extract (include/sufr_fm_text.h, DESIGN.md section 25) ------------------------------------------------
+// text_kept[SA[r] / q] = r for the marked ranks of every tile: every entry has one writer, so there is no order in it
+template <typename T>
+__global__ __launch_bounds__(256) void k_fm_text_samples(const T* __restrict__ sa, uint64_t s, uint32_t tile, uint64_t ntiles, uint64_t q, uint64_t samples,
+                                                         T* __restrict__ text_kept)
+{
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t base = t * tile;
+        const uint32_t len = (uint32_t)(s - base < tile ? s - base : tile);
+        for (uint32_t i = threadIdx.x; i < len; i += 256) {
+            const uint64_t p = sa[base + i];
+            if (p % q == 0 && p / q < samples) text_kept[p / q] = (T)(base + i);      // (p < n in a suffix array: the guard keeps any array inside)
+        }
+    }
+}
+
+// A lane per request: its clipped length and its chunks, scanned in the workgroup; wg_*: the workgroup's sums
+__global__ __launch_bounds__(256) void k_fm_extract_counts(const uint64_t* __restrict__ starts, const uint64_t* __restrict__ ends, uint64_t num, uint64_t n,
+                                                           uint64_t q, uint64_t* __restrict__ off, uint64_t* __restrict__ choff,
+                                                           uint64_t* __restrict__ wg_bytes, uint64_t* __restrict__ wg_chunks)
+{
+    __shared__ uint64_t s_w[8];
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t v[2] = {0, 0}, tot[2];                       // bytes, chunks
+    if (i < num) {
+        uint64_t a = starts[i], b = ends[i];
+        fm_extract_clip(n, a, b);
+        v[0] = b - a;
+        v[1] = fm_extract_chunks(q, a, b);
+    }
+    wg_scan(v, tot, s_w);
+    if (i < num) { off[i] = v[0]; choff[i] = v[1]; }
+    if (threadIdx.x == 0) { wg_bytes[blockIdx.x] = tot[0]; wg_chunks[blockIdx.x] = tot[1]; }
+}
+
+// the workgroups' bases (k_locate_scan) onto the offsets of every request, and the two totals behind them
+__global__ __launch_bounds__(256) void k_fm_extract_apply(uint64_t* __restrict__ off, uint64_t* __restrict__ choff, uint64_t num,
+                                                          const uint64_t* __restrict__ wg_bytes, const uint64_t* __restrict__ wg_chunks,
+                                                          const uint64_t* __restrict__ totals)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < num) { off[i] += wg_bytes[i / 256]; choff[i] += wg_chunks[i / 256]; }
+    if (i == num) { off[num] = totals[0]; choff[num] = totals[1]; }
+}
+
+// the low cnt <= 3 bytes of acc to a[0 .. cnt)
+__device__ __forceinline__ void fm_put_bytes(uint8_t* a, uint32_t acc, uint32_t cnt)
+{
+    if (cnt > 0) a[0] = (uint8_t)acc;
+    if (cnt > 1) a[1] = (uint8_t)(acc >> 8);
+    if (cnt > 2) a[2] = (uint8_t)(acc >> 16);
+}
+
+// A lane per chunk: fm_extract_chunk of sufr_fm_scan.h with a step that reads the block once, for the byte and for its occ.
+// The lane's bytes go to consecutive addresses, downwards: they are gathered in one register, the byte of the lower address
+// shifted in below the others, and stored as a dword whenever an aligned address is reached with four of them, as single
+// bytes at the two edges of the lane's slice (a neighbouring lane owns the rest of those dwords).
+template <bool LINE>
+__global__ __launch_bounds__(256) void k_fm_extract(FmView V, const uint8_t* __restrict__ text_kept, const uint64_t* __restrict__ starts,
+                                                    const uint64_t* __restrict__ ends, uint64_t num, const uint64_t* __restrict__ off,
+                                                    const uint64_t* __restrict__ choff, uint64_t nchunks, uint8_t* __restrict__ bytes)
+{
+    __shared__ uint64_t s_C[257];
+    __shared__ uint32_t s_col[256];
+    fm_stage_tables(V, s_C, s_col);
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nchunks) return;
+    const uint64_t i = last_le(choff, 0, num, j);                    // the request whose chunks hold chunk j
+    uint64_t lo = starts[i], hi = ends[i];
+    fm_extract_clip(V.s, lo, hi);
+    const uint64_t k = lo / V.q + (j - choff[i]);
+    const uint64_t r0 = fm_ld(text_kept + fm_extract_slot(V.q, V.s, k) * V.sh.w, V.sh.w);
+    const uint32_t B = fm_B<LINE>(V.sh);
+    uint8_t* const dst = bytes + off[i];                             // of position lo
+    uint32_t acc = 0, cnt = 0;
+    uint8_t* a = dst;
+    fm_extract_chunk(V.q, V.s, k, lo, hi, r0,
+        [&](uint64_t r, uint32_t& c) {
+            const uint8_t* pb = V.blocks + r / B * fm_stride<LINE>(V.sh);
+            const uint32_t rem = (uint32_t)(r % B);
+            c = pb[fm_cbytes<LINE>(V.sh) + rem];
+            return fm_occ_one<LINE>(V, c, s_col[c], s_C[c], pb, rem);
+        },
+        [&](uint64_t p, uint32_t c) {
+            a = dst + (p - lo);
+            acc = acc << 8 | c;
+            cnt++;
+            if (((uintptr_t)a & 3u) == 0) {
+                if (cnt == 4) *(uint32_t*)a = acc; else fm_put_bytes(a, acc, cnt);
+                cnt = 0;
+            }
+        });
+    fm_put_bytes(a, acc, cnt);                                       // (the lower edge: a is the lane's lowest address, cnt <= 3)
+}
+
 }  // namespace sufr
 
 namespace {
@@ -427,7 +531,7 @@ int fm_alloc(sufr::Pipeline& pl, void** p, uint64_t bytes, const char* what)
 }
 
 template <typename T>
-int fm_build_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, sufr_hip_fm* fm)
+int fm_build_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, uint32_t flags, sufr_hip_fm* fm)
 {
     sufr::Pipeline& pl = ctx->pl;
     const uint64_t s = ix->ix.s, n = ix->ix.n;
@@ -483,6 +587,13 @@ int fm_build_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, s
         V.kept = (const uint8_t*)fm->kept;
         hipLaunchKernelGGL(sufr::k_fm_samples<T>, dim3(grid), dim3(256), 0, pl.stream, sa, s, tile, ntiles, (const uint64_t*)t_cnt, (sufr::FmMark*)fm->marks,
                            (T*)fm->kept);
+        if (flags & SUFR_FM_TEXT) {
+            if ((rc = fm_alloc(pl, &fm->text_kept, total * sh.w, "text samples"))) return rc;
+            // (a suffix array writes every entry; rank 0 where an array that is none leaves one out, so that every walk stays inside)
+            if (hipMemsetAsync(fm->text_kept, 0, total * sh.w, pl.stream) != hipSuccess) { pl.set_error("fm_build: memset failed"); return SUFR_HIP_E_HIP; }
+            hipLaunchKernelGGL(sufr::k_fm_text_samples<T>, dim3(grid), dim3(256), 0, pl.stream, sa, s, tile, ntiles, sample, (uint64_t)total,
+                               (T*)fm->text_kept);
+        }
     }
     if ((rc = launch_status(pl, "fm_build"))) return rc;
     if (hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("fm_build: the build failed"); return SUFR_HIP_E_HIP; }      // nothing reads ix from here on
@@ -497,23 +608,16 @@ int fm_check(sufr_hip_ctx* ctx, const sufr_hip_fm* fm)
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-void sufr_hip_fm_free(sufr_hip_fm* fm)
-{
-    if (!fm) return;
-    (void)hipSetDevice(fm->device);
-    for (void* p : {fm->blocks, fm->marks, fm->kept, fm->tabs}) if (p) (void)hipFree(p);
-    delete fm;
-}
-
-int sufr_hip_fm_build(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, sufr_hip_fm** out)
+// sufr_hip_fm_build_flags (include/sufr_fm_text.h); flags == 0: sufr_hip_fm_build
+int fm_build_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, uint32_t flags, sufr_hip_fm** out)
 {
     if (!ctx || !ix || !out) return SUFR_HIP_E_INVALID;
     *out = nullptr;
     ctx->pl.err.clear();
+    if ((flags & ~SUFR_FM_TEXT) || ((flags & SUFR_FM_TEXT) && !sample)) {
+        ctx->pl.set_error("fm_build: unknown flags, or SUFR_FM_TEXT with sample == 0");
+        return SUFR_HIP_E_INVALID;
+    }
     if (const int rc = query_check(ctx, ix)) return rc;
     const char* why = !ix->ix.n || ix->ix.s != ix->ix.n ? "the index leaves text positions out"
                       : ix->ix.maskpos                 ? "the index was built with a seed mask"
@@ -522,7 +626,7 @@ int sufr_hip_fm_build(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t samp
     if (why) { ctx->pl.set_error(std::string("fm_build: ") + why); return SUFR_HIP_E_UNSUPPORTED; }
     sufr_hip_fm* fm = new sufr_hip_fm;
     fm->device = ctx->pl.device;
-    const int rc = by_width(ix, [&](auto w) { return fm_build_run<decltype(w)>(ctx, ix, sample, fm); });
+    const int rc = by_width(ix, [&](auto w) { return fm_build_run<decltype(w)>(ctx, ix, sample, flags, fm); });
     if (rc) {
         (void)hipStreamSynchronize(ctx->pl.stream);                 // (nothing in flight writes what is freed)
         sufr_hip_fm_free(fm);
@@ -531,6 +635,20 @@ int sufr_hip_fm_build(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t samp
     *out = fm;
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
+
+void sufr_hip_fm_free(sufr_hip_fm* fm)
+{
+    if (!fm) return;
+    (void)hipSetDevice(fm->device);
+    for (void* p : {fm->blocks, fm->marks, fm->kept, fm->tabs, fm->text_kept}) if (p) (void)hipFree(p);
+    delete fm;
+}
+
+int sufr_hip_fm_build(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, sufr_hip_fm** out) { return fm_build_device(ctx, ix, sample, 0, out); }
 
 int sufr_hip_fm_get_info(const sufr_hip_fm* fm, sufr_fm_info* info)
 {
@@ -658,6 +776,159 @@ int sufr_hip_fm_approx(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const uint8_t* 
                           [&](const void* d_q, const void* d_off, void* const* col, uint64_t* total) {
         return sufr_hip_fm_approx_device(ctx, fm, d_q, d_off, num_queries, max_mismatches, flags, cap, col[0], col[1], col[2], col[3], total);
     });
+}
+
+// ---- include/sufr_fm_text.h: text samples, extract and the copies between host and device (DESIGN.md section 25) ----------
+int sufr_hip_fm_build_flags(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, uint32_t flags, sufr_hip_fm** out)
+{
+    return fm_build_device(ctx, ix, sample, flags, out);
+}
+
+int sufr_hip_fm_get_text_info(const sufr_hip_fm* fm, sufr_fm_text_info* info)
+{
+    if (!fm || !info) return SUFR_HIP_E_INVALID;
+    const sufr::FmView& V = fm->V;
+    const uint64_t ts = fm->text_kept ? fm->samples : 0;
+    *info = sufr_fm_text_info{ts, ts * V.sh.w, sufr::fm_file_layout(V.sh, V.s, V.q, fm->samples, fm->text_kept != nullptr, 0, 0).bytes};
+    return 0;
+}
+
+int sufr_hip_fm_extract_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const void* d_starts, const void* d_ends, uint64_t num,
+                                     void* d_offsets, void* d_bytes, uint64_t cap, uint64_t* total_out)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !fm || !d_offsets || (num && (!d_starts || !d_ends))) return SUFR_HIP_E_INVALID;
+    sufr::Pipeline& pl = ctx->pl;
+    int rc;
+    if ((rc = fm_check(ctx, fm))) return rc;
+    if (!fm->text_kept) { pl.set_error("fm_extract: the index was built without SUFR_FM_TEXT"); return SUFR_HIP_E_UNSUPPORTED; }
+    if (!num) {
+        if (hipMemsetAsync(d_offsets, 0, 8, pl.stream) != hipSuccess) { pl.set_error("fm_extract: memset failed"); return SUFR_HIP_E_HIP; }
+        return 0;
+    }
+    const uint64_t wgs = (num + 255) / 256;
+    if (wgs > 0x7fffffffull) { pl.set_error("fm_extract: too many requests in one batch"); return SUFR_HIP_E_INVALID; }
+    // xlo: the chunks in front of every request; xsum: the workgroups' bytes, their chunks, the two totals
+    if ((rc = pl.ensure(ctx->xlo, (num + 1) * 8)) || (rc = pl.ensure(ctx->xsum, (2 * wgs + 2) * 8))) return rc;
+    uint64_t* off = (uint64_t*)d_offsets;
+    uint64_t* choff = (uint64_t*)ctx->xlo.p;
+    uint64_t* sums = (uint64_t*)ctx->xsum.p;
+    const sufr::FmView& V = fm->V;
+    hipLaunchKernelGGL(sufr::k_fm_extract_counts, dim3((uint32_t)wgs), dim3(256), 0, pl.stream, (const uint64_t*)d_starts, (const uint64_t*)d_ends, num,
+                       V.s, V.q, off, choff, sums, sums + wgs);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, sums, wgs, sums + 2 * wgs);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, sums + wgs, wgs, sums + 2 * wgs + 1);
+    hipLaunchKernelGGL(sufr::k_fm_extract_apply, dim3((uint32_t)((num + 256) / 256)), dim3(256), 0, pl.stream, off, choff, num, (const uint64_t*)sums,
+                       (const uint64_t*)(sums + wgs), (const uint64_t*)(sums + 2 * wgs));
+    unsigned long long totals[2] = {0, 0};               // bytes, chunks
+    if ((rc = launch_status(pl, "fm_extract")) || (rc = read_totals(pl, sums + 2 * wgs, 2, totals, "fm_extract", "counting the bytes failed"))) return rc;
+    if ((rc = records_fit(pl, "fm_extract", "bytes", totals[0], cap, total_out)) || !totals[0]) return rc;
+    if (!d_bytes) return SUFR_HIP_E_INVALID;
+    const uint64_t blocks = (totals[1] + 255) / 256;
+    if (blocks > 0x7fffffffull) { pl.set_error("fm_extract: too many chunks for one launch"); return SUFR_HIP_E_INVALID; }
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, pl.stream, V, (const uint8_t*)fm->text_kept, (const uint64_t*)d_starts,
+                           (const uint64_t*)d_ends, num, (const uint64_t*)off, (const uint64_t*)choff, (uint64_t)totals[1], (uint8_t*)d_bytes);
+    };
+    if (sufr::fm_is_line(V.sh)) launch(sufr::k_fm_extract<true>); else launch(sufr::k_fm_extract<false>);
+    return launch_status(pl, "fm_extract");
+}
+
+int sufr_hip_fm_extract_batch(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const uint64_t* starts, const uint64_t* ends, uint64_t num, uint64_t* offsets,
+                              uint8_t* bytes, uint64_t cap, uint64_t* total_out)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !fm || !offsets || (num && (!starts || !ends))) return SUFR_HIP_E_INVALID;
+    if (const int rc = fm_check(ctx, fm)) return rc;
+    if (!fm->text_kept) { ctx->pl.set_error("fm_extract: the index was built without SUFR_FM_TEXT"); return SUFR_HIP_E_UNSUPPORTED; }
+    if (!num) { offsets[0] = 0; return 0; }
+    // the requests are the staged bytes: starts | ends, one "query" of 16 num bytes; the offsets come back from the extra room
+    std::vector<uint64_t> req(2 * num);
+    memcpy(req.data(), starts, num * 8);
+    memcpy(req.data() + num, ends, num * 8);
+    const uint64_t req_bytes[1] = {16 * num};
+    return staged_records(ctx, "FM extract", (const uint8_t*)req.data(), req_bytes, 0, cap, {{bytes, 1}}, (num + 1) * 8, total_out,
+                          [&](const void* d_req, const void*, void* const* col, uint64_t* total) {
+        int rc = sufr_hip_fm_extract_batch_device(ctx, fm, d_req, (const uint64_t*)d_req + num, num, col[1], col[0], cap, total);
+        if ((!rc || rc == SUFR_HIP_E_CAPACITY) && (hipMemcpyAsync(offsets, col[1], (num + 1) * 8, hipMemcpyDeviceToHost, ctx->pl.stream) != hipSuccess ||
+                                                   hipStreamSynchronize(ctx->pl.stream) != hipSuccess)) rc = SUFR_HIP_E_HIP;
+        return rc;
+    });
+}
+
+int sufr_hip_fm_upload(sufr_hip_ctx* ctx, const sufr_fm* h, sufr_hip_fm** out)
+{
+    if (!ctx || !h || !out) return SUFR_HIP_E_INVALID;
+    *out = nullptr;
+    sufr::Pipeline& pl = ctx->pl;
+    pl.err.clear();
+    if (hipSetDevice(pl.device) != hipSuccess) { pl.set_error("hipSetDevice failed"); return SUFR_HIP_E_HIP; }
+    sufr_hip_fm* fm = new sufr_hip_fm;
+    fm->device = pl.device;
+    fm->samples = h->samples;
+    std::vector<uint8_t> tabs(sufr::FM_TABLE_BYTES);
+    memcpy(tabs.data(), h->C, 257 * 8);
+    memcpy(tabs.data() + 257 * 8, h->col, 256 * 4);
+    struct Part { void** d; const void* src; uint64_t bytes; const char* what; bool have; };
+    const Part parts[] = {{&fm->blocks, h->blocks.data(), h->blocks.size(), "blocks", true},
+                          {&fm->tabs, tabs.data(), tabs.size(), "tables", true},
+                          {&fm->marks, h->marks.data(), h->marks.size() * sizeof(sufr::FmMark), "marks", h->q != 0},
+                          {&fm->kept, h->kept.data(), h->kept.size(), "samples", h->q != 0},
+                          {&fm->text_kept, h->text_kept.data(), h->text_kept.size(), "text samples", !h->text_kept.empty()}};
+    int rc = 0;
+    for (const Part& p : parts) {
+        if (!p.have) continue;
+        if ((rc = fm_alloc(pl, p.d, p.bytes, p.what))) break;
+        if (p.bytes && hipMemcpy(*p.d, p.src, p.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            pl.set_error(std::string("fm_upload: copying the ") + p.what + " failed");
+            rc = SUFR_HIP_E_HIP;
+            break;
+        }
+    }
+    if (rc) { sufr_hip_fm_free(fm); return rc; }
+    uint64_t* d_C = (uint64_t*)fm->tabs;
+    fm->V = sufr::FmView{(const uint8_t*)fm->blocks, (const sufr::FmMark*)fm->marks, (const uint8_t*)fm->kept, d_C, (const uint32_t*)(d_C + 257),
+                         h->s, h->q, h->sh, h->e};
+    *out = fm;
+    return 0;
+}
+
+int sufr_hip_fm_download(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, sufr_fm** out)
+{
+    if (!ctx || !fm || !out) return SUFR_HIP_E_INVALID;
+    *out = nullptr;
+    if (const int rc = fm_check(ctx, fm)) return rc;
+    sufr::Pipeline& pl = ctx->pl;
+    if (hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("fm_download: the stream failed"); return SUFR_HIP_E_HIP; }
+    const sufr::FmView& V = fm->V;
+    const sufr::FmShape sh = V.sh;
+    sufr_fm* h = new sufr_fm;
+    h->sh = sh; h->s = V.s; h->q = V.q; h->samples = fm->samples; h->e = V.e;
+    std::vector<uint8_t> tabs(sufr::FM_TABLE_BYTES);
+    h->blocks.resize(sufr::fm_blocks(V.s, sh.B) * sh.stride);
+    if (V.q) { h->marks.resize(sufr::fm_mark_words(V.s)); h->kept.resize(fm->samples * sh.w); }
+    if (fm->text_kept) h->text_kept.resize(fm->samples * sh.w);
+    struct Part { void* dst; const void* d; uint64_t bytes; };
+    const Part parts[] = {{h->blocks.data(), fm->blocks, h->blocks.size()}, {tabs.data(), fm->tabs, tabs.size()},
+                          {h->marks.data(), fm->marks, h->marks.size() * sizeof(sufr::FmMark)}, {h->kept.data(), fm->kept, h->kept.size()},
+                          {h->text_kept.data(), fm->text_kept, h->text_kept.size()}};
+    for (const Part& p : parts)
+        if (p.bytes && hipMemcpy(p.dst, p.d, p.bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+            pl.set_error("fm_download: copying the index failed");
+            delete h;
+            return SUFR_HIP_E_HIP;
+        }
+    memcpy(h->C, tabs.data(), 257 * 8);
+    memcpy(h->col, tabs.data() + 257 * 8, 256 * 4);
+    // what the file format wants zero, whoever built the index: the checkpoint bytes behind K w, the BWT bytes behind s and
+    // the mark bits behind s
+    const uint64_t nblocks = h->blocks.size() / sh.stride;
+    if (sh.K * sh.w < sh.cbytes)
+        for (uint64_t j = 0; j < nblocks; j++) memset(h->blocks.data() + j * sh.stride + sh.K * sh.w, 0, sh.cbytes - sh.K * sh.w);
+    memset(h->blocks.data() + (nblocks - 1) * sh.stride + sh.cbytes + V.s % sh.B, 0, sh.B - V.s % sh.B);
+    if (V.q && (V.s & 63u)) h->marks.back().bits &= ((uint64_t)1 << (V.s & 63u)) - 1;
+    *out = h;
+    return 0;
 }
 
 }  // extern "C"

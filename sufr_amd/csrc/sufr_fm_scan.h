@@ -1,6 +1,6 @@
 // sufr_fm_scan.h -- the layout and the arithmetic of the FM-index over the BWT of the indexed text (include/sufr_fm.h,
 // DESIGN.md section 23): the shape of a block, the count of a byte value in the front of a block, occ, the backward search
-// of one query, the walk from a rank to a sampled suffix and the backtracking walk of the k-mismatch search (section 24).  Plain integer code that the kernels of sufr_fm.inc and the host
+// of one query, the walk from a rank to a sampled suffix, the chunk walk of extract (section 25) and the backtracking walk of the k-mismatch search (section 24).  Plain integer code that the kernels of sufr_fm.inc and the host
 // path of sufr_query.cpp both compile (SUFR_HD, the way of sufr_bwt_scan.h); there is no second copy of it.  The kernels read
 // a block with wider loads than fm_occ does and count with the same fm_eq_bytes.
 //
@@ -123,6 +123,44 @@ SUFR_HD uint64_t fm_position(const FmView& V, uint64_t r)
         r = V.C[c] + fm_occ(V, c, r);
     }
     return ~(uint64_t)0;
+}
+
+// ---- extract: a range of the text read back from the BWT (include/sufr_fm_text.h) ------------------
+// One LF step from rank r < s: c = BWT[r], the byte in front of the suffix of rank r, and the rank of the suffix that begins
+// with it.  On the cyclic row (SA[r] == 0) c is the end byte and the step gives C[e], the rank of suffix n - 1: the row stands
+// for position n there (include/sufr_fm_text.h), which is the one use extract makes of it.
+SUFR_HD uint64_t fm_lf(const FmView& V, uint64_t r, uint32_t& c)
+{
+    c = V.blocks[r / V.sh.B * V.sh.stride + V.sh.cbytes + r % V.sh.B];
+    return V.C[c] + fm_occ(V, c, r);
+}
+
+// A clipped request [start, end) with start < end <= n holds the chunks first .. first + count - 1 of q positions each
+SUFR_HD void fm_extract_clip(uint64_t n, uint64_t& start, uint64_t& end)
+{
+    if (end > n) end = n;
+    if (start > end) start = end;
+}
+SUFR_HD uint64_t fm_extract_chunks(uint64_t q, uint64_t start, uint64_t end) { return start < end ? (end - 1) / q - start / q + 1 : 0; }
+
+// The entry of text_kept that chunk k of an index of n positions starts from: k + 1, the rank of position (k + 1) q, where
+// that is a position of the text; else 0, the cyclic row, which stands for position n
+SUFR_HD uint64_t fm_extract_slot(uint64_t q, uint64_t n, uint64_t k) { return (k + 1) * q < n ? k + 1 : 0; }
+
+// Chunk k of the clipped request [start, end): from r, the rank text_kept[fm_extract_slot(q, n, k)], top - min(end, top) silent
+// steps and then one emit(p, T[p]) per step for p = min(end, top) - 1 down to max(start, k q); top = min((k + 1) q, n).  q steps
+// at most.  lf(r, c) is one LF step: it sets c = BWT[r] and returns the next rank (fm_lf, or the kernel's wider loads).
+template <class Lf, class Emit>
+SUFR_HD void fm_extract_chunk(uint64_t q, uint64_t n, uint64_t k, uint64_t start, uint64_t end, uint64_t r, Lf&& lf, Emit&& emit)
+{
+    const uint64_t top = (k + 1) * q < n ? (k + 1) * q : n;
+    const uint64_t hi = end < top ? end : top, lo = start > k * q ? start : k * q;
+    uint32_t c = 0;
+    for (uint64_t p = top; p > hi; p--) r = lf(r, c);
+    for (uint64_t p = hi; p > lo; p--) {
+        r = lf(r, c);
+        emit(p - 1, c);
+    }
 }
 
 // ---- k-mismatch search by backtracking (include/sufr_fm.h) ---------------------------------------

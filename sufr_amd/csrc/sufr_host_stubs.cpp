@@ -25,6 +25,7 @@
 #include "../../include/sufr_shared.h"
 #include "../../include/sufr_bwt.h"
 #include "../../include/sufr_fm_approx.h"
+#include "../../include/sufr_fm_text.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -206,5 +207,14 @@ int sufr_hip_fm_approx_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const void*
                               void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 int sufr_hip_fm_approx(sufr_hip_ctx* ctx, const sufr_hip_fm*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint32_t, uint64_t, uint64_t*, uint8_t*,
                        uint64_t*, uint8_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+// ---- include/sufr_fm_text.h: the device side
+int sufr_hip_fm_build_flags(sufr_hip_ctx* ctx, const sufr_hip_index*, uint64_t, uint32_t, sufr_hip_fm** out) { if (out) *out = nullptr; return no_device(ctx); }
+int sufr_hip_fm_get_text_info(const sufr_hip_fm*, sufr_fm_text_info*) { return SUFR_HIP_E_NO_DEVICE; }
+int sufr_hip_fm_extract_batch_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const void*, const void*, uint64_t, void*, void*, uint64_t,
+                                     uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_fm_extract_batch(sufr_hip_ctx* ctx, const sufr_hip_fm*, const uint64_t*, const uint64_t*, uint64_t, uint64_t*, uint8_t*, uint64_t,
+                              uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_fm_upload(sufr_hip_ctx* ctx, const sufr_fm*, sufr_hip_fm** out) { if (out) *out = nullptr; return no_device(ctx); }
+int sufr_hip_fm_download(sufr_hip_ctx* ctx, const sufr_hip_fm*, sufr_fm** out) { if (out) *out = nullptr; return no_device(ctx); }
 
 }  // extern "C"

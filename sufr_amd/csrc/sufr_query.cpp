@@ -1500,18 +1500,8 @@ int sufr_file_lf(const sufr_file* f, void* lf, int threads)
 // ---- the FM-index over the BWT: backward search and locate without text and suffix array (include/sufr_fm.h, DESIGN.md
 // section 23) ---------------------------------------------------------------------------------------------------------
 #include "../../include/sufr_fm_approx.h"
-#include "sufr_fm_scan.h"
-
-struct sufr_fm {
-    sufr::FmShape sh{};
-    uint64_t s = 0, q = 0, samples = 0;
-    uint32_t e = 0;
-    uint64_t C[257] = {0};
-    uint32_t col[256];
-    std::vector<uint8_t> blocks, kept;
-    std::vector<sufr::FmMark> marks;
-    sufr::FmView view() const { return sufr::FmView{blocks.data(), marks.data(), kept.data(), C, col, s, q, sh, e}; }
-};
+#include "../../include/sufr_fm_text.h"
+#include "sufr_fm_host.h"
 
 namespace {
 
@@ -1521,14 +1511,12 @@ uint64_t fm_bytes(const sufr::FmShape& sh, uint64_t s, uint64_t q, uint64_t samp
     return sufr::fm_blocks(s, sh.B) * sh.stride + (q ? sufr::fm_mark_words(s) * sizeof(sufr::FmMark) + samples * sh.w : 0) + 257 * 8 + 256 * 4;
 }
 
-}  // namespace
-
-extern "C" {
-
-int sufr_file_fm_build(const sufr_file* f, uint64_t sample, sufr_fm** out, int threads)
+// sufr_file_fm_build_flags (include/sufr_fm_text.h); flags == 0: sufr_file_fm_build
+int fm_build_host(const sufr_file* f, uint64_t sample, uint32_t flags, sufr_fm** out, int threads)
 {
     if (!f || !out) return SUFR_HIP_E_INVALID;
     *out = nullptr;
+    if ((flags & ~SUFR_FM_TEXT) || ((flags & SUFR_FM_TEXT) && !sample)) return SUFR_HIP_E_INVALID;
     const uint64_t s = f->meta.len_suffixes, n = f->meta.text_len;
     if (!n || s != n || f->meta.seed_mask_len || f->meta.max_query_len) return SUFR_HIP_E_UNSUPPORTED;
     const std::vector<uint8_t> bwt = bwt_host_bytes(*f, threads);
@@ -1588,17 +1576,30 @@ int sufr_file_fm_build(const sufr_file* f, uint64_t sample, sufr_fm** out, int t
         });
         for (uint64_t t = 0; t < ntiles; t++) { const uint64_t k = kept[t]; kept[t] = fm->samples; fm->samples += k; }
         fm->kept.assign(fm->samples * w, 0);
+        const bool text = flags & SUFR_FM_TEXT;                       // (s == n: the kept positions are 0, q, 2 q, ..: one entry each)
+        if (text) fm->text_kept.assign(fm->samples * w, 0);
         parallel_chunks(ntiles, 1, threads, [&](uint64_t t, uint64_t) {
             uint64_t o = kept[t];
             for (uint64_t r = t * tile, end = r + tile < s ? r + tile : s; r < end; r++) {
                 if (!(r & 63u)) fm->marks[r >> 6].before = o;
-                if (sufr::fm_marked(fm->marks[r >> 6], r)) kmer_put(fm->kept.data(), w, o++, rdT(f->sa, w, r));
+                if (!sufr::fm_marked(fm->marks[r >> 6], r)) continue;
+                const uint64_t p = rdT(f->sa, w, r);
+                kmer_put(fm->kept.data(), w, o++, p);
+                if (text) kmer_put(fm->text_kept.data(), w, p / sample, r);
             }
         });
     }
+    fm->seq_starts = f->seq_starts;
+    fm->seq_names = f->seq_names;
     *out = fm;
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_fm_build(const sufr_file* f, uint64_t sample, sufr_fm** out, int threads) { return fm_build_host(f, sample, 0, out, threads); }
 
 void sufr_fm_free(sufr_fm* fm) { delete fm; }
 
@@ -1763,6 +1764,300 @@ int sufr_fm_approx_steps(const sufr_fm* fm, const uint8_t* queries, const uint64
             steps[a] = ops.steps;
         }
     }, 4);
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- the FM-index as a self-contained object: extract, the index file, the sequences (include/sufr_fm_text.h, DESIGN.md
+// section 25) ----------------------------------------------------------------------------------------------------------------
+namespace {
+
+uint64_t fm_name_bytes(const std::vector<std::string>& names)
+{
+    uint64_t b = 0;
+    for (const std::string& s : names) b += strlen(s.c_str()) + 1;
+    return b;
+}
+
+// the head of the index file; the rest of its first page is zero
+struct FmFileHeader {
+    char magic[8];
+    uint32_t version, flags, w, e, K, B, stride, cbytes;
+    uint64_t s, q, samples, sequences;
+    uint64_t sec[2 * sufr::FM_FILE_SECTIONS];            // (offset, length) of every section
+};
+static_assert(sizeof(FmFileHeader) == 184, "the header of the index file is 184 bytes");
+const char FM_FILE_MAGIC[8] = {'S', 'U', 'F', 'R', 'F', 'M', 'I', 0};
+
+sufr::FmFileLayout fm_layout_of(const sufr_fm* fm, uint64_t sequences, uint64_t name_bytes)
+{
+    return sufr::fm_file_layout(fm->sh, fm->s, fm->q, fm->samples, !fm->text_kept.empty(), sequences, name_bytes);
+}
+
+bool fm_starts_fit(const uint64_t* starts, uint64_t num, uint64_t s)
+{
+    for (uint64_t i = 0; i < num; i++) if (starts[i] >= s || (i && starts[i] < starts[i - 1])) return false;
+    return true;
+}
+
+// The checks of sufr_fm_load on the arrays of `fm`, whose header fields have been checked: "" or the check that failed
+std::string fm_verify(const sufr_fm* fm, bool text, int threads)
+{
+    const sufr::FmShape sh = fm->sh;
+    const uint64_t s = fm->s, q = fm->q;
+    uint32_t K = 0, sym[256];
+    if (fm->C[0] != 0) return "tables: C[0] is not 0";
+    for (uint32_t c = 0; c < 256; c++) {
+        if (fm->C[c + 1] < fm->C[c]) return "tables: C decreases at byte value " + std::to_string(c);
+        const bool occurs = fm->C[c + 1] > fm->C[c];
+        if (fm->col[c] != (occurs ? K : sufr::FM_NO_COL)) return "tables: the column of byte value " + std::to_string(c) + " is not its number among the occurring ones";
+        if (occurs) { if (K < 256) sym[K] = c; K++; }
+    }
+    if (K != sh.K) return "tables: " + std::to_string(K) + " byte values occur, the header says " + std::to_string(sh.K);
+    if (fm->C[256] != s) return "tables: C[256] is not the number of ranks";
+    if (fm->C[fm->e + 1] - fm->C[fm->e] != 1) return "tables: the end byte does not occur exactly once";
+    std::mutex mu;
+    std::string bad;
+    std::atomic<bool> failed{false};
+    auto fail = [&](const std::string& why) {
+        std::lock_guard<std::mutex> lock(mu);
+        if (bad.empty()) bad = why;
+        failed = true;
+    };
+    // blocks: every checkpoint against the one before it plus the bytes between them, so the tiles are independent
+    const uint64_t nblocks = sufr::fm_blocks(s, sh.B);
+    parallel_chunks(nblocks, 512, threads, [&](uint64_t b, uint64_t end) {
+        uint64_t cnt[256];
+        for (uint64_t j = b; j < end && !failed; j++) {
+            const uint8_t* p = fm->blocks.data() + j * sh.stride;
+            const uint64_t len = s - j * sh.B < sh.B ? s - j * sh.B : sh.B;
+            const std::string at = "block " + std::to_string(j);
+            for (uint32_t i = K * sh.w; i < sh.cbytes; i++) if (p[i]) return fail("blocks: " + at + " has a non-zero byte behind its checkpoints");
+            for (uint32_t k = 0; k < K; k++) cnt[k] = 0;
+            for (uint64_t i = 0; i < len; i++) {
+                const uint32_t k = fm->col[p[sh.cbytes + i]];
+                if (k == sufr::FM_NO_COL) return fail("blocks: " + at + " holds a byte value that has no column");
+                cnt[k]++;
+            }
+            for (uint64_t i = len; i < sh.B; i++) if (p[sh.cbytes + i]) return fail("blocks: " + at + " has a non-zero byte behind the last rank");
+            for (uint32_t k = 0; k < K; k++) {
+                const uint64_t have = sufr::fm_rd(p + k * sh.w, sh.w);
+                if (j == 0 && have != 0) return fail("blocks: a checkpoint of block 0 is not 0");
+                const uint64_t next = j + 1 < nblocks ? sufr::fm_rd(p + sh.stride + k * sh.w, sh.w) : fm->C[sym[k] + 1] - fm->C[sym[k]];
+                if (have + cnt[k] != next)
+                    return fail(j + 1 < nblocks ? "blocks: a checkpoint of block " + std::to_string(j + 1) + " is not the running count"
+                                                : std::string("blocks: the final counts are not the differences of C"));
+            }
+        }
+    }, 512);
+    if (failed) return bad;
+    if (!q) return "";
+    const uint64_t nwords = sufr::fm_mark_words(s);
+    parallel_chunks(nwords, 4096, threads, [&](uint64_t b, uint64_t end) {
+        for (uint64_t i = b; i < end; i++) {
+            const sufr::FmMark mk = fm->marks[i];
+            const uint64_t next = i + 1 < nwords ? fm->marks[i + 1].before : fm->samples;
+            if ((i == 0 && mk.before != 0) || mk.before > next || next - mk.before != (uint64_t)__builtin_popcountll(mk.bits))
+                return fail("marks: `before` of word " + std::to_string(i + 1 < nwords ? i + 1 : i) + " is not the running count (the total: the samples)");
+            if (i + 1 == nwords && (s & 63u) && (mk.bits >> (s & 63u))) return fail("marks: a bit is set behind the last rank");
+        }
+    }, 4096);
+    if (failed) return bad;
+    std::atomic<bool> zero{false};
+    parallel_chunks(fm->samples, 4096, threads, [&](uint64_t b, uint64_t end) {
+        for (uint64_t i = b; i < end; i++) {
+            const uint64_t v = rdT(fm->kept.data(), (int)sh.w, i);
+            if (v % q || v >= s) return fail("kept: entry " + std::to_string(i) + " is not a multiple of the sample rate below the number of ranks");
+            if (!v) zero = true;
+        }
+    }, 4096);
+    if (failed) return bad;
+    if (!zero) return "kept: position 0 is not among the kept values";
+    if (!text) return "";
+    parallel_chunks(fm->samples, 4096, threads, [&](uint64_t b, uint64_t end) {
+        for (uint64_t k = b; k < end; k++) {
+            const uint64_t r = rdT(fm->text_kept.data(), (int)sh.w, k);
+            if (r >= s || !sufr::fm_marked(fm->marks[r >> 6], r)) return fail("text_kept: entry " + std::to_string(k) + " is not a marked rank");
+            if (rdT(fm->kept.data(), (int)sh.w, sufr::fm_slot(fm->marks[r >> 6], r)) != k * q)
+                return fail("text_kept: the kept value of entry " + std::to_string(k) + " is not its position");
+        }
+    }, 4096);
+    return failed ? bad : "";
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_file_fm_build_flags(const sufr_file* f, uint64_t sample, uint32_t flags, sufr_fm** out, int threads)
+{
+    return fm_build_host(f, sample, flags, out, threads);
+}
+
+int sufr_fm_get_text_info(const sufr_fm* fm, sufr_fm_text_info* info)
+{
+    if (!fm || !info) return SUFR_HIP_E_INVALID;
+    const uint64_t ts = fm->text_kept.size() / fm->sh.w;
+    *info = sufr_fm_text_info{ts, ts * fm->sh.w, fm_layout_of(fm, fm->seq_starts.size(), fm_name_bytes(fm->seq_names)).bytes};
+    return 0;
+}
+
+uint64_t sufr_fm_num_sequences(const sufr_fm* fm) { return fm ? fm->seq_starts.size() : 0; }
+uint64_t sufr_fm_sequence_start(const sufr_fm* fm, uint64_t i) { return fm && i < fm->seq_starts.size() ? fm->seq_starts[i] : 0; }
+const char* sufr_fm_sequence_name(const sufr_fm* fm, uint64_t i) { return fm && i < fm->seq_names.size() ? fm->seq_names[i].c_str() : ""; }
+
+int sufr_fm_set_sequences(sufr_fm* fm, const uint64_t* starts, const char* const* names, uint64_t num)
+{
+    if (!fm || (num && (!starts || !names)) || !fm_starts_fit(starts, num, fm->s)) return SUFR_HIP_E_INVALID;
+    for (uint64_t i = 0; i < num; i++) if (!names[i]) return SUFR_HIP_E_INVALID;
+    fm->seq_starts.assign(starts, starts + num);
+    fm->seq_names.assign(names, names + num);
+    return 0;
+}
+
+int sufr_fm_extract_batch(const sufr_fm* fm, const uint64_t* starts, const uint64_t* ends, uint64_t num, uint64_t* offsets, uint8_t* bytes,
+                          uint64_t cap, uint64_t* total_out, int threads)
+{
+    if (total_out) *total_out = 0;
+    if (!fm || !offsets || (num && (!starts || !ends))) return SUFR_HIP_E_INVALID;
+    if (fm->text_kept.empty()) return SUFR_HIP_E_UNSUPPORTED;
+    const uint64_t n = fm->s, q = fm->q;
+    std::vector<uint64_t> choff(num + 1);                // the chunks in front of every request
+    uint64_t total = 0, chunks = 0;
+    for (uint64_t i = 0; i < num; i++) {
+        uint64_t a = starts[i], b = ends[i];
+        sufr::fm_extract_clip(n, a, b);
+        offsets[i] = total;
+        choff[i] = chunks;
+        total += b - a;
+        chunks += sufr::fm_extract_chunks(q, a, b);
+    }
+    offsets[num] = total;
+    choff[num] = chunks;
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!bytes) return SUFR_HIP_E_INVALID;
+    const sufr::FmView V = fm->view();
+    const uint8_t* tk = fm->text_kept.data();
+    parallel_chunks(chunks, 64, threads, [&](uint64_t b, uint64_t e) {
+        uint64_t i = query_of(choff.data(), num, b);
+        for (uint64_t g = b; g < e; g++) {
+            while (choff[i + 1] <= g) i++;
+            uint64_t lo = starts[i], hi = ends[i];
+            sufr::fm_extract_clip(n, lo, hi);
+            const uint64_t k = lo / q + (g - choff[i]);
+            uint8_t* dst = bytes + offsets[i];
+            sufr::fm_extract_chunk(q, n, k, lo, hi, rdT(tk, (int)V.sh.w, sufr::fm_extract_slot(q, n, k)),
+                                   [&](uint64_t r, uint32_t& c) { return sufr::fm_lf(V, r, c); },
+                                   [&](uint64_t p, uint32_t c) { dst[p - lo] = (uint8_t)c; });
+        }
+    }, 16);
+    return 0;
+}
+
+int sufr_fm_save(const sufr_fm* fm, const char* path, const sufr_file* names_from, char* err, size_t errlen)
+{
+    if (!fm || !path) return SUFR_HIP_E_INVALID;
+    const std::vector<uint64_t>& starts = names_from ? names_from->seq_starts : fm->seq_starts;
+    const std::vector<std::string>& names = names_from ? names_from->seq_names : fm->seq_names;
+    if (starts.size() != names.size() || !fm_starts_fit(starts.data(), starts.size(), fm->s)) {
+        put_err(err, errlen, std::string(path) + ": the sequences to store are not those of the indexed text");
+        return SUFR_HIP_E_INVALID;
+    }
+    const sufr::FmFileLayout L = fm_layout_of(fm, starts.size(), fm_name_bytes(names));
+    std::vector<uint8_t> tables(sufr::FM_TABLE_BYTES), name_bytes;
+    memcpy(tables.data(), fm->C, 257 * 8);
+    memcpy(tables.data() + 257 * 8, fm->col, 256 * 4);
+    for (const std::string& s : names) name_bytes.insert(name_bytes.end(), s.c_str(), s.c_str() + strlen(s.c_str()) + 1);
+    FmFileHeader h{};
+    memcpy(h.magic, FM_FILE_MAGIC, 8);
+    h.version = 1; h.flags = fm->text_kept.empty() ? 0 : SUFR_FM_TEXT; h.w = fm->sh.w; h.e = fm->e; h.K = fm->sh.K; h.B = fm->sh.B;
+    h.stride = fm->sh.stride; h.cbytes = fm->sh.cbytes; h.s = fm->s; h.q = fm->q; h.samples = fm->samples; h.sequences = starts.size();
+    for (uint64_t i = 0; i < sufr::FM_FILE_SECTIONS; i++) { h.sec[2 * i] = L.off[i]; h.sec[2 * i + 1] = L.len[i]; }
+    const void* data[sufr::FM_FILE_SECTIONS] = {tables.data(), starts.data(), name_bytes.data(), fm->blocks.data(), fm->marks.data(), fm->kept.data(),
+                                                fm->text_kept.data()};
+    FILE* fp = fopen(path, "wb");
+    if (!fp) { put_err(err, errlen, std::string(path) + ": " + strerror(errno)); return SUFR_HIP_E_IO; }
+    const std::vector<uint8_t> zeros(sufr::FM_FILE_PAGE, 0);
+    uint64_t at = sizeof h;
+    bool ok = fwrite(&h, sizeof h, 1, fp) == 1;
+    for (uint64_t i = 0; i < sufr::FM_FILE_SECTIONS && ok; i++) {
+        ok = fwrite(zeros.data(), 1, L.off[i] - at, fp) == L.off[i] - at && (!L.len[i] || fwrite(data[i], 1, L.len[i], fp) == L.len[i]);
+        at = L.off[i] + L.len[i];
+    }
+    if (fclose(fp) != 0) ok = false;
+    if (!ok) { put_err(err, errlen, std::string(path) + ": writing the index file failed: " + strerror(errno)); return SUFR_HIP_E_IO; }
+    return 0;
+}
+
+int sufr_fm_load(const char* path, sufr_fm** out, int threads, char* err, size_t errlen)
+{
+    if (!path || !out) return SUFR_HIP_E_INVALID;
+    *out = nullptr;
+    FILE* fp = fopen(path, "rb");
+    struct stat sb;
+    if (!fp || fstat(fileno(fp), &sb) != 0) {
+        put_err(err, errlen, std::string(path) + ": " + strerror(errno));
+        if (fp) fclose(fp);
+        return SUFR_HIP_E_IO;
+    }
+    sufr_fm* fm = nullptr;
+    auto fail = [&](int rc, const std::string& why) {
+        put_err(err, errlen, std::string(path) + ": " + why);
+        fclose(fp);
+        delete fm;
+        return rc;
+    };
+    const uint64_t size = (uint64_t)sb.st_size;
+    FmFileHeader h;
+    if (size < sufr::FM_FILE_PAGE) return fail(SUFR_HIP_E_INVALID, "not an FM-index file (shorter than its header)");
+    if (fread(&h, sizeof h, 1, fp) != 1) return fail(SUFR_HIP_E_IO, "reading the header failed");
+    if (memcmp(h.magic, FM_FILE_MAGIC, 8) != 0) return fail(SUFR_HIP_E_INVALID, "header: not an FM-index file (wrong magic)");
+    if (h.version != 1) return fail(SUFR_HIP_E_INVALID, "header: version " + std::to_string(h.version) + ", this library reads version 1");
+    if (h.flags & ~SUFR_FM_TEXT) return fail(SUFR_HIP_E_INVALID, "header: unknown flags");
+    const bool text = h.flags & SUFR_FM_TEXT;
+    if (h.w != 4 && h.w != 8) return fail(SUFR_HIP_E_INVALID, "header: the index width is neither 4 nor 8");
+    if (h.K < 1 || h.K > 256 || h.e > 255) return fail(SUFR_HIP_E_INVALID, "header: the number of byte values or the end byte is out of range");
+    const sufr::FmShape sh = sufr::fm_shape(h.K, h.w);
+    if (h.B != sh.B || h.stride != sh.stride || h.cbytes != sh.cbytes) return fail(SUFR_HIP_E_INVALID, "header: the block shape is not that of K and w");
+    if (!h.s || h.s > size || (h.w == 4 && h.s > 0xFFFFFFFFull)) return fail(SUFR_HIP_E_INVALID, "header: the number of ranks does not fit the file or the width");
+    if (h.samples != (h.q ? (h.s - 1) / h.q + 1 : 0) || (text && !h.q)) return fail(SUFR_HIP_E_INVALID, "header: the number of samples is not ceil(s / q)");
+    const uint64_t name_len = h.sec[2 * sufr::FM_SEC_NAMES + 1];
+    if (h.sequences > size / 8 || name_len > size) return fail(SUFR_HIP_E_INVALID, "header: the sequences do not fit the file");
+    const sufr::FmFileLayout L = sufr::fm_file_layout(sh, h.s, h.q, h.samples, text, h.sequences, name_len);
+    for (uint64_t i = 0; i < sufr::FM_FILE_SECTIONS; i++)
+        if (h.sec[2 * i] != L.off[i] || h.sec[2 * i + 1] != L.len[i])
+            return fail(SUFR_HIP_E_INVALID, "header: section " + std::to_string(i) + " is not where or as long as its formula says");
+    if (L.bytes != size) return fail(SUFR_HIP_E_INVALID, "header: the file is " + std::to_string(size) + " bytes long, its sections end at " + std::to_string(L.bytes));
+    fm = new sufr_fm;
+    fm->sh = sh; fm->s = h.s; fm->q = h.q; fm->samples = h.samples; fm->e = h.e;
+    std::vector<uint8_t> tables(sufr::FM_TABLE_BYTES), name_bytes(name_len);
+    fm->seq_starts.resize(h.sequences);
+    fm->blocks.resize(L.len[sufr::FM_SEC_BLOCKS]);
+    fm->marks.resize(L.len[sufr::FM_SEC_MARKS] / sizeof(sufr::FmMark));
+    fm->kept.resize(L.len[sufr::FM_SEC_KEPT]);
+    fm->text_kept.resize(L.len[sufr::FM_SEC_TEXT]);
+    void* data[sufr::FM_FILE_SECTIONS] = {tables.data(), fm->seq_starts.data(), name_bytes.data(), fm->blocks.data(), fm->marks.data(), fm->kept.data(),
+                                          fm->text_kept.data()};
+    for (uint64_t i = 0; i < sufr::FM_FILE_SECTIONS; i++)
+        if (L.len[i] && (fseeko(fp, (off_t)L.off[i], SEEK_SET) != 0 || fread(data[i], 1, L.len[i], fp) != L.len[i]))
+            return fail(SUFR_HIP_E_IO, "reading section " + std::to_string(i) + " failed");
+    memcpy(fm->C, tables.data(), 257 * 8);
+    memcpy(fm->col, tables.data() + 257 * 8, 256 * 4);
+    if (!fm_starts_fit(fm->seq_starts.data(), h.sequences, h.s)) return fail(SUFR_HIP_E_INVALID, "sequences: the starts decrease or lie behind the text");
+    for (uint64_t at = 0; at < name_len;) {
+        const void* z = memchr(name_bytes.data() + at, 0, name_len - at);
+        if (!z) return fail(SUFR_HIP_E_INVALID, "sequences: the last name does not end");
+        fm->seq_names.emplace_back((const char*)name_bytes.data() + at);
+        at = (uint64_t)((const uint8_t*)z - name_bytes.data()) + 1;
+    }
+    if (fm->seq_names.size() != h.sequences) return fail(SUFR_HIP_E_INVALID, "sequences: the names are not one per start");
+    const std::string bad = fm_verify(fm, text, threads);
+    if (!bad.empty()) return fail(SUFR_HIP_E_INVALID, bad);
+    fclose(fp);
+    *out = fm;
     return 0;
 }
 

@@ -13,6 +13,7 @@ from __future__ import annotations
 import builtins
 import ctypes as C
 import datetime
+import os
 from dataclasses import dataclass, field
 from functools import partial
 from typing import Iterable, List, Optional, Sequence, Tuple
@@ -665,15 +666,20 @@ class SufrFile:
         return out[:s]
 
     # -- the FM-index over the BWT (include/sufr_fm.h) ---------------------------------------------------------------------
-    def fm(self, sample: int = 32, threads: int = 0) -> "FmIndex":
+    def fm(self, sample: int = 32, threads: int = 0, text: bool = False) -> "FmIndex":
         """An FM-index of this file on the host: it answers search_batch and locate without the text and the suffix array and
         owns what it reads, so the file may be closed.  sample: every suffix at a multiple of it is kept for locate (0: none,
-        no locate).  Refused (-6) unless every position is indexed, there is no seed mask and no max_query_len, and the last
-        byte of the text occurs once."""
+        no locate).  text: also keep the text samples, with which FmIndex.extract reads the text back (include/sufr_fm_text.h).
+        Refused (-6) unless every position is indexed, there is no seed mask and no max_query_len, and the last byte of the
+        text occurs once."""
         h = C.c_void_p()
-        rc = lib().sufr_file_fm_build(self._h, sample, C.byref(h), threads)
+        if text:
+            from ._lib import FM_TEXT
+            rc = lib().sufr_file_fm_build_flags(self._h, sample, FM_TEXT, C.byref(h), threads)
+        else:
+            rc = lib().sufr_file_fm_build(self._h, sample, C.byref(h), threads)
         if rc != 0:
-            raise SufrHipError(rc, "sufr_file_fm_build: " + {-6: _FM_REFUSED}.get(rc, "failed"))
+            raise SufrHipError(rc, "sufr_file_fm_build: " + {-6: _FM_REFUSED, -1: "text=True needs a sample rate"}.get(rc, "failed"))
         return FmIndex(h, self.index_width)
 
     def _sequence_of(self, suffix: int) -> int:
@@ -774,6 +780,31 @@ def _fm_info(call, handle) -> dict:
     return info.as_dict()
 
 
+def _fm_text_info(call, handle) -> dict:
+    from ._lib import FmTextInfo
+    info = FmTextInfo()
+    rc = call(handle, C.byref(info))
+    if rc != 0:
+        raise SufrHipError(rc, "reading the text info of the FM-index failed")
+    return info.as_dict()
+
+
+def _range_arrays(starts, ends) -> Tuple[np.ndarray, np.ndarray]:
+    starts = np.ascontiguousarray(np.atleast_1d(starts), dtype=np.uint64)
+    ends = np.ascontiguousarray(np.atleast_1d(ends), dtype=np.uint64)
+    if starts.shape != ends.shape or starts.ndim != 1:
+        raise ValueError("starts and ends must be one-dimensional and of one length")
+    return starts, ends
+
+
+def _clipped_total(starts: np.ndarray, ends: np.ndarray, n: int) -> int:
+    e = np.minimum(ends, np.uint64(n))
+    return int((e - np.minimum(starts, e)).sum())
+
+
+_NO_TEXT = "the index was built without text samples (text=False)"
+
+
 def _counts(queries: Sequence, lo, hi) -> List[CountResult]:
     return [CountResult(i, q if isinstance(q, str) else bytes(q).decode("latin-1"), int(hi[i] - lo[i])) for i, q in enumerate(queries)]
 
@@ -838,6 +869,72 @@ class FmIndex:
         """Text positions of every query's matches in rank order (unsigned arrays of the index's width)."""
         o, p = self.locate_ranges(*self.search_batch(queries, threads), max_hits, threads)
         return [p[int(o[i]):int(o[i + 1])] for i in range(len(queries))]
+
+    # -- extract, the index file, the copies (include/sufr_fm_text.h) ---------------------------------------------------------
+    @property
+    def text_info(self) -> dict:
+        """text_samples, text_bytes, file_bytes (sufr_fm_text_info)"""
+        return _fm_text_info(lib().sufr_fm_get_text_info, self._h)
+
+    def extract_ranges(self, starts, ends, threads: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(offsets uint64[num + 1], bytes uint8): request i owns bytes[offsets[i]:offsets[i + 1]], the text from starts[i] to
+        min(ends[i], text_len), read back from the BWT.  The index must have been built with text=True."""
+        starts, ends = _range_arrays(starts, ends)
+        cap = _clipped_total(starts, ends, self.info["ranks"])
+        off = np.zeros(starts.size + 1, dtype=np.uint64)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        total = C.c_uint64(0)
+        rc = lib().sufr_fm_extract_batch(self._h, starts.ctypes.data, ends.ctypes.data, starts.size, off.ctypes.data, out.ctypes.data, cap,
+                                         C.byref(total), threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_fm_extract_batch: " + {-6: _NO_TEXT}.get(rc, "failed"))
+        return off, out[:total.value]
+
+    def extract(self, start: int, end: int) -> bytes:
+        """The text from `start` to min(end, text_len)."""
+        return self.extract_ranges([start], [end])[1].tobytes()
+
+    def save(self, path, names_from: Optional["SufrFile"] = None) -> None:
+        """Write the index to a file FmIndex.load reads without a .sufr (the layout: include/sufr_fm_text.h).  names_from: the
+        open SufrFile whose sequence starts and names are stored; None stores those the index remembers (sequences())."""
+        err = C.create_string_buffer(512)
+        rc = lib().sufr_fm_save(self._h, os.fsencode(str(path)), names_from._h if names_from is not None else None, err, 512)
+        if rc != 0:
+            raise SufrHipError(rc, err.value.decode(errors="replace") or "sufr_fm_save failed")
+
+    @classmethod
+    def load(cls, path, threads: int = 0) -> "FmIndex":
+        """The index FmIndex.save wrote, read into memory and verified: a damaged file is refused (-1, or -7 where it cannot be
+        read) with the check that failed."""
+        from ._lib import FmInfo
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().sufr_fm_load(os.fsencode(str(path)), C.byref(h), threads, err, 512)
+        if rc != 0:
+            raise SufrHipError(rc, err.value.decode(errors="replace") or "sufr_fm_load failed")
+        info = FmInfo()
+        lib().sufr_fm_get_info(h, C.byref(info))
+        return cls(h, int(info.width))
+
+    def sequences(self) -> Tuple[List[int], List[str]]:
+        """(starts, names) of the sequences the index remembers: those of the file it was built from or loaded with."""
+        L = lib()
+        num = int(L.sufr_fm_num_sequences(self._h))
+        return ([int(L.sufr_fm_sequence_start(self._h, i)) for i in range(num)],
+                [L.sufr_fm_sequence_name(self._h, i).decode("latin-1") for i in range(num)])
+
+    def set_sequences(self, starts: Sequence[int], names: Sequence[str]) -> None:
+        """Replace the sequences the index remembers (none: save() then stores no names)."""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode("latin-1") for n in names])
+        rc = lib().sufr_fm_set_sequences(self._h, st.ctypes.data, arr, len(names))
+        if rc != 0 or st.size != len(names):
+            raise SufrHipError(rc or -1, "sufr_fm_set_sequences: the starts must not decrease and must lie in the text, one name each")
+
+    def to_device(self, ctx: Context) -> "DeviceFmIndex":
+        """A copy of this index in the HBM of the context's device: allocations and copies only."""
+        h = C.c_void_p()
+        ctx.check(lib().sufr_hip_fm_upload(ctx.handle, self._h, C.byref(h)))
+        return DeviceFmIndex(ctx, h, self.index_width)
 
     # -- k-mismatch search by backtracking (include/sufr_fm_approx.h) -------------------------------------------------------
     def approx_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, max_mismatches: int = 2, both_strands: bool = False,
@@ -942,6 +1039,56 @@ class DeviceFmIndex:
 
     def count(self, queries: Sequence) -> List[CountResult]:
         return _counts(queries, *self.search(queries))
+
+    # -- extract and the copies (include/sufr_fm_text.h) ------------------------------------------------------------------------
+    @property
+    def text_info(self) -> dict:
+        """text_samples, text_bytes, file_bytes (sufr_fm_text_info; the file without names)"""
+        return _fm_text_info(lib().sufr_hip_fm_get_text_info, self._h)
+
+    def extract_device(self, starts, ends, cap: Optional[int] = None):
+        """(offsets int64[num + 1], bytes uint8) on the device for int64 CUDA tensors of starts and ends: request i owns
+        bytes[offsets[i]:offsets[i + 1]], the text from starts[i] to min(ends[i], text_len).  Complete on return.  With a `cap`
+        too small the SufrHipError (code -5) carries the total in `.total`; without one the bytes are sized to fit."""
+        import torch
+        torch.cuda.current_stream(starts.device).synchronize()
+        num = starts.numel()
+        if cap is None:
+            n = self.info["ranks"]
+            e = ends.clamp(min=0, max=n) if num else ends
+            cap = int((e - torch.minimum(starts.clamp(min=0), e)).sum()) if num else 0
+        off = torch.empty(num + 1, dtype=torch.int64, device=starts.device)
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=starts.device)
+        total = C.c_uint64(0)
+        rc = lib().sufr_hip_fm_extract_batch_device(self.ctx.handle, self._h, starts.data_ptr(), ends.data_ptr(), num, off.data_ptr(), out.data_ptr(),
+                                                    cap, C.byref(total))
+        if rc != 0:
+            err = SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode())
+            err.total = int(total.value)
+            raise err
+        self.ctx.synchronize()
+        return off, out[:total.value]
+
+    def extract_ranges(self, starts, ends) -> Tuple[np.ndarray, np.ndarray]:
+        """FmIndex.extract_ranges, read on the device: (offsets uint64[num + 1], bytes uint8) as numpy arrays."""
+        import torch
+        starts, ends = _range_arrays(starts, ends)
+        dev = torch.device("cuda", self.ctx.device)
+        # (positions beyond 2^63 mean "behind the text" and are held to int64's range)
+        top = np.uint64(2**63 - 1)
+        off, out = self.extract_device(torch.from_numpy(np.minimum(starts, top).astype(np.int64)).to(dev),
+                                       torch.from_numpy(np.minimum(ends, top).astype(np.int64)).to(dev))
+        return off.cpu().numpy().view(np.uint64), out.cpu().numpy()
+
+    def extract(self, start: int, end: int) -> bytes:
+        """The text from `start` to min(end, text_len)."""
+        return self.extract_ranges([start], [end])[1].tobytes()
+
+    def to_host(self) -> FmIndex:
+        """A copy of this index in host memory (it remembers no sequences)."""
+        h = C.c_void_p()
+        self.ctx.check(lib().sufr_hip_fm_download(self.ctx.handle, self._h, C.byref(h)))
+        return FmIndex(h, self.index_width)
 
     # -- k-mismatch search by backtracking (include/sufr_fm_approx.h) -------------------------------------------------------
     def approx_device(self, qbytes, offsets, max_mismatches: int = 2, both_strands: bool = False, cap: Optional[int] = None):
@@ -1310,13 +1457,18 @@ class DeviceIndex:
         return out[:s]
 
     # -- the FM-index over the BWT (include/sufr_fm.h) -------------------------------------------------------------------
-    def fm_device(self, sample: int = 32) -> "DeviceFmIndex":
+    def fm_device(self, sample: int = 32, text: bool = False) -> "DeviceFmIndex":
         """SufrFile.fm on the device: the FM-index of this index in HBM, complete on return.  It owns everything it reads; this
-        index may be closed afterwards.  Refused (-6) as SufrFile.fm refuses."""
+        index may be closed afterwards.  text: also keep the text samples, for DeviceFmIndex.extract_device.  Refused (-6) as
+        SufrFile.fm refuses."""
         import torch
         torch.cuda.current_stream(self._device()).synchronize()     # (wrapped tensors: their producer is done)
         h = C.c_void_p()
-        self.ctx.check(lib().sufr_hip_fm_build(self.ctx.handle, self._h, sample, C.byref(h)))
+        if text:
+            from ._lib import FM_TEXT
+            self.ctx.check(lib().sufr_hip_fm_build_flags(self.ctx.handle, self._h, sample, FM_TEXT, C.byref(h)))
+        else:
+            self.ctx.check(lib().sufr_hip_fm_build(self.ctx.handle, self._h, sample, C.byref(h)))
         return DeviceFmIndex(self.ctx, h, self.index_width)
 
     # -- MEMs (include/sufr_mem.h) -----------------------------------------------------------------------------------
