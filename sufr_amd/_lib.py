@@ -190,6 +190,9 @@ FM_TEXT_EXPORTS = ["sufr_file_fm_build_flags", "sufr_fm_get_text_info", "sufr_fm
                    "sufr_hip_fm_build_flags", "sufr_hip_fm_get_text_info", "sufr_hip_fm_extract_batch_device", "sufr_hip_fm_extract_batch",
                    "sufr_hip_fm_upload", "sufr_hip_fm_download"]
 FM_TEXT = 0x1
+# every symbol include/sufr_fm_match.h declares
+FM_MATCH_EXPORTS = ["sufr_fm_pair_check", "sufr_fm_matching_stats", "sufr_fm_smems", "sufr_fm_matching_stats_steps",
+                    "sufr_file_write_reversed_fasta", "sufr_hip_fm_matching_stats_device", "sufr_hip_fm_smems_device", "sufr_hip_fm_smems"]
 
 
 class FmTextInfo(C.Structure):
@@ -436,6 +439,16 @@ def lib() -> C.CDLL:
     L.sufr_hip_fm_extract_batch.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]; L.sufr_hip_fm_extract_batch.restype = C.c_int
     L.sufr_hip_fm_upload.argtypes = [vp, vp, C.POINTER(vp)]; L.sufr_hip_fm_upload.restype = C.c_int
     L.sufr_hip_fm_download.argtypes = [vp, vp, C.POINTER(vp)]; L.sufr_hip_fm_download.restype = C.c_int
+    # include/sufr_fm_match.h
+    L.sufr_fm_pair_check.argtypes = [vp, vp]; L.sufr_fm_pair_check.restype = C.c_int
+    L.sufr_fm_matching_stats.argtypes = [vp, vp, vp, vp, u64, vp, C.c_int]; L.sufr_fm_matching_stats.restype = C.c_int
+    L.sufr_fm_smems.argtypes = [vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64), C.c_int]; L.sufr_fm_smems.restype = C.c_int
+    L.sufr_fm_matching_stats_steps.argtypes = [vp, vp, vp, vp, u64, vp, C.c_int]; L.sufr_fm_matching_stats_steps.restype = C.c_int
+    L.sufr_file_write_reversed_fasta.argtypes = [vp, cp, cp, C.c_size_t]; L.sufr_file_write_reversed_fasta.restype = C.c_int
+    L.sufr_hip_fm_matching_stats_device.argtypes = [vp, vp, vp, vp, vp, u64, vp]; L.sufr_hip_fm_matching_stats_device.restype = C.c_int
+    L.sufr_hip_fm_smems_device.argtypes = [vp, vp, vp, vp, vp, u64, u32, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.sufr_hip_fm_smems_device.restype = C.c_int
+    L.sufr_hip_fm_smems.argtypes = [vp, vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]; L.sufr_hip_fm_smems.restype = C.c_int
     _lib = L
     return L
 

@@ -5,6 +5,7 @@
 // "Error: <msg>" and exit code 1).  The query sub-commands (count / locate / extract / list / summarize,
 // sufr/src/lib.rs:129-271 for their arguments, 292-646 for their output) read the file through
 // include/sufr_query.h; their output is the reference's, character for character.
+#include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,6 +31,7 @@
 #include "../../include/sufr_bwt.h"
 #include "../../include/sufr_fm_approx.h"
 #include "../../include/sufr_fm_text.h"
+#include "../../include/sufr_fm_match.h"
 #include "../../include/sufr_shared.h"
 
 #include <hip/hip_runtime_api.h>
@@ -131,6 +133,12 @@ int usage(FILE* f)
             "                                       on the GPU with --device; no .sufr is opened]\n"
             "                                       [--extract [--prefix-len N] [--suffix-len N]: the lines of extract for the hits of every\n"
             "                                       query, the bases read back from the BWT; implies --text]\n"
+            "                                       [--write-reverse OUT.fa: write the FASTA of the reversed text (every sequence reversed, their\n"
+            "                                       order reversed); `sufr create` it with the flags of <SUFR> for the .sufr of --reverse]\n"
+            "                                       [--smems --reverse REV [-k MIN_LEN (20)] [--max-hits N] [-a]: the lines of match (name,\n"
+            "                                       offset, length, count, positions) from two FM-indexes alone, that of <SUFR> or --index and\n"
+            "                                       that of the reversed text; REV is the .sufr of the reversed FASTA (its index is built\n"
+            "                                       without samples) or an index file saved from it.  Needs samples: -s 0 is an error]\n"
             "  count / locate / extract / match / mems / approx / edit take --device <ID>: the queries are searched as one batch on that GPU\n\n"
             "Global options:\n"
             "  -t, --threads <THREADS>   Host workers of count / locate / extract [default: one per core]; create runs on the GPU\n"
@@ -195,6 +203,8 @@ struct QueryArgs {
     bool fm_approx = false;                     // fm: -d / --mismatches given (the distance is `mismatches`)
     std::string fm_save, fm_index;              // fm: --save OUT.fm, --index IN.fm
     bool fm_text = false, fm_extract = false;   // fm: --text, --extract
+    bool fm_smems = false;                      // fm: --smems
+    std::string fm_reverse, fm_write_reverse;   // fm: --reverse REV, --write-reverse OUT.fa
 };
 
 // parse_locate_queries (lib.rs:449-466): an argument that names an existing file is read as whitespace-separated queries
@@ -714,6 +724,35 @@ std::string place(const sufr_file* f, bool abs, uint64_t p)
     return seq_pos(f, i, p - sufr_file_sequence_start(f, i));
 }
 
+// The lines of `sufr match` for `total` SMEM records: name, offset, length, count, positions.  positions(t) are the text
+// positions of record t in rank order, at most max_hits of them: printed as they come with --abs, else as seq:pos ordered by
+// sequence name, then position.  `sufr fm --smems` prints through here too, with the sequences of the index
+template <typename Seqs, typename Positions>
+void print_smems(const Seqs& seqs, FILE* out, bool abs, const std::vector<std::string>& names, uint64_t total, const std::vector<uint64_t>& qi,
+                 const std::vector<uint32_t>& qo, const std::vector<uint32_t>& len, const std::vector<uint64_t>& lo, const std::vector<uint64_t>& hi,
+                 Positions positions)
+{
+    for (uint64_t t = 0; t < total; t++) {
+        const std::vector<uint64_t> where = positions(t);
+        std::string pos;
+        if (abs) for (size_t k = 0; k < where.size(); k++) pos += (k ? "," : "") + std::to_string(where[k]);
+        else {
+            struct Pos { uint64_t seq, at; };
+            std::vector<Pos> ps;
+            for (const uint64_t sfx : where) {
+                const uint64_t i = seq_of(seqs, sfx);
+                ps.push_back({i, sfx - seq_start(seqs, i)});
+            }
+            std::stable_sort(ps.begin(), ps.end(), [&](const Pos& x, const Pos& y) {
+                const int c = x.seq == y.seq ? 0 : strcmp(seq_name(seqs, x.seq), seq_name(seqs, y.seq));
+                return c ? c < 0 : x.at < y.at;
+            });
+            for (size_t k = 0; k < ps.size(); k++) pos += (k ? "," : "") + std::string(seq_name(seqs, ps[k].seq)) + ":" + std::to_string(ps[k].at);
+        }
+        fprintf(out, "%s\t%u\t%u\t%llu\t%s\n", names[qi[t]].c_str(), qo[t], len[t], (unsigned long long)(hi[t] - lo[t]), pos.c_str());
+    }
+}
+
 // arguments of the query sub-commands (clap definitions of lib.rs:129-271)
 // sufr match: the SMEMs of every query, one line each: name, offset, length, count, positions.
 // Positions: SA[rank_lo .. rank_lo + max_hits) (all with 0), printed as seq:pos ordered by sequence name then position
@@ -736,25 +775,13 @@ int cmd_match(const QueryArgs& a)
                                           hi.data(), tot, a.threads);
         })) return 1;
     s.release_device();
-    for (uint64_t t = 0; t < total; t++) {
+    const sufr_file* f = s.f;
+    print_smems(f, s.out.f, a.abs, s.names, total, qi, qo, len, lo, hi, [&](uint64_t t) {
         const uint64_t end = a.max_hits && hi[t] - lo[t] > a.max_hits ? lo[t] + a.max_hits : hi[t];
-        std::string pos;
-        if (a.abs) for (uint64_t r = lo[t]; r < end; r++) pos += (r > lo[t] ? "," : "") + place(s.f, true, sufr_file_suffix(s.f, r));
-        else {
-            struct Pos { uint64_t seq, at; };
-            std::vector<Pos> ps;
-            for (uint64_t r = lo[t]; r < end; r++) {
-                const uint64_t sfx = sufr_file_suffix(s.f, r), i = sufr_file_sequence_of(s.f, sfx);
-                ps.push_back({i, sfx - sufr_file_sequence_start(s.f, i)});
-            }
-            std::stable_sort(ps.begin(), ps.end(), [&](const Pos& x, const Pos& y) {
-                const int c = x.seq == y.seq ? 0 : strcmp(sufr_file_sequence_name(s.f, x.seq), sufr_file_sequence_name(s.f, y.seq));
-                return c ? c < 0 : x.at < y.at;
-            });
-            for (size_t k = 0; k < ps.size(); k++) pos += (k ? "," : "") + seq_pos(s.f, ps[k].seq, ps[k].at);
-        }
-        fprintf(s.out.f, "%s\t%u\t%u\t%llu\t%s\n", s.names[qi[t]].c_str(), qo[t], len[t], (unsigned long long)(hi[t] - lo[t]), pos.c_str());
-    }
+        std::vector<uint64_t> where;
+        for (uint64_t r = lo[t]; r < end; r++) where.push_back(sufr_file_suffix(f, r));
+        return where;
+    });
     return 0;
 }
 
@@ -1042,6 +1069,135 @@ int cmd_fm_index(const QueryArgs& a)
     return 0;
 }
 
+// sufr fm <SUFR> --write-reverse OUT.fa (include/sufr_fm_match.h): the FASTA of the reversed text
+int cmd_fm_write_reverse(const QueryArgs& a)
+{
+    if (!a.fm_index.empty()) { fprintf(stderr, "Error: --write-reverse needs the text: a .sufr file, not --index\n"); return 1; }
+    char err[512] = {0};
+    OpenFile f(a.file);
+    if (sufr_file_write_reversed_fasta(f, a.fm_write_reverse.c_str(), err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
+    return 0;
+}
+
+// sufr fm --smems --reverse REV: the lines of `sufr match` from two FM-indexes alone, the one of the
+// text (built from <SUFR> at -s, or loaded with --index) and the one of the reversed text (REV: an index file, told by its
+// magic, or the .sufr of the reversed FASTA, whose index is built at sample 0), on the GPU with --device.
+int cmd_fm_smems(const QueryArgs& a)
+{
+    char err[512] = {0};
+    if (!a.fm_smems) { fprintf(stderr, "Error: --reverse goes with --smems\n"); return 1; }
+    if (a.fm_reverse.empty()) { fprintf(stderr, "Error: --smems needs --reverse REV: the .sufr or the FM-index of the reversed text (sufr fm --write-reverse)\n"); return 1; }
+    if (a.fm_index.empty() && !a.sample) { fprintf(stderr, "Error: --smems prints positions, which need the sampled suffixes: -s must be at least 1\n"); return 1; }
+    if (a.min_len == 0 || a.min_len > 0xFFFFFFFFull) { fprintf(stderr, "Error: --min-len must be between 1 and 2^32 - 1\n"); return 1; }
+    OutFile out;
+    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
+    struct Held {
+        sufr_fm *fwd = nullptr, *rev = nullptr;
+        sufr_hip_ctx* ctx = nullptr;
+        sufr_hip_fm *dfwd = nullptr, *drev = nullptr;
+        ~Held()
+        {
+            if (dfwd) sufr_hip_fm_free(dfwd);
+            if (drev) sufr_hip_fm_free(drev);
+            if (ctx) sufr_hip_destroy(ctx);
+            if (fwd) sufr_fm_free(fwd);
+            if (rev) sufr_fm_free(rev);
+        }
+    } h;
+    if (a.device >= 0 && !(h.ctx = sufr_hip_create(a.device))) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
+    SeqTable seqs;
+    // one index of the pair: loaded from an index file, or built from a .sufr at `sample`, on the device with --device
+    auto take = [&](const std::string& path, bool index_file, uint64_t sample, bool names, sufr_fm** fm, sufr_hip_fm** dfm) {
+        if (index_file) {
+            if (sufr_fm_load(path.c_str(), fm, a.threads, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return false; }
+            if (h.ctx && sufr_hip_fm_upload(h.ctx, *fm, dfm) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return false; }
+            for (uint64_t i = 0; names && i < sufr_fm_num_sequences(*fm); i++) {
+                seqs.starts.push_back(sufr_fm_sequence_start(*fm, i));
+                seqs.names.push_back(sufr_fm_sequence_name(*fm, i));
+            }
+            return true;
+        }
+        OpenFile f(path);
+        int rc;
+        if (h.ctx) {
+            sufr_hip_index* ix = nullptr;
+            if ((rc = sufr_hip_index_load(h.ctx, f, &ix)) == 0) {
+                rc = sufr_hip_fm_build(h.ctx, ix, sample, dfm);
+                sufr_hip_index_free(ix);            // text and suffix array leave the device: the pair answers alone
+            }
+            if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", path.c_str(), sufr_hip_last_error(h.ctx)); return false; }
+        } else if ((rc = sufr_file_fm_build(f, sample, fm, a.threads)) != 0) {
+            fprintf(stderr, "Error: %s: no FM-index: %s\n", path.c_str(),
+                    rc == SUFR_HIP_E_UNSUPPORTED ? "every position must be indexed, without seed mask and max_query_len, and the last byte must occur once" : "the build failed");
+            return false;
+        }
+        sufr_file_meta m;
+        sufr_file_metadata(f, &m);
+        for (uint64_t i = 0; names && i < m.num_sequences; i++) {
+            seqs.starts.push_back(sufr_file_sequence_start(f, i));
+            seqs.names.push_back(sufr_file_sequence_name(f, i));
+        }
+        return true;
+    };
+    // an index file is told from a .sufr by its magic
+    char magic[8] = {0};
+    if (FILE* fp = fopen(a.fm_reverse.c_str(), "rb")) { if (fread(magic, 1, 8, fp) != 8) magic[0] = 0; fclose(fp); }
+    else { fprintf(stderr, "Error: %s: %s\n", a.fm_reverse.c_str(), strerror(errno)); return 1; }
+    if (!take(a.file, !a.fm_index.empty(), a.sample, true, &h.fwd, &h.dfwd) ||
+        !take(a.fm_reverse, !memcmp(magic, "SUFRFMI\0", 8), 0, false, &h.rev, &h.drev)) return 1;
+    sufr_fm_info info;
+    if (h.dfwd ? sufr_hip_fm_get_info(h.dfwd, &info) : sufr_fm_get_info(h.fwd, &info)) { fprintf(stderr, "Error: reading the info of the FM-index failed\n"); return 1; }
+    if (!info.sample) { fprintf(stderr, "Error: %s: the index was saved without samples (-s 0): it gives no positions\n", a.file.c_str()); return 1; }
+    if (!h.ctx && sufr_fm_pair_check(h.fwd, h.rev) != 0) { fprintf(stderr, "Error: %s: not an index of the reversed text\n", a.fm_reverse.c_str()); return 1; }
+    std::vector<std::string> names, queries;
+    if (!named_queries(a, names, queries)) return 1;
+    const uint64_t nq = queries.size();
+    std::string bytes;
+    std::vector<uint64_t> off(nq + 1, 0);
+    for (size_t i = 0; i < nq; i++) { bytes += queries[i]; off[i + 1] = bytes.size(); }
+    // records: room for one SMEM per 8 query bytes first, the exact count when that is short
+    uint64_t total = 0, cap = bytes.size() / 8 + 16;
+    std::vector<uint64_t> qi, lo, hi;
+    std::vector<uint32_t> qo, len;
+    for (;;) {
+        qi.resize(cap); lo.resize(cap); hi.resize(cap); qo.resize(cap); len.resize(cap);
+        const int rc = h.ctx ? sufr_hip_fm_smems(h.ctx, h.dfwd, h.drev, (const uint8_t*)bytes.data(), off.data(), nq, (uint32_t)a.min_len, cap, qi.data(), qo.data(),
+                                                 len.data(), lo.data(), hi.data(), &total)
+                             : sufr_fm_smems(h.fwd, h.rev, (const uint8_t*)bytes.data(), off.data(), nq, (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(),
+                                             lo.data(), hi.data(), &total, a.threads);
+        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
+        if (rc) { fprintf(stderr, "Error: %s\n", h.ctx ? sufr_hip_last_error(h.ctx) : "the FM-index search failed"); return 1; }
+        break;
+    }
+    // the positions of every SMEM: locate on the index of the text
+    const int w = (int)info.width;
+    uint64_t npos = 0;
+    for (uint64_t t = 0; t < total; t++) npos += a.max_hits && hi[t] - lo[t] > a.max_hits ? a.max_hits : hi[t] - lo[t];
+    std::vector<uint64_t> loff(total + 1, 0);
+    std::vector<uint8_t> pos((npos + 1) * w);
+    if (h.ctx && total) {
+        uint8_t* d = nullptr;
+        const uint64_t hi_at = total * 8, l_at = 2 * total * 8, p_at = l_at + (total + 1) * 8;
+        bool ok = hipMalloc((void**)&d, p_at + (npos + 1) * w) == hipSuccess && hipMemcpy(d, lo.data(), total * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d + hi_at, hi.data(), total * 8, hipMemcpyHostToDevice) == hipSuccess;
+        int rc = ok ? sufr_hip_fm_locate_batch_device(h.ctx, h.dfwd, d, d + hi_at, total, a.max_hits, d + l_at, d + p_at, npos, &npos) : SUFR_HIP_E_HIP;
+        if (!rc) rc = sufr_hip_synchronize(h.ctx);
+        ok = ok && !rc && hipMemcpy(loff.data(), d + l_at, (total + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+             (!npos || hipMemcpy(pos.data(), d + p_at, npos * w, hipMemcpyDeviceToHost) == hipSuccess);
+        if (d) (void)hipFree(d);
+        if (!ok) { fprintf(stderr, "Error: %s\n", rc ? sufr_hip_last_error(h.ctx) : "device memory for the positions"); return 1; }
+    } else if (total) {
+        const int rc = sufr_fm_locate_batch(h.fwd, lo.data(), hi.data(), total, a.max_hits, loff.data(), pos.data(), npos, &npos, a.threads);
+        if (rc) { fprintf(stderr, "Error: the FM-index locate failed (%d)\n", rc); return 1; }
+    }
+    print_smems(seqs, out.f, a.abs, names, total, qi, qo, len, lo, hi, [&](uint64_t t) {
+        std::vector<uint64_t> where(loff[t + 1] - loff[t], 0);
+        for (size_t k = 0; k < where.size(); k++) memcpy(&where[k], pos.data() + (loff[t] + k) * w, w);      // (little-endian entries of 4 or 8 bytes)
+        return where;
+    });
+    return 0;
+}
+
 // sufr edit: every text position where a query ends with at most -d edits, one line each in record
 // order (query, strand, end): name, strand (+ / -), the end as seq:offset (0-based) or absolute with --abs, edits.
 // -c: the records are traced back (on the device with --device); two more columns, the start in the
@@ -1115,6 +1271,10 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         else if (is_fm && s == "--index") a.fm_index = need(i, "--index");
         else if (is_fm && s == "--text") a.fm_text = true;
         else if (is_fm && s == "--extract") a.fm_extract = true;
+        else if (is_fm && s == "--smems") a.fm_smems = true;
+        else if (is_fm && s == "--reverse") a.fm_reverse = need(i, "--reverse");
+        else if (is_fm && s == "--write-reverse") a.fm_write_reverse = need(i, "--write-reverse");
+        else if (is_fm && (s == "-k" || s == "--min-len")) a.min_len = strtoull(need(i, "-k"), nullptr, 10);
         else if (is_fm && s == "--prefix-len") { a.has_prefix = true; a.prefix_len = strtoull(need(i, "--prefix-len"), nullptr, 10); }
         else if (is_fm && s == "--suffix-len") { a.has_suffix = true; a.suffix_len = strtoull(need(i, "--suffix-len"), nullptr, 10); }
         else if (is_fm && s == "--max-hits") a.max_hits = strtoull(need(i, "--max-hits"), nullptr, 10);
@@ -1154,12 +1314,17 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
     if (pos.empty()) { fprintf(stderr, "error: the following required arguments were not provided:\n  <%s>\n", is_list ? "FILE" : "SUFR"); return 2; }
     a.file = pos[0];
     a.positional.assign(pos.begin() + 1, pos.end());
-    if (!is_list && !is_sum && a.positional.empty() && !((is_match || is_fm) && !a.reads.empty()) && a.fm_save.empty()) {
+    if (!is_list && !is_sum && a.positional.empty() && !((is_match || is_fm) && !a.reads.empty()) && a.fm_save.empty() && a.fm_write_reverse.empty()) {
         fprintf(stderr, "error: the following required arguments were not provided:\n  <QUERY>...\n");
         return 2;
     }
     if (cmd == "count") return cmd_count(a);
     if (is_locate) return cmd_locate(a);
+    if (is_fm && !a.fm_write_reverse.empty()) {
+        const int rc = cmd_fm_write_reverse(a);
+        if (rc || !(a.fm_smems || !a.fm_reverse.empty())) return rc;
+    }
+    if (is_fm && (a.fm_smems || !a.fm_reverse.empty())) return cmd_fm_smems(a);
     if (is_fm && (!a.fm_index.empty() || !a.fm_save.empty() || a.fm_text || a.fm_extract)) return cmd_fm_index(a);
     if (is_fm) return a.fm_approx ? cmd_fm_approx(a) : cmd_fm(a);
     if (is_edit) return cmd_edit(a);

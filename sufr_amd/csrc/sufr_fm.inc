@@ -34,10 +34,14 @@
 //                  k_locate_scan over both sums (the one synchronisation, for the two totals), k_fm_extract_apply; then a lane
 //                  per chunk runs fm_extract_chunk of sufr_fm_scan.h: at most q LF steps from a text sample, each one fm_occ_one
 //                  in the block that also holds the step's BWT byte, the bytes gathered in a register and stored as dwords.
+// k_fm_ms          matching statistics on a pair of indexes, that of the text and that of its reversal (include/sufr_fm_match.h,
+//                  DESIGN.md section 26): a lane per slab of G bytes of the batch runs fm_ms_walk of sufr_fm_scan.h for the part of
+//                  every query in it; the SMEMs then come from the kernels of sufr_match.inc and k_fm_search on the slices.
 // The copies (sufr_hip_fm_upload / _download) are allocations and copies.
-// No scratch.  LDS: k_fm_blocks 34 KB, k_fm_samples 4 KB, k_fm_search, k_fm_locate and k_fm_extract 3 KB, k_fm_approx 25 KB.
+// No scratch.  LDS: k_fm_blocks 34 KB, k_fm_samples 4 KB, k_fm_search, k_fm_locate, k_fm_extract and k_fm_ms 3 KB, k_fm_approx 25 KB.
 
 #include "../../include/sufr_fm_text.h"
+#include "../../include/sufr_fm_match.h"
 #include "sufr_fm_host.h"
 
 struct sufr_hip_fm {
@@ -46,6 +50,7 @@ struct sufr_hip_fm {
     uint64_t samples = 0;
     void *blocks = nullptr, *marks = nullptr, *kept = nullptr, *tabs = nullptr;      // the allocations: tabs = C (257 u64), col (256 u32)
     void* text_kept = nullptr;         // SUFR_FM_TEXT: the rank of every kept position, `samples` entries of w bytes (sufr_fm_text.h)
+    uint8_t h_tabs[257 * 8 + 256 * 4] = {0};       // what tabs holds, on the host: the pair check of sufr_fm_match.h reads no device memory
 };
 
 namespace sufr {
@@ -333,6 +338,42 @@ __global__ __launch_bounds__(256) void k_fm_approx_expand(const uint64_t* __rest
     out_mism[j] = (uint8_t)tag;
 }
 
+// ---- matching statistics on a pair of indexes (include/sufr_fm_match.h, DESIGN.md section 26) --------------------------------
+// C and the columns in LDS: the tables of fm_ms_walk.  The pair agrees in them (fm_pair_check), so one copy serves both views
+struct FmLaneTab {
+    const uint64_t* s_C;
+    const uint32_t* s_col;
+    __device__ __forceinline__ uint32_t col(uint32_t c) const { return s_col[c]; }
+    __device__ __forceinline__ uint64_t C(uint32_t c) const { return s_C[c]; }
+};
+
+// A lane per slab of G consecutive bytes of the concatenated batch (grid-stride: the grid does not depend on the batch).  The
+// part of every query that the slab touches is one fm_ms_walk of sufr_fm_scan.h over the offsets the slab owns; the walk
+// reads the query beyond the slab, up to its end, and writes ms only inside the slab.  No atomics, no per-lane array.
+template <bool LINE, uint32_t G>
+__global__ __launch_bounds__(256) void k_fm_ms(FmView F, FmView R, const uint8_t* __restrict__ queries, const uint64_t* __restrict__ qoff, uint64_t nq,
+                                               uint32_t* __restrict__ ms)
+{
+    __shared__ uint64_t s_C[257];
+    __shared__ uint32_t s_col[256];
+    fm_stage_tables(F, s_C, s_col);
+    const FmLaneTab tab{s_C, s_col};
+    const uint64_t g0 = qoff[0], g_end = qoff[nq], nslabs = (g_end - g0 + G - 1) / G, stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t slab = (uint64_t)blockIdx.x * 256 + threadIdx.x; slab < nslabs; slab += stride) {
+        const uint64_t lo = g0 + slab * G, hi = lo + G < g_end ? lo + G : g_end;
+        uint64_t a = last_le(qoff, 0, nq, lo);
+        for (uint64_t g = lo; g < hi;) {
+            while (qoff[a + 1] <= g) a++;                  // (g < g_end == qoff[nq]: a stays below nq)
+            const uint64_t qb = qoff[a], qe = qoff[a + 1], pe = qe < hi ? qe : hi;
+            uint32_t* out = ms + qb;
+            fm_ms_walk(F, R, tab, queries + qb, qe - qb, g - qb, pe - qb,
+                       [&](const FmView& V, uint32_t c, uint32_t k, uint64_t& x, uint64_t& y) { fm_occ_pair<LINE>(V, c, k, s_C[c], x, y); },
+                       [&](uint64_t j, uint32_t v) { out[j] = v; });
+            g = pe;
+        }
+    }
+}
+
 // The blocks of tile t and, with a sampling rate q, its mark words and t_cnt[t], the number of its marks.  tab: the ranks of
 // every column before the tile (k_bwt_col_scan)
 template <typename T>
@@ -596,7 +637,8 @@ int fm_build_run(sufr_hip_ctx* ctx, const sufr_hip_index* ix, uint64_t sample, u
         }
     }
     if ((rc = launch_status(pl, "fm_build"))) return rc;
-    if (hipStreamSynchronize(pl.stream) != hipSuccess) { pl.set_error("fm_build: the build failed"); return SUFR_HIP_E_HIP; }      // nothing reads ix from here on
+    const bool tabs_back = hipMemcpyAsync(fm->h_tabs, fm->tabs, sizeof fm->h_tabs, hipMemcpyDeviceToHost, pl.stream) == hipSuccess;
+    if (hipStreamSynchronize(pl.stream) != hipSuccess || !tabs_back) { pl.set_error("fm_build: the build failed"); return SUFR_HIP_E_HIP; }      // nothing reads ix from here on
     return 0;
 }
 
@@ -886,6 +928,7 @@ int sufr_hip_fm_upload(sufr_hip_ctx* ctx, const sufr_fm* h, sufr_hip_fm** out)
         }
     }
     if (rc) { sufr_hip_fm_free(fm); return rc; }
+    memcpy(fm->h_tabs, tabs.data(), sizeof fm->h_tabs);
     uint64_t* d_C = (uint64_t*)fm->tabs;
     fm->V = sufr::FmView{(const uint8_t*)fm->blocks, (const sufr::FmMark*)fm->marks, (const uint8_t*)fm->kept, d_C, (const uint32_t*)(d_C + 257),
                          h->s, h->q, h->sh, h->e};
@@ -929,6 +972,93 @@ int sufr_hip_fm_download(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, sufr_fm** out
     if (V.q && (V.s & 63u)) h->marks.back().bits &= ((uint64_t)1 << (V.s & 63u)) - 1;
     *out = h;
     return 0;
+}
+
+}  // extern "C"
+
+// ---- include/sufr_fm_match.h: matching statistics and SMEMs on a pair of indexes (DESIGN.md section 26) ---------------------
+namespace {
+
+static constexpr uint32_t FM_MS_SLAB = 32;               // the bytes of a lane of k_fm_ms (profiles/fm_match_bench.txt)
+
+// both indexes on the context's device, and a pair (sufr_fm_match.h): from the host copies of the tables
+int fm_pair_check(sufr_hip_ctx* ctx, const sufr_hip_fm* fwd, const sufr_hip_fm* rev)
+{
+    int rc;
+    if ((rc = fm_check(ctx, fwd)) || (rc = fm_check(ctx, rev))) return rc;
+    const sufr::FmView &F = fwd->V, &R = rev->V;
+    if (F.s == R.s && F.sh.w == R.sh.w && F.e == R.e && !memcmp(fwd->h_tabs, rev->h_tabs, sizeof fwd->h_tabs)) return 0;
+    ctx->pl.set_error("not an index of the reversed text");
+    return SUFR_HIP_E_INVALID;
+}
+
+template <uint32_t G>
+void fm_ms_launch(sufr_hip_ctx* ctx, const sufr_hip_fm* fwd, const sufr_hip_fm* rev, const void* d_queries, const void* d_offsets, uint64_t nq, void* d_ms)
+{
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(batch_grid(ctx->pl)), dim3(256), 0, ctx->pl.stream, fwd->V, rev->V, (const uint8_t*)d_queries,
+                           (const uint64_t*)d_offsets, nq, (uint32_t*)d_ms);
+    };
+    if (sufr::fm_is_line(fwd->V.sh)) launch(sufr::k_fm_ms<true, G>); else launch(sufr::k_fm_ms<false, G>);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_hip_fm_matching_stats_device(sufr_hip_ctx* ctx, const sufr_hip_fm* fwd, const sufr_hip_fm* rev, const void* d_queries, const void* d_offsets,
+                                      uint64_t num_queries, void* d_ms)
+{
+    if (!ctx || !fwd || !rev || (num_queries && (!d_queries || !d_offsets || !d_ms))) return SUFR_HIP_E_INVALID;
+    if (const int rc = fm_pair_check(ctx, fwd, rev)) return rc;
+    if (!num_queries) return 0;
+#ifdef SUFR_HIP_PROBES
+    // the probes build has the other slabs too, for the table FM_MS_SLAB was chosen from; no result depends on the slab
+    const char* v = getenv("SUFR_PROBE_FM_MS_SLAB");
+    switch (v ? atoi(v) : 0) {
+        case 64: fm_ms_launch<64>(ctx, fwd, rev, d_queries, d_offsets, num_queries, d_ms); break;
+        case 128: fm_ms_launch<128>(ctx, fwd, rev, d_queries, d_offsets, num_queries, d_ms); break;
+        case 256: fm_ms_launch<256>(ctx, fwd, rev, d_queries, d_offsets, num_queries, d_ms); break;
+        default: fm_ms_launch<FM_MS_SLAB>(ctx, fwd, rev, d_queries, d_offsets, num_queries, d_ms); break;
+    }
+#else
+    fm_ms_launch<FM_MS_SLAB>(ctx, fwd, rev, d_queries, d_offsets, num_queries, d_ms);
+#endif
+    return launch_status(ctx->pl, "fm_matching_stats");
+}
+
+int sufr_hip_fm_smems_device(sufr_hip_ctx* ctx, const sufr_hip_fm* fwd, const sufr_hip_fm* rev, const void* d_queries, const void* d_offsets,
+                             uint64_t num_queries, uint32_t min_len, void* d_ms, uint64_t cap, void* d_query, void* d_query_offset, void* d_length,
+                             void* d_rank_lo, void* d_rank_hi, uint64_t* total_out)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !fwd || !rev || (num_queries && (!d_queries || !d_offsets || !d_ms))) return SUFR_HIP_E_INVALID;
+    int rc;
+    if ((rc = fm_pair_check(ctx, fwd, rev))) return rc;
+    if (min_len == 0) { ctx->pl.set_error("fm_smems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
+    if (!num_queries) return 0;
+    if ((rc = sufr_hip_fm_matching_stats_device(ctx, fwd, rev, d_queries, d_offsets, num_queries, d_ms))) return rc;
+    // the rank range of every SMEM: the backward search of the packed slices on the index of the text
+    return smems_from_stats(ctx, d_queries, d_offsets, num_queries, min_len, d_ms, cap, d_query, d_query_offset, d_length, d_rank_lo, d_rank_hi, total_out,
+                            [&](const void* packed, const uint64_t* slice_off, uint64_t nsm) {
+        return sufr_hip_fm_search_batch_device(ctx, fwd, packed, slice_off, nsm, d_rank_lo, d_rank_hi);
+    });
+}
+
+int sufr_hip_fm_smems(sufr_hip_ctx* ctx, const sufr_hip_fm* fwd, const sufr_hip_fm* rev, const uint8_t* queries, const uint64_t* offsets,
+                      uint64_t num_queries, uint32_t min_len, uint64_t cap, uint64_t* query, uint32_t* query_offset, uint32_t* length, uint64_t* rank_lo,
+                      uint64_t* rank_hi, uint64_t* total_out)
+{
+    if (total_out) *total_out = 0;
+    if (!ctx || !fwd || !rev || (num_queries && !offsets)) return SUFR_HIP_E_INVALID;
+    if (const int rc = fm_pair_check(ctx, fwd, rev)) return rc;
+    if (min_len == 0) { ctx->pl.set_error("fm_smems: min_len must be at least 1"); return SUFR_HIP_E_INVALID; }
+    if (!num_queries) return 0;
+    // the matching statistics (4 bytes per query byte) stay on the device: they ride behind the record columns
+    return staged_records(ctx, "FM SMEM", queries, offsets, num_queries, cap, {{query, 8}, {query_offset, 4}, {length, 4}, {rank_lo, 8}, {rank_hi, 8}},
+                          offsets[num_queries] * 4, total_out, [&](const void* d_q, const void* d_off, void* const* col, uint64_t* total) {
+        return sufr_hip_fm_smems_device(ctx, fwd, rev, d_q, d_off, num_queries, min_len, col[5], cap, col[0], col[1], col[2], col[3], col[4], total);
+    });
 }
 
 }  // extern "C"

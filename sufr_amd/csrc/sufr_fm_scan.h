@@ -1,6 +1,6 @@
 // sufr_fm_scan.h -- the layout and the arithmetic of the FM-index over the BWT of the indexed text (include/sufr_fm.h,
 // DESIGN.md section 23): the shape of a block, the count of a byte value in the front of a block, occ, the backward search
-// of one query, the walk from a rank to a sampled suffix, the chunk walk of extract (section 25) and the backtracking walk of the k-mismatch search (section 24).  Plain integer code that the kernels of sufr_fm.inc and the host
+// of one query, the walk from a rank to a sampled suffix, the chunk walk of extract (section 25), the backtracking walk of the k-mismatch search (section 24) and the walk of the matching statistics on a pair of indexes (section 26).  Plain integer code that the kernels of sufr_fm.inc and the host
 // path of sufr_query.cpp both compile (SUFR_HD, the way of sufr_bwt_scan.h); there is no second copy of it.  The kernels read
 // a block with wider loads than fm_occ does and count with the same fm_eq_bytes.
 //
@@ -241,6 +241,52 @@ SUFR_HD void fm_approx_walk(const FmView& V, const uint8_t* Q, uint64_t m, uint3
             f = st.get(--h);
         }
     }
+}
+
+// ---- matching statistics on a pair of indexes (include/sufr_fm_match.h) ----------------------------
+// May byte c of column k stand inside a match?  Not where it does not occur, and never the end byte: X leaves it out
+SUFR_HD bool fm_ms_byte_ok(uint32_t k, uint32_t c, uint32_t e) { return k != FM_NO_COL && c != e; }
+
+// The walk of include/sufr_fm_match.h over the offsets [a, b) of the query Q[0..m), a <= b <= m: out(j, ms[j]) once for every
+// a <= j < b, in descending order of j.  F is the index of T, R that of the reversed text; the two agree in C and in the
+// columns (sufr_fm_pair_check), which tab.C(c) and tab.col(c) read from wherever they are kept.  step(V, c, k, lo, hi) moves
+// the range [lo, hi) of V by the byte c of column k: lo = C[c] + occ(c, lo), hi = C[c] + occ(c, hi).  The extension of an
+// offset reads the query up to m, beyond b; the search back stops at a, where the offsets of this piece end -- Q[a..end)
+// occurs then, which is all that the offsets a .. x need (fact (a) of the header).  Returns the steps: the bytes looked at.
+// Arrays that are no pair of a text and its reversal may end a search back above the offset it came from; the walk then
+// gives that one offset its extension and goes on below it, so that it ends, and it reads only what each index reads alone.
+template <class Tab, class Step, class Out>
+SUFR_HD uint64_t fm_ms_walk(const FmView& F, const FmView& R, const Tab& tab, const uint8_t* Q, uint64_t m, uint64_t a, uint64_t b, Step&& step, Out&& out)
+{
+    uint64_t steps = 0;
+    for (uint64_t x1 = b; x1 > a;) {                     // x1 - 1: the offset at work, x of the header
+        const uint64_t x = x1 - 1;
+        uint64_t end = x, lo = 0, hi = 0;
+        for (; end < m; end++) {                         // forwards on R: ms[x] = end - x
+            const uint32_t c = Q[end], k = tab.col(c);
+            steps++;
+            if (!fm_ms_byte_ok(k, c, F.e)) break;
+            uint64_t ua = lo, ub = hi;
+            if (end == x) { ua = tab.C(c); ub = tab.C(c + 1u); } else step(R, c, k, ua, ub);
+            if (ua >= ub) break;
+            lo = ua; hi = ub;
+        }
+        if (end == x) { out(x, (uint32_t)0); x1 = x; continue; }
+        uint64_t start = end;
+        for (; start > a; start--) {                     // backwards on F from end: Q[start..end) occurs
+            const uint32_t c = Q[start - 1], k = tab.col(c);
+            steps++;
+            if (!fm_ms_byte_ok(k, c, F.e)) break;
+            uint64_t ua = lo, ub = hi;
+            if (start == end) { ua = tab.C(c); ub = tab.C(c + 1u); } else step(F, c, k, ua, ub);
+            if (ua >= ub) break;
+            lo = ua; hi = ub;
+        }
+        if (start > x) start = x;                        // (only arrays that are no pair)
+        for (uint64_t j = x1; j-- > start;) out(j, (uint32_t)(end - j));
+        x1 = start;
+    }
+    return steps;
 }
 
 }  // namespace sufr

@@ -26,6 +26,7 @@
 #include "../../include/sufr_bwt.h"
 #include "../../include/sufr_fm_approx.h"
 #include "../../include/sufr_fm_text.h"
+#include "../../include/sufr_fm_match.h"
 
 struct sufr_hip_ctx { std::string err; };
 
@@ -216,5 +217,11 @@ int sufr_hip_fm_extract_batch(sufr_hip_ctx* ctx, const sufr_hip_fm*, const uint6
                               uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 int sufr_hip_fm_upload(sufr_hip_ctx* ctx, const sufr_fm*, sufr_hip_fm** out) { if (out) *out = nullptr; return no_device(ctx); }
 int sufr_hip_fm_download(sufr_hip_ctx* ctx, const sufr_hip_fm*, sufr_fm** out) { if (out) *out = nullptr; return no_device(ctx); }
+// ---- include/sufr_fm_match.h: the device side
+int sufr_hip_fm_matching_stats_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const sufr_hip_fm*, const void*, const void*, uint64_t, void*) { return no_device(ctx); }
+int sufr_hip_fm_smems_device(sufr_hip_ctx* ctx, const sufr_hip_fm*, const sufr_hip_fm*, const void*, const void*, uint64_t, uint32_t, void*, uint64_t, void*,
+                             void*, void*, void*, void*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
+int sufr_hip_fm_smems(sufr_hip_ctx* ctx, const sufr_hip_fm*, const sufr_hip_fm*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint64_t*,
+                      uint32_t*, uint32_t*, uint64_t*, uint64_t*, uint64_t* total_out) { if (total_out) *total_out = 0; return no_device(ctx); }
 
 }  // extern "C"

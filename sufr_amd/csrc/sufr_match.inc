@@ -10,7 +10,8 @@
 // k_smem_emit        the flags again, scanned inside the workgroup: records in (query, offset) order + packed slice offsets
 // k_smem_gather      the SMEM slices packed into one query batch, searched by the unchanged sufr_hip_search_batch_device
 // No MFMA, no LDS beyond the scan words, no scratch.
-// Its own: match_stat, the SMEM rule (match_flags8) and the three SMEM kernels.  The search, last_le, wg_scan, scan_chunk
+// Its own: match_stat, the SMEM rule (match_flags8), the three SMEM kernels and smems_from_stats, the SMEMs of statistics that
+// are there, which sufr_fm.inc calls too (include/sufr_fm_match.h).  The search, last_le, wg_scan, scan_chunk
 // (SCAN_WGS workgroups), query_check, read_totals, the record epilogue and staged_records are sufr_search.inc's.
 
 namespace sufr {
@@ -118,6 +119,49 @@ __global__ __launch_bounds__(256) void k_smem_gather(const uint8_t* __restrict__
 
 }  // namespace sufr
 
+namespace {
+
+// The SMEMs of a batch whose statistics are in d_ms: flags, the one synchronisation for the totals, records and the packed
+// slices; search(packed, slice_off, nsm) then enqueues the rank range of every slice
+template <typename Search>
+int smems_from_stats(sufr_hip_ctx* ctx, const void* d_queries, const void* d_offsets, uint64_t num_queries, uint32_t min_len, const void* d_ms,
+                     uint64_t cap, void* d_query, void* d_query_offset, void* d_length, void* d_rank_lo, void* d_rank_hi, uint64_t* total_out,
+                     Search search)
+{
+    sufr::Pipeline& pl = ctx->pl;
+    int rc;
+    // blocksums of the counts and of the lengths, then their two totals
+    const uint64_t G = sufr::SCAN_WGS;
+    if ((rc = pl.ensure(ctx->mtmp, (2 * G + 2) * 8))) return rc;
+    uint64_t* cnt_sum = (uint64_t*)ctx->mtmp.p;
+    uint64_t* len_sum = cnt_sum + G;
+    uint64_t* tot = len_sum + G;
+    const uint64_t* off = (const uint64_t*)d_offsets;
+    const uint32_t* ms = (const uint32_t*)d_ms;
+    hipLaunchKernelGGL(sufr::k_smem_count, dim3((uint32_t)G), dim3(256), 0, pl.stream, ms, off, num_queries, min_len, cnt_sum, len_sum);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, G, tot);
+    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, len_sum, G, tot + 1);
+    unsigned long long totals[2] = {0, 0};
+    if ((rc = read_totals(pl, tot, 2, totals, "smems", "counting the SMEMs failed"))) return rc;
+    const uint64_t nsm = totals[0], nbytes = totals[1];
+    if ((rc = records_fit(pl, "smems", "SMEMs", nsm, cap, total_out)) || !nsm) return rc;
+    if (any_null({d_query, d_query_offset, d_length, d_rank_lo, d_rank_hi})) return SUFR_HIP_E_INVALID;
+    if ((rc = pl.ensure(ctx->mpoff, (nsm + 1) * 8)) || (rc = pl.ensure(ctx->mbytes, nbytes))) return rc;
+    uint64_t* slice_off = (uint64_t*)ctx->mpoff.p;
+    hipLaunchKernelGGL(sufr::k_smem_emit, dim3((uint32_t)G), dim3(256), 0, pl.stream, ms, off, num_queries, min_len,
+                       (const uint64_t*)cnt_sum, (const uint64_t*)len_sum, (uint64_t*)d_query, (uint32_t*)d_query_offset,
+                       (uint32_t*)d_length, slice_off);
+    uint64_t gw = (nsm + 3) / 4;
+    if (gw > 16384) gw = 16384;
+    hipLaunchKernelGGL(sufr::k_smem_gather, dim3((uint32_t)gw), dim3(256), 0, pl.stream, (const uint8_t*)d_queries, off,
+                       (const uint64_t*)d_query, (const uint32_t*)d_query_offset, (const uint32_t*)d_length, slice_off, nsm, nbytes,
+                       (uint8_t*)ctx->mbytes.p);
+    if ((rc = launch_status(pl, "smems"))) return rc;
+    return search(ctx->mbytes.p, slice_off, nsm);
+}
+
+}  // namespace
+
 extern "C" {
 
 int sufr_hip_matching_stats_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const void* d_queries, const void* d_offsets,
@@ -149,35 +193,11 @@ int sufr_hip_smems_device(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const voi
     if (!num_queries) return 0;
     int rc;
     if ((rc = sufr_hip_matching_stats_device(ctx, ix, d_queries, d_offsets, num_queries, d_ms))) return rc;
-    // blocksums of the counts and of the lengths, then their two totals
-    const uint64_t G = sufr::SCAN_WGS;
-    if ((rc = pl.ensure(ctx->mtmp, (2 * G + 2) * 8))) return rc;
-    uint64_t* cnt_sum = (uint64_t*)ctx->mtmp.p;
-    uint64_t* len_sum = cnt_sum + G;
-    uint64_t* tot = len_sum + G;
-    const uint64_t* off = (const uint64_t*)d_offsets;
-    const uint32_t* ms = (const uint32_t*)d_ms;
-    hipLaunchKernelGGL(sufr::k_smem_count, dim3((uint32_t)G), dim3(256), 0, pl.stream, ms, off, num_queries, min_len, cnt_sum, len_sum);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, cnt_sum, G, tot);
-    hipLaunchKernelGGL(sufr::k_locate_scan, dim3(1), dim3(1024), 0, pl.stream, len_sum, G, tot + 1);
-    unsigned long long totals[2] = {0, 0};
-    if ((rc = read_totals(pl, tot, 2, totals, "smems", "counting the SMEMs failed"))) return rc;
-    const uint64_t nsm = totals[0], nbytes = totals[1];
-    if ((rc = records_fit(pl, "smems", "SMEMs", nsm, cap, total_out)) || !nsm) return rc;
-    if (any_null({d_query, d_query_offset, d_length, d_rank_lo, d_rank_hi})) return SUFR_HIP_E_INVALID;
-    if ((rc = pl.ensure(ctx->mpoff, (nsm + 1) * 8)) || (rc = pl.ensure(ctx->mbytes, nbytes))) return rc;
-    uint64_t* slice_off = (uint64_t*)ctx->mpoff.p;
-    hipLaunchKernelGGL(sufr::k_smem_emit, dim3((uint32_t)G), dim3(256), 0, pl.stream, ms, off, num_queries, min_len,
-                       (const uint64_t*)cnt_sum, (const uint64_t*)len_sum, (uint64_t*)d_query, (uint32_t*)d_query_offset,
-                       (uint32_t*)d_length, slice_off);
-    uint64_t gw = (nsm + 3) / 4;
-    if (gw > 16384) gw = 16384;
-    hipLaunchKernelGGL(sufr::k_smem_gather, dim3((uint32_t)gw), dim3(256), 0, pl.stream, (const uint8_t*)d_queries, off,
-                       (const uint64_t*)d_query, (const uint32_t*)d_query_offset, (const uint32_t*)d_length, slice_off, nsm, nbytes,
-                       (uint8_t*)ctx->mbytes.p);
-    if ((rc = launch_status(pl, "smems"))) return rc;
     // the rank range of every SMEM: the unchanged batched search of the packed slices (the build's cap applies as in count)
-    return sufr_hip_search_batch_device(ctx, ix, ctx->mbytes.p, slice_off, nsm, 0, 0, d_rank_lo, d_rank_hi);
+    return smems_from_stats(ctx, d_queries, d_offsets, num_queries, min_len, d_ms, cap, d_query, d_query_offset, d_length, d_rank_lo, d_rank_hi, total_out,
+                            [&](const void* packed, const uint64_t* slice_off, uint64_t nsm) {
+        return sufr_hip_search_batch_device(ctx, ix, packed, slice_off, nsm, 0, 0, d_rank_lo, d_rank_hi);
+    });
 }
 
 int sufr_hip_smems(sufr_hip_ctx* ctx, const sufr_hip_index* ix, const uint8_t* queries, const uint64_t* offsets,

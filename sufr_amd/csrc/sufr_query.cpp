@@ -6,6 +6,7 @@
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -359,6 +360,29 @@ void host_ms_batch(const sufr_file& f, const uint8_t* queries, const uint64_t* o
     });
 }
 
+// The SMEM rule over the statistics ms[g - g0] of a batch, in (query, offset) order: the records are counted, then written.
+// total: their number, also where it exceeds cap (SUFR_HIP_E_CAPACITY, nothing written)
+int smem_records(const uint32_t* ms, uint64_t g0, const uint64_t* offsets, uint64_t nq, uint32_t min_len, uint64_t cap, uint64_t* query,
+                 uint32_t* qoff, uint32_t* len, const uint64_t* rank_lo, const uint64_t* rank_hi, uint64_t& total, uint64_t* total_out)
+{
+    auto each_smem = [&](auto emit) {
+        for (uint64_t i = 0; i < nq; i++)
+            for (uint64_t g = offsets[i]; g < offsets[i + 1]; g++) {
+                const uint32_t v = ms[g - g0];
+                if (v >= min_len && (g == offsets[i] || ms[g - g0 - 1] <= v)) emit(i, g, v);
+            }
+    };
+    total = 0;
+    each_smem([&](uint64_t, uint64_t, uint32_t) { total++; });
+    if (total_out) *total_out = total;
+    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (!total) return 0;
+    if (!query || !qoff || !len || !rank_lo || !rank_hi) return SUFR_HIP_E_INVALID;
+    uint64_t t = 0;
+    each_smem([&](uint64_t i, uint64_t g, uint32_t v) { query[t] = i; qoff[t] = (uint32_t)(g - offsets[i]); len[t] = v; t++; });
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -384,22 +408,9 @@ int sufr_file_smems(const sufr_file* f, const uint8_t* queries, const uint64_t* 
     const uint64_t g0 = offsets[0];
     std::vector<uint32_t> ms(offsets[nq] - g0);
     host_ms_batch(*f, queries, offsets, nq, threads, ms.data(), g0);
-    // the SMEM rule in (query, offset) order: emit(i, g, length) for every SMEM; they are counted, then written
-    auto each_smem = [&](auto emit) {
-        for (uint64_t i = 0; i < nq; i++)
-            for (uint64_t g = offsets[i]; g < offsets[i + 1]; g++) {
-                const uint32_t v = ms[g - g0];
-                if (v >= min_len && (g == offsets[i] || ms[g - g0 - 1] <= v)) emit(i, g, v);
-            }
-    };
     uint64_t total = 0;
-    each_smem([&](uint64_t, uint64_t, uint32_t) { total++; });
-    if (total_out) *total_out = total;
-    if (total > cap) return SUFR_HIP_E_CAPACITY;
+    if (const int rc = smem_records(ms.data(), g0, offsets, nq, min_len, cap, query, qoff, len, rank_lo, rank_hi, total, total_out)) return rc;
     if (!total) return 0;
-    if (!query || !qoff || !len || !rank_lo || !rank_hi) return SUFR_HIP_E_INVALID;
-    uint64_t t = 0;
-    each_smem([&](uint64_t i, uint64_t g, uint32_t v) { query[t] = i; qoff[t] = (uint32_t)(g - offsets[i]); len[t] = v; t++; });
     // the rank range of every SMEM: a plain search of its slice (it occurs: ms >= min_len >= 1)
     parallel_chunks(total, 256, threads, [&](uint64_t b, uint64_t e) {
         for (uint64_t k = b; k < e; k++) {
@@ -1501,6 +1512,7 @@ int sufr_file_lf(const sufr_file* f, void* lf, int threads)
 // section 23) ---------------------------------------------------------------------------------------------------------
 #include "../../include/sufr_fm_approx.h"
 #include "../../include/sufr_fm_text.h"
+#include "../../include/sufr_fm_match.h"
 #include "sufr_fm_host.h"
 
 namespace {
@@ -2058,6 +2070,144 @@ int sufr_fm_load(const char* path, sufr_fm** out, int threads, char* err, size_t
     if (!bad.empty()) return fail(SUFR_HIP_E_INVALID, bad);
     fclose(fp);
     *out = fm;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- matching statistics and SMEMs on a pair of indexes (include/sufr_fm_match.h) -----------------------
+namespace {
+
+// C and the columns of the pair, which agree (sufr_fm_pair_check), read from the index of the text
+struct FmHostTab {
+    const sufr::FmView& V;
+    uint32_t col(uint32_t c) const { return V.col[c]; }
+    uint64_t C(uint32_t c) const { return V.C[c]; }
+};
+
+void fm_host_step(const sufr::FmView& V, uint32_t c, uint32_t, uint64_t& a, uint64_t& b)
+{
+    a = V.C[c] + sufr::fm_occ(V, c, a);
+    b = V.C[c] + sufr::fm_occ(V, c, b);
+}
+
+int fm_match_args(const sufr_fm* fwd, const sufr_fm* rev, const uint8_t* queries, const uint64_t* offsets, uint64_t nq)
+{
+    if (!fwd || !rev || (nq && !offsets) || (nq && offsets[nq] > offsets[0] && !queries)) return SUFR_HIP_E_INVALID;
+    for (uint64_t i = 0; i < nq; i++) if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFFFull) return SUFR_HIP_E_INVALID;
+    return sufr_fm_pair_check(fwd, rev);
+}
+
+// The bytes of a piece of the batch that one call of a worker takes.  SUFR_FM_MS_HOST_SLAB sets it for the tests of the
+// cuts; no result depends on it (fact (a) of the header)
+uint64_t fm_ms_host_slab()
+{
+    const char* v = getenv("SUFR_FM_MS_HOST_SLAB");
+    const long long k = v ? atoll(v) : 0;
+    return k > 0 ? (uint64_t)k : 4096;
+}
+
+// ms[g - base] for every byte g of the batch: workers take slabs of the concatenated bytes, and in a slab the part of every
+// query that it touches is one fm_ms_walk
+void fm_ms_batch(const sufr_fm* fwd, const sufr_fm* rev, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, int threads, uint32_t* ms,
+                 uint64_t base)
+{
+    const sufr::FmView F = fwd->view(), R = rev->view();
+    const FmHostTab tab{F};
+    const uint64_t g0 = offsets[0];
+    parallel_chunks(offsets[nq] - g0, fm_ms_host_slab(), threads, [&](uint64_t b, uint64_t e) {
+        uint64_t a = query_of(offsets, nq, g0 + b);
+        for (uint64_t g = g0 + b; g < g0 + e;) {
+            while (offsets[a + 1] <= g) a++;
+            const uint64_t qb = offsets[a], qe = offsets[a + 1], pe = qe < g0 + e ? qe : g0 + e;
+            uint32_t* out = ms + (qb - base);
+            sufr::fm_ms_walk(F, R, tab, queries + qb, qe - qb, g - qb, pe - qb, fm_host_step, [&](uint64_t j, uint32_t v) { out[j] = v; });
+            g = pe;
+        }
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sufr_fm_pair_check(const sufr_fm* fwd, const sufr_fm* rev)
+{
+    if (!fwd || !rev) return SUFR_HIP_E_INVALID;
+    const bool same = fwd->s == rev->s && fwd->sh.w == rev->sh.w && fwd->e == rev->e && !memcmp(fwd->col, rev->col, sizeof fwd->col) &&
+                      !memcmp(fwd->C, rev->C, sizeof fwd->C);
+    return same ? 0 : SUFR_HIP_E_INVALID;
+}
+
+int sufr_fm_matching_stats(const sufr_fm* fwd, const sufr_fm* rev, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t* ms,
+                           int threads)
+{
+    if (const int rc = fm_match_args(fwd, rev, queries, offsets, nq)) return rc;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    if (!ms) return SUFR_HIP_E_INVALID;
+    fm_ms_batch(fwd, rev, queries, offsets, nq, threads, ms, 0);
+    return 0;
+}
+
+int sufr_fm_smems(const sufr_fm* fwd, const sufr_fm* rev, const uint8_t* queries, const uint64_t* offsets, uint64_t nq, uint32_t min_len,
+                  uint64_t cap, uint64_t* query, uint32_t* qoff, uint32_t* len, uint64_t* rank_lo, uint64_t* rank_hi, uint64_t* total_out,
+                  int threads)
+{
+    if (total_out) *total_out = 0;
+    if (const int rc = fm_match_args(fwd, rev, queries, offsets, nq)) return rc;
+    if (min_len == 0) return SUFR_HIP_E_INVALID;
+    if (!nq || offsets[nq] == offsets[0]) return 0;
+    const uint64_t g0 = offsets[0];
+    std::vector<uint32_t> ms(offsets[nq] - g0);
+    fm_ms_batch(fwd, rev, queries, offsets, nq, threads, ms.data(), g0);
+    uint64_t total = 0;
+    if (const int rc = smem_records(ms.data(), g0, offsets, nq, min_len, cap, query, qoff, len, rank_lo, rank_hi, total, total_out)) return rc;
+    if (!total) return 0;
+    // the rank range of every SMEM: the backward search of its slice on the index of the text
+    const sufr::FmView F = fwd->view();
+    parallel_chunks(total, 256, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t k = b; k < e; k++) sufr::fm_search(F, queries + offsets[query[k]] + qoff[k], len[k], rank_lo[k], rank_hi[k]);
+    }, 64);
+    return 0;
+}
+
+int sufr_fm_matching_stats_steps(const sufr_fm* fwd, const sufr_fm* rev, const uint8_t* queries, const uint64_t* offsets, uint64_t nq,
+                                 uint64_t* steps, int threads)
+{
+    if (const int rc = fm_match_args(fwd, rev, queries, offsets, nq)) return rc;
+    if (!nq) return 0;
+    if (!steps) return SUFR_HIP_E_INVALID;
+    const sufr::FmView F = fwd->view(), R = rev->view();
+    const FmHostTab tab{F};
+    parallel_chunks(nq, 16, threads, [&](uint64_t b, uint64_t e) {
+        for (uint64_t i = b; i < e; i++)
+            steps[i] = sufr::fm_ms_walk(F, R, tab, queries + offsets[i], offsets[i + 1] - offsets[i], 0, offsets[i + 1] - offsets[i], fm_host_step,
+                                        [](uint64_t, uint32_t) {});
+    }, 4);
+    return 0;
+}
+
+int sufr_file_write_reversed_fasta(const sufr_file* f, const char* path, char* err, size_t errlen)
+{
+    if (!f || !path) return SUFR_HIP_E_INVALID;
+    const uint64_t n = f->meta.text_len, k = f->seq_starts.size();
+    if (!n) { put_err(err, errlen, "the file holds no text"); return SUFR_HIP_E_INVALID; }
+    FILE* fp = fopen(path, "wb");
+    if (!fp) { put_err(err, errlen, std::string(path) + ": " + strerror(errno)); return SUFR_HIP_E_IO; }
+    // sequence i is T[starts[i] .. the delimiter in front of starts[i + 1]), the last one ends in front of the end byte
+    std::vector<uint8_t> line;
+    bool ok = true;
+    for (uint64_t i = k; i-- > 0 && ok;) {
+        const uint64_t b = f->seq_starts[i], e = i + 1 < k ? f->seq_starts[i + 1] - 1 : n - 1;
+        line.assign(1, (uint8_t)'>');
+        line.insert(line.end(), f->seq_names[i].begin(), f->seq_names[i].end());
+        line.push_back((uint8_t)'\n');
+        for (uint64_t p = e; p-- > b;) line.push_back(f->text[p]);
+        if (e > b) line.push_back((uint8_t)'\n');
+        ok = fwrite(line.data(), 1, line.size(), fp) == line.size();
+    }
+    if (fclose(fp) != 0) ok = false;
+    if (!ok) { put_err(err, errlen, std::string(path) + ": write failed"); return SUFR_HIP_E_IO; }
     return 0;
 }
 

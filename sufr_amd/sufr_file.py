@@ -447,6 +447,14 @@ class SufrFile:
             out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), a, b, sa[a:_hit_end(a, b, max_hits)].copy()))
         return out
 
+    def write_reversed_fasta(self, path) -> None:
+        """Writes the FASTA of the reversed text (include/sufr_fm_match.h): every sequence reversed and their order reversed,
+        each under its name.  Created with this file's flags it gives the .sufr whose FM-index is the `rev` of a pair."""
+        err = C.create_string_buffer(512)
+        rc = lib().sufr_file_write_reversed_fasta(self._h, str(path).encode(), err, 512)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_file_write_reversed_fasta: " + (err.value.decode() or "failed"))
+
     def mem_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, min_len: int = 20, max_occ: int = 0, both_strands: bool = False,
                    cap: Optional[int] = None, threads: int = 0):
         """(query, query_offset, strand, length, position) of every MEM of a packed batch, in (query, strand, offset, rank)
@@ -972,6 +980,63 @@ class FmIndex:
             raise SufrHipError(rc, "sufr_fm_approx_steps failed")
         return leaves, steps
 
+    # -- matching statistics and SMEMs on a pair of indexes (include/sufr_fm_match.h) ---------------------------------------
+    @staticmethod
+    def _pair_error(fn: str, noun: str = "records"):
+        return lambda rc, total, c: SufrHipError(rc, f"{fn}: " + {
+            -5: f"{total} {noun}, room for {c}",
+            -1: "not an index of the reversed text, or an invalid argument (min_len must be at least 1)"}.get(rc, "failed"))
+
+    def pair_check(self, rev: "FmIndex") -> None:
+        """Raises unless `rev` agrees with this index in ranks, width, end byte, byte values and C: necessary for an index of
+        the reversed text, not sufficient."""
+        rc = lib().sufr_fm_pair_check(self._h, rev._h)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_fm_pair_check: not an index of the reversed text")
+
+    def matching_stats(self, queries: Sequence, rev: "FmIndex", threads: int = 0) -> List[np.ndarray]:
+        """ms[j] per query (uint32 arrays), as SufrFile.matching_statistics returns them, from this index and `rev`, the index
+        of the reversed text, alone."""
+        self.pair_check(rev)
+        qb, off = pack_queries(queries)
+        ms = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        rc = lib().sufr_fm_matching_stats(self._h, rev._h, qb.ctypes.data, off.ctypes.data, len(off) - 1, ms.ctypes.data, threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_fm_matching_stats failed")
+        return _split(ms, off)
+
+    def smem_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, rev: "FmIndex", min_len: int = 20, cap: Optional[int] = None,
+                    threads: int = 0):
+        """(query, query_offset, length, rank_lo, rank_hi) of every SMEM of a packed batch, as SufrFile.smem_arrays returns
+        them.  With a `cap` too small the SufrHipError (code -5) carries the total in `.total`."""
+        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nq = len(offsets) - 1
+        return _sized_to_fit(
+            cap, int(offsets[-1] - offsets[0]) // 8 + 16, lambda c: [np.zeros(c, dtype=d) for d in _SMEM_DTYPES],
+            lambda c, out, total: lib().sufr_fm_smems(self._h, rev._h, qbytes.ctypes.data, offsets.ctypes.data, nq, min_len, c,
+                                                      *[a.ctypes.data for a in out], C.byref(total), threads),
+            self._pair_error("sufr_fm_smems", "SMEMs"))
+
+    def smems(self, queries: Sequence, rev: "FmIndex", min_len: int = 20, max_hits: int = 0, threads: int = 0) -> List[List[SmemHit]]:
+        """The SMEMs of every query as SufrFile.smems returns them, the positions by locate_ranges."""
+        qb, off = pack_queries(queries)
+        qi, qo, ln, lo, hi = self.smem_arrays(qb, off, rev, min_len, threads=threads)
+        po, pos = self.locate_ranges(lo, hi, max_hits, threads) if len(qi) else (np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=np.uint32))
+        out: List[List[SmemHit]] = [[] for _ in queries]
+        for t in range(len(qi)):
+            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[int(po[t]):int(po[t + 1])].copy()))
+        return out
+
+    def matching_stats_steps(self, queries: Sequence, rev: "FmIndex", threads: int = 0) -> np.ndarray:
+        """The steps of the whole-query walk of every query (uint64): what the statistics of a batch cost."""
+        qb, off = pack_queries(queries)
+        steps = np.zeros(max(len(off) - 1, 1), dtype=np.uint64)
+        rc = lib().sufr_fm_matching_stats_steps(self._h, rev._h, qb.ctypes.data, off.ctypes.data, len(off) - 1, steps.ctypes.data, threads)
+        if rc != 0:
+            raise SufrHipError(rc, "sufr_fm_matching_stats_steps: " + ("not an index of the reversed text" if rc == -1 else "failed"))
+        return steps[:len(off) - 1]
+
 
 class DeviceFmIndex:
     """The FM-index of a DeviceIndex in HBM (DeviceIndex.fm_device; include/sufr_fm.h).  It owns everything it reads: the
@@ -1121,6 +1186,61 @@ class DeviceFmIndex:
         o, p = self.locate_device(*self.search_device(*self._packed(queries)), max_hits)
         o = o.cpu().numpy(); p = p.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
         return [p[o[i]:o[i + 1]] for i in range(len(queries))]
+
+    # -- matching statistics and SMEMs on a pair of indexes (include/sufr_fm_match.h) ---------------------------------------
+    def matching_stats_device(self, qbytes, offsets, rev: "DeviceFmIndex", wait: bool = True):
+        """DeviceIndex.matching_statistics_device from this index and `rev`, the index of the reversed text, alone: an int32
+        tensor (u32 values) indexed like the bytes.  wait=False: call ctx.synchronize() before reading it."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        qbytes = DeviceIndex._device_bytes(qbytes)
+        ms = torch.zeros(max(int(offsets[-1]) if nq >= 0 and offsets.numel() else 0, 1), dtype=torch.int32, device=qbytes.device)
+        self.ctx.check(lib().sufr_hip_fm_matching_stats_device(self.ctx.handle, self._h, rev._h, qbytes.data_ptr(), offsets.data_ptr(),
+                                                               max(nq, 0), ms.data_ptr()))
+        if wait:
+            self.ctx.synchronize()
+        return ms
+
+    def matching_stats(self, queries: Sequence, rev: "DeviceFmIndex") -> List[np.ndarray]:
+        """ms[j] per query (uint32 arrays), computed on the device."""
+        qb, off = self._packed(queries)
+        ms = self.matching_stats_device(qb, off, rev)
+        return _split(ms.cpu().numpy().view(np.uint32), off.cpu().numpy().astype(np.uint64))
+
+    def smems_device(self, qbytes, offsets, rev: "DeviceFmIndex", min_len: int = 20, cap: Optional[int] = None):
+        """DeviceIndex.smems_device from the pair alone: (query int64, query_offset int32, length int32, rank_lo int64, rank_hi
+        int64) tensors in (query, offset) order, complete on return; `last_ms` keeps the statistics.  With a `cap` too small
+        the SufrHipError (code -5) carries the total in `.total`; without one the outputs are sized to fit."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        dev = qbytes.device
+        qbytes = DeviceIndex._device_bytes(qbytes)
+        nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
+        ms = torch.empty(max(int(offsets[-1]) if nq > 0 else 0, 1), dtype=torch.int32, device=dev)
+        out = _sized_to_fit(
+            cap, nbytes // 8 + 16, lambda c: [torch.empty(c, dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.int32, torch.int64, torch.int64)],
+            lambda c, out, total: lib().sufr_hip_fm_smems_device(self.ctx.handle, self._h, rev._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
+                                                                 min_len, ms.data_ptr(), c, *[t.data_ptr() for t in out], C.byref(total)),
+            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
+        self.ctx.synchronize()
+        self.last_ms = ms
+        return out
+
+    def smems(self, queries: Sequence, rev: "DeviceFmIndex", min_len: int = 20, max_hits: int = 0) -> List[List[SmemHit]]:
+        """The SMEMs of every query with their rank ranges and up to `max_hits` positions (0: all), as DeviceIndex.smems
+        returns them (sufr_hip_fm_smems_device + sufr_hip_fm_locate_batch_device)."""
+        qb, off = self._packed(queries)
+        qi, qo, ln, lo, hi = self.smems_device(qb, off, rev, min_len)
+        po, pos = self.locate_device(lo, hi, max_hits)
+        po = po.cpu().numpy()
+        pos = pos.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
+        qi, qo, ln, lo, hi = (t.cpu().numpy() for t in (qi, qo, ln, lo, hi))
+        out: List[List[SmemHit]] = [[] for _ in queries]
+        for t in range(len(qi)):
+            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[po[t]:po[t + 1]].copy()))
+        return out
 
 
 class DeviceIndex:
