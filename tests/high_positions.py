@@ -55,6 +55,51 @@ tests/lz_shim.cpp (tests/test_query_high_positions.py); the n-entry outputs are 
   lz_witness()      the twin's LPF, SRC and parse, held to the text alone (witness_lpf_at at lz_sample(), check_parse)
   assert_lz_shared_witness_is_not_empty()   targets, sources and copies on both sides of and across the boundary, positions that
                     the clip decides, every value of seqs, the records whose seqs a truncated position would change
+
+The BWT, its runs and LF (include/sufr_bwt.h) accept every index, so they use the plain region and the four geometries as they
+are: BWT[r] = T[SA[r] - 1] reads the filler byte in front of the region's first position, position 0 is never indexed (no
+cyclic row), and only `first` = SA[a] of a run record takes the shift.
+
+  bwt_answers()     the BWT bytes and counts, the run records and stats at min_len 1 and 8, LF, as plain lists
+  bwt_witness()     the twin's, held to numpy on the arrays (witness() of tests/test_bwt_host.py) and shown not to be empty
+
+The FM-index (include/sufr_fm.h, sufr_fm_approx.h, sufr_fm_text.h, sufr_fm_match.h) refuses an index that leaves positions out,
+so there the filler is indexed, and its suffix order is known without sorting.  Let T = 0x00^F region, where the region ends
+in `$` and holds no 0x00.  Suffix i < F is 0^(F-i) region: of two of them the one with the longer run of zeros is smaller,
+because a zero meets region[0] > 0 there, so ranks 0 .. F-1 are positions 0 .. F-1 in order; the region's suffixes follow in the
+order of SA(region), because they are the tail of the text:
+
+  SA(T)   = [0, 1, .., F-1] ++ (SA(region) + F)             every position indexed, `$` once: a valid input with K = 8 byte
+  BWT(T)  = `$`, 0^(F-1), then the region's BWT              values (0x00 $ % A C G N T), the one-line block shape at w == 4 and
+  LF[0]   = F, LF[r] = r - 1 for 1 <= r < F                  the generic one (64 + 64) at w == 8; the run records start with
+                                                             (0, 1, `$`, 0) and (1, F-1, 0x00, 1)
+
+The reversed text of sufr_fm_match.h is reverse(region[:-1]) 0^F `$`, and SA of it is [(R-1)+i for i < F] ++ [n-1] ++
+SA(reverse(region[:-1]) + `$`)[1:]: the zeros sort as above (the `$` behind them is larger than a zero), then the `$`, which is
+smaller than every byte of the region, and two suffixes that start in the reversed region differ inside it or where the shorter
+one meets its first zero, which is where it meets the `$` in the region alone -- the order does not depend on F >= 1.  Both
+formulas are held to a sort of the suffixes at F = 1, 7, 500 (tests/test_query_high_positions.py), and SA(region) and
+SA(reversed region) are the oracle's, every adjacent pair compared on the text in Python.
+
+Against the twin (F = 4096, shift = F - 4096): every text position differs by the shift; every non-empty rank range of a
+query that holds a non-zero byte differs by the shift (such a query occurs only where its non-zero byte meets the region, so
+its ranks are F - k for k leading zeros, or the region's); matching statistics, SMEM lengths and offsets, mismatch counts and
+extracted bytes are equal; the empty answer lo == hi == 0 is not shifted; a pure-zero query 0^k has the range [0, F - k + 1),
+the empty query [0, n): both analytic and asserted apart.  k-mismatch records are translation-invariant for queries of more
+than d bytes that fit the twin's filler and hold more than d non-zero bytes: a non-zero query byte then matches a region
+byte, so the window starts within a query's length of the region and sees filler to its left in both texts.  Here ranks *and*
+positions of the region straddle the boundary at its middle byte: rank F + r and the position of the region's r-th byte are
+both 4096 + r on the twin.  symbols=9 sets three bytes of the region to R, which makes K = 9: the wide block shape (64 + 64 in
+128) at w == 4.
+
+  full_region()     the region's bytes, SA(region) with every position indexed and SA(reversed region), at 8 or 9 symbols
+  FULL_GEOMETRIES   the four fillers and widths again; FULL_SYMBOLS: 9 symbols at twin and u32_across_2_31 only
+  full_arrays_host()    text, SA, reversed text and its SA as numpy arrays, for small F; full_host_pair() builds the host pair
+  full_sa_tail()    the last R entries of either suffix array at any F: what a device test copies behind an arange
+  fm_batch()        about 400 queries and, apart, the pure-zero ones
+  fm_answers()      every operation on a pair of indexes, host objects or adapters of device ones, as plain lists
+  assert_fm_witness_is_not_empty()   ranges and positions on both sides of the boundary, windows and SMEMs over it, 0 to 3
+                    mismatches on both strands, walks of 0 and q - 1 steps, the chunk of the cyclic row, zeros matched in the filler
 """
 from __future__ import annotations
 
@@ -699,4 +744,289 @@ def assert_lz_shared_witness_is_not_empty(f: SufrFile, lz: dict, shared: dict) -
     seen["shared kind=0 records whose seqs changes if positions from the boundary on read as sequence 0"] = \
         sum(1 for a, c, k in zip(rank.tolist(), count.tolist(), seqs.tolist()) if len(set(wrapped[a:a + c].tolist())) != k)
     assert all(v for key, v in seen.items() if key != "lpf nonzero in the filler") and seen["lpf nonzero in the filler"] == 0, seen
+    return seen
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the BWT, its runs and LF on the partial-index geometries (include/sufr_bwt.h): the plain region
+# ---------------------------------------------------------------------------------------------------------------------
+BWT_MIN_LENS = (1, 8)
+
+
+def bwt_answers(bwt, runs, lf, shift: int) -> dict:
+    """The BWT bytes with their 256 counts, the run records at every min_len of BWT_MIN_LENS (rank, length, symbol, first with
+    the shift taken off, the stats as sorted items) and LF as plain lists.  bwt() -> (bytes, counts), runs(min_len) -> (rank,
+    length, symbol, first, stats) and lf() -> the array are callables over numpy arrays or tensors; everything but `first`
+    is translation-invariant."""
+    b, counts = bwt()
+    out = {"bwt": [_ints(b), _ints(counts)]}
+    for min_len in BWT_MIN_LENS:
+        rank, length, symbol, first, stats = runs(min_len)
+        out[f"bwt runs min_len={min_len}"] = [_ints(rank), _ints(length), _ints(symbol), _ints(first, shift), sorted(stats.items())]
+    out["lf"] = _ints(lf())
+    return out
+
+
+def host_bwt_answers(f: SufrFile, shift: int, threads: int = 0) -> dict:
+    return bwt_answers(lambda: f.bwt(threads), lambda min_len: f.bwt_runs(min_len, threads), lambda: f.lf(threads), shift)
+
+
+def bwt_witness(f: SufrFile):
+    """(answers, counts): the twin's BWT answers, held to numpy on the arrays (text[sa - 1], np.bincount, a run-length pass and
+    a stable argsort: witness() of tests/test_bwt_host.py) and shown not to be empty: run records whose first position lies on
+    either side of the boundary, the filler byte in front of the region's first position, N and % among the BWT bytes"""
+    from test_bwt_host import witness
+    twin = GEOMETRIES["twin"]
+    assert f.text_len == twin.n and 0 not in np.asarray(f.suffix_array)           # position 0 is not indexed: no cyclic row
+    want = host_bwt_answers(f, 0)
+    text, sa = np.asarray(f.text), np.asarray(f.suffix_array)
+    for min_len in BWT_MIN_LENS:
+        bwt, counts, records, stats, lf = witness(text, sa, min_len)
+        numpy = {"bwt": [_ints(bwt), _ints(counts)], "lf": _ints(lf),
+                 f"bwt runs min_len={min_len}": [_ints(r) for r in records] + [sorted(stats.items())]}
+        compare(want, numpy, "the twin against numpy")
+    seen = {}
+    for min_len in BWT_MIN_LENS:
+        first = np.asarray(want[f"bwt runs min_len={min_len}"][3], dtype=np.int64)
+        seen[f"runs min_len={min_len} first below the boundary"] = int((first < twin.boundary).sum())
+        seen[f"runs min_len={min_len} first above the boundary"] = int((first > twin.boundary).sum())
+    b = np.asarray(want["bwt"][0])
+    seen.update({"bwt bytes 0x00": int((b == 0).sum()), "bwt bytes N": int((b == ord("N")).sum()), "bwt bytes %": int((b == ord("%")).sum())})
+    assert all(seen.values()) and seen["bwt bytes 0x00"] == 1 and int(sa[np.nonzero(b == 0)[0][0]]) == twin.filler, seen
+    return want, seen
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the FM-index (include/sufr_fm.h and its companions): the filler is indexed, its suffix order is known without sorting
+# ---------------------------------------------------------------------------------------------------------------------
+FULL_GEOMETRIES = dict(GEOMETRIES)                      # the same fillers and widths; here ranks *and* positions straddle the boundary
+FULL_SYMBOLS = {"twin": (8, 9), "u32_across_2_31": (8, 9), "u32_top": (8,), "u64_across_2_32": (8,)}
+assert FULL_GEOMETRIES["u32_across_2_31"].boundary == 1 << 31 and FULL_GEOMETRIES["u64_across_2_32"].boundary == 1 << 32
+R_AT = (7_000, MID + 37, 36_000)                        # symbols=9: three bytes set to R, one in each half and one by the middle
+FM_SAMPLE = 32
+FM_LOCATE_HITS = (0, 3)
+FM_APPROX_COMBOS = ((2, True), (3, False))              # (d, both strands)
+FM_SMEM_MIN_LENS = (1, 15)
+ZERO_PREFIXES = ((1, 40), (5, 16), (37, 150), (100, 40))  # (k, j) of the queries 0^k region[:j]; j > 3: see fm_batch()
+
+
+def check_suffix_order(t: bytes, sa):
+    """every adjacent pair of the array is in the order of the text's suffixes (and the array is a permutation): the arrays
+    rest on the text alone.  (4096 bytes decide all but a handful of pairs; the whole suffixes are compared where they do not)"""
+    sa = np.asarray(sa).astype(np.int64)
+    assert np.array_equal(np.sort(sa), np.arange(len(t)))
+    prev = int(sa[0])
+    for cur in sa[1:].tolist():
+        x, y = t[prev:prev + 4096], t[cur:cur + 4096]
+        assert x < y or (x == y and t[prev:] < t[cur:]), (prev, cur)
+        prev = cur
+
+
+@functools.lru_cache(maxsize=None)
+def full_region(symbols: int = 8):
+    """text (the bytes of region(); symbols=9: with the three bytes at R_AT set to R), sa = SA(text) with every position indexed,
+    rtext = reverse(text[:-1]) + $ and rsa = SA(rtext): uint8 and int64 arrays, the order of either array checked pair by pair
+    against the text in Python"""
+    from oracle_helper import Oracle
+    t = region().text.copy()
+    if symbols == 9:
+        assert all(t[p] in b"ACGT" for p in R_AT) and R_AT[0] < MID - 100 < R_AT[1] < MID + 100 < R_AT[2]
+        t[list(R_AT)] = ord("R")
+    assert t[-1] == ord("$") and 0 not in t and int((t == ord("$")).sum()) == 1 and np.unique(t).size == symbols - 1   # (0x00 is the filler's)
+    rt = np.concatenate([t[:-1][::-1], t[-1:]])
+    out = []
+    for x in (t, rt):
+        sa, _, _ = Oracle().build(x, is_dna=False)
+        assert sa.size == R
+        check_suffix_order(x.tobytes(), sa)
+        out.append(np.asarray(sa).astype(np.int64))
+    assert out[0][0] == out[1][0] == R - 1                          # the $ sorts first in both
+    t.setflags(write=False); rt.setflags(write=False)
+    return SimpleNamespace(text=t, sa=out[0], rtext=rt, rsa=out[1], symbols=symbols)
+
+
+def full_sa_tail(F: int, symbols: int = 8):
+    """(the last R entries of SA(T), the last R entries of SA(reversed T)) for T = 0x00^F region, as int64 arrays.  SA(T) =
+    [0 .. F) ++ SA(region) + F; SA(reversed T) = [R - 1 .. R - 1 + F) ++ [n - 1] ++ SA(reversed region)[1:] (see the docstring)"""
+    reg = full_region(symbols)
+    return reg.sa + F, np.concatenate([[F + R - 1], reg.rsa[1:]]).astype(np.int64)
+
+
+def full_arrays_host(F: int, symbols: int = 8):
+    """text, sa, rtext, rsa of T = 0x00^F region as numpy arrays (uint8, uint32): small F only"""
+    reg = full_region(symbols)
+    assert 1 <= F < 1 << 24
+    tail, rtail = full_sa_tail(F, symbols)
+    text = np.concatenate([np.zeros(F, dtype=np.uint8), reg.text])
+    rtext = np.concatenate([reg.rtext[:-1], np.zeros(F, dtype=np.uint8), reg.rtext[-1:]])
+    sa = np.concatenate([np.arange(F, dtype=np.int64), tail]).astype(np.uint32)
+    rsa = np.concatenate([np.arange(F, dtype=np.int64) + (R - 1), rtail]).astype(np.uint32)
+    assert np.array_equal(rtext, np.concatenate([text[:-1][::-1], text[-1:]])) and sa.size == rsa.size == F + R
+    return text, sa, rtext, rsa
+
+
+def full_host_pair(directory, F: int, symbols: int = 8, sample: int = FM_SAMPLE, threads: int = 0):
+    """(FmIndex of T with text samples, FmIndex of the reversed T without samples) built on the host from the files of
+    full_arrays_host(), and the two open files"""
+    from test_bwt_host import write_arrays
+    text, sa, rtext, rsa = full_arrays_host(F, symbols)
+    f = write_arrays(directory / f"full_{F}_{symbols}.sufr", text, sa)
+    g = write_arrays(directory / f"full_{F}_{symbols}_rev.sufr", rtext, rsa)
+    return f.fm(sample, threads, text=True), g.fm(0, threads), f, g
+
+
+@functools.lru_cache(maxsize=None)
+def fm_batch(symbols: int = 8, seed: int = 11):
+    """(queries, pure-zero queries).  About 400 queries: reads of 12 to 200 bytes cut from the region at 2 % substitutions, 40
+    of them over the middle byte; the region's first and last 16 / 40 / 150 bytes, with and without the $; 0^k region[:j] for
+    ZERO_PREFIXES, plain and with the region's part substituted behind its first byte (so every piece that occurs and is all
+    zeros can be extended to the right, and no SMEM is a pure-zero string; j > 3 keeps a non-zero byte matched at d = 3, so a
+    window touches the region); $, %, N x 5, A x 30, the empty query; a 900-byte prefix of the planted segment.  The pure-zero
+    queries 0^1, 0^5, 0^100 have ranges that are analytic, [0, F - k + 1), not the twin's plus a shift: a list of their own."""
+    rng = np.random.default_rng(seed)
+    text = full_region(symbols).text.tobytes()
+    seg = text[SEG_AT[0]:SEG_AT[0] + SEG_LEN]
+    qs = [seg[:900], b"A" * 30, b"", b"$", b"%", b"N" * 5]
+    for _ in range(320):
+        length = int(rng.integers(12, 201))
+        at = int(rng.integers(0, R - length + 1))
+        qs.append(_substitute(rng, text[at:at + length]))
+    for _ in range(40):                                                                     # over the boundary byte
+        length = int(rng.integers(20, 201))
+        at = MID - int(rng.integers(1, length - 1))
+        qs.append(_substitute(rng, text[at:at + length]))
+    for length in (16, 40, 150):                                                            # the ends of the region
+        qs += [text[:length], text[R - length:], text[R - length:R - 1]]
+    for k, j in ZERO_PREFIXES:
+        assert k <= 100 and j > 3
+        qs += [bytes(k) + text[:j], bytes(k) + text[:1] + _substitute(rng, text[1:j], 0.05)]
+    assert max(len(q) for q in qs) <= MAX_QUERY < TWIN_FILLER
+    return tuple(qs), (bytes(1), bytes(5), bytes(100))
+
+
+def fm_extract_requests(F: int, n: int):
+    """(starts, ends) of the fixed extract requests, relative to F and n: across F, 1000 bytes over the middle, over the end of
+    the text, behind it, an empty one, the first 64 bytes, 100 bytes deep in the filler, 3000 bytes inside the region, and
+    where the text has them the 100 bytes around position 2^31"""
+    req = [(F - 50, F + 50), (F + MID - 500, F + MID + 500), (n - 5, n + 5), (n + 3, n + 9), (F + 10, F + 10), (0, 64),
+           (F // 2, F // 2 + 100), (F + 5_000, F + 8_000)]
+    if n > (1 << 31) + 50:
+        req.append(((1 << 31) - 50, (1 << 31) + 50))
+    return np.array([a for a, _ in req], dtype=np.uint64), np.array([b for _, b in req], dtype=np.uint64)
+
+
+FM_PARTS = ("info", "search", "locate", "approx", "ms", "smems", "extract")
+
+
+def fm_answers(fwd, rev, shift: int, F: int, symbols: int = 8, parts=FM_PARTS, threads: int = 0) -> dict:
+    """Every operation on the pair (fwd: the index of T = 0x00^F region with text samples, rev: that of the reversed T) as plain
+    lists, for host FmIndex objects and for anything with their methods (tests/test_gpu_fm_high_positions.py wraps a
+    DeviceFmIndex).  `shift` is taken off every text position and off both ends of every rank range that is not empty; the
+    empty answer (0, 0) stays.  What is analytic is asserted here and not returned: the range of the empty query, [0, n);
+    those of the pure-zero queries, [0, F - k + 1); the positions of the ranks [0, 3); every extracted byte."""
+    queries, zeros = fm_batch(symbols)
+    queries = list(queries)
+    qb, off = pack_queries(queries)
+    kw = {"threads": threads} if threads else {}
+    n = F + R
+    reg = full_region(symbols)
+    out = {}
+
+    def ranges(lo, hi):
+        lo, hi = np.asarray(lo).astype(np.int64), np.asarray(hi).astype(np.int64)
+        some = hi > lo
+        return np.where(some, lo - shift, lo), np.where(some, hi - shift, hi)
+
+    if "info" in parts:
+        info = fwd.info
+        assert info["ranks"] == n == rev.info["ranks"]
+        out["info"] = [info["symbols"], info["sample"], info["end_byte"], info["ranks"] - shift]
+    lo = hi = None
+    if {"search", "locate"} & set(parts):
+        lo, hi = (np.asarray(a).astype(np.int64) for a in fwd.search_batch(queries, **kw))
+        empty = queries.index(b"")
+        assert (int(lo[empty]), int(hi[empty])) == (0, n), "the empty query"
+        lo[empty] = hi[empty] = 0                                    # (n ranks: not located)
+        zlo, zhi = fwd.search_batch(list(zeros), **kw)
+        assert _ints(zlo) == [0] * len(zeros) and _ints(zhi) == [F - len(z) + 1 for z in zeros], ("pure-zero queries", _ints(zlo), _ints(zhi))
+        out["search"] = [a.tolist() for a in ranges(lo, hi)]
+    if "locate" in parts:
+        for max_hits in FM_LOCATE_HITS:
+            o, pos = fwd.locate_ranges(lo.astype(np.uint64), hi.astype(np.uint64), max_hits, **kw)
+            out[f"locate max_hits={max_hits}"] = [_ints(o), _ints(pos, shift)]
+        elo, ehi = np.array([0, F - 40, n - 3], dtype=np.uint64), np.array([3, F + 40, n], dtype=np.uint64)
+        o, pos = fwd.locate_ranges(elo, ehi, 0, **kw)
+        assert _ints(o) == [0, 3, 83, 86] and _ints(pos[:3]) == [0, 1, 2], "the ranks [0, 3) are the positions [0, 3)"
+        out["locate of explicit ranges"] = _ints(pos[3:], shift)
+    if "approx" in parts:
+        for d, both in FM_APPROX_COMBOS:
+            keep = [i for i, q in enumerate(queries) if len(q) > d]
+            sqb, soff = pack_queries([queries[i] for i in keep])
+            qi, st, pos, mm = fwd.approx_arrays(sqb, soff, d, both, **kw)
+            out[f"approx d={d} both={both}"] = [np.asarray(keep)[_ints(qi)].tolist() if len(qi) else [], _ints(st), _ints(pos, shift), _ints(mm)]
+    if "ms" in parts:
+        out["matching statistics"] = _ints(np.concatenate(fwd.matching_stats(queries, rev, **kw)))
+    if "smems" in parts:
+        for min_len in FM_SMEM_MIN_LENS:
+            qi, qo, ln, slo, shi = (np.asarray(a).astype(np.int64) for a in fwd.smem_arrays(qb, off, rev, min_len, **kw))
+            assert all(any(queries[i][o:o + l]) for i, o, l in zip(qi.tolist(), qo.tolist(), ln.tolist())), "an SMEM that is all zeros"
+            assert (shi > slo).all()
+            o, pos = fwd.locate_ranges(slo.astype(np.uint64), shi.astype(np.uint64), 0, **kw)
+            out[f"smems min_len={min_len}"] = [_ints(qi), _ints(qo), _ints(ln), _ints(slo, shift), _ints(shi, shift), _ints(o), _ints(pos, shift)]
+    if "extract" in parts:
+        starts, ends = fm_extract_requests(F, n)
+        o, data = fwd.extract_ranges(starts, ends, **kw)
+        o, data = _ints(o), np.asarray(data)
+        got = [data[o[i]:o[i + 1]] for i in range(starts.size)]
+        for (a, b), g in zip(zip(starts.tolist(), ends.tolist()), got):
+            a, b = min(a, n), min(b, n)
+            want = np.concatenate([np.zeros(max(min(b, F) - a, 0), dtype=np.uint8), reg.text[max(a, F) - F:max(b, F) - F]])
+            assert g.size == b - a and np.array_equal(g, want), f"extract [{a}, {b}) is not the text"
+        out["extract"] = [g.tolist() for g in got[:8]]               # (the ninth is not in the twin: held to the text above)
+    return out
+
+
+def assert_fm_witness_is_not_empty(want: dict, symbols: int = 8) -> dict:
+    """What keeps a comparison of the FM-index answers from being empty, decided by the twin's answers alone.  Rank F + r of the
+    region's r-th byte and the byte's position are both 4096 + r on the twin, so the boundary rank and the boundary position
+    are the twin's 4096 + MID.  Returns the counts it looked at."""
+    twin = FULL_GEOMETRIES["twin"]
+    B, F, q = twin.boundary, twin.filler, FM_SAMPLE
+    queries = fm_batch(symbols)[0]
+    lens = np.array([len(x) for x in queries], dtype=np.int64)
+    seen = {}
+
+    def sides(name, values):
+        v = np.asarray(values, dtype=np.int64)
+        seen[name + " below the boundary"], seen[name + " above the boundary"] = int(((v < B) & (v >= F)).sum()), int((v > B).sum())
+
+    lo, hi = (np.asarray(a, dtype=np.int64) for a in want["search"])
+    found = hi > lo
+    sides("search ranges", lo[found])
+    seen["queries not found"] = int((~found).sum())
+    seen["queries whose leading zeros are matched in the filler"] = int(sum(1 for i, x in enumerate(queries) if x[:1] == b"\0" and found[i] and lo[i] < F))
+    pos = np.asarray(want["locate max_hits=0"][1], dtype=np.int64)
+    sides("located positions", pos)
+    seen["located ranks q - 1 steps from their mark"] = int((pos % q == q - 1).sum())
+    seen["located ranks that are marked"] = int((pos % q == 0).sum())
+    for d, both in FM_APPROX_COMBOS:
+        qi, st, p, mm = (np.asarray(a, dtype=np.int64) for a in want[f"approx d={d} both={both}"])
+        tag = f"approx d={d} both={both} "
+        sides(tag + "positions", p)
+        seen[tag + "windows that hold the boundary byte"] = int(((p <= B) & (B < p + lens[qi])).sum())
+        for k in range(d + 1):
+            seen[tag + f"records with {k} mismatches"] = int((mm == k).sum())
+        for s in (0, 1) if both else (0,):
+            seen[tag + f"records on strand {s}"] = int((st == s).sum())
+    for min_len in FM_SMEM_MIN_LENS:
+        qi, qo, ln, slo, shi, o, p = (np.asarray(a, dtype=np.int64) for a in want[f"smems min_len={min_len}"])
+        tag = f"smems min_len={min_len} "
+        sides(tag + "ranges", slo)
+        sides(tag + "positions", p)
+        seen[tag + "occurrences that hold the boundary byte"] = int(((p <= B) & (B < p + np.repeat(ln, np.diff(o)))).sum())
+    starts, ends = fm_extract_requests(F, twin.n)
+    seen["extract requests over the boundary"] = int(((starts < B) & (ends > B + 1)).sum())
+    seen["extract requests over the end of the text (the chunk of text_kept[0], the cyclic row)"] = int(((starts < twin.n) & (ends >= twin.n)).sum())
+    seen["max ms"] = max(want["matching statistics"])
+    assert all(seen.values()) and seen["max ms"] >= 900, seen
     return seen

@@ -2,7 +2,9 @@
 argument).  The text on the device is one torch.zeros with the 40 000-byte region copied to its end, the suffix array is
 SA(region) + filler: as int32 it holds negative values at u32_across_2_31 and u32_top, as int64 values of 2^32 and more at
 u64_across_2_32.  The witness is always the host path on the 44 KB twin file (tests/test_query_high_positions.py holds the
-host to it at the same geometries); no case compares the device with itself, every comparison is exact."""
+host to it at the same geometries); no case compares the device with itself, every comparison is exact.  The BWT, its runs
+and LF run here too (they accept an index that leaves positions out); the FM-index does not, and has a module and a
+construction of its own: tests/test_gpu_fm_high_positions.py."""
 import ctypes as C
 import threading
 from types import SimpleNamespace
@@ -270,6 +272,34 @@ def test_the_python_wrappers_read_positions_at_the_index_width(placed, twin, que
     got[f"edit d={d} max_occ={occ} both={both} minima={minima} queries=all"] = [[h.query for h in hits], [h.strand for h in hits],
                                                                                [h.end - geo.shift for h in hits], [h.edits for h in hits]]
     compare(got, twin.want, geo.name + " (Python wrappers)", got.keys())
+
+
+@pytest.fixture(scope="module")
+def bwt_want(twin):
+    """the twin's BWT, runs and LF from the host path, held to numpy on the arrays and shown not to be empty"""
+    return hp.bwt_witness(twin.file)[0]
+
+
+@pytest.mark.parametrize("tile", [0, 256], ids=["default_tile", "tile_256"])
+def test_bwt_runs_and_lf(ctx, placed, bwt_want, tile):
+    """BWT[r] = T[SA[r] - 1] and first = SA[a] of the run records at positions that are negative as int32 or beyond 2^32:
+    everything but `first` is the twin's.  The capacity refusal of the runs writes nothing."""
+    ix, geo = placed.ix[False], placed.geo
+    ctx.set_bwt_tile(tile)
+    try:
+        got = hp.bwt_answers(lambda: tuple(t.cpu() for t in ix.bwt_device()),
+                             lambda min_len: tuple(t.cpu() for t in ix.bwt_runs_device(min_len)[:4]) + (ix.bwt_runs_device(min_len)[4],),
+                             lambda: _unsigned(ix.lf_device()), geo.shift)
+        compare(got, bwt_want, f"{geo.name} (tile {tile})")
+        assert ix.lf_device().dtype == (torch.int32 if geo.width == 4 else torch.int64)
+        z = len(bwt_want["bwt runs min_len=1"][0])
+        out = [torch.full((z,), -1, dtype=torch.int64, device="cuda") for _ in range(4)]
+        total = C.c_uint64(0)
+        rc = sufr_amd.lib().sufr_hip_bwt_runs_device(ctx.handle, ix._h, 1, z - 1, *(o.data_ptr() for o in out), C.byref(total), None)
+        ctx.synchronize()
+        assert rc == -5 and total.value == z and all(bool((o == -1).all()) for o in out)
+    finally:
+        ctx.set_bwt_tile(0)
 
 
 def _all_zero(t: torch.Tensor) -> bool:

@@ -13,7 +13,14 @@ The sequence counts and the k-common profile (include/sufr_shared.h) use that re
 LPF and the LZ77 parse by position have n entries on the host as well (sufr_file_lpf: 17 to 34 GB; sufr_file_lz: two n-entry
 u64 vectors, 69 GB) and are left out; the decision of one rank that the host path and the kernels share (lz_rank of
 sufr_lz_scan.h) runs on the shifted arrays through tests/lz_shim.cpp, and tests/test_gpu_lz_shared_high_positions.py holds
-the device to the same witness."""
+the device to the same witness.
+
+The BWT, its runs and LF (include/sufr_bwt.h) have s-sized outputs and run on the three sparse files and through `sufr bwt`.
+The FM-index refuses an index that leaves positions out, so its cases index the filler (T = 0x00^F region, whose suffix array
+is known without a sort): the two suffix array formulas against a sort at small F, the host pair at F = 4096 against numpy and
+the search on text and suffix array, and the host pair at F = 2^20 + 17 against the pair at 4096.  A host build at the large
+geometries needs a 17 to 34 GB suffix array in a file that cannot be sparse; tests/test_gpu_fm_high_positions.py builds on the
+device and runs the host query code on the downloaded index."""
 import subprocess
 
 import numpy as np
@@ -303,3 +310,137 @@ def test_lpf_rank_decisions_at_shifted_positions(shim, repeat_files, lz_shared_w
         shim.shim_lz_rank_all(sa.ctypes.data, up.ctypes.data, lcp.ctypes.data, up_lcp.ctypes.data, sa.size, room.ctypes.data, lpf.ctypes.data, src.ctypes.data)
         assert np.array_equal(lpf.astype(np.int64), want_lpf), name
         assert np.array_equal(np.where(src == LZ_NONE, -1, src.astype(np.int64)), want_src), name
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the BWT, its runs and LF (include/sufr_bwt.h): the plain region, s-sized outputs
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def bwt_witness(files):
+    """the twin's BWT answers, held to numpy on the arrays and shown not to be empty, and the counts"""
+    with hp.open_checked(files["twin"][0], GEOMETRIES["twin"]) as f:
+        return hp.bwt_witness(f)
+
+
+def test_the_bwt_witness_equals_numpy_and_its_counts_are_pinned(bwt_witness):
+    """(asserted in the fixture, from the twin alone)  The counts of the committed region are pinned."""
+    want, counts = bwt_witness
+    print(counts)
+    assert counts["bwt bytes 0x00"] == 1 and counts["bwt bytes %"] == 2 and counts["bwt bytes N"] == 1
+    assert min(v for k, v in counts.items() if k.startswith("runs min_len=1")) > 10_000
+    assert min(v for k, v in counts.items() if k.startswith("runs min_len=8")) >= 1
+    assert len(want["lf"]) == hp.region().sa.size and sorted(want["lf"]) != want["lf"]
+
+
+@pytest.mark.parametrize("name", LARGE)
+def test_host_bwt_runs_and_lf_equal_the_twin(files, bwt_witness, name):
+    """BWT[r] = T[SA[r] - 1] and first = SA[a] at positions that are negative as int32 or beyond 2^32; everything but `first`
+    is the twin's"""
+    geo = GEOMETRIES[name]
+    path = sparse_or_skip(files, name)
+    with hp.open_checked(path, geo) as f:
+        for threads in (1, 0):
+            hp.compare(hp.host_bwt_answers(f, geo.shift, threads), bwt_witness[0], f"{name} (threads={threads})")
+
+
+def _bwt_lines(stdout: str, shift: int):
+    """`sufr bwt --runs` output: (count lines and # lines, run records).  A record is (rank, length, symbol, name, position),
+    the shift taken off the positions within the first sequence, which holds the filler (see _repeat_lines)."""
+    other, records = [], []
+    for line in stdout.splitlines():
+        w = line.split("\t")
+        if len(w) == 4:
+            nm, x = w[3].rsplit(":", 1)
+            records.append((w[0], w[1], w[2], nm, int(x) - shift if nm == hp.SEQ_NAMES[0] else int(x)))
+        else:
+            other.append(line)
+    return other, records
+
+
+def test_cli_bwt_runs_beyond_2_32(files):
+    geo = GEOMETRIES["u64_across_2_32"]
+    path = sparse_or_skip(files, geo.name)
+    starts = dict(zip(hp.SEQ_NAMES, geo.seq_starts))
+    for opts in (("--runs",), ("--runs", "--min-len", 8)):
+        got, want = run("bwt", *opts, path).stdout, run("bwt", *opts, files["twin"][0]).stdout
+        (g_other, g_rec), (w_other, w_rec) = _bwt_lines(got, geo.shift), _bwt_lines(want, 0)
+        assert g_other == w_other and len(w_other) > 4 and g_rec == w_rec and w_rec, opts
+        absolute = [starts[nm] + x for _, _, _, nm, x in _bwt_lines(got, 0)[1]]
+        assert min(absolute) < 1 << 32 < max(absolute), opts                    # records first seen on both sides of 2^32
+        assert {r[3] for r in w_rec} == set(hp.SEQ_NAMES) or len(opts) > 1
+    assert run("bwt", path).stdout == run("bwt", files["twin"][0]).stdout != ""
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the FM-index: the filler indexed, T = 0x00^F region (the construction: tests/high_positions.py)
+# ---------------------------------------------------------------------------------------------------------------------
+FM_BIG_FILLER = (1 << 20) + 17          # the region at odd places in blocks, mark words and tiles
+
+
+@pytest.mark.parametrize("F", [1, 7, 500])
+def test_the_suffix_array_formulas_equal_a_sort(F):
+    """SA(0^F region) and SA(its reversal) as the helper writes them down, against the order of the suffixes themselves"""
+    for symbols in (8, 9):
+        text, sa, rtext, rsa = hp.full_arrays_host(F, symbols)
+        hp.check_suffix_order(text.tobytes(), sa)
+        hp.check_suffix_order(rtext.tobytes(), rsa)
+
+
+@pytest.fixture(scope="module", params=[8, 9], ids=["8_symbols", "9_symbols"])
+def fm_twin(request, tmp_path_factory):
+    """the host pair on the twin, its files and its answers (the witness), shown not to be empty"""
+    from types import SimpleNamespace
+    symbols = request.param
+    d = tmp_path_factory.mktemp("fm_high_positions")
+    fwd, rev, f, g = hp.full_host_pair(d, hp.TWIN_FILLER, symbols)
+    fwd.pair_check(rev)
+    want = hp.fm_answers(fwd, rev, 0, hp.TWIN_FILLER, symbols)
+    counts = hp.assert_fm_witness_is_not_empty(want, symbols)
+    return SimpleNamespace(symbols=symbols, dir=d, fwd=fwd, rev=rev, f=f, g=g, want=want, counts=counts)
+
+
+def test_the_fm_witness_is_held_to_the_arrays_and_is_not_empty(fm_twin):
+    """the twin's search and locate against the numpy backward search of tests/test_fm_host.py, its matching statistics against
+    the search on text and suffix array of the same file; the counts of assert_fm_witness_is_not_empty are printed"""
+    from test_fm_host import Witness
+    print(fm_twin.symbols, fm_twin.counts)
+    info = fm_twin.fwd.info
+    assert info["symbols"] == fm_twin.symbols and info["width"] == 4 and info["samples"] == -(-info["ranks"] // hp.FM_SAMPLE)
+    assert (info["block"], info["stride"]) == ((96, 128) if fm_twin.symbols == 8 else (64, 128))
+    w = Witness(np.asarray(fm_twin.f.text), np.asarray(fm_twin.f.suffix_array))
+    queries = list(hp.fm_batch(fm_twin.symbols)[0])
+    lo, hi = fm_twin.fwd.search_batch(queries)
+    got = [w.search(q)[:2] for q in queries]
+    assert [g[0] for g in got] == lo.tolist() and [g[1] for g in got] == hi.tolist()
+    empty = queries.index(b"")
+    lo[empty] = hi[empty] = 0
+    off, pos = fm_twin.fwd.locate_ranges(lo, hi)
+    assert np.array_equal(pos, np.concatenate([w.sa[int(a):int(b)] for a, b in zip(lo, hi)]))
+    assert pos.tolist() == fm_twin.want["locate max_hits=0"][1]
+    # (the pair matches in the text without its end byte, include/sufr_fm_match.h: the four queries that hold a $ are left out)
+    ms = fm_twin.f.matching_statistics(queries)
+    bounds = np.concatenate([[0], np.cumsum([len(q) for q in queries])])
+    plain = [i for i, q in enumerate(queries) if b"$" not in q]
+    assert len(plain) == len(queries) - 4
+    for i in plain:
+        assert ms[i].astype(np.int64).tolist() == fm_twin.want["matching statistics"][bounds[i]:bounds[i + 1]], i
+
+
+def test_the_host_pair_at_an_odd_filler_equals_the_twin(fm_twin):
+    F = FM_BIG_FILLER
+    for threads in (1, 0):
+        fwd, rev, f, g = hp.full_host_pair(fm_twin.dir, F, fm_twin.symbols, threads=threads)
+        fwd.pair_check(rev)
+        hp.compare(hp.fm_answers(fwd, rev, F - hp.TWIN_FILLER, F, fm_twin.symbols, threads=threads), fm_twin.want, f"F = {F} (threads={threads})")
+        # the run records and LF of the full index: analytic in the filler, the twin's behind it
+        rank, length, symbol, first, st = f.bwt_runs(1, threads)
+        t_rank, t_length, t_symbol, t_first, t_st = fm_twin.f.bwt_runs(1)
+        assert (rank[:2].tolist(), length[:2].tolist(), symbol[:2].tolist(), first[:2].tolist()) == ([0, 1], [1, F - 1], [36, 0], [0, 1])
+        shift = F - hp.TWIN_FILLER
+        assert np.array_equal(rank[2:] - shift, t_rank[2:]) and np.array_equal(first[2:] - shift, t_first[2:])
+        assert np.array_equal(length[2:], t_length[2:]) and np.array_equal(symbol[2:], t_symbol[2:])
+        assert st == dict(t_st, longest=F - 1) and st["longest_rank"] == 1
+        lf, t_lf = f.lf(threads).astype(np.int64), fm_twin.f.lf().astype(np.int64)
+        assert lf[0] == F and np.array_equal(lf[1:F], np.arange(F - 1)) and np.array_equal(lf[F:] - shift, t_lf[hp.TWIN_FILLER:])
+        for x in (fwd, rev, f, g):
+            x.close()
