@@ -566,107 +566,40 @@ bool named_queries(const QueryArgs& a, std::vector<std::string>& names, std::vec
     return true;
 }
 
-// Search and, with `locate`, locate of a packed batch on a device FM-index: lo, hi (nq each), loff (nq + 1), pos (total
-// entries of w bytes).  false: an error, printed
-bool fm_device_search(sufr_hip_ctx* ctx, const sufr_hip_fm* fm, const std::string& bytes, const std::vector<uint64_t>& off, bool locate, uint64_t max_hits,
-                      int w, std::vector<uint64_t>& lo, std::vector<uint64_t>& hi, std::vector<uint64_t>& loff, std::vector<uint8_t>& pos, uint64_t& total)
-{
-    const uint64_t nq = off.size() - 1;
-    auto hits_of = [&](size_t i) { const uint64_t h = hi[i] - lo[i]; return max_hits && h > max_hits ? max_hits : h; };
-    int rc;
-    // one allocation: queries | offsets | lo | hi | the offsets of locate; the positions once their number is known
-    const uint64_t o_at = (bytes.size() + 7) / 8 * 8, lo_at = o_at + (nq + 1) * 8, hi_at = lo_at + nq * 8, l_at = hi_at + nq * 8;
-    uint8_t *d = nullptr, *d_pos = nullptr;
-    bool ok = hipMalloc((void**)&d, l_at + (nq + 1) * 8) == hipSuccess && (bytes.empty() || hipMemcpy(d, bytes.data(), bytes.size(), hipMemcpyHostToDevice) == hipSuccess) &&
-              hipMemcpy(d + o_at, off.data(), (nq + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
-    rc = ok ? sufr_hip_fm_search_batch_device(ctx, fm, d, d + o_at, nq, d + lo_at, d + hi_at) : SUFR_HIP_E_HIP;
-    if (!rc) rc = sufr_hip_synchronize(ctx);
-    ok = !rc && (!nq || (hipMemcpy(lo.data(), d + lo_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-                         hipMemcpy(hi.data(), d + hi_at, nq * 8, hipMemcpyDeviceToHost) == hipSuccess));
-    if (ok && locate) {
-        for (size_t i = 0; i < nq; i++) total += hits_of(i);
-        pos.resize((total + 1) * w);
-        ok = hipMalloc((void**)&d_pos, (total + 1) * w) == hipSuccess;
-        rc = ok ? sufr_hip_fm_locate_batch_device(ctx, fm, d + lo_at, d + hi_at, nq, max_hits, d + l_at, d_pos, total, &total) : SUFR_HIP_E_HIP;
-        if (!rc) rc = sufr_hip_synchronize(ctx);
-        ok = ok && !rc && hipMemcpy(loff.data(), d + l_at, (nq + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-             (!total || hipMemcpy(pos.data(), d_pos, total * w, hipMemcpyDeviceToHost) == hipSuccess);
-    }
-    if (!ok) fprintf(stderr, "Error: %s\n", rc ? sufr_hip_last_error(ctx) : "device memory for the query batch");
-    if (d_pos) (void)hipFree(d_pos);
-    if (d) (void)hipFree(d);
-    return ok;
-}
+// The named queries of a command packed into one batch: what QuerySession and FmSession search
+struct QueryBatch {
+    std::vector<std::string> names;
+    std::string bytes;                          // the queries, one after the other ...
+    std::vector<uint64_t> off;                  // ... query i is bytes [off[i], off[i + 1])
 
-// sufr fm: count, or with --locate locate, through an FM-index built from the file (include/sufr_fm.h): the lines are those
-// of `sufr count` / `sufr locate`, the path reads neither the text nor the suffix array once the index stands.
-int cmd_fm(const QueryArgs& a)
+    bool pack(const QueryArgs& a)
+    {
+        std::vector<std::string> seqs;
+        if (!named_queries(a, names, seqs)) return false;
+        off.assign(seqs.size() + 1, 0);
+        for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
+        return true;
+    }
+    const uint8_t* q() const { return (const uint8_t*)bytes.data(); }
+    uint64_t nq() const { return off.size() - 1; }
+};
+
+// call(cap, &total) until the records fit: `cap` first, the exact count when that is short.  The code of the last call
+template <typename Call>
+int until_fits(uint64_t cap, uint64_t& total, Call call)
 {
-    OpenFile f(a.file);
-    OutFile out;
-    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
-    sufr_file_meta m;
-    sufr_file_metadata(f, &m);
-    const char* why = m.len_suffixes != m.text_len || !m.text_len ? "the file leaves text positions out (every position must be indexed: --dna needs --allow-ambiguity)"
-                      : m.seed_mask_len                           ? "the file was built with a seed mask"
-                      : m.max_query_len                           ? "the file was built with a max_query_len"
-                                                                  : nullptr;
-    const char* twice = "the last byte of the text occurs more than once";
-    if (why) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), why); return 1; }
-    std::vector<std::string> names, queries;
-    if (!named_queries(a, names, queries)) return 1;
-    const uint64_t nq = queries.size(), sample = a.locate ? (a.sample ? a.sample : 1) : 0;
-    std::string bytes;
-    std::vector<uint64_t> off(nq + 1, 0), lo(nq, 0), hi(nq, 0), loff(nq + 1, 0), pos64;
-    for (size_t i = 0; i < nq; i++) { bytes += queries[i]; off[i + 1] = bytes.size(); }
-    const int w = m.index_width;
-    auto hits_of = [&](size_t i) { const uint64_t h = hi[i] - lo[i]; return a.max_hits && h > a.max_hits ? a.max_hits : h; };
-    uint64_t total = 0;
-    std::vector<uint8_t> pos;                   // the positions, w bytes each
-    if (a.device < 0) {
-        sufr_fm* fm = nullptr;
-        int rc = sufr_file_fm_build(f, sample, &fm, a.threads);
-        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : "the build failed"); return 1; }
-        rc = sufr_fm_search_batch(fm, (const uint8_t*)bytes.data(), off.data(), nq, lo.data(), hi.data(), a.threads);
-        if (!rc && a.locate) {
-            for (size_t i = 0; i < nq; i++) total += hits_of(i);
-            pos.resize((total + 1) * w);
-            rc = sufr_fm_locate_batch(fm, lo.data(), hi.data(), nq, a.max_hits, loff.data(), pos.data(), total, &total, a.threads);
-        }
-        sufr_fm_free(fm);
-        if (rc) { fprintf(stderr, "Error: the FM-index search failed (%d)\n", rc); return 1; }
-    } else {
-        DeviceIndex dev(a.device, f);
-        if (!dev.up()) { fprintf(stderr, "Error: %s\n", dev.error()); return 1; }
-        sufr_hip_fm* fm = nullptr;
-        int rc = sufr_hip_fm_build(dev.ctx, dev.ix, sample, &fm);
-        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : dev.error()); return 1; }
-        sufr_hip_index_free(dev.ix);            // text and suffix array leave the device: the FM-index answers alone
-        dev.ix = nullptr;
-        const bool ok = fm_device_search(dev.ctx, fm, bytes, off, a.locate, a.max_hits, w, lo, hi, loff, pos, total);
-        sufr_hip_fm_free(fm);
-        if (!ok) return 1;
+    for (;;) {
+        const int rc = call(cap, &total);
+        if (rc != SUFR_HIP_E_CAPACITY || total <= cap) return rc;
+        cap = total;
     }
-    if (!a.locate) {
-        for (size_t i = 0; i < nq; i++) fprintf(out.f, "%s %llu\n", names[i].c_str(), (unsigned long long)(hi[i] - lo[i]));
-        return 0;
-    }
-    print_located(f.f, out.f, a.abs, names, [&](size_t qi) { return loff[qi + 1] - loff[qi]; }, [&](size_t qi, uint64_t k) {
-        uint64_t p = 0;
-        memcpy(&p, pos.data() + (loff[qi] + k) * w, w);               // (little-endian entries of 4 or 8 bytes)
-        return p;
-    });
-    return 0;
 }
 
 // What match, mems, approx and edit hold while they run: the .sufr file, the output, the named queries packed into one
 // batch and, with --device, the index on that device.  Everything is released on every way out.
-struct QuerySession {
+struct QuerySession : QueryBatch {
     sufr_file* f = nullptr;
     OutFile out;
-    std::vector<std::string> names;
-    std::string bytes;                          // the queries, one after the other ...
-    std::vector<uint64_t> off;                  // ... query i is bytes [off[i], off[i + 1])
     std::optional<DeviceIndex> dev;
 
     bool open(const QueryArgs& a)
@@ -677,17 +610,12 @@ struct QuerySession {
     }
     bool load(const QueryArgs& a)
     {
-        std::vector<std::string> seqs;
-        if (!named_queries(a, names, seqs)) return false;
-        off.assign(seqs.size() + 1, 0);
-        for (size_t i = 0; i < seqs.size(); i++) { bytes += seqs[i]; off[i + 1] = bytes.size(); }
+        if (!pack(a)) return false;
         if (a.device < 0) return true;
         dev.emplace(a.device, f);
         if (!dev->up()) { fprintf(stderr, "Error: %s\n", dev->error()); return false; }
         return true;
     }
-    const uint8_t* q() const { return (const uint8_t*)bytes.data(); }
-    uint64_t nq() const { return off.size() - 1; }
     // the device is not held while the records are printed: the output may be large
     void release_device() { dev.reset(); }
     ~QuerySession() { release_device(); if (f) sufr_file_close(f); }
@@ -695,33 +623,29 @@ struct QuerySession {
     QuerySession(const QuerySession&) = delete;
     QuerySession& operator=(const QuerySession&) = delete;
 
-    // call(cap, &total) until the records fit: `cap` first, the exact count when that is short.  false: an error, printed
+    // ::until_fits with the report of a failure.  false: an error, printed
     // (`cmd` names the sub-command; ok_unsupported: an E_UNSUPPORTED whose text has it is no seed-mask refusal)
     template <typename Call>
     bool until_fits(const QueryArgs& a, const char* cmd, uint64_t cap, uint64_t& total, Call call, const char* ok_unsupported = nullptr)
     {
-        for (;;) {
-            const int rc = call(cap, &total);
-            if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-            if (rc == SUFR_HIP_E_UNSUPPORTED && !(ok_unsupported && dev && strstr(dev->error(), ok_unsupported))) {
-                fprintf(stderr, "Error: %s: %s does not support files built with a seed mask\n", a.file.c_str(), cmd);
-                return false;
-            }
-            if (rc != 0) { fprintf(stderr, "Error: %s\n", dev ? dev->error() : (std::string(cmd) + " failed").c_str()); return false; }
-            return true;
+        const int rc = ::until_fits(cap, total, call);
+        if (rc == SUFR_HIP_E_UNSUPPORTED && !(ok_unsupported && dev && strstr(dev->error(), ok_unsupported))) {
+            fprintf(stderr, "Error: %s: %s does not support files built with a seed mask\n", a.file.c_str(), cmd);
+            return false;
         }
+        if (rc != 0) { fprintf(stderr, "Error: %s\n", dev ? dev->error() : (std::string(cmd) + " failed").c_str()); return false; }
+        return true;
     }
 };
 
-// position `at` of sequence i as seq:pos (0-based inside the sequence)
-std::string seq_pos(const sufr_file* f, uint64_t i, uint64_t at) { return std::string(sufr_file_sequence_name(f, i)) + ":" + std::to_string(at); }
-
-// a text position as seq:pos, or absolute with --abs
-std::string place(const sufr_file* f, bool abs, uint64_t p)
+// a text position as seq:pos (0-based inside the sequence), or absolute with --abs; the sequences are those of an open
+// .sufr file or a SeqTable
+template <typename Seqs>
+std::string place(const Seqs& t, bool abs, uint64_t p)
 {
     if (abs) return std::to_string(p);
-    const uint64_t i = sufr_file_sequence_of(f, p);
-    return seq_pos(f, i, p - sufr_file_sequence_start(f, i));
+    const uint64_t i = seq_of(t, p);
+    return std::string(seq_name(t, i)) + ":" + std::to_string(p - seq_start(t, i));
 }
 
 // The lines of `sufr match` for `total` SMEM records: name, offset, length, count, positions.  positions(t) are the text
@@ -837,209 +761,245 @@ int cmd_approx(const QueryArgs& a)
     return 0;
 }
 
-// sufr fm --mismatches: the windows of the text within D mismatches of a query by backtracking on the
-// FM-index, which is all the search reads; the lines of `sufr approx` in (query, strand, leaf, rank) order.  The file stays
-// open for the sequence names of the output.
-int cmd_fm_approx(const QueryArgs& a)
-{
-    if (a.mismatches > SUFR_FM_APPROX_MAX_MISMATCHES) { fprintf(stderr, "Error: --mismatches must be at most %u\n", SUFR_FM_APPROX_MAX_MISMATCHES); return 1; }
-    if (!a.sample) { fprintf(stderr, "Error: --mismatches needs the sampled suffixes: -s must be at least 1\n"); return 1; }
-    QuerySession s;
-    if (!s.open(a)) return 1;
-    sufr_file_meta m;
-    sufr_file_metadata(s.f, &m);
-    const char* why = m.len_suffixes != m.text_len || !m.text_len ? "the file leaves text positions out (every position must be indexed: --dna needs --allow-ambiguity)"
-                      : m.seed_mask_len                           ? "the file was built with a seed mask"
-                      : m.max_query_len                           ? "the file was built with a max_query_len"
-                                                                  : nullptr;
-    const char* twice = "the last byte of the text occurs more than once";
-    if (why) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), why); return 1; }
-    if (!s.load(a)) return 1;
-    const uint32_t flags = a.both_strands ? SUFR_FM_APPROX_BOTH_STRANDS : 0, d = (uint32_t)a.mismatches;
-    sufr_fm* fm = nullptr;
-    sufr_hip_fm* dfm = nullptr;
-    if (s.dev) {
-        const int rc = sufr_hip_fm_build(s.dev->ctx, s.dev->ix, a.sample, &dfm);
-        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : s.dev->error()); return 1; }
-        sufr_hip_index_free(s.dev->ix);         // text and suffix array leave the device: the FM-index answers alone
-        s.dev->ix = nullptr;
-    } else {
-        const int rc = sufr_file_fm_build(s.f, a.sample, &fm, a.threads);
-        if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : "the build failed"); return 1; }
+// What `sufr fm` holds while it runs (DESIGN.md sections 23 - 26): the output, the named queries packed into one batch, one
+// FM-index or the pair of --smems (that of the text and that of the reversed text), the sequences of the text and, with
+// --device, the context and every device allocation.  An index comes from an index file or is built from a .sufr, which is
+// closed again at once: the index answers alone.  Everything is released on every way out.
+struct FmSession : QueryBatch {
+    struct Index {
+        sufr_fm* host = nullptr;                // loaded, built on the host, or downloaded for --save
+        sufr_hip_fm* dev = nullptr;             // with --device: uploaded or built there; it answers when it is there
+        sufr_fm_info info{};
+        sufr_fm_text_info text{};
+    };
+    const int device, threads;
+    const bool pair;                            // --smems: the library checks the files and names all it asks in one text
+    OutFile out;
+    sufr_hip_ctx* ctx = nullptr;                // made by the first step that needs the device
+    SeqTable seqs;
+    Index ix[2];
+    std::vector<void*> allocations;
+    std::vector<uint64_t> loff;                 // of the last locate: range i has the positions loff[i] .. loff[i + 1] ...
+    std::vector<uint8_t> pos;                   // ... of info.width bytes each
+
+    FmSession(const QueryArgs& a, bool pair) : device(a.device), threads(a.threads), pair(pair) {}
+    // the device is not held while the records are printed: the output may be large
+    void release()
+    {
+        for (void* p : allocations) (void)hipFree(p);
+        allocations.clear();
+        for (Index& x : ix) {
+            if (x.dev) sufr_hip_fm_free(x.dev);
+            if (x.host) sufr_fm_free(x.host);
+            x.dev = nullptr; x.host = nullptr;
+        }
+        if (ctx) sufr_hip_destroy(ctx);
+        ctx = nullptr;
     }
-    uint64_t total = 0;
-    std::vector<uint64_t> qi, pos;
-    std::vector<uint8_t> st, mm;
-    const bool ok = s.until_fits(a, "fm", 4 * s.nq() + 16, total, [&](uint64_t cap, uint64_t* tot) {
-        qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
-        return dfm ? sufr_hip_fm_approx(s.dev->ctx, dfm, s.q(), s.off.data(), s.nq(), d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), tot)
-                   : sufr_fm_approx(fm, s.q(), s.off.data(), s.nq(), d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), tot, a.threads);
-    });
-    sufr_hip_fm_free(dfm);
-    sufr_fm_free(fm);
-    s.release_device();
-    if (!ok) return 1;
-    for (uint64_t t = 0; t < total; t++)
-        fprintf(s.out.f, "%s\t%c\t%s\t%u\n", s.names[qi[t]].c_str(), st[t] ? '-' : '+', place(s.f, a.abs, pos[t]).c_str(), (unsigned)mm[t]);
-    return 0;
-}
+    ~FmSession() { release(); }
+    FmSession(const FmSession&) = delete;
+    FmSession& operator=(const FmSession&) = delete;
 
-// sufr fm with --save, --index or --extract (include/sufr_fm_text.h).  The index comes from a .sufr
-// file (built on the host, or on the GPU with --device) or from an index file (--index: loaded and verified; no .sufr is
-// opened, the sequence names are the file's); --save writes it; the queries are then answered by it alone, on the GPU with
-// --device (an index from a file is uploaded, one built there stays).  The lines are those of count, locate, approx
-// (--mismatches) and extract (--extract: the hits through locate, the bases through the FM extract).
-template <typename Seqs>
-std::string place_in(const Seqs& t, bool abs, uint64_t p)
-{
-    if (abs) return std::to_string(p);
-    const uint64_t i = seq_of(t, p);
-    return std::string(seq_name(t, i)) + ":" + std::to_string(p - seq_start(t, i));
-}
+    bool fail(const char* what) const { fprintf(stderr, "Error: %s\n", what); return false; }
+    bool open(const std::string& output) { return out.open(output) || fail((output + ": cannot create").c_str()); }
+    bool device_up() { return ctx || (ctx = sufr_hip_create(device)); }
+    const char* device_error() const { return sufr_hip_last_error(ctx); }      // (no context: the text of the failed create)
 
-int cmd_fm_index(const QueryArgs& a)
+    // Why a .sufr file gives no FM-index: by its metadata (nullptr: nothing against it), and for a build that refused
+    const char* refusal(const sufr_file_meta& m) const
+    {
+        return pair                                          ? nullptr
+               : m.len_suffixes != m.text_len || !m.text_len ? "the file leaves text positions out (every position must be indexed: --dna needs --allow-ambiguity)"
+               : m.seed_mask_len                             ? "the file was built with a seed mask"
+               : m.max_query_len                             ? "the file was built with a max_query_len"
+                                                             : nullptr;
+    }
+    const char* refusal() const
+    {
+        return pair ? "every position must be indexed, without seed mask and max_query_len, and the last byte must occur once"
+                    : "the last byte of the text occurs more than once";
+    }
+
+    // Index `slot` from `path`: an index file (loaded and verified; with --device uploaded), or a .sufr file whose index is
+    // built at `sample` with `flags`, on the device with --device, and written to `save` unless that is empty.  want_names:
+    // its sequences are those of the output.  false: an error, printed
+    bool take(const std::string& path, bool index_file, uint64_t sample, uint32_t flags, bool want_names, const std::string& save, int slot)
+    {
+        Index& x = ix[slot];
+        char err[512] = {0};
+        if (index_file) {
+            if (sufr_fm_load(path.c_str(), &x.host, threads, err, sizeof err) != 0) return fail(err);
+            if (device >= 0 && (!device_up() || sufr_hip_fm_upload(ctx, x.host, &x.dev) != 0)) return fail(device_error());
+            for (uint64_t i = 0; want_names && i < sufr_fm_num_sequences(x.host); i++) {
+                seqs.starts.push_back(sufr_fm_sequence_start(x.host, i));
+                seqs.names.push_back(sufr_fm_sequence_name(x.host, i));
+            }
+        } else {
+            OpenFile f(path);
+            sufr_file_meta m;
+            sufr_file_metadata(f, &m);
+            const char* why = refusal(m);
+            if (!why && device >= 0) {
+                sufr_hip_index* text_sa = nullptr;
+                if (!device_up() || sufr_hip_index_load(ctx, f, &text_sa) != 0) return fail(device_error());
+                const int rc = sufr_hip_fm_build_flags(ctx, text_sa, sample, flags, &x.dev);
+                sufr_hip_index_free(text_sa);   // text and suffix array leave the device: the FM-index answers alone
+                if (rc) why = rc == SUFR_HIP_E_UNSUPPORTED && !pair ? refusal() : device_error();
+                else if (!save.empty() && sufr_hip_fm_download(ctx, x.dev, &x.host) != 0) return fail(device_error());
+            } else if (!why) {
+                const int rc = sufr_file_fm_build_flags(f, sample, flags, &x.host, threads);
+                if (rc) why = rc == SUFR_HIP_E_UNSUPPORTED ? refusal() : "the build failed";
+            }
+            if (why) { fprintf(stderr, "Error: %s: no FM-index: %s\n", path.c_str(), why); return false; }
+            for (uint64_t i = 0; want_names && i < m.num_sequences; i++) {
+                seqs.starts.push_back(sufr_file_sequence_start(f, i));
+                seqs.names.push_back(sufr_file_sequence_name(f, i));
+            }
+            if (!save.empty() && sufr_fm_save(x.host, save.c_str(), f, err, sizeof err) != 0) return fail(err);
+        }
+        if (x.dev ? sufr_hip_fm_get_info(x.dev, &x.info) || sufr_hip_fm_get_text_info(x.dev, &x.text)
+                  : sufr_fm_get_info(x.host, &x.info) || sufr_fm_get_text_info(x.host, &x.text))
+            return fail("reading the info of the FM-index failed");
+        return true;
+    }
+
+    // device memory, released with the session.  nullptr: an error, printed
+    uint8_t* alloc(uint64_t bytes)
+    {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { fail("device memory for the batch"); return nullptr; }
+        allocations.push_back(p);
+        return (uint8_t*)p;
+    }
+    static bool copy(void* to, const void* from, uint64_t bytes, hipMemcpyKind kind) { return !bytes || hipMemcpy(to, from, bytes, kind) == hipSuccess; }
+    bool copied(bool ok) const { return ok || fail("copying the batch"); }
+    // after a device call: waits for it.  false: an error, printed
+    bool done(int rc) const { return !(rc ? rc : sufr_hip_synchronize(ctx)) || fail(device_error()); }
+
+    // The rank range of every query in index 0: lo, hi.  false: an error, printed
+    bool search(std::vector<uint64_t>& lo, std::vector<uint64_t>& hi)
+    {
+        const uint64_t n = nq();
+        lo.assign(n, 0); hi.assign(n, 0);
+        if (!ix[0].dev) {
+            const int rc = sufr_fm_search_batch(ix[0].host, q(), off.data(), n, lo.data(), hi.data(), threads);
+            if (rc) fprintf(stderr, "Error: the FM-index search failed (%d)\n", rc);
+            return !rc;
+        }
+        // one allocation: queries | offsets | lo | hi
+        const uint64_t o_at = (bytes.size() + 7) / 8 * 8, lo_at = o_at + (n + 1) * 8, hi_at = lo_at + n * 8;
+        uint8_t* d = alloc(hi_at + n * 8);
+        if (!d) return false;
+        return copied(copy(d, bytes.data(), bytes.size(), hipMemcpyHostToDevice) && copy(d + o_at, off.data(), (n + 1) * 8, hipMemcpyHostToDevice)) &&
+               done(sufr_hip_fm_search_batch_device(ctx, ix[0].dev, d, d + o_at, n, d + lo_at, d + hi_at)) &&
+               copied(copy(lo.data(), d + lo_at, n * 8, hipMemcpyDeviceToHost) && copy(hi.data(), d + hi_at, n * 8, hipMemcpyDeviceToHost));
+    }
+
+    // The text positions of the first `n` rank ranges lo[i] .. hi[i] in index 0, at most max_hits of each (0: all), in rank
+    // order: loff and pos.  false: an error, printed
+    bool locate(const std::vector<uint64_t>& lo, const std::vector<uint64_t>& hi, uint64_t n, uint64_t max_hits)
+    {
+        const uint64_t w = ix[0].info.width;
+        uint64_t total = 0;
+        for (uint64_t i = 0; i < n; i++) total += max_hits && hi[i] - lo[i] > max_hits ? max_hits : hi[i] - lo[i];
+        loff.assign(n + 1, 0);
+        pos.assign((total + 1) * w, 0);
+        if (!n) return true;
+        if (!ix[0].dev) {
+            const int rc = sufr_fm_locate_batch(ix[0].host, lo.data(), hi.data(), n, max_hits, loff.data(), pos.data(), total, &total, threads);
+            if (rc) fprintf(stderr, "Error: the FM-index locate failed (%d)\n", rc);
+            return !rc;
+        }
+        // one allocation: lo | hi | the offsets | the positions
+        const uint64_t hi_at = n * 8, l_at = 2 * n * 8, p_at = l_at + (n + 1) * 8;
+        uint8_t* d = alloc(p_at + (total + 1) * w);
+        if (!d) return false;
+        return copied(copy(d, lo.data(), n * 8, hipMemcpyHostToDevice) && copy(d + hi_at, hi.data(), n * 8, hipMemcpyHostToDevice)) &&
+               done(sufr_hip_fm_locate_batch_device(ctx, ix[0].dev, d, d + hi_at, n, max_hits, d + l_at, d + p_at, total, &total)) &&
+               copied(copy(loff.data(), d + l_at, (n + 1) * 8, hipMemcpyDeviceToHost) && copy(pos.data(), d + p_at, total * w, hipMemcpyDeviceToHost));
+    }
+    // position `at` of the last locate (little-endian entries of 4 or 8 bytes)
+    uint64_t position(uint64_t at) const
+    {
+        uint64_t p = 0;
+        memcpy(&p, pos.data() + at * ix[0].info.width, ix[0].info.width);
+        return p;
+    }
+
+    // call(cap, &total) until the records fit (::until_fits).  false: an error, printed
+    template <typename Call>
+    bool records(uint64_t cap, uint64_t& total, Call call)
+    {
+        return !::until_fits(cap, total, call) || fail(ctx ? device_error() : "the FM-index search failed");
+    }
+};
+
+// sufr fm (include/sufr_fm.h, sufr_fm_approx.h, sufr_fm_text.h; DESIGN.md sections 23 - 25): count, with --locate locate, with
+// --mismatches the windows within D mismatches by backtracking, with --extract the lines of extract (the hits through locate,
+// the bases read back from the BWT), through an FM-index alone.  The index is built from the .sufr file (on the GPU with
+// --device) or loaded from an index file (--index: no .sufr is opened, the sequence names are the file's; with --device it is
+// uploaded); --save writes it.  The lines are those of count, locate, approx (in (query, strand, leaf, rank) order) and extract.
+int cmd_fm(const QueryArgs& a)
 {
     if (a.fm_approx && a.mismatches > SUFR_FM_APPROX_MAX_MISMATCHES) { fprintf(stderr, "Error: --mismatches must be at most %u\n", SUFR_FM_APPROX_MAX_MISMATCHES); return 1; }
-    const bool from_file = !a.fm_index.empty(), want_text = a.fm_text || a.fm_extract;
-    const bool want_pos = a.locate || a.fm_approx || a.fm_extract || !a.fm_save.empty();
+    const bool want_text = a.fm_text || a.fm_extract, locate = a.locate || a.fm_extract;
     if (want_text && !a.sample) { fprintf(stderr, "Error: --text and --extract need the sampled suffixes: -s must be at least 1\n"); return 1; }
     if (a.fm_approx && !a.sample) { fprintf(stderr, "Error: --mismatches needs the sampled suffixes: -s must be at least 1\n"); return 1; }
-    OutFile out;
-    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
-    // what is released on every way out
-    struct Held {
-        sufr_file* f = nullptr;
-        sufr_fm* fm = nullptr;
-        sufr_hip_ctx* ctx = nullptr;
-        sufr_hip_index* ix = nullptr;
-        sufr_hip_fm* dfm = nullptr;
-        ~Held()
-        {
-            if (dfm) sufr_hip_fm_free(dfm);
-            if (ix) sufr_hip_index_free(ix);
-            if (ctx) sufr_hip_destroy(ctx);
-            if (fm) sufr_fm_free(fm);
-            if (f) sufr_file_close(f);
-        }
-    } h;
-    char err[512] = {0};
-    SeqTable seqs;
-    if (a.device >= 0 && !(h.ctx = sufr_hip_create(a.device))) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
-    if (from_file) {
-        if (sufr_fm_load(a.fm_index.c_str(), &h.fm, a.threads, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
-        if (h.ctx && sufr_hip_fm_upload(h.ctx, h.fm, &h.dfm) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return 1; }
-        for (uint64_t i = 0; i < sufr_fm_num_sequences(h.fm); i++) {
-            seqs.starts.push_back(sufr_fm_sequence_start(h.fm, i));
-            seqs.names.push_back(sufr_fm_sequence_name(h.fm, i));
-        }
-    } else {
-        h.f = open_or_die(a.file);
-        sufr_file_meta m;
-        sufr_file_metadata(h.f, &m);
-        const char* why = m.len_suffixes != m.text_len || !m.text_len ? "the file leaves text positions out (every position must be indexed: --dna needs --allow-ambiguity)"
-                          : m.seed_mask_len                           ? "the file was built with a seed mask"
-                          : m.max_query_len                           ? "the file was built with a max_query_len"
-                                                                      : nullptr;
-        const char* twice = "the last byte of the text occurs more than once";
-        if (why) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), why); return 1; }
-        const uint64_t sample = want_pos ? a.sample : 0;
-        const uint32_t flags = want_text ? SUFR_FM_TEXT : 0;
-        int rc;
-        if (h.ctx) {
-            if ((rc = sufr_hip_index_load(h.ctx, h.f, &h.ix)) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return 1; }
-            rc = sufr_hip_fm_build_flags(h.ctx, h.ix, sample, flags, &h.dfm);
-            if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : sufr_hip_last_error(h.ctx)); return 1; }
-            sufr_hip_index_free(h.ix);          // text and suffix array leave the device: the FM-index answers alone
-            h.ix = nullptr;
-            if (!a.fm_save.empty() && sufr_hip_fm_download(h.ctx, h.dfm, &h.fm) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return 1; }
-        } else {
-            rc = sufr_file_fm_build_flags(h.f, sample, flags, &h.fm, a.threads);
-            if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", a.file.c_str(), rc == SUFR_HIP_E_UNSUPPORTED ? twice : "the build failed"); return 1; }
-        }
-        for (uint64_t i = 0; i < m.num_sequences; i++) {
-            seqs.starts.push_back(sufr_file_sequence_start(h.f, i));
-            seqs.names.push_back(sufr_file_sequence_name(h.f, i));
-        }
-        if (!a.fm_save.empty() && sufr_fm_save(h.fm, a.fm_save.c_str(), h.f, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
-        sufr_file_close(h.f);                   // the index answers alone from here on
-        h.f = nullptr;
-    }
-    sufr_fm_info info;
-    sufr_fm_text_info tinfo;
-    if (h.dfm ? sufr_hip_fm_get_info(h.dfm, &info) || sufr_hip_fm_get_text_info(h.dfm, &tinfo) : sufr_fm_get_info(h.fm, &info) || sufr_fm_get_text_info(h.fm, &tinfo)) {
-        fprintf(stderr, "Error: reading the info of the FM-index failed\n");
-        return 1;
-    }
-    std::vector<std::string> names, queries;
-    if (!named_queries(a, names, queries)) return 1;
-    const uint64_t nq = queries.size();
+    // An index that only counts keeps no suffixes.  -s 0 with --locate alone has always meant 1; with --index, --save, --text
+    // or --extract it is taken as given, and an index without samples then refuses to locate
+    const bool as_given = !a.fm_index.empty() || !a.fm_save.empty() || want_text;
+    uint64_t sample = locate || a.fm_approx || !a.fm_save.empty() ? a.sample : 0;
+    if (a.locate && !sample && !as_given) sample = 1;
+    FmSession s(a, false);
+    if (!s.open(a.output) || !s.take(a.file, !a.fm_index.empty(), sample, want_text ? SUFR_FM_TEXT : 0, true, a.fm_save, 0) || !s.pack(a)) return 1;
+    const uint64_t nq = s.nq();
     if (!nq) return 0;                          // (--save alone)
-    if ((a.locate || a.fm_approx || a.fm_extract) && !info.sample) {
+    const FmSession::Index& x = s.ix[0];
+    if ((locate || a.fm_approx) && !x.info.sample) {
         fprintf(stderr, "Error: %s: the index was saved without samples (-s 0): it counts only\n", a.file.c_str());
         return 1;
     }
-    if (a.fm_extract && !tinfo.text_samples) {
+    if (a.fm_extract && !x.text.text_samples) {
         fprintf(stderr, "Error: %s: the index was saved without --text: it cannot give the text back\n", a.file.c_str());
         return 1;
     }
-    std::string bytes;
-    std::vector<uint64_t> off(nq + 1, 0);
-    for (size_t i = 0; i < nq; i++) { bytes += queries[i]; off[i + 1] = bytes.size(); }
-    const int w = (int)info.width;
     if (a.fm_approx) {
         const uint32_t flags = a.both_strands ? SUFR_FM_APPROX_BOTH_STRANDS : 0, d = (uint32_t)a.mismatches;
-        uint64_t total = 0, cap = 4 * nq + 16;
+        // records: room for four windows per query first, the exact count when that is short
+        uint64_t total = 0;
         std::vector<uint64_t> qi, pos;
         std::vector<uint8_t> st, mm;
-        for (;;) {
-            qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
-            const int rc = h.dfm ? sufr_hip_fm_approx(h.ctx, h.dfm, (const uint8_t*)bytes.data(), off.data(), nq, d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total)
-                                 : sufr_fm_approx(h.fm, (const uint8_t*)bytes.data(), off.data(), nq, d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), &total, a.threads);
-            if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-            if (rc) { fprintf(stderr, "Error: %s\n", h.dfm ? sufr_hip_last_error(h.ctx) : "the FM-index search failed"); return 1; }
-            break;
-        }
+        if (!s.records(4 * nq + 16, total, [&](uint64_t cap, uint64_t* tot) {
+                qi.resize(cap); pos.resize(cap); st.resize(cap); mm.resize(cap);
+                return x.dev ? sufr_hip_fm_approx(s.ctx, x.dev, s.q(), s.off.data(), nq, d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), tot)
+                             : sufr_fm_approx(x.host, s.q(), s.off.data(), nq, d, flags, cap, qi.data(), st.data(), pos.data(), mm.data(), tot, a.threads);
+            })) return 1;
+        s.release();
         for (uint64_t t = 0; t < total; t++)
-            fprintf(out.f, "%s\t%c\t%s\t%u\n", names[qi[t]].c_str(), st[t] ? '-' : '+', place_in(seqs, a.abs, pos[t]).c_str(), (unsigned)mm[t]);
+            fprintf(s.out.f, "%s\t%c\t%s\t%u\n", s.names[qi[t]].c_str(), st[t] ? '-' : '+', place(s.seqs, a.abs, pos[t]).c_str(), (unsigned)mm[t]);
         return 0;
     }
-    const bool locate = a.locate || a.fm_extract;
-    const uint64_t max_hits = a.fm_extract ? 0 : a.max_hits;
-    std::vector<uint64_t> lo(nq, 0), hi(nq, 0), loff(nq + 1, 0);
-    std::vector<uint8_t> pos;                   // the positions, w bytes each
-    uint64_t total = 0;
-    if (h.dfm) {
-        if (!fm_device_search(h.ctx, h.dfm, bytes, off, locate, max_hits, w, lo, hi, loff, pos, total)) return 1;
-    } else {
-        int rc = sufr_fm_search_batch(h.fm, (const uint8_t*)bytes.data(), off.data(), nq, lo.data(), hi.data(), a.threads);
-        if (!rc && locate) {
-            for (size_t i = 0; i < nq; i++) total += max_hits && hi[i] - lo[i] > max_hits ? max_hits : hi[i] - lo[i];
-            pos.resize((total + 1) * w);
-            rc = sufr_fm_locate_batch(h.fm, lo.data(), hi.data(), nq, max_hits, loff.data(), pos.data(), total, &total, a.threads);
-        }
-        if (rc) { fprintf(stderr, "Error: the FM-index search failed (%d)\n", rc); return 1; }
-    }
-    auto position = [&](uint64_t at) {
-        uint64_t p = 0;
-        memcpy(&p, pos.data() + at * w, w);                           // (little-endian entries of 4 or 8 bytes)
-        return p;
-    };
+    std::vector<uint64_t> lo, hi;
+    if (!s.search(lo, hi)) return 1;
     if (!locate) {
-        for (size_t i = 0; i < nq; i++) fprintf(out.f, "%s %llu\n", names[i].c_str(), (unsigned long long)(hi[i] - lo[i]));
+        for (size_t i = 0; i < nq; i++) fprintf(s.out.f, "%s %llu\n", s.names[i].c_str(), (unsigned long long)(hi[i] - lo[i]));
         return 0;
     }
+    if (!s.locate(lo, hi, nq, a.fm_extract ? 0 : a.max_hits)) return 1;
+    const std::vector<uint64_t>& loff = s.loff;
     if (!a.fm_extract) {
-        print_located(seqs, out.f, a.abs, names, [&](size_t qi) { return loff[qi + 1] - loff[qi]; }, [&](size_t qi, uint64_t k) { return position(loff[qi] + k); });
+        s.release();
+        print_located(s.seqs, s.out.f, a.abs, s.names, [&](size_t qi) { return loff[qi + 1] - loff[qi]; }, [&](size_t qi, uint64_t k) { return s.position(loff[qi] + k); });
         return 0;
     }
     // the lines of cmd_extract: the range of every hit, then all of them read back in one batch
-    const uint64_t n = info.ranks;
+    const uint64_t n = x.info.ranks, total = loff[nq];
     struct Line { uint64_t seq, cstart, cend, at; };
     std::vector<Line> lines(total);
     std::vector<uint64_t> starts(total), ends(total), boff(total + 1, 0);
     for (uint64_t t = 0; t < total; t++) {
-        const uint64_t sfx = position(t), i = seq_of(seqs, sfx), s0 = seq_start(seqs, i);
-        const uint64_t seq_end = i + 1 >= seqs.starts.size() ? n : seqs.starts[i + 1];
+        const uint64_t sfx = s.position(t), i = seq_of(s.seqs, sfx), s0 = seq_start(s.seqs, i);
+        const uint64_t seq_end = i + 1 >= s.seqs.starts.size() ? n : s.seqs.starts[i + 1];
         const uint64_t rel = sfx - s0, pre = a.has_prefix ? a.prefix_len : 0;
         const uint64_t cstart = rel > pre ? rel - pre : 0;
         uint64_t cend = a.has_suffix ? rel + a.suffix_len : seq_end;
@@ -1054,16 +1014,16 @@ int cmd_fm_index(const QueryArgs& a)
         nbytes += e - (starts[t] < e ? starts[t] : e);
     }
     std::vector<uint8_t> text(nbytes + 1);
-    const int rc = h.dfm ? sufr_hip_fm_extract_batch(h.ctx, h.dfm, starts.data(), ends.data(), total, boff.data(), text.data(), nbytes, &nbytes)
-                         : sufr_fm_extract_batch(h.fm, starts.data(), ends.data(), total, boff.data(), text.data(), nbytes, &nbytes, a.threads);
-    if (rc) { fprintf(stderr, "Error: %s\n", h.dfm ? sufr_hip_last_error(h.ctx) : "the FM-index extract failed"); return 1; }
+    const int rc = x.dev ? sufr_hip_fm_extract_batch(s.ctx, x.dev, starts.data(), ends.data(), total, boff.data(), text.data(), nbytes, &nbytes)
+                         : sufr_fm_extract_batch(x.host, starts.data(), ends.data(), total, boff.data(), text.data(), nbytes, &nbytes, a.threads);
+    if (rc) { s.fail(x.dev ? s.device_error() : "the FM-index extract failed"); return 1; }
     for (size_t qi = 0; qi < nq; qi++) {
-        if (loff[qi + 1] == loff[qi]) { fprintf(stderr, "%s not found\n", names[qi].c_str()); continue; }
+        if (loff[qi + 1] == loff[qi]) { fprintf(stderr, "%s not found\n", s.names[qi].c_str()); continue; }
         for (uint64_t t = loff[qi]; t < loff[qi + 1]; t++) {
-            fprintf(out.f, ">%s:%llu-%llu %s %llu\n", seq_name(seqs, lines[t].seq), (unsigned long long)lines[t].cstart, (unsigned long long)lines[t].cend,
-                    names[qi].c_str(), (unsigned long long)lines[t].at);
-            fwrite(text.data() + boff[t], 1, (size_t)(boff[t + 1] - boff[t]), out.f);
-            fputc('\n', out.f);
+            fprintf(s.out.f, ">%s:%llu-%llu %s %llu\n", seq_name(s.seqs, lines[t].seq), (unsigned long long)lines[t].cstart, (unsigned long long)lines[t].cend,
+                    s.names[qi].c_str(), (unsigned long long)lines[t].at);
+            fwrite(text.data() + boff[t], 1, (size_t)(boff[t + 1] - boff[t]), s.out.f);
+            fputc('\n', s.out.f);
         }
     }
     return 0;
@@ -1084,115 +1044,39 @@ int cmd_fm_write_reverse(const QueryArgs& a)
 // magic, or the .sufr of the reversed FASTA, whose index is built at sample 0), on the GPU with --device.
 int cmd_fm_smems(const QueryArgs& a)
 {
-    char err[512] = {0};
     if (!a.fm_smems) { fprintf(stderr, "Error: --reverse goes with --smems\n"); return 1; }
     if (a.fm_reverse.empty()) { fprintf(stderr, "Error: --smems needs --reverse REV: the .sufr or the FM-index of the reversed text (sufr fm --write-reverse)\n"); return 1; }
     if (a.fm_index.empty() && !a.sample) { fprintf(stderr, "Error: --smems prints positions, which need the sampled suffixes: -s must be at least 1\n"); return 1; }
     if (a.min_len == 0 || a.min_len > 0xFFFFFFFFull) { fprintf(stderr, "Error: --min-len must be between 1 and 2^32 - 1\n"); return 1; }
-    OutFile out;
-    if (!out.open(a.output)) { fprintf(stderr, "Error: %s: cannot create\n", a.output.c_str()); return 1; }
-    struct Held {
-        sufr_fm *fwd = nullptr, *rev = nullptr;
-        sufr_hip_ctx* ctx = nullptr;
-        sufr_hip_fm *dfwd = nullptr, *drev = nullptr;
-        ~Held()
-        {
-            if (dfwd) sufr_hip_fm_free(dfwd);
-            if (drev) sufr_hip_fm_free(drev);
-            if (ctx) sufr_hip_destroy(ctx);
-            if (fwd) sufr_fm_free(fwd);
-            if (rev) sufr_fm_free(rev);
-        }
-    } h;
-    if (a.device >= 0 && !(h.ctx = sufr_hip_create(a.device))) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(nullptr)); return 1; }
-    SeqTable seqs;
-    // one index of the pair: loaded from an index file, or built from a .sufr at `sample`, on the device with --device
-    auto take = [&](const std::string& path, bool index_file, uint64_t sample, bool names, sufr_fm** fm, sufr_hip_fm** dfm) {
-        if (index_file) {
-            if (sufr_fm_load(path.c_str(), fm, a.threads, err, sizeof err) != 0) { fprintf(stderr, "Error: %s\n", err); return false; }
-            if (h.ctx && sufr_hip_fm_upload(h.ctx, *fm, dfm) != 0) { fprintf(stderr, "Error: %s\n", sufr_hip_last_error(h.ctx)); return false; }
-            for (uint64_t i = 0; names && i < sufr_fm_num_sequences(*fm); i++) {
-                seqs.starts.push_back(sufr_fm_sequence_start(*fm, i));
-                seqs.names.push_back(sufr_fm_sequence_name(*fm, i));
-            }
-            return true;
-        }
-        OpenFile f(path);
-        int rc;
-        if (h.ctx) {
-            sufr_hip_index* ix = nullptr;
-            if ((rc = sufr_hip_index_load(h.ctx, f, &ix)) == 0) {
-                rc = sufr_hip_fm_build(h.ctx, ix, sample, dfm);
-                sufr_hip_index_free(ix);            // text and suffix array leave the device: the pair answers alone
-            }
-            if (rc) { fprintf(stderr, "Error: %s: no FM-index: %s\n", path.c_str(), sufr_hip_last_error(h.ctx)); return false; }
-        } else if ((rc = sufr_file_fm_build(f, sample, fm, a.threads)) != 0) {
-            fprintf(stderr, "Error: %s: no FM-index: %s\n", path.c_str(),
-                    rc == SUFR_HIP_E_UNSUPPORTED ? "every position must be indexed, without seed mask and max_query_len, and the last byte must occur once" : "the build failed");
-            return false;
-        }
-        sufr_file_meta m;
-        sufr_file_metadata(f, &m);
-        for (uint64_t i = 0; names && i < m.num_sequences; i++) {
-            seqs.starts.push_back(sufr_file_sequence_start(f, i));
-            seqs.names.push_back(sufr_file_sequence_name(f, i));
-        }
-        return true;
-    };
+    FmSession s(a, true);
+    if (!s.open(a.output)) return 1;
     // an index file is told from a .sufr by its magic
     char magic[8] = {0};
     if (FILE* fp = fopen(a.fm_reverse.c_str(), "rb")) { if (fread(magic, 1, 8, fp) != 8) magic[0] = 0; fclose(fp); }
     else { fprintf(stderr, "Error: %s: %s\n", a.fm_reverse.c_str(), strerror(errno)); return 1; }
-    if (!take(a.file, !a.fm_index.empty(), a.sample, true, &h.fwd, &h.dfwd) ||
-        !take(a.fm_reverse, !memcmp(magic, "SUFRFMI\0", 8), 0, false, &h.rev, &h.drev)) return 1;
-    sufr_fm_info info;
-    if (h.dfwd ? sufr_hip_fm_get_info(h.dfwd, &info) : sufr_fm_get_info(h.fwd, &info)) { fprintf(stderr, "Error: reading the info of the FM-index failed\n"); return 1; }
-    if (!info.sample) { fprintf(stderr, "Error: %s: the index was saved without samples (-s 0): it gives no positions\n", a.file.c_str()); return 1; }
-    if (!h.ctx && sufr_fm_pair_check(h.fwd, h.rev) != 0) { fprintf(stderr, "Error: %s: not an index of the reversed text\n", a.fm_reverse.c_str()); return 1; }
-    std::vector<std::string> names, queries;
-    if (!named_queries(a, names, queries)) return 1;
-    const uint64_t nq = queries.size();
-    std::string bytes;
-    std::vector<uint64_t> off(nq + 1, 0);
-    for (size_t i = 0; i < nq; i++) { bytes += queries[i]; off[i + 1] = bytes.size(); }
+    if (!s.take(a.file, !a.fm_index.empty(), a.sample, 0, true, "", 0) || !s.take(a.fm_reverse, !memcmp(magic, "SUFRFMI\0", 8), 0, 0, false, "", 1)) return 1;
+    const FmSession::Index &fwd = s.ix[0], &rev = s.ix[1];
+    if (!fwd.info.sample) { fprintf(stderr, "Error: %s: the index was saved without samples (-s 0): it gives no positions\n", a.file.c_str()); return 1; }
+    // (on the device the library checks the pair)
+    if (a.device < 0 && sufr_fm_pair_check(fwd.host, rev.host) != 0) { fprintf(stderr, "Error: %s: not an index of the reversed text\n", a.fm_reverse.c_str()); return 1; }
+    if (!s.pack(a)) return 1;
     // records: room for one SMEM per 8 query bytes first, the exact count when that is short
-    uint64_t total = 0, cap = bytes.size() / 8 + 16;
+    uint64_t total = 0;
     std::vector<uint64_t> qi, lo, hi;
     std::vector<uint32_t> qo, len;
-    for (;;) {
-        qi.resize(cap); lo.resize(cap); hi.resize(cap); qo.resize(cap); len.resize(cap);
-        const int rc = h.ctx ? sufr_hip_fm_smems(h.ctx, h.dfwd, h.drev, (const uint8_t*)bytes.data(), off.data(), nq, (uint32_t)a.min_len, cap, qi.data(), qo.data(),
-                                                 len.data(), lo.data(), hi.data(), &total)
-                             : sufr_fm_smems(h.fwd, h.rev, (const uint8_t*)bytes.data(), off.data(), nq, (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(),
-                                             lo.data(), hi.data(), &total, a.threads);
-        if (rc == SUFR_HIP_E_CAPACITY && total > cap) { cap = total; continue; }
-        if (rc) { fprintf(stderr, "Error: %s\n", h.ctx ? sufr_hip_last_error(h.ctx) : "the FM-index search failed"); return 1; }
-        break;
-    }
+    if (!s.records(s.bytes.size() / 8 + 16, total, [&](uint64_t cap, uint64_t* tot) {
+            qi.resize(cap); lo.resize(cap); hi.resize(cap); qo.resize(cap); len.resize(cap);
+            return fwd.dev ? sufr_hip_fm_smems(s.ctx, fwd.dev, rev.dev, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(),
+                                               lo.data(), hi.data(), tot)
+                           : sufr_fm_smems(fwd.host, rev.host, s.q(), s.off.data(), s.nq(), (uint32_t)a.min_len, cap, qi.data(), qo.data(), len.data(), lo.data(),
+                                           hi.data(), tot, a.threads);
+        })) return 1;
     // the positions of every SMEM: locate on the index of the text
-    const int w = (int)info.width;
-    uint64_t npos = 0;
-    for (uint64_t t = 0; t < total; t++) npos += a.max_hits && hi[t] - lo[t] > a.max_hits ? a.max_hits : hi[t] - lo[t];
-    std::vector<uint64_t> loff(total + 1, 0);
-    std::vector<uint8_t> pos((npos + 1) * w);
-    if (h.ctx && total) {
-        uint8_t* d = nullptr;
-        const uint64_t hi_at = total * 8, l_at = 2 * total * 8, p_at = l_at + (total + 1) * 8;
-        bool ok = hipMalloc((void**)&d, p_at + (npos + 1) * w) == hipSuccess && hipMemcpy(d, lo.data(), total * 8, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(d + hi_at, hi.data(), total * 8, hipMemcpyHostToDevice) == hipSuccess;
-        int rc = ok ? sufr_hip_fm_locate_batch_device(h.ctx, h.dfwd, d, d + hi_at, total, a.max_hits, d + l_at, d + p_at, npos, &npos) : SUFR_HIP_E_HIP;
-        if (!rc) rc = sufr_hip_synchronize(h.ctx);
-        ok = ok && !rc && hipMemcpy(loff.data(), d + l_at, (total + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-             (!npos || hipMemcpy(pos.data(), d + p_at, npos * w, hipMemcpyDeviceToHost) == hipSuccess);
-        if (d) (void)hipFree(d);
-        if (!ok) { fprintf(stderr, "Error: %s\n", rc ? sufr_hip_last_error(h.ctx) : "device memory for the positions"); return 1; }
-    } else if (total) {
-        const int rc = sufr_fm_locate_batch(h.fwd, lo.data(), hi.data(), total, a.max_hits, loff.data(), pos.data(), npos, &npos, a.threads);
-        if (rc) { fprintf(stderr, "Error: the FM-index locate failed (%d)\n", rc); return 1; }
-    }
-    print_smems(seqs, out.f, a.abs, names, total, qi, qo, len, lo, hi, [&](uint64_t t) {
-        std::vector<uint64_t> where(loff[t + 1] - loff[t], 0);
-        for (size_t k = 0; k < where.size(); k++) memcpy(&where[k], pos.data() + (loff[t] + k) * w, w);      // (little-endian entries of 4 or 8 bytes)
+    if (!s.locate(lo, hi, total, a.max_hits)) return 1;
+    s.release();
+    print_smems(s.seqs, s.out.f, a.abs, s.names, total, qi, qo, len, lo, hi, [&](uint64_t t) {
+        std::vector<uint64_t> where(s.loff[t + 1] - s.loff[t], 0);
+        for (size_t k = 0; k < where.size(); k++) where[k] = s.position(s.loff[t] + k);
         return where;
     });
     return 0;
@@ -1324,9 +1208,7 @@ int run_query(const std::string& cmd, int argc, char** argv, int first, int thre
         const int rc = cmd_fm_write_reverse(a);
         if (rc || !(a.fm_smems || !a.fm_reverse.empty())) return rc;
     }
-    if (is_fm && (a.fm_smems || !a.fm_reverse.empty())) return cmd_fm_smems(a);
-    if (is_fm && (!a.fm_index.empty() || !a.fm_save.empty() || a.fm_text || a.fm_extract)) return cmd_fm_index(a);
-    if (is_fm) return a.fm_approx ? cmd_fm_approx(a) : cmd_fm(a);
+    if (is_fm) return a.fm_smems || !a.fm_reverse.empty() ? cmd_fm_smems(a) : cmd_fm(a);
     if (is_edit) return cmd_edit(a);
     if (is_approx) return cmd_approx(a);
     if (is_mems) return cmd_mems(a);

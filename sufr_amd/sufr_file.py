@@ -88,6 +88,15 @@ def _split(flat: np.ndarray, off: np.ndarray) -> list:
 _SMEM_DTYPES = (np.uint64, np.uint32, np.uint32, np.uint64, np.uint64)     # query, query_offset, length, rank_lo, rank_hi
 
 
+def _smem_hits(nq: int, recs, positions_of) -> List[List[SmemHit]]:
+    """The SmemHit lists of `nq` queries from the five record columns; positions_of(t) are the positions of record t."""
+    qi, qo, ln, lo, hi = recs
+    out: List[List[SmemHit]] = [[] for _ in range(nq)]
+    for t in range(len(qi)):
+        out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), positions_of(t).copy()))
+    return out
+
+
 @dataclass
 class MemHit:                          # one MEM of a query (include/sufr_mem.h)
     query_offset: int                  # query[query_offset : query_offset + length] (strand 1: of the reverse complement) ...
@@ -274,6 +283,11 @@ def _as_bytes(q) -> bytes:
     return q.encode() if isinstance(q, str) else bytes(q)
 
 
+def _packed_arrays(qbytes, offsets) -> Tuple[np.ndarray, np.ndarray]:
+    """A packed batch as the host calls take it: contiguous uint8 bytes and uint64 offsets."""
+    return np.ascontiguousarray(qbytes, dtype=np.uint8), np.ascontiguousarray(offsets, dtype=np.uint64)
+
+
 class SufrFile:
     """An open version-6 .sufr file (SufrFile::read, sufr_file.rs:145-275).  The file is mapped, `low_memory` /
     `very_low_memory` of the reference only choose how much of it the reference copies to memory and are accepted
@@ -410,8 +424,7 @@ class SufrFile:
         return lo, hi
 
     def count(self, queries: Sequence, max_query_len: Optional[int] = None, low_memory: bool = False) -> List[CountResult]:
-        lo, hi = self.search_batch(queries, max_query_len)
-        return [CountResult(i, q if isinstance(q, str) else bytes(q).decode("latin-1"), int(hi[i] - lo[i])) for i, q in enumerate(queries)]
+        return _counts(queries, *self.search_batch(queries, max_query_len))
 
     def matching_statistics(self, queries: Sequence, threads: int = 0) -> List[np.ndarray]:
         """ms[j] per query (uint32 arrays): the longest prefix of query[j:] that starts an indexed suffix, capped at the
@@ -426,8 +439,7 @@ class SufrFile:
     def smem_arrays(self, qbytes: np.ndarray, offsets: np.ndarray, min_len: int = 20, cap: Optional[int] = None, threads: int = 0):
         """(query, query_offset, length, rank_lo, rank_hi) of every SMEM of a packed batch, in (query, offset) order.  With a
         `cap` too small the SufrHipError (code -5) carries the total in `.total`; without one the arrays are sized to fit."""
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         nq = len(offsets) - 1
         return _sized_to_fit(
             cap, int(offsets[-1] - offsets[0]) // 8 + 16, lambda c: [np.zeros(c, dtype=d) for d in _SMEM_DTYPES],
@@ -439,13 +451,9 @@ class SufrFile:
         """The SMEMs of every query (at least `min_len` long) with their rank ranges and up to `max_hits` positions each
         (0: all), on the host."""
         qb, off = pack_queries(queries)
-        qi, qo, ln, lo, hi = self.smem_arrays(qb, off, min_len, threads=threads)
-        sa = self.suffix_array
-        out: List[List[SmemHit]] = [[] for _ in queries]
-        for t in range(len(qi)):
-            a, b = int(lo[t]), int(hi[t])
-            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), a, b, sa[a:_hit_end(a, b, max_hits)].copy()))
-        return out
+        recs = self.smem_arrays(qb, off, min_len, threads=threads)
+        sa, lo, hi = self.suffix_array, recs[3], recs[4]
+        return _smem_hits(len(queries), recs, lambda t: sa[int(lo[t]):_hit_end(int(lo[t]), int(hi[t]), max_hits)])
 
     def write_reversed_fasta(self, path) -> None:
         """Writes the FASTA of the reversed text (include/sufr_fm_match.h): every sequence reversed and their order reversed,
@@ -461,8 +469,7 @@ class SufrFile:
         order.  With a `cap` too small the SufrHipError (code -5) carries the total in `.total`; without one the arrays are
         sized to fit."""
         from ._lib import MEM_BOTH_STRANDS
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         nq = len(offsets) - 1
         flags = MEM_BOTH_STRANDS if both_strands else 0
         return _sized_to_fit(
@@ -484,8 +491,7 @@ class SufrFile:
         of a packed batch, in (query, strand, piece, rank) order.  With a `cap` too small the SufrHipError (code -5) carries
         the total in `.total`; without one the arrays are sized to fit."""
         from ._lib import APPROX_BOTH_STRANDS
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         nq = len(offsets) - 1
         flags = APPROX_BOTH_STRANDS if both_strands else 0
         return _sized_to_fit(
@@ -509,8 +515,7 @@ class SufrFile:
         """(query, strand, end, edits) of every text position where a query of a packed batch ends with at most `max_edits`
         substitutions, insertions and deletions, sorted by (query, strand, end), each once.  With a `cap` too small the
         SufrHipError (code -5) carries the total in `.total`; without one the arrays are sized to fit."""
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         nq = len(offsets) - 1
         flags = _edit_flags(both_strands, local_minima)
         return _sized_to_fit(
@@ -534,8 +539,7 @@ class SufrFile:
         record t starts at start[t] and owns the BAM-encoded runs cigar[cigar_off[t]:cigar_off[t + 1]] (include/sufr_align.h).
         With a `cap` (of runs) too small the SufrHipError (code -5) carries the total in `.total`; without one the runs are
         sized to fit.  A record that is none of this batch and text is code -1, with its index in the message."""
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         recs = [np.ascontiguousarray(a, dtype=d) for a, d in zip((query, strand, end, edits), _APPROX_DTYPES)]
         nq, nr = len(offsets) - 1, len(recs[0])
         start = np.zeros(max(nr, 1), dtype=np.uint64)
@@ -843,8 +847,7 @@ class FmIndex:
     def search_packed(self, qbytes: np.ndarray, offsets: np.ndarray, threads: int = 0):
         nq = len(offsets) - 1
         lo, hi = np.zeros(nq, dtype=np.uint64), np.zeros(nq, dtype=np.uint64)
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         rc = lib().sufr_fm_search_batch(self._h, qbytes.ctypes.data, offsets.ctypes.data, nq, lo.ctypes.data, hi.ctypes.data, threads)
         if rc != 0:
             raise SufrHipError(rc, "sufr_fm_search_batch failed")
@@ -951,8 +954,7 @@ class FmIndex:
         of a query of a packed batch, as SufrFile.approx_arrays returns them, in (query, strand, leaf, rank) order.  With a `cap`
         too small the SufrHipError (code -5) carries the total in `.total`; without one the arrays are sized to fit."""
         from ._lib import FM_APPROX_BOTH_STRANDS
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         nq = len(offsets) - 1
         flags = FM_APPROX_BOTH_STRANDS if both_strands else 0
         return _sized_to_fit(
@@ -1009,8 +1011,7 @@ class FmIndex:
                     threads: int = 0):
         """(query, query_offset, length, rank_lo, rank_hi) of every SMEM of a packed batch, as SufrFile.smem_arrays returns
         them.  With a `cap` too small the SufrHipError (code -5) carries the total in `.total`."""
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         nq = len(offsets) - 1
         return _sized_to_fit(
             cap, int(offsets[-1] - offsets[0]) // 8 + 16, lambda c: [np.zeros(c, dtype=d) for d in _SMEM_DTYPES],
@@ -1021,12 +1022,9 @@ class FmIndex:
     def smems(self, queries: Sequence, rev: "FmIndex", min_len: int = 20, max_hits: int = 0, threads: int = 0) -> List[List[SmemHit]]:
         """The SMEMs of every query as SufrFile.smems returns them, the positions by locate_ranges."""
         qb, off = pack_queries(queries)
-        qi, qo, ln, lo, hi = self.smem_arrays(qb, off, rev, min_len, threads=threads)
-        po, pos = self.locate_ranges(lo, hi, max_hits, threads) if len(qi) else (np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=np.uint32))
-        out: List[List[SmemHit]] = [[] for _ in queries]
-        for t in range(len(qi)):
-            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[int(po[t]):int(po[t + 1])].copy()))
-        return out
+        recs = self.smem_arrays(qb, off, rev, min_len, threads=threads)
+        po, pos = self.locate_ranges(recs[3], recs[4], max_hits, threads) if len(recs[0]) else (np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=np.uint32))
+        return _smem_hits(len(queries), recs, lambda t: pos[int(po[t]):int(po[t + 1])])
 
     def matching_stats_steps(self, queries: Sequence, rev: "FmIndex", threads: int = 0) -> np.ndarray:
         """The steps of the whole-query walk of every query (uint64): what the statistics of a batch cost."""
@@ -1038,7 +1036,101 @@ class FmIndex:
         return steps[:len(off) - 1]
 
 
-class DeviceFmIndex:
+class _DeviceBatch:
+    """The batch path DeviceIndex and DeviceFmIndex share: an object with `ctx`, `_h` and `index_width` whose methods hand
+    over the library call and the handles it takes after the context (the index; for a pair call of the FM-index the index
+    and that of the reversed text).  Everything else about a call is the same on both."""
+
+    def _packed(self, queries: Sequence):
+        """The queries as a packed batch on the context's device: (uint8 bytes, int64 offsets)."""
+        import torch
+        qb, off = pack_queries(queries)
+        dev = torch.device("cuda", self.ctx.device)
+        return torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev)
+
+    @staticmethod
+    def _device_bytes(qbytes):
+        """The query bytes as the library takes them: a batch of empty queries still needs a device address."""
+        import torch
+        return qbytes if qbytes.numel() else torch.zeros(1, dtype=torch.uint8, device=qbytes.device)
+
+    def _device_records(self, cap, guess, device, dtypes, call):
+        """_sized_to_fit for torch outputs on `device`; the error text is the context's, the records are complete on return."""
+        import torch
+        out = _sized_to_fit(cap, guess, lambda c: [torch.empty(c, dtype=d, device=device) for d in dtypes], call,
+                            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
+        self.ctx.synchronize()
+        return out
+
+    def _search_device(self, call, qbytes, offsets, wait, *limit):
+        """search_device: `limit` is what the call takes between the batch and the outputs."""
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        lo = torch.empty(nq, dtype=torch.int64, device=qbytes.device)
+        hi = torch.empty(nq, dtype=torch.int64, device=qbytes.device)
+        self.ctx.check(call(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), nq, *limit, lo.data_ptr(), hi.data_ptr()))
+        if wait:
+            self.ctx.synchronize()
+        return lo, hi
+
+    def _locate_device(self, call, lo, hi, max_hits, capacity):
+        import torch
+        nq = lo.numel()
+        off = torch.empty(nq + 1, dtype=torch.int64, device=lo.device)
+        total = C.c_uint64(0)
+        torch.cuda.current_stream(lo.device).synchronize()
+        if capacity is None:                                   # size the output from the counts
+            cnt = hi - lo
+            capacity = int((cnt.clamp(max=max_hits) if max_hits else cnt).sum())
+        pos = torch.empty(max(capacity, 1), dtype=torch.int64 if self.index_width == 8 else torch.int32, device=lo.device)
+        self.ctx.check(call(self.ctx.handle, self._h, lo.data_ptr(), hi.data_ptr(), nq, max_hits, off.data_ptr(), pos.data_ptr(), capacity,
+                            C.byref(total)))
+        self.ctx.synchronize()
+        return off, pos[:total.value]
+
+    def _located(self, lo, hi, max_hits: int):
+        """locate_device on the host: (offsets, positions as unsigned values of the index's width)."""
+        o, p = self.locate_device(lo, hi, max_hits)
+        return o.cpu().numpy(), p.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
+
+    def _locate(self, n: int, lo, hi, max_hits: int) -> List[np.ndarray]:
+        o, p = self._located(lo, hi, max_hits)
+        return [p[o[i]:o[i + 1]] for i in range(n)]
+
+    def _matching_stats_device(self, call, handles, qbytes, offsets, wait):
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        qbytes = self._device_bytes(qbytes)
+        ms = torch.zeros(max(int(offsets[-1]) if nq >= 0 and offsets.numel() else 0, 1), dtype=torch.int32, device=qbytes.device)
+        self.ctx.check(call(self.ctx.handle, *handles, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0), ms.data_ptr()))
+        if wait:
+            self.ctx.synchronize()
+        return ms
+
+    def _smems_device(self, call, handles, qbytes, offsets, min_len, cap):
+        import torch
+        torch.cuda.current_stream(qbytes.device).synchronize()
+        nq = offsets.numel() - 1
+        dev = qbytes.device
+        qbytes = self._device_bytes(qbytes)
+        nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
+        ms = torch.empty(max(int(offsets[-1]) if nq > 0 else 0, 1), dtype=torch.int32, device=dev)
+        out = self._device_records(
+            cap, nbytes // 8 + 16, dev, (torch.int64, torch.int32, torch.int32, torch.int64, torch.int64),
+            lambda c, out, total: call(self.ctx.handle, *handles, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0), min_len, ms.data_ptr(), c,
+                                       *[t.data_ptr() for t in out], C.byref(total)))
+        self.last_ms = ms
+        return out
+
+    def _smems(self, nq: int, recs, max_hits: int) -> List[List[SmemHit]]:
+        """The SmemHit lists of device records, the positions through locate_device."""
+        po, pos = self._located(recs[3], recs[4], max_hits)
+        return _smem_hits(nq, [t.cpu().numpy() for t in recs], lambda t: pos[po[t]:po[t + 1]])
+
+
+class DeviceFmIndex(_DeviceBatch):
     """The FM-index of a DeviceIndex in HBM (DeviceIndex.fm_device; include/sufr_fm.h).  It owns everything it reads: the
     DeviceIndex may be closed and wrapped tensors overwritten.  The calls mirror DeviceIndex.search_device / locate_device."""
 
@@ -1063,39 +1155,12 @@ class DeviceFmIndex:
     def search_device(self, qbytes, offsets, wait: bool = True):
         """torch CUDA tensors in (uint8 bytes, int64 offsets), int64 CUDA tensors (lo, hi) out; see DeviceIndex.search_device
         for `wait` and the streams."""
-        import torch
-        torch.cuda.current_stream(qbytes.device).synchronize()
-        nq = offsets.numel() - 1
-        lo = torch.empty(nq, dtype=torch.int64, device=offsets.device)
-        hi = torch.empty(nq, dtype=torch.int64, device=offsets.device)
-        self.ctx.check(lib().sufr_hip_fm_search_batch_device(self.ctx.handle, self._h, DeviceIndex._device_bytes(qbytes).data_ptr(), offsets.data_ptr(),
-                                                            nq, lo.data_ptr(), hi.data_ptr()))
-        if wait:
-            self.ctx.synchronize()
-        return lo, hi
+        return self._search_device(lib().sufr_hip_fm_search_batch_device, self._device_bytes(qbytes), offsets, wait)
 
     def locate_device(self, lo, hi, max_hits: int = 0, capacity: Optional[int] = None):
         """(offsets int64[nq + 1], positions) on the device for rank ranges on the device, as DeviceIndex.locate_device returns
         them: int32 holding u32 values, or int64 for a 64-bit index.  Complete on return."""
-        import torch
-        nq = lo.numel()
-        off = torch.empty(nq + 1, dtype=torch.int64, device=lo.device)
-        total = C.c_uint64(0)
-        torch.cuda.current_stream(lo.device).synchronize()
-        if capacity is None:                                   # size the output from the counts
-            cnt = hi - lo
-            capacity = int((cnt.clamp(max=max_hits) if max_hits else cnt).sum())
-        pos = torch.empty(max(capacity, 1), dtype=torch.int64 if self.index_width == 8 else torch.int32, device=lo.device)
-        self.ctx.check(lib().sufr_hip_fm_locate_batch_device(self.ctx.handle, self._h, lo.data_ptr(), hi.data_ptr(), nq, max_hits, off.data_ptr(),
-                                                            pos.data_ptr(), capacity, C.byref(total)))
-        self.ctx.synchronize()
-        return off, pos[:total.value]
-
-    def _packed(self, queries: Sequence):
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        return torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev)
+        return self._locate_device(lib().sufr_hip_fm_locate_batch_device, lo, hi, max_hits, capacity)
 
     def search(self, queries: Sequence) -> Tuple[np.ndarray, np.ndarray]:
         """rank_lo, rank_hi (uint64 arrays; lo == hi == 0 where the query does not occur)."""
@@ -1165,15 +1230,12 @@ class DeviceFmIndex:
         torch.cuda.current_stream(qbytes.device).synchronize()
         nq = max(offsets.numel() - 1, 0)
         dev = qbytes.device
-        qbytes = DeviceIndex._device_bytes(qbytes)
+        qbytes = self._device_bytes(qbytes)
         flags = FM_APPROX_BOTH_STRANDS if both_strands else 0
-        out = _sized_to_fit(
-            cap, 4 * nq + 16, lambda c: [torch.empty(c, dtype=d, device=dev) for d in (torch.int64, torch.uint8, torch.int64, torch.uint8)],
+        return self._device_records(
+            cap, 4 * nq + 16, dev, (torch.int64, torch.uint8, torch.int64, torch.uint8),
             lambda c, out, total: lib().sufr_hip_fm_approx_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), nq,
-                                                                  max_mismatches, flags, c, *[t.data_ptr() for t in out], C.byref(total)),
-            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
-        self.ctx.synchronize()
-        return out
+                                                                  max_mismatches, flags, c, *[t.data_ptr() for t in out], C.byref(total)))
 
     def approx(self, queries: Sequence, max_mismatches: int = 2, both_strands: bool = False) -> List[List[ApproxHit]]:
         """The k-mismatch occurrences of every query (FmIndex.approx), found on the device."""
@@ -1183,24 +1245,13 @@ class DeviceFmIndex:
 
     def locate(self, queries: Sequence, max_hits: int = 0) -> List[np.ndarray]:
         """Text positions of every query's matches in rank order (unsigned arrays of the index's width)."""
-        o, p = self.locate_device(*self.search_device(*self._packed(queries)), max_hits)
-        o = o.cpu().numpy(); p = p.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
-        return [p[o[i]:o[i + 1]] for i in range(len(queries))]
+        return self._locate(len(queries), *self.search_device(*self._packed(queries)), max_hits)
 
     # -- matching statistics and SMEMs on a pair of indexes (include/sufr_fm_match.h) ---------------------------------------
     def matching_stats_device(self, qbytes, offsets, rev: "DeviceFmIndex", wait: bool = True):
         """DeviceIndex.matching_statistics_device from this index and `rev`, the index of the reversed text, alone: an int32
         tensor (u32 values) indexed like the bytes.  wait=False: call ctx.synchronize() before reading it."""
-        import torch
-        torch.cuda.current_stream(qbytes.device).synchronize()
-        nq = offsets.numel() - 1
-        qbytes = DeviceIndex._device_bytes(qbytes)
-        ms = torch.zeros(max(int(offsets[-1]) if nq >= 0 and offsets.numel() else 0, 1), dtype=torch.int32, device=qbytes.device)
-        self.ctx.check(lib().sufr_hip_fm_matching_stats_device(self.ctx.handle, self._h, rev._h, qbytes.data_ptr(), offsets.data_ptr(),
-                                                               max(nq, 0), ms.data_ptr()))
-        if wait:
-            self.ctx.synchronize()
-        return ms
+        return self._matching_stats_device(lib().sufr_hip_fm_matching_stats_device, (self._h, rev._h), qbytes, offsets, wait)
 
     def matching_stats(self, queries: Sequence, rev: "DeviceFmIndex") -> List[np.ndarray]:
         """ms[j] per query (uint32 arrays), computed on the device."""
@@ -1212,38 +1263,15 @@ class DeviceFmIndex:
         """DeviceIndex.smems_device from the pair alone: (query int64, query_offset int32, length int32, rank_lo int64, rank_hi
         int64) tensors in (query, offset) order, complete on return; `last_ms` keeps the statistics.  With a `cap` too small
         the SufrHipError (code -5) carries the total in `.total`; without one the outputs are sized to fit."""
-        import torch
-        torch.cuda.current_stream(qbytes.device).synchronize()
-        nq = offsets.numel() - 1
-        dev = qbytes.device
-        qbytes = DeviceIndex._device_bytes(qbytes)
-        nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
-        ms = torch.empty(max(int(offsets[-1]) if nq > 0 else 0, 1), dtype=torch.int32, device=dev)
-        out = _sized_to_fit(
-            cap, nbytes // 8 + 16, lambda c: [torch.empty(c, dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.int32, torch.int64, torch.int64)],
-            lambda c, out, total: lib().sufr_hip_fm_smems_device(self.ctx.handle, self._h, rev._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
-                                                                 min_len, ms.data_ptr(), c, *[t.data_ptr() for t in out], C.byref(total)),
-            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
-        self.ctx.synchronize()
-        self.last_ms = ms
-        return out
+        return self._smems_device(lib().sufr_hip_fm_smems_device, (self._h, rev._h), qbytes, offsets, min_len, cap)
 
     def smems(self, queries: Sequence, rev: "DeviceFmIndex", min_len: int = 20, max_hits: int = 0) -> List[List[SmemHit]]:
         """The SMEMs of every query with their rank ranges and up to `max_hits` positions (0: all), as DeviceIndex.smems
         returns them (sufr_hip_fm_smems_device + sufr_hip_fm_locate_batch_device)."""
-        qb, off = self._packed(queries)
-        qi, qo, ln, lo, hi = self.smems_device(qb, off, rev, min_len)
-        po, pos = self.locate_device(lo, hi, max_hits)
-        po = po.cpu().numpy()
-        pos = pos.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
-        qi, qo, ln, lo, hi = (t.cpu().numpy() for t in (qi, qo, ln, lo, hi))
-        out: List[List[SmemHit]] = [[] for _ in queries]
-        for t in range(len(qi)):
-            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[po[t]:po[t + 1]].copy()))
-        return out
+        return self._smems(len(queries), self.smems_device(*self._packed(queries), rev, min_len), max_hits)
 
 
-class DeviceIndex:
+class DeviceIndex(_DeviceBatch):
     """Text + suffix array resident in HBM, searched a batch at a time (include/sufr_query.h, device section).
 
     DeviceIndex.load(ctx, sufr_file)                              copies an open file to the GPU
@@ -1304,8 +1332,7 @@ class DeviceIndex:
         nq = len(offsets) - 1
         lo = np.zeros(nq, dtype=np.uint64)
         hi = np.zeros(nq, dtype=np.uint64)
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         self.ctx.check(lib().sufr_hip_search_batch(self.ctx.handle, self._h, qbytes.ctypes.data, offsets.ctypes.data, nq,
                                                   int(max_query_len is not None), max_query_len or 0,
                                                   lo.ctypes.data, hi.ctypes.data))
@@ -1315,123 +1342,44 @@ class DeviceIndex:
         """torch CUDA tensors in (uint8 bytes, int64 offsets), torch CUDA tensors out.  The launch goes to the context's
         stream, which is not ordered against torch's: the producer of the inputs is synchronised first, and with `wait`
         the answers are complete on return (wait=False: call ctx.synchronize() before reading them)."""
-        import torch
-        torch.cuda.current_stream(qbytes.device).synchronize()
-        nq = offsets.numel() - 1
-        lo = torch.empty(nq, dtype=torch.int64, device=qbytes.device)
-        hi = torch.empty(nq, dtype=torch.int64, device=qbytes.device)
-        self.ctx.check(lib().sufr_hip_search_batch_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), nq,
-                                                         int(max_query_len is not None), max_query_len or 0,
-                                                         lo.data_ptr(), hi.data_ptr()))
-        if wait:
-            self.ctx.synchronize()
-        return lo, hi
+        return self._search_device(lib().sufr_hip_search_batch_device, qbytes, offsets, wait, int(max_query_len is not None), max_query_len or 0)
 
     def locate_device(self, lo, hi, max_hits: int = 0, capacity: Optional[int] = None):
         """Positions behind rank ranges that are on the device (torch int64 tensors from search_device): returns
         (offsets int64[nq + 1], positions); query i owns positions[offsets[i]:offsets[i + 1]], in rank order, at most max_hits
         of them (0: all).  The positions have the index's width: int32 holding u32 values, or int64 for a 64-bit index."""
-        import torch
-        nq = lo.numel()
-        off = torch.empty(nq + 1, dtype=torch.int64, device=lo.device)
-        total = C.c_uint64(0)
-        torch.cuda.current_stream(lo.device).synchronize()
-        if capacity is None:                                   # size the output from the counts
-            cnt = hi - lo
-            capacity = int((cnt.clamp(max=max_hits) if max_hits else cnt).sum())
-        pos = torch.empty(max(capacity, 1), dtype=torch.int64 if self.index_width == 8 else torch.int32,
-                          device=lo.device)
-        self.ctx.check(lib().sufr_hip_locate_batch_device(self.ctx.handle, self._h, lo.data_ptr(), hi.data_ptr(), nq, max_hits,
-                                                         off.data_ptr(), pos.data_ptr(), capacity, C.byref(total)))
-        self.ctx.synchronize()
-        return off, pos[:total.value]
+        return self._locate_device(lib().sufr_hip_locate_batch_device, lo, hi, max_hits, capacity)
 
     def locate(self, queries: Sequence, max_query_len: Optional[int] = None, max_hits: int = 0) -> List[np.ndarray]:
         """Text positions of every query's matches in rank order (unsigned arrays of the index's width), searched and gathered
         on the device."""
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        lo, hi = self.search_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_query_len)
-        o, p = self.locate_device(lo, hi, max_hits)
-        o = o.cpu().numpy(); p = p.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
-        return [p[o[i]:o[i + 1]] for i in range(len(queries))]
+        return self._locate(len(queries), *self.search_device(*self._packed(queries), max_query_len), max_hits)
 
     def count(self, queries: Sequence, max_query_len: Optional[int] = None) -> List[CountResult]:
-        lo, hi = self.search(queries, max_query_len)
-        return [CountResult(i, q if isinstance(q, str) else bytes(q).decode("latin-1"), int(hi[i] - lo[i]))
-                for i, q in enumerate(queries)]
+        return _counts(queries, *self.search(queries, max_query_len))
 
     # -- matching statistics and SMEMs (include/sufr_match.h) ---------------------------------------------------------
-    @staticmethod
-    def _device_bytes(qbytes):
-        """The query bytes as the library takes them: a batch of empty queries still needs a device address."""
-        import torch
-        return qbytes if qbytes.numel() else torch.zeros(1, dtype=torch.uint8, device=qbytes.device)
-
-    def _device_records(self, cap, guess, device, dtypes, call):
-        """_sized_to_fit for torch outputs on `device`; the error text is the context's, the records are complete on return."""
-        import torch
-        out = _sized_to_fit(cap, guess, lambda c: [torch.empty(c, dtype=d, device=device) for d in dtypes], call,
-                            lambda rc, total, c: SufrHipError(rc, lib().sufr_hip_last_error(self.ctx.handle).decode()))
-        self.ctx.synchronize()
-        return out
-
     def matching_statistics_device(self, qbytes, offsets, wait: bool = True):
         """ms of a packed batch of torch CUDA tensors (uint8 bytes, int64 offsets): an int32 tensor (u32 values) indexed like
         the bytes.  wait=False: call ctx.synchronize() before reading it."""
-        import torch
-        torch.cuda.current_stream(qbytes.device).synchronize()
-        nq = offsets.numel() - 1
-        qbytes = self._device_bytes(qbytes)
-        ms = torch.zeros(max(int(offsets[-1]) if nq >= 0 and offsets.numel() else 0, 1), dtype=torch.int32, device=qbytes.device)
-        self.ctx.check(lib().sufr_hip_matching_stats_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(),
-                                                            max(nq, 0), ms.data_ptr()))
-        if wait:
-            self.ctx.synchronize()
-        return ms
+        return self._matching_stats_device(lib().sufr_hip_matching_stats_device, (self._h,), qbytes, offsets, wait)
 
     def matching_statistics(self, queries: Sequence) -> List[np.ndarray]:
         """ms[j] per query (uint32 arrays), computed on the device."""
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        ms = self.matching_statistics_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev))
-        return _split(ms.cpu().numpy().view(np.uint32), off)
+        qb, off = self._packed(queries)
+        ms = self.matching_statistics_device(qb, off)
+        return _split(ms.cpu().numpy().view(np.uint32), off.cpu().numpy().astype(np.uint64))
 
     def smems_device(self, qbytes, offsets, min_len: int = 20, cap: Optional[int] = None):
         """SMEMs of a packed batch of torch CUDA tensors: (query int64, query_offset int32, length int32, rank_lo int64,
         rank_hi int64) tensors in (query, offset) order, complete on return.  With a `cap` too small the SufrHipError
         (code -5) carries the total in `.total`; without one the outputs are sized to fit."""
-        import torch
-        torch.cuda.current_stream(qbytes.device).synchronize()
-        nq = offsets.numel() - 1
-        dev = qbytes.device
-        qbytes = self._device_bytes(qbytes)
-        nbytes = int(offsets[-1] - offsets[0]) if nq > 0 else 0
-        ms = torch.empty(max(int(offsets[-1]) if nq > 0 else 0, 1), dtype=torch.int32, device=dev)
-        out = self._device_records(
-            cap, nbytes // 8 + 16, dev, (torch.int64, torch.int32, torch.int32, torch.int64, torch.int64),
-            lambda c, out, total: lib().sufr_hip_smems_device(self.ctx.handle, self._h, qbytes.data_ptr(), offsets.data_ptr(), max(nq, 0),
-                                                              min_len, ms.data_ptr(), c, *[t.data_ptr() for t in out], C.byref(total)))
-        self.last_ms = ms
-        return out
+        return self._smems_device(lib().sufr_hip_smems_device, (self._h,), qbytes, offsets, min_len, cap)
 
     def smems(self, queries: Sequence, min_len: int = 20, max_hits: int = 0) -> List[List[SmemHit]]:
         """The SMEMs of every query with their rank ranges and up to `max_hits` positions (0: all), searched and gathered
         on the device (sufr_hip_smems_device + sufr_hip_locate_batch_device)."""
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        qi, qo, ln, lo, hi = self.smems_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), min_len)
-        po, pos = self.locate_device(lo, hi, max_hits)
-        po = po.cpu().numpy()
-        pos = pos.cpu().numpy().view(np.uint64 if self.index_width == 8 else np.uint32)
-        qi, qo, ln, lo, hi = (t.cpu().numpy() for t in (qi, qo, ln, lo, hi))
-        out: List[List[SmemHit]] = [[] for _ in queries]
-        for t in range(len(qi)):
-            out[int(qi[t])].append(SmemHit(int(qi[t]), int(qo[t]), int(ln[t]), int(lo[t]), int(hi[t]), pos[po[t]:po[t + 1]].copy()))
-        return out
+        return self._smems(len(queries), self.smems_device(*self._packed(queries), min_len), max_hits)
 
     # -- k-mer spectra, occurrence maps, unique lengths (include/sufr_kmer.h) ------------------------------------------
     def _lcp_inputs(self, lcp, seq_starts):
@@ -1613,12 +1561,8 @@ class DeviceIndex:
 
     def mems(self, queries: Sequence, min_len: int = 20, max_occ: int = 0, both_strands: bool = False) -> List[List[MemHit]]:
         """The MEMs of every query (SufrFile.mems), found on the device."""
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        recs = self.mems_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), min_len, max_occ,
-                                both_strands)
-        return _mem_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
+        recs = self.mems_device(*self._packed(queries), min_len, max_occ, both_strands)
+        return _mem_hits(len(queries), [t.cpu().numpy() for t in recs])
 
     # -- k-mismatch search (include/sufr_approx.h) -------------------------------------------------------------------
     def approx_device(self, qbytes, offsets, max_mismatches: int = 2, max_occ: int = 0, both_strands: bool = False,
@@ -1641,12 +1585,8 @@ class DeviceIndex:
 
     def approx(self, queries: Sequence, max_mismatches: int = 2, max_occ: int = 0, both_strands: bool = False) -> List[List[ApproxHit]]:
         """The k-mismatch occurrences of every query (SufrFile.approx), found on the device."""
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        recs = self.approx_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_mismatches,
-                                  max_occ, both_strands)
-        return _approx_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
+        recs = self.approx_device(*self._packed(queries), max_mismatches, max_occ, both_strands)
+        return _approx_hits(len(queries), [t.cpu().numpy() for t in recs])
 
     # -- k-difference search (include/sufr_edit.h) -------------------------------------------------------------------
     def edit_device(self, qbytes, offsets, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False,
@@ -1669,12 +1609,8 @@ class DeviceIndex:
     def edit(self, queries: Sequence, max_edits: int = 2, max_occ: int = 0, both_strands: bool = False,
              local_minima: bool = False) -> List[List[EditHit]]:
         """The k-difference ends of every query (SufrFile.edit), found on the device."""
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        recs = self.edit_device(torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev), max_edits, max_occ,
-                                both_strands, local_minima)
-        return _edit_hits(len(off) - 1, [t.cpu().numpy() for t in recs])
+        recs = self.edit_device(*self._packed(queries), max_edits, max_occ, both_strands, local_minima)
+        return _edit_hits(len(queries), [t.cpu().numpy() for t in recs])
 
     # -- alignment traceback (include/sufr_align.h) -------------------------------------------------------------------
     def edit_trace_device(self, qbytes, offsets, query, strand, end, edits, cap: Optional[int] = None):
@@ -1698,8 +1634,7 @@ class DeviceIndex:
 
     def edit_trace(self, qbytes: np.ndarray, offsets: np.ndarray, query, strand, end, edits, cap: Optional[int] = None):
         """`SufrFile.edit_trace_arrays` on host arrays through sufr_hip_edit_trace (staged, traced on the device, copied back)."""
-        qbytes = np.ascontiguousarray(qbytes, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        qbytes, offsets = _packed_arrays(qbytes, offsets)
         recs = [np.ascontiguousarray(a, dtype=d) for a, d in zip((query, strand, end, edits), _APPROX_DTYPES)]
         nq, nr = len(offsets) - 1, len(recs[0])
         start = np.zeros(max(nr, 1), dtype=np.uint64)
@@ -1716,12 +1651,9 @@ class DeviceIndex:
               local_minima: bool = False) -> List[List[AlignHit]]:
         """The hits of `edit` with the start and the CIGAR string of every one (SufrFile.align), searched and traced on the
         device."""
-        import torch
-        qb, off = pack_queries(queries)
-        dev = torch.device("cuda", self.ctx.device)
-        dq, do = torch.from_numpy(qb).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev)
+        dq, do = self._packed(queries)
         recs = self.edit_device(dq, do, max_edits, max_occ, both_strands, local_minima)
         recs = tuple(t.contiguous() for t in recs)
         st, co, cg = self.edit_trace_device(dq, do, *recs)
-        return _align_hits(len(off) - 1, [t.cpu().numpy() for t in recs],
+        return _align_hits(len(queries), [t.cpu().numpy() for t in recs],
                            (st.cpu().numpy(), co.cpu().numpy(), cg.cpu().numpy().view(np.uint32)))

@@ -313,3 +313,12 @@ def test_cli_fm_on_the_device_prints_the_host_lines():
     assert run("fm", "--device", 0, path, *queries).stdout == run("count", path, *queries).stdout != ""
     want, got = run("locate", path, *queries), run("fm", "--locate", "--device", 0, path, *queries)
     assert got.stdout == want.stdout != "" and got.stderr == want.stderr
+
+
+def test_cli_fm_locate_with_max_hits_on_the_device_prints_the_host_lines():
+    """the device locate that --locate and --smems share, cut at --max-hits"""
+    from test_match_host import run
+    path = EXP / "2ns.sufr"
+    for flags in (("--max-hits", 2), ("--max-hits", 2, "-a", "-s", 3)):
+        want, got = run("fm", "--locate", *flags, path, "N", "ACGT", "TTT"), run("fm", "--locate", *flags, "--device", 0, path, "N", "ACGT", "TTT")
+        assert got.stdout == want.stdout != "" and got.stderr == want.stderr

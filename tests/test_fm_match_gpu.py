@@ -342,3 +342,41 @@ def test_cli_on_the_device_prints_the_host_lines(oracle, tmp_path):
     want = run("match", "-k", 5, src, *queries).stdout
     assert want and run("fm", src, "--smems", "--reverse", rev, "-k", 5, "--device", 0, *queries).stdout == want
     assert run("fm", "--index", fwd_fm, "--smems", "--reverse", rev_fm, "-k", 5, "--device", 0, *queries).stdout == want
+
+
+def test_cli_smems_with_max_hits_on_the_device_prints_the_host_lines(oracle, tmp_path):
+    """the positions of --smems come through the device locate of --locate, cut at --max-hits"""
+    from test_fm_match_host import cli_files, cli_queries
+    from test_match_host import run
+    src, rev, fwd_fm, rev_fm = cli_files(oracle, tmp_path, DNA)
+    queries = cli_queries(src, DNA)
+    for args in ((src, "--smems", "--reverse", rev), ("--index", fwd_fm, "--smems", "--reverse", rev_fm, "-a")):
+        want = run("fm", *args, "-k", 5, "--max-hits", 1, *queries).stdout
+        assert want and run("fm", *args, "-k", 5, "--max-hits", 1, "--device", 0, *queries).stdout == want
+
+
+def test_one_batch_through_both_device_classes(ctx, tmp_path):
+    """DeviceIndex and DeviceFmIndex answer through one batch path: the same queries through both give the same counts,
+    positions (cut at max_hits) and SMEMs, an empty query and one that does not occur among them"""
+    from test_fm_match_host import planted_pair
+    rng = np.random.default_rng(5)
+    text = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 3001)].copy()
+    text[-1] = ord("$")
+    p = planted_pair(tmp_path, text, "both")
+    qs = [p.X[a:a + n] for a, n in ((0, 40), (17, 3), (1500, 25), (2990, 10), (64, 1), (700, 60), (2000, 12), (333, 7))]
+    qs += [b"", b"ACGTN", p.X[100:130] + p.X[2500:2530], p.X[5:25] + b"N" + p.X[900:920]]      # (no end byte: the pair matches in T[:-1])
+    ix, rix = DeviceIndex.load(ctx, p.f), DeviceIndex.load(ctx, p.g)
+    fm, rev = ix.fm_device(7), rix.fm_device(0)
+    rix.close()
+    counts = p.f.count(qs)                                            # the host file is the reference of both
+    assert fm.count(qs) == ix.count(qs) == counts and counts[8].count == text.size and sum(c.count == 0 for c in counts) >= 2
+    sa, (lo, hi) = np.asarray(p.f.suffix_array), p.f.search_batch(qs)
+    for i, (a, b) in enumerate(zip(fm.locate(qs, max_hits=2), ix.locate(qs, max_hits=2))):
+        want = sa[int(lo[i]):int(lo[i]) + min(int(hi[i] - lo[i]), 2)]
+        assert a.dtype == b.dtype == want.dtype and np.array_equal(a, want) and np.array_equal(b, want), i
+    for min_len in (1, 20):
+        want = p.f.smems(qs, min_len, max_hits=1)
+        assert repr(fm.smems(qs, rev, min_len, max_hits=1)) == repr(ix.smems(qs, min_len, max_hits=1)) == repr(want), min_len
+        assert len(want) == len(qs) and any(want) and all(h.positions.size == 1 for hits in want for h in hits)
+    for x in (fm, rev, ix):
+        x.close()

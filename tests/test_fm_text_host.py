@@ -529,3 +529,50 @@ def _saved(fm, tmp_path) -> bytes:
     p = tmp_path / "py.fm"
     fm.save(p)
     return p.read_bytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sufr fm: one session behind count, --locate, --mismatches, --index, --save, --extract and --smems
+# ---------------------------------------------------------------------------------------------------------------------
+NS, NS_QUERIES = EXP / "2ns.sufr", ["AC", "GT", "N", "TTT"]
+
+
+def test_cli_locate_at_sample_zero_prints_the_lines_of_locate():
+    """--locate alone builds at sample 1 when told -s 0"""
+    want, got = run("locate", NS, *NS_QUERIES), run("fm", "--locate", "-s", 0, NS, *NS_QUERIES)
+    assert got.stdout == want.stdout != "" and got.stderr == want.stderr
+
+
+def test_cli_index_without_samples_counts_and_refuses_the_rest(tmp_path):
+    bare = tmp_path / "bare.fm"
+    run("fm", NS, "--save", bare, "-s", 0)
+    assert run("fm", "--index", bare, *NS_QUERIES).stdout == run("count", NS, *NS_QUERIES).stdout != ""
+    for args in (("--locate",), ("-d", 1), ("--extract",)):
+        r = run("fm", "--index", bare, *args, "ACGT", check=False)
+        assert r.returncode == 1 and r.stdout == "" and len(r.stderr.splitlines()) == 1 and "counts only" in r.stderr, (args, r.stderr)
+
+
+def test_cli_save_alone_writes_a_file_that_index_reads(tmp_path):
+    idx = tmp_path / "x.fm"
+    r = run("fm", NS, "--save", idx, check=False)
+    assert r.returncode == 0 and r.stdout == "" and r.stderr == ""
+    want, got = run("locate", NS, *NS_QUERIES), run("fm", "--index", idx, "--locate", *NS_QUERIES)
+    assert got.stdout == want.stdout != "" and got.stderr == want.stderr
+
+
+def test_cli_mismatches_from_an_index_file_prints_the_lines_of_the_sufr(tmp_path):
+    idx = tmp_path / "x.fm"
+    run("fm", NS, "--save", idx)
+    for flags in ((), ("-b", "-a")):
+        want, got = run("fm", "-d", 1, *flags, NS, "ACGA", "NNNT", "TTTTTT"), run("fm", "-d", 1, *flags, "--index", idx, "ACGA", "NNNT", "TTTTTT")
+        assert got.stdout == want.stdout != "" and got.stderr == want.stderr
+
+
+def test_cli_write_reverse_and_smems_in_one_run(oracle, tmp_path):
+    from test_fm_match_host import cli_files, cli_queries
+    name = "long_dna_sequence_allow_ambiguity.sufr"
+    src, rev, _, _ = cli_files(oracle, tmp_path, name)
+    queries, again = cli_queries(src, name), tmp_path / "again.fa"
+    got = run("fm", src, "--write-reverse", again, "--smems", "--reverse", rev, "-k", 5, *queries)
+    assert again.read_bytes() == (tmp_path / "rev.fa").read_bytes() != b""
+    assert got.stdout == run("match", "-k", 5, src, *queries).stdout != ""
